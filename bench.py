@@ -11,10 +11,11 @@ Workload (default): BASELINE config 3 -- 100 M paired-end reads, 8 haplotypes x 
 transcripts (~3.3 G BAM records, ~40 GB of tuples), synthetic (alntools_amd/synth.py, seed
 20260101), read-sharded contiguously over the N GPUs (strong scaling: total work fixed).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c1|tiny]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c1|tiny] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0; ``ms_per_step`` is the wall time of one of the K timed steps.  The inputs are a pure function of
+the workload's seed, so ``--dump-outputs`` of two builds can be compared file for file.
 """
 from __future__ import annotations
 
@@ -44,6 +45,40 @@ WORKLOADS = {
     "dip": (200_000_000, 40_000, 2, False, "diploid single-end reads: 2 hap x 40k transcripts, ~4 records per read (short reads: several passes per tile)"),
 }
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8.0 TB/s spec, ~6.3 TB/s achievable)
+DUMP_BYTES = 64_000_000    # --dump-outputs: the .npy files of one run together stay under this
+DUMP_SEED = 20260101
+
+
+def step_outputs(h, multisample, n_cells, min_count):
+    """What a caller of the timed path receives from the handle ``h`` that holds the step's result, as name -> 1-D integer array:
+    CSR A and N (``EcBuilder.export``; after the cell filter for multisample, ``EcBuilder.ms_filter``) and finalize's counters."""
+    import numpy as np
+    if multisample:
+        out = h.ms_filter(n_cells, min_count)
+        out["n_cells_seen"] = np.array([out["n_cells_seen"]])
+    else:
+        out = h.export()
+    out["sizes"] = np.array(list(h.sizes.values()))      # (in the field order of ecb.Sizes)
+    return out
+
+
+def dump_outputs(path, arrays, budget=DUMP_BYTES, seed=DUMP_SEED):
+    """``arrays`` as ``path/<name>.npy`` in float64 (exact for every 32-bit integer).  The budget of ``budget`` bytes is split
+    evenly over the arrays, smallest first, so that an array under its share is written whole and the rest go to the larger ones.
+    An array over its share is cut to the values at sorted positions drawn without replacement by a generator seeded from ``seed``
+    and the array's name and length: the same positions in every run whose output has that length."""
+    import zlib
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    room = (budget - 4096 * len(arrays)) // 8          # (4 KiB per file for the .npy header, with room to spare)
+    for left, (name, a) in zip(range(len(arrays), 0, -1), sorted(arrays.items(), key=lambda kv: (np.size(kv[1]), kv[0]))):
+        a = np.asarray(a).ravel()
+        keep = min(a.size, room // left)
+        room -= keep
+        if keep < a.size:
+            rng = np.random.default_rng([seed, zlib.crc32(name.encode()), a.size])
+            a = a[np.sort(rng.choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64))
 
 
 def workload_spec(name):
@@ -447,7 +482,11 @@ def main():
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary workloads (c2, c3r, dip) behind a default config-3 run")
     ap.add_argument("--secondary-steps", type=int, default=5)
     ap.add_argument("--e2e-slice-reads", type=int, default=100_000, help="reads of the config-2 slice converted from a real BAM file")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (CSR A and N, counters) "
+                                                          "as DIR/<name>.npy, float64, at most 64 MB in all (a seeded sample of larger outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # (before anything can touch the GPU runtime: the host driver of this pool only supports dmabuf IPC, and the variable is read
     #  when the runtime starts, not when the process group does)
@@ -630,6 +669,8 @@ def main():
     k_ms, k_launches, _ = b.profile_read()
     kernel_name = b.profile_kernel()              # (what libecb launched: k_stream.inc is compiled more than once, the library picks per batch)
     b.profile(False)
+    if args.dump_outputs and rank == 0:           # (before anything below steps the handle again; across GPUs the root's handle holds the result)
+        dump_outputs(args.dump_outputs, step_outputs(root_eng.b if use_dist else b, multisample, n_cells, min_count))
     # config 3 names bam2emase: the .h5 holds one CSC matrix per haplotype, so its device work is the step plus the transposition
     # of the finished CSR (ecb_csr_to_hapcsc_device).  Timed on its own, outside the K steps the headline is measured on.
     emase_ms = None

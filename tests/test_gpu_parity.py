@@ -1430,3 +1430,27 @@ def test_long_keys_through_export_merge_and_adopt():
     _check(root.b.export(), s, exp)
     assert int(np.diff(exp["indptr"]).max()) == 900 and s["n_reads"] == base
     root.b.close()
+
+
+def test_bench_dump_outputs_are_what_the_timed_steps_computed(tmp_path):
+    """``bench.py --workload c1 --dump-outputs DIR`` in a process of its own: the files hold the last timed step's CSR A, counts and
+    counters, equal to the oracle's on the same seeded tuples; the result line reports the steps asked for and their time."""
+    import subprocess
+    import sys
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "c1", "--steps", "3", "--warmup", "1",
+                        "--no-cpu-baseline", "--dump-outputs", str(d)], cwd=root, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    spec = synth.SynthSpec(10000, 1000, 2)
+    t = synth.generate(spec, 0, spec.n_reads)
+    exp = _expect(t, spec.n_loci, spec.n_haps)
+    got = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+    assert all(a.dtype == np.float64 for a in got.values())
+    for name, key in (("indptrA", "indptr"), ("indicesA", "indices"), ("dataA", "data"), ("dataN", "count")):
+        assert np.array_equal(got[name], np.asarray(exp[key], dtype=np.float64)), name
+    n_ecs, nnz_a, n_samples, nnz_n, n_all, n_valid, n_reads = got["sizes"]
+    assert (n_ecs, nnz_a, n_all, n_valid, n_reads) == (len(exp["count"]), len(exp["indices"]), exp["n_all"], exp["n_valid"],
+                                                       int(np.sum(exp["count"])))

@@ -491,3 +491,34 @@ def test_rank_zero_deals_a_decoded_file_out_in_contiguous_read_ranges():
             assert np.array_equal(np.concatenate([b[i] for b in back]), exp), (world, batch, i)
         if batch < n // world:                                                   # (progress moves while the file is read: more than one rank gets reads)
             assert sum(1 for r in range(world) if got[r]) >= 2
+
+
+def test_bench_dump_outputs_stays_in_budget_and_samples_reproducibly(tmp_path):
+    """``bench.py --dump-outputs``: float64 files under the byte budget; arrays under their share written whole, larger ones as
+    the values at the same seeded positions in every run (so two builds can be compared file for file)."""
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
+    import bench
+    rng = np.random.default_rng(7)
+    arrays = {"indptrA": np.arange(300_001, dtype=np.int32), "indicesA": rng.integers(0, 1 << 20, 900_000).astype(np.int32),
+              "dataN": rng.integers(1, 1 << 31, 300_000).astype(np.int64).astype(np.int32), "sizes": np.array([3, 900_000, 1])}
+    budget = 1 << 20
+    runs = []
+    for k in range(2):
+        d = tmp_path / str(k)
+        bench.dump_outputs(str(d), arrays, budget=budget)
+        assert sorted(os.listdir(d)) == sorted(n + ".npy" for n in arrays)
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= budget
+        runs.append({n: np.load(d / (n + ".npy")) for n in arrays})
+    for n, a in arrays.items():
+        got = runs[0][n]
+        assert got.dtype == np.float64 and np.array_equal(got, runs[1][n]), n
+        if n == "sizes":
+            assert np.array_equal(got, a)
+        else:
+            assert 0 < len(got) < len(a) and np.all(np.isin(got, a)), n
+    assert np.all(np.diff(runs[0]["indptrA"]) > 0)                          # positions kept in order
+    whole = tmp_path / "whole"
+    bench.dump_outputs(str(whole), arrays)                                   # the default budget holds all of it
+    for n, a in arrays.items():
+        assert np.array_equal(np.load(whole / (n + ".npy")), a.astype(np.float64)), n
