@@ -122,3 +122,82 @@ def emase2ec(emase_file, ec_file, **converters):
     (``emase_h5.device_csr``; tests may pass ``csr=`` their checker)."""
     from . import emase_h5
     ecsave2(ec_file, emase_h5.load(emase_file, **converters))
+
+
+def load_groups(m, grp_filename):
+    """Group file -> (group names, per group the list of locus ids) -- ``AlignmentPropertyMatrix.load_groups``
+    (``AlignmentPropertyMatrix.py:176-191``): every line is ``rstrip().split("\\t")`` into ``gene, tx1, tx2, ...``, no line is
+    skipped, and a transcript that is not a target of the ``.bin`` is a KeyError."""
+    lid = dict(zip(m.lname, range(m.num_loci)))                       # (a duplicated target name: the last one counts, as dict(zip()))
+    gname, groups = [], []
+    with open(grp_filename) as fh:
+        for curline in fh:
+            item = curline.rstrip().split("\t")
+            gname.append(item[0])
+            groups.append([lid[t] for t in item[1:]])
+    return gname, groups
+
+
+def genotype_mask(m, gt_filename, gname, groups):
+    """Genotype file -> ``mask u32[T]`` (bit h = haplotype h allowed at that locus) -- ``AlignmentPropertyMatrix.apply_genotypes``
+    (``AlignmentPropertyMatrix.py:483-505``): the leading lines that start with ``#`` are skipped; every later line gives ``gene,
+    genotype = item[:2]``; each character of the genotype is a haplotype name (looked up first), the gene is a group name (the last
+    group line of that name counts); every transcript of the gene gets the genotype's haplotypes.  Transcripts of no listed gene get 0."""
+    from itertools import dropwhile
+    hid = dict(zip(m.hname, range(m.num_haplotypes)))
+    gid = dict(zip(gname, range(len(gname))))
+    mask = np.zeros(m.num_loci, dtype=np.uint32)
+    with open(gt_filename) as fh:
+        for curline in dropwhile(lambda s: s.startswith('#'), fh):
+            item = curline.rstrip().split("\t")
+            g, gt = item[:2]
+            hids = [hid[c] for c in gt]
+            tids = groups[gid[g]]
+            if not hids or not tids:                                  # (np.meshgrid of an empty float array indexes gtmask)
+                raise IndexError("arrays used as indices must be of integer (or boolean) type")
+            bits = 0
+            for h in hids:
+                bits |= 1 << h
+            mask[np.asarray(tids, dtype=np.int64)] |= np.uint32(bits)
+    return mask
+
+
+def apply_genotypes(ec_filename, gt_filename, grp_filename, out_filename, device=0):
+    """``alntools apply-genotypes`` (``bin_utils.py:1031-1051``): the ``.bin``'s alignments that the genotypes do not allow are
+    removed -- the mask is parsed here, applied to CSR A on the GPU (``ecb.apply_mask``); rows that lose every alignment stay, as
+    empty rows.  N: a multisample file's is written back as it was read; a single sample's goes through the reference's dense count
+    vector (``ecload`` / ``ecsave2``: duplicates added, zero counts dropped).  Any failure is logged as ``Error: ...`` and no file is
+    written, as in the reference (which returns normally then)."""
+    import time
+    from . import ecb, utils
+    LOG = utils.get_logger()
+    try:
+        start_time = time.time()
+        LOG.info("Loading {}...".format(ec_filename))
+        m = ecload(ec_filename)
+        gname, groups = load_groups(m, grp_filename)
+        LOG.info("Applying genotypes to the alignment profile...")
+        mask = genotype_mask(m, gt_filename, gname, groups)
+        m.indptrA, m.indicesA, m.dataA = ecb.apply_mask(m.indptrA, m.indicesA, m.dataA, mask, m.num_haplotypes, device=device)
+        converted = False
+        if m.num_samples == 1:
+            E = m.num_reads
+            lo, hi = int(m.indptrN[0]), int(m.indptrN[1])
+            count = np.bincount(m.indicesN[lo:hi], weights=m.dataN[lo:hi], minlength=E)
+            rows = np.flatnonzero(count)
+            m.indptrN = np.array([0, len(rows)], dtype=np.int32)
+            m.indicesN, m.dataN = rows.astype(np.int32), count[rows].astype(int).astype(np.int32)
+            converted = True
+        LOG.info("Saviing to {}...".format(out_filename))             # (sic: the reference's line)
+        LOG.info("Number of haplotypes: {:,}".format(m.num_haplotypes))
+        LOG.info("Number of reference targets: {:,}".format(m.num_loci))
+        LOG.info("Number of samples: {:,}".format(m.num_samples))
+        LOG.info("Saving alignment incidence matrix...")
+        LOG.info("Saving EC count matrix...")
+        if converted:
+            LOG.info('N matrix converted to csc_matrix.')
+        ecsave2(out_filename, m)
+        LOG.info("Saving completed")
+        LOG.info("{} created in total time: {}".format(out_filename, utils.format_time(start_time, time.time())))
+    except Exception as e:
+        LOG.error("Error: {}".format(str(e)))

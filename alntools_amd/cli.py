@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
 """Command line with the reference's hot-path sub-commands and options (``alntools/cli.py:43-113``):
-``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
+``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``, ``apply-genotypes``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
 from __future__ import annotations
 
 import os
@@ -82,6 +82,20 @@ def ec2emase(ec_file, emase_file, verbose):
 def emase2ec(emase_file, ec_file, verbose):
     utils.configure_logging(verbose)
     methods.emase2ec(emase_file, ec_file)
+
+
+@cli.command('apply-genotypes', options_metavar='<options>', short_help='remove alignments inconsistent to the genotypes')
+@click.argument('ec_file', metavar='ec_file', type=click.Path(exists=True, resolve_path=True, dir_okay=False))
+@click.argument('gt_file', metavar='gt_file', type=click.Path(resolve_path=True, dir_okay=False))
+@click.argument('grp_file', metavar='grp_file', type=click.Path(resolve_path=True, dir_okay=False))
+@click.argument('out_file', metavar='out_file', type=click.Path(resolve_path=True, dir_okay=False))
+@click.option('-v', '--verbose', count=True, help='enables verbose mode')
+def apply_genotypes(ec_file, gt_file, grp_file, out_file, verbose):
+    """
+    Apply genotypes (gt_file) to an alignment profile in a binary EC format (ec_file)
+    """
+    utils.configure_logging(verbose)
+    methods.apply_genotypes(ec_file, gt_file, grp_file, out_file)
 
 
 if __name__ == '__main__':

@@ -4412,6 +4412,180 @@ extern "C" int ecb_hapcsc_to_csr(int device, uint32_t n_ecs, uint32_t n_loci, ui
     return ECB_OK;
 }
 
+// ---- apply-genotypes: the haplotype bitmasks of a CSR A ANDed with a per-locus mask, what becomes zero dropped -----------------------------
+// (AlignmentPropertyMatrix.apply_genotypes + ecsave2, AlignmentPropertyMatrix.py:483-505, Sparse3DMatrix.py:295-299: every non-zero of every
+//  haplotype's matrix times gtmask[h, locus], zeros eliminated, rows kept.)  No loop over a row: three launches over the non-zeros -- a check
+// that writes the keep flags, the one-pass scan of the flags, a scatter -- so rows of 1 and of 900 loci cost the same per non-zero.  The mask is
+// a gather (T x 4 bytes: 320 KB at 80 k loci, L2-resident; it does not fit LDS).  Columns ascending within a row is checked without knowing
+// the rows: a "descent" is a non-zero whose column is not above the one before it; the CSR is ascending exactly when every descent sits at
+// the first non-zero of a row, i.e. when the descents the non-zeros count equal those the row pointers find at their rows' starts.
+namespace {
+constexpr int GM_ITEMS = 4;                            // non-zeros per thread (16-byte loads)
+constexpr u32 GM_SHARDS = 256, GM_SHARD_WORDS = 16;    // descent balance: 256 counters, one 128-byte line each
+enum : u32 { GM_ERR_PTR = 1u, GM_ERR_LOCUS = 2u, GM_ERR_BITS = 4u, GM_ERR_MASK = 8u };
+// words: [0] error bits, [3] kept non-zeros (the scan's total), then from word 16 the shards: shard s at word 16 + 16 s holds, summed over
+// the workgroups b with b % 256 == s, (descents among the non-zeros) - (descents at a row's first non-zero), mod 2^64.  The balance of the
+// whole CSR is 0 exactly when it is ascending.  (One counter for the whole grid took every wave's add: 1.3 ms at 13 M non-zeros.)
+// thread t: row pointer t (t <= E), mask word t (t < T), non-zeros [4t, 4t + 4) (< nnz)
+__global__ __launch_bounds__(TPB) void k_gm_check(const int* indptr, u32 n_ecs, const int* indices, const int* data, u64 nnz, const u32* mask,
+                                                  u32 n_loci, u32 n_haps, u32* keep, u64* words) {
+    const u64 t = blockIdx.x * (u64)TPB + threadIdx.x;
+    u32 err = 0, desc = 0, desc_row = 0;
+    if (t <= n_ecs) {
+        const long long a = indptr[t];
+        if (a < 0 || (u64)a > nnz || (t == 0 && a != 0) || (t == n_ecs && (u64)a != nnz)) err |= GM_ERR_PTR;
+        else if (t < n_ecs) {
+            const long long b = indptr[t + 1];
+            if (b < a || (u64)b > nnz) err |= GM_ERR_PTR;
+            else if (b > a && a > 0 && (u32)indices[a] <= (u32)indices[a - 1]) desc_row = 1;
+        }
+    }
+    if (t < n_loci && (mask[t] >> n_haps) != 0u) err |= GM_ERR_MASK;
+    const u64 i0 = t * GM_ITEMS;
+    if (i0 < nnz) {
+        u32 c[GM_ITEMS], d[GM_ITEMS], k[GM_ITEMS];
+        const bool whole = i0 + GM_ITEMS <= nnz;
+        if (whole && ((reinterpret_cast<uintptr_t>(indices) | reinterpret_cast<uintptr_t>(data) | reinterpret_cast<uintptr_t>(keep)) & 15u) == 0u) {
+            const uint4 q = reinterpret_cast<const uint4*>(indices + i0)[0], r = reinterpret_cast<const uint4*>(data + i0)[0];
+            c[0] = q.x; c[1] = q.y; c[2] = q.z; c[3] = q.w; d[0] = r.x; d[1] = r.y; d[2] = r.z; d[3] = r.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < GM_ITEMS; ++j) { c[j] = i0 + j < nnz ? (u32)indices[i0 + j] : 0u; d[j] = i0 + j < nnz ? (u32)data[i0 + j] : 0u; }
+        }
+        u32 prev = i0 ? (u32)indices[i0 - 1] : 0u;
+#pragma unroll
+        for (int j = 0; j < GM_ITEMS; ++j) {
+            k[j] = 0u;
+            if (i0 + j >= nnz) continue;
+            if (i0 + j > 0 && c[j] <= prev) ++desc;
+            prev = c[j];
+            if ((d[j] >> n_haps) != 0u) err |= GM_ERR_BITS;
+            if (c[j] >= n_loci) err |= GM_ERR_LOCUS;
+            else k[j] = (d[j] & mask[c[j]]) != 0u;
+        }
+        if (whole && (reinterpret_cast<uintptr_t>(keep) & 15u) == 0u) reinterpret_cast<uint4*>(keep + i0)[0] = make_uint4(k[0], k[1], k[2], k[3]);
+        else {
+#pragma unroll
+            for (int j = 0; j < GM_ITEMS; ++j) if (i0 + j < nnz) keep[i0 + j] = k[j];
+        }
+    }
+    // (every lane of the workgroup gets here: the wave sums and the barrier need them all)
+    if (err) atomicOr(reinterpret_cast<u32*>(words), err);
+    __shared__ long long s_bal[TPB / 64];
+    const long long bal = (long long)wave_sum(desc) - (long long)wave_sum(desc_row);
+    if ((threadIdx.x & 63u) == 0u) s_bal[threadIdx.x >> 6] = bal;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long b = 0;
+#pragma unroll
+        for (int w = 0; w < TPB / 64; ++w) b += s_bal[w];
+        if (b) atomicAdd(reinterpret_cast<unsigned long long*>(words + GM_SHARD_WORDS * (1 + blockIdx.x % GM_SHARDS)), (unsigned long long)b);
+    }
+}
+// excl = exclusive scan of keep, nnz + 1 values (excl[nnz] = kept): non-zero i is kept when excl[i + 1] != excl[i] and goes to excl[i];
+// row e starts at excl[indptr[e]].  Every write stays inside its array whatever the input held (a malformed CSR has been flagged and the
+// call reports it: the outputs are then not used).
+__global__ __launch_bounds__(TPB) void k_gm_scatter(const int* indptr, u32 n_ecs, const int* indices, const int* data, u64 nnz, const u32* mask,
+                                                    u32 n_loci, const u32* excl, int* out_indptr, int* out_indices, int* out_data) {
+    const u64 t = blockIdx.x * (u64)TPB + threadIdx.x;
+    if (t <= n_ecs) {
+        const long long a = indptr[t];
+        out_indptr[t] = a >= 0 && (u64)a <= nnz ? (int)excl[a] : 0;
+    }
+    const u64 i0 = t * GM_ITEMS;
+    if (i0 >= nnz) return;
+    u32 c[GM_ITEMS], d[GM_ITEMS], x[GM_ITEMS + 1];
+    if (i0 + GM_ITEMS <= nnz && ((reinterpret_cast<uintptr_t>(indices) | reinterpret_cast<uintptr_t>(data) | reinterpret_cast<uintptr_t>(excl)) & 15u) == 0u) {
+        const uint4 q = reinterpret_cast<const uint4*>(indices + i0)[0], r = reinterpret_cast<const uint4*>(data + i0)[0];
+        const uint4 s = reinterpret_cast<const uint4*>(excl + i0)[0];
+        c[0] = q.x; c[1] = q.y; c[2] = q.z; c[3] = q.w; d[0] = r.x; d[1] = r.y; d[2] = r.z; d[3] = r.w;
+        x[0] = s.x; x[1] = s.y; x[2] = s.z; x[3] = s.w; x[4] = excl[i0 + GM_ITEMS];
+    } else {
+#pragma unroll
+        for (int j = 0; j < GM_ITEMS; ++j) {
+            c[j] = i0 + j < nnz ? (u32)indices[i0 + j] : 0u; d[j] = i0 + j < nnz ? (u32)data[i0 + j] : 0u;
+            x[j] = i0 + j <= nnz ? excl[i0 + j] : 0u;
+        }
+        x[GM_ITEMS] = i0 + GM_ITEMS <= nnz ? excl[i0 + GM_ITEMS] : 0u;
+    }
+#pragma unroll
+    for (int j = 0; j < GM_ITEMS; ++j) {
+        if (i0 + j >= nnz || x[j + 1] == x[j] || c[j] >= n_loci) continue;
+        out_indices[x[j]] = (int)c[j];
+        out_data[x[j]] = (int)(d[j] & mask[c[j]]);
+    }
+}
+bool gm_overlap(const void* a, u64 na, const void* b, u64 nb) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return na && nb && x < y + nb && y < x + na;
+}
+}  // namespace
+
+extern "C" int ecb_apply_mask_device(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, uint64_t nnz, const void* d_indptr,
+                                     const void* d_indices, const void* d_data, const void* d_mask, void* d_out_indptr, void* d_out_indices,
+                                     void* d_out_data, uint64_t* kept) {
+    if (!d_indptr || !d_mask || !d_out_indptr || !kept || !n_loci || !n_haps || n_haps > 31) return fail(nullptr, ECB_ERR_ARG, "bad argument");
+    if (nnz && (!d_indices || !d_data || !d_out_indices || !d_out_data)) return fail(nullptr, ECB_ERR_ARG, "bad argument");
+    if (nnz >= (1ull << 31) || n_ecs >= (1u << 31) - 1u) return fail(nullptr, ECB_ERR_LIMIT, "the CSR exceeds the .bin format's int32 limits");
+    const u64 rowb = ((u64)n_ecs + 1) * 4, nzb = nnz * 4;
+    const void* ins[4] = {d_indptr, d_indices, d_data, d_mask};
+    const u64 inb[4] = {rowb, nzb, nzb, (u64)n_loci * 4};
+    for (int i = 0; i < 4; ++i)
+        if (gm_overlap(d_out_indptr, rowb, ins[i], inb[i]) || gm_overlap(d_out_indices, nzb, ins[i], inb[i]) || gm_overlap(d_out_data, nzb, ins[i], inb[i]))
+            return fail(nullptr, ECB_ERR_ARG, "an output overlaps an input");
+    if (gm_overlap(d_out_indptr, rowb, d_out_indices, nzb) || gm_overlap(d_out_indptr, rowb, d_out_data, nzb) || gm_overlap(d_out_indices, nzb, d_out_data, nzb))
+        return fail(nullptr, ECB_ERR_ARG, "the outputs overlap");
+    if (device < 0 || device >= CV_MAX_DEV || hipSetDevice(device) != hipSuccess) return fail(nullptr, ECB_ERR_NO_DEVICE, "no such device");
+    hipStream_t st = nullptr;
+    std::lock_guard<std::mutex> guard(g_cv_lock);
+    CvScratch& S = g_cv[device];
+    const u64 n_words = GM_SHARD_WORDS * (1 + GM_SHARDS);
+    u64* words = S.get<u64>(CvScratch::WORDS, n_words);
+    u32 *keep = S.get<u32>(CvScratch::X0, nnz), *excl = S.get<u32>(CvScratch::X1, nnz + 1), *sums = S.get<u32>(CvScratch::SUMS2, scan_words(nnz));
+    if (!words || !keep || !excl || !sums) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
+    if (hipMemsetAsync(words, 0, n_words * 8, st) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "memset");
+    const u64 threads = std::max<u64>(std::max<u64>((u64)n_ecs + 1, n_loci), (nnz + GM_ITEMS - 1) / GM_ITEMS);
+    const int* ip = (const int*)d_indptr; const int* ix = (const int*)d_indices; const int* da = (const int*)d_data; const u32* mk = (const u32*)d_mask;
+    k_gm_check<<<nblk(threads, TPB), TPB, 0, st>>>(ip, n_ecs, ix, da, nnz, mk, n_loci, n_haps, keep, words);
+    if (hipGetLastError() != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "apply-mask: check launch");
+    if (scan_launch(st, keep, nnz, excl, sums, words + 3, 1, excl + nnz) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "apply-mask: scan launch");
+    k_gm_scatter<<<nblk(threads, TPB), TPB, 0, st>>>(ip, n_ecs, ix, da, nnz, mk, n_loci, excl, (int*)d_out_indptr, (int*)d_out_indices, (int*)d_out_data);
+    if (hipGetLastError() != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "apply-mask: scatter launch");
+    std::vector<u64> back(n_words);
+    if (hipMemcpy(back.data(), words, n_words * 8, hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "apply-mask: %s", hipGetErrorString(hipGetLastError()));
+    const u32 err = (u32)back[0];
+    u64 balance = 0;
+    for (u32 k = 1; k <= GM_SHARDS; ++k) balance += back[GM_SHARD_WORDS * k];
+    if (err & GM_ERR_PTR) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSR: row pointers do not start at 0, go backwards or do not end at nnz");
+    if (err & GM_ERR_LOCUS) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSR: a locus at or beyond n_loci");
+    if (err & GM_ERR_BITS) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSR: a haplotype bit at or beyond n_haplotypes");
+    if (err & GM_ERR_MASK) return fail(nullptr, ECB_ERR_CONTRACT, "a locus mask has a bit at or beyond n_haplotypes");
+    if (balance != 0) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSR: columns not strictly ascending within a row (unsorted or duplicate)");
+    *kept = back[3];
+    return ECB_OK;
+}
+
+extern "C" int ecb_apply_mask(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, uint64_t nnz, const int32_t* indptr, const int32_t* indices,
+                              const int32_t* data, const uint32_t* mask, int32_t* out_indptr, int32_t* out_indices, int32_t* out_data, uint64_t* kept) {
+    if (!indptr || !mask || !out_indptr || !kept || !n_loci || !n_haps || n_haps > 31) return fail(nullptr, ECB_ERR_ARG, "bad argument");
+    if (nnz && (!indices || !data || !out_indices || !out_data)) return fail(nullptr, ECB_ERR_ARG, "bad argument");
+    if (nnz >= (1ull << 31) || n_ecs >= (1u << 31) - 1u) return fail(nullptr, ECB_ERR_LIMIT, "the CSR exceeds the .bin format's int32 limits");
+    if (device < 0 || device >= CV_MAX_DEV || hipSetDevice(device) != hipSuccess) return fail(nullptr, ECB_ERR_NO_DEVICE, "no such device");
+    const u64 rowb = ((u64)n_ecs + 1) * 4, nzb = nnz * 4;
+    DevBuf ip, ix, da, mk, oip, oix, oda;
+    if (ip.take(rowb) || ix.take(nzb) || da.take(nzb) || mk.take((u64)n_loci * 4) || oip.take(rowb) || oix.take(nzb) || oda.take(nzb))
+        return fail(nullptr, ECB_ERR_HIP, "out of device memory");
+    if (hipMemcpy(ip.p, indptr, rowb, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(mk.p, mask, (u64)n_loci * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        (nnz && (hipMemcpy(ix.p, indices, nzb, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(da.p, data, nzb, hipMemcpyHostToDevice) != hipSuccess)))
+        return fail(nullptr, ECB_ERR_HIP, "copy to the device");
+    const int rc = ecb_apply_mask_device(device, n_ecs, n_loci, n_haps, nnz, ip.p, ix.p, da.p, mk.p, oip.p, oix.p, oda.p, kept);
+    if (rc != ECB_OK) return rc;
+    if (hipMemcpy(out_indptr, oip.p, rowb, hipMemcpyDeviceToHost) != hipSuccess ||
+        (*kept && (hipMemcpy(out_indices, oix.p, *kept * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(out_data, oda.p, *kept * 4, hipMemcpyDeviceToHost) != hipSuccess)))
+        return fail(nullptr, ECB_ERR_HIP, "copy from the device");
+    return ECB_OK;
+}
+
 // ---- ecb_merge: the multi-GPU merge for ONE process that drives several GPUs ----------------------------------------------
 // shards[r] holds the reads of contiguous read shard r on its own device; `root` is an empty handle (any device).  The same protocol as
 // alntools_amd/dist.py runs over RCCL with one process per GPU, here with peer copies (hipMemcpyPeerAsync: xGMI between the GPUs of a

@@ -34,7 +34,8 @@ SYMBOLS = ("ecb_abi_version", "ecb_device_count", "ecb_create", "ecb_destroy", "
            "ecb_export_firsts_device", "ecb_assemble_ranges_device", "ecb_table_rebase_device",
            "ecb_export_ec_keys_device", "ecb_ms_local_triples_device", "ecb_ms_adopt_triples_device", "ecb_counters", "ecb_add_counters", "ecb_profile",
            "ecb_profile_read", "ecb_profile_kernel", "ecb_csr_to_hapcsc_device", "ecb_hapcsc_to_csr_device", "ecb_release_scratch",
-           "ecb_csr_to_hapcsc", "ecb_hapcsc_to_csr", "ecb_merge", "ecb_push_device_tiled", "ecb_verify_device_tiled")
+           "ecb_csr_to_hapcsc", "ecb_hapcsc_to_csr", "ecb_merge", "ecb_push_device_tiled", "ecb_verify_device_tiled",
+           "ecb_apply_mask_device", "ecb_apply_mask")
 ABI_VERSION = 4            # include/ecb.h: ECB_ABI_VERSION
 
 
@@ -141,6 +142,9 @@ def load():
     if not ab or hasattr(lib, "ecb_csr_to_hapcsc"):
         lib.ecb_csr_to_hapcsc.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, u64, C.POINTER(u64)]
         lib.ecb_hapcsc_to_csr.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, u64, vp, vp, vp, C.POINTER(u64)]
+    if not ab or hasattr(lib, "ecb_apply_mask"):
+        for f in (lib.ecb_apply_mask_device, lib.ecb_apply_mask):
+            f.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64] + [vp] * 7 + [C.POINTER(u64)]
     lib.ecb_csr_to_hapcsc_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.POINTER(u64)]
     lib.ecb_hapcsc_to_csr_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, u64, vp, vp, vp, C.POINTER(u64)]
     _lib = lib
@@ -251,6 +255,44 @@ def hapcsc_to_csr(csc_indptr, csc_indices, n_ecs):
     if rc != 0:
         raise EcbError(rc, (lib.ecb_last_error(None) or b"").decode())
     return ip, ix[:nnz.value], da[:nnz.value]
+
+
+def apply_mask(indptr, indices, data, mask, n_haps, device=0):
+    """apply-genotypes on the GPU: CSR A (``.bin``'s bitmask values) with every value ANDed with ``mask[locus]``, the non-zeros that
+    become 0 dropped, every row kept (``AlignmentPropertyMatrix.apply_genotypes``).  numpy arrays go through ``ecb_apply_mask`` (host
+    arrays, no PyTorch), CUDA tensors through ``ecb_apply_mask_device`` (``device`` is then the tensors' own).  Returns (indptr, indices,
+    data), int32, of the same kind as the input.  A malformed CSR or mask raises :class:`EcbError` (``ECB_ERR_CONTRACT``)."""
+    lib = load()
+    if hasattr(indptr, "data_ptr"):
+        import torch
+        dev = indptr.device
+        ip, ix, da = (t.contiguous().to(torch.int32) for t in (indptr, indices, data))
+        mk = mask.contiguous().to(torch.int32)
+        E, T, nnz = ip.numel() - 1, mk.numel(), ix.numel()
+        if da.numel() != nnz:
+            raise ValueError("indices and data differ in length")
+        oip = torch.empty(E + 1, dtype=torch.int32, device=dev)
+        oix = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
+        oda = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
+        kept = C.c_uint64()
+        rc = lib.ecb_apply_mask_device(dev.index or 0, E, T, n_haps, nnz, _dev_ptr(ip), _dev_ptr(ix), _dev_ptr(da), _dev_ptr(mk),
+                                       _dev_ptr(oip), _dev_ptr(oix), _dev_ptr(oda), C.byref(kept))
+        if rc != 0:
+            raise EcbError(rc, (lib.ecb_last_error(None) or b"").decode())
+        return oip, oix[:kept.value], oda[:kept.value]
+    ip, ix, da = (np.ascontiguousarray(a, dtype=np.int32) for a in (indptr, indices, data))
+    mk = np.ascontiguousarray(mask, dtype=np.uint32)
+    E, T, nnz = len(ip) - 1, len(mk), len(ix)
+    if len(da) != nnz:
+        raise ValueError("indices and data differ in length")
+    oip = np.empty(E + 1, dtype=np.int32)
+    oix = np.empty(max(nnz, 1), dtype=np.int32)
+    oda = np.empty(max(nnz, 1), dtype=np.int32)
+    kept = C.c_uint64()
+    rc = lib.ecb_apply_mask(device, E, T, n_haps, nnz, _ptr(ip), _ptr(ix), _ptr(da), _ptr(mk), _ptr(oip), _ptr(oix), _ptr(oda), C.byref(kept))
+    if rc != 0:
+        raise EcbError(rc, (lib.ecb_last_error(None) or b"").decode())
+    return oip, oix[:kept.value], oda[:kept.value]
 
 
 class EcBuilder(object):

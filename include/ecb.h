@@ -290,6 +290,22 @@ int ecb_csr_to_hapcsc(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_ha
 int ecb_hapcsc_to_csr(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, const int32_t* csc_indptr, const int32_t* csc_indices,
                       uint64_t total, int32_t* indptr_a, int32_t* indices_a, int32_t* data_a, uint64_t* nnz);
 
+/* apply-genotypes (ABI 4, additive): A' = every non-zero of a CSR A (.bin's bitmask values) ANDed with the haplotype mask of its locus,
+ * the non-zeros that become 0 removed, every row kept (empty rows too), columns ascending -- what the reference's
+ * AlignmentPropertyMatrix.apply_genotypes + ecsave2 write (AlignmentPropertyMatrix.py:483-505, bin_utils.py:1031-1051).
+ * indptr n_ecs + 1, indices / data nnz, mask n_loci values (bit h = haplotype h allowed at that locus), all int32 / uint32.
+ * The input must be well formed; otherwise ECB_ERR_CONTRACT and nothing is reported kept: row pointers from 0 to nnz, never falling;
+ * loci below n_loci; columns strictly ascending within a row (an unsorted or duplicate column is refused); no data or mask bit at or above
+ * n_haps (<= 31).
+ * ecb_apply_mask_device: device pointers; the outputs (out_indptr n_ecs + 1, out_indices / out_data room for nnz) must not overlap the
+ *   inputs or each other; *kept = non-zeros written.
+ * ecb_apply_mask: the same on HOST arrays (the library allocates and frees its own device buffers); out_indices / out_data hold nnz. */
+int ecb_apply_mask_device(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, uint64_t nnz, const void* d_indptr,
+                          const void* d_indices, const void* d_data, const void* d_mask, void* d_out_indptr, void* d_out_indices,
+                          void* d_out_data, uint64_t* kept);
+int ecb_apply_mask(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, uint64_t nnz, const int32_t* indptr, const int32_t* indices,
+                   const int32_t* data, const uint32_t* mask, int32_t* out_indptr, int32_t* out_indices, int32_t* out_data, uint64_t* kept);
+
 /* Measurement: HIP-event time of the record-stream kernel on the handle's own stream; ecb_profile_kernel (ABI 4): the name of the
  * kernel the last batch launched, as rocprofv3 prints it (the stream kernel is compiled more than once; the library picks per batch). */
 int ecb_profile(ecb_handle* h, int enable);
