@@ -10,6 +10,7 @@ data = haplotype bitmask); N as CSC (``len(indptr)``, ``nnz``, indptr, indices =
 """
 from __future__ import annotations
 
+import os
 from struct import pack, unpack_from
 
 import numpy as np
@@ -201,3 +202,109 @@ def apply_genotypes(ec_filename, gt_filename, grp_filename, out_filename, device
         LOG.info("{} created in total time: {}".format(out_filename, utils.format_time(start_time, time.time())))
     except Exception as e:
         LOG.error("Error: {}".format(str(e)))
+
+
+class MergePlan(object):
+    """What ``plan_merge`` decides from the headers alone: the output's names and lengths and, per input, the maps of its
+    columns and samples into the output's (``target_maps[k]`` is None when every input has the same target list)."""
+
+    def __init__(self, hname, lname, lengths, sname, target_maps, sample_maps):
+        self.hname, self.lname, self.lengths, self.sname = hname, lname, lengths, sname
+        self.target_maps, self.sample_maps = target_maps, sample_maps
+
+
+def plan_merge(ms, names=None):
+    """The header side of ``ecmerge``: every input must have the same haplotypes in the same order.  Targets: one identical list
+    everywhere is used as it is; otherwise the output's targets are the union by name in first-seen order, and a list that repeats a
+    name is then an error.  A name seen in several inputs must have the same per-haplotype lengths.  Samples: the union by name in
+    first-seen order; a list that repeats a name is an error.  Raises ValueError with the reason."""
+    names = names or ["input {}".format(k + 1) for k in range(len(ms))]
+    if not ms:
+        raise ValueError("no input files")
+    m0 = ms[0]
+    for m, f in zip(ms[1:], names[1:]):
+        if m.hname != m0.hname:
+            raise ValueError("{}: haplotypes {} differ from {}'s {}".format(f, m.hname, names[0], m0.hname))
+    H = m0.num_haplotypes
+    lens = [np.asarray(m.lengths).astype(np.int64).reshape(m.num_loci, H) for m in ms]
+    if all(m.lname == m0.lname for m in ms[1:]):
+        for m, L, f in zip(ms[1:], lens[1:], names[1:]):
+            bad = np.flatnonzero((L != lens[0]).any(axis=1))
+            if len(bad):
+                raise ValueError("{}: target {} has lengths {} against {} in {}".format(
+                    f, m.lname[bad[0]], L[bad[0]].tolist(), lens[0][bad[0]].tolist(), names[0]))
+        lname, lengths, tmaps = list(m0.lname), lens[0], [None] * len(ms)
+    else:
+        tid, lname, rows, tmaps = {}, [], [], []
+        for m, L, f in zip(ms, lens, names):
+            if len(set(m.lname)) != len(m.lname):
+                dup = next(t for i, t in enumerate(m.lname) if t in m.lname[:i])
+                raise ValueError("{}: target {} is listed more than once (the target lists differ, so columns are matched by name)".format(f, dup))
+            tm = np.empty(m.num_loci, dtype=np.int64)
+            for i, t in enumerate(m.lname):
+                j = tid.get(t)
+                if j is None:
+                    j = tid[t] = len(lname)
+                    lname.append(t)
+                    rows.append(L[i])
+                elif not np.array_equal(rows[j], L[i]):
+                    raise ValueError("{}: target {} has lengths {} against {} before".format(f, t, L[i].tolist(), rows[j].tolist()))
+                tm[i] = j
+            tmaps.append(tm)
+        lengths = np.array(rows, dtype=np.int64).reshape(len(lname), H)
+    sid, sname, smaps = {}, [], []
+    for m, f in zip(ms, names):
+        if len(set(m.sname)) != len(m.sname):
+            dup = next(s for i, s in enumerate(m.sname) if s in m.sname[:i])
+            raise ValueError("{}: sample {} is listed more than once".format(f, dup))
+        sm = np.empty(m.num_samples, dtype=np.int64)
+        for i, s in enumerate(m.sname):
+            if s not in sid:
+                sid[s] = len(sname)
+                sname.append(s)
+            sm[i] = sid[s]
+        smaps.append(sm)
+    return MergePlan(list(m0.hname), lname, lengths, sname, tmaps, smaps)
+
+
+def ecmerge(ec_files, ec_out, device=0):
+    """``alntools ecmerge`` (the reference's ``bin_utils.ecmerge``, ``bin_utils.py:443-956``, which cannot run): several ``.bin``
+    files as one.  The headers are read and planned here (``plan_merge``) before libecb is loaded; A and N are combined on the GPU
+    (``ecb.combine``): rows with equal (column, haplotype mask) sets are one EC, numbered by first appearance over the files in
+    order, counts add per (EC, sample) and zero sums are dropped.  Any failure is logged as ``Error: ...``, no file is written and
+    the exception is raised again (the command line exits with status 1)."""
+    import time
+    from . import utils
+    LOG = utils.get_logger()
+    try:
+        start_time = time.time()
+        ms = []
+        for f in ec_files:
+            LOG.info("Loading {}...".format(f))
+            ms.append(ecload(f))
+        plan = plan_merge(ms, list(ec_files))
+        LOG.info("Combining {:,} files...".format(len(ms)))
+        from . import ecb
+        parts = [dict(indptrA=m.indptrA, indicesA=m.indicesA, dataA=m.dataA, indptrN=m.indptrN, indicesN=m.indicesN, dataN=m.dataN,
+                      n_loci=m.num_loci, target_map=tm, sample_map=sm)
+                 for m, tm, sm in zip(ms, plan.target_maps, plan.sample_maps)]
+        A_N = ecb.combine(parts, len(plan.lname), len(plan.hname), len(plan.sname), device=device)
+        out = ECMatrices(plan.hname, plan.lname, plan.lengths, plan.sname, *A_N)
+        LOG.info("Saving to {}...".format(ec_out))
+        LOG.info("Number of haplotypes: {:,}".format(out.num_haplotypes))
+        LOG.info("Number of reference targets: {:,}".format(out.num_loci))
+        LOG.info("Number of samples: {:,}".format(out.num_samples))
+        LOG.info("Number of equivalence classes: {:,} (from {:,} rows)".format(out.num_reads, sum(m.num_reads for m in ms)))
+        b = ecsave2_bytes(out)
+        try:
+            with open(ec_out, 'wb') as fh:
+                fh.write(b)
+        except BaseException:
+            if os.path.exists(ec_out):
+                os.remove(ec_out)
+            raise
+        LOG.info("Saving completed")
+        LOG.info("{} created in total time: {}".format(ec_out, utils.format_time(start_time, time.time())))
+    except Exception as e:
+        LOG.error("Error: {}".format(str(e)))
+        raise

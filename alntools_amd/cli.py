@@ -1,9 +1,11 @@
 # -*- coding: utf-8 -*-
 """Command line with the reference's hot-path sub-commands and options (``alntools/cli.py:43-113``):
-``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``, ``apply-genotypes``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
+``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``, ``apply-genotypes``, ``ecmerge``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
 from __future__ import annotations
 
+import glob
 import os
+import sys
 
 import click
 
@@ -96,6 +98,31 @@ def apply_genotypes(ec_file, gt_file, grp_file, out_file, verbose):
     """
     utils.configure_logging(verbose)
     methods.apply_genotypes(ec_file, gt_file, grp_file, out_file)
+
+
+@cli.command('ecmerge', options_metavar='<options>', short_help='merge multiple ec files')
+@click.option('-i', '--input', 'inputs', metavar='input', type=click.Path(exists=True, resolve_path=True, dir_okay=False), multiple=True,
+              help="input file, can specify multiple")
+@click.option('-d', '--directory', metavar='directory', type=click.Path(exists=True, resolve_path=True, file_okay=False, dir_okay=True),
+              help="input directory (its *.bin files, in name order, after the -i files)")
+@click.option('-o', '--output', metavar='output', required=True, type=click.Path(resolve_path=True, dir_okay=False), help="output file")
+@click.option('-v', '--verbose', count=True, help='the more times listed, the more output')
+def ecmerge(inputs, directory, output, verbose):
+    """
+    Combine binary EC files
+    """
+    utils.configure_logging(verbose)
+    input_files = list(inputs)
+    if directory:
+        bin_files = sorted(glob.glob(os.path.join(directory, "*.bin")))
+        if len(bin_files) == 0:
+            print('No bin files found in directory: {}'.format(directory))
+            sys.exit(1)
+        input_files.extend(bin_files)
+    try:
+        methods.ecmerge(input_files, output)
+    except Exception:
+        sys.exit(1)                                                  # (logged as "Error: ..." by bin_utils.ecmerge)
 
 
 if __name__ == '__main__':

@@ -4586,6 +4586,478 @@ extern "C" int ecb_apply_mask(int device, uint32_t n_ecs, uint32_t n_loci, uint3
     return ECB_OK;
 }
 
+// ---- ecmerge: several .bin files' A and N combined into one (ecb_combine / ecb_combine_device) ---------------------------------------------
+// The rows of all parts are one concatenated index space: global row g = the part's first row + its own row, and g plays the "read" of the
+// EC builder.  Every row becomes one Entry (hash, first_inv = ~g, its pairs in the merged column numbering, sorted) and k_merge puts them all
+// into one table -- equal keys from one part or several find each other there exactly as two ranks' ECs do -- then ecb_finalize ranks the
+// ECs by first appearance and emits CSR A.  A lookup pass gives every row its EC; N is the (output sample, EC) pairs of every part's N through
+// the two maps, sorted, summed per pair, zeros dropped, written as CSC.  No loop over a row anywhere except the key compare of the lookup:
+// the pair passes run one thread per non-zero, so rows of 1 and of 10 000 loci cost the same per pair.
+// The empty key (a row without pairs) is a key like any other: n = 0, hash finish_hash(0, 0) = 1, n1 = 1 in its slot; ListCmp compares
+// zero pairs and finds it equal, k_merge stores nothing and publishes n1, and the emit writes a row of length 0.
+namespace {
+struct CbPart {                                  // one part, device pointers, and where it sits in the concatenation
+    const int *ipa, *ixa, *daa, *ipn, *ixn, *dan;
+    const u32 *tmap, *smap;
+    u32 n_ecs, n_loci, n_samples, pad;
+    u64 nnz_a, nnz_n;
+};
+// base arrays (u64, n_parts + 1 each, exclusive sums): rows, pairs, N non-zeros, row pointers (E + 1 per part), N column pointers (S + 1)
+enum { CB_ROWS = 0, CB_PAIRS, CB_NZ, CB_APTR, CB_NPTR, CB_BASES };
+enum : u32 { CB_ERR_PTR = 1u, CB_ERR_LOCUS = 2u, CB_ERR_BITS = 4u, CB_ERR_ORDER = 8u, CB_ERR_MAP = 16u, CB_ERR_NPTR = 32u, CB_ERR_NEC = 64u,
+             CB_ERR_NCOUNT = 128u, CB_ERR_SMAP = 256u, CB_ERR_LOST = 512u, CB_ERR_SUM = 1024u };
+constexpr u32 CB_SHARDS = 256, CB_SHARD_WORDS = 16;    // arena sizing: per shard (its own 128-byte line) the largest and the summed wave demand
+// the largest p < n with base[p] <= x (x below base[n]: an empty part never wins, the part after it starts at the same place)
+__device__ __forceinline__ u32 cb_find(const u64* base, u32 n, u64 x) {
+    u32 a = 0, b = n;
+    while (b - a > 1) { const u32 m = (a + b) >> 1; if (base[m] <= x) a = m; else b = m; }
+    return a;
+}
+// the row of non-zero i of a CSR whose row pointers have been checked: the largest e < E with ptr[e] <= i
+__device__ __forceinline__ u32 cb_row(const int* ptr, u32 E, long long i) {
+    u32 a = 0, b = E;
+    while (b - a > 1) { const u32 m = (a + b) >> 1; if ((long long)ptr[m] <= i) a = m; else b = m; }
+    return a;
+}
+// inclusive sum of v over the lanes of a run of equal keys (keys non-decreasing over the wave's lanes; the lanes past the end come last and
+// never feed a valid lane).  Written by the run's last lane: a plain store when the run lies inside the wave, an add when it goes on in a
+// neighbouring wave (dst zeroed) -- one write per run, not one atomic per element.
+__device__ __forceinline__ void cb_run_sum(u64 key, u64 v, bool valid, u64 i, u64 n, const u64* keys, u64* dst, u64 at) {
+    const u32 lane = threadIdx.x & 63u;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const u64 ov = __shfl_up(v, d), ok = __shfl_up(key, d);
+        if ((int)lane >= d && ok == key) v += ov;
+    }
+    const u64 nk = __shfl_down(key, 1);
+    const bool nvalid = __shfl_down((int)valid, 1) != 0;
+    const u64 k0 = __shfl(key, 0);
+    if (!valid) return;
+    if (lane != 63u && nvalid && nk == key) return;                     // not the run's last lane in this wave
+    const u64 i0 = i - lane;                                             // the wave's first element
+    const bool before = key == k0 && i0 > 0 && keys[i0 - 1] == key;
+    const bool after = i + 1 < n && keys[i + 1] == key;                  // (only the wave's last lane can see its run go on)
+    if (before || after) atomicAdd(reinterpret_cast<unsigned long long*>(dst + at), (unsigned long long)v);
+    else dst[at] = v;
+}
+// row pointers of A (one thread per pointer of every part) and column pointers of N
+__global__ __launch_bounds__(TPB) void k_cb_check(const CbPart* P, u32 n_parts, const u64* base, u32* err) {
+    const u64 t = blockIdx.x * (u64)TPB + threadIdx.x;
+    const u64* ab = base + CB_APTR * (n_parts + 1);
+    const u64* nb = base + CB_NPTR * (n_parts + 1);
+    u32 e = 0;
+    if (t < ab[n_parts]) {
+        const u32 p = cb_find(ab, n_parts, t);
+        const CbPart& q = P[p];
+        const u64 k = t - ab[p];
+        const long long a = q.ipa[k];
+        if (a < 0 || (u64)a > q.nnz_a || (k == 0 && a != 0) || (k == q.n_ecs && (u64)a != q.nnz_a)) e |= CB_ERR_PTR;
+        else if (k < q.n_ecs && q.ipa[k + 1] < a) e |= CB_ERR_PTR;
+    }
+    if (t < nb[n_parts]) {
+        const u32 p = cb_find(nb, n_parts, t);
+        const CbPart& q = P[p];
+        const u64 k = t - nb[p];
+        const long long a = q.ipn[k];
+        if (a < 0 || (u64)a > q.nnz_n || (k == 0 && a != 0) || (k == q.n_samples && (u64)a != q.nnz_n)) e |= CB_ERR_NPTR;
+        else if (k < q.n_samples && q.ipn[k + 1] < a) e |= CB_ERR_NPTR;
+    }
+    if (__ballot(e != 0u)) {
+        u32 w = e;
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) w |= (u32)__shfl_xor((int)w, d);
+        if ((threadIdx.x & 63u) == 0u) atomicOr(err, w);
+    }
+}
+// one thread per non-zero of every part: checked, its column mapped, out as (global row << 32 | merged column, mask) -- the sort key
+__global__ __launch_bounds__(TPB) void k_cb_pairs(const CbPart* P, u32 n_parts, const u64* base, u32 n_loci, u32 n_haps, u64* keys, u32* vals, u32* err) {
+    const u64 i = blockIdx.x * (u64)TPB + threadIdx.x;
+    const u64* pb = base + CB_PAIRS * (n_parts + 1);
+    u32 e = 0;
+    if (i < pb[n_parts]) {
+        const u32 p = cb_find(pb, n_parts, i);
+        const CbPart& q = P[p];
+        const long long li = (long long)(i - pb[p]);
+        const u32 r = cb_row(q.ipa, q.n_ecs, li);
+        const int c = q.ixa[li];
+        const u32 d = (u32)q.daa[li];
+        u32 m = 0;
+        if (d == 0u || (d >> n_haps) != 0u) e |= CB_ERR_BITS;
+        if (c < 0 || (u32)c >= q.n_loci) e |= CB_ERR_LOCUS;
+        else {
+            m = q.tmap ? q.tmap[c] : (u32)c;
+            if (m >= n_loci) e |= CB_ERR_MAP;
+        }
+        if (li > q.ipa[r] && q.ixa[li - 1] >= c) e |= CB_ERR_ORDER;                      // ascending as the part stores it
+        keys[i] = ((base[CB_ROWS * (n_parts + 1) + p] + r) << 32) | m;
+        vals[i] = d;
+    }
+    if (__ballot(e != 0u)) {
+        u32 w = e;
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) w |= (u32)__shfl_xor((int)w, d);
+        if ((threadIdx.x & 63u) == 0u) atomicOr(err, w);
+    }
+}
+// the pairs in (row, column) order -> the key list k_merge reads, and every row's set hash (sum of pair_hash64 over its pairs); a column
+// that repeats within a row (a target map that sends two columns to one) is refused here
+__global__ __launch_bounds__(TPB) void k_cb_hash(const u64* keys, const u32* vals, u64 n, uint2* pairs, u64* rowhash, u32* err) {
+    const u64 i = blockIdx.x * (u64)TPB + threadIdx.x;
+    const bool valid = i < n;
+    u64 k = ~0ull, h = 0, row = 0;
+    bool dup = false;
+    if (valid) {
+        k = keys[i];
+        row = k >> 32;
+        const u32 col = (u32)k, mask = vals[i];
+        pairs[i] = make_uint2(col, mask);
+        h = pair_hash64(col, mask);
+        dup = i > 0 && (keys[i - 1] >> 32) == row && keys[i - 1] >= k;
+    }
+    if (__ballot(dup) && (threadIdx.x & 63u) == 0u) atomicOr(err, CB_ERR_ORDER);
+    // (runs are rows: the row is the key's high word, and a row's pairs are adjacent)
+    const u64 rk = valid ? row : ~0ull;
+    const u32 lane = threadIdx.x & 63u;
+    u64 v = h;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const u64 ov = __shfl_up(v, d), ok = __shfl_up(rk, d);
+        if ((int)lane >= d && ok == rk) v += ov;
+    }
+    const u64 nk = __shfl_down(rk, 1), k0 = __shfl(rk, 0);
+    if (!valid || (lane != 63u && nk == rk)) return;
+    const u64 i0 = i - lane;
+    const bool before = rk == k0 && i0 > 0 && (keys[i0 - 1] >> 32) == rk;
+    const bool after = i + 1 < n && (keys[i + 1] >> 32) == rk;
+    if (before || after) atomicAdd(reinterpret_cast<unsigned long long*>(rowhash + row), (unsigned long long)v);
+    else rowhash[row] = v;
+}
+// one Entry per global row (k_merge's exchange format), and per aligned 64 rows -- one k_merge wave -- the arena pairs it reserves
+__global__ __launch_bounds__(TPB) void k_cb_entries(const CbPart* P, u32 n_parts, const u64* base, const u64* rowhash, Entry* ent, u64* words) {
+    const u64 g = blockIdx.x * (u64)TPB + threadIdx.x;
+    const u64* rb = base + CB_ROWS * (n_parts + 1);
+    u32 over = 0;
+    if (g < rb[n_parts]) {
+        const u32 p = cb_find(rb, n_parts, g);
+        const CbPart& q = P[p];
+        const u64 r = g - rb[p];
+        const u32 a = (u32)q.ipa[r], n = (u32)q.ipa[r + 1] - a;
+        Entry en;
+        en.lo = finish_hash(rowhash[g], n); en.reserved = 0; en.count = 0; en.first_inv = ~(u32)g;
+        en.off = (u32)(base[CB_PAIRS * (n_parts + 1) + p] + a); en.n = n;
+        ent[g] = en;
+        over = n > INL ? n - INL : 0u;
+    }
+    const u32 ws = wave_sum(over);
+    if ((threadIdx.x & 63u) == 0u && ws) {
+        u64* s = words + CB_SHARD_WORDS * (1 + (g >> 6) % CB_SHARDS);
+        atomicMax(reinterpret_cast<unsigned long long*>(s), (unsigned long long)ws);
+        atomicAdd(reinterpret_cast<unsigned long long*>(s + 1), (unsigned long long)ws);
+    }
+}
+// every row's EC: its hash, then its key compared pair for pair with the slot's (both in column order, as k_merge stored them); no slot
+// is created.  A row that finds no slot is an internal error (CB_ERR_LOST).
+__global__ __launch_bounds__(TPB) void k_cb_lookup(const Entry* ent, u64 n, const uint2* pairs, const Slot* table, u64 cap_mask, const uint2* arena,
+                                                   const u32* rank_of_slot, u32* ec_of_row, u32* err) {
+    const u64 g = blockIdx.x * (u64)TPB + threadIdx.x;
+    if (g >= n) return;
+    const Entry en = ent[g];
+    u64 j = en.lo & cap_mask;
+    for (u64 probe = 0; probe <= cap_mask; ++probe, j = (j + 1) & cap_mask) {
+        const Slot& s = table[j];
+        if (s.lo == 0ull) break;
+        if (s.lo != en.lo || s.n1 != en.n + 1u) continue;
+        bool same = true;
+        for (u32 t = 0; t < en.n && same; ++t) {
+            const uint2 a = key_pair(s, arena, t), b = pairs[(u64)en.off + t];
+            same = a.x == b.x && a.y == b.y;
+        }
+        if (same) { ec_of_row[g] = rank_of_slot[j]; return; }
+    }
+    ec_of_row[g] = 0;
+    atomicOr(err, CB_ERR_LOST);
+}
+// one thread per non-zero of every part's N: (output sample << 32 | EC, count)
+__global__ __launch_bounds__(TPB) void k_cb_ntrip(const CbPart* P, u32 n_parts, const u64* base, u32 n_samples, const u32* ec_of_row,
+                                                  u64* keys, u32* vals, u32* err) {
+    const u64 i = blockIdx.x * (u64)TPB + threadIdx.x;
+    const u64* zb = base + CB_NZ * (n_parts + 1);
+    u32 e = 0;
+    if (i < zb[n_parts]) {
+        const u32 p = cb_find(zb, n_parts, i);
+        const CbPart& q = P[p];
+        const long long li = (long long)(i - zb[p]);
+        const u32 s = cb_row(q.ipn, q.n_samples, li);
+        const int r = q.ixn[li], c = q.dan[li];
+        const u32 os = q.smap ? q.smap[s] : s;
+        u32 ec = 0;
+        if (r < 0 || (u32)r >= q.n_ecs) e |= CB_ERR_NEC;
+        else ec = ec_of_row[base[CB_ROWS * (n_parts + 1) + p] + (u32)r];
+        if (c < 0) e |= CB_ERR_NCOUNT;
+        if (os >= n_samples) e |= CB_ERR_SMAP;
+        keys[i] = ((u64)os << 32) | ec;
+        vals[i] = c < 0 ? 0u : (u32)c;
+    }
+    if (__ballot(e != 0u)) {
+        u32 w = e;
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) w |= (u32)__shfl_xor((int)w, d);
+        if ((threadIdx.x & 63u) == 0u) atomicOr(err, w);
+    }
+}
+__global__ void k_cb_heads(const u64* keys, u64 n, u32* flag) {
+    const u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+    if (i < n) flag[i] = (i == 0 || keys[i] != keys[i - 1]) ? 1u : 0u;
+}
+// sorted (sample, EC) keys -> one sum per distinct key (run id = exclusive scan of the head flags), and each run's key
+__global__ __launch_bounds__(TPB) void k_cb_nsum(const u64* keys, const u32* vals, const u32* flag, const u32* pos, u64 n, u64* sums, u64* runkey) {
+    const u64 i = blockIdx.x * (u64)TPB + threadIdx.x;
+    const bool valid = i < n;
+    u64 k = ~0ull, v = 0, at = 0;
+    if (valid) {
+        k = keys[i]; v = vals[i];
+        at = pos[i] + flag[i] - 1u;
+        if (flag[i]) runkey[at] = k;
+    }
+    cb_run_sum(k, v, valid, i, n, keys, sums, at);
+}
+// (every one of the n flags is written -- the scan behind reads them all -- and the run count is bounded by n whatever the device holds)
+__global__ void k_cb_nkeep(const u64* sums, const u64* n_runs, u64 n, u32* keep, u32* err) {
+    const u64 r = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const u64 s = r < min(*n_runs, n) ? sums[r] : 0ull;
+    keep[r] = s != 0ull;
+    if (s > (u64)INT_MAX) atomicOr(err, CB_ERR_SUM);
+}
+__global__ void k_cb_nemit(const u64* sums, const u64* runkey, const u32* keep, const u32* opos, const u64* n_runs, u64 n, int* indices, int* data, u64* okey) {
+    const u64 r = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+    if (r >= min(*n_runs, n) || !keep[r]) return;
+    const u32 o = opos[r];
+    indices[o] = (int)(u32)runkey[r];
+    data[o] = (int)sums[r];
+    okey[o] = runkey[r];
+}
+// column pointers of the output N: column s starts at the first kept key of sample s
+__global__ void k_cb_nptr(const u64* okey, const u64* n_out, u64 n, u32 n_samples, int* indptr) {
+    const u64 s = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+    if (s <= n_samples) indptr[s] = (int)lower_bound_u64(okey, min(*n_out, n), s << 32);
+}
+struct StreamGuard { hipStream_t s = nullptr; ~StreamGuard() { if (s) { hipStreamSynchronize(s); hipStreamDestroy(s); } } };
+struct CbHandle { ecb_handle* h = nullptr; ~CbHandle() { if (h) ecb_destroy(h); } };
+}  // namespace
+
+extern "C" int ecb_combine_device(int device, uint32_t n_parts, const ecb_combine_part* parts, uint32_t n_loci, uint32_t n_haps, uint32_t n_samples,
+                                  void* d_out_indptr_a, void* d_out_indices_a, void* d_out_data_a, void* d_out_indptr_n, void* d_out_indices_n,
+                                  void* d_out_data_n, uint64_t* out_sizes) {
+    if (!parts || !n_parts || !out_sizes || !d_out_indptr_a || !d_out_indptr_n || !n_loci || !n_haps || n_haps > 31)
+        return fail(nullptr, ECB_ERR_ARG, "combine: bad argument");
+    if (n_loci >= MAX_LOCI) return fail(nullptr, ECB_ERR_ARG, "combine: n_loci out of range (1 .. 2^26-3)");
+    const u32 B = n_parts + 1;
+    std::vector<u64> base((u64)CB_BASES * B, 0);
+    std::vector<CbPart> hp(n_parts);
+    for (u32 p = 0; p < n_parts; ++p) {
+        const ecb_combine_part& c = parts[p];
+        if (c.struct_size != sizeof(ecb_combine_part)) return fail(nullptr, ECB_ERR_ARG, "combine: part %u: bad struct_size", p);
+        if (!c.indptr_a || !c.indptr_n || (c.nnz_a && (!c.indices_a || !c.data_a)) || (c.nnz_n && (!c.indices_n || !c.data_n)))
+            return fail(nullptr, ECB_ERR_ARG, "combine: part %u: null array", p);
+        if (c.n_samples && !c.sample_map) return fail(nullptr, ECB_ERR_ARG, "combine: part %u: no sample map", p);
+        if (!c.target_map && c.n_loci != n_loci) return fail(nullptr, ECB_ERR_ARG, "combine: part %u: no target map, but %u loci against %u", p, c.n_loci, n_loci);
+        if (c.nnz_a >= (1ull << 31) || c.nnz_n >= (1ull << 31) || c.n_ecs >= (1u << 31) - 1u || c.n_samples >= (1u << 31) - 1u)
+            return fail(nullptr, ECB_ERR_LIMIT, "combine: part %u exceeds the .bin format's int32 limits", p);
+        hp[p] = CbPart{(const int*)c.indptr_a, (const int*)c.indices_a, (const int*)c.data_a, (const int*)c.indptr_n, (const int*)c.indices_n,
+                       (const int*)c.data_n, c.target_map, c.sample_map, c.n_ecs, c.n_loci, c.n_samples, 0u, c.nnz_a, c.nnz_n};
+        const u64 add[CB_BASES] = {c.n_ecs, c.nnz_a, c.nnz_n, (u64)c.n_ecs + 1, (u64)c.n_samples + 1};
+        for (int k = 0; k < CB_BASES; ++k) base[(u64)k * B + p + 1] = base[(u64)k * B + p] + add[k];
+    }
+    const u64 R = base[CB_ROWS * B + n_parts], NP = base[CB_PAIRS * B + n_parts], NZ = base[CB_NZ * B + n_parts];
+    // (the outputs are bounded by these sums, which is what the caller allocates; the sort of N takes fewer than 2^30 keys)
+    if (R >= (1ull << 31) - 1 || NP >= (1ull << 31) || NZ >= (1ull << 30) || n_samples >= (1u << 31) - 1u)
+        return fail(nullptr, ECB_ERR_LIMIT, "combine: the merged sizes exceed the .bin format's int32 limits");
+    if ((R && (!d_out_indices_a || !d_out_data_a)) || (NZ && (!d_out_indices_n || !d_out_data_n))) return fail(nullptr, ECB_ERR_ARG, "combine: null output");
+    bool any_map = false;
+    for (u32 p = 0; p < n_parts; ++p) any_map |= hp[p].tmap != nullptr;
+    if (any_map && NP >= (1ull << 30)) return fail(nullptr, ECB_ERR_LIMIT, "combine: more than 2^30 non-zeros to re-sort after a target map");
+    if (device < 0 || device >= CV_MAX_DEV || hipSetDevice(device) != hipSuccess) return fail(nullptr, ECB_ERR_NO_DEVICE, "no such device");
+    StreamGuard sg;
+    if (hipStreamCreate(&sg.s) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "combine: stream");
+    hipStream_t st = sg.s;
+    Scratch S;
+    CbPart* d_parts = S.get<CbPart>(n_parts);
+    u64* d_base = S.get<u64>(base.size());
+    const u64 n_words = CB_SHARD_WORDS * (1 + CB_SHARDS);
+    u64* words = S.get<u64>(n_words);                    // [0] error bits (u32), then the arena shards
+    const u64 NK = std::max(NP, NZ);                     // (the sort buffers serve the pairs of A, then the entries of N)
+    u64 *keys0 = S.get<u64>(NK), *keys1 = S.get<u64>(NK), *rowhash = S.get<u64>(R);
+    u32 *vals0 = S.get<u32>(NK), *vals1 = S.get<u32>(NK);
+    uint2* pairs = S.get<uint2>(NP);
+    Entry* ent = S.get<Entry>(R);
+    if (!d_parts || !d_base || !words || !keys0 || !keys1 || !rowhash || !vals0 || !vals1 || !pairs || !ent) return fail(nullptr, ECB_ERR_HIP, "combine: out of device memory");
+    u32* err = reinterpret_cast<u32*>(words);
+    std::vector<u64> back(n_words);
+    hipStream_t cur = st;                                // (the handle's own stream once there is one: it queues the slot ranks)
+    auto check = [&](const char* what) -> int {           // one wait: the error word and the shards
+        if (hipMemcpyAsync(back.data(), words, n_words * 8, hipMemcpyDeviceToHost, cur) != hipSuccess || hipStreamSynchronize(cur) != hipSuccess)
+            return fail(nullptr, ECB_ERR_HIP, "combine: %s: %s", what, hipGetErrorString(hipGetLastError()));
+        const u32 e = (u32)back[0];
+        if (e & CB_ERR_PTR) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSR A: row pointers do not start at 0, go backwards or do not end at nnz");
+        if (e & CB_ERR_NPTR) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSC N: column pointers do not start at 0, go backwards or do not end at nnz");
+        if (e & CB_ERR_LOCUS) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSR A: a column at or beyond the part's n_loci");
+        if (e & CB_ERR_BITS) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSR A: a stored 0 or a haplotype bit at or beyond n_haplotypes");
+        if (e & CB_ERR_MAP) return fail(nullptr, ECB_ERR_CONTRACT, "a target map sends a column at or beyond n_loci");
+        if (e & CB_ERR_ORDER) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSR A: columns not strictly ascending within a row (unsorted or duplicate, before or after the target map)");
+        if (e & CB_ERR_NEC) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSC N: an EC index at or beyond the part's n_ecs");
+        if (e & CB_ERR_NCOUNT) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSC N: a negative count");
+        if (e & CB_ERR_SMAP) return fail(nullptr, ECB_ERR_CONTRACT, "a sample map sends a sample at or beyond n_samples");
+        if (e & CB_ERR_SUM) return fail(nullptr, ECB_ERR_LIMIT, "a merged count exceeds int32");
+        if (e & CB_ERR_LOST) return fail(nullptr, ECB_ERR_HIP, "internal: a row found no EC");
+        return ECB_OK;
+    };
+    if (hipMemcpyAsync(d_parts, hp.data(), n_parts * sizeof(CbPart), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(d_base, base.data(), base.size() * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemsetAsync(words, 0, n_words * 8, st) != hipSuccess || hipMemsetAsync(rowhash, 0, std::max<u64>(R, 1) * 8, st) != hipSuccess)
+        return fail(nullptr, ECB_ERR_HIP, "combine: copy to the device");
+    // 1. the pointers; 2. the pairs (their binary searches trust checked pointers)
+    const u64 n_ptr = std::max(base[CB_APTR * B + n_parts], base[CB_NPTR * B + n_parts]);
+    k_cb_check<<<nblk(n_ptr, TPB), TPB, 0, st>>>(d_parts, n_parts, d_base, err);
+    int rc = check("pointer check");
+    if (rc != ECB_OK) return rc;
+    if (NP) k_cb_pairs<<<nblk(NP, TPB), TPB, 0, st>>>(d_parts, n_parts, d_base, n_loci, n_haps, keys0, vals0, err);
+    rc = check("pair check");
+    if (rc != ECB_OK) return rc;
+    // 3. rows that a target map re-numbered are re-sorted: one radix sort of (row, column) over all pairs (parts without a map are sorted already)
+    u64* keys = keys0; u32* vals = vals0;
+    if (any_map && NP > 1) {
+        u64 bits = 0;
+        for (u64 x = (R - 1) << 32 | (n_loci - 1); x; x >>= 1) bits = (bits << 1) | 1ull;
+        SortScratch sc{S.get<u32>(rs_words(NP)), S.get<u32>(RS_AUX_WORDS), S.get<u32>(rs_scan_blocks(NP) + 8), words + 1};
+        if (!sc.hist || !sc.offs || !sc.sums) return fail(nullptr, ECB_ERR_HIP, "combine: out of device memory");
+        u64* kk[2] = {keys0, keys1}; u32* vv[2] = {vals0, vals1};
+        int where = 0;
+        const hipError_t e = radix_sort_pairs64(st, kk, vv, NP, sc, &where, bits);
+        if (e != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "combine: radix sort: %s", hipGetErrorString(e));
+        keys = kk[where]; vals = vv[where];
+    }
+    // 4. key lists and row hashes; 5. the entries, and the key arena's worst wave
+    if (NP) k_cb_hash<<<nblk(NP, TPB), TPB, 0, st>>>(keys, vals, NP, pairs, rowhash, err);
+    if (R) k_cb_entries<<<nblk(R, TPB), TPB, 0, st>>>(d_parts, n_parts, d_base, rowhash, ent, words);
+    rc = check("entries");
+    if (rc != ECB_OK) return rc;
+    u64 wmax = 0, wsum = 0;
+    for (u32 k = 1; k <= CB_SHARDS; ++k) { wmax = std::max<u64>(wmax, back[CB_SHARD_WORDS * k]); wsum += back[CB_SHARD_WORDS * k + 1]; }
+    u64 E = 0, nnz_a = 0, nnz_n = 0;
+    DevBuf ecr;                                          // EC of every global row
+    if (ecr.take(std::max<u64>(R, 1) * 4)) return fail(nullptr, ECB_ERR_HIP, "combine: out of device memory");
+    u32* ec_of_row = (u32*)ecr.p;
+    CbHandle hg;
+    if (R) {
+        // 6. one table: room for every row being an EC of its own (half full at most: no growth), and a key arena in which every wave's one
+        //    reservation fits one of its 64 regions whatever the others took (arena_alloc: a region that cannot take a reservation is skipped)
+        ecb_config cfg{};
+        cfg.struct_size = sizeof(ecb_config); cfg.device = device; cfg.n_loci = n_loci; cfg.n_haplotypes = n_haps;
+        cfg.ec_capacity = 2 * R;
+        cfg.arena_capacity = std::max<u64>(1ull << 22, (u64)ARENA_REGIONS * (wmax + wsum / ARENA_REGIONS + 2));
+        ecb_handle* h = nullptr;
+        rc = ecb_create(&cfg, &h);
+        if (rc != ECB_OK) return rc;
+        hg.h = h;
+        auto hfail = [&](int code) { return fail(nullptr, code, "combine: %s", h->err.c_str()); };
+        ecb_add_counters(h, 0, R, R);                     // R "reads", all valid: the ranking's bitmap spans the rows
+        rc = ecb_table_merge_device(h, ent, R, pairs, NP);
+        if (rc != ECB_OK) return hfail(rc);
+        ecb_sizes sz{};
+        rc = ecb_finalize(h, &sz);
+        if (rc != ECB_OK) return hfail(rc);
+        E = sz.n_ecs; nnz_a = sz.nnz_a;
+        rc = ecb_export_device(h, d_out_indptr_a, d_out_indices_a, d_out_data_a, nullptr, nullptr, nullptr);
+        if (rc != ECB_OK) return hfail(rc);
+        rc = ensure_slot_ranks(h, E);
+        if (rc != ECB_OK) return hfail(rc);
+        cur = h->stream;
+        // 7. every row's EC
+        k_cb_lookup<<<nblk(R, TPB), TPB, 0, cur>>>(ent, R, pairs, h->table, h->cap - 1, h->arena, h->rank_of_slot, ec_of_row, err);
+    } else {
+        if (hipMemsetAsync(d_out_indptr_a, 0, 4, st) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "combine: memset");
+    }
+    // 8. N: (sample, EC) keys sorted, summed per key, zeros dropped, CSC
+    if (NZ) {
+        u32 *flag = S.get<u32>(NZ), *pos = S.get<u32>(NZ + 1), *keep = S.get<u32>(NZ), *opos = S.get<u32>(NZ + 1);
+        u32 *sums1 = S.get<u32>(scan_words(NZ)), *sums2 = S.get<u32>(scan_words(NZ));
+        u64 *rsum = S.get<u64>(NZ), *rkey = S.get<u64>(NZ), *okey = S.get<u64>(NZ), *tot = S.get<u64>(2);
+        SortScratch sc{S.get<u32>(rs_words(NZ)), S.get<u32>(RS_AUX_WORDS), S.get<u32>(rs_scan_blocks(NZ) + 8), words + 1};
+        if (!flag || !pos || !keep || !opos || !sums1 || !sums2 || !rsum || !rkey || !okey || !tot || !sc.hist || !sc.offs || !sc.sums)
+            return fail(nullptr, ECB_ERR_HIP, "combine: out of device memory");
+        k_cb_ntrip<<<nblk(NZ, TPB), TPB, 0, cur>>>(d_parts, n_parts, d_base, n_samples, ec_of_row, keys0, vals0, err);
+        rc = check("N check");
+        if (rc != ECB_OK) return rc;
+        u64* kk[2] = {keys0, keys1}; u32* vv[2] = {vals0, vals1};
+        int where = 0;
+        u64 bits = 0;
+        for (u64 x = ((u64)n_samples - 1) << 32 | (E ? E - 1 : 0); x; x >>= 1) bits = (bits << 1) | 1ull;
+        hipError_t e = radix_sort_pairs64(cur, kk, vv, NZ, sc, &where, bits);
+        if (e != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "combine: radix sort: %s", hipGetErrorString(e));
+        const u64* sk = kk[where]; const u32* sv = vv[where];
+        if (hipMemsetAsync(rsum, 0, NZ * 8, cur) != hipSuccess || hipMemsetAsync(tot, 0, 16, cur) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "combine: memset");
+        k_cb_heads<<<nblk(NZ, TPB), TPB, 0, cur>>>(sk, NZ, flag);
+        if (scan_launch(cur, flag, NZ, pos, sums1, tot) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "combine: scan");
+        k_cb_nsum<<<nblk(NZ, TPB), TPB, 0, cur>>>(sk, sv, flag, pos, NZ, rsum, rkey);
+        k_cb_nkeep<<<nblk(NZ, TPB), TPB, 0, cur>>>(rsum, tot, NZ, keep, err);
+        if (scan_launch(cur, keep, NZ, opos, sums2, tot + 1) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "combine: scan");
+        k_cb_nemit<<<nblk(NZ, TPB), TPB, 0, cur>>>(rsum, rkey, keep, opos, tot, NZ, (int*)d_out_indices_n, (int*)d_out_data_n, okey);
+        k_cb_nptr<<<nblk((u64)n_samples + 1, TPB), TPB, 0, cur>>>(okey, tot + 1, NZ, n_samples, (int*)d_out_indptr_n);
+        u64 t2[2] = {0, 0};
+        if ((e = hipMemcpyAsync(t2, tot, 16, hipMemcpyDeviceToHost, cur)) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "combine: copy: %s", hipGetErrorString(e));
+        rc = check("N");
+        if (rc != ECB_OK) return rc;
+        if (t2[1] > NZ) return fail(nullptr, ECB_ERR_HIP, "internal: %llu N entries from %llu", (unsigned long long)t2[1], (unsigned long long)NZ);
+        nnz_n = t2[1];
+    } else {
+        if (hipMemsetAsync(d_out_indptr_n, 0, ((u64)n_samples + 1) * 4, cur) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "combine: memset");
+        rc = check("lookup");
+        if (rc != ECB_OK) return rc;
+    }
+    out_sizes[0] = E; out_sizes[1] = nnz_a; out_sizes[2] = nnz_n;
+    return ECB_OK;
+}
+
+extern "C" int ecb_combine(int device, uint32_t n_parts, const ecb_combine_part* parts, uint32_t n_loci, uint32_t n_haps, uint32_t n_samples,
+                           int32_t* out_indptr_a, int32_t* out_indices_a, int32_t* out_data_a, int32_t* out_indptr_n, int32_t* out_indices_n,
+                           int32_t* out_data_n, uint64_t* out_sizes) {
+    if (!parts || !n_parts || !out_sizes || !out_indptr_a || !out_indptr_n) return fail(nullptr, ECB_ERR_ARG, "combine: bad argument");
+    if (device < 0 || device >= CV_MAX_DEV || hipSetDevice(device) != hipSuccess) return fail(nullptr, ECB_ERR_NO_DEVICE, "no such device");
+    std::vector<ecb_combine_part> dp(parts, parts + n_parts);
+    std::vector<DevBuf> bufs((u64)n_parts * 8);
+    u64 R = 0, NP = 0, NZ = 0;
+    for (u32 p = 0; p < n_parts; ++p) {
+        const ecb_combine_part& c = parts[p];
+        if (c.struct_size != sizeof(ecb_combine_part)) return fail(nullptr, ECB_ERR_ARG, "combine: part %u: bad struct_size", p);
+        const void* src[8] = {c.indptr_a, c.indices_a, c.data_a, c.indptr_n, c.indices_n, c.data_n, c.target_map, c.sample_map};
+        const u64 len[8] = {((u64)c.n_ecs + 1) * 4, c.nnz_a * 4, c.nnz_a * 4, ((u64)c.n_samples + 1) * 4, c.nnz_n * 4, c.nnz_n * 4, (u64)c.n_loci * 4, (u64)c.n_samples * 4};
+        const void** dst[8] = {(const void**)&dp[p].indptr_a, (const void**)&dp[p].indices_a, (const void**)&dp[p].data_a, (const void**)&dp[p].indptr_n,
+                               (const void**)&dp[p].indices_n, (const void**)&dp[p].data_n, (const void**)&dp[p].target_map, (const void**)&dp[p].sample_map};
+        if (c.nnz_a >= (1ull << 31) || c.nnz_n >= (1ull << 31)) return fail(nullptr, ECB_ERR_LIMIT, "combine: part %u exceeds the .bin format's int32 limits", p);
+        for (int k = 0; k < 8; ++k) {
+            if (!src[k]) { *dst[k] = nullptr; continue; }
+            DevBuf& b = bufs[(u64)p * 8 + k];
+            if (b.take(len[k]) || (len[k] && hipMemcpy(b.p, src[k], len[k], hipMemcpyHostToDevice) != hipSuccess))
+                return fail(nullptr, ECB_ERR_HIP, "combine: copy to the device");
+            *dst[k] = b.p;
+        }
+        R += c.n_ecs; NP += c.nnz_a; NZ += c.nnz_n;
+    }
+    DevBuf oia, oxa, oda, oin, oxn, odn;
+    if (oia.take((R + 1) * 4) || oxa.take(NP * 4) || oda.take(NP * 4) || oin.take(((u64)n_samples + 1) * 4) || oxn.take(NZ * 4) || odn.take(NZ * 4))
+        return fail(nullptr, ECB_ERR_HIP, "combine: out of device memory");
+    const int rc = ecb_combine_device(device, n_parts, dp.data(), n_loci, n_haps, n_samples, oia.p, oxa.p, oda.p, oin.p, oxn.p, odn.p, out_sizes);
+    if (rc != ECB_OK) return rc;
+    const u64 E = out_sizes[0], nnz_a = out_sizes[1], nnz_n = out_sizes[2];
+    if (hipMemcpy(out_indptr_a, oia.p, (E + 1) * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(out_indptr_n, oin.p, ((u64)n_samples + 1) * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        (nnz_a && (hipMemcpy(out_indices_a, oxa.p, nnz_a * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(out_data_a, oda.p, nnz_a * 4, hipMemcpyDeviceToHost) != hipSuccess)) ||
+        (nnz_n && (hipMemcpy(out_indices_n, oxn.p, nnz_n * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(out_data_n, odn.p, nnz_n * 4, hipMemcpyDeviceToHost) != hipSuccess)))
+        return fail(nullptr, ECB_ERR_HIP, "combine: copy from the device");
+    return ECB_OK;
+}
+
 // ---- ecb_merge: the multi-GPU merge for ONE process that drives several GPUs ----------------------------------------------
 // shards[r] holds the reads of contiguous read shard r on its own device; `root` is an empty handle (any device).  The same protocol as
 // alntools_amd/dist.py runs over RCCL with one process per GPU, here with peer copies (hipMemcpyPeerAsync: xGMI between the GPUs of a

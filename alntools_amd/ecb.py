@@ -35,7 +35,7 @@ SYMBOLS = ("ecb_abi_version", "ecb_device_count", "ecb_create", "ecb_destroy", "
            "ecb_export_ec_keys_device", "ecb_ms_local_triples_device", "ecb_ms_adopt_triples_device", "ecb_counters", "ecb_add_counters", "ecb_profile",
            "ecb_profile_read", "ecb_profile_kernel", "ecb_csr_to_hapcsc_device", "ecb_hapcsc_to_csr_device", "ecb_release_scratch",
            "ecb_csr_to_hapcsc", "ecb_hapcsc_to_csr", "ecb_merge", "ecb_push_device_tiled", "ecb_verify_device_tiled",
-           "ecb_apply_mask_device", "ecb_apply_mask")
+           "ecb_apply_mask_device", "ecb_apply_mask", "ecb_combine_device", "ecb_combine")
 ABI_VERSION = 4            # include/ecb.h: ECB_ABI_VERSION
 
 
@@ -61,6 +61,13 @@ class Sizes(C.Structure):
 class MsSizes(C.Structure):
     _fields_ = [("n_cells_seen", C.c_uint64), ("n_cells_kept", C.c_uint64), ("n_ecs_kept", C.c_uint64),
                 ("nnz_a", C.c_uint64), ("nnz_n", C.c_uint64)]
+
+
+class CombinePart(C.Structure):
+    """``ecb_combine_part``: one input ``.bin`` of ``ecb_combine`` / ``ecb_combine_device``."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_ecs", C.c_uint32), ("n_samples", C.c_uint32), ("n_loci", C.c_uint32),
+                ("nnz_a", C.c_uint64), ("nnz_n", C.c_uint64)] + [(n, C.c_void_p) for n in (
+                    "indptr_a", "indices_a", "data_a", "indptr_n", "indices_n", "data_n", "target_map", "sample_map")]
 
 
 _lib = None
@@ -145,6 +152,9 @@ def load():
     if not ab or hasattr(lib, "ecb_apply_mask"):
         for f in (lib.ecb_apply_mask_device, lib.ecb_apply_mask):
             f.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64] + [vp] * 7 + [C.POINTER(u64)]
+    if not ab or hasattr(lib, "ecb_combine"):
+        for f in (lib.ecb_combine_device, lib.ecb_combine):
+            f.argtypes = [C.c_int, C.c_uint32, C.POINTER(CombinePart), C.c_uint32, C.c_uint32, C.c_uint32] + [vp] * 6 + [C.POINTER(u64)]
     lib.ecb_csr_to_hapcsc_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.POINTER(u64)]
     lib.ecb_hapcsc_to_csr_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, u64, vp, vp, vp, C.POINTER(u64)]
     _lib = lib
@@ -293,6 +303,60 @@ def apply_mask(indptr, indices, data, mask, n_haps, device=0):
     if rc != 0:
         raise EcbError(rc, (lib.ecb_last_error(None) or b"").decode())
     return oip, oix[:kept.value], oda[:kept.value]
+
+
+def combine(parts, n_loci, n_haps, n_samples, device=0):
+    """ecmerge on the GPU: several ``.bin`` files' A and N as one (``ecb_combine``).  ``parts``: one dict per input with ``indptrA,
+    indicesA, dataA, indptrN, indicesN, dataN`` (CSR A and CSC N as the file stores them), ``n_loci`` (the file's targets),
+    ``target_map`` (the file's column -> merged column, or None: the same numbering) and ``sample_map`` (the file's sample -> output
+    sample).  Rows with equal keys become one EC, numbered by first appearance; counts add per (EC, sample), zero sums are dropped.
+    numpy arrays go through ``ecb_combine`` (host arrays, no PyTorch), CUDA tensors through ``ecb_combine_device`` (``device`` is then
+    the tensors' own).  Returns (indptrA, indicesA, dataA, indptrN, indicesN, dataN), int32, of the same kind as the input.  Malformed
+    input raises :class:`EcbError` (``ECB_ERR_CONTRACT``), sizes beyond the format's limits ``ECB_ERR_LIMIT``."""
+    lib = load()
+    keys = ("indptrA", "indicesA", "dataA", "indptrN", "indicesN", "dataN")
+    on_device = hasattr(parts[0]["indptrA"], "data_ptr") if parts else False
+    if on_device:
+        import torch
+        dev = parts[0]["indptrA"].device
+
+        def arr(a, dt):
+            return None if a is None else torch.as_tensor(a).to(device=dev, dtype=dt).contiguous()
+
+        def empty(n):
+            return torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        ptr, entry, device = _dev_ptr, lib.ecb_combine_device, dev.index or 0
+    else:
+        def arr(a, dt):                             # (a map's values are below 2^31: int32 and uint32 are the same bytes)
+            return None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+
+        def empty(n):
+            return np.empty(max(n, 1), dtype=np.int32)
+        ptr, entry = _ptr, lib.ecb_combine
+    i32 = torch.int32 if on_device else None
+    held, cp = [], (CombinePart * max(len(parts), 1))()
+    R = NP = NZ = 0
+    for k, p in enumerate(parts):
+        a = [arr(p[n], i32) for n in keys]
+        tm = arr(p.get("target_map"), i32)
+        sm = arr(p.get("sample_map"), i32)
+        held += a + [tm, sm]
+        E, S = len(a[0]) - 1, len(a[3]) - 1
+        if len(a[1]) != len(a[2]) or len(a[4]) != len(a[5]):
+            raise ValueError("part %d: indices and data differ in length" % k)
+        c = cp[k]
+        c.struct_size, c.n_ecs, c.n_samples, c.n_loci = C.sizeof(CombinePart), E, S, int(p["n_loci"])
+        c.nnz_a, c.nnz_n = len(a[1]), len(a[4])
+        for n, x in zip(("indptr_a", "indices_a", "data_a", "indptr_n", "indices_n", "data_n", "target_map", "sample_map"), a + [tm, sm]):
+            setattr(c, n, None if x is None else ptr(x).value)
+        R, NP, NZ = R + E, NP + len(a[1]), NZ + len(a[4])
+    out = [empty(R + 1), empty(NP), empty(NP), empty(n_samples + 1), empty(NZ), empty(NZ)]
+    sizes = (C.c_uint64 * 3)()
+    rc = entry(device, len(parts), cp, n_loci, n_haps, n_samples, *[ptr(o) for o in out], sizes)
+    if rc != 0:
+        raise EcbError(rc, (lib.ecb_last_error(None) or b"").decode())
+    E, nnz_a, nnz_n = (int(x) for x in sizes)
+    return out[0][:E + 1], out[1][:nnz_a], out[2][:nnz_a], out[3], out[4][:nnz_n], out[5][:nnz_n]
 
 
 class EcBuilder(object):

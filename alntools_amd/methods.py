@@ -1,5 +1,5 @@
 # -*- coding: utf-8 -*-
-"""Same driver functions as the reference's ``alntools/methods.py:32-53, 205-210``, and ``apply_genotypes`` for the hot path."""
+"""Same driver functions as the reference's ``alntools/methods.py:32-53, 205-210``, ``apply_genotypes`` and ``ecmerge`` for the hot path."""
 from __future__ import annotations
 
 from . import bam_utils, bin_utils
@@ -49,3 +49,7 @@ def emase2ec(emase_file, ec_file):
 
 def apply_genotypes(ec_file, gt_file, grp_file, out_file):
     bin_utils.apply_genotypes(ec_file, gt_file, grp_file, out_file)
+
+
+def ecmerge(input_files, out_file):
+    bin_utils.ecmerge(input_files, out_file)

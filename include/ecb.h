@@ -306,6 +306,36 @@ int ecb_apply_mask_device(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t 
 int ecb_apply_mask(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, uint64_t nnz, const int32_t* indptr, const int32_t* indices,
                    const int32_t* data, const uint32_t* mask, int32_t* out_indptr, int32_t* out_indices, int32_t* out_data, uint64_t* kept);
 
+/* ecmerge (ABI 4, additive): several .bin files' A and N combined into one.  Every row of every part is an EC key, the set of its
+ * (merged column, haplotype mask) pairs; rows with equal keys, in one part or several, are one EC (all empty rows share the empty key);
+ * ECs are numbered by first appearance over the parts in order and each part's rows in order.  N: counts summed per (EC, output sample),
+ * zero sums dropped.  Out: CSR A with columns ascending, CSC N (n_samples + 1 column pointers, EC indices ascending within a column).
+ * A part, as the .bin stores it: indptr_a n_ecs + 1, indices_a / data_a nnz_a (columns below n_loci, strictly ascending within a row,
+ * masks non-zero and below 2^n_haps); indptr_n n_samples + 1, indices_n / data_n nnz_n (EC indices below n_ecs, counts >= 0).
+ * target_map: n_loci values, the part's column -> merged column (below the call's n_loci; one-to-one); NULL = the same numbering (the
+ * part's n_loci must then equal the call's).  sample_map: n_samples values, the part's sample -> output sample (below the call's n_samples).
+ * Malformed input is refused with ECB_ERR_CONTRACT (and nothing else happens); sums of the parts' n_ecs or nnz_a beyond int32, of their
+ * nnz_n beyond 2^30 (of their nnz_a beyond 2^30 when a target map asks for a re-sort), or a merged count beyond int32: ECB_ERR_LIMIT.
+ * The outputs are bounded by the sums over the parts: out_indptr_a sum(n_ecs) + 1, out_indices_a / out_data_a sum(nnz_a),
+ * out_indptr_n n_samples + 1, out_indices_n / out_data_n sum(nnz_n).  out_sizes = {n_ecs, nnz_a, nnz_n} of the result.
+ * ecb_combine_device: every array of the parts and the outputs in device memory (outputs not overlapping the inputs);
+ * ecb_combine: the same on HOST arrays (the library allocates and frees its own device buffers). */
+typedef struct ecb_combine_part {
+    uint32_t struct_size;             /* sizeof(ecb_combine_part) */
+    uint32_t n_ecs, n_samples, n_loci;
+    uint64_t nnz_a, nnz_n;
+    const int32_t *indptr_a, *indices_a, *data_a;
+    const int32_t *indptr_n, *indices_n, *data_n;
+    const uint32_t* target_map;
+    const uint32_t* sample_map;
+} ecb_combine_part;
+int ecb_combine_device(int device, uint32_t n_parts, const ecb_combine_part* parts, uint32_t n_loci, uint32_t n_haps, uint32_t n_samples,
+                       void* d_out_indptr_a, void* d_out_indices_a, void* d_out_data_a, void* d_out_indptr_n, void* d_out_indices_n,
+                       void* d_out_data_n, uint64_t* out_sizes);
+int ecb_combine(int device, uint32_t n_parts, const ecb_combine_part* parts, uint32_t n_loci, uint32_t n_haps, uint32_t n_samples,
+                int32_t* out_indptr_a, int32_t* out_indices_a, int32_t* out_data_a, int32_t* out_indptr_n, int32_t* out_indices_n,
+                int32_t* out_data_n, uint64_t* out_sizes);
+
 /* Measurement: HIP-event time of the record-stream kernel on the handle's own stream; ecb_profile_kernel (ABI 4): the name of the
  * kernel the last batch launched, as rocprofv3 prints it (the stream kernel is compiled more than once; the library picks per batch). */
 int ecb_profile(ecb_handle* h, int enable);
