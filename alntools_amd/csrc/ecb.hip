@@ -1784,8 +1784,9 @@ __global__ __launch_bounds__(CVU_TPB) void k_cvu_union(const int* cscptr, const 
         }
         return;
     }
-    u32 tsz = 64;                                            // slots in use: a power of two, at least 4/3 of the row indices
-    while (tsz < tot + tot / 3u + 1u) tsz <<= 1;
+    u32 tsz = 64;                                            // slots in use: a power of two, at least 4/3 of the row indices, at most the table
+    while (tsz < CVU_TSZ && tsz < tot + tot / 3u + 1u) tsz <<= 1;      // (a piece of exactly CVU_MAX asks for 4 097: all 4 096 it gets, 3/4 full)
+    static_assert(CVU_MAX < CVU_TSZ && (CVU_TSZ & (CVU_TSZ - 1u)) == 0, "a free slot is always found");
     // all of a thread's row indices are fetched before the first is inserted (their loads overlap), haplotype after haplotype in one index space
     u32 ev[CVU_K], hv[CVU_K];
 #pragma unroll
