@@ -37,6 +37,7 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -2366,6 +2367,71 @@ __global__ void k_msf_rows(const u32* indptr, const int* indices, const int* dat
     for (u32 i = a; i < b; ++i) { indices2[o + (i - a)] = indices[i]; data2[o + (i - a)] = data[i]; }
 }
 
+// ---- device memory: one owner per buffer ------------------------------------------------------------------------------------------------
+// A move-only buffer: its pointer, its size in bytes and the device it was allocated on, where it is freed when it goes.  It stands in for
+// a T* where one is used (kernel arguments, StreamCold, pointer arithmetic): only the ownership lives here.  Three ways to fill it:
+//   alloc  -- fresh: exactly max(n, at_least) bytes;
+//   regrow -- kept while it holds `need` bytes, else freed and need + slack bytes taken in its place (the contents are not kept);
+//   grow   -- a new n-byte buffer, filled with the byte `fill` (-1: not filled), the first `keep` bytes of the old one copied over on `st`
+//             and waited for, then the old one freed (no copy and no wait when there is none).  A failing step leaves the old one in place.
+// alloc and regrow free what the buffer held before they allocate.
+template <class T = void>
+struct DevBuf {
+    void* p = nullptr;
+    u64 bytes = 0;
+    int dev = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes), dev(o.dev) { o.p = nullptr; o.bytes = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) { reset(); p = o.p; bytes = o.bytes; dev = o.dev; o.p = nullptr; o.bytes = 0; }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    operator T*() const { return static_cast<T*>(p); }
+    T* operator->() const { return static_cast<T*>(p); }
+    template <class U> U* as() const { return static_cast<U*>(p); }
+    hipError_t reset() {
+        hipError_t e = hipSuccess;
+        if (p) { hipSetDevice(dev); e = hipFree(p); }
+        p = nullptr; bytes = 0;
+        return e;
+    }
+    hipError_t alloc(u64 n, u64 at_least = 0) {
+        reset();
+        n = std::max(n, at_least);
+        hipError_t e = hipGetDevice(&dev);
+        if (e == hipSuccess) e = hipMalloc(&p, n);
+        if (e != hipSuccess) { p = nullptr; return e; }
+        bytes = n;
+        return hipSuccess;
+    }
+    hipError_t regrow(u64 need, u64 slack) { return bytes >= need ? hipSuccess : alloc(need + slack); }
+    hipError_t grow(u64 n, int fill, u64 keep, hipStream_t st) {
+        DevBuf q;
+        hipError_t e = q.alloc(n);
+        if (e == hipSuccess && fill >= 0) e = hipMemsetAsync(q.p, fill, n, st);
+        if (e == hipSuccess && p) {
+            e = hipMemcpyAsync(q.p, p, keep, hipMemcpyDeviceToDevice, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+        }
+        if (e != hipSuccess) return e;
+        e = reset();
+        *this = std::move(q);
+        return e;
+    }
+};
+// pinned host memory, freed with its owner
+struct HostFree { void operator()(void* q) const { hipHostFree(q); } };
+template <class T> using Pinned = std::unique_ptr<T, HostFree>;
+template <class T> hipError_t pin(Pinned<T>& out) {
+    void* q = nullptr;
+    const hipError_t e = hipHostMalloc(&q, sizeof(T), hipHostMallocDefault);
+    out.reset(static_cast<T*>(q));
+    return e;
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -2378,7 +2444,7 @@ struct ecb_handle {
     std::string err;
     bool finalized = false;
     bool counted = false;             // Slot::count / first_inv hold the reads pushed so far (k_count ran)
-    u64* wave_arena = nullptr; u64 wave_arena_n = 0;   // see StreamArgs::wave_arena
+    u64 wave_arena_n = 0;             // see StreamArgs::wave_arena
     bool scatter_attr_set = false, count_attr_set = false;
     bool list_from_counts = false;             // finalize: k_count_bins listed the occupied slots (no k_compact pass)
     bool assembled = false;                    // the result was put together from per-range results (ecb_assemble_ranges_device)
@@ -2392,23 +2458,17 @@ struct ecb_handle {
     bool ctr_synced = false;          // hctr is what the device holds (no kernel that counts has been queued since the last read-back)
     bool adopted = false;             // the table holds adopted entries in consecutive slots (no hashing): finalize / export only
 
-    Slot* table = nullptr; u64 cap = 0;
-    uint2* arena = nullptr; u64 arena_cap = 0;
-    Counters* ctr = nullptr;
+    u64 cap = 0, arena_cap = 0;       // slots of table, pairs of arena
     Counters hctr{};                  // last read-back
-    Counters* pin_ctr = nullptr;      // pinned staging for clear_counters
     struct PinOut { Counters c; u64 tot[8]; };
-    PinOut* pin_out = nullptr;        // ... and where the device's counters and finalize's totals land (a copy into pageable memory is staged by the runtime, behind a wait of its own)
-    StreamCold *d_cold = nullptr, *pin_cold = nullptr;   // k_stream's rarely used arguments (device copy, pinned staging)
-    u32* read_slot = nullptr; u64 read_slot_cap = 0;
-    u32* meta = nullptr; u64 meta_cap = 0, meta_hi = 0;   // multisample: cell | file << 22 per read
+    u64 read_slot_cap = 0;
+    u64 meta_cap = 0, meta_hi = 0;    // multisample: cell | file << 22 per read
     u64 n_triples = 0; u64* ms_okey = nullptr; u32 *ms_ofirst = nullptr, *ms_ostart = nullptr, *ms_ocount = nullptr;
     bool ms_adopted = false;          // the triples came from ecb_ms_adopt_triples_device (multi-GPU)
     // ecb_ms_filter's results (device): kept cells in sample order, rows of A of the kept ECs, CSC N
     bool ms_filtered = false; ecb_ms_sizes msf{};
     u32* f_cells = nullptr; int *f_ipa = nullptr, *f_ixa = nullptr, *f_daa = nullptr, *f_ipn = nullptr, *f_ixn = nullptr, *f_dan = nullptr;
-    int2* rng = nullptr;                       // ECB_F_RANGES: {min, max} of reference_start per (locus, haplotype)
-    u64* queue = nullptr; u64 queue_cap = 0;
+    u64 queue_cap = 0;
     u64 n_ecs() const { return hctr.n_ecs; }
     u32 prev_rid = 0xFFFFFFFFu;       // read_id of the last record pushed so far
     u64 n_reads = 0;
@@ -2417,8 +2477,8 @@ struct ecb_handle {
     u64 extra_all = 0, extra_valid = 0, extra_reads = 0;   // counters merged in from other ranks
     u64 n_mismatch = 0;               // ECB_F_VERIFY: reads the exactness pass found in a wrong EC, over all pushes
 
-    // host-pointer staging
-    u32 *st_rid = nullptr, *st_loc = nullptr, *st_hf = nullptr; int* st_pos = nullptr; u64 st_cap = 0;
+    // host-pointer staging (the streams behind st_rid, in its allocation)
+    u32 *st_loc = nullptr, *st_hf = nullptr; int* st_pos = nullptr; u64 st_cap = 0;
     std::vector<u32> c_rid, c_loc, c_hf; std::vector<int> c_pos;   // open read carried between pushes
 
     // results
@@ -2427,18 +2487,39 @@ struct ecb_handle {
     int *indices = nullptr, *data = nullptr, *counts = nullptr;
     ecb_sizes sizes{};
 
-    // device scratch reused across calls (grown on demand, freed at destroy)
+    // device scratch reused across calls (grown on demand: POOL)
     enum { P_RESUME, P_SUMS, P_HIST, P_OFFS, P_PAIRS, P_CNT, P_PARTS, P_STARTS, P_WORK, P_LIST, P_BITMAP, P_WPOP, P_WPREFIX, P_ROWLEN, P_ORDER,
            P_WCOUNTS, P_RANK, P_INDPTR, P_COUNTS, P_INDICES, P_DATA, P_MS_KEYS, P_MS_KEYS2, P_MS_VALS, P_MS_VALS2, P_MS_TMP,
            P_MS_FLAG, P_MS_POS, P_MS_OKEY, P_MS_OFIRST, P_MS_OSTART, P_MS_X, P_MS_OCOUNT, P_MS_GRANK, P_MS_CIN, P_MS_FIN, P_LISTFN,
            P_REMAP, P_TOTALS, P_SLOW_LEN, P_SLOW_OFF, P_SLOW_NRE, P_SLOW_REQ, P_SLOW_REQ2, P_QCOMPACT, P_SLOW_KEY, P_SLOW_MASK, P_BIG, P_RS_HIST, P_RS_OFFS, P_RS_SUMS,
            P_F_CELLS, P_F_IPA, P_F_IXA, P_F_DAA, P_F_IPN, P_F_IXN, P_F_DAN, P_EXPORT, P_N };
-    void* pool[P_N] = {}; u64 pool_bytes[P_N] = {};
 
     // profiling
     bool prof = false; double prof_ms = 0; u64 prof_launches = 0, prof_records = 0;
     const char* last_kernel = "";     // which compilation of the stream kernel the last batch launched (ecb_profile_kernel)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+
+    // The memory the handle owns, freed when it is deleted, after the stream (members go last to first: the table first, the staging last)
+    DevBuf<u32> st_rid;                        // one allocation for all host-pointer staging streams (ensure_staging)
+    DevBuf<> pool[P_N];
+    DevBuf<StreamCold> d_cold;                 // k_stream's rarely used arguments (device copy; pin_cold is its pinned staging)
+    Pinned<StreamCold> pin_cold;
+    Pinned<PinOut> pin_out;                    // where the device's counters and finalize's totals land (a copy into pageable memory is staged by the runtime, behind a wait of its own)
+    Pinned<Counters> pin_ctr;                  // pinned staging for clear_counters
+    DevBuf<u64> wave_arena;                    // two words per wave, wave_arena_n waves
+    DevBuf<u64> queue;                         // deferred reads (queue_cap of them)
+    DevBuf<int2> rng;                          // ECB_F_RANGES: {min, max} of reference_start per (locus, haplotype)
+    DevBuf<u32> meta;                          // meta_cap entries
+    DevBuf<u32> read_slot;                     // read_slot_cap entries
+    DevBuf<Counters> ctr;
+    DevBuf<uint2> arena;
+    DevBuf<Slot> table;
+
+    ~ecb_handle() {
+        if (ev0) hipEventDestroy(ev0);
+        if (ev1) hipEventDestroy(ev1);
+        if (stream) hipStreamDestroy(stream);
+    }
 };
 
 namespace {
@@ -2457,25 +2538,16 @@ int fail(ecb_handle* h, int code, const char* fmt, ...) {
 u64 next_pow2(u64 x) { u64 p = 1; while (p < x) p <<= 1; return p; }
 inline unsigned nblk(u64 n, unsigned per) { return (unsigned)((n + per - 1) / per); }
 
-template <class T>
-int pool_get(ecb_handle* h, int id, u64 count, T** out) {
-    const u64 need = std::max<u64>(count, 1) * sizeof(T);
-    if (h->pool_bytes[id] < need) {
-        if (h->pool[id]) hipFree(h->pool[id]);
-        h->pool[id] = nullptr; h->pool_bytes[id] = 0;
-        const u64 take = need + need / 4;
-        HIPCHK(h, hipMalloc(&h->pool[id], take));
-        h->pool_bytes[id] = take;
-    }
-    *out = reinterpret_cast<T*>(h->pool[id]);
-    return ECB_OK;
+// ptr = the handle's scratch buffer `id`, holding at least max(count, 1) of what ptr points to (regrown with a quarter more)
+#define POOL(h, id, ptr, count) do { const u64 need_ = std::max<u64>(count, 1) * sizeof(*(ptr)); \
+    HIPCHK(h, h->pool[ecb_handle::id].regrow(need_, need_ / 4)); \
+    (ptr) = h->pool[ecb_handle::id].as<std::remove_reference_t<decltype(*(ptr))>>(); } while (0)
+// one call's scratch: a fresh buffer of max(n, 1) T's that lives as long as `keep` (nullptr when it cannot be had: see missing)
+template <class T> T* fresh(std::vector<DevBuf<>>& keep, u64 n) {
+    keep.emplace_back();
+    return keep.back().alloc(std::max<u64>(n, 1) * sizeof(T)) == hipSuccess ? keep.back().as<T>() : nullptr;
 }
-struct Scratch {                       // frees what it allocated
-    std::vector<void*> p;
-    template <class T> T* get(u64 n) { void* q = nullptr; if (hipMalloc(&q, std::max<u64>(n, 1) * sizeof(T)) != hipSuccess) return nullptr; p.push_back(q); return (T*)q; }
-    ~Scratch() { for (void* q : p) hipFree(q); }
-};
-#define POOL(h, id, ptr, count) do { int rc_ = pool_get(h, ecb_handle::id, count, &(ptr)); if (rc_ != ECB_OK) return rc_; } while (0)
+bool missing(const std::vector<DevBuf<>>& keep) { return std::any_of(keep.begin(), keep.end(), [](const DevBuf<>& b) { return !b.p; }); }
 
 // zero the device counters and point every arena region's cursor at its first pair
 int clear_counters(ecb_handle* h) {
@@ -2486,7 +2558,7 @@ int clear_counters(ecb_handle* h) {
     h->hctr = c;
     if (h->pin_ctr) {                               // pinned staging: queued behind the stream's work, no wait (rewritten only by the next reset,
         *h->pin_ctr = c;                            //  which comes after the waits of a push and a finalize)
-        HIPCHK(h, hipMemcpyAsync(h->ctr, h->pin_ctr, sizeof(Counters), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->ctr, h->pin_ctr.get(), sizeof(Counters), hipMemcpyHostToDevice, h->stream));
     } else {
         HIPCHK(h, hipMemcpyAsync(h->ctr, &h->hctr, sizeof(Counters), hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2517,11 +2589,11 @@ int sync_counters(ecb_handle* h) {
 }
 
 int grow_table(ecb_handle* h, u64 new_cap) {
-    Slot* nt = nullptr;
+    DevBuf<Slot> nt;
     u32* remap = nullptr;
     if (new_cap > (1ull << 32)) return fail(h, ECB_ERR_LIMIT, "EC table beyond 2^32 slots");
     POOL(h, P_REMAP, remap, h->cap);
-    HIPCHK(h, hipMalloc(&nt, new_cap * sizeof(Slot)));
+    HIPCHK(h, nt.alloc(new_cap * sizeof(Slot)));
     hipError_t e = hipMemsetAsync(nt, 0, new_cap * sizeof(Slot), h->stream);
     // (slots the old table did not hold map to PENDING: read_slot may hold slot ids of an EARLIER stream beyond the reads processed so far --
     //  ecb_reset leaves them, ecb_hint_reads makes reads_hi run ahead of the stream -- and what such an entry maps to must not be pool garbage)
@@ -2532,9 +2604,10 @@ int grow_table(ecb_handle* h, u64 new_cap) {
             k_remap_read_slot<<<2048, TPB, 0, h->stream>>>(h->read_slot, h->reads_hi, remap);
         e = hipStreamSynchronize(h->stream);
     }
-    if (e != hipSuccess) { hipFree(nt); return fail(h, ECB_ERR_HIP, "grow_table: %s", hipGetErrorString(e)); }
-    HIPCHK(h, hipFree(h->table));
-    h->table = nt; h->cap = new_cap; h->list_counted = false;     // (slot ids changed)
+    if (e != hipSuccess) return fail(h, ECB_ERR_HIP, "grow_table: %s", hipGetErrorString(e));
+    HIPCHK(h, h->table.reset());
+    h->table = std::move(nt);
+    h->cap = new_cap; h->list_counted = false;     // (slot ids changed)
     return ECB_OK;
 }
 
@@ -2542,15 +2615,17 @@ int ensure_read_slot(ecb_handle* h, u64 need) {
     if (need <= h->read_slot_cap) return ECB_OK;
     u64 nc = std::max<u64>(need, h->read_slot_cap * 2);
     nc = std::max<u64>(nc, 1024);
-    u32* p = nullptr;
-    HIPCHK(h, hipMalloc(&p, nc * sizeof(u32)));
-    HIPCHK(h, hipMemsetAsync(p, 0xFF, nc * sizeof(u32), h->stream));
-    if (h->read_slot) {
-        HIPCHK(h, hipMemcpyAsync(p, h->read_slot, h->n_reads * sizeof(u32), hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, hipFree(h->read_slot));
-    }
-    h->read_slot = p; h->read_slot_cap = nc;
+    HIPCHK(h, h->read_slot.grow(nc * sizeof(u32), 0xFF, h->n_reads * sizeof(u32), h->stream));
+    h->read_slot_cap = nc;
+    return ECB_OK;
+}
+
+// multisample: room in meta for reads [0, need), what is set so far kept
+int ensure_meta(ecb_handle* h, u64 need) {
+    if (need <= h->meta_cap) return ECB_OK;
+    const u64 nc = std::max<u64>(need, h->meta_cap * 2);
+    HIPCHK(h, h->meta.grow(nc * sizeof(u32), -1, h->meta_hi * sizeof(u32), h->stream));
+    h->meta_cap = nc;
     return ECB_OK;
 }
 
@@ -2572,11 +2647,13 @@ int run_slow(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* d_hf,
         u64 tot = 0;
         for (u64 i = 0; i < nq; ++i) { off[i] = tot; tot += 2 * len[i]; }
         u32 *sk = nullptr, *sm = nullptr;
-        const u64 had_k = h->pool_bytes[ecb_handle::P_SLOW_KEY], had_m = h->pool_bytes[ecb_handle::P_SLOW_MASK];
+        const DevBuf<>& bk = h->pool[ecb_handle::P_SLOW_KEY];
+        const DevBuf<>& bm = h->pool[ecb_handle::P_SLOW_MASK];
+        const u64 had_k = bk.bytes, had_m = bm.bytes;
         POOL(h, P_SLOW_KEY, sk, tot); POOL(h, P_SLOW_MASK, sm, tot);
         // k_slow leaves its scratch zeroed: only a fresh (re)allocation needs clearing
-        if (h->pool_bytes[ecb_handle::P_SLOW_KEY] != had_k) HIPCHK(h, hipMemsetAsync(sk, 0, h->pool_bytes[ecb_handle::P_SLOW_KEY], h->stream));
-        if (h->pool_bytes[ecb_handle::P_SLOW_MASK] != had_m) HIPCHK(h, hipMemsetAsync(sm, 0, h->pool_bytes[ecb_handle::P_SLOW_MASK], h->stream));
+        if (bk.bytes != had_k) HIPCHK(h, hipMemsetAsync(sk, 0, bk.bytes, h->stream));
+        if (bm.bytes != had_m) HIPCHK(h, hipMemsetAsync(sm, 0, bm.bytes, h->stream));
         HIPCHK(h, hipMemcpyAsync(d_off, off.data(), nq * sizeof(u64), hipMemcpyHostToDevice, h->stream));
         SlowArgs a{d_rid, d_loc, d_hf, d_q, d_len, d_off, sk, sm, h->cfg.n_loci, h->cfg.n_haplotypes,
                    h->table, h->cap - 1, h->arena, h->arena_cap, h->ctr, h->read_slot, h->reads_hi, nre_buf, d_nre, verify ? 1u : 0u};
@@ -2633,9 +2710,8 @@ int plan_stream(ecb_handle* h, u64 n, StreamPlan* P, bool ranges = false, bool s
     // with more than CMAX loci takes more than CMAX records
     const u64 need_q = P->pwaves * (u64)(WT + 1) + n / 64 + 16;      // (64: the smaller of the two kernels' carry limits, k_stream.inc)
     if (h->queue_cap < need_q) {
-        if (h->queue) hipFree(h->queue);
-        h->queue = nullptr; h->queue_cap = 0;
-        HIPCHK(h, hipMalloc(&h->queue, need_q * sizeof(u64)));
+        h->queue_cap = 0;
+        HIPCHK(h, h->queue.alloc(need_q * sizeof(u64)));
         h->queue_cap = need_q;
     }
     return ECB_OK;
@@ -2671,7 +2747,7 @@ int verify_batch(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* d
     HIPCHK(h, hipMemsetAsync(&h->ctr->n_mismatch, 0, sizeof(u64), h->stream));
     *h->pin_cold = StreamCold{h->arena, h->arena_cap, h->queue, h->queue_cap, d_resume, d_wcounts, nullptr, nullptr, P.chunk, prev_rid,
                               nullptr, nullptr, 0u, 0u};
-    HIPCHK(h, hipMemcpyAsync(h->d_cold, h->pin_cold, sizeof(StreamCold), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_cold, h->pin_cold.get(), sizeof(StreamCold), hipMemcpyHostToDevice, h->stream));
     StreamArgs a{d_rid, d_loc, d_hf, n, h->table, h->cap - 1, h->ctr, h->read_slot, h->reads_hi, h->d_cold, 0u};
     ks_std::k_stream<true><<<(unsigned)P.blocks, TPB, 0, h->stream>>>(a);
     k_sum_counts<<<1, 1024, 0, h->stream>>>(d_wcounts, P.pwaves, h->ctr, 1u, 0ull, h->queue_cap);
@@ -2728,15 +2804,8 @@ int process_batch(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* 
     u32* d_wcounts = nullptr;
     POOL(h, P_WCOUNTS, d_wcounts, 3 * pwaves);
     if (h->wave_arena_n < pwaves) {                 // (only ever grows to the resident wave count; zero = nothing reserved)
-        u64* wa = nullptr;
-        HIPCHK(h, hipMalloc(&wa, 2 * pwaves * sizeof(u64)));
-        HIPCHK(h, hipMemsetAsync(wa, 0, 2 * pwaves * sizeof(u64), h->stream));
-        if (h->wave_arena) {
-            HIPCHK(h, hipMemcpyAsync(wa, h->wave_arena, 2 * h->wave_arena_n * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            hipFree(h->wave_arena);
-        }
-        h->wave_arena = wa; h->wave_arena_n = pwaves;
+        HIPCHK(h, h->wave_arena.grow(2 * pwaves * sizeof(u64), 0, 2 * h->wave_arena_n * sizeof(u64), h->stream));
+        h->wave_arena_n = pwaves;
     }
     StreamCold cold{h->arena, h->arena_cap, h->queue, h->queue_cap, d_resume, d_wcounts, h->wave_arena, nullptr, chunk, h->prev_rid,
                     d_pos, h->rng, h->cfg.n_loci, h->cfg.n_haplotypes};
@@ -2745,7 +2814,7 @@ int process_batch(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* 
     HIPCHK(h, hipMemset(cold.timing, 0, 8 * sizeof(u64)));
 #endif
     *h->pin_cold = cold;      // (pinned: rewritten by the next batch, which starts after this one's host wait)
-    HIPCHK(h, hipMemcpyAsync(h->d_cold, h->pin_cold, sizeof(StreamCold), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_cold, h->pin_cold.get(), sizeof(StreamCold), hipMemcpyHostToDevice, h->stream));
     StreamArgs a{d_rid, d_loc, d_hf, n, h->table, h->cap - 1, h->ctr, h->read_slot, h->reads_hi, h->d_cold,
                  getenv("ECB_ABLATE") ? (u32)atoi(getenv("ECB_ABLATE")) : 0u, d_pos, h->rng};
     h->ctr_synced = false;
@@ -2821,12 +2890,12 @@ int ensure_staging(ecb_handle* h, u64 need) {
     // one allocation for the three (four) staging streams, each on a 2 MiB boundary within it.  (Staging in whole tiles -- what
     // ecb_push_device_tiled takes -- was built and measured: the pitched host-to-device copies cost the PCIe-inclusive rate 8 %, and the
     // tile layout did not take the placement dependence out of the kernel after all: DESIGN.md section 6.)
-    if (h->st_rid) hipFree(h->st_rid);
-    h->st_rid = h->st_loc = h->st_hf = nullptr; h->st_pos = nullptr;
-    h->st_cap = std::max<u64>(need, h->cfg.max_batch_records);
-    const u64 stride = (h->st_cap * sizeof(u32) + (2ull << 20) - 1) / (2ull << 20) * (2ull << 20) / sizeof(u32);
+    h->st_loc = h->st_hf = nullptr; h->st_pos = nullptr; h->st_cap = 0;
+    const u64 cap = std::max<u64>(need, h->cfg.max_batch_records);
+    const u64 stride = (cap * sizeof(u32) + (2ull << 20) - 1) / (2ull << 20) * (2ull << 20) / sizeof(u32);
     const bool rg = (h->cfg.flags & ECB_F_RANGES) != 0;
-    HIPCHK(h, hipMalloc(&h->st_rid, (rg ? 4 : 3) * stride * sizeof(u32)));
+    HIPCHK(h, h->st_rid.alloc((rg ? 4 : 3) * stride * sizeof(u32)));
+    h->st_cap = cap;
     h->st_loc = h->st_rid + stride; h->st_hf = h->st_rid + 2 * stride;
     if (rg) h->st_pos = reinterpret_cast<int*>(h->st_rid + 3 * stride);
     return ECB_OK;
@@ -2926,13 +2995,13 @@ hipError_t radix_sort_pairs64(hipStream_t st, u64* k[2], u32* v[2], u64 n, const
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
     return gave_up ? hipErrorUnknown : hipSuccess;
 }
-int handle_sort(ecb_handle* h, u64* k[2], u32* v[2], u64 n, int* where) {
+int handle_sort(ecb_handle* h, u64* k[2], u32* v[2], u64 n, int* where, u64 bit_mask = ~0ull) {
     SortScratch sc{};
     u64* tot = nullptr;
     POOL(h, P_RS_HIST, sc.hist, rs_words(n)); POOL(h, P_RS_OFFS, sc.offs, RS_AUX_WORDS);
     POOL(h, P_RS_SUMS, sc.sums, rs_scan_blocks(n) + 8); POOL(h, P_TOTALS, tot, 8);
     sc.d_word = tot + 6;
-    const hipError_t e = radix_sort_pairs64(h->stream, k, v, n, sc, where);
+    const hipError_t e = radix_sort_pairs64(h->stream, k, v, n, sc, where, bit_mask);
     if (e != hipSuccess) return fail(h, ECB_ERR_HIP, "radix sort: %s", hipGetErrorString(e));
     return ECB_OK;
 }
@@ -3147,7 +3216,7 @@ int ecb_create(const ecb_config* cfg, ecb_handle** out) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, ECB_ERR_NO_DEVICE, "no HIP device: libecb has no CPU path");
     if (cfg->device < 0 || cfg->device >= ndev) return fail(nullptr, ECB_ERR_ARG, "device %d out of range (%d present)", cfg->device, ndev);
-    ecb_handle* h = new ecb_handle();
+    std::unique_ptr<ecb_handle> h(new ecb_handle());      // (an early return frees what was built so far)
     h->cfg = *cfg;
     h->device = cfg->device;
     if (!h->cfg.ec_capacity) h->cfg.ec_capacity = 1ull << 22;
@@ -3155,32 +3224,26 @@ int ecb_create(const ecb_config* cfg, ecb_handle** out) {
     if (!h->cfg.max_batch_records) h->cfg.max_batch_records = 1ull << 24;
     h->cap = std::max<u64>(next_pow2(h->cfg.ec_capacity), 1024);
     h->arena_cap = std::min<u64>(h->cfg.arena_capacity, 1ull << 32);
-    auto bail = [&](int code, const char* what, hipError_t e) {
-        fail(nullptr, code, "%s: %s", what, hipGetErrorString(e));
-        ecb_destroy(h);
-        return code;
-    };
+    auto bail = [](const char* what, hipError_t e) { return fail(nullptr, ECB_ERR_HIP, "%s: %s", what, hipGetErrorString(e)); };
     hipError_t e;
-    if ((e = hipSetDevice(h->device)) != hipSuccess) return bail(ECB_ERR_HIP, "hipSetDevice", e);
-    if ((e = hipStreamCreate(&h->stream)) != hipSuccess) return bail(ECB_ERR_HIP, "hipStreamCreate", e);
-    if ((e = hipMalloc(&h->table, h->cap * sizeof(Slot))) != hipSuccess) return bail(ECB_ERR_HIP, "hipMalloc(table)", e);
-    if ((e = hipMalloc(&h->arena, h->arena_cap * sizeof(uint2))) != hipSuccess) return bail(ECB_ERR_HIP, "hipMalloc(arena)", e);
-    if ((e = hipMalloc(&h->ctr, sizeof(Counters))) != hipSuccess) return bail(ECB_ERR_HIP, "hipMalloc(counters)", e);
-    if ((e = hipHostMalloc(reinterpret_cast<void**>(&h->pin_ctr), sizeof(Counters), hipHostMallocDefault)) != hipSuccess) return bail(ECB_ERR_HIP, "hipHostMalloc", e);
-    if ((e = hipHostMalloc(reinterpret_cast<void**>(&h->pin_cold), sizeof(StreamCold), hipHostMallocDefault)) != hipSuccess) return bail(ECB_ERR_HIP, "hipHostMalloc", e);
-    if ((e = hipHostMalloc(reinterpret_cast<void**>(&h->pin_out), sizeof(ecb_handle::PinOut), hipHostMallocDefault)) != hipSuccess) return bail(ECB_ERR_HIP, "hipHostMalloc", e);
-    if ((e = hipMalloc(&h->d_cold, sizeof(StreamCold))) != hipSuccess) return bail(ECB_ERR_HIP, "hipMalloc(args)", e);
+    if ((e = hipSetDevice(h->device)) != hipSuccess) return bail("hipSetDevice", e);
+    if ((e = hipStreamCreate(&h->stream)) != hipSuccess) return bail("hipStreamCreate", e);
+    if ((e = h->table.alloc(h->cap * sizeof(Slot))) != hipSuccess) return bail("hipMalloc(table)", e);
+    if ((e = h->arena.alloc(h->arena_cap * sizeof(uint2))) != hipSuccess) return bail("hipMalloc(arena)", e);
+    if ((e = h->ctr.alloc(sizeof(Counters))) != hipSuccess) return bail("hipMalloc(counters)", e);
+    if ((e = pin(h->pin_ctr)) != hipSuccess || (e = pin(h->pin_cold)) != hipSuccess || (e = pin(h->pin_out)) != hipSuccess) return bail("hipHostMalloc", e);
+    if ((e = h->d_cold.alloc(sizeof(StreamCold))) != hipSuccess) return bail("hipMalloc(args)", e);
     hipMemsetAsync(h->table, 0, h->cap * sizeof(Slot), h->stream);
     hipMemsetAsync(h->arena, 0, h->arena_cap * sizeof(uint2), h->stream);     // stale arena bytes must never look like a key (see ecb_reset)
-    clear_counters(h);
+    clear_counters(h.get());
     if (cfg->flags & ECB_F_RANGES) {
         const u64 ns = (u64)cfg->n_loci * cfg->n_haplotypes;
-        if ((e = hipMalloc(&h->rng, ns * sizeof(int2))) != hipSuccess) return bail(ECB_ERR_HIP, "hipMalloc(ranges)", e);
+        if ((e = h->rng.alloc(ns * sizeof(int2))) != hipSuccess) return bail("hipMalloc(ranges)", e);
         k_fill_minmax<<<nblk(ns, TPB), TPB, 0, h->stream>>>(h->rng, ns);
     }
     hipEventCreate(&h->ev0); hipEventCreate(&h->ev1);
-    if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return bail(ECB_ERR_HIP, "init", e);
-    *out = h;
+    if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return bail("init", e);
+    *out = h.release();
     return ECB_OK;
 }
 
@@ -3188,19 +3251,7 @@ void ecb_destroy(ecb_handle* h) {
     if (!h) return;
     hipSetDevice(h->device);
     if (h->stream) hipStreamSynchronize(h->stream);
-    free_results(h);
-    hipFree(h->table); hipFree(h->arena); hipFree(h->ctr); hipFree(h->read_slot); hipFree(h->meta);
-    hipFree(h->rng); hipFree(h->queue); hipFree(h->wave_arena);
-    if (h->pin_ctr) hipHostFree(h->pin_ctr);
-    if (h->pin_out) hipHostFree(h->pin_out);
-    if (h->pin_cold) hipHostFree(h->pin_cold);
-    hipFree(h->d_cold);
-    for (int i = 0; i < ecb_handle::P_N; ++i) hipFree(h->pool[i]);
-    hipFree(h->st_rid);                                  // (one allocation holds all staging streams: ensure_staging)
-    if (h->ev0) hipEventDestroy(h->ev0);
-    if (h->ev1) hipEventDestroy(h->ev1);
-    if (h->stream) hipStreamDestroy(h->stream);
-    delete h;
+    delete h;                                            // (the events and the stream, then the memory the handle owns)
 }
 
 int ecb_verify_device(ecb_handle* h, const void* d_read_id, const void* d_locus, const void* d_hapflag, size_t n,
@@ -3368,17 +3419,8 @@ int ecb_push_cells(ecb_handle* h, const uint32_t* meta, uint64_t first_read, siz
     if (!meta) return fail(h, ECB_ERR_ARG, "null meta");
     HIPCHK(h, hipSetDevice(h->device));
     const u64 need = first_read + n;
-    if (need > h->meta_cap) {
-        const u64 nc = std::max<u64>(need, h->meta_cap * 2);
-        u32* p = nullptr;
-        HIPCHK(h, hipMalloc(&p, nc * sizeof(u32)));
-        if (h->meta) {
-            HIPCHK(h, hipMemcpyAsync(p, h->meta, h->meta_hi * sizeof(u32), hipMemcpyDeviceToDevice, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            HIPCHK(h, hipFree(h->meta));
-        }
-        h->meta = p; h->meta_cap = nc;
-    }
+    const int rc = ensure_meta(h, need);
+    if (rc != ECB_OK) return rc;
     HIPCHK(h, hipMemcpyAsync(h->meta + first_read, meta, n * sizeof(u32), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->meta_hi = std::max<u64>(h->meta_hi, need);
@@ -3394,17 +3436,8 @@ int ecb_push_cells_device(ecb_handle* h, const void* d_meta, uint64_t first_read
     HIPCHK(h, hipSetDevice(h->device));
     if (first_read >= (1ull << 32) - 1 || (u64)n >= (1ull << 32) - 1 - first_read) return fail(h, ECB_ERR_LIMIT, "more than 2^32-2 reads");
     const u64 need = first_read + n;
-    if (need > h->meta_cap) {
-        const u64 nc = std::max<u64>(need, h->meta_cap * 2);
-        u32* p = nullptr;
-        HIPCHK(h, hipMalloc(&p, nc * sizeof(u32)));
-        if (h->meta) {
-            HIPCHK(h, hipMemcpyAsync(p, h->meta, h->meta_hi * sizeof(u32), hipMemcpyDeviceToDevice, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            HIPCHK(h, hipFree(h->meta));
-        }
-        h->meta = p; h->meta_cap = nc;
-    }
+    const int rc = ensure_meta(h, need);
+    if (rc != ECB_OK) return rc;
     // (the copy is ordered on the handle's own stream, behind nothing of the caller's: d_meta must be COMPLETE when this is called -- see ecb.h)
     HIPCHK(h, hipMemcpyAsync(h->meta + first_read, d_meta, n * sizeof(u32), hipMemcpyDeviceToDevice, h->stream));
     h->meta_hi = std::max<u64>(h->meta_hi, need);
@@ -3728,7 +3761,7 @@ int ecb_table_merge_batch_device(ecb_handle* h, uint32_t n_tables, const void* c
     // key range), or its list is current and has room (a buffer that had to grow would lose what it holds).
     u32* mlist = nullptr;
     const u64 list_need = h->n_ecs() + total;
-    if (h->n_ecs() == 0 || (h->list_counted && h->pool_bytes[ecb_handle::P_LIST] >= list_need * sizeof(u32))) {
+    if (h->n_ecs() == 0 || (h->list_counted && h->pool[ecb_handle::P_LIST].bytes >= list_need * sizeof(u32))) {
         const bool fresh = h->n_ecs() == 0;
         POOL(h, P_LIST, h->list, list_need);
         if (fresh) { POOL(h, P_CNT, h->d_list_n, 1); HIPCHK(h, hipMemsetAsync(h->d_list_n, 0, sizeof(u64), h->stream)); }
@@ -3834,13 +3867,8 @@ int ecb_table_adopt_batch_device(ecb_handle* h, uint32_t n_tables, const void* c
     if (have + add_e > h->cap) {                        // consecutive slots: a bigger array and a copy, no rehash
         u64 nc = h->cap;
         while (nc < have + add_e) nc *= 2;
-        Slot* nt = nullptr;
-        HIPCHK(h, hipMalloc(&nt, nc * sizeof(Slot)));
-        HIPCHK(h, hipMemsetAsync(nt, 0, nc * sizeof(Slot), h->stream));
-        HIPCHK(h, hipMemcpyAsync(nt, h->table, have * sizeof(Slot), hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, hipFree(h->table));
-        h->table = nt; h->cap = nc;
+        HIPCHK(h, h->table.grow(nc * sizeof(Slot), 0, have * sizeof(Slot), h->stream));
+        h->cap = nc;
     }
     for (u32 t = 0; t < n_tables; ++t) {
         if (!n_entries[t]) continue;
@@ -3976,11 +4004,11 @@ int ecb_ms_filter(ecb_handle* h, uint32_t n_cells, int64_t minimum_count, ecb_ms
     u32 *ec = x, *meta = x + T, *cnt = x + 2 * T;
     k_ms_split<<<nblk(T, TPB), TPB, 0, st>>>(h->ms_okey, h->ms_ostart, h->ms_ocount, T, ec, meta, cnt);
     const u32* first = h->ms_ofirst;
-    Scratch sc;                                              // (cell- and EC-sized scratch: small)
-    u64 *total = sc.get<u64>(n_cells), *cellkey = sc.get<u64>(n_cells);
-    u32 *firstfile = sc.get<u32>(n_cells), *seg = sc.get<u32>(E + 1), *keep_ec = sc.get<u32>(E), *new_rank = sc.get<u32>(E), *new_cell = sc.get<u32>(n_cells);
-    u32* d_err = sc.get<u32>(1);
-    if (!total || !cellkey || !firstfile || !seg || !keep_ec || !new_rank || !new_cell || !d_err) return fail(h, ECB_ERR_HIP, "out of device memory");
+    std::vector<DevBuf<>> sc;                                              // (cell- and EC-sized scratch: small)
+    u64 *total = fresh<u64>(sc, n_cells), *cellkey = fresh<u64>(sc, n_cells);
+    u32 *firstfile = fresh<u32>(sc, n_cells), *seg = fresh<u32>(sc, E + 1), *keep_ec = fresh<u32>(sc, E), *new_rank = fresh<u32>(sc, E), *new_cell = fresh<u32>(sc, n_cells);
+    u32* d_err = fresh<u32>(sc, 1);
+    if (missing(sc)) return fail(h, ECB_ERR_HIP, "out of device memory");
     HIPCHK(h, hipMemsetAsync(total, 0, (u64)n_cells * 8, st));
     HIPCHK(h, hipMemsetAsync(cellkey, 0xFF, (u64)n_cells * 8, st));
     HIPCHK(h, hipMemsetAsync(firstfile, 0xFF, (u64)n_cells * 4, st));
@@ -3995,10 +4023,10 @@ int ecb_ms_filter(ecb_handle* h, uint32_t n_cells, int64_t minimum_count, ecb_ms
     // 2. per EC: its first appearance in every file; where every cell enters the cell order; whether the EC keeps a cell
     k_msf2_seg<<<nblk(T, TPB), TPB, 0, st>>>(ec, T, (u32)E, seg, d_err);
     {
-        u32* big = sc.get<u32>(E + 1);                       // ECs of more than MSF_SMALL triples, their number behind the list
+        u32* big = fresh<u32>(sc, E + 1);                       // ECs of more than MSF_SMALL triples, their number behind the list
         const u64 max_giant = T / MSF_GIANT + 1;             // ... and of more than MSF_GIANT, with their per-file first appearances
-        u32 *giant = sc.get<u32>(max_giant + 1), *gfec = sc.get<u32>(max_giant * MSF_FILES);
-        if (!big || !giant || !gfec) return fail(h, ECB_ERR_HIP, "out of device memory");
+        u32 *giant = fresh<u32>(sc, max_giant + 1), *gfec = fresh<u32>(sc, max_giant * MSF_FILES);
+        if (missing(sc)) return fail(h, ECB_ERR_HIP, "out of device memory");
         HIPCHK(h, hipMemsetAsync(big + E, 0, 4, st));
         HIPCHK(h, hipMemsetAsync(giant + max_giant, 0, 4, st));
         HIPCHK(h, hipMemsetAsync(gfec, 0xFF, max_giant * MSF_FILES * 4, st));
@@ -4020,9 +4048,9 @@ int ecb_ms_filter(ecb_handle* h, uint32_t n_cells, int64_t minimum_count, ecb_ms
         if (err & 2u) return fail(h, ECB_ERR_CONTRACT, "a read's cell id is not below n_cells");
     }
     if (!C) return fail(h, ECB_ERR_EMPTY, "no (EC, cell) counts: nothing to filter");
-    u32 *cell_id = sc.get<u32>(C), *corder = sc.get<u32>(C), *corder2 = sc.get<u32>(C), *cflag = sc.get<u32>(C), *cpos = sc.get<u32>(C);
-    u64 *ctotal = sc.get<u64>(C), *bhi = sc.get<u64>(C), *blo = sc.get<u64>(C), *ck0 = sc.get<u64>(C), *ck1 = sc.get<u64>(C);
-    if (!cell_id || !corder || !corder2 || !cflag || !cpos || !ctotal || !bhi || !blo || !ck0 || !ck1) return fail(h, ECB_ERR_HIP, "out of device memory");
+    u32 *cell_id = fresh<u32>(sc, C), *corder = fresh<u32>(sc, C), *corder2 = fresh<u32>(sc, C), *cflag = fresh<u32>(sc, C), *cpos = fresh<u32>(sc, C);
+    u64 *ctotal = fresh<u64>(sc, C), *bhi = fresh<u64>(sc, C), *blo = fresh<u64>(sc, C), *ck0 = fresh<u64>(sc, C), *ck1 = fresh<u64>(sc, C);
+    if (missing(sc)) return fail(h, ECB_ERR_HIP, "out of device memory");
     k_msf2_celllist<<<nblk(n_cells, TPB), TPB, 0, st>>>(total, firstfile, cellkey, flag, pos, n_cells, cell_id, ctotal, bhi, blo);
     k_msf_iota<<<nblk(C, TPB), TPB, 0, st>>>(corder, C);
     HIPCHK(h, hipMemcpyAsync(ck0, blo, C * 8, hipMemcpyDeviceToDevice, st));
@@ -4052,21 +4080,16 @@ int ecb_ms_filter(ecb_handle* h, uint32_t n_cells, int64_t minimum_count, ecb_ms
     {
         u32 sbits = 1;
         while (sbits < 32 && (1ull << sbits) < S) ++sbits;
-        SortScratch ss{};
-        u64* tot = nullptr;
-        POOL(h, P_RS_HIST, ss.hist, rs_words(K)); POOL(h, P_RS_OFFS, ss.offs, RS_AUX_WORDS);
-        POOL(h, P_RS_SUMS, ss.sums, rs_scan_blocks(K) + 8); POOL(h, P_TOTALS, tot, 8);
-        ss.d_word = tot + 6;
         u64* kk[2] = {k0, k1}; u32* vv[2] = {v0, v1};
-        const hipError_t e = radix_sort_pairs64(st, kk, vv, K, ss, &where, ((1ull << sbits) - 1ull) << 32);
-        if (e != hipSuccess) return fail(h, ECB_ERR_HIP, "radix sort: %s", hipGetErrorString(e));
+        rc = handle_sort(h, kk, vv, K, &where, ((1ull << sbits) - 1ull) << 32);
+        if (rc != ECB_OK) return rc;
         POOL(h, P_F_IPN, h->f_ipn, S + 1); POOL(h, P_F_IXN, h->f_ixn, nnz_n); POOL(h, P_F_DAN, h->f_dan, nnz_n);
         k_msf2_nout<<<nblk(K, TPB), TPB, 0, st>>>(kk[where], vv[where], K, h->f_ixn, h->f_dan);
         k_msf2_nptr<<<nblk(S + 1, TPB), TPB, 0, st>>>(kk[where], K, (u32)S, h->f_ipn);
     }
     // 6. the rows of A of the ECs that are left
-    u32* rowlen2 = sc.get<u32>(E2 + 1);
-    if (!rowlen2) return fail(h, ECB_ERR_HIP, "out of device memory");
+    u32* rowlen2 = fresh<u32>(sc, E2 + 1);
+    if (missing(sc)) return fail(h, ECB_ERR_HIP, "out of device memory");
     POOL(h, P_F_IPA, h->f_ipa, E2 + 1);
     k_msf_rowlen<<<nblk(E, TPB), TPB, 0, st>>>(h->indptr, keep_ec, new_rank, E, rowlen2);
     u64 nnz_a = 0;
@@ -4140,8 +4163,8 @@ const char* ecb_profile_kernel(const ecb_handle* h) { return h ? h->last_kernel 
 
 // ---- f-2 conversions (stateless; scratch is allocated per call: this is not the hot path) ------------------------
 namespace {
-int cv_scan(hipStream_t st, const u32* in, u64 n, u32* out, u64* total, Scratch& sc) {
-    u32* sums = sc.get<u32>(scan_words(n) + 4);
+int cv_scan(hipStream_t st, const u32* in, u64 n, u32* out, u64* total, std::vector<DevBuf<>>& sc) {
+    u32* sums = fresh<u32>(sc, scan_words(n) + 4);
     if (!sums) return ECB_ERR_HIP;
     u64* grand = reinterpret_cast<u64*>(sums + scan_words(n));
     if (scan_launch(st, in, n, out, sums, grand) != hipSuccess) return ECB_ERR_HIP;
@@ -4153,24 +4176,16 @@ int cv_scan(hipStream_t st, const u32* in, u64 n, u32* out, u64* total, Scratch&
 // Scratch of the stateless conversions, kept per device between calls (grown on demand; ecb_release_scratch frees it): a
 // config-3-sized conversion needs ~0.4 GB in a dozen buffers, and a dozen hipMallocs cost more than its kernels do.
 namespace {
-struct CvScratch {
-    enum { KEYS0, KEYS1, VALS0, VALS1, HIST, OFFS, SUMS, SUMS2, BLK, SCAN, HEAD, WORDS, X0, X1, X2, X3, N };
-    void* p[N] = {}; u64 bytes[N] = {};
-    template <class T> T* get(int id, u64 count) {
-        const u64 need = std::max<u64>(count, 1) * sizeof(T);
-        if (bytes[id] < need) {
-            if (p[id]) hipFree(p[id]);
-            p[id] = nullptr; bytes[id] = 0;
-            if (hipMalloc(&p[id], need + need / 8) != hipSuccess) return nullptr;
-            bytes[id] = need + need / 8;
-        }
-        return reinterpret_cast<T*>(p[id]);
-    }
-    void release() { for (int i = 0; i < N; ++i) { if (p[i]) hipFree(p[i]); p[i] = nullptr; bytes[i] = 0; } }
-};
+enum { CV_KEYS0, CV_KEYS1, CV_VALS0, CV_VALS1, CV_HIST, CV_OFFS, CV_SUMS, CV_SUMS2, CV_BLK, CV_SCAN, CV_HEAD, CV_WORDS, CV_X0, CV_X1, CV_X2, CV_X3, CV_N };
 constexpr int CV_MAX_DEV = 64;
-CvScratch g_cv[CV_MAX_DEV];
+DevBuf<>* const g_cv = new DevBuf<>[CV_MAX_DEV * CV_N];      // (never destroyed: no HIP call may run after the runtime has gone, at exit)
 std::mutex g_cv_lock;
+// device `device`'s buffer `id`, holding at least max(count, 1) T's (regrown with an eighth more); nullptr when it cannot be had
+template <class T> T* cv_get(int device, int id, u64 count) {
+    DevBuf<>& b = g_cv[device * CV_N + id];
+    const u64 need = std::max<u64>(count, 1) * sizeof(T);
+    return b.regrow(need, need / 8) == hipSuccess ? b.as<T>() : nullptr;
+}
 // exclusive scan on `st`, nothing waits: sums = scan_words(n) words of scratch, the total (64 bits) lands in *d_grand
 void cv_scan_queue(hipStream_t st, const u32* in, u64 n, u32* out, u32* sums, u64* d_grand) { (void)scan_launch(st, in, n, out, sums, d_grand); }
 }  // namespace
@@ -4179,7 +4194,7 @@ extern "C" int ecb_release_scratch(int device) {
     if (device < 0 || device >= CV_MAX_DEV) return ECB_ERR_ARG;
     if (hipSetDevice(device) != hipSuccess) return fail(nullptr, ECB_ERR_NO_DEVICE, "no such device");
     std::lock_guard<std::mutex> g(g_cv_lock);
-    g_cv[device].release();
+    for (int i = 0; i < CV_N; ++i) g_cv[device * CV_N + i].reset();
     return ECB_OK;
 }
 
@@ -4196,8 +4211,7 @@ extern "C" int ecb_csr_to_hapcsc_device(int device, uint32_t n_ecs, uint32_t n_l
     const u64 nnz = (u64)nnz_i;
     if (nnz && (!d_indices || !d_data)) return fail(nullptr, ECB_ERR_ARG, "bad argument");       // (a matrix without non-zeros has no arrays to point at)
     std::lock_guard<std::mutex> guard(g_cv_lock);
-    CvScratch& S = g_cv[device];
-    u64* words = S.get<u64>(CvScratch::WORDS, 4);                  // [0] set bits, [1] the scan's total, [2] error bits
+    u64* words = cv_get<u64>(device, CV_WORDS, 4);                  // [0] set bits, [1] the scan's total, [2] error bits
     if (!words) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
     if (!d_cscidx || !d_cscptr) {                                  // the first call: how many row indices there will be
         u64 tot = 0;
@@ -4215,12 +4229,12 @@ extern "C" int ecb_csr_to_hapcsc_device(int device, uint32_t n_ecs, uint32_t n_l
         return ECB_OK;
     }
     const u32 nb = (u32)nblk(nnz, CVB);
-    u64 *k0 = S.get<u64>(CvScratch::KEYS0, nnz), *k1 = S.get<u64>(CvScratch::KEYS1, nnz);
-    u32 *v0 = S.get<u32>(CvScratch::VALS0, nnz), *v1 = S.get<u32>(CvScratch::VALS1, nnz);
-    SortScratch ss{S.get<u32>(CvScratch::HIST, rs_words(nnz)), S.get<u32>(CvScratch::OFFS, RS_AUX_WORDS),
-                   S.get<u32>(CvScratch::SUMS, rs_scan_blocks(nnz) + 8), words + 3};
-    u32 *blk = S.get<u32>(CvScratch::BLK, (u64)n_haps * nb), *scan = S.get<u32>(CvScratch::SCAN, (u64)n_haps * nb);
-    u32 *sums2 = S.get<u32>(CvScratch::SUMS2, scan_words((u64)n_haps * nb) + 2), *headval = S.get<u32>(CvScratch::HEAD, (u64)n_haps * n_loci);
+    u64 *k0 = cv_get<u64>(device, CV_KEYS0, nnz), *k1 = cv_get<u64>(device, CV_KEYS1, nnz);
+    u32 *v0 = cv_get<u32>(device, CV_VALS0, nnz), *v1 = cv_get<u32>(device, CV_VALS1, nnz);
+    SortScratch ss{cv_get<u32>(device, CV_HIST, rs_words(nnz)), cv_get<u32>(device, CV_OFFS, RS_AUX_WORDS),
+                   cv_get<u32>(device, CV_SUMS, rs_scan_blocks(nnz) + 8), words + 3};
+    u32 *blk = cv_get<u32>(device, CV_BLK, (u64)n_haps * nb), *scan = cv_get<u32>(device, CV_SCAN, (u64)n_haps * nb);
+    u32 *sums2 = cv_get<u32>(device, CV_SUMS2, scan_words((u64)n_haps * nb) + 2), *headval = cv_get<u32>(device, CV_HEAD, (u64)n_haps * n_loci);
     if (!k0 || !k1 || !v0 || !v1 || !ss.hist || !ss.offs || !ss.sums || !blk || !scan || !sums2 || !headval) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
     if (hipMemsetAsync(words, 0, 24, st) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "memset");
     k_cv_keys<<<nblk(n_ecs, TPB), TPB, 0, st>>>((const int*)d_indptr, n_ecs, (const int*)d_indices, (const int*)d_data, nnz, n_loci, n_haps,
@@ -4249,15 +4263,15 @@ namespace {
 // the general case: lists in any order, an EC more than once in a list -- every row index becomes a 64-bit key, all of them are sorted
 int hapcsc_to_csr_general(hipStream_t st, u32 n_ecs, u32 n_loci, u32 n_haps, const void* d_cscptr, const void* d_cscidx, u64 total,
                           const std::vector<u64>& hs, void* d_indptr, void* d_indices, void* d_data, uint64_t* nnz_out) {
-    Scratch sc;
-    u64 *d_hs = sc.get<u64>(n_haps + 1), *keys = sc.get<u64>(total), *keys2 = sc.get<u64>(total);
-    u32 *vals = sc.get<u32>(total), *vals2 = sc.get<u32>(total), *flag = sc.get<u32>(total), *pos = sc.get<u32>(total);
-    if (!d_hs || !keys || !keys2 || !vals || !vals2 || !flag || !pos) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
+    std::vector<DevBuf<>> sc;
+    u64 *d_hs = fresh<u64>(sc, n_haps + 1), *keys = fresh<u64>(sc, total), *keys2 = fresh<u64>(sc, total);
+    u32 *vals = fresh<u32>(sc, total), *vals2 = fresh<u32>(sc, total), *flag = fresh<u32>(sc, total), *pos = fresh<u32>(sc, total);
+    if (missing(sc)) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
     hipMemcpy(d_hs, hs.data(), (n_haps + 1) * 8, hipMemcpyHostToDevice);
     k_cv_back_expand<<<nblk(total, TPB), TPB, 0, st>>>((const int*)d_cscptr, (const int*)d_cscidx, total, n_loci, n_haps, d_hs, keys, vals);
     {
-        SortScratch ss{sc.get<u32>(rs_words(total)), sc.get<u32>(RS_AUX_WORDS), sc.get<u32>(rs_scan_blocks(total) + 8), sc.get<u64>(1)};
-        if (!ss.hist || !ss.offs || !ss.sums || !ss.d_word) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
+        SortScratch ss{fresh<u32>(sc, rs_words(total)), fresh<u32>(sc, RS_AUX_WORDS), fresh<u32>(sc, rs_scan_blocks(total) + 8), fresh<u64>(sc, 1)};
+        if (missing(sc)) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
         u64* kk[2] = {keys, keys2}; u32* vv[2] = {vals, vals2};
         int where = 0;
         if (radix_sort_pairs64(st, kk, vv, total, ss, &where) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "sort");
@@ -4283,9 +4297,8 @@ extern "C" int ecb_hapcsc_to_csr_device(int device, uint32_t n_ecs, uint32_t n_l
     if (device < 0 || device >= CV_MAX_DEV || hipSetDevice(device) != hipSuccess) return fail(nullptr, ECB_ERR_NO_DEVICE, "no such device");
     hipStream_t st = nullptr;
     std::lock_guard<std::mutex> guard(g_cv_lock);
-    CvScratch& S = g_cv[device];
     // start of every haplotype's block = running sum of its last column pointer
-    u64* words = S.get<u64>(CvScratch::WORDS, 40);                 // [0] error bits  [1] the scan's total  [3] the sort's  [4 ..) last pointers, then block starts
+    u64* words = cv_get<u64>(device, CV_WORDS, 40);                 // [0] error bits  [1] the scan's total  [3] the sort's  [4 ..) last pointers, then block starts
     if (!words) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
     int* d_last = reinterpret_cast<int*>(words + 4);
     std::vector<int> last(n_haps);
@@ -4299,9 +4312,9 @@ extern "C" int ecb_hapcsc_to_csr_device(int device, uint32_t n_ecs, uint32_t n_l
     if (hs[n_haps] != total) return fail(nullptr, ECB_ERR_ARG, "total does not match the column pointers");
     u32 ebits = 0;
     while (ebits < 32 && ((u64)1 << ebits) < n_ecs) ++ebits;
-    u64* d_hs = S.get<u64>(CvScratch::X0, n_haps + 1);
-    u32 *Ssum = S.get<u32>(CvScratch::X1, (u64)n_loci + 1);
-    u32 *colcnt = S.get<u32>(CvScratch::HEAD, 5ull * n_loci + 8), *sums = S.get<u32>(CvScratch::SUMS2, scan_words(n_loci) + 2);
+    u64* d_hs = cv_get<u64>(device, CV_X0, n_haps + 1);
+    u32 *Ssum = cv_get<u32>(device, CV_X1, (u64)n_loci + 1);
+    u32 *colcnt = cv_get<u32>(device, CV_HEAD, 5ull * n_loci + 8), *sums = cv_get<u32>(device, CV_SUMS2, scan_words(n_loci) + 2);
     if (!d_hs || !Ssum || !colcnt || !sums) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
     u32 *colbase = colcnt + n_loci, *colcur = colbase + n_loci, *pieces = colcur + n_loci, *pbase = pieces + n_loci;
     u32* d_err = reinterpret_cast<u32*>(words);
@@ -4316,7 +4329,7 @@ extern "C" int ecb_hapcsc_to_csr_device(int device, uint32_t n_ecs, uint32_t n_l
     if ((u32)back[0]) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSC: column pointers do not start at zero or go backwards");
     const u64 n_items = back[2];
     if (n_items == 0 || n_items >= (1ull << 31)) return fail(nullptr, ECB_ERR_LIMIT, "csc -> csr: pieces of work");
-    u32 *item_col = S.get<u32>(CvScratch::X2, n_items + 1), *bnd = S.get<u32>(CvScratch::X3, (n_items + 1) * n_haps);
+    u32 *item_col = cv_get<u32>(device, CV_X2, n_items + 1), *bnd = cv_get<u32>(device, CV_X3, (n_items + 1) * n_haps);
     if (!item_col || !bnd) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
     k_cvu_items<<<nblk(n_loci, TPB), TPB, 0, st>>>(pieces, pbase, n_loci, item_col);
     k_cvu_bounds<<<nblk(n_items * n_haps, TPB), TPB, 0, st>>>((const int*)d_cscptr, (const int*)d_cscidx, d_hs, pieces, pbase, item_col, (u32)n_items,
@@ -4329,10 +4342,10 @@ extern "C" int ecb_hapcsc_to_csr_device(int device, uint32_t n_ecs, uint32_t n_l
     if ((u32)back[0] & CVB_ERR_ORDER)                              // a long column whose lists are not ascending: sort everything
         return hapcsc_to_csr_general(st, n_ecs, n_loci, n_haps, d_cscptr, d_cscidx, total, hs, d_indptr, d_indices, d_data, nnz_out);
     const u64 nnz = back[1];
-    u64 *k0 = S.get<u64>(CvScratch::KEYS0, nnz), *k1 = S.get<u64>(CvScratch::KEYS1, nnz);
-    u32 *v0 = S.get<u32>(CvScratch::VALS0, nnz), *v1 = S.get<u32>(CvScratch::VALS1, nnz);
-    SortScratch ss{S.get<u32>(CvScratch::HIST, rs_words(nnz)), S.get<u32>(CvScratch::OFFS, RS_AUX_WORDS),
-                   S.get<u32>(CvScratch::SUMS, rs_scan_blocks(nnz) + 8), words + 3};
+    u64 *k0 = cv_get<u64>(device, CV_KEYS0, nnz), *k1 = cv_get<u64>(device, CV_KEYS1, nnz);
+    u32 *v0 = cv_get<u32>(device, CV_VALS0, nnz), *v1 = cv_get<u32>(device, CV_VALS1, nnz);
+    SortScratch ss{cv_get<u32>(device, CV_HIST, rs_words(nnz)), cv_get<u32>(device, CV_OFFS, RS_AUX_WORDS),
+                   cv_get<u32>(device, CV_SUMS, rs_scan_blocks(nnz) + 8), words + 3};
     if (!k0 || !k1 || !v0 || !v1 || !ss.hist || !ss.offs || !ss.sums) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
     k_cvu_union<true><<<(unsigned)n_items, CVU_TPB, 0, st>>>((const int*)d_cscptr, (const int*)d_cscidx, d_hs, pieces, pbase, item_col, bnd, (u32)n_items,
                                                              n_loci, n_haps, n_ecs, colcnt, colbase, colcur, nnz, k0, v0, d_err);
@@ -4351,11 +4364,20 @@ extern "C" int ecb_hapcsc_to_csr_device(int device, uint32_t n_ecs, uint32_t n_l
 // that only converts files (alntools ec2emase / emase2ec, the .h5 writer of bam2emase: bin_utils.py:979-1028) needs no device
 // allocator of its own -- and the Python drop-in no PyTorch on that path.
 namespace {
-struct DevBuf {                        // a device buffer that goes away with its scope
-    void* p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-    int take(u64 bytes) { return hipMalloc(&p, std::max<u64>(bytes, 4)) == hipSuccess ? ECB_OK : ECB_ERR_HIP; }
-};
+// every array in a fresh device buffer of max(bytes, 4) bytes (in list order), then the inputs copied in; what failed, or nullptr
+struct StageIn { DevBuf<>* d; const void* src; u64 bytes; };          // (src null: an output, allocated only)
+const char* stage_in(const std::vector<StageIn>& list) {
+    for (const StageIn& a : list) if (a.d->alloc(a.bytes, 4) != hipSuccess) return "out of device memory";
+    for (const StageIn& a : list)
+        if (a.src && a.bytes && hipMemcpy(a.d->p, a.src, a.bytes, hipMemcpyHostToDevice) != hipSuccess) return "copy to the device";
+    return nullptr;
+}
+// the results back: `bytes` of each (none when that is 0); false when a copy fails
+struct StageOut { void* dst; const DevBuf<>* d; u64 bytes; };
+bool stage_out(const std::vector<StageOut>& list) {
+    for (const StageOut& a : list) if (a.bytes && hipMemcpy(a.dst, a.d->p, a.bytes, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    return true;
+}
 }  // namespace
 
 extern "C" int ecb_csr_to_hapcsc(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, const int32_t* indptr, const int32_t* indices,
@@ -4372,13 +4394,11 @@ extern "C" int ecb_csr_to_hapcsc(int device, uint32_t n_ecs, uint32_t n_loci, ui
         *total = tot;
         return ECB_OK;
     }
-    DevBuf ip, ix, da, cp, ci;
+    DevBuf<> ip, ix, da, cp, ci;
     const u64 nc = (u64)n_haps * (n_loci + 1);
-    if (ip.take(((u64)n_ecs + 1) * 4) || ix.take(nnz * 4) || da.take(nnz * 4) || cp.take(nc * 4) || ci.take(capacity * 4))
-        return fail(nullptr, ECB_ERR_HIP, "out of device memory");
-    if (hipMemcpy(ip.p, indptr, ((u64)n_ecs + 1) * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        (nnz && (hipMemcpy(ix.p, indices, nnz * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(da.p, data, nnz * 4, hipMemcpyHostToDevice) != hipSuccess)))
-        return fail(nullptr, ECB_ERR_HIP, "copy to the device");
+    if (const char* why = stage_in({{&ip, indptr, ((u64)n_ecs + 1) * 4}, {&ix, indices, nnz * 4}, {&da, data, nnz * 4}, {&cp, nullptr, nc * 4},
+                                    {&ci, nullptr, capacity * 4}}))
+        return fail(nullptr, ECB_ERR_HIP, "%s", why);
     // (the device entry point writes at most one row index per set bit: ask it for the count first when the caller's buffer might be short)
     uint64_t need = 0;
     int rc = ecb_csr_to_hapcsc_device(device, n_ecs, n_loci, n_haps, ip.p, ix.p, da.p, nullptr, nullptr, &need);
@@ -4387,9 +4407,7 @@ extern "C" int ecb_csr_to_hapcsc(int device, uint32_t n_ecs, uint32_t n_loci, ui
     if (need > capacity) return fail(nullptr, ECB_ERR_ARG, "csc_indices holds %llu entries, the matrix has %llu set bits", (unsigned long long)capacity, (unsigned long long)need);
     rc = ecb_csr_to_hapcsc_device(device, n_ecs, n_loci, n_haps, ip.p, ix.p, da.p, cp.p, ci.p, total);
     if (rc != ECB_OK) return rc;
-    if (hipMemcpy(csc_indptr, cp.p, nc * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-        (*total && hipMemcpy(csc_indices, ci.p, *total * 4, hipMemcpyDeviceToHost) != hipSuccess))
-        return fail(nullptr, ECB_ERR_HIP, "copy from the device");
+    if (!stage_out({{csc_indptr, &cp, nc * 4}, {csc_indices, &ci, *total * 4}})) return fail(nullptr, ECB_ERR_HIP, "copy from the device");
     return ECB_OK;
 }
 
@@ -4399,17 +4417,14 @@ extern "C" int ecb_hapcsc_to_csr(int device, uint32_t n_ecs, uint32_t n_loci, ui
         return fail(nullptr, ECB_ERR_ARG, "bad argument");
     if (total >= (1ull << 32)) return fail(nullptr, ECB_ERR_LIMIT, "more than 2^32-1 row indices");
     if (device < 0 || device >= CV_MAX_DEV || hipSetDevice(device) != hipSuccess) return fail(nullptr, ECB_ERR_NO_DEVICE, "no such device");
-    DevBuf cp, ci, ip, ix, da;
-    const u64 nc = (u64)n_haps * (n_loci + 1);
-    if (cp.take(nc * 4) || ci.take(total * 4) || ip.take(((u64)n_ecs + 1) * 4) || ix.take(total * 4) || da.take(total * 4))
-        return fail(nullptr, ECB_ERR_HIP, "out of device memory");
-    if (hipMemcpy(cp.p, csc_indptr, nc * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(ci.p, csc_indices, total * 4, hipMemcpyHostToDevice) != hipSuccess)
-        return fail(nullptr, ECB_ERR_HIP, "copy to the device");
+    DevBuf<> cp, ci, ip, ix, da;
+    const u64 nc = (u64)n_haps * (n_loci + 1), rowb = ((u64)n_ecs + 1) * 4;
+    if (const char* why = stage_in({{&cp, csc_indptr, nc * 4}, {&ci, csc_indices, total * 4}, {&ip, nullptr, rowb}, {&ix, nullptr, total * 4},
+                                    {&da, nullptr, total * 4}}))
+        return fail(nullptr, ECB_ERR_HIP, "%s", why);
     const int rc = ecb_hapcsc_to_csr_device(device, n_ecs, n_loci, n_haps, cp.p, ci.p, total, ip.p, ix.p, da.p, nnz);
     if (rc != ECB_OK) return rc;
-    if (hipMemcpy(indptr, ip.p, ((u64)n_ecs + 1) * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-        (*nnz && (hipMemcpy(indices, ix.p, *nnz * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(data, da.p, *nnz * 4, hipMemcpyDeviceToHost) != hipSuccess)))
-        return fail(nullptr, ECB_ERR_HIP, "copy from the device");
+    if (!stage_out({{indptr, &ip, rowb}, {indices, &ix, *nnz * 4}, {data, &da, *nnz * 4}})) return fail(nullptr, ECB_ERR_HIP, "copy from the device");
     return ECB_OK;
 }
 
@@ -4539,10 +4554,9 @@ extern "C" int ecb_apply_mask_device(int device, uint32_t n_ecs, uint32_t n_loci
     if (device < 0 || device >= CV_MAX_DEV || hipSetDevice(device) != hipSuccess) return fail(nullptr, ECB_ERR_NO_DEVICE, "no such device");
     hipStream_t st = nullptr;
     std::lock_guard<std::mutex> guard(g_cv_lock);
-    CvScratch& S = g_cv[device];
     const u64 n_words = GM_SHARD_WORDS * (1 + GM_SHARDS);
-    u64* words = S.get<u64>(CvScratch::WORDS, n_words);
-    u32 *keep = S.get<u32>(CvScratch::X0, nnz), *excl = S.get<u32>(CvScratch::X1, nnz + 1), *sums = S.get<u32>(CvScratch::SUMS2, scan_words(nnz));
+    u64* words = cv_get<u64>(device, CV_WORDS, n_words);
+    u32 *keep = cv_get<u32>(device, CV_X0, nnz), *excl = cv_get<u32>(device, CV_X1, nnz + 1), *sums = cv_get<u32>(device, CV_SUMS2, scan_words(nnz));
     if (!words || !keep || !excl || !sums) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
     if (hipMemsetAsync(words, 0, n_words * 8, st) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "memset");
     const u64 threads = std::max<u64>(std::max<u64>((u64)n_ecs + 1, n_loci), (nnz + GM_ITEMS - 1) / GM_ITEMS);
@@ -4573,16 +4587,13 @@ extern "C" int ecb_apply_mask(int device, uint32_t n_ecs, uint32_t n_loci, uint3
     if (nnz >= (1ull << 31) || n_ecs >= (1u << 31) - 1u) return fail(nullptr, ECB_ERR_LIMIT, "the CSR exceeds the .bin format's int32 limits");
     if (device < 0 || device >= CV_MAX_DEV || hipSetDevice(device) != hipSuccess) return fail(nullptr, ECB_ERR_NO_DEVICE, "no such device");
     const u64 rowb = ((u64)n_ecs + 1) * 4, nzb = nnz * 4;
-    DevBuf ip, ix, da, mk, oip, oix, oda;
-    if (ip.take(rowb) || ix.take(nzb) || da.take(nzb) || mk.take((u64)n_loci * 4) || oip.take(rowb) || oix.take(nzb) || oda.take(nzb))
-        return fail(nullptr, ECB_ERR_HIP, "out of device memory");
-    if (hipMemcpy(ip.p, indptr, rowb, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(mk.p, mask, (u64)n_loci * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        (nnz && (hipMemcpy(ix.p, indices, nzb, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(da.p, data, nzb, hipMemcpyHostToDevice) != hipSuccess)))
-        return fail(nullptr, ECB_ERR_HIP, "copy to the device");
+    DevBuf<> ip, ix, da, mk, oip, oix, oda;
+    if (const char* why = stage_in({{&ip, indptr, rowb}, {&ix, indices, nzb}, {&da, data, nzb}, {&mk, mask, (u64)n_loci * 4}, {&oip, nullptr, rowb},
+                                    {&oix, nullptr, nzb}, {&oda, nullptr, nzb}}))
+        return fail(nullptr, ECB_ERR_HIP, "%s", why);
     const int rc = ecb_apply_mask_device(device, n_ecs, n_loci, n_haps, nnz, ip.p, ix.p, da.p, mk.p, oip.p, oix.p, oda.p, kept);
     if (rc != ECB_OK) return rc;
-    if (hipMemcpy(out_indptr, oip.p, rowb, hipMemcpyDeviceToHost) != hipSuccess ||
-        (*kept && (hipMemcpy(out_indices, oix.p, *kept * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(out_data, oda.p, *kept * 4, hipMemcpyDeviceToHost) != hipSuccess)))
+    if (!stage_out({{out_indptr, &oip, rowb}, {out_indices, &oix, *kept * 4}, {out_data, &oda, *kept * 4}}))
         return fail(nullptr, ECB_ERR_HIP, "copy from the device");
     return ECB_OK;
 }
@@ -4882,17 +4893,17 @@ extern "C" int ecb_combine_device(int device, uint32_t n_parts, const ecb_combin
     StreamGuard sg;
     if (hipStreamCreate(&sg.s) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "combine: stream");
     hipStream_t st = sg.s;
-    Scratch S;
-    CbPart* d_parts = S.get<CbPart>(n_parts);
-    u64* d_base = S.get<u64>(base.size());
+    std::vector<DevBuf<>> S;
+    CbPart* d_parts = fresh<CbPart>(S, n_parts);
+    u64* d_base = fresh<u64>(S, base.size());
     const u64 n_words = CB_SHARD_WORDS * (1 + CB_SHARDS);
-    u64* words = S.get<u64>(n_words);                    // [0] error bits (u32), then the arena shards
+    u64* words = fresh<u64>(S, n_words);                    // [0] error bits (u32), then the arena shards
     const u64 NK = std::max(NP, NZ);                     // (the sort buffers serve the pairs of A, then the entries of N)
-    u64 *keys0 = S.get<u64>(NK), *keys1 = S.get<u64>(NK), *rowhash = S.get<u64>(R);
-    u32 *vals0 = S.get<u32>(NK), *vals1 = S.get<u32>(NK);
-    uint2* pairs = S.get<uint2>(NP);
-    Entry* ent = S.get<Entry>(R);
-    if (!d_parts || !d_base || !words || !keys0 || !keys1 || !rowhash || !vals0 || !vals1 || !pairs || !ent) return fail(nullptr, ECB_ERR_HIP, "combine: out of device memory");
+    u64 *keys0 = fresh<u64>(S, NK), *keys1 = fresh<u64>(S, NK), *rowhash = fresh<u64>(S, R);
+    u32 *vals0 = fresh<u32>(S, NK), *vals1 = fresh<u32>(S, NK);
+    uint2* pairs = fresh<uint2>(S, NP);
+    Entry* ent = fresh<Entry>(S, R);
+    if (missing(S)) return fail(nullptr, ECB_ERR_HIP, "combine: out of device memory");
     u32* err = reinterpret_cast<u32*>(words);
     std::vector<u64> back(n_words);
     hipStream_t cur = st;                                // (the handle's own stream once there is one: it queues the slot ranks)
@@ -4930,8 +4941,8 @@ extern "C" int ecb_combine_device(int device, uint32_t n_parts, const ecb_combin
     if (any_map && NP > 1) {
         u64 bits = 0;
         for (u64 x = (R - 1) << 32 | (n_loci - 1); x; x >>= 1) bits = (bits << 1) | 1ull;
-        SortScratch sc{S.get<u32>(rs_words(NP)), S.get<u32>(RS_AUX_WORDS), S.get<u32>(rs_scan_blocks(NP) + 8), words + 1};
-        if (!sc.hist || !sc.offs || !sc.sums) return fail(nullptr, ECB_ERR_HIP, "combine: out of device memory");
+        SortScratch sc{fresh<u32>(S, rs_words(NP)), fresh<u32>(S, RS_AUX_WORDS), fresh<u32>(S, rs_scan_blocks(NP) + 8), words + 1};
+        if (missing(S)) return fail(nullptr, ECB_ERR_HIP, "combine: out of device memory");
         u64* kk[2] = {keys0, keys1}; u32* vv[2] = {vals0, vals1};
         int where = 0;
         const hipError_t e = radix_sort_pairs64(st, kk, vv, NP, sc, &where, bits);
@@ -4946,9 +4957,9 @@ extern "C" int ecb_combine_device(int device, uint32_t n_parts, const ecb_combin
     u64 wmax = 0, wsum = 0;
     for (u32 k = 1; k <= CB_SHARDS; ++k) { wmax = std::max<u64>(wmax, back[CB_SHARD_WORDS * k]); wsum += back[CB_SHARD_WORDS * k + 1]; }
     u64 E = 0, nnz_a = 0, nnz_n = 0;
-    DevBuf ecr;                                          // EC of every global row
-    if (ecr.take(std::max<u64>(R, 1) * 4)) return fail(nullptr, ECB_ERR_HIP, "combine: out of device memory");
-    u32* ec_of_row = (u32*)ecr.p;
+    DevBuf<u32> ecr;                                     // EC of every global row
+    if (ecr.alloc(std::max<u64>(R, 1) * 4, 4) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "combine: out of device memory");
+    u32* ec_of_row = ecr;
     CbHandle hg;
     if (R) {
         // 6. one table: room for every row being an EC of its own (half full at most: no growth), and a key arena in which every wave's one
@@ -4981,12 +4992,11 @@ extern "C" int ecb_combine_device(int device, uint32_t n_parts, const ecb_combin
     }
     // 8. N: (sample, EC) keys sorted, summed per key, zeros dropped, CSC
     if (NZ) {
-        u32 *flag = S.get<u32>(NZ), *pos = S.get<u32>(NZ + 1), *keep = S.get<u32>(NZ), *opos = S.get<u32>(NZ + 1);
-        u32 *sums1 = S.get<u32>(scan_words(NZ)), *sums2 = S.get<u32>(scan_words(NZ));
-        u64 *rsum = S.get<u64>(NZ), *rkey = S.get<u64>(NZ), *okey = S.get<u64>(NZ), *tot = S.get<u64>(2);
-        SortScratch sc{S.get<u32>(rs_words(NZ)), S.get<u32>(RS_AUX_WORDS), S.get<u32>(rs_scan_blocks(NZ) + 8), words + 1};
-        if (!flag || !pos || !keep || !opos || !sums1 || !sums2 || !rsum || !rkey || !okey || !tot || !sc.hist || !sc.offs || !sc.sums)
-            return fail(nullptr, ECB_ERR_HIP, "combine: out of device memory");
+        u32 *flag = fresh<u32>(S, NZ), *pos = fresh<u32>(S, NZ + 1), *keep = fresh<u32>(S, NZ), *opos = fresh<u32>(S, NZ + 1);
+        u32 *sums1 = fresh<u32>(S, scan_words(NZ)), *sums2 = fresh<u32>(S, scan_words(NZ));
+        u64 *rsum = fresh<u64>(S, NZ), *rkey = fresh<u64>(S, NZ), *okey = fresh<u64>(S, NZ), *tot = fresh<u64>(S, 2);
+        SortScratch sc{fresh<u32>(S, rs_words(NZ)), fresh<u32>(S, RS_AUX_WORDS), fresh<u32>(S, rs_scan_blocks(NZ) + 8), words + 1};
+        if (missing(S)) return fail(nullptr, ECB_ERR_HIP, "combine: out of device memory");
         k_cb_ntrip<<<nblk(NZ, TPB), TPB, 0, cur>>>(d_parts, n_parts, d_base, n_samples, ec_of_row, keys0, vals0, err);
         rc = check("N check");
         if (rc != ECB_OK) return rc;
@@ -5026,7 +5036,9 @@ extern "C" int ecb_combine(int device, uint32_t n_parts, const ecb_combine_part*
     if (!parts || !n_parts || !out_sizes || !out_indptr_a || !out_indptr_n) return fail(nullptr, ECB_ERR_ARG, "combine: bad argument");
     if (device < 0 || device >= CV_MAX_DEV || hipSetDevice(device) != hipSuccess) return fail(nullptr, ECB_ERR_NO_DEVICE, "no such device");
     std::vector<ecb_combine_part> dp(parts, parts + n_parts);
-    std::vector<DevBuf> bufs((u64)n_parts * 8);
+    std::vector<DevBuf<>> bufs((u64)n_parts * 8);
+    std::vector<StageIn> in;
+    std::vector<const void**> at;                        // (the pointer of dp that each staged array replaces)
     u64 R = 0, NP = 0, NZ = 0;
     for (u32 p = 0; p < n_parts; ++p) {
         const ecb_combine_part& c = parts[p];
@@ -5036,25 +5048,22 @@ extern "C" int ecb_combine(int device, uint32_t n_parts, const ecb_combine_part*
         const void** dst[8] = {(const void**)&dp[p].indptr_a, (const void**)&dp[p].indices_a, (const void**)&dp[p].data_a, (const void**)&dp[p].indptr_n,
                                (const void**)&dp[p].indices_n, (const void**)&dp[p].data_n, (const void**)&dp[p].target_map, (const void**)&dp[p].sample_map};
         if (c.nnz_a >= (1ull << 31) || c.nnz_n >= (1ull << 31)) return fail(nullptr, ECB_ERR_LIMIT, "combine: part %u exceeds the .bin format's int32 limits", p);
-        for (int k = 0; k < 8; ++k) {
-            if (!src[k]) { *dst[k] = nullptr; continue; }
-            DevBuf& b = bufs[(u64)p * 8 + k];
-            if (b.take(len[k]) || (len[k] && hipMemcpy(b.p, src[k], len[k], hipMemcpyHostToDevice) != hipSuccess))
-                return fail(nullptr, ECB_ERR_HIP, "combine: copy to the device");
-            *dst[k] = b.p;
-        }
+        for (int k = 0; k < 8; ++k)
+            if (src[k]) { in.push_back({&bufs[(u64)p * 8 + k], src[k], len[k]}); at.push_back(dst[k]); }
         R += c.n_ecs; NP += c.nnz_a; NZ += c.nnz_n;
     }
-    DevBuf oia, oxa, oda, oin, oxn, odn;
-    if (oia.take((R + 1) * 4) || oxa.take(NP * 4) || oda.take(NP * 4) || oin.take(((u64)n_samples + 1) * 4) || oxn.take(NZ * 4) || odn.take(NZ * 4))
+    if (stage_in(in)) return fail(nullptr, ECB_ERR_HIP, "combine: copy to the device");
+    for (size_t i = 0; i < in.size(); ++i) *at[i] = in[i].d->p;
+    DevBuf<> oia, oxa, oda, oin, oxn, odn;
+    const u64 nptr = ((u64)n_samples + 1) * 4;
+    if (stage_in({{&oia, nullptr, (R + 1) * 4}, {&oxa, nullptr, NP * 4}, {&oda, nullptr, NP * 4}, {&oin, nullptr, nptr}, {&oxn, nullptr, NZ * 4},
+                  {&odn, nullptr, NZ * 4}}))
         return fail(nullptr, ECB_ERR_HIP, "combine: out of device memory");
     const int rc = ecb_combine_device(device, n_parts, dp.data(), n_loci, n_haps, n_samples, oia.p, oxa.p, oda.p, oin.p, oxn.p, odn.p, out_sizes);
     if (rc != ECB_OK) return rc;
     const u64 E = out_sizes[0], nnz_a = out_sizes[1], nnz_n = out_sizes[2];
-    if (hipMemcpy(out_indptr_a, oia.p, (E + 1) * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(out_indptr_n, oin.p, ((u64)n_samples + 1) * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-        (nnz_a && (hipMemcpy(out_indices_a, oxa.p, nnz_a * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(out_data_a, oda.p, nnz_a * 4, hipMemcpyDeviceToHost) != hipSuccess)) ||
-        (nnz_n && (hipMemcpy(out_indices_n, oxn.p, nnz_n * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(out_data_n, odn.p, nnz_n * 4, hipMemcpyDeviceToHost) != hipSuccess)))
+    if (!stage_out({{out_indptr_a, &oia, (E + 1) * 4}, {out_indptr_n, &oin, nptr}, {out_indices_a, &oxa, nnz_a * 4}, {out_data_a, &oda, nnz_a * 4},
+                    {out_indices_n, &oxn, nnz_n * 4}, {out_data_n, &odn, nnz_n * 4}}))
         return fail(nullptr, ECB_ERR_HIP, "combine: copy from the device");
     return ECB_OK;
 }
@@ -5067,18 +5076,8 @@ extern "C" int ecb_combine(int device, uint32_t n_parts, const ecb_combine_part*
 // (bam_utils.py:646-724: contiguous chunks per worker, the workers' dicts merged in order.)  Everything is built from the entry points above;
 // the devices work one after the other here -- a host that wants them side by side runs one thread or one process per GPU over the same calls.
 namespace {
-struct PeerBuf {                       // device memory on a given device, freed with its scope
-    void* p = nullptr; int dev = 0;
-    PeerBuf() {}
-    PeerBuf(const PeerBuf&) = delete; PeerBuf& operator=(const PeerBuf&) = delete;
-    PeerBuf(PeerBuf&& o) noexcept : p(o.p), dev(o.dev) { o.p = nullptr; }
-    ~PeerBuf() { if (p) { hipSetDevice(dev); hipFree(p); } }
-    int take(int device, u64 bytes) {
-        dev = device;
-        if (hipSetDevice(device) != hipSuccess) return ECB_ERR_NO_DEVICE;
-        return hipMalloc(&p, std::max<u64>(bytes, 16)) == hipSuccess ? ECB_OK : ECB_ERR_HIP;
-    }
-};
+// max(bytes, 16) bytes on device `device` (left current); true when that fails
+bool take(DevBuf<>& b, int device, u64 bytes) { return hipSetDevice(device) != hipSuccess || b.alloc(bytes, 16) != hipSuccess; }
 struct HandleGuard { std::vector<ecb_handle*> h; ~HandleGuard() { for (ecb_handle* x : h) ecb_destroy(x); } };
 }  // namespace
 
@@ -5093,7 +5092,7 @@ extern "C" int ecb_merge(ecb_handle* const* shards, uint32_t n, ecb_handle* root
     }
     // 1. every shard: sizes, counters, its table cut into n key ranges (first reads counted from the shard's own 0)
     std::vector<u64> ne(n), np(n), nr(n), all(n), valid(n), base(n + 1, 0);
-    std::vector<PeerBuf> ent(n), prs(n);
+    std::vector<DevBuf<>> ent(n), prs(n);
     std::vector<std::vector<uint64_t>> eoff(n, std::vector<uint64_t>(n + 1, 0)), poff(n, std::vector<uint64_t>(n + 1, 0));
     for (u32 r = 0; r < n; ++r) {
         uint64_t a = 0, b = 0, c = 0;
@@ -5105,7 +5104,7 @@ extern "C" int ecb_merge(ecb_handle* const* shards, uint32_t n, ecb_handle* root
         if (rc != ECB_OK) return fail(root, rc, "ecb_merge: shard %u: %s", r, ecb_last_error(shards[r]));
         all[r] = ca; valid[r] = cv;
         base[r + 1] = base[r] + nr[r];
-        if (ent[r].take(shards[r]->device, std::max<u64>(ne[r], 1) * sizeof(Entry)) || prs[r].take(shards[r]->device, std::max<u64>(np[r], 1) * sizeof(uint2)))
+        if (take(ent[r], shards[r]->device, std::max<u64>(ne[r], 1) * sizeof(Entry)) || take(prs[r], shards[r]->device, std::max<u64>(np[r], 1) * sizeof(uint2)))
             return fail(root, ECB_ERR_HIP, "ecb_merge: out of device memory on device %d", shards[r]->device);
         if (ne[r]) {
             rc = ecb_table_export_parts_device(shards[r], ent[r].p, prs[r].p, 0, n, eoff[r].data(), poff[r].data());
@@ -5117,7 +5116,7 @@ extern "C" int ecb_merge(ecb_handle* const* shards, uint32_t n, ecb_handle* root
     const u64 t_reads = base[n];
     // 2. range q: its pieces to device q (the device of shard q), merged in shard order on a handle of its own, finalized there
     HandleGuard parts;
-    struct Piece { PeerBuf ip, ix, da, cn, fi; u64 n_ecs = 0, nnz = 0; };
+    struct Piece { DevBuf<> ip, ix, da, cn, fi; u64 n_ecs = 0, nnz = 0; };
     std::vector<Piece> piece(n);
     for (u32 q = 0; q < n; ++q) {
         const int dq = shards[q]->device;
@@ -5131,12 +5130,12 @@ extern "C" int ecb_merge(ecb_handle* const* shards, uint32_t n, ecb_handle* root
         int rc = ecb_create(&cfg, &part);
         if (rc != ECB_OK) return fail(root, rc, "ecb_merge: range %u: %s", q, ecb_last_error(nullptr));
         parts.h.push_back(part);
-        std::vector<PeerBuf> pe(n), pp(n);
+        std::vector<DevBuf<>> pe(n), pp(n);
         std::vector<const void*> le, lp; std::vector<uint64_t> lne, lnp;
         for (u32 r = 0; r < n; ++r) {
             const u64 e_n = eoff[r][q + 1] - eoff[r][q], p_n = poff[r][q + 1] - poff[r][q];
             if (!e_n) continue;
-            if (pe[r].take(dq, e_n * sizeof(Entry)) || pp[r].take(dq, std::max<u64>(p_n, 1) * sizeof(uint2))) return fail(root, ECB_ERR_HIP, "ecb_merge: out of device memory on device %d", dq);
+            if (take(pe[r], dq, e_n * sizeof(Entry)) || take(pp[r], dq, std::max<u64>(p_n, 1) * sizeof(uint2))) return fail(root, ECB_ERR_HIP, "ecb_merge: out of device memory on device %d", dq);
             if (hipMemcpyPeer(pe[r].p, dq, (const char*)ent[r].p + eoff[r][q] * sizeof(Entry), shards[r]->device, e_n * sizeof(Entry)) != hipSuccess ||
                 (p_n && hipMemcpyPeer(pp[r].p, dq, (const char*)prs[r].p + poff[r][q] * sizeof(uint2), shards[r]->device, p_n * sizeof(uint2)) != hipSuccess))
                 return fail(root, ECB_ERR_HIP, "ecb_merge: peer copy from device %d to device %d failed", shards[r]->device, dq);
@@ -5150,7 +5149,7 @@ extern "C" int ecb_merge(ecb_handle* const* shards, uint32_t n, ecb_handle* root
         if (rc != ECB_OK) return fail(root, rc, "ecb_merge: range %u: %s", q, ecb_last_error(part));
         Piece& P = piece[q];
         P.n_ecs = s.n_ecs; P.nnz = s.nnz_a;
-        if (P.ip.take(dq, (s.n_ecs + 1) * 4) || P.ix.take(dq, s.nnz_a * 4) || P.da.take(dq, s.nnz_a * 4) || P.cn.take(dq, s.n_ecs * 4) || P.fi.take(dq, s.n_ecs * 4))
+        if (take(P.ip, dq, (s.n_ecs + 1) * 4) || take(P.ix, dq, s.nnz_a * 4) || take(P.da, dq, s.nnz_a * 4) || take(P.cn, dq, s.n_ecs * 4) || take(P.fi, dq, s.n_ecs * 4))
             return fail(root, ECB_ERR_HIP, "ecb_merge: out of device memory on device %d", dq);
         rc = ecb_export_device(part, P.ip.p, P.ix.p, P.da.p, nullptr, nullptr, P.cn.p);
         if (rc == ECB_OK) rc = ecb_export_firsts_device(part, P.fi.p);
@@ -5166,7 +5165,7 @@ extern "C" int ecb_merge(ecb_handle* const* shards, uint32_t n, ecb_handle* root
         Piece* use = &S;
         if (S.ip.dev != d0) {
             Piece& D = at_root[q];
-            if (D.ip.take(d0, (S.n_ecs + 1) * 4) || D.ix.take(d0, S.nnz * 4) || D.da.take(d0, S.nnz * 4) || D.cn.take(d0, S.n_ecs * 4) || D.fi.take(d0, S.n_ecs * 4))
+            if (take(D.ip, d0, (S.n_ecs + 1) * 4) || take(D.ix, d0, S.nnz * 4) || take(D.da, d0, S.nnz * 4) || take(D.cn, d0, S.n_ecs * 4) || take(D.fi, d0, S.n_ecs * 4))
                 return fail(root, ECB_ERR_HIP, "ecb_merge: out of device memory on device %d", d0);
             if (hipMemcpyPeer(D.ip.p, d0, S.ip.p, S.ip.dev, (S.n_ecs + 1) * 4) != hipSuccess || hipMemcpyPeer(D.ix.p, d0, S.ix.p, S.ip.dev, S.nnz * 4) != hipSuccess ||
                 hipMemcpyPeer(D.da.p, d0, S.da.p, S.ip.dev, S.nnz * 4) != hipSuccess || hipMemcpyPeer(D.cn.p, d0, S.cn.p, S.ip.dev, S.n_ecs * 4) != hipSuccess ||

@@ -45,6 +45,12 @@ class EcbError(RuntimeError):
         self.code = code
 
 
+def _check(lib, rc, h=None):
+    """Raise :class:`EcbError` for a non-zero return code of libecb, with the message of handle ``h`` (None: of the last call without one)."""
+    if rc != 0:
+        raise EcbError(rc, (lib.ecb_last_error(h) or b"").decode())
+
+
 class Config(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("n_loci", C.c_uint32),
                 ("n_haplotypes", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
@@ -200,17 +206,13 @@ def csr_to_hapcsc(indptr, indices, data, n_loci, n_haps, nnz=None):
     nnz = indices.numel() if nnz is None else int(nnz)
     cap = nnz * n_haps
     if cap >= (1 << 28):                             # (a count first: the exact size)
-        rc = lib.ecb_csr_to_hapcsc_device(dev.index or 0, E, n_loci, n_haps, _dev_ptr(indptr), _dev_ptr(indices), _dev_ptr(data),
-                                          None, None, C.byref(tot))
-        if rc != 0:
-            raise EcbError(rc, (lib.ecb_last_error(None) or b"").decode())
+        _check(lib, lib.ecb_csr_to_hapcsc_device(dev.index or 0, E, n_loci, n_haps, _dev_ptr(indptr), _dev_ptr(indices), _dev_ptr(data),
+                                                 None, None, C.byref(tot)))
         cap = tot.value
     cptr = torch.empty((n_haps, n_loci + 1), dtype=torch.int32, device=dev)
     cidx = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-    rc = lib.ecb_csr_to_hapcsc_device(dev.index or 0, E, n_loci, n_haps, _dev_ptr(indptr), _dev_ptr(indices), _dev_ptr(data),
-                                      _dev_ptr(cptr), _dev_ptr(cidx), C.byref(tot))
-    if rc != 0:
-        raise EcbError(rc, (lib.ecb_last_error(None) or b"").decode())
+    _check(lib, lib.ecb_csr_to_hapcsc_device(dev.index or 0, E, n_loci, n_haps, _dev_ptr(indptr), _dev_ptr(indices), _dev_ptr(data),
+                                             _dev_ptr(cptr), _dev_ptr(cidx), C.byref(tot)))
     return cptr, cidx[:tot.value]
 
 
@@ -221,14 +223,10 @@ def csr_to_hapcsc_host(indptr, indices, data, n_loci, n_haps, device=0):
     ip, ix, da = (np.ascontiguousarray(a, dtype=np.int32) for a in (indptr, indices, data))
     E = len(ip) - 1
     tot = C.c_uint64()
-    rc = lib.ecb_csr_to_hapcsc(device, E, n_loci, n_haps, _ptr(ip), _ptr(ix), _ptr(da), None, None, 0, C.byref(tot))
-    if rc != 0:
-        raise EcbError(rc, (lib.ecb_last_error(None) or b"").decode())
+    _check(lib, lib.ecb_csr_to_hapcsc(device, E, n_loci, n_haps, _ptr(ip), _ptr(ix), _ptr(da), None, None, 0, C.byref(tot)))
     cptr = np.empty((n_haps, n_loci + 1), dtype=np.int32)
     cidx = np.empty(max(tot.value, 1), dtype=np.int32)
-    rc = lib.ecb_csr_to_hapcsc(device, E, n_loci, n_haps, _ptr(ip), _ptr(ix), _ptr(da), _ptr(cptr), _ptr(cidx), len(cidx), C.byref(tot))
-    if rc != 0:
-        raise EcbError(rc, (lib.ecb_last_error(None) or b"").decode())
+    _check(lib, lib.ecb_csr_to_hapcsc(device, E, n_loci, n_haps, _ptr(ip), _ptr(ix), _ptr(da), _ptr(cptr), _ptr(cidx), len(cidx), C.byref(tot)))
     return cptr, cidx[:tot.value]
 
 
@@ -243,9 +241,7 @@ def hapcsc_to_csr_host(csc_indptr, csc_indices, n_ecs, device=0):
     ix = np.empty(max(total, 1), dtype=np.int32)
     da = np.empty(max(total, 1), dtype=np.int32)
     nnz = C.c_uint64()
-    rc = lib.ecb_hapcsc_to_csr(device, n_ecs, T1 - 1, H, _ptr(cptr), _ptr(cidx), total, _ptr(ip), _ptr(ix), _ptr(da), C.byref(nnz))
-    if rc != 0:
-        raise EcbError(rc, (lib.ecb_last_error(None) or b"").decode())
+    _check(lib, lib.ecb_hapcsc_to_csr(device, n_ecs, T1 - 1, H, _ptr(cptr), _ptr(cidx), total, _ptr(ip), _ptr(ix), _ptr(da), C.byref(nnz)))
     return ip, ix[:nnz.value], da[:nnz.value]
 
 
@@ -260,10 +256,8 @@ def hapcsc_to_csr(csc_indptr, csc_indices, n_ecs):
     ix = torch.empty(total, dtype=torch.int32, device=dev)
     da = torch.empty(total, dtype=torch.int32, device=dev)
     nnz = C.c_uint64()
-    rc = lib.ecb_hapcsc_to_csr_device(dev.index or 0, n_ecs, T1 - 1, H, _dev_ptr(csc_indptr), _dev_ptr(csc_indices), total,
-                                      _dev_ptr(ip), _dev_ptr(ix), _dev_ptr(da), C.byref(nnz))
-    if rc != 0:
-        raise EcbError(rc, (lib.ecb_last_error(None) or b"").decode())
+    _check(lib, lib.ecb_hapcsc_to_csr_device(dev.index or 0, n_ecs, T1 - 1, H, _dev_ptr(csc_indptr), _dev_ptr(csc_indices), total,
+                                             _dev_ptr(ip), _dev_ptr(ix), _dev_ptr(da), C.byref(nnz)))
     return ip, ix[:nnz.value], da[:nnz.value]
 
 
@@ -285,10 +279,8 @@ def apply_mask(indptr, indices, data, mask, n_haps, device=0):
         oix = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
         oda = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
         kept = C.c_uint64()
-        rc = lib.ecb_apply_mask_device(dev.index or 0, E, T, n_haps, nnz, _dev_ptr(ip), _dev_ptr(ix), _dev_ptr(da), _dev_ptr(mk),
-                                       _dev_ptr(oip), _dev_ptr(oix), _dev_ptr(oda), C.byref(kept))
-        if rc != 0:
-            raise EcbError(rc, (lib.ecb_last_error(None) or b"").decode())
+        _check(lib, lib.ecb_apply_mask_device(dev.index or 0, E, T, n_haps, nnz, _dev_ptr(ip), _dev_ptr(ix), _dev_ptr(da), _dev_ptr(mk),
+                                              _dev_ptr(oip), _dev_ptr(oix), _dev_ptr(oda), C.byref(kept)))
         return oip, oix[:kept.value], oda[:kept.value]
     ip, ix, da = (np.ascontiguousarray(a, dtype=np.int32) for a in (indptr, indices, data))
     mk = np.ascontiguousarray(mask, dtype=np.uint32)
@@ -299,9 +291,7 @@ def apply_mask(indptr, indices, data, mask, n_haps, device=0):
     oix = np.empty(max(nnz, 1), dtype=np.int32)
     oda = np.empty(max(nnz, 1), dtype=np.int32)
     kept = C.c_uint64()
-    rc = lib.ecb_apply_mask(device, E, T, n_haps, nnz, _ptr(ip), _ptr(ix), _ptr(da), _ptr(mk), _ptr(oip), _ptr(oix), _ptr(oda), C.byref(kept))
-    if rc != 0:
-        raise EcbError(rc, (lib.ecb_last_error(None) or b"").decode())
+    _check(lib, lib.ecb_apply_mask(device, E, T, n_haps, nnz, _ptr(ip), _ptr(ix), _ptr(da), _ptr(mk), _ptr(oip), _ptr(oix), _ptr(oda), C.byref(kept)))
     return oip, oix[:kept.value], oda[:kept.value]
 
 
@@ -352,9 +342,7 @@ def combine(parts, n_loci, n_haps, n_samples, device=0):
         R, NP, NZ = R + E, NP + len(a[1]), NZ + len(a[4])
     out = [empty(R + 1), empty(NP), empty(NP), empty(n_samples + 1), empty(NZ), empty(NZ)]
     sizes = (C.c_uint64 * 3)()
-    rc = entry(device, len(parts), cp, n_loci, n_haps, n_samples, *[ptr(o) for o in out], sizes)
-    if rc != 0:
-        raise EcbError(rc, (lib.ecb_last_error(None) or b"").decode())
+    _check(lib, entry(device, len(parts), cp, n_loci, n_haps, n_samples, *[ptr(o) for o in out], sizes))
     E, nnz_a, nnz_n = (int(x) for x in sizes)
     return out[0][:E + 1], out[1][:nnz_a], out[2][:nnz_a], out[3], out[4][:nnz_n], out[5][:nnz_n]
 
@@ -370,16 +358,13 @@ class EcBuilder(object):
         self.multisample = multisample
         cfg = Config(C.sizeof(Config), device, n_loci, n_haplotypes, flags, 0, ec_capacity,
                      arena_capacity, max_batch_records)
-        rc = self._lib.ecb_create(C.byref(cfg), C.byref(self._h))
-        if rc != 0:
-            raise EcbError(rc, (self._lib.ecb_last_error(None) or b"").decode())
+        _check(self._lib, self._lib.ecb_create(C.byref(cfg), C.byref(self._h)))
         self.n_loci, self.n_haplotypes, self.track_ranges = n_loci, n_haplotypes, track_ranges
         self.sizes = None
 
     # -- plumbing ------------------------------------------------------------
     def _chk(self, rc):
-        if rc != 0:
-            raise EcbError(rc, (self._lib.ecb_last_error(self._h) or b"").decode())
+        _check(self._lib, rc, self._h)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
