@@ -67,6 +67,7 @@ constexpr u32 ERR_RANGE = 2u;
 constexpr u32 ERR_ARENA = 4u;
 constexpr u32 ERR_QUEUE = 8u;
 constexpr u32 ERR_INTERNAL = 16u;
+constexpr u32 ERR_COUNT = 32u;       // a count handed in by the caller does not fit the int32 of N
 
 // One EC = one 64-byte line.  EC identity is EXACT: `lo` is only the hash that picks the slot; a lookup that finds its hash
 // compares the read's {locus -> haplotype mask} set with the key stored in the slot, pair by pair, before it calls the slot
@@ -2214,10 +2215,12 @@ __global__ void k_msf2_seg(const u32* ec, u64 n, u32 n_ecs, u32* seg, u32* err) 
 // their file's first appearance up by walking the EC's stretch again -- neighbours' stretches follow each other in memory), one
 // WORKGROUP per larger EC, queued by the first kernel, with the per-file table in LDS.  (One wave per EC with three dependent
 // sweeps was latency: 14 us per EC.)
+// A triple whose cell is not below n_cells is passed over by every kernel here (k_msf2_cells has reported it: the call fails once
+// they are done), so that total / firstfile / cellkey -- n_cells entries each -- are never read or written past their end.
 constexpr u32 MSF_SMALL = 256;
 constexpr u32 MSF_FILES = 1u << MS_FILE_BITS;
 constexpr u32 MSF_GIANT = 1u << 15;           // triples above which an EC is shared out over the whole grid (k_msf2_giant_*), not given to one workgroup
-__global__ void k_msf2_ecs_small(const u32* meta, const u32* first, const u32* seg, u32 n_ecs, const u64* total, const u32* firstfile,
+__global__ void k_msf2_ecs_small(const u32* meta, const u32* first, const u32* seg, u32 n_ecs, u32 n_cells, const u64* total, const u32* firstfile,
                                  u64 min_count, u64* cellkey, u32* keep_ec, u32* big, u32* n_big, u32* giant, u32* n_giant) {
     const u64 e = blockIdx.x * (u64)blockDim.x + threadIdx.x;
     if (e >= n_ecs) return;
@@ -2228,6 +2231,7 @@ __global__ void k_msf2_ecs_small(const u32* meta, const u32* first, const u32* s
     u32 last_f = 0xFFFFFFFFu, last_fec = 0;                                  // (the EC's first appearance in the file asked for last: cells' first files repeat)
     for (u32 t = a; t < b; ++t) {
         const u32 m = meta[t], c = m & ((1u << ECB_CELL_BITS) - 1u), f = m >> ECB_CELL_BITS;
+        if (c >= n_cells) continue;
         keep |= total[c] >= min_count;
         if (firstfile[c] != f) continue;
         if (f != last_f) {
@@ -2241,7 +2245,7 @@ __global__ void k_msf2_ecs_small(const u32* meta, const u32* first, const u32* s
     }
     if (keep) keep_ec[e] = 1u;
 }
-__global__ __launch_bounds__(TPB) void k_msf2_ecs_big(const u32* meta, const u32* first, const u32* seg, const u32* big, const u32* n_big,
+__global__ __launch_bounds__(TPB) void k_msf2_ecs_big(const u32* meta, const u32* first, const u32* seg, const u32* big, const u32* n_big, u32 n_cells,
                                                       const u64* total, const u32* firstfile, u64 min_count, u64* cellkey, u32* keep_ec) {
     __shared__ u32 fec[MSF_FILES];
     __shared__ u32 s_keep;
@@ -2252,15 +2256,16 @@ __global__ __launch_bounds__(TPB) void k_msf2_ecs_big(const u32* meta, const u32
         __syncthreads();
         bool keep = false;
         for (u32 t = a + threadIdx.x; t < b; t += TPB) {
-            const u32 m = meta[t];
+            const u32 m = meta[t], c = m & ((1u << ECB_CELL_BITS) - 1u);
+            if (c >= n_cells) continue;
             atomicMin(&fec[m >> ECB_CELL_BITS], first[t]);
-            keep |= total[m & ((1u << ECB_CELL_BITS) - 1u)] >= min_count;
+            keep |= total[c] >= min_count;
         }
         if (keep) s_keep = 1u;
         __syncthreads();
         for (u32 t = a + threadIdx.x; t < b; t += TPB) {
             const u32 m = meta[t], c = m & ((1u << ECB_CELL_BITS) - 1u), f = m >> ECB_CELL_BITS;
-            if (firstfile[c] == f) {
+            if (c < n_cells && firstfile[c] == f) {
                 const u64 offer = ((u64)fec[f] << 32) | first[t];
                 if (offer < cellkey[c]) atomicMin(&cellkey[c], offer);
             }
@@ -2272,7 +2277,7 @@ __global__ __launch_bounds__(TPB) void k_msf2_ecs_big(const u32* meta, const u32
 // The few ECs with tens of thousands of triples and more (config 4's most popular EC has millions): one workgroup each was the tail of the
 // whole filter.  Every workgroup of the grid takes a strided share of each such EC: first the EC's first appearance per file (LDS, then one
 // global atomic per file and workgroup), then -- a launch later -- the offers.
-__global__ __launch_bounds__(TPB) void k_msf2_giant_fec(const u32* meta, const u32* first, const u32* seg, const u32* giant, const u32* n_giant,
+__global__ __launch_bounds__(TPB) void k_msf2_giant_fec(const u32* meta, const u32* first, const u32* seg, const u32* giant, const u32* n_giant, u32 n_cells,
                                                         const u64* total, u64 min_count, u32* gfec, u32* keep_ec) {
     __shared__ u32 fec[MSF_FILES];
     __shared__ u32 s_keep;
@@ -2283,9 +2288,10 @@ __global__ __launch_bounds__(TPB) void k_msf2_giant_fec(const u32* meta, const u
         __syncthreads();
         bool keep = false;
         for (u64 t = (u64)a + (u64)blockIdx.x * TPB + threadIdx.x; t < b; t += (u64)gridDim.x * TPB) {
-            const u32 m = meta[t];
+            const u32 m = meta[t], c = m & ((1u << ECB_CELL_BITS) - 1u);
+            if (c >= n_cells) continue;
             atomicMin(&fec[m >> ECB_CELL_BITS], first[t]);
-            keep |= total[m & ((1u << ECB_CELL_BITS) - 1u)] >= min_count;
+            keep |= total[c] >= min_count;
         }
         if (keep) s_keep = 1u;
         __syncthreads();
@@ -2294,13 +2300,13 @@ __global__ __launch_bounds__(TPB) void k_msf2_giant_fec(const u32* meta, const u
         __syncthreads();
     }
 }
-__global__ __launch_bounds__(TPB) void k_msf2_giant_offer(const u32* meta, const u32* first, const u32* seg, const u32* giant, const u32* n_giant,
+__global__ __launch_bounds__(TPB) void k_msf2_giant_offer(const u32* meta, const u32* first, const u32* seg, const u32* giant, const u32* n_giant, u32 n_cells,
                                                           const u32* firstfile, const u32* gfec, u64* cellkey) {
     for (u32 g = 0; g < *n_giant; ++g) {
         const u32 e = giant[g], a = seg[e], b = seg[e + 1];
         for (u64 t = (u64)a + (u64)blockIdx.x * TPB + threadIdx.x; t < b; t += (u64)gridDim.x * TPB) {
             const u32 m = meta[t], c = m & ((1u << ECB_CELL_BITS) - 1u), f = m >> ECB_CELL_BITS;
-            if (firstfile[c] == f) {
+            if (c < n_cells && firstfile[c] == f) {
                 const u64 offer = ((u64)gfec[(u64)g * MSF_FILES + f] << 32) | first[t];
                 if (offer < cellkey[c]) atomicMin(&cellkey[c], offer);
             }
@@ -2328,14 +2334,15 @@ __global__ void k_msf2_pairflag(const u32* ec, const u32* meta, u64 n, const u32
     flag[t] = (head && new_cell[c] != 0xFFFFFFFFu) ? 1u : 0u;
 }
 __global__ void k_msf2_pairs(const u32* ec, const u32* meta, const u32* cnt, const u32* flag, const u32* pos, u64 n, const u32* new_cell,
-                             const u32* new_rank, u64* key, u32* val) {
+                             const u32* new_rank, u64* key, u32* val, u32* err) {
     const u64 t = blockIdx.x * (u64)blockDim.x + threadIdx.x;
     if (t >= n || !flag[t]) return;
     const u32 e = ec[t], c = meta[t] & ((1u << ECB_CELL_BITS) - 1u);
-    u32 sum = 0;
+    u64 sum = 0;
     for (u64 x = t; x < n && ec[x] == e && (meta[x] & ((1u << ECB_CELL_BITS) - 1u)) == c; ++x) sum += cnt[x];   // (the same cell's reads of one EC in several files add up, :737-791)
+    if (sum > 0x7FFFFFFFull) atomicOr(err, 4u);             // (an entry of N is an int32)
     key[pos[t]] = ((u64)new_cell[c] << 32) | new_rank[e];
-    val[pos[t]] = sum;
+    val[pos[t]] = (u32)sum;
 }
 __global__ void k_msf2_nout(const u64* key, const u32* val, u64 n, int* indices, int* data) {
     const u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x;
@@ -2585,6 +2592,7 @@ int sync_counters(ecb_handle* h) {
     if (h->hctr.err & ERR_ARENA) return fail(h, ECB_ERR_TABLE_FULL, "EC key arena exhausted (%llu pairs): raise arena_capacity", (unsigned long long)h->arena_cap);
     if (h->hctr.err & ERR_QUEUE) return fail(h, ECB_ERR_TABLE_FULL, "deferred-read queue exhausted");
     if (h->hctr.err & ERR_INTERNAL) return fail(h, ECB_ERR_HIP, "internal: an EC-table slot was claimed but its key never published");
+    if (h->hctr.err & ERR_COUNT) return fail(h, ECB_ERR_LIMIT, "an EC's count is above 2^31-1");
     return ECB_OK;
 }
 
@@ -3175,7 +3183,9 @@ __global__ void k_piece_place(const PieceDesc* P, u64 n_total, u64 n_bits, const
     if (s0 < 0 || s1 < s0 || (u64)s1 > d.nnz) { atomicOr(&ctr->err, ERR_CONTRACT); return; }
     const u32 r = bit_rank(bitmap, wprefix, f);
     if (r >= n_total) return;
-    place[r] = make_uint4((u32)e + 1u, (u32)(s1 - s0), (u32)d.counts[e], blockIdx.y);    // (two pieces claiming one first read: either, whole; the caller reports it)
+    const u32 cnt = (u32)d.counts[e];
+    if (cnt > 0x7FFFFFFFu) atomicOr(&ctr->err, ERR_COUNT);     // (an entry of N is an int32)
+    place[r] = make_uint4((u32)e + 1u, (u32)(s1 - s0), cnt, blockIdx.y);    // (two pieces claiming one first read: either, whole; the caller reports it)
 }
 // One thread per row of the result: neighbours write neighbouring rows, and read rows that follow each other within their piece
 // (a piece is in first-read order itself).
@@ -3418,6 +3428,7 @@ int ecb_push_cells(ecb_handle* h, const uint32_t* meta, uint64_t first_read, siz
     if (!n) return ECB_OK;
     if (!meta) return fail(h, ECB_ERR_ARG, "null meta");
     HIPCHK(h, hipSetDevice(h->device));
+    if (first_read >= (1ull << 32) - 1 || (u64)n >= (1ull << 32) - 1 - first_read) return fail(h, ECB_ERR_LIMIT, "more than 2^32-2 reads");
     const u64 need = first_read + n;
     const int rc = ensure_meta(h, need);
     if (rc != ECB_OK) return rc;
@@ -3989,6 +4000,7 @@ int ecb_ms_filter(ecb_handle* h, uint32_t n_cells, int64_t minimum_count, ecb_ms
     if ((h->adopted || h->assembled) && !h->ms_adopted) return fail(h, ECB_ERR_STATE, "multisample across GPUs: no triples adopted yet (ecb_ms_adopt_triples_device)");
     if (!n_cells || n_cells > (1u << ECB_CELL_BITS)) return fail(h, ECB_ERR_ARG, "n_cells out of range");
     HIPCHK(h, hipSetDevice(h->device));
+    h->ms_filtered = false;                          // (until this call succeeds: its pool buffers are regrown under the last result)
     hipStream_t st = h->stream;
     const u64 T = h->n_triples, E = h->sizes.n_ecs;
     const u64 min_count = minimum_count <= 0 ? 1ull : (u64)minimum_count;          // bam_utils_multisample.py:596-597
@@ -4030,10 +4042,10 @@ int ecb_ms_filter(ecb_handle* h, uint32_t n_cells, int64_t minimum_count, ecb_ms
         HIPCHK(h, hipMemsetAsync(big + E, 0, 4, st));
         HIPCHK(h, hipMemsetAsync(giant + max_giant, 0, 4, st));
         HIPCHK(h, hipMemsetAsync(gfec, 0xFF, max_giant * MSF_FILES * 4, st));
-        k_msf2_ecs_small<<<nblk(E, TPB), TPB, 0, st>>>(meta, first, seg, (u32)E, total, firstfile, min_count, cellkey, keep_ec, big, big + E, giant, giant + max_giant);
-        k_msf2_ecs_big<<<(unsigned)std::min<u64>(std::max<u64>(E / MSF_SMALL, 1), 4096), TPB, 0, st>>>(meta, first, seg, big, big + E, total, firstfile, min_count, cellkey, keep_ec);
-        k_msf2_giant_fec<<<1024, TPB, 0, st>>>(meta, first, seg, giant, giant + max_giant, total, min_count, gfec, keep_ec);
-        k_msf2_giant_offer<<<1024, TPB, 0, st>>>(meta, first, seg, giant, giant + max_giant, firstfile, gfec, cellkey);
+        k_msf2_ecs_small<<<nblk(E, TPB), TPB, 0, st>>>(meta, first, seg, (u32)E, n_cells, total, firstfile, min_count, cellkey, keep_ec, big, big + E, giant, giant + max_giant);
+        k_msf2_ecs_big<<<(unsigned)std::min<u64>(std::max<u64>(E / MSF_SMALL, 1), 4096), TPB, 0, st>>>(meta, first, seg, big, big + E, n_cells, total, firstfile, min_count, cellkey, keep_ec);
+        k_msf2_giant_fec<<<1024, TPB, 0, st>>>(meta, first, seg, giant, giant + max_giant, n_cells, total, min_count, gfec, keep_ec);
+        k_msf2_giant_offer<<<1024, TPB, 0, st>>>(meta, first, seg, giant, giant + max_giant, n_cells, firstfile, gfec, cellkey);
     }
     // 3. cell order: by (first appearance of the EC in the cell's first file, first read), then -- stable -- by that file
     int rc, where = 0;
@@ -4075,7 +4087,7 @@ int ecb_ms_filter(ecb_handle* h, uint32_t n_cells, int64_t minimum_count, ecb_ms
     k_msf2_pairflag<<<nblk(T, TPB), TPB, 0, st>>>(ec, meta, T, new_cell, flag);
     rc = excl_scan(h, flag, T, pos, &K); if (rc != ECB_OK) return rc;
     if (K >= (1ull << 31)) return fail(h, ECB_ERR_LIMIT, "N has more than 2^31-1 non-zeros");
-    k_msf2_pairs<<<nblk(T, TPB), TPB, 0, st>>>(ec, meta, cnt, flag, pos, T, new_cell, new_rank, k0, v0);
+    k_msf2_pairs<<<nblk(T, TPB), TPB, 0, st>>>(ec, meta, cnt, flag, pos, T, new_cell, new_rank, k0, v0, d_err);
     const u64 nnz_n = K;
     {
         u32 sbits = 1;
@@ -4097,7 +4109,10 @@ int ecb_ms_filter(ecb_handle* h, uint32_t n_cells, int64_t minimum_count, ecb_ms
     { const u32 last = (u32)nnz_a; HIPCHK(h, hipMemcpyAsync(h->f_ipa + E2, &last, 4, hipMemcpyHostToDevice, st)); HIPCHK(h, hipStreamSynchronize(st)); }
     POOL(h, P_F_IXA, h->f_ixa, nnz_a); POOL(h, P_F_DAA, h->f_daa, nnz_a);
     k_msf_rows<<<nblk(E, TPB), TPB, 0, st>>>(h->indptr, h->indices, h->data, keep_ec, new_rank, reinterpret_cast<const u32*>(h->f_ipa), E, h->f_ixa, h->f_daa);
+    u32 err = 0;
+    HIPCHK(h, hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));
+    if (err & 4u) return fail(h, ECB_ERR_LIMIT, "an entry of N (the reads of one EC in one cell) is above 2^31-1");
     h->msf.n_cells_seen = C; h->msf.n_cells_kept = S; h->msf.n_ecs_kept = E2; h->msf.nnz_a = nnz_a; h->msf.nnz_n = nnz_n;
     h->ms_filtered = true;
     *out = h->msf;

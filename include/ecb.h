@@ -127,7 +127,8 @@ int ecb_hint_reads(ecb_handle* h, uint64_t max_reads);
 /* Multisample only (ECB_F_MULTISAMPLE): per read, in read order, for reads [first_read, first_read + n):
  *   meta = cell id (bits 0-21; dictionary-encoded by the host from the read name, bam_utils_multisample.py:270-280)
  *        | input file index << 22 (bits 22-31; the reference scans one file per worker, :473-480).
- * The host leaves out the last read of every file (the reference never counts it, :306-321). */
+ * The host leaves out the last read of every file (the reference never counts it, :306-321).
+ * first_read + n beyond 2^32 - 2 reads: ECB_ERR_LIMIT. */
 int ecb_push_cells(ecb_handle* h, const uint32_t* meta, uint64_t first_read, size_t n);
 /* The same from device memory (the cell stream of a resident workload: +4 bytes per read).  The copy is queued on the
  * handle's own stream and waits for nothing of the caller's: whatever produced d_meta must have COMPLETED before the call (as for
@@ -162,7 +163,10 @@ int ecb_export_pairs(ecb_handle* h, uint32_t* ec, uint32_t* meta, uint32_t* coun
  * minimum_count reads (<= 0 means 1) dropped, ECs left without a cell dropped and the rest re-ranked, N as CSC over
  * (kept EC, kept cell), and the rows of A of the kept ECs.  n_cells = number of cell ids the host handed out.
  * ecb_ms_export fills caller buffers of the sizes ecb_ms_filter reported: kept_cells[n_cells_kept] = cell ids in sample
- * order; A as CSR (n_ecs_kept + 1, nnz_a, nnz_a); N as CSC (n_cells_kept + 1, nnz_n, nnz_n).  Any pointer may be NULL. */
+ * order; A as CSR (n_ecs_kept + 1, nnz_a, nnz_a); N as CSC (n_cells_kept + 1, nnz_n, nnz_n).  Any pointer may be NULL.
+ * A read whose cell id is not below n_cells: ECB_ERR_CONTRACT (nothing is touched beyond n_cells).  An entry of N -- the reads of
+ * one EC in one cell, over all files -- above 2^31 - 1: ECB_ERR_LIMIT.  After a failed call ecb_ms_export refuses until the next
+ * ecb_ms_filter succeeds. */
 typedef struct ecb_ms_sizes {
     uint64_t n_cells_seen;       /* cells with at least one read */
     uint64_t n_cells_kept;       /* S */
@@ -231,7 +235,8 @@ int ecb_table_adopt_batch_device(ecb_handle* h, uint32_t n_tables, const void* c
  * together on an EMPTY handle with ecb_assemble_ranges_device: the global rank of an EC = the number of ECs with an earlier
  * first read (a bitmap over the reads, marked from all pieces, and its prefix popcount), rows copied to their places.
  * Afterwards that handle behaves as finalized (ecb_finalize returns the sizes again; ecb_export, ecb_export_device), but it
- * holds no table: the per-read and hash exports refuse.  ECB_ERR_CONTRACT if two pieces name the same first read.
+ * holds no table: the per-read and hash exports refuse.  ECB_ERR_CONTRACT if two pieces name the same first read; ECB_ERR_LIMIT if a
+ * count (read as uint32) is above 2^31 - 1.
  * (bam_utils.py:680-724: the ordered merge of the workers' dicts; the order of the result is the same.) */
 int ecb_export_firsts_device(ecb_handle* h, void* d_firsts);
 int ecb_assemble_ranges_device(ecb_handle* h, uint32_t n_pieces, const void* const* d_indptr, const void* const* d_indices,

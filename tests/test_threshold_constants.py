@@ -21,6 +21,9 @@ PINNED = [
     ("ecb.hip", "CVU_MAX", "3072", "test_per_haplotype_csc_columns_on_the_piece_limits"),
     ("ecb.hip", "CVU_TSZ", "4096", "test_per_haplotype_csc_columns_on_the_piece_limits (a piece of CVU_MAX fills 3/4 of it)"),
     ("ecb.hip", "QSTRIPES", "64", "test_every_read_deferred"),
+    ("ecb.hip", "MSF_LDS_CELLS", "8192", "test_gpu_multisample.py::test_cell_counts_on_the_lds_limit_and_the_radix_tile"),
+    ("ecb.hip", "MSF_SMALL", "256", "test_gpu_multisample.py::test_ecs_on_the_thread_workgroup_and_grid_limits_and_every_meta_edge"),
+    ("ecb.hip", "MSF_GIANT", "1u << 15", "test_gpu_multisample.py::test_ecs_on_the_thread_workgroup_and_grid_limits_and_every_meta_edge"),
 ]
 
 
@@ -33,11 +36,22 @@ def _source(name):
 def test_constants_the_boundary_tests_straddle(fname, name, value, test):
     defs = re.findall(r"constexpr\s+(?:u32|int)\s+%s\s*=\s*([^;]+);" % name, _source(fname))
     assert len(defs) == 1, "%s: %d definitions of %s" % (fname, len(defs), name)
-    assert defs[0].strip() == value, ("%s is now %s in %s (was %s): move the inputs of test_gpu_thresholds.py::%s onto the new value"
-                                      % (name, defs[0].strip(), fname, value, test))
+    where = test if "::" in test else "test_gpu_thresholds.py::" + test
+    assert defs[0].strip() == value, ("%s is now %s in %s (was %s): move the inputs of %s onto the new value"
+                                      % (name, defs[0].strip(), fname, value, where))
 
 
 def test_records_per_lane_default():
     """WT = 64 * ECB_RPL records: ECB_RPL defaults to 8 (512-record tiles), and k_stream insists on 512."""
     assert re.search(r"#ifndef ECB_RPL\s*\n#define ECB_RPL 8\b", _source("ecb.hip"))
     assert "static_assert(WT == 512" in _source("k_stream.inc")
+
+
+def test_cell_bits():
+    """22 bits of cell id under 10 of file in the meta word: ecb.h, the host that packs it, and test_gpu_multisample.py's top cell
+    2^22 - 1 in file 1023 (meta 0xFFFFFFFF)."""
+    with open(os.path.join(CSRC, "..", "..", "include", "ecb.h")) as f:
+        assert re.findall(r"#define ECB_CELL_BITS\s+(\d+)", f.read()) == ["22"]
+    with open(os.path.join(CSRC, "..", "bam_utils_multisample.py")) as f:
+        assert re.findall(r"^CELL_BITS\s*=\s*(\d+)", f.read(), re.M) == ["22"]
+    assert re.search(r"constexpr u32 MS_FILE_BITS = 32 - ECB_CELL_BITS;", _source("ecb.hip"))
