@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
 """Command line with the reference's hot-path sub-commands and options (``alntools/cli.py:43-113``):
-``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``, ``apply-genotypes``, ``ecmerge``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
+``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``, ``apply-genotypes``, ``ecmerge``, ``salmon2ec``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
 from __future__ import annotations
 
 import glob
@@ -123,6 +123,23 @@ def ecmerge(inputs, directory, output, verbose):
         methods.ecmerge(input_files, output)
     except Exception:
         sys.exit(1)                                                  # (logged as "Error: ..." by bin_utils.ecmerge)
+
+
+@cli.command('salmon2ec', options_metavar='<options>', short_help='convert a salmon eq_classes file to EC')
+@click.argument('salmon_dir', metavar='salmon_dir', type=click.Path(exists=True, resolve_path=True, dir_okay=True))
+@click.argument('ec_file', metavar='ec_file', type=click.Path(resolve_path=True, dir_okay=False, writable=True))
+@click.option('-s', '--sample', metavar='sample', default='NA', help="sample identifier")
+@click.option('-t', '--targets', metavar='FILE', type=click.Path(exists=True, resolve_path=True, file_okay=True, dir_okay=False), help="target file")
+@click.option('-v', '--verbose', count=True, help='enables verbose mode')
+def salmon2ec(salmon_dir, ec_file, sample, targets, verbose):
+    """
+    Convert a salmon eq_classes file to a binary EC file (ec_file)
+    """
+    utils.configure_logging(verbose)
+    try:
+        methods.salmon2ec(salmon_dir, ec_file, sample, targets)
+    except Exception:
+        sys.exit(1)                                                  # (logged as "Error: ..." by salmon_utils.convert)
 
 
 if __name__ == '__main__':

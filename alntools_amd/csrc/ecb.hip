@@ -5083,6 +5083,334 @@ extern "C" int ecb_combine(int device, uint32_t n_parts, const ecb_combine_part*
     return ECB_OK;
 }
 
+// ---- salmon2ec: CSR A and N of a salmon eq_classes.txt EC section (ecb_salmon_ecs / ecb_salmon_ecs_device) ------------------------------
+// (salmon_utils.py:31-127: every EC line `k t_1 .. t_k count`, each target id -> (transcript, haplotype); A[row, transcript] = sum of 2^h over
+//  the line's targets, columns ascending; N = the non-zero counts.)  No serial walk over lines and no per-byte atomics:
+//   k_sl_count   one workgroup per 4 KB tile (16 bytes per thread, one 16-byte load): its line ends and field starts (a digit after a
+//                non-digit), one pair of counts per tile; the library's one-pass scan (scan_launch) turns them into each tile's first line
+//                and first field
+//   k_sl_place   the tile again: every byte checked with its neighbours, every line end writes its line's field end, and every field is
+//                parsed by the thread that holds its first digit (into the next thread's bytes when it runs on) -> value and line per field
+//   k_sl_fields  one thread per field: the line's field range says what it is (k, target id or count); k and the targets are checked,
+//                a target becomes (row << 32 | column << 5 | haplotype, 1 << haplotype), a count goes to its line
+//   radix_sort_pairs64 on the row and column bits only (rows come in order, the sort orders the columns within them); the haplotype
+//   rides in the key's low 5 bits, so a target id repeated in a line is an equal neighbour after the sort
+//   k_sl_heads   head flags of the (row, column) runs, repeats refused; scan; k_sl_emit ORs each run's bits (a run holds at most n_haps
+//                pairs) into one non-zero; k_sl_rowptr row pointers by binary search; k_sl_nkeep / scan / k_sl_nemit: N
+// A refusal names the lowest offending line: every check does an atomicMin of (line << 8 | reason) on one word, which only an error
+// touches.  The targets of a well-formed text are slot f - 2 l - 1 of field f in line l (k and the count of every line before it are not
+// targets); when some line is malformed that numbering does not hold, and the fields go once more into one slot each (the non-targets as
+// a key that sorts last) so that repeats are still found in the lines before the first malformed one.
+namespace {
+using u8 = unsigned char;
+constexpr u32 SL_TILE = TPB * 16;                         // bytes per workgroup of k_sl_count / k_sl_place
+constexpr u32 SL_NONE = 256u;                             // "no byte" (before the start, after the end): not a digit, not a separator
+constexpr u64 SL_NO_ERR = ~0ull;
+enum : u32 { SL_R_BYTE = 1, SL_R_EMPTY, SL_R_BIG, SL_R_FEW, SL_R_K, SL_R_TARGET, SL_R_REPEAT, SL_R_COUNT };
+const char* sl_reason(u32 r) {
+    switch (r) {
+    case SL_R_BYTE: return "a byte other than a digit, tab or line end";
+    case SL_R_EMPTY: return "an empty field";
+    case SL_R_BIG: return "a value of 2^31 or more";
+    case SL_R_FEW: return "fewer than 2 fields";
+    case SL_R_K: return "k differs from the number of target ids";
+    case SL_R_TARGET: return "a target id at or beyond the number of targets";
+    case SL_R_REPEAT: return "a target id repeated within the line";
+    case SL_R_COUNT: return "the number of EC lines differs from the header's";
+    default: return "unknown";
+    }
+}
+__device__ __forceinline__ bool sl_digit(u32 c) { return c - 48u < 10u; }
+// value * 10 + digit, held at 2^31 once it gets there (every value from 2^31 on is refused alike)
+__device__ __forceinline__ u32 sl_acc(u32 acc, u32 c) { const u64 x = (u64)acc * 10u + (c - 48u); return x < (1ull << 31) ? (u32)x : 1u << 31; }
+__device__ __forceinline__ void sl_err(u64* err, u64 line, u32 reason) { atomicMin(reinterpret_cast<unsigned long long*>(err), (unsigned long long)(line << 8 | reason)); }
+// the 16 bytes at base (zero past the end), and the bytes just before and after them (SL_NONE outside the text)
+__device__ __forceinline__ void sl_load(const u8* text, u64 L, u64 base, u32 w[4], u32& prev, u32& next) {
+    if (base + 16 <= L && (reinterpret_cast<uintptr_t>(text + base) & 15u) == 0u) {
+        const uint4 q = *reinterpret_cast<const uint4*>(text + base);
+        w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
+    } else {
+        w[0] = w[1] = w[2] = w[3] = 0u;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) if (base + k < L) w[k >> 2] |= (u32)text[base + k] << (8 * (k & 3));
+    }
+    prev = base > 0 && base - 1 < L ? (u32)text[base - 1] : SL_NONE;
+    next = base + 16 < L ? (u32)text[base + 16] : SL_NONE;
+}
+__device__ __forceinline__ u32 sl_byte(const u32 w[4], int j) { return (w[j >> 2] >> (8 * (j & 3))) & 255u; }
+// line ends and field starts among this thread's 16 bytes
+__device__ __forceinline__ void sl_counts(const u32 w[4], u32 prev, u64 base, u64 L, u32& nl, u32& fs) {
+    nl = 0; fs = 0;
+    u32 pc = prev;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const u32 c = base + j < L ? sl_byte(w, j) : SL_NONE;
+        nl += c == 10u;
+        fs += sl_digit(c) && !sl_digit(pc);
+        pc = c;
+    }
+}
+// exclusive prefix of a and b over the workgroup's threads, and the workgroup's totals
+__device__ __forceinline__ void sl_block_scan(u32& a, u32& b, u32& ta, u32& tb) {
+    __shared__ u32 s_a[TPB / 64], s_b[TPB / 64];
+    const u32 ia = wave_incl_scan(a), ib = wave_incl_scan(b), w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 63u) { s_a[w] = ia; s_b[w] = ib; }
+    __syncthreads();
+    u32 pa = 0, pb = 0;
+    ta = 0; tb = 0;
+#pragma unroll
+    for (u32 k = 0; k < TPB / 64; ++k) { if (k < w) { pa += s_a[k]; pb += s_b[k]; } ta += s_a[k]; tb += s_b[k]; }
+    a = pa + ia - a; b = pb + ib - b;
+}
+__global__ __launch_bounds__(TPB) void k_sl_count(const u8* text, u64 L, u32* blk_nl, u32* blk_fs) {
+    const u64 base = blockIdx.x * (u64)SL_TILE + threadIdx.x * 16ull;
+    u32 w[4], prev, next, nl = 0, fs = 0;
+    if (base < L) {
+        sl_load(text, L, base, w, prev, next);
+        sl_counts(w, prev, base, L, nl, fs);
+    }
+    u32 ta, tb;
+    sl_block_scan(nl, fs, ta, tb);
+    if (threadIdx.x == 0) { blk_nl[blockIdx.x] = ta; blk_fs[blockIdx.x] = tb; }
+}
+// every byte checked; line l's end writes fend[l] (its fields are [fend[l - 1], fend[l])); field f's value (2^31 for 2^31 and above) and line
+__global__ __launch_bounds__(TPB) void k_sl_place(const u8* text, u64 L, const u32* blk_nl, const u32* blk_fs, u32 fs_total, u32* fval, u32* fline,
+                                                  u32* fend, u64* err) {
+    const u64 base = blockIdx.x * (u64)SL_TILE + threadIdx.x * 16ull;
+    u32 w[4] = {0u, 0u, 0u, 0u}, prev = SL_NONE, next = SL_NONE, nl = 0, fs = 0;
+    if (base < L) {
+        sl_load(text, L, base, w, prev, next);
+        sl_counts(w, prev, base, L, nl, fs);
+    }
+    u32 ta, tb;
+    sl_block_scan(nl, fs, ta, tb);
+    if (base >= L) return;
+    u32 l = blk_nl[blockIdx.x] + nl, f = blk_fs[blockIdx.x] + fs;
+    u32 acc = 0;
+    bool open = false;                                    // a field whose first digit is ours is being read
+    u32 pc = prev;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const u64 p = base + j;
+        if (p < L) {
+            const u32 c = sl_byte(w, j), nc = j < 15 ? (p + 1 < L ? sl_byte(w, j + 1) : SL_NONE) : next;
+            if (sl_digit(c)) {
+                if (!sl_digit(pc)) { open = true; acc = c - 48u; }
+                else if (open) acc = sl_acc(acc, c);
+                if (open && !sl_digit(nc)) {
+                    fval[f] = acc; fline[f] = l; ++f; open = false;
+                }
+            } else if (c == 10u) {
+                if (!sl_digit(pc) && pc != 13u) sl_err(err, l, SL_R_EMPTY);
+                fend[l] = f; ++l;
+            } else if (c == 9u) {
+                if (!sl_digit(pc) || !sl_digit(nc)) sl_err(err, l, SL_R_EMPTY);
+            } else if (c == 13u) {
+                if (nc != 10u) sl_err(err, l, SL_R_BYTE);
+                else if (!sl_digit(pc)) sl_err(err, l, SL_R_EMPTY);
+            } else {
+                sl_err(err, l, SL_R_BYTE);
+            }
+            if (p + 1 == L && c != 10u) fend[l] = fs_total;    // (the last line has no line end)
+            pc = c;
+        }
+    }
+    if (open) {                                           // our last field runs on into the next thread's bytes
+        u64 p = base + 16;
+        for (; p < L; ++p) {
+            const u32 c = text[p];
+            if (!sl_digit(c)) break;
+            acc = sl_acc(acc, c);
+        }
+        fval[f] = acc; fline[f] = l;
+    }
+}
+// field f of line l: k (the first), a target id (between), or the count (the last).  dense: target slot f - 2 l - 1 (exact when every line has
+// at least 2 fields; slots out of range are skipped); otherwise slot f for every field, the non-targets (and targets out of range) as ~0.
+__global__ __launch_bounds__(TPB) void k_sl_fields(const u32* fval, const u32* fline, const u32* fend, u32 n_fields, u32 n_targets, const u32* tcol,
+                                                   const u32* thap, bool dense, u64 n_slots, u64* keys, u32* vals, u32* cnt, u64* err) {
+    const u64 f = blockIdx.x * (u64)TPB + threadIdx.x;
+    if (f >= n_fields) return;
+    const u32 v = fval[f], l = fline[f];
+    const u32 f0 = l ? fend[l - 1] : 0u, nf = fend[l] - f0, i = (u32)f - f0;
+    if (v >= (1u << 31)) sl_err(err, l, SL_R_BIG);
+    if (i == 0 && nf < 2) sl_err(err, l, SL_R_FEW);
+    else if (i == 0 && v != nf - 2) sl_err(err, l, SL_R_K);
+    if (nf >= 2 && i == nf - 1) cnt[l] = v;
+    const bool target = nf >= 2 && i >= 1 && i + 1 < nf;
+    u64 key = ~0ull;
+    u32 val = 0;
+    if (target) {
+        if (v >= n_targets) sl_err(err, l, SL_R_TARGET);
+        else { const u32 h = thap[v]; key = (u64)l << 32 | (tcol[v] << 5 | h); val = 1u << h; }
+    }
+    if (dense) {
+        const long long s = (long long)f - 2ll * l - 1;
+        if (!target || s < 0 || (u64)s >= n_slots) return;
+        keys[s] = key; vals[s] = val;
+    } else {
+        keys[f] = key; vals[f] = val;
+    }
+}
+__global__ void k_sl_targets(const u32* tcol, const u32* thap, u32 T, u32 n_loci, u32 n_haps, u32* bad) {
+    const u64 t = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+    const bool b = t < T && (tcol[t] >= n_loci || thap[t] >= n_haps);
+    if (__ballot(b) && (threadIdx.x & 63u) == 0u) atomicOr(bad, 1u);
+}
+// sorted keys: flag = first of its (row, column) run; an equal neighbour is a repeated target id
+__global__ __launch_bounds__(TPB) void k_sl_heads(const u64* keys, u64 n, u32* flag, u64* err) {
+    const u64 i = blockIdx.x * (u64)TPB + threadIdx.x;
+    if (i >= n) return;
+    const u64 k = keys[i];
+    u32 h = 0;
+    if (k != ~0ull) {
+        const u64 q = i ? keys[i - 1] : ~0ull;
+        if (q == k) sl_err(err, k >> 32, SL_R_REPEAT);
+        h = i == 0 || (q >> 5) != (k >> 5);
+    }
+    flag[i] = h;
+}
+__global__ __launch_bounds__(TPB) void k_sl_emit(const u64* keys, const u32* vals, const u32* flag, const u32* pos, u64 n, u64 cap, int* indices, int* data) {
+    const u64 i = blockIdx.x * (u64)TPB + threadIdx.x;
+    if (i >= n || !flag[i] || pos[i] >= cap) return;
+    const u64 run = keys[i] >> 5;
+    u32 m = 0;
+    for (u64 j = i; j < n && (keys[j] >> 5) == run; ++j) m |= vals[j];
+    indices[pos[i]] = (int)((u32)run & 0x7FFFFFFu);
+    data[pos[i]] = (int)m;
+}
+__global__ void k_sl_rowptr(const u64* keys, u64 n, const u32* pos, u32 n_rows, int* indptr) {
+    const u64 r = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+    if (r <= n_rows) indptr[r] = (int)pos[lower_bound_u64(keys, n, r << 32)];
+}
+__global__ void k_sl_nkeep(const u32* cnt, u32 n, u32* keep) {
+    const u64 l = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+    if (l < n) keep[l] = cnt[l] != 0u;
+}
+__global__ void k_sl_nemit(const u32* cnt, const u32* keep, const u32* pos, u32 n, int* indices, int* data) {
+    const u64 l = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+    if (l >= n || !keep[l]) return;
+    indices[pos[l]] = (int)l;
+    data[pos[l]] = (int)cnt[l];
+}
+u64 sl_bits(u64 x) { u64 b = 0; for (; x; x >>= 1) b = b << 1 | 1ull; return b; }
+}  // namespace
+
+extern "C" int ecb_salmon_ecs_device(int device, const void* d_text, uint64_t n_bytes, uint32_t n_ecs, uint32_t n_targets, const void* d_target_col,
+                                     const void* d_target_hap, uint32_t n_loci, uint32_t n_haps, uint64_t capacity, void* d_out_indptr,
+                                     void* d_out_indices, void* d_out_data, void* d_out_n_indices, void* d_out_n_data, uint64_t* out_sizes) {
+    if (!out_sizes || !d_out_indptr || (n_bytes && !d_text) || (n_targets && (!d_target_col || !d_target_hap)) || !n_loci || !n_haps || n_haps > 31 ||
+        (capacity && (!d_out_indices || !d_out_data)) || (n_ecs && (!d_out_n_indices || !d_out_n_data)))
+        return fail(nullptr, ECB_ERR_ARG, "salmon: bad argument");
+    if (n_loci >= MAX_LOCI) return fail(nullptr, ECB_ERR_ARG, "salmon: n_loci out of range (1 .. 2^26-3)");
+    if (n_ecs >= (1u << 31) - 1u || n_targets >= (1u << 31)) return fail(nullptr, ECB_ERR_LIMIT, "salmon: E or T beyond int32");
+    if (device < 0 || device >= CV_MAX_DEV || hipSetDevice(device) != hipSuccess) return fail(nullptr, ECB_ERR_NO_DEVICE, "no such device");
+    auto refuse = [](u64 e) { const u32 r = (u32)(e & 255u); return fail(nullptr, ECB_ERR_CONTRACT, "EC line %llu: %s (reason %u)", (unsigned long long)(e >> 8), sl_reason(r), r); };
+    StreamGuard sg;
+    if (hipStreamCreate(&sg.s) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "salmon: stream");
+    hipStream_t st = sg.s;
+    const u8* text = (const u8*)d_text;
+    const u32 *tcol = (const u32*)d_target_col, *thap = (const u32*)d_target_hap;
+    const u64 L = n_bytes, nb = std::max<u64>(1, (L + SL_TILE - 1) / SL_TILE);
+    if (nb >= (1ull << 31)) return fail(nullptr, ECB_ERR_LIMIT, "salmon: text too long");
+    std::vector<DevBuf<>> S;
+    u32 *blk_nl = fresh<u32>(S, nb), *blk_fs = fresh<u32>(S, nb), *nl_ex = fresh<u32>(S, nb), *fs_ex = fresh<u32>(S, nb);
+    u32 *sc1 = fresh<u32>(S, scan_words(nb)), *sc2 = fresh<u32>(S, scan_words(nb));
+    u64* words = fresh<u64>(S, 8);                        // [0] lowest (line << 8 | reason), [1] [2] line ends, field starts, [3] bad target map, [4] [5] scan totals
+    if (missing(S)) return fail(nullptr, ECB_ERR_HIP, "salmon: out of device memory");
+    u64* err = words;
+    u32* bad = reinterpret_cast<u32*>(words + 3);
+    u64 back[8] = {0};
+    u8 last = 10;
+    auto sync = [&](const char* what) -> int {
+        if (hipMemcpyAsync(back, words, 64, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+            return fail(nullptr, ECB_ERR_HIP, "salmon: %s: %s", what, hipGetErrorString(hipGetLastError()));
+        return ECB_OK;
+    };
+    if (hipMemsetAsync(words, 0, 64, st) != hipSuccess || hipMemsetAsync(err, 0xFF, 8, st) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "salmon: memset");
+    // 1. the target map; line ends and field starts per tile, placed
+    if (n_targets) k_sl_targets<<<nblk(n_targets, TPB), TPB, 0, st>>>(tcol, thap, n_targets, n_loci, n_haps, bad);
+    if (L) {
+        k_sl_count<<<(unsigned)nb, TPB, 0, st>>>(text, L, blk_nl, blk_fs);
+        if (scan_launch(st, blk_nl, nb, nl_ex, sc1, words + 1) != hipSuccess || scan_launch(st, blk_fs, nb, fs_ex, sc2, words + 2) != hipSuccess)
+            return fail(nullptr, ECB_ERR_HIP, "salmon: scan");
+        if (hipMemcpyAsync(&last, text + L - 1, 1, hipMemcpyDeviceToHost, st) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "salmon: copy");
+    }
+    int rc = sync("count");
+    if (rc != ECB_OK) return rc;
+    if (back[3]) return fail(nullptr, ECB_ERR_CONTRACT, "salmon: the target map has a column at or beyond n_loci or a haplotype at or beyond n_haps");
+    const u64 n_lines = back[1] + (L && last != 10), NF = back[2];
+    if (NF >= (1ull << 30) || n_lines >= (1ull << 31) - 1) return fail(nullptr, ECB_ERR_LIMIT, "salmon: %llu fields in %llu lines: beyond the limits (2^30, 2^31-1)",
+                                                                       (unsigned long long)NF, (unsigned long long)n_lines);
+    const u64 count_err = n_lines != n_ecs ? (std::min<u64>(n_lines, n_ecs) << 8 | SL_R_COUNT) : SL_NO_ERR;
+    // 2. bytes checked, fields parsed; 3. fields classified, targets to keys (dense slots)
+    u32 *fval = fresh<u32>(S, NF), *fline = fresh<u32>(S, NF), *fend = fresh<u32>(S, n_lines), *cnt = fresh<u32>(S, n_lines);
+    u64 *keys0 = fresh<u64>(S, NF), *keys1 = fresh<u64>(S, NF);
+    u32 *vals0 = fresh<u32>(S, NF), *vals1 = fresh<u32>(S, NF), *flag = fresh<u32>(S, NF), *pos = fresh<u32>(S, NF + 1), *sc3 = fresh<u32>(S, scan_words(NF));
+    SortScratch ss{fresh<u32>(S, rs_words(NF)), fresh<u32>(S, RS_AUX_WORDS), fresh<u32>(S, rs_scan_blocks(NF) + 8), words + 6};
+    if (missing(S)) return fail(nullptr, ECB_ERR_HIP, "salmon: out of device memory");
+    if (L) k_sl_place<<<(unsigned)nb, TPB, 0, st>>>(text, L, nl_ex, fs_ex, (u32)NF, fval, fline, fend, err);
+    const u64 NP = NF >= 2 * n_lines ? NF - 2 * n_lines : 0;
+    if (NF) k_sl_fields<<<nblk(NF, TPB), TPB, 0, st>>>(fval, fline, fend, (u32)NF, n_targets, tcol, thap, true, NP, keys0, vals0, cnt, err);
+    if ((rc = sync("parse")) != ECB_OK) return rc;
+    u64* kk[2] = {keys0, keys1}; u32* vv[2] = {vals0, vals1};
+    int where = 0;
+    if (back[0] != SL_NO_ERR) {
+        // a malformed line: every field in a slot of its own, sorted on all bits, so that repeats in the lines before it are found too
+        k_sl_fields<<<nblk(NF, TPB), TPB, 0, st>>>(fval, fline, fend, (u32)NF, n_targets, tcol, thap, false, NF, keys0, vals0, cnt, err);
+        const hipError_t e = radix_sort_pairs64(st, kk, vv, NF, ss, &where);
+        if (e != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "salmon: radix sort: %s", hipGetErrorString(e));
+        k_sl_heads<<<nblk(NF, TPB), TPB, 0, st>>>(kk[where], NF, flag, err);
+        if ((rc = sync("repeats")) != ECB_OK) return rc;
+        return refuse(std::min(back[0], count_err));
+    }
+    // 4. sort within rows (the row and column bits only); runs, repeats refused
+    const u64 mask = sl_bits(n_lines ? n_lines - 1 : 0) << 32 | sl_bits((u64)(n_loci - 1) << 5 | 31u);
+    const hipError_t e = radix_sort_pairs64(st, kk, vv, NP, ss, &where, mask);
+    if (e != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "salmon: radix sort: %s", hipGetErrorString(e));
+    const u64* keys = kk[where]; const u32* vals = vv[where];
+    if (NP) k_sl_heads<<<nblk(NP, TPB), TPB, 0, st>>>(keys, NP, flag, err);
+    if (scan_launch(st, flag, NP, pos, sc3, words + 4, 1, pos + NP) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "salmon: scan");
+    if ((rc = sync("runs")) != ECB_OK) return rc;
+    if (std::min(back[0], count_err) != SL_NO_ERR) return refuse(std::min(back[0], count_err));
+    const u64 nnz = NP ? back[4] : 0;
+    if (nnz > capacity) return fail(nullptr, ECB_ERR_LIMIT, "salmon: %llu non-zeros, room for %llu", (unsigned long long)nnz, (unsigned long long)capacity);
+    if (nnz >= (1ull << 31)) return fail(nullptr, ECB_ERR_LIMIT, "salmon: non-zeros beyond int32");
+    // 5. A: one non-zero per run, row pointers; N: the non-zero counts
+    if (NP) k_sl_emit<<<nblk(NP, TPB), TPB, 0, st>>>(keys, vals, flag, pos, NP, capacity, (int*)d_out_indices, (int*)d_out_data);
+    k_sl_rowptr<<<nblk((u64)n_ecs + 1, TPB), TPB, 0, st>>>(keys, NP, pos, n_ecs, (int*)d_out_indptr);
+    if (n_ecs) {
+        k_sl_nkeep<<<nblk(n_ecs, TPB), TPB, 0, st>>>(cnt, n_ecs, flag);
+        if (scan_launch(st, flag, n_ecs, pos, sc3, words + 5) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "salmon: scan");
+        k_sl_nemit<<<nblk(n_ecs, TPB), TPB, 0, st>>>(cnt, flag, pos, n_ecs, (int*)d_out_n_indices, (int*)d_out_n_data);
+    }
+    if ((rc = sync("emit")) != ECB_OK) return rc;
+    out_sizes[0] = nnz;
+    out_sizes[1] = n_ecs ? back[5] : 0;
+    return ECB_OK;
+}
+
+extern "C" int ecb_salmon_ecs(int device, const char* text, uint64_t n_bytes, uint32_t n_ecs, uint32_t n_targets, const uint32_t* target_col,
+                              const uint32_t* target_hap, uint32_t n_loci, uint32_t n_haps, uint64_t capacity, int32_t* out_indptr, int32_t* out_indices,
+                              int32_t* out_data, int32_t* out_n_indices, int32_t* out_n_data, uint64_t* out_sizes) {
+    if (!out_sizes || !out_indptr || (n_bytes && !text) || (n_targets && (!target_col || !target_hap)) || (capacity && (!out_indices || !out_data)) ||
+        (n_ecs && (!out_n_indices || !out_n_data)))
+        return fail(nullptr, ECB_ERR_ARG, "salmon: bad argument");
+    if (n_ecs >= (1u << 31) - 1u || capacity >= (1ull << 31)) return fail(nullptr, ECB_ERR_LIMIT, "salmon: E or the capacity beyond int32");
+    if (device < 0 || device >= CV_MAX_DEV || hipSetDevice(device) != hipSuccess) return fail(nullptr, ECB_ERR_NO_DEVICE, "no such device");
+    DevBuf<> dt, dc, dh, oip, oix, oda, onx, ond;
+    const u64 rowb = ((u64)n_ecs + 1) * 4;
+    if (const char* why = stage_in({{&dt, text, n_bytes}, {&dc, target_col, (u64)n_targets * 4}, {&dh, target_hap, (u64)n_targets * 4}, {&oip, nullptr, rowb},
+                                    {&oix, nullptr, capacity * 4}, {&oda, nullptr, capacity * 4}, {&onx, nullptr, (u64)n_ecs * 4}, {&ond, nullptr, (u64)n_ecs * 4}}))
+        return fail(nullptr, ECB_ERR_HIP, "salmon: %s", why);
+    const int rc = ecb_salmon_ecs_device(device, dt.p, n_bytes, n_ecs, n_targets, dc.p, dh.p, n_loci, n_haps, capacity, oip.p, oix.p, oda.p, onx.p, ond.p, out_sizes);
+    if (rc != ECB_OK) return rc;
+    if (!stage_out({{out_indptr, &oip, rowb}, {out_indices, &oix, out_sizes[0] * 4}, {out_data, &oda, out_sizes[0] * 4}, {out_n_indices, &onx, out_sizes[1] * 4},
+                    {out_n_data, &ond, out_sizes[1] * 4}}))
+        return fail(nullptr, ECB_ERR_HIP, "salmon: copy from the device");
+    return ECB_OK;
+}
+
 // ---- ecb_merge: the multi-GPU merge for ONE process that drives several GPUs ----------------------------------------------
 // shards[r] holds the reads of contiguous read shard r on its own device; `root` is an empty handle (any device).  The same protocol as
 // alntools_amd/dist.py runs over RCCL with one process per GPU, here with peer copies (hipMemcpyPeerAsync: xGMI between the GPUs of a

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import sys
 
 import numpy as np
@@ -35,7 +36,8 @@ SYMBOLS = ("ecb_abi_version", "ecb_device_count", "ecb_create", "ecb_destroy", "
            "ecb_export_ec_keys_device", "ecb_ms_local_triples_device", "ecb_ms_adopt_triples_device", "ecb_counters", "ecb_add_counters", "ecb_profile",
            "ecb_profile_read", "ecb_profile_kernel", "ecb_csr_to_hapcsc_device", "ecb_hapcsc_to_csr_device", "ecb_release_scratch",
            "ecb_csr_to_hapcsc", "ecb_hapcsc_to_csr", "ecb_merge", "ecb_push_device_tiled", "ecb_verify_device_tiled",
-           "ecb_apply_mask_device", "ecb_apply_mask", "ecb_combine_device", "ecb_combine")
+           "ecb_apply_mask_device", "ecb_apply_mask", "ecb_combine_device", "ecb_combine",
+           "ecb_salmon_ecs_device", "ecb_salmon_ecs")
 ABI_VERSION = 4            # include/ecb.h: ECB_ABI_VERSION
 
 
@@ -161,6 +163,9 @@ def load():
     if not ab or hasattr(lib, "ecb_combine"):
         for f in (lib.ecb_combine_device, lib.ecb_combine):
             f.argtypes = [C.c_int, C.c_uint32, C.POINTER(CombinePart), C.c_uint32, C.c_uint32, C.c_uint32] + [vp] * 6 + [C.POINTER(u64)]
+    if not ab or hasattr(lib, "ecb_salmon_ecs"):
+        for f in (lib.ecb_salmon_ecs_device, lib.ecb_salmon_ecs):
+            f.argtypes = [C.c_int, vp, u64, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, u64] + [vp] * 5 + [C.POINTER(u64)]
     lib.ecb_csr_to_hapcsc_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.POINTER(u64)]
     lib.ecb_hapcsc_to_csr_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, u64, vp, vp, vp, C.POINTER(u64)]
     _lib = lib
@@ -345,6 +350,57 @@ def combine(parts, n_loci, n_haps, n_samples, device=0):
     _check(lib, entry(device, len(parts), cp, n_loci, n_haps, n_samples, *[ptr(o) for o in out], sizes))
     E, nnz_a, nnz_n = (int(x) for x in sizes)
     return out[0][:E + 1], out[1][:nnz_a], out[2][:nnz_a], out[3], out[4][:nnz_n], out[5][:nnz_n]
+
+
+ECB_ERR_CONTRACT = -5      # include/ecb.h
+#: ``ecb_salmon_ecs``'s reason codes (include/ecb.h)
+SALMON_REASONS = {1: "a byte other than a digit, tab or line end", 2: "an empty field", 3: "a value of 2^31 or more",
+                  4: "fewer than 2 fields", 5: "k differs from the number of target ids", 6: "a target id at or beyond the number of targets",
+                  7: "a target id repeated within the line", 8: "the number of EC lines differs from the header's"}
+
+
+class SalmonFormatError(EcbError):
+    """``ecb_salmon_ecs`` refused the EC section: ``line`` is the lowest offending EC line (0-based), ``reason`` its code."""
+
+    def __init__(self, code, msg, line, reason):
+        EcbError.__init__(self, code, msg)
+        self.line, self.reason = line, reason
+
+
+def salmon_ecs(text, n_ecs, target_col, target_hap, n_loci, n_haps, device=0):
+    """salmon2ec on the GPU: CSR A and N of the EC section of a salmon ``eq_classes.txt`` (the bytes after the target names;
+    ``ecb_salmon_ecs``).  ``target_col[t]`` / ``target_hap[t]``: the column and haplotype of salmon target t.  A bytes-like ``text``
+    goes through ``ecb_salmon_ecs`` (host arrays, no PyTorch), a CUDA uint8 tensor through ``ecb_salmon_ecs_device`` (with the
+    other arrays moved to its device).  Returns (indptrA, indicesA, dataA, indicesN, dataN), int32, N's being the ECs with a non-zero
+    count and their counts.  A malformed text raises :class:`SalmonFormatError` with the lowest offending line; sizes beyond the
+    limits raise :class:`EcbError` (``ECB_ERR_LIMIT``)."""
+    lib = load()
+    sizes = (C.c_uint64 * 2)()
+    if hasattr(text, "data_ptr"):
+        import torch
+        dev = text.device
+        t = text.contiguous().view(torch.uint8).reshape(-1)
+        cap = max(int((t == 9).sum().item()) - n_ecs, 0)           # (target ids = tabs - E in a well-formed text: the non-zeros' bound)
+        tc, th = (torch.as_tensor(np.asarray(a, dtype=np.int64)).to(device=dev, dtype=torch.int32).contiguous() for a in (target_col, target_hap))
+        out = [torch.empty(n, dtype=torch.int32, device=dev) for n in (n_ecs + 1, max(cap, 1), max(cap, 1), max(n_ecs, 1), max(n_ecs, 1))]
+        rc = lib.ecb_salmon_ecs_device(dev.index or 0, _dev_ptr(t), t.numel(), n_ecs, tc.numel(), _dev_ptr(tc), _dev_ptr(th), n_loci, n_haps, cap,
+                                       *[_dev_ptr(o) for o in out], sizes)
+    else:
+        t = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text, dtype=np.uint8).reshape(-1)
+        cap = max(int(np.count_nonzero(t == 9)) - n_ecs, 0)
+        tc, th = (np.ascontiguousarray(a, dtype=np.uint32) for a in (target_col, target_hap))
+        if len(tc) != len(th):
+            raise ValueError("target_col and target_hap differ in length")
+        out = [np.empty(n, dtype=np.int32) for n in (n_ecs + 1, max(cap, 1), max(cap, 1), max(n_ecs, 1), max(n_ecs, 1))]
+        rc = lib.ecb_salmon_ecs(device, _ptr(t), len(t), n_ecs, len(tc), _ptr(tc), _ptr(th), n_loci, n_haps, cap, *[_ptr(o) for o in out], sizes)
+    if rc != 0:
+        msg = (lib.ecb_last_error(None) or b"").decode()
+        m = re.match(r"EC line (\d+): .* \(reason (\d+)\)$", msg)
+        if rc == ECB_ERR_CONTRACT and m:
+            raise SalmonFormatError(rc, msg, int(m.group(1)), int(m.group(2)))
+        raise EcbError(rc, msg)
+    nnz, nnz_n = int(sizes[0]), int(sizes[1])
+    return out[0], out[1][:nnz], out[2][:nnz], out[3][:nnz_n], out[4][:nnz_n]
 
 
 class EcBuilder(object):

@@ -1,5 +1,5 @@
 # -*- coding: utf-8 -*-
-"""Same driver functions as the reference's ``alntools/methods.py:32-53, 205-210``, ``apply_genotypes`` and ``ecmerge`` for the hot path."""
+"""Same driver functions as the reference's ``alntools/methods.py:32-53, 205-210``, ``apply_genotypes``, ``ecmerge`` and ``salmon2ec`` for the hot path."""
 from __future__ import annotations
 
 from . import bam_utils, bin_utils
@@ -53,3 +53,8 @@ def apply_genotypes(ec_file, gt_file, grp_file, out_file):
 
 def ecmerge(input_files, out_file):
     bin_utils.ecmerge(input_files, out_file)
+
+
+def salmon2ec(salmon_dir, ec_filename, sample=None, target_filename=None):
+    from . import salmon_utils
+    salmon_utils.convert(salmon_dir, ec_filename, sample='NA' if sample is None else sample, target_filename=target_filename)

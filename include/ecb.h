@@ -341,6 +341,29 @@ int ecb_combine(int device, uint32_t n_parts, const ecb_combine_part* parts, uin
                 int32_t* out_indptr_a, int32_t* out_indices_a, int32_t* out_data_a, int32_t* out_indptr_n, int32_t* out_indices_n,
                 int32_t* out_data_n, uint64_t* out_sizes);
 
+/* salmon2ec (ABI 4, additive): CSR A and N of the EC section of a salmon aux_info/eq_classes.txt (the bytes after the T target names).
+ * Every line is `k t_1 ... t_k count`, tab-separated, ending in \n (or \r\n; the last line may have no line end).  Target id t is column
+ * target_col[t] (below n_loci) and haplotype target_hap[t] (below n_haps <= 31).  Row e of A holds, per column, the sum of 2^h over the
+ * line's targets of that column (columns ascending; a line without targets is an empty row); N is the lines with a non-zero count,
+ * ascending, and their counts (N's column pointers are {0, nnz_n}).  (salmon_utils.py:31-127.)
+ * The text must be well formed; otherwise ECB_ERR_CONTRACT, nothing is written, and the error text names the LOWEST offending line
+ * (0-based among the EC lines) and a reason code, as "EC line <i>: <reason> (reason <r>)":
+ *   1 a byte other than a digit, \t, \n, or \r directly before \n;  2 an empty field (leading, doubled or trailing tab, empty line);
+ *   3 a value of 2^31 or more;  4 fewer than 2 fields;  5 k differs from the number of fields - 2;  6 a target id at or beyond n_targets;
+ *   7 a target id twice in one line (two targets with the same column and haplotype count as one);
+ *   8 the number of lines differs from n_ecs (the line named is the first missing or the first extra one).
+ * A target map with a column or haplotype out of range is ECB_ERR_CONTRACT as well.  Limits (ECB_ERR_LIMIT): fewer than 2^30 fields in all,
+ * n_ecs and the non-zeros below 2^31 - 1, n_targets below 2^31, and the non-zeros within `capacity` (target ids = tabs - n_ecs bounds them).
+ * Outputs: out_indptr n_ecs + 1, out_indices / out_data `capacity`, out_n_indices / out_n_data n_ecs; out_sizes = {nnz_a, nnz_n}.
+ * ecb_salmon_ecs_device: text, target map and outputs in device memory (outputs not overlapping the inputs);
+ * ecb_salmon_ecs: the same on HOST arrays (the library allocates and frees its own device buffers). */
+int ecb_salmon_ecs_device(int device, const void* d_text, uint64_t n_bytes, uint32_t n_ecs, uint32_t n_targets, const void* d_target_col,
+                          const void* d_target_hap, uint32_t n_loci, uint32_t n_haps, uint64_t capacity, void* d_out_indptr, void* d_out_indices,
+                          void* d_out_data, void* d_out_n_indices, void* d_out_n_data, uint64_t* out_sizes);
+int ecb_salmon_ecs(int device, const char* text, uint64_t n_bytes, uint32_t n_ecs, uint32_t n_targets, const uint32_t* target_col,
+                   const uint32_t* target_hap, uint32_t n_loci, uint32_t n_haps, uint64_t capacity, int32_t* out_indptr, int32_t* out_indices,
+                   int32_t* out_data, int32_t* out_n_indices, int32_t* out_n_data, uint64_t* out_sizes);
+
 /* Measurement: HIP-event time of the record-stream kernel on the handle's own stream; ecb_profile_kernel (ABI 4): the name of the
  * kernel the last batch launched, as rocprofv3 prints it (the stream kernel is compiled more than once; the library picks per batch). */
 int ecb_profile(ecb_handle* h, int enable);
