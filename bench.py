@@ -11,11 +11,16 @@ Workload (default): BASELINE config 3 -- 100 M paired-end reads, 8 haplotypes x 
 transcripts (~3.3 G BAM records, ~40 GB of tuples), synthetic (alntools_amd/synth.py, seed
 20260101), read-sharded contiguously over the N GPUs (strong scaling: total work fixed).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c1|tiny] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c1|tiny] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0; ``ms_per_step`` is the wall time of one of the K timed steps.  The inputs are a pure function of
 the workload's seed, so ``--dump-outputs`` of two builds can be compared file for file.
+
+A plain run does only what the headline needs: generate the tuples, warm up, time the K steps, dump, print.  ``--full`` adds
+everything else the line can carry, all of it after the timed steps: the step with the bam2emase transposition, the exactness
+pass, the measured copy / read peaks, the sensors under load, and on one GPU the kernel at other placements, the C oracle on the
+whole workload with bit-for-bit parity, the secondary workloads, the Python baseline, the PCIe-inclusive push and BAM -> .bin.
 """
 from __future__ import annotations
 
@@ -472,14 +477,18 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure and check everything else too (transposition step, exactness pass, copy / read peaks, "
+                         "sensors, placements, C oracle parity, secondary workloads, Python baseline, PCIe-inclusive push, BAM -> .bin); "
+                         "off: only what the headline needs")
     ap.add_argument("--cpu-sample-reads", type=int, default=0, help="reads of the C baseline's sample (0 = the whole workload)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the C baseline (0 = every hardware thread of the host)")
     ap.add_argument("--py-sample-reads", type=int, default=1_000_000, help="reads of the Python restatement's slice")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip every host-side measurement (C / Python baselines, H2D, BAM)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip every host-side measurement (C / Python baselines, H2D, BAM)")
     ap.add_argument("--layout", default="arrays", choices=("arrays", "tiles"),
                     help="how the resident tuples sit in HBM: three arrays in one allocation (ecb_push_device; the default: what the library's own staging for "
                          "host batches uses) or one buffer of whole tiles (ecb_push_device_tiled)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary workloads (c2, c3r, dip) behind a default config-3 run")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary workloads (c2, c3r, dip) behind a config-3 run")
     ap.add_argument("--secondary-steps", type=int, default=5)
     ap.add_argument("--e2e-slice-reads", type=int, default=100_000, help="reads of the config-2 slice converted from a real BAM file")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (CSR A and N, counters) "
@@ -674,7 +683,7 @@ def main():
     # config 3 names bam2emase: the .h5 holds one CSC matrix per haplotype, so its device work is the step plus the transposition
     # of the finished CSR (ecb_csr_to_hapcsc_device).  Timed on its own, outside the K steps the headline is measured on.
     emase_ms = None
-    if not use_dist and not multisample and not os.environ.get("ECB_ABLATE") and sizes.get("n_ecs"):
+    if args.full and not use_dist and not multisample and not os.environ.get("ECB_ABLATE") and sizes.get("n_ecs"):
         ipt = torch.empty(sizes["n_ecs"] + 1, dtype=torch.int32, device=device)
         ixt = torch.empty(sizes["nnz_a"], dtype=torch.int32, device=device)
         dat = torch.empty(sizes["nnz_a"], dtype=torch.int32, device=device)
@@ -696,7 +705,7 @@ def main():
         emase_bits = int(cidx.numel())
         del ipt, ixt, dat, cptr, cidx
     exact = None
-    if not use_dist and not multisample and not os.environ.get("ECB_ABLATE") and not os.environ.get("ECB_NO_VERIFY"):
+    if args.full and not use_dist and not multisample and not os.environ.get("ECB_ABLATE") and not os.environ.get("ECB_NO_VERIFY"):
         # outside the timed region: re-derive every read's target set and compare it with its EC's stored key
         b.reset()
         push()
@@ -726,9 +735,9 @@ def main():
         if multisample:      # + the cell stream and N
             step_bytes += 4.0 * total_reads + 8.0 * ms_sizes.get("nnz_n", 0)
         step_achieved = step_bytes / (ms_per_step * 1e-3) / 1e9
-        peak_copy, peak_read, peak_how = copy_peak(device) if not rehearsal else (None, None, None)
+        peak_copy, peak_read, peak_how = copy_peak(device) if args.full and not rehearsal else (None, None, None)
         sensors = None
-        if world == 1 and not rehearsal and not os.environ.get("ECB_ABLATE"):
+        if args.full and world == 1 and not rehearsal and not os.environ.get("ECB_ABLATE"):
             try:
                 sensors = sensors_under_load(step, fence, local)
             except Exception as e:      # (never the reason a bench line is missing)
@@ -784,7 +793,7 @@ def main():
                          "frac_of_measured_copy": (achieved / peak_copy) if peak_copy else None},
         }
         out["config"]["sensors_under_load"] = sensors
-        if world == 1 and not multisample and not os.environ.get("ECB_ABLATE") and not args.no_cpu_baseline and args.workload in ("c3", "c2"):
+        if args.full and world == 1 and not multisample and not os.environ.get("ECB_ABLATE") and not args.no_cpu_baseline and args.workload in ("c3", "c2"):
             def step_from(*t_):
                 b.reset()
                 if tiled:
@@ -801,7 +810,7 @@ def main():
                                                                   "(profiles/r04_tiles_against_arrays.txt).  The headline is the first one's, whatever it is" % (len(spread) - 1, args.layout))
             except Exception as e:
                 out["roofline"]["kernel_ms_by_placement"] = {"error": repr(e)}
-        if not use_dist and not args.no_cpu_baseline and not multisample:
+        if args.full and not use_dist and not args.no_cpu_baseline and not multisample:
             if tiled:                          # (the host-side legs -- the oracle, the Python baseline, the PCIe-inclusive push -- take arrays: copies)
                 rid, loc, hf = tiles_to_arrays(tiles, n_rec)
             out["cpu_baseline"], oracle_result = cpu_baseline(rid, loc, hf, H, args.cpu_sample_reads, args.cpu_threads)

@@ -1454,3 +1454,30 @@ def test_bench_dump_outputs_are_what_the_timed_steps_computed(tmp_path):
     n_ecs, nnz_a, n_samples, nnz_n, n_all, n_valid, n_reads = got["sizes"]
     assert (n_ecs, nnz_a, n_all, n_valid, n_reads) == (len(exp["count"]), len(exp["indices"]), exp["n_all"], exp["n_valid"],
                                                        int(np.sum(exp["count"])))
+
+
+def test_bench_plain_run_is_the_headline_alone_and_full_adds_the_rest():
+    """``bench.py --workload c1``: a plain run prints the headline and measures nothing besides it (no transposition step, no
+    exactness pass, no copy peaks, no host-side legs); ``--full`` adds them after the same timed steps, the exactness pass at 0."""
+    import subprocess
+    import sys
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+
+    def run(*extra):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "c1", "--steps", "2", "--warmup", "1", *extra],
+                           cwd=root, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        return json.loads(r.stdout.strip().splitlines()[-1])
+    plain = run()
+    assert plain["unit"] == "alignments/s" and plain["higher_is_better"] is True and plain["dtype"] == "u32"
+    assert plain["steps"] == 2 and plain["warmup"] == 1 and plain["ms_per_step"] > 0
+    assert plain["value"] == pytest.approx(plain["config"]["records"] / (plain["ms_per_step"] * 1e-3))
+    assert plain["step_emase_ms"] is None and plain["config"]["exactness_pass"] is None
+    assert plain["config"]["sensors_under_load"] is None and plain["roofline"]["peak_measured_copy"] is None
+    assert not {"cpu_baseline", "parity_vs_oracle", "secondary", "cpu_baseline_py", "h2d_inclusive", "e2e_from_bam"} & set(plain)
+    full = run("--full", "--no-cpu-baseline")
+    assert full["steps"] == 2 and full["ms_per_step"] > 0 and full["config"]["records"] == plain["config"]["records"]
+    assert full["config"]["ecs"] == plain["config"]["ecs"] and full["config"]["nnz_a"] == plain["config"]["nnz_a"]
+    assert full["step_emase_ms"] > 0
+    assert full["config"]["exactness_pass"]["reads_differing_from_their_ec_key"] == 0
+    assert full["roofline"]["peak_measured_copy"] > 0

@@ -6,7 +6,7 @@ timeout -k 10 420 python -m pytest tests -m gpu -x -q > $O/ab_test.log 2>&1; rc=
 tail -5 $O/ab_test.log
 [ $rc -ne 0 ] && { echo "tests failed rc=$rc"; grep -n "Error\|error\|assert" $O/ab_test.log | head -30; exit 1; }
 for w in $WLS; do for l in $LIBS; do
-  ECB_LIB=$l timeout -k 10 200 python bench.py --workload $w --steps $STEPS --no-cpu-baseline 2>$O/ab_err.log | python -c "
+  ECB_LIB=$l timeout -k 10 200 python bench.py --workload $w --steps $STEPS --full --no-cpu-baseline 2>$O/ab_err.log | python -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):

@@ -11,7 +11,7 @@ for l in sys.stdin:
         d = json.loads(l); r = d['roofline']
         print('%-22s %-4s step %.2f ms  k_stream %.3f ms  %.0f GB/s  frac %.3f  ecs %s  copy %.0f read %.0f' % ('$1', '$2', d['ms_per_step'], r['kernel_ms_per_launch'], r['achieved'], r['frac'], d['config']['ecs'], r.get('peak_measured_copy') or 0, r.get('peak_measured_read') or 0))
 "; }
-ECB_LIB=$LIB ECB_NO_VERIFY=1 timeout -k 10 300 python bench.py --workload c3 --steps 8 --no-cpu-baseline 2>$O/c3.err | tee $O/c3.json | line $LIB c3 | tee $O/summary.txt
+ECB_LIB=$LIB ECB_NO_VERIFY=1 timeout -k 10 300 python bench.py --workload c3 --steps 8 --full --no-cpu-baseline 2>$O/c3.err | tee $O/c3.json | line $LIB c3 | tee $O/summary.txt
 K=$(python -c "
 import json
 for l in open('$O/c3.json'):
@@ -41,6 +41,6 @@ PY
   cd $R
 fi
 for w in $WLS; do
-  ECB_LIB=$LIB ECB_NO_VERIFY=1 timeout -k 10 300 python bench.py --workload $w --steps 6 --no-cpu-baseline 2>$O/$w.err | tee $O/$w.json | line $LIB $w | tee -a $O/summary.txt
+  ECB_LIB=$LIB ECB_NO_VERIFY=1 timeout -k 10 300 python bench.py --workload $w --steps 6 --full --no-cpu-baseline 2>$O/$w.err | tee $O/$w.json | line $LIB $w | tee -a $O/summary.txt
 done
-ECB_LIB=$LIB ECB_NO_VERIFY=1 timeout -k 10 300 python bench.py --workload c3 --steps 8 --no-cpu-baseline 2>>$O/c3.err | line $LIB c3 | tee -a $O/summary.txt
+ECB_LIB=$LIB ECB_NO_VERIFY=1 timeout -k 10 300 python bench.py --workload c3 --steps 8 --full --no-cpu-baseline 2>>$O/c3.err | line $LIB c3 | tee -a $O/summary.txt

@@ -3,7 +3,7 @@
 W=${1:-c2}; OUT=${2:-gpurun_out/prof}
 R=$GRAFT_REPO_ROOT; mkdir -p $R/$OUT; RAW=/tmp/prof_raw_$$; mkdir -p $RAW
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $RAW -- python $R/bench.py --workload $W --steps 5 --warmup 1 --no-cpu-baseline > $R/$OUT/run.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $RAW -- python $R/bench.py --workload $W --steps 5 --warmup 1 --full --no-cpu-baseline > $R/$OUT/run.log 2>&1
 cd $R
 f=$(find $RAW -name "*kernel_stats.csv" | head -1)
 python - "$f" <<'PY'
