@@ -1584,7 +1584,8 @@ __global__ void k_ms_swz_keys(u64* keys, u64 n) {           // EC << 32 | meta  
     const u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x;
     if (i < n) keys[i] = ms_swz_key(keys[i]);
 }
-__global__ void k_ms_heads(const u64* keys, u64 n, u32* flag) {
+// flag[i] = 1 where a run of equal sorted keys starts
+__global__ void k_run_heads(const u64* keys, u64 n, u32* flag) {
     const u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x;
     if (i < n) flag[i] = (i == 0 || keys[i] != keys[i - 1]) ? 1u : 0u;
 }
@@ -1672,7 +1673,7 @@ __device__ __forceinline__ u64 lower_bound_u64(const u64* a, u64 n, u64 v) {
 //                   {EC -> haplotype mask}; within a piece no order is needed and an EC listed twice ORs into the same bit.
 //                   First launch: distinct ECs per column; second, behind a scan of those: the entries go out column by column as
 //                   (EC << 32 | locus, mask) -- within a column in any order --
-//   then a stable sort on the EC digits alone makes rows with ascending loci, and k_cvb_out / k_cvb_rowptr write the CSR.
+//   then a stable sort on the EC digits alone makes rows with ascending loci, and k_split_out / k_row_ptr write the CSR.
 // A row index outside its piece's EC range (a cut column whose lists are not ascending) is noticed: the caller then takes the
 // general, sort-everything path below.  A piece with more row indices than the table takes (EC ids bunched in one range) goes
 // entry by entry: the first haplotype's copy of an EC gathers the mask by binary searches in the other haplotypes' lists.
@@ -1834,13 +1835,15 @@ __global__ __launch_bounds__(CVU_TPB) void k_cvu_union(const int* cscptr, const 
         if (pos < nnz) { keys[pos] = ((u64)e << 32) | l; vals[pos] = tmask[q]; }
     }
 }
-__global__ void k_cvb_out(const u64* keys, const u32* vals, u64 nnz, int* indices, int* data) {
+// sorted (row << 32 | column, value) pairs -> a CSR's (or CSC's) indices, data and pointers: the column is the low half of the key,
+// row r starts at the first key of row r or above
+__global__ void k_split_out(const u64* keys, const u32* vals, u64 nnz, int* indices, int* data) {
     const u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x;
     if (i < nnz) { indices[i] = (int)(u32)keys[i]; data[i] = (int)vals[i]; }
 }
-__global__ void k_cvb_rowptr(const u64* keys, u64 nnz, u32 n_ecs, int* indptr) {
+__global__ void k_row_ptr(const u64* keys, u64 nnz, u32 n_rows, int* indptr) {
     const u64 r = blockIdx.x * (u64)blockDim.x + threadIdx.x;
-    if (r <= n_ecs) indptr[r] = (int)lower_bound_u64(keys, nnz, r << 32);
+    if (r <= n_rows) indptr[r] = (int)lower_bound_u64(keys, nnz, r << 32);
 }
 __global__ void k_cv_back_expand(const int* cscptr, const int* cscidx, u64 total, u32 n_loci, u32 n_haps, const u64* hap_start,
                                  u64* keys, u32* vals) {
@@ -1962,9 +1965,9 @@ __global__ void k_cv_ptr(const u64* keys, u64 nnz, u32 n_loci, u32 n_haps, u32 n
     }
 }
 
-__global__ void k_iota(int* out, u64 n) {
+__global__ void k_iota(u32* out, u64 n) {
     const u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x;
-    if (i < n) out[i] = (int)i;
+    if (i < n) out[i] = (u32)i;
 }
 __global__ void k_read_ec(const u32* read_slot, u64 n, const u32* rank_of_slot, int* out) {
     const u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x;
@@ -2344,15 +2347,6 @@ __global__ void k_msf2_pairs(const u32* ec, const u32* meta, const u32* cnt, con
     key[pos[t]] = ((u64)new_cell[c] << 32) | new_rank[e];
     val[pos[t]] = (u32)sum;
 }
-__global__ void k_msf2_nout(const u64* key, const u32* val, u64 n, int* indices, int* data) {
-    const u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x;
-    if (i < n) { indices[i] = (int)(u32)key[i]; data[i] = (int)val[i]; }
-}
-__global__ void k_msf2_nptr(const u64* key, u64 n, u32 n_cells, int* indptr) {
-    const u64 c = blockIdx.x * (u64)blockDim.x + threadIdx.x;
-    if (c <= n_cells) indptr[c] = (int)lower_bound_u64(key, n, c << 32);
-}
-__global__ void k_msf_iota(u32* v, u64 n) { const u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; if (i < n) v[i] = (u32)i; }
 __global__ void k_msf_gather64(const u64* src, const u32* idx, u64 n, u64* dst) { const u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; if (i < n) dst[i] = src[idx[i]]; }
 __global__ void k_msf_keepflag(const u32* order, const u64* total, u64 n, u64 min_count, u32* flag) {
     const u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x;
@@ -2495,10 +2489,10 @@ struct ecb_handle {
     ecb_sizes sizes{};
 
     // device scratch reused across calls (grown on demand: POOL)
-    enum { P_RESUME, P_SUMS, P_HIST, P_OFFS, P_PAIRS, P_CNT, P_PARTS, P_STARTS, P_WORK, P_LIST, P_BITMAP, P_WPOP, P_WPREFIX, P_ROWLEN, P_ORDER,
+    enum { P_RESUME, P_SUMS, P_HIST, P_OFFS, P_PAIRS, P_CNT, P_PARTS, P_WORK, P_LIST, P_BITMAP, P_WPOP, P_WPREFIX, P_ROWLEN, P_ORDER,
            P_WCOUNTS, P_RANK, P_INDPTR, P_COUNTS, P_INDICES, P_DATA, P_MS_KEYS, P_MS_KEYS2, P_MS_VALS, P_MS_VALS2, P_MS_TMP,
            P_MS_FLAG, P_MS_POS, P_MS_OKEY, P_MS_OFIRST, P_MS_OSTART, P_MS_X, P_MS_OCOUNT, P_MS_GRANK, P_MS_CIN, P_MS_FIN, P_LISTFN,
-           P_REMAP, P_TOTALS, P_SLOW_LEN, P_SLOW_OFF, P_SLOW_NRE, P_SLOW_REQ, P_SLOW_REQ2, P_QCOMPACT, P_SLOW_KEY, P_SLOW_MASK, P_BIG, P_RS_HIST, P_RS_OFFS, P_RS_SUMS,
+           P_REMAP, P_TOTALS, P_SLOW_LEN, P_SLOW_OFF, P_SLOW_NRE, P_SLOW_REQ, P_SLOW_REQ2, P_QCOMPACT, P_SLOW_KEY, P_SLOW_MASK, P_BIG, P_RS_HIST, P_RS_OFFS,
            P_F_CELLS, P_F_IPA, P_F_IXA, P_F_DAA, P_F_IPN, P_F_IXN, P_F_DAN, P_EXPORT, P_N };
 
     // profiling
@@ -2543,6 +2537,8 @@ int fail(ecb_handle* h, int code, const char* fmt, ...) {
     return fail(h, ECB_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); } while (0)
 
 u64 next_pow2(u64 x) { u64 p = 1; while (p < x) p <<= 1; return p; }
+// all ones up to the highest set bit of x (0 for 0): the bits a sort of keys no larger than x has to look at
+u64 msb_mask(u64 x) { return x ? ~0ull >> __builtin_clzll(x) : 0ull; }
 inline unsigned nblk(u64 n, unsigned per) { return (unsigned)((n + per - 1) / per); }
 
 // ptr = the handle's scratch buffer `id`, holding at least max(count, 1) of what ptr points to (regrown with a quarter more)
@@ -2958,25 +2954,34 @@ int excl_scan(ecb_handle* h, const u32* in, u64 n, u32* out, u64* total) {
     return ECB_OK;
 }
 
-// Stable LSD radix sort of n (key, value) pairs on `st`: only the digits some key has a bit in are sorted on (one OR-reduction
-// and one host wait up front).  k[0] / v[0] hold the input; the result lands in k[*where] / v[*where].  scratch: u32 hist and
-// offs of 256 * tiles each, u32 sums of tiles / 8 + 8, and 8 bytes at d_word.
+// The buffers of a sort of n (key, value) pairs: k[0] / v[0] hold the input; the sort records in `at` which buffer of each pair
+// holds its result, and the other one is free.
+struct SortBufs {
+    u64* k[2];
+    u32* v[2];
+    int at = 0;
+    u64* keys() const { return k[at]; }
+    u32* vals() const { return v[at]; }
+    u64* spare_keys() const { return k[at ^ 1]; }
+    u32* spare_vals() const { return v[at ^ 1]; }
+};
 // scratch of a sort of n pairs: `hist` = the (tile, digit) words of the look-back, rs_words(n) of them; `offs` = RS_AUX_WORDS words
-// (histograms and first places of all passes, the tile counter, the error word); `sums` unused; d_word = 8 bytes
-struct SortScratch { u32 *hist, *offs, *sums; u64* d_word; };
+// (histograms and first places of all passes, the tile counter, the error word); d_word = 8 bytes
+struct SortScratch { u32 *hist, *offs; u64* d_word; };
 inline u64 rs_tiles(u64 n) { return std::max<u64>(1, (n + RS_TILE - 1) / RS_TILE); }
 constexpr u64 RS_AUX_WORDS = 2 * RS_MAX_PASSES * 256 + 64;
 inline u64 rs_words(u64 n) { return std::max<u64>(256 * rs_tiles(n), RS_AUX_WORDS); }
-inline u64 rs_scan_blocks(u64) { return 1; }
-hipError_t radix_sort_pairs64(hipStream_t st, u64* k[2], u32* v[2], u64 n, const SortScratch& sc, int* where, u64 bit_mask = ~0ull) {
-    *where = 0;
+// Stable LSD radix sort of n (key, value) pairs on `st`: only the digits some key has a bit in are sorted on (one OR-reduction
+// and one host wait up front, unless bit_mask names them).
+hipError_t radix_sort_pairs64(hipStream_t st, SortBufs& b, u64 n, const SortScratch& sc, u64 bit_mask = ~0ull) {
+    b.at = 0;
     if (n < 2) return hipSuccess;
     if (n >= (1ull << 30)) return hipErrorInvalidValue;          // (a look-back word carries a 30-bit count)
     hipError_t e = hipSuccess;
     u64 ormask = bit_mask;                          // (a caller that names the bits to sort on has no use for the reduction and its host wait)
     if (bit_mask == ~0ull) {
         if ((e = hipMemsetAsync(sc.d_word, 0, 8, st)) != hipSuccess) return e;
-        k_or_reduce<<<(unsigned)std::min<u64>(1024, (n + TPB - 1) / TPB), TPB, 0, st>>>(k[0], n, sc.d_word);
+        k_or_reduce<<<(unsigned)std::min<u64>(1024, (n + TPB - 1) / TPB), TPB, 0, st>>>(b.k[0], n, sc.d_word);
         if ((e = hipMemcpyAsync(&ormask, sc.d_word, 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
         if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
     }
@@ -2987,31 +2992,36 @@ hipError_t radix_sort_pairs64(hipStream_t st, u64* k[2], u32* v[2], u64 n, const
     const u32 nt = (u32)rs_tiles(n);
     u32 *ghist = sc.offs, *base = sc.offs + RS_MAX_PASSES * 256, *ticket = sc.offs + 2 * RS_MAX_PASSES * 256, *err = ticket + 1;
     if ((e = hipMemsetAsync(sc.offs, 0, RS_AUX_WORDS * 4, st)) != hipSuccess) return e;
-    k_rs_hist_all<<<(unsigned)std::min<u64>(2048, (n + 16 * RS_TPB - 1) / (16 * RS_TPB)), RS_TPB, 0, st>>>(k[0], n, sh, ghist);
+    k_rs_hist_all<<<(unsigned)std::min<u64>(2048, (n + 16 * RS_TPB - 1) / (16 * RS_TPB)), RS_TPB, 0, st>>>(b.k[0], n, sh, ghist);
     k_rs_bases<<<1, 256, 0, st>>>(ghist, sh.n, base);
-    int cur = 0;
     for (u32 p = 0; p < sh.n; ++p) {
         if ((e = hipMemsetAsync(sc.hist, 0, (u64)nt * 256 * 4, st)) != hipSuccess) return e;
         if ((e = hipMemsetAsync(ticket, 0, 4, st)) != hipSuccess) return e;
-        k_rs_pass<<<nt, RS_TPB, 0, st>>>(k[cur], v[cur], n, sh.s[p], base + p * 256, sc.hist, ticket, err, k[cur ^ 1], v[cur ^ 1]);
-        cur ^= 1;
+        k_rs_pass<<<nt, RS_TPB, 0, st>>>(b.keys(), b.vals(), n, sh.s[p], base + p * 256, sc.hist, ticket, err, b.spare_keys(), b.spare_vals());
+        b.at ^= 1;
     }
-    *where = cur;
     if ((e = hipGetLastError()) != hipSuccess) return e;
     u32 gave_up = 0;                                // (a look-back that ran out of polls leaves the order undefined: never silently)
     if ((e = hipMemcpyAsync(&gave_up, err, 4, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
     return gave_up ? hipErrorUnknown : hipSuccess;
 }
-int handle_sort(ecb_handle* h, u64* k[2], u32* v[2], u64 n, int* where, u64 bit_mask = ~0ull) {
+// ... on the handle's stream, with its pool's scratch
+int handle_sort(ecb_handle* h, SortBufs& b, u64 n, u64 bit_mask = ~0ull) {
     SortScratch sc{};
     u64* tot = nullptr;
-    POOL(h, P_RS_HIST, sc.hist, rs_words(n)); POOL(h, P_RS_OFFS, sc.offs, RS_AUX_WORDS);
-    POOL(h, P_RS_SUMS, sc.sums, rs_scan_blocks(n) + 8); POOL(h, P_TOTALS, tot, 8);
+    POOL(h, P_RS_HIST, sc.hist, rs_words(n)); POOL(h, P_RS_OFFS, sc.offs, RS_AUX_WORDS); POOL(h, P_TOTALS, tot, 8);
     sc.d_word = tot + 6;
-    const hipError_t e = radix_sort_pairs64(h->stream, k, v, n, sc, where, bit_mask);
+    const hipError_t e = radix_sort_pairs64(h->stream, b, n, sc, bit_mask);
     if (e != hipSuccess) return fail(h, ECB_ERR_HIP, "radix sort: %s", hipGetErrorString(e));
     return ECB_OK;
+}
+// ... and its runs of equal keys: flag[i] = 1 where one starts, pos = the exclusive scan of the flags, *n_runs their number (one wait)
+int sorted_runs(ecb_handle* h, SortBufs& b, u64 n, u32* flag, u32* pos, u64* n_runs) {
+    const int rc = handle_sort(h, b, n);
+    if (rc != ECB_OK) return rc;
+    k_run_heads<<<nblk(n, TPB), TPB, 0, h->stream>>>(b.keys(), n, flag);
+    return excl_scan(h, flag, n, pos, n_runs);
 }
 
 int ensure_slot_ranks(ecb_handle* h, u64 E) {
@@ -3128,19 +3138,12 @@ int ms_reduce(ecb_handle* h, const u32* ec_of_slot) {
     POOL(h, P_MS_KEYS, keys, R); POOL(h, P_MS_KEYS2, keys2, R); POOL(h, P_MS_VALS, vals, R); POOL(h, P_MS_VALS2, vals2, R);
     POOL(h, P_MS_FLAG, flag, R); POOL(h, P_MS_POS, pos, R);
     k_ms_keys<<<nblk(R, TPB), TPB, 0, h->stream>>>(h->read_slot, ec_of_slot, h->meta, R, keys, vals);
-    {
-        u64* kk[2] = {keys, keys2}; u32* vv[2] = {vals, vals2};
-        int where = 0;
-        const int rc0 = handle_sort(h, kk, vv, R, &where);
-        if (rc0 != ECB_OK) return rc0;
-        keys2 = kk[where]; vals2 = vv[where];
-    }
-    k_ms_heads<<<nblk(R, TPB), TPB, 0, h->stream>>>(keys2, R, flag);
+    SortBufs s{{keys, keys2}, {vals, vals2}};
     u64 nt = 0;
-    int rc = excl_scan(h, flag, R, pos, &nt);
+    const int rc = sorted_runs(h, s, R, flag, pos, &nt);
     if (rc != ECB_OK) return rc;
     POOL(h, P_MS_OKEY, h->ms_okey, nt); POOL(h, P_MS_OFIRST, h->ms_ofirst, nt); POOL(h, P_MS_OSTART, h->ms_ostart, (u64)nt + 1);
-    k_ms_emit<<<nblk(R, TPB), TPB, 0, h->stream>>>(keys2, vals2, flag, pos, R, nt, h->ms_okey, h->ms_ofirst, h->ms_ostart);
+    k_ms_emit<<<nblk(R, TPB), TPB, 0, h->stream>>>(s.keys(), s.vals(), flag, pos, R, nt, h->ms_okey, h->ms_ofirst, h->ms_ostart);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->n_triples = nt; h->ms_ocount = nullptr;
     return ECB_OK;
@@ -3645,7 +3648,7 @@ int ecb_export_device(ecb_handle* h, void* ia, void* ja, void* da, void* in_, vo
     if (ja) HIPCHK(h, hipMemcpyAsync(ja, h->indices, nnz * 4, hipMemcpyDeviceToDevice, h->stream));
     if (da) HIPCHK(h, hipMemcpyAsync(da, h->data, nnz * 4, hipMemcpyDeviceToDevice, h->stream));
     if (in_) { const int v[2] = {0, (int)E}; HIPCHK(h, hipMemcpyAsync(in_, v, 8, hipMemcpyHostToDevice, h->stream)); }
-    if (jn) k_iota<<<nblk(E, TPB), TPB, 0, h->stream>>>((int*)jn, E);
+    if (jn) k_iota<<<nblk(E, TPB), TPB, 0, h->stream>>>((u32*)jn, E);
     if (dn) HIPCHK(h, hipMemcpyAsync(dn, h->counts, E * 4, hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return ECB_OK;
@@ -3968,23 +3971,16 @@ int ecb_ms_adopt_triples_device(ecb_handle* h, uint32_t n_tables, const void* co
     u64 nt = 0;
     if (tot) {
         k_ms_swz_keys<<<nblk(tot, TPB), TPB, 0, h->stream>>>(keys, tot);      // (sorted as (EC, cell, file), like a handle's own triples)
-        k_iota<<<nblk(tot, TPB), TPB, 0, h->stream>>>((int*)vals, tot);
-        {
-            u64* kk[2] = {keys, keys2}; u32* vv[2] = {vals, vals2};
-            int where = 0;
-            const int rc0 = handle_sort(h, kk, vv, tot, &where);
-            if (rc0 != ECB_OK) return rc0;
-            keys2 = kk[where]; vals2 = vv[where];
-        }
-        k_ms_heads<<<nblk(tot, TPB), TPB, 0, h->stream>>>(keys2, tot, flag);
-        int rc = excl_scan(h, flag, tot, pos, &nt);
+        k_iota<<<nblk(tot, TPB), TPB, 0, h->stream>>>(vals, tot);
+        SortBufs s{{keys, keys2}, {vals, vals2}};
+        const int rc = sorted_runs(h, s, tot, flag, pos, &nt);
         if (rc != ECB_OK) return rc;
         POOL(h, P_MS_OKEY, h->ms_okey, nt); POOL(h, P_MS_OFIRST, h->ms_ofirst, nt); POOL(h, P_MS_OCOUNT, h->ms_ocount, nt);
         HIPCHK(h, hipMemsetAsync(h->ms_ocount, 0, (u64)nt * 4, h->stream));
         HIPCHK(h, hipMemsetAsync(h->ms_ofirst, 0xFF, (u64)nt * 4, h->stream));
-        k_ms_combine<<<nblk(tot, TPB), TPB, 0, h->stream>>>(keys2, vals2, flag, pos, tot, cin, fin, h->ms_okey, h->ms_ocount, h->ms_ofirst);
+        k_ms_combine<<<nblk(tot, TPB), TPB, 0, h->stream>>>(s.keys(), s.vals(), flag, pos, tot, cin, fin, h->ms_okey, h->ms_ocount, h->ms_ofirst);
         u64 last = 0;
-        HIPCHK(h, hipMemcpyAsync(&last, keys2 + (tot - 1), sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(&last, s.keys() + (tot - 1), sizeof(u64), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         if ((last >> 32) >= h->sizes.n_ecs) return fail(h, ECB_ERR_CONTRACT, "triple with an EC id beyond the merged ECs");
     }
@@ -4048,7 +4044,7 @@ int ecb_ms_filter(ecb_handle* h, uint32_t n_cells, int64_t minimum_count, ecb_ms
         k_msf2_giant_offer<<<1024, TPB, 0, st>>>(meta, first, seg, giant, giant + max_giant, n_cells, firstfile, gfec, cellkey);
     }
     // 3. cell order: by (first appearance of the EC in the cell's first file, first read), then -- stable -- by that file
-    int rc, where = 0;
+    int rc;
     k_msf2_cellflag<<<nblk(n_cells, TPB), TPB, 0, st>>>(total, n_cells, flag);
     u64 C = 0;
     rc = excl_scan(h, flag, n_cells, pos, &C); if (rc != ECB_OK) return rc;
@@ -4064,14 +4060,13 @@ int ecb_ms_filter(ecb_handle* h, uint32_t n_cells, int64_t minimum_count, ecb_ms
     u64 *ctotal = fresh<u64>(sc, C), *bhi = fresh<u64>(sc, C), *blo = fresh<u64>(sc, C), *ck0 = fresh<u64>(sc, C), *ck1 = fresh<u64>(sc, C);
     if (missing(sc)) return fail(h, ECB_ERR_HIP, "out of device memory");
     k_msf2_celllist<<<nblk(n_cells, TPB), TPB, 0, st>>>(total, firstfile, cellkey, flag, pos, n_cells, cell_id, ctotal, bhi, blo);
-    k_msf_iota<<<nblk(C, TPB), TPB, 0, st>>>(corder, C);
+    k_iota<<<nblk(C, TPB), TPB, 0, st>>>(corder, C);
     HIPCHK(h, hipMemcpyAsync(ck0, blo, C * 8, hipMemcpyDeviceToDevice, st));
     u32* ord = nullptr;
-    { u64* kk[2] = {ck0, ck1}; u32* vv[2] = {corder, corder2}; rc = handle_sort(h, kk, vv, C, &where); if (rc != ECB_OK) return rc;
-      u32* o1 = vv[where]; u32* o2 = vv[where ^ 1]; u64* ka = kk[where ^ 1]; u64* kb = kk[where];
-      k_msf_gather64<<<nblk(C, TPB), TPB, 0, st>>>(bhi, o1, C, ka);
-      u64* kk2[2] = {ka, kb}; u32* vv2[2] = {o1, o2}; rc = handle_sort(h, kk2, vv2, C, &where); if (rc != ECB_OK) return rc;
-      ord = vv2[where]; }
+    { SortBufs s{{ck0, ck1}, {corder, corder2}}; rc = handle_sort(h, s, C); if (rc != ECB_OK) return rc;
+      k_msf_gather64<<<nblk(C, TPB), TPB, 0, st>>>(bhi, s.vals(), C, s.spare_keys());   // (the second key, in the first sort's order)
+      SortBufs s2{{s.spare_keys(), s.keys()}, {s.vals(), s.spare_vals()}}; rc = handle_sort(h, s2, C); if (rc != ECB_OK) return rc;
+      ord = s2.vals(); }
     k_msf_keepflag<<<nblk(C, TPB), TPB, 0, st>>>(ord, ctotal, C, min_count, cflag);
     u64 S = 0;
     rc = excl_scan(h, cflag, C, cpos, &S); if (rc != ECB_OK) return rc;
@@ -4090,14 +4085,12 @@ int ecb_ms_filter(ecb_handle* h, uint32_t n_cells, int64_t minimum_count, ecb_ms
     k_msf2_pairs<<<nblk(T, TPB), TPB, 0, st>>>(ec, meta, cnt, flag, pos, T, new_cell, new_rank, k0, v0, d_err);
     const u64 nnz_n = K;
     {
-        u32 sbits = 1;
-        while (sbits < 32 && (1ull << sbits) < S) ++sbits;
-        u64* kk[2] = {k0, k1}; u32* vv[2] = {v0, v1};
-        rc = handle_sort(h, kk, vv, K, &where, ((1ull << sbits) - 1ull) << 32);
+        SortBufs s{{k0, k1}, {v0, v1}};
+        rc = handle_sort(h, s, K, msb_mask(S - 1) << 32);
         if (rc != ECB_OK) return rc;
         POOL(h, P_F_IPN, h->f_ipn, S + 1); POOL(h, P_F_IXN, h->f_ixn, nnz_n); POOL(h, P_F_DAN, h->f_dan, nnz_n);
-        k_msf2_nout<<<nblk(K, TPB), TPB, 0, st>>>(kk[where], vv[where], K, h->f_ixn, h->f_dan);
-        k_msf2_nptr<<<nblk(S + 1, TPB), TPB, 0, st>>>(kk[where], K, (u32)S, h->f_ipn);
+        k_split_out<<<nblk(K, TPB), TPB, 0, st>>>(s.keys(), s.vals(), K, h->f_ixn, h->f_dan);
+        k_row_ptr<<<nblk(S + 1, TPB), TPB, 0, st>>>(s.keys(), K, (u32)S, h->f_ipn);
     }
     // 6. the rows of A of the ECs that are left
     u32* rowlen2 = fresh<u32>(sc, E2 + 1);
@@ -4191,7 +4184,7 @@ int cv_scan(hipStream_t st, const u32* in, u64 n, u32* out, u64* total, std::vec
 // Scratch of the stateless conversions, kept per device between calls (grown on demand; ecb_release_scratch frees it): a
 // config-3-sized conversion needs ~0.4 GB in a dozen buffers, and a dozen hipMallocs cost more than its kernels do.
 namespace {
-enum { CV_KEYS0, CV_KEYS1, CV_VALS0, CV_VALS1, CV_HIST, CV_OFFS, CV_SUMS, CV_SUMS2, CV_BLK, CV_SCAN, CV_HEAD, CV_WORDS, CV_X0, CV_X1, CV_X2, CV_X3, CV_N };
+enum { CV_KEYS0, CV_KEYS1, CV_VALS0, CV_VALS1, CV_HIST, CV_OFFS, CV_SUMS2, CV_BLK, CV_SCAN, CV_HEAD, CV_WORDS, CV_X0, CV_X1, CV_X2, CV_X3, CV_N };
 constexpr int CV_MAX_DEV = 64;
 DevBuf<>* const g_cv = new DevBuf<>[CV_MAX_DEV * CV_N];      // (never destroyed: no HIP call may run after the runtime has gone, at exit)
 std::mutex g_cv_lock;
@@ -4201,8 +4194,11 @@ template <class T> T* cv_get(int device, int id, u64 count) {
     const u64 need = std::max<u64>(count, 1) * sizeof(T);
     return b.regrow(need, need / 8) == hipSuccess ? b.as<T>() : nullptr;
 }
-// exclusive scan on `st`, nothing waits: sums = scan_words(n) words of scratch, the total (64 bits) lands in *d_grand
-void cv_scan_queue(hipStream_t st, const u32* in, u64 n, u32* out, u32* sums, u64* d_grand) { (void)scan_launch(st, in, n, out, sums, d_grand); }
+// a stateless entry point's device made current: ECB_OK, or the error to return
+int use_device(int device) {
+    if (device < 0 || device >= CV_MAX_DEV || hipSetDevice(device) != hipSuccess) return fail(nullptr, ECB_ERR_NO_DEVICE, "no such device");
+    return ECB_OK;
+}
 }  // namespace
 
 extern "C" int ecb_release_scratch(int device) {
@@ -4218,7 +4214,7 @@ extern "C" int ecb_csr_to_hapcsc_device(int device, uint32_t n_ecs, uint32_t n_l
                                         uint64_t* total) {
     if (!d_indptr || !total || !n_ecs || !n_loci || !n_haps || n_haps > 31) return fail(nullptr, ECB_ERR_ARG, "bad argument");
     if ((u64)n_haps * n_loci >= (1ull << 32)) return fail(nullptr, ECB_ERR_LIMIT, "haplotypes x loci does not fit 32 bits");
-    if (device < 0 || device >= CV_MAX_DEV || hipSetDevice(device) != hipSuccess) return fail(nullptr, ECB_ERR_NO_DEVICE, "no such device");
+    if (const int rc = use_device(device)) return rc;
     hipStream_t st = nullptr;
     int nnz_i = 0;
     if (hipMemcpy(&nnz_i, (const int*)d_indptr + n_ecs, 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "read nnz");
@@ -4246,23 +4242,19 @@ extern "C" int ecb_csr_to_hapcsc_device(int device, uint32_t n_ecs, uint32_t n_l
     const u32 nb = (u32)nblk(nnz, CVB);
     u64 *k0 = cv_get<u64>(device, CV_KEYS0, nnz), *k1 = cv_get<u64>(device, CV_KEYS1, nnz);
     u32 *v0 = cv_get<u32>(device, CV_VALS0, nnz), *v1 = cv_get<u32>(device, CV_VALS1, nnz);
-    SortScratch ss{cv_get<u32>(device, CV_HIST, rs_words(nnz)), cv_get<u32>(device, CV_OFFS, RS_AUX_WORDS),
-                   cv_get<u32>(device, CV_SUMS, rs_scan_blocks(nnz) + 8), words + 3};
+    SortScratch ss{cv_get<u32>(device, CV_HIST, rs_words(nnz)), cv_get<u32>(device, CV_OFFS, RS_AUX_WORDS), words + 3};
     u32 *blk = cv_get<u32>(device, CV_BLK, (u64)n_haps * nb), *scan = cv_get<u32>(device, CV_SCAN, (u64)n_haps * nb);
     u32 *sums2 = cv_get<u32>(device, CV_SUMS2, scan_words((u64)n_haps * nb) + 2), *headval = cv_get<u32>(device, CV_HEAD, (u64)n_haps * n_loci);
-    if (!k0 || !k1 || !v0 || !v1 || !ss.hist || !ss.offs || !ss.sums || !blk || !scan || !sums2 || !headval) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
+    if (!k0 || !k1 || !v0 || !v1 || !ss.hist || !ss.offs || !blk || !scan || !sums2 || !headval) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
     if (hipMemsetAsync(words, 0, 24, st) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "memset");
     k_cv_keys<<<nblk(n_ecs, TPB), TPB, 0, st>>>((const int*)d_indptr, n_ecs, (const int*)d_indices, (const int*)d_data, nnz, n_loci, n_haps,
                                                k0, v0, reinterpret_cast<u32*>(words + 2));
-    u32 lbits = 1;
-    while (lbits < 32 && ((u64)1 << lbits) < n_loci) ++lbits;
-    u64* kk[2] = {k0, k1}; u32* vv[2] = {v0, v1};
-    int where = 0;
+    SortBufs s{{k0, k1}, {v0, v1}};
     // stable sort on the locus alone: ECs stay ascending within a column, as scipy's tocsc() leaves them
-    if (radix_sort_pairs64(st, kk, vv, nnz, ss, &where, ((1ull << lbits) - 1ull) << 32) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "sort");
-    const u64* keys = kk[where]; const u32* masks = vv[where];
+    if (radix_sort_pairs64(st, s, nnz, ss, msb_mask(n_loci - 1) << 32) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "sort");
+    const u64* keys = s.keys(); const u32* masks = s.vals();
     k_cv_cnt<<<nb, TPB, 0, st>>>(masks, nnz, n_haps, nb, blk);
-    cv_scan_queue(st, blk, (u64)n_haps * nb, scan, sums2, words + 1);
+    (void)scan_launch(st, blk, (u64)n_haps * nb, scan, sums2, words + 1);
     u64 back[3] = {0, 0, 0};
     if (hipMemcpy(back, words, 24, hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "csr -> csc (count)");
     if (back[2]) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSR: row pointers out of order, a locus beyond n_loci, or a mask that is zero or beyond n_haplotypes");
@@ -4284,19 +4276,15 @@ int hapcsc_to_csr_general(hipStream_t st, u32 n_ecs, u32 n_loci, u32 n_haps, con
     if (missing(sc)) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
     hipMemcpy(d_hs, hs.data(), (n_haps + 1) * 8, hipMemcpyHostToDevice);
     k_cv_back_expand<<<nblk(total, TPB), TPB, 0, st>>>((const int*)d_cscptr, (const int*)d_cscidx, total, n_loci, n_haps, d_hs, keys, vals);
-    {
-        SortScratch ss{fresh<u32>(sc, rs_words(total)), fresh<u32>(sc, RS_AUX_WORDS), fresh<u32>(sc, rs_scan_blocks(total) + 8), fresh<u64>(sc, 1)};
-        if (missing(sc)) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
-        u64* kk[2] = {keys, keys2}; u32* vv[2] = {vals, vals2};
-        int where = 0;
-        if (radix_sort_pairs64(st, kk, vv, total, ss, &where) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "sort");
-        keys2 = kk[where]; vals2 = vv[where];
-    }
-    k_ms_heads<<<nblk(total, TPB), TPB, 0, st>>>(keys2, total, flag);
+    SortScratch ss{fresh<u32>(sc, rs_words(total)), fresh<u32>(sc, RS_AUX_WORDS), fresh<u64>(sc, 1)};
+    if (missing(sc)) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
+    SortBufs s{{keys, keys2}, {vals, vals2}};
+    if (radix_sort_pairs64(st, s, total, ss) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "sort");
+    k_run_heads<<<nblk(total, TPB), TPB, 0, st>>>(s.keys(), total, flag);
     u64 nnz = 0;
     if (cv_scan(st, flag, total, pos, &nnz, sc) != ECB_OK) return fail(nullptr, ECB_ERR_HIP, "scan");
-    k_cv_back_emit<<<nblk(total, TPB), TPB, 0, st>>>(keys2, vals2, flag, pos, total, n_loci, (int*)d_indices, (int*)d_data);
-    k_cv_back_rowptr<<<nblk((u64)n_ecs + 1, TPB), TPB, 0, st>>>(keys2, pos, total, nnz, n_ecs, n_loci, (int*)d_indptr);
+    k_cv_back_emit<<<nblk(total, TPB), TPB, 0, st>>>(s.keys(), s.vals(), flag, pos, total, n_loci, (int*)d_indices, (int*)d_data);
+    k_cv_back_rowptr<<<nblk((u64)n_ecs + 1, TPB), TPB, 0, st>>>(s.keys(), pos, total, nnz, n_ecs, n_loci, (int*)d_indptr);
     if (hipStreamSynchronize(st) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "csc -> csr");
     *nnz_out = nnz;
     return ECB_OK;
@@ -4309,7 +4297,7 @@ extern "C" int ecb_hapcsc_to_csr_device(int device, uint32_t n_ecs, uint32_t n_l
     if (!d_cscptr || !d_cscidx || !d_indptr || !d_indices || !d_data || !nnz_out || !n_ecs || !n_loci || !n_haps || n_haps > 31 || !total)
         return fail(nullptr, ECB_ERR_ARG, "bad argument");
     if (total >= (1ull << 32)) return fail(nullptr, ECB_ERR_LIMIT, "more than 2^32-1 row indices");
-    if (device < 0 || device >= CV_MAX_DEV || hipSetDevice(device) != hipSuccess) return fail(nullptr, ECB_ERR_NO_DEVICE, "no such device");
+    if (const int rc = use_device(device)) return rc;
     hipStream_t st = nullptr;
     std::lock_guard<std::mutex> guard(g_cv_lock);
     // start of every haplotype's block = running sum of its last column pointer
@@ -4325,8 +4313,6 @@ extern "C" int ecb_hapcsc_to_csr_device(int device, uint32_t n_ecs, uint32_t n_l
         hs[h + 1] = hs[h] + (u64)last[h];
     }
     if (hs[n_haps] != total) return fail(nullptr, ECB_ERR_ARG, "total does not match the column pointers");
-    u32 ebits = 0;
-    while (ebits < 32 && ((u64)1 << ebits) < n_ecs) ++ebits;
     u64* d_hs = cv_get<u64>(device, CV_X0, n_haps + 1);
     u32 *Ssum = cv_get<u32>(device, CV_X1, (u64)n_loci + 1);
     u32 *colcnt = cv_get<u32>(device, CV_HEAD, 5ull * n_loci + 8), *sums = cv_get<u32>(device, CV_SUMS2, scan_words(n_loci) + 2);
@@ -4338,7 +4324,7 @@ extern "C" int ecb_hapcsc_to_csr_device(int device, uint32_t n_ecs, uint32_t n_l
         return fail(nullptr, ECB_ERR_HIP, "csc -> csr (set-up)");
     k_cvu_colsum<<<nblk((u64)n_loci + 1, TPB), TPB, 0, st>>>((const int*)d_cscptr, n_loci, n_haps, Ssum, d_err);
     k_cvu_pieces<<<nblk(n_loci, TPB), TPB, 0, st>>>(Ssum, n_loci, pieces);
-    cv_scan_queue(st, pieces, n_loci, pbase, sums, words + 2);
+    (void)scan_launch(st, pieces, n_loci, pbase, sums, words + 2);
     u64 back[3] = {0, 0, 0};
     if (hipMemcpy(back, words, 24, hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "csc -> csr (pointers)");
     if ((u32)back[0]) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSC: column pointers do not start at zero or go backwards");
@@ -4351,7 +4337,7 @@ extern "C" int ecb_hapcsc_to_csr_device(int device, uint32_t n_ecs, uint32_t n_l
                                                              n_loci, n_haps, n_ecs, bnd);
     k_cvu_union<false><<<(unsigned)n_items, CVU_TPB, 0, st>>>((const int*)d_cscptr, (const int*)d_cscidx, d_hs, pieces, pbase, item_col, bnd, (u32)n_items,
                                                               n_loci, n_haps, n_ecs, colcnt, colbase, colcur, 0, nullptr, nullptr, d_err);
-    cv_scan_queue(st, colcnt, n_loci, colbase, sums, words + 1);
+    (void)scan_launch(st, colcnt, n_loci, colbase, sums, words + 1);
     if (hipMemcpy(back, words, 16, hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "csc -> csr (union)");
     if ((u32)back[0] & CVB_ERR_EC) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSC: a row index beyond the number of ECs");
     if ((u32)back[0] & CVB_ERR_ORDER)                              // a long column whose lists are not ascending: sort everything
@@ -4359,17 +4345,15 @@ extern "C" int ecb_hapcsc_to_csr_device(int device, uint32_t n_ecs, uint32_t n_l
     const u64 nnz = back[1];
     u64 *k0 = cv_get<u64>(device, CV_KEYS0, nnz), *k1 = cv_get<u64>(device, CV_KEYS1, nnz);
     u32 *v0 = cv_get<u32>(device, CV_VALS0, nnz), *v1 = cv_get<u32>(device, CV_VALS1, nnz);
-    SortScratch ss{cv_get<u32>(device, CV_HIST, rs_words(nnz)), cv_get<u32>(device, CV_OFFS, RS_AUX_WORDS),
-                   cv_get<u32>(device, CV_SUMS, rs_scan_blocks(nnz) + 8), words + 3};
-    if (!k0 || !k1 || !v0 || !v1 || !ss.hist || !ss.offs || !ss.sums) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
+    SortScratch ss{cv_get<u32>(device, CV_HIST, rs_words(nnz)), cv_get<u32>(device, CV_OFFS, RS_AUX_WORDS), words + 3};
+    if (!k0 || !k1 || !v0 || !v1 || !ss.hist || !ss.offs) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
     k_cvu_union<true><<<(unsigned)n_items, CVU_TPB, 0, st>>>((const int*)d_cscptr, (const int*)d_cscidx, d_hs, pieces, pbase, item_col, bnd, (u32)n_items,
                                                              n_loci, n_haps, n_ecs, colcnt, colbase, colcur, nnz, k0, v0, d_err);
-    u64* kk[2] = {k0, k1}; u32* vv[2] = {v0, v1};
-    int where = 0;
+    SortBufs s{{k0, k1}, {v0, v1}};
     // stable, on the EC alone: what left column by column arrives row by row with its loci ascending
-    if (radix_sort_pairs64(st, kk, vv, nnz, ss, &where, (ebits >= 32 ? 0xFFFFFFFFull : (1ull << ebits) - 1ull) << 32) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "sort");
-    k_cvb_out<<<nblk(nnz, TPB), TPB, 0, st>>>(kk[where], vv[where], nnz, (int*)d_indices, (int*)d_data);
-    k_cvb_rowptr<<<nblk((u64)n_ecs + 1, TPB), TPB, 0, st>>>(kk[where], nnz, n_ecs, (int*)d_indptr);
+    if (radix_sort_pairs64(st, s, nnz, ss, msb_mask(n_ecs - 1) << 32) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "sort");
+    k_split_out<<<nblk(nnz, TPB), TPB, 0, st>>>(s.keys(), s.vals(), nnz, (int*)d_indices, (int*)d_data);
+    k_row_ptr<<<nblk((u64)n_ecs + 1, TPB), TPB, 0, st>>>(s.keys(), nnz, n_ecs, (int*)d_indptr);
     if (hipStreamSynchronize(st) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "csc -> csr");
     *nnz_out = nnz;
     return ECB_OK;
@@ -4398,7 +4382,7 @@ bool stage_out(const std::vector<StageOut>& list) {
 extern "C" int ecb_csr_to_hapcsc(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, const int32_t* indptr, const int32_t* indices,
                                  const int32_t* data, int32_t* csc_indptr, int32_t* csc_indices, uint64_t capacity, uint64_t* total) {
     if (!indptr || !total || !n_ecs || !n_loci || !n_haps || n_haps > 31) return fail(nullptr, ECB_ERR_ARG, "bad argument");
-    if (device < 0 || device >= CV_MAX_DEV || hipSetDevice(device) != hipSuccess) return fail(nullptr, ECB_ERR_NO_DEVICE, "no such device");
+    if (const int rc = use_device(device)) return rc;
     if (indptr[n_ecs] < 0) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSR: negative row pointer");
     const u64 nnz = (u64)indptr[n_ecs];
     if (nnz && (!indices || !data)) return fail(nullptr, ECB_ERR_ARG, "bad argument");
@@ -4431,7 +4415,7 @@ extern "C" int ecb_hapcsc_to_csr(int device, uint32_t n_ecs, uint32_t n_loci, ui
     if (!csc_indptr || !csc_indices || !indptr || !indices || !data || !nnz || !n_ecs || !n_loci || !n_haps || n_haps > 31 || !total)
         return fail(nullptr, ECB_ERR_ARG, "bad argument");
     if (total >= (1ull << 32)) return fail(nullptr, ECB_ERR_LIMIT, "more than 2^32-1 row indices");
-    if (device < 0 || device >= CV_MAX_DEV || hipSetDevice(device) != hipSuccess) return fail(nullptr, ECB_ERR_NO_DEVICE, "no such device");
+    if (const int rc = use_device(device)) return rc;
     DevBuf<> cp, ci, ip, ix, da;
     const u64 nc = (u64)n_haps * (n_loci + 1), rowb = ((u64)n_ecs + 1) * 4;
     if (const char* why = stage_in({{&cp, csc_indptr, nc * 4}, {&ci, csc_indices, total * 4}, {&ip, nullptr, rowb}, {&ix, nullptr, total * 4},
@@ -4566,7 +4550,7 @@ extern "C" int ecb_apply_mask_device(int device, uint32_t n_ecs, uint32_t n_loci
             return fail(nullptr, ECB_ERR_ARG, "an output overlaps an input");
     if (gm_overlap(d_out_indptr, rowb, d_out_indices, nzb) || gm_overlap(d_out_indptr, rowb, d_out_data, nzb) || gm_overlap(d_out_indices, nzb, d_out_data, nzb))
         return fail(nullptr, ECB_ERR_ARG, "the outputs overlap");
-    if (device < 0 || device >= CV_MAX_DEV || hipSetDevice(device) != hipSuccess) return fail(nullptr, ECB_ERR_NO_DEVICE, "no such device");
+    if (const int rc = use_device(device)) return rc;
     hipStream_t st = nullptr;
     std::lock_guard<std::mutex> guard(g_cv_lock);
     const u64 n_words = GM_SHARD_WORDS * (1 + GM_SHARDS);
@@ -4600,7 +4584,7 @@ extern "C" int ecb_apply_mask(int device, uint32_t n_ecs, uint32_t n_loci, uint3
     if (!indptr || !mask || !out_indptr || !kept || !n_loci || !n_haps || n_haps > 31) return fail(nullptr, ECB_ERR_ARG, "bad argument");
     if (nnz && (!indices || !data || !out_indices || !out_data)) return fail(nullptr, ECB_ERR_ARG, "bad argument");
     if (nnz >= (1ull << 31) || n_ecs >= (1u << 31) - 1u) return fail(nullptr, ECB_ERR_LIMIT, "the CSR exceeds the .bin format's int32 limits");
-    if (device < 0 || device >= CV_MAX_DEV || hipSetDevice(device) != hipSuccess) return fail(nullptr, ECB_ERR_NO_DEVICE, "no such device");
+    if (const int rc = use_device(device)) return rc;
     const u64 rowb = ((u64)n_ecs + 1) * 4, nzb = nnz * 4;
     DevBuf<> ip, ix, da, mk, oip, oix, oda;
     if (const char* why = stage_in({{&ip, indptr, rowb}, {&ix, indices, nzb}, {&da, data, nzb}, {&mk, mask, (u64)n_loci * 4}, {&oip, nullptr, rowb},
@@ -4832,10 +4816,6 @@ __global__ __launch_bounds__(TPB) void k_cb_ntrip(const CbPart* P, u32 n_parts, 
         if ((threadIdx.x & 63u) == 0u) atomicOr(err, w);
     }
 }
-__global__ void k_cb_heads(const u64* keys, u64 n, u32* flag) {
-    const u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x;
-    if (i < n) flag[i] = (i == 0 || keys[i] != keys[i - 1]) ? 1u : 0u;
-}
 // sorted (sample, EC) keys -> one sum per distinct key (run id = exclusive scan of the head flags), and each run's key
 __global__ __launch_bounds__(TPB) void k_cb_nsum(const u64* keys, const u32* vals, const u32* flag, const u32* pos, u64 n, u64* sums, u64* runkey) {
     const u64 i = blockIdx.x * (u64)TPB + threadIdx.x;
@@ -4904,7 +4884,7 @@ extern "C" int ecb_combine_device(int device, uint32_t n_parts, const ecb_combin
     bool any_map = false;
     for (u32 p = 0; p < n_parts; ++p) any_map |= hp[p].tmap != nullptr;
     if (any_map && NP >= (1ull << 30)) return fail(nullptr, ECB_ERR_LIMIT, "combine: more than 2^30 non-zeros to re-sort after a target map");
-    if (device < 0 || device >= CV_MAX_DEV || hipSetDevice(device) != hipSuccess) return fail(nullptr, ECB_ERR_NO_DEVICE, "no such device");
+    if (const int rc = use_device(device)) return rc;
     StreamGuard sg;
     if (hipStreamCreate(&sg.s) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "combine: stream");
     hipStream_t st = sg.s;
@@ -4954,15 +4934,12 @@ extern "C" int ecb_combine_device(int device, uint32_t n_parts, const ecb_combin
     // 3. rows that a target map re-numbered are re-sorted: one radix sort of (row, column) over all pairs (parts without a map are sorted already)
     u64* keys = keys0; u32* vals = vals0;
     if (any_map && NP > 1) {
-        u64 bits = 0;
-        for (u64 x = (R - 1) << 32 | (n_loci - 1); x; x >>= 1) bits = (bits << 1) | 1ull;
-        SortScratch sc{fresh<u32>(S, rs_words(NP)), fresh<u32>(S, RS_AUX_WORDS), fresh<u32>(S, rs_scan_blocks(NP) + 8), words + 1};
+        SortScratch sc{fresh<u32>(S, rs_words(NP)), fresh<u32>(S, RS_AUX_WORDS), words + 1};
         if (missing(S)) return fail(nullptr, ECB_ERR_HIP, "combine: out of device memory");
-        u64* kk[2] = {keys0, keys1}; u32* vv[2] = {vals0, vals1};
-        int where = 0;
-        const hipError_t e = radix_sort_pairs64(st, kk, vv, NP, sc, &where, bits);
+        SortBufs s{{keys0, keys1}, {vals0, vals1}};
+        const hipError_t e = radix_sort_pairs64(st, s, NP, sc, msb_mask((R - 1) << 32 | (n_loci - 1)));
         if (e != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "combine: radix sort: %s", hipGetErrorString(e));
-        keys = kk[where]; vals = vv[where];
+        keys = s.keys(); vals = s.vals();
     }
     // 4. key lists and row hashes; 5. the entries, and the key arena's worst wave
     if (NP) k_cb_hash<<<nblk(NP, TPB), TPB, 0, st>>>(keys, vals, NP, pairs, rowhash, err);
@@ -5010,20 +4987,17 @@ extern "C" int ecb_combine_device(int device, uint32_t n_parts, const ecb_combin
         u32 *flag = fresh<u32>(S, NZ), *pos = fresh<u32>(S, NZ + 1), *keep = fresh<u32>(S, NZ), *opos = fresh<u32>(S, NZ + 1);
         u32 *sums1 = fresh<u32>(S, scan_words(NZ)), *sums2 = fresh<u32>(S, scan_words(NZ));
         u64 *rsum = fresh<u64>(S, NZ), *rkey = fresh<u64>(S, NZ), *okey = fresh<u64>(S, NZ), *tot = fresh<u64>(S, 2);
-        SortScratch sc{fresh<u32>(S, rs_words(NZ)), fresh<u32>(S, RS_AUX_WORDS), fresh<u32>(S, rs_scan_blocks(NZ) + 8), words + 1};
+        SortScratch sc{fresh<u32>(S, rs_words(NZ)), fresh<u32>(S, RS_AUX_WORDS), words + 1};
         if (missing(S)) return fail(nullptr, ECB_ERR_HIP, "combine: out of device memory");
         k_cb_ntrip<<<nblk(NZ, TPB), TPB, 0, cur>>>(d_parts, n_parts, d_base, n_samples, ec_of_row, keys0, vals0, err);
         rc = check("N check");
         if (rc != ECB_OK) return rc;
-        u64* kk[2] = {keys0, keys1}; u32* vv[2] = {vals0, vals1};
-        int where = 0;
-        u64 bits = 0;
-        for (u64 x = ((u64)n_samples - 1) << 32 | (E ? E - 1 : 0); x; x >>= 1) bits = (bits << 1) | 1ull;
-        hipError_t e = radix_sort_pairs64(cur, kk, vv, NZ, sc, &where, bits);
+        SortBufs s{{keys0, keys1}, {vals0, vals1}};
+        hipError_t e = radix_sort_pairs64(cur, s, NZ, sc, msb_mask(((u64)n_samples - 1) << 32 | (E ? E - 1 : 0)));
         if (e != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "combine: radix sort: %s", hipGetErrorString(e));
-        const u64* sk = kk[where]; const u32* sv = vv[where];
+        const u64* sk = s.keys(); const u32* sv = s.vals();
         if (hipMemsetAsync(rsum, 0, NZ * 8, cur) != hipSuccess || hipMemsetAsync(tot, 0, 16, cur) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "combine: memset");
-        k_cb_heads<<<nblk(NZ, TPB), TPB, 0, cur>>>(sk, NZ, flag);
+        k_run_heads<<<nblk(NZ, TPB), TPB, 0, cur>>>(sk, NZ, flag);
         if (scan_launch(cur, flag, NZ, pos, sums1, tot) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "combine: scan");
         k_cb_nsum<<<nblk(NZ, TPB), TPB, 0, cur>>>(sk, sv, flag, pos, NZ, rsum, rkey);
         k_cb_nkeep<<<nblk(NZ, TPB), TPB, 0, cur>>>(rsum, tot, NZ, keep, err);
@@ -5049,7 +5023,7 @@ extern "C" int ecb_combine(int device, uint32_t n_parts, const ecb_combine_part*
                            int32_t* out_indptr_a, int32_t* out_indices_a, int32_t* out_data_a, int32_t* out_indptr_n, int32_t* out_indices_n,
                            int32_t* out_data_n, uint64_t* out_sizes) {
     if (!parts || !n_parts || !out_sizes || !out_indptr_a || !out_indptr_n) return fail(nullptr, ECB_ERR_ARG, "combine: bad argument");
-    if (device < 0 || device >= CV_MAX_DEV || hipSetDevice(device) != hipSuccess) return fail(nullptr, ECB_ERR_NO_DEVICE, "no such device");
+    if (const int rc = use_device(device)) return rc;
     std::vector<ecb_combine_part> dp(parts, parts + n_parts);
     std::vector<DevBuf<>> bufs((u64)n_parts * 8);
     std::vector<StageIn> in;
@@ -5293,7 +5267,6 @@ __global__ void k_sl_nemit(const u32* cnt, const u32* keep, const u32* pos, u32 
     indices[pos[l]] = (int)l;
     data[pos[l]] = (int)cnt[l];
 }
-u64 sl_bits(u64 x) { u64 b = 0; for (; x; x >>= 1) b = b << 1 | 1ull; return b; }
 }  // namespace
 
 extern "C" int ecb_salmon_ecs_device(int device, const void* d_text, uint64_t n_bytes, uint32_t n_ecs, uint32_t n_targets, const void* d_target_col,
@@ -5304,7 +5277,7 @@ extern "C" int ecb_salmon_ecs_device(int device, const void* d_text, uint64_t n_
         return fail(nullptr, ECB_ERR_ARG, "salmon: bad argument");
     if (n_loci >= MAX_LOCI) return fail(nullptr, ECB_ERR_ARG, "salmon: n_loci out of range (1 .. 2^26-3)");
     if (n_ecs >= (1u << 31) - 1u || n_targets >= (1u << 31)) return fail(nullptr, ECB_ERR_LIMIT, "salmon: E or T beyond int32");
-    if (device < 0 || device >= CV_MAX_DEV || hipSetDevice(device) != hipSuccess) return fail(nullptr, ECB_ERR_NO_DEVICE, "no such device");
+    if (const int rc = use_device(device)) return rc;
     auto refuse = [](u64 e) { const u32 r = (u32)(e & 255u); return fail(nullptr, ECB_ERR_CONTRACT, "EC line %llu: %s (reason %u)", (unsigned long long)(e >> 8), sl_reason(r), r); };
     StreamGuard sg;
     if (hipStreamCreate(&sg.s) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "salmon: stream");
@@ -5347,28 +5320,27 @@ extern "C" int ecb_salmon_ecs_device(int device, const void* d_text, uint64_t n_
     u32 *fval = fresh<u32>(S, NF), *fline = fresh<u32>(S, NF), *fend = fresh<u32>(S, n_lines), *cnt = fresh<u32>(S, n_lines);
     u64 *keys0 = fresh<u64>(S, NF), *keys1 = fresh<u64>(S, NF);
     u32 *vals0 = fresh<u32>(S, NF), *vals1 = fresh<u32>(S, NF), *flag = fresh<u32>(S, NF), *pos = fresh<u32>(S, NF + 1), *sc3 = fresh<u32>(S, scan_words(NF));
-    SortScratch ss{fresh<u32>(S, rs_words(NF)), fresh<u32>(S, RS_AUX_WORDS), fresh<u32>(S, rs_scan_blocks(NF) + 8), words + 6};
+    SortScratch ss{fresh<u32>(S, rs_words(NF)), fresh<u32>(S, RS_AUX_WORDS), words + 6};
     if (missing(S)) return fail(nullptr, ECB_ERR_HIP, "salmon: out of device memory");
     if (L) k_sl_place<<<(unsigned)nb, TPB, 0, st>>>(text, L, nl_ex, fs_ex, (u32)NF, fval, fline, fend, err);
     const u64 NP = NF >= 2 * n_lines ? NF - 2 * n_lines : 0;
     if (NF) k_sl_fields<<<nblk(NF, TPB), TPB, 0, st>>>(fval, fline, fend, (u32)NF, n_targets, tcol, thap, true, NP, keys0, vals0, cnt, err);
     if ((rc = sync("parse")) != ECB_OK) return rc;
-    u64* kk[2] = {keys0, keys1}; u32* vv[2] = {vals0, vals1};
-    int where = 0;
+    SortBufs s{{keys0, keys1}, {vals0, vals1}};
     if (back[0] != SL_NO_ERR) {
         // a malformed line: every field in a slot of its own, sorted on all bits, so that repeats in the lines before it are found too
         k_sl_fields<<<nblk(NF, TPB), TPB, 0, st>>>(fval, fline, fend, (u32)NF, n_targets, tcol, thap, false, NF, keys0, vals0, cnt, err);
-        const hipError_t e = radix_sort_pairs64(st, kk, vv, NF, ss, &where);
+        const hipError_t e = radix_sort_pairs64(st, s, NF, ss);
         if (e != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "salmon: radix sort: %s", hipGetErrorString(e));
-        k_sl_heads<<<nblk(NF, TPB), TPB, 0, st>>>(kk[where], NF, flag, err);
+        k_sl_heads<<<nblk(NF, TPB), TPB, 0, st>>>(s.keys(), NF, flag, err);
         if ((rc = sync("repeats")) != ECB_OK) return rc;
         return refuse(std::min(back[0], count_err));
     }
     // 4. sort within rows (the row and column bits only); runs, repeats refused
-    const u64 mask = sl_bits(n_lines ? n_lines - 1 : 0) << 32 | sl_bits((u64)(n_loci - 1) << 5 | 31u);
-    const hipError_t e = radix_sort_pairs64(st, kk, vv, NP, ss, &where, mask);
+    const u64 mask = msb_mask(n_lines ? n_lines - 1 : 0) << 32 | msb_mask((u64)(n_loci - 1) << 5 | 31u);
+    const hipError_t e = radix_sort_pairs64(st, s, NP, ss, mask);
     if (e != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "salmon: radix sort: %s", hipGetErrorString(e));
-    const u64* keys = kk[where]; const u32* vals = vv[where];
+    const u64* keys = s.keys(); const u32* vals = s.vals();
     if (NP) k_sl_heads<<<nblk(NP, TPB), TPB, 0, st>>>(keys, NP, flag, err);
     if (scan_launch(st, flag, NP, pos, sc3, words + 4, 1, pos + NP) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "salmon: scan");
     if ((rc = sync("runs")) != ECB_OK) return rc;
@@ -5397,7 +5369,7 @@ extern "C" int ecb_salmon_ecs(int device, const char* text, uint64_t n_bytes, ui
         (n_ecs && (!out_n_indices || !out_n_data)))
         return fail(nullptr, ECB_ERR_ARG, "salmon: bad argument");
     if (n_ecs >= (1u << 31) - 1u || capacity >= (1ull << 31)) return fail(nullptr, ECB_ERR_LIMIT, "salmon: E or the capacity beyond int32");
-    if (device < 0 || device >= CV_MAX_DEV || hipSetDevice(device) != hipSuccess) return fail(nullptr, ECB_ERR_NO_DEVICE, "no such device");
+    if (const int rc = use_device(device)) return rc;
     DevBuf<> dt, dc, dh, oip, oix, oda, onx, ond;
     const u64 rowb = ((u64)n_ecs + 1) * 4;
     if (const char* why = stage_in({{&dt, text, n_bytes}, {&dc, target_col, (u64)n_targets * 4}, {&dh, target_hap, (u64)n_targets * 4}, {&oip, nullptr, rowb},
