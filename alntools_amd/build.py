@@ -14,10 +14,18 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wal
          "-Wno-unused-function"]
 
 
+def inputs():
+    """What libecb.so is compiled from: ecb.hip, the files under csrc/ it includes, and the public header."""
+    import re
+    csrc = os.path.dirname(SRC)
+    local = set(re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(SRC).read(), re.M))
+    return [SRC] + [p for p in (os.path.normpath(os.path.join(csrc, n)) for n in sorted(local)) if os.path.dirname(p) == csrc] + [os.path.join(HERE, "..", "include", "ecb.h")]
+
+
 def needs_build():
     if not os.path.exists(OUT):
         return True
-    newest = max(os.path.getmtime(p) for p in (SRC, os.path.join(HERE, "csrc", "k_stream.inc"), os.path.join(HERE, "..", "include", "ecb.h")))
+    newest = max(os.path.getmtime(p) for p in inputs())
     return os.path.getmtime(OUT) < newest
 
 
@@ -53,8 +61,8 @@ def build_tools(force=False):
 
 def build_sanitized(out=None, verbose=False):
     """Host side of libecb under AddressSanitizer + UndefinedBehaviorSanitizer (the device code is compiled as usual:
-    GPU sanitizers are not available): ``libecb_asan.so``, for the no-GPU argument / state checking tests.  The C++ half of
-    the library is ~1.5 kLoC of manual hipMalloc / hipFree pairs and early returns."""
+    GPU sanitizers are not available): ``libecb_asan.so``, for the no-GPU argument / state checking tests: the C++ half of
+    the library is some 3 kLoC of argument checks and early returns over buffers that free themselves (DevBuf)."""
     out = out or os.path.join(HERE, "libecb_asan.so")
     cmd = [HIPCC, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-shared", "-fPIC", "-fsanitize=address,undefined",
            "-fno-gpu-sanitize", "-shared-libsan", "-Wno-unused-value", "-o", out, SRC]

@@ -2525,16 +2525,34 @@ struct ecb_handle {
 
 namespace {
 
-std::string g_create_err;
+thread_local std::string t_err;       // the text of a failing call without a handle: one per thread (ecb_last_error(NULL))
 
 int fail(ecb_handle* h, int code, const char* fmt, ...) {
     char buf[512];
     va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-    if (h) h->err = buf; else g_create_err = buf;
+    if (h) h->err = buf; else t_err = buf;
     return code;
 }
-#define HIPCHK(h, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) \
-    return fail(h, ECB_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); } while (0)
+// a failing HIP call ends the function: "<prefix><the call>: <what HIP says>"
+#define HIPCHK_AS(h, prefix, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) \
+    return fail(h, ECB_ERR_HIP, "%s%s: %s", prefix, #call, hipGetErrorString(e_)); } while (0)
+#define HIPCHK(h, call) HIPCHK_AS(h, "", call)
+
+// Error bits a kernel leaves behind, as data: the first entry of `table` with a bit in `bits` is the refusal (ECB_OK when none is
+// set), so the table's order says which one wins.  `arg` fills the one %llu a text may hold.
+struct ErrBit { u32 bit; int code; const char* text; };
+template <size_t N> int refuse_bits(ecb_handle* h, const ErrBit (&table)[N], u32 bits, unsigned long long arg = 0) {
+    for (const ErrBit& e : table) if (bits & e.bit) return fail(h, e.code, e.text, arg);
+    return ECB_OK;
+}
+const ErrBit COUNTER_ERRS[] = {
+    {ERR_CONTRACT, ECB_ERR_CONTRACT, "read_id run counter violates the tuple contract (see ecb.h)"},
+    {ERR_RANGE, ECB_ERR_CONTRACT, "locus or haplotype index out of range in a valid record"},
+    {ERR_ARENA, ECB_ERR_TABLE_FULL, "EC key arena exhausted (%llu pairs): raise arena_capacity"},
+    {ERR_QUEUE, ECB_ERR_TABLE_FULL, "deferred-read queue exhausted"},
+    {ERR_INTERNAL, ECB_ERR_HIP, "internal: an EC-table slot was claimed but its key never published"},
+    {ERR_COUNT, ECB_ERR_LIMIT, "an EC's count is above 2^31-1"},
+};
 
 u64 next_pow2(u64 x) { u64 p = 1; while (p < x) p <<= 1; return p; }
 // all ones up to the highest set bit of x (0 for 0): the bits a sort of keys no larger than x has to look at
@@ -2583,13 +2601,7 @@ int sync_counters(ecb_handle* h) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->hctr = h->pin_out->c;
     h->ctr_synced = true;
-    if (h->hctr.err & ERR_CONTRACT) return fail(h, ECB_ERR_CONTRACT, "read_id run counter violates the tuple contract (see ecb.h)");
-    if (h->hctr.err & ERR_RANGE) return fail(h, ECB_ERR_CONTRACT, "locus or haplotype index out of range in a valid record");
-    if (h->hctr.err & ERR_ARENA) return fail(h, ECB_ERR_TABLE_FULL, "EC key arena exhausted (%llu pairs): raise arena_capacity", (unsigned long long)h->arena_cap);
-    if (h->hctr.err & ERR_QUEUE) return fail(h, ECB_ERR_TABLE_FULL, "deferred-read queue exhausted");
-    if (h->hctr.err & ERR_INTERNAL) return fail(h, ECB_ERR_HIP, "internal: an EC-table slot was claimed but its key never published");
-    if (h->hctr.err & ERR_COUNT) return fail(h, ECB_ERR_LIMIT, "an EC's count is above 2^31-1");
-    return ECB_OK;
+    return refuse_bits(h, COUNTER_ERRS, h->hctr.err, h->arena_cap);
 }
 
 int grow_table(ecb_handle* h, u64 new_cap) {
@@ -3220,7 +3232,7 @@ int ecb_device_count(void) {
     return n;
 }
 
-const char* ecb_last_error(const ecb_handle* h) { return h ? h->err.c_str() : g_create_err.c_str(); }
+const char* ecb_last_error(const ecb_handle* h) { return h ? h->err.c_str() : t_err.c_str(); }
 
 int ecb_create(const ecb_config* cfg, ecb_handle** out) {
     if (!cfg || !out || cfg->struct_size != sizeof(ecb_config)) return fail(nullptr, ECB_ERR_ARG, "bad ecb_config (struct_size)");
@@ -4048,13 +4060,16 @@ int ecb_ms_filter(ecb_handle* h, uint32_t n_cells, int64_t minimum_count, ecb_ms
     k_msf2_cellflag<<<nblk(n_cells, TPB), TPB, 0, st>>>(total, n_cells, flag);
     u64 C = 0;
     rc = excl_scan(h, flag, n_cells, pos, &C); if (rc != ECB_OK) return rc;
-    {
-        u32 err = 0;
-        HIPCHK(h, hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipStreamSynchronize(st));
-        if (err & 1u) return fail(h, ECB_ERR_CONTRACT, "triple with an EC id beyond the finalized ECs");
-        if (err & 2u) return fail(h, ECB_ERR_CONTRACT, "a read's cell id is not below n_cells");
-    }
+    // (the bits come in the table's order: 1 and 2 from the passes above, 4 from k_msf2_pairs below, behind this check)
+    static const ErrBit MSF_ERRS[] = {
+        {1u, ECB_ERR_CONTRACT, "triple with an EC id beyond the finalized ECs"},
+        {2u, ECB_ERR_CONTRACT, "a read's cell id is not below n_cells"},
+        {4u, ECB_ERR_LIMIT, "an entry of N (the reads of one EC in one cell) is above 2^31-1"},
+    };
+    u32 err = 0;
+    HIPCHK(h, hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    rc = refuse_bits(h, MSF_ERRS, err); if (rc != ECB_OK) return rc;
     if (!C) return fail(h, ECB_ERR_EMPTY, "no (EC, cell) counts: nothing to filter");
     u32 *cell_id = fresh<u32>(sc, C), *corder = fresh<u32>(sc, C), *corder2 = fresh<u32>(sc, C), *cflag = fresh<u32>(sc, C), *cpos = fresh<u32>(sc, C);
     u64 *ctotal = fresh<u64>(sc, C), *bhi = fresh<u64>(sc, C), *blo = fresh<u64>(sc, C), *ck0 = fresh<u64>(sc, C), *ck1 = fresh<u64>(sc, C);
@@ -4102,10 +4117,9 @@ int ecb_ms_filter(ecb_handle* h, uint32_t n_cells, int64_t minimum_count, ecb_ms
     { const u32 last = (u32)nnz_a; HIPCHK(h, hipMemcpyAsync(h->f_ipa + E2, &last, 4, hipMemcpyHostToDevice, st)); HIPCHK(h, hipStreamSynchronize(st)); }
     POOL(h, P_F_IXA, h->f_ixa, nnz_a); POOL(h, P_F_DAA, h->f_daa, nnz_a);
     k_msf_rows<<<nblk(E, TPB), TPB, 0, st>>>(h->indptr, h->indices, h->data, keep_ec, new_rank, reinterpret_cast<const u32*>(h->f_ipa), E, h->f_ixa, h->f_daa);
-    u32 err = 0;
     HIPCHK(h, hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));
-    if (err & 4u) return fail(h, ECB_ERR_LIMIT, "an entry of N (the reads of one EC in one cell) is above 2^31-1");
+    rc = refuse_bits(h, MSF_ERRS, err); if (rc != ECB_OK) return rc;
     h->msf.n_cells_seen = C; h->msf.n_cells_kept = S; h->msf.n_ecs_kept = E2; h->msf.nnz_a = nnz_a; h->msf.nnz_n = nnz_n;
     h->ms_filtered = true;
     *out = h->msf;
@@ -4169,34 +4183,88 @@ const char* ecb_profile_kernel(const ecb_handle* h) { return h ? h->last_kernel 
 
 }  // extern "C"
 
-// ---- f-2 conversions (stateless; scratch is allocated per call: this is not the hot path) ------------------------
-namespace {
-int cv_scan(hipStream_t st, const u32* in, u64 n, u32* out, u64* total, std::vector<DevBuf<>>& sc) {
-    u32* sums = fresh<u32>(sc, scan_words(n) + 4);
-    if (!sums) return ECB_ERR_HIP;
-    u64* grand = reinterpret_cast<u64*>(sums + scan_words(n));
-    if (scan_launch(st, in, n, out, sums, grand) != hipSuccess) return ECB_ERR_HIP;
-    if (hipMemcpyAsync(total, grand, 8, hipMemcpyDeviceToHost, st) != hipSuccess) return ECB_ERR_HIP;
-    return hipStreamSynchronize(st) == hipSuccess ? ECB_OK : ECB_ERR_HIP;
-}
-}  // namespace
-
-// Scratch of the stateless conversions, kept per device between calls (grown on demand; ecb_release_scratch frees it): a
-// config-3-sized conversion needs ~0.4 GB in a dozen buffers, and a dozen hipMallocs cost more than its kernels do.
+// ---- the entry points that take a device instead of a handle (the f-2 conversions, apply-mask, combine, salmon) --------------------------
+// Each is one Call.  Its scratch has two backings behind one get: the conversions and apply-mask take theirs from a pool
+// kept per device between calls (grown on demand; ecb_release_scratch frees it) -- a config-3-sized conversion needs ~0.4 GB in a dozen
+// buffers, and a dozen hipMallocs cost more than its kernels do; combine, salmon and the conversion's sort-everything path take buffers of
+// their own, freed with the Call.  The pool serves all threads: g_cv_lock is held from a call's first pool buffer to its end.
 namespace {
 enum { CV_KEYS0, CV_KEYS1, CV_VALS0, CV_VALS1, CV_HIST, CV_OFFS, CV_SUMS2, CV_BLK, CV_SCAN, CV_HEAD, CV_WORDS, CV_X0, CV_X1, CV_X2, CV_X3, CV_N };
 constexpr int CV_MAX_DEV = 64;
 DevBuf<>* const g_cv = new DevBuf<>[CV_MAX_DEV * CV_N];      // (never destroyed: no HIP call may run after the runtime has gone, at exit)
 std::mutex g_cv_lock;
-// device `device`'s buffer `id`, holding at least max(count, 1) T's (regrown with an eighth more); nullptr when it cannot be had
-template <class T> T* cv_get(int device, int id, u64 count) {
-    DevBuf<>& b = g_cv[device * CV_N + id];
-    const u64 need = std::max<u64>(count, 1) * sizeof(T);
-    return b.regrow(need, need / 8) == hipSuccess ? b.as<T>() : nullptr;
-}
-// a stateless entry point's device made current: ECB_OK, or the error to return
-int use_device(int device) {
-    if (device < 0 || device >= CV_MAX_DEV || hipSetDevice(device) != hipSuccess) return fail(nullptr, ECB_ERR_NO_DEVICE, "no such device");
+struct StreamGuard { hipStream_t s = nullptr; ~StreamGuard() { if (s) { hipStreamSynchronize(s); hipStreamDestroy(s); } } };
+
+#define CALLCHK(c, call) HIPCHK_AS(nullptr, (c).prefix, call)
+struct Call {
+    const int device;
+    const char* const prefix;            // of this entry point's ECB_ERR_HIP texts ("combine: ")
+    StreamGuard own;                     // the stream of a call that has one of its own (waited for and destroyed after the scratch has gone)
+    hipStream_t st = nullptr;            // where the call's work goes: the null stream, or own.s
+    std::unique_lock<std::mutex> pool;   // g_cv_lock, once a pool buffer has been handed out
+    std::vector<DevBuf<>> keep;          // this call's own buffers
+    bool short_of = false;               // a get came back empty
+    const int rc;                        // ECB_OK, or why there is no call: the entry point returns it
+
+    Call(int device_, const char* prefix_, bool own_stream = false) : device(device_), prefix(prefix_), rc(open(own_stream)) {}
+    int open(bool own_stream) {
+        if (device < 0 || device >= CV_MAX_DEV || hipSetDevice(device) != hipSuccess) return fail(nullptr, ECB_ERR_NO_DEVICE, "no such device");
+        if (own_stream) { CALLCHK(*this, hipStreamCreate(&own.s)); st = own.s; }
+        return ECB_OK;
+    }
+    // max(n, 1) T's: a fresh buffer that lives as long as the call, or the device's pool buffer `id`, regrown with an eighth more when it
+    // is too small.  nullptr when it cannot be had: see missing
+    template <class T> T* get(u64 n) { keep.emplace_back(); return got<T>(keep.back(), keep.back().alloc(std::max<u64>(n, 1) * sizeof(T))); }
+    template <class T> T* get(int id, u64 n) {
+        if (!pool) pool = std::unique_lock<std::mutex>(g_cv_lock);
+        DevBuf<>& b = g_cv[device * CV_N + id];
+        const u64 need = std::max<u64>(n, 1) * sizeof(T);
+        return got<T>(b, b.regrow(need, need / 8));
+    }
+    template <class T> T* got(const DevBuf<>& b, hipError_t e) { short_of |= e != hipSuccess; return e == hipSuccess ? b.as<T>() : nullptr; }
+    // after a run of get: ECB_OK, or the refusal when one of them came back empty
+    int missing() const { return short_of ? fail(nullptr, ECB_ERR_HIP, "%sout of device memory", prefix) : ECB_OK; }
+    // n of the call's status words to the host, on its stream, and waited for; with a table, the error bits in word 0 refused
+    int read_back(u64* host, const u64* words, u64 n) {
+        CALLCHK(*this, hipMemcpyAsync(host, words, n * 8, hipMemcpyDeviceToHost, st));
+        CALLCHK(*this, hipStreamSynchronize(st));
+        return ECB_OK;
+    }
+    template <size_t N> int read_back(u64* host, const u64* words, u64 n, const ErrBit (&table)[N]) {
+        const int r = read_back(host, words, n);
+        return r != ECB_OK ? r : refuse_bits(nullptr, table, (u32)host[0]);
+    }
+};
+
+const ErrBit CV_ERRS[] = {{~0u, ECB_ERR_CONTRACT, "malformed CSR: row pointers out of order, a locus beyond n_loci, or a mask that is zero or beyond n_haplotypes"}};
+const ErrBit CVB_ERRS[] = {      // (CVB_ERR_ORDER is no refusal: the sort-everything path takes such a matrix)
+    {CVB_ERR_PTR, ECB_ERR_CONTRACT, "malformed CSC: column pointers do not start at zero or go backwards"},
+    {CVB_ERR_EC, ECB_ERR_CONTRACT, "malformed CSC: a row index beyond the number of ECs"},
+};
+// the general case: lists in any order, an EC more than once in a list -- every row index becomes a 64-bit key, all of them are sorted
+// (rare, and as large as the matrix: in buffers of its own, not the pool's)
+int hapcsc_to_csr_general(Call& c, u32 n_ecs, u32 n_loci, u32 n_haps, const void* d_cscptr, const void* d_cscidx, u64 total,
+                          const std::vector<u64>& hs, void* d_indptr, void* d_indices, void* d_data, uint64_t* nnz_out) {
+    hipStream_t st = c.st;
+    u64 *d_hs = c.get<u64>(n_haps + 1), *keys = c.get<u64>(total), *keys2 = c.get<u64>(total);
+    u32 *vals = c.get<u32>(total), *vals2 = c.get<u32>(total), *flag = c.get<u32>(total), *pos = c.get<u32>(total);
+    if (const int rc = c.missing()) return rc;
+    CALLCHK(c, hipMemcpy(d_hs, hs.data(), (n_haps + 1) * 8, hipMemcpyHostToDevice));
+    k_cv_back_expand<<<nblk(total, TPB), TPB, 0, st>>>((const int*)d_cscptr, (const int*)d_cscidx, total, n_loci, n_haps, d_hs, keys, vals);
+    SortScratch ss{c.get<u32>(rs_words(total)), c.get<u32>(RS_AUX_WORDS), c.get<u64>(1)};
+    u32* sums = c.get<u32>(scan_words(total) + 4);                  // (the scan's total behind its words)
+    if (const int rc = c.missing()) return rc;
+    u64* grand = reinterpret_cast<u64*>(sums + scan_words(total));
+    SortBufs s{{keys, keys2}, {vals, vals2}};
+    CALLCHK(c, radix_sort_pairs64(st, s, total, ss));
+    k_run_heads<<<nblk(total, TPB), TPB, 0, st>>>(s.keys(), total, flag);
+    u64 nnz = 0;
+    CALLCHK(c, scan_launch(st, flag, total, pos, sums, grand));
+    if (const int rc = c.read_back(&nnz, grand, 1)) return rc;
+    k_cv_back_emit<<<nblk(total, TPB), TPB, 0, st>>>(s.keys(), s.vals(), flag, pos, total, n_loci, (int*)d_indices, (int*)d_data);
+    k_cv_back_rowptr<<<nblk((u64)n_ecs + 1, TPB), TPB, 0, st>>>(s.keys(), pos, total, nnz, n_ecs, n_loci, (int*)d_indptr);
+    CALLCHK(c, hipStreamSynchronize(st));
+    *nnz_out = nnz;
     return ECB_OK;
 }
 }  // namespace
@@ -4214,82 +4282,56 @@ extern "C" int ecb_csr_to_hapcsc_device(int device, uint32_t n_ecs, uint32_t n_l
                                         uint64_t* total) {
     if (!d_indptr || !total || !n_ecs || !n_loci || !n_haps || n_haps > 31) return fail(nullptr, ECB_ERR_ARG, "bad argument");
     if ((u64)n_haps * n_loci >= (1ull << 32)) return fail(nullptr, ECB_ERR_LIMIT, "haplotypes x loci does not fit 32 bits");
-    if (const int rc = use_device(device)) return rc;
-    hipStream_t st = nullptr;
+    Call c(device, ""); if (c.rc) return c.rc;
+    hipStream_t st = c.st;
     int nnz_i = 0;
-    if (hipMemcpy(&nnz_i, (const int*)d_indptr + n_ecs, 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "read nnz");
+    CALLCHK(c, hipMemcpy(&nnz_i, (const int*)d_indptr + n_ecs, 4, hipMemcpyDeviceToHost));
     if (nnz_i < 0) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSR: negative row pointer");
     const u64 nnz = (u64)nnz_i;
     if (nnz && (!d_indices || !d_data)) return fail(nullptr, ECB_ERR_ARG, "bad argument");       // (a matrix without non-zeros has no arrays to point at)
-    std::lock_guard<std::mutex> guard(g_cv_lock);
-    u64* words = cv_get<u64>(device, CV_WORDS, 4);                  // [0] set bits, [1] the scan's total, [2] error bits
-    if (!words) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
+    u64* words = c.get<u64>(CV_WORDS, 4);                          // [0] set bits, [1] the scan's total, [2] error bits
+    if (const int rc = c.missing()) return rc;
     if (!d_cscidx || !d_cscptr) {                                  // the first call: how many row indices there will be
         u64 tot = 0;
-        if (hipMemsetAsync(words, 0, 8, st) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "memset");
+        CALLCHK(c, hipMemsetAsync(words, 0, 8, st));
         if (nnz) k_cv_bits<<<(unsigned)std::min<u64>(2048, nblk(nnz, TPB)), TPB, 0, st>>>((const int*)d_data, nnz, words);
-        if (hipMemcpy(&tot, words, 8, hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "count");
+        if (const int rc = c.read_back(&tot, words, 1)) return rc;
         if (tot >= (1ull << 32)) return fail(nullptr, ECB_ERR_LIMIT, "more than 2^32-1 set haplotype bits");
         *total = tot;
         return ECB_OK;
     }
     const u64 nc = (u64)n_haps * (n_loci + 1);
     if (!nnz) {
-        if (hipMemset(d_cscptr, 0, nc * 4) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "memset");
+        CALLCHK(c, hipMemset(d_cscptr, 0, nc * 4));
         *total = 0;
         return ECB_OK;
     }
     const u32 nb = (u32)nblk(nnz, CVB);
-    u64 *k0 = cv_get<u64>(device, CV_KEYS0, nnz), *k1 = cv_get<u64>(device, CV_KEYS1, nnz);
-    u32 *v0 = cv_get<u32>(device, CV_VALS0, nnz), *v1 = cv_get<u32>(device, CV_VALS1, nnz);
-    SortScratch ss{cv_get<u32>(device, CV_HIST, rs_words(nnz)), cv_get<u32>(device, CV_OFFS, RS_AUX_WORDS), words + 3};
-    u32 *blk = cv_get<u32>(device, CV_BLK, (u64)n_haps * nb), *scan = cv_get<u32>(device, CV_SCAN, (u64)n_haps * nb);
-    u32 *sums2 = cv_get<u32>(device, CV_SUMS2, scan_words((u64)n_haps * nb) + 2), *headval = cv_get<u32>(device, CV_HEAD, (u64)n_haps * n_loci);
-    if (!k0 || !k1 || !v0 || !v1 || !ss.hist || !ss.offs || !blk || !scan || !sums2 || !headval) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
-    if (hipMemsetAsync(words, 0, 24, st) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "memset");
+    u64 *k0 = c.get<u64>(CV_KEYS0, nnz), *k1 = c.get<u64>(CV_KEYS1, nnz);
+    u32 *v0 = c.get<u32>(CV_VALS0, nnz), *v1 = c.get<u32>(CV_VALS1, nnz);
+    SortScratch ss{c.get<u32>(CV_HIST, rs_words(nnz)), c.get<u32>(CV_OFFS, RS_AUX_WORDS), words + 3};
+    u32 *blk = c.get<u32>(CV_BLK, (u64)n_haps * nb), *scan = c.get<u32>(CV_SCAN, (u64)n_haps * nb);
+    u32 *sums2 = c.get<u32>(CV_SUMS2, scan_words((u64)n_haps * nb) + 2), *headval = c.get<u32>(CV_HEAD, (u64)n_haps * n_loci);
+    if (const int rc = c.missing()) return rc;
+    CALLCHK(c, hipMemsetAsync(words, 0, 24, st));
     k_cv_keys<<<nblk(n_ecs, TPB), TPB, 0, st>>>((const int*)d_indptr, n_ecs, (const int*)d_indices, (const int*)d_data, nnz, n_loci, n_haps,
                                                k0, v0, reinterpret_cast<u32*>(words + 2));
     SortBufs s{{k0, k1}, {v0, v1}};
     // stable sort on the locus alone: ECs stay ascending within a column, as scipy's tocsc() leaves them
-    if (radix_sort_pairs64(st, s, nnz, ss, msb_mask(n_loci - 1) << 32) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "sort");
+    CALLCHK(c, radix_sort_pairs64(st, s, nnz, ss, msb_mask(n_loci - 1) << 32));
     const u64* keys = s.keys(); const u32* masks = s.vals();
     k_cv_cnt<<<nb, TPB, 0, st>>>(masks, nnz, n_haps, nb, blk);
-    (void)scan_launch(st, blk, (u64)n_haps * nb, scan, sums2, words + 1);
+    CALLCHK(c, scan_launch(st, blk, (u64)n_haps * nb, scan, sums2, words + 1));
     u64 back[3] = {0, 0, 0};
-    if (hipMemcpy(back, words, 24, hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "csr -> csc (count)");
-    if (back[2]) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSR: row pointers out of order, a locus beyond n_loci, or a mask that is zero or beyond n_haplotypes");
+    if (const int rc = c.read_back(back, words, 3)) return rc;
+    if (const int rc = refuse_bits(nullptr, CV_ERRS, (u32)back[2])) return rc;
     if (back[1] >= (1ull << 32)) return fail(nullptr, ECB_ERR_LIMIT, "more than 2^32-1 set haplotype bits");
     *total = back[1];
     k_cv_emit<<<nb, TPB, 0, st>>>(keys, masks, nnz, n_haps, n_loci, nb, scan, (int*)d_cscidx, headval);
     k_cv_ptr<<<nblk((u64)n_loci + 1, TPB), TPB, 0, st>>>(keys, nnz, n_loci, n_haps, nb, scan, words + 1, headval, (int*)d_cscptr);
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "csr -> csc");
+    CALLCHK(c, hipStreamSynchronize(st));
     return ECB_OK;
 }
-
-namespace {
-// the general case: lists in any order, an EC more than once in a list -- every row index becomes a 64-bit key, all of them are sorted
-int hapcsc_to_csr_general(hipStream_t st, u32 n_ecs, u32 n_loci, u32 n_haps, const void* d_cscptr, const void* d_cscidx, u64 total,
-                          const std::vector<u64>& hs, void* d_indptr, void* d_indices, void* d_data, uint64_t* nnz_out) {
-    std::vector<DevBuf<>> sc;
-    u64 *d_hs = fresh<u64>(sc, n_haps + 1), *keys = fresh<u64>(sc, total), *keys2 = fresh<u64>(sc, total);
-    u32 *vals = fresh<u32>(sc, total), *vals2 = fresh<u32>(sc, total), *flag = fresh<u32>(sc, total), *pos = fresh<u32>(sc, total);
-    if (missing(sc)) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
-    hipMemcpy(d_hs, hs.data(), (n_haps + 1) * 8, hipMemcpyHostToDevice);
-    k_cv_back_expand<<<nblk(total, TPB), TPB, 0, st>>>((const int*)d_cscptr, (const int*)d_cscidx, total, n_loci, n_haps, d_hs, keys, vals);
-    SortScratch ss{fresh<u32>(sc, rs_words(total)), fresh<u32>(sc, RS_AUX_WORDS), fresh<u64>(sc, 1)};
-    if (missing(sc)) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
-    SortBufs s{{keys, keys2}, {vals, vals2}};
-    if (radix_sort_pairs64(st, s, total, ss) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "sort");
-    k_run_heads<<<nblk(total, TPB), TPB, 0, st>>>(s.keys(), total, flag);
-    u64 nnz = 0;
-    if (cv_scan(st, flag, total, pos, &nnz, sc) != ECB_OK) return fail(nullptr, ECB_ERR_HIP, "scan");
-    k_cv_back_emit<<<nblk(total, TPB), TPB, 0, st>>>(s.keys(), s.vals(), flag, pos, total, n_loci, (int*)d_indices, (int*)d_data);
-    k_cv_back_rowptr<<<nblk((u64)n_ecs + 1, TPB), TPB, 0, st>>>(s.keys(), pos, total, nnz, n_ecs, n_loci, (int*)d_indptr);
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "csc -> csr");
-    *nnz_out = nnz;
-    return ECB_OK;
-}
-}  // namespace
 
 extern "C" int ecb_hapcsc_to_csr_device(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, const void* d_cscptr,
                                         const void* d_cscidx, uint64_t total, void* d_indptr, void* d_indices, void* d_data,
@@ -4297,64 +4339,61 @@ extern "C" int ecb_hapcsc_to_csr_device(int device, uint32_t n_ecs, uint32_t n_l
     if (!d_cscptr || !d_cscidx || !d_indptr || !d_indices || !d_data || !nnz_out || !n_ecs || !n_loci || !n_haps || n_haps > 31 || !total)
         return fail(nullptr, ECB_ERR_ARG, "bad argument");
     if (total >= (1ull << 32)) return fail(nullptr, ECB_ERR_LIMIT, "more than 2^32-1 row indices");
-    if (const int rc = use_device(device)) return rc;
-    hipStream_t st = nullptr;
-    std::lock_guard<std::mutex> guard(g_cv_lock);
+    Call c(device, ""); if (c.rc) return c.rc;
+    hipStream_t st = c.st;
     // start of every haplotype's block = running sum of its last column pointer
-    u64* words = cv_get<u64>(device, CV_WORDS, 40);                 // [0] error bits  [1] the scan's total  [3] the sort's  [4 ..) last pointers, then block starts
-    if (!words) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
+    u64* words = c.get<u64>(CV_WORDS, 40);                          // [0] error bits  [1] the scan's total  [3] the sort's  [4 ..) last pointers, then block starts
+    if (const int rc = c.missing()) return rc;
     int* d_last = reinterpret_cast<int*>(words + 4);
     std::vector<int> last(n_haps);
     k_cvb_last<<<1, 64, 0, st>>>((const int*)d_cscptr, n_loci, n_haps, d_last);
-    if (hipMemcpy(last.data(), d_last, n_haps * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "read csc pointers");
+    CALLCHK(c, hipMemcpy(last.data(), d_last, n_haps * 4, hipMemcpyDeviceToHost));
     std::vector<u64> hs(n_haps + 1, 0);
     for (u32 h = 0; h < n_haps; ++h) {
         if (last[h] < 0) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSC: negative column pointer");
         hs[h + 1] = hs[h] + (u64)last[h];
     }
     if (hs[n_haps] != total) return fail(nullptr, ECB_ERR_ARG, "total does not match the column pointers");
-    u64* d_hs = cv_get<u64>(device, CV_X0, n_haps + 1);
-    u32 *Ssum = cv_get<u32>(device, CV_X1, (u64)n_loci + 1);
-    u32 *colcnt = cv_get<u32>(device, CV_HEAD, 5ull * n_loci + 8), *sums = cv_get<u32>(device, CV_SUMS2, scan_words(n_loci) + 2);
-    if (!d_hs || !Ssum || !colcnt || !sums) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
+    u64* d_hs = c.get<u64>(CV_X0, n_haps + 1);
+    u32 *Ssum = c.get<u32>(CV_X1, (u64)n_loci + 1);
+    u32 *colcnt = c.get<u32>(CV_HEAD, 5ull * n_loci + 8), *sums = c.get<u32>(CV_SUMS2, scan_words(n_loci) + 2);
+    if (const int rc = c.missing()) return rc;
     u32 *colbase = colcnt + n_loci, *colcur = colbase + n_loci, *pieces = colcur + n_loci, *pbase = pieces + n_loci;
     u32* d_err = reinterpret_cast<u32*>(words);
-    if (hipMemcpyAsync(d_hs, hs.data(), (n_haps + 1) * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemsetAsync(words, 0, 24, st) != hipSuccess || hipMemsetAsync(colcnt, 0, 3ull * n_loci * 4, st) != hipSuccess)
-        return fail(nullptr, ECB_ERR_HIP, "csc -> csr (set-up)");
+    CALLCHK(c, hipMemcpyAsync(d_hs, hs.data(), (n_haps + 1) * 8, hipMemcpyHostToDevice, st));
+    CALLCHK(c, hipMemsetAsync(words, 0, 24, st));
+    CALLCHK(c, hipMemsetAsync(colcnt, 0, 3ull * n_loci * 4, st));
     k_cvu_colsum<<<nblk((u64)n_loci + 1, TPB), TPB, 0, st>>>((const int*)d_cscptr, n_loci, n_haps, Ssum, d_err);
     k_cvu_pieces<<<nblk(n_loci, TPB), TPB, 0, st>>>(Ssum, n_loci, pieces);
-    (void)scan_launch(st, pieces, n_loci, pbase, sums, words + 2);
+    CALLCHK(c, scan_launch(st, pieces, n_loci, pbase, sums, words + 2));
     u64 back[3] = {0, 0, 0};
-    if (hipMemcpy(back, words, 24, hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "csc -> csr (pointers)");
-    if ((u32)back[0]) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSC: column pointers do not start at zero or go backwards");
+    if (const int rc = c.read_back(back, words, 3, CVB_ERRS)) return rc;           // (CVB_ERR_PTR: nothing else has run)
     const u64 n_items = back[2];
     if (n_items == 0 || n_items >= (1ull << 31)) return fail(nullptr, ECB_ERR_LIMIT, "csc -> csr: pieces of work");
-    u32 *item_col = cv_get<u32>(device, CV_X2, n_items + 1), *bnd = cv_get<u32>(device, CV_X3, (n_items + 1) * n_haps);
-    if (!item_col || !bnd) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
+    u32 *item_col = c.get<u32>(CV_X2, n_items + 1), *bnd = c.get<u32>(CV_X3, (n_items + 1) * n_haps);
+    if (const int rc = c.missing()) return rc;
     k_cvu_items<<<nblk(n_loci, TPB), TPB, 0, st>>>(pieces, pbase, n_loci, item_col);
     k_cvu_bounds<<<nblk(n_items * n_haps, TPB), TPB, 0, st>>>((const int*)d_cscptr, (const int*)d_cscidx, d_hs, pieces, pbase, item_col, (u32)n_items,
                                                              n_loci, n_haps, n_ecs, bnd);
     k_cvu_union<false><<<(unsigned)n_items, CVU_TPB, 0, st>>>((const int*)d_cscptr, (const int*)d_cscidx, d_hs, pieces, pbase, item_col, bnd, (u32)n_items,
                                                               n_loci, n_haps, n_ecs, colcnt, colbase, colcur, 0, nullptr, nullptr, d_err);
-    (void)scan_launch(st, colcnt, n_loci, colbase, sums, words + 1);
-    if (hipMemcpy(back, words, 16, hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "csc -> csr (union)");
-    if ((u32)back[0] & CVB_ERR_EC) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSC: a row index beyond the number of ECs");
+    CALLCHK(c, scan_launch(st, colcnt, n_loci, colbase, sums, words + 1));
+    if (const int rc = c.read_back(back, words, 2, CVB_ERRS)) return rc;
     if ((u32)back[0] & CVB_ERR_ORDER)                              // a long column whose lists are not ascending: sort everything
-        return hapcsc_to_csr_general(st, n_ecs, n_loci, n_haps, d_cscptr, d_cscidx, total, hs, d_indptr, d_indices, d_data, nnz_out);
+        return hapcsc_to_csr_general(c, n_ecs, n_loci, n_haps, d_cscptr, d_cscidx, total, hs, d_indptr, d_indices, d_data, nnz_out);
     const u64 nnz = back[1];
-    u64 *k0 = cv_get<u64>(device, CV_KEYS0, nnz), *k1 = cv_get<u64>(device, CV_KEYS1, nnz);
-    u32 *v0 = cv_get<u32>(device, CV_VALS0, nnz), *v1 = cv_get<u32>(device, CV_VALS1, nnz);
-    SortScratch ss{cv_get<u32>(device, CV_HIST, rs_words(nnz)), cv_get<u32>(device, CV_OFFS, RS_AUX_WORDS), words + 3};
-    if (!k0 || !k1 || !v0 || !v1 || !ss.hist || !ss.offs) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
+    u64 *k0 = c.get<u64>(CV_KEYS0, nnz), *k1 = c.get<u64>(CV_KEYS1, nnz);
+    u32 *v0 = c.get<u32>(CV_VALS0, nnz), *v1 = c.get<u32>(CV_VALS1, nnz);
+    SortScratch ss{c.get<u32>(CV_HIST, rs_words(nnz)), c.get<u32>(CV_OFFS, RS_AUX_WORDS), words + 3};
+    if (const int rc = c.missing()) return rc;
     k_cvu_union<true><<<(unsigned)n_items, CVU_TPB, 0, st>>>((const int*)d_cscptr, (const int*)d_cscidx, d_hs, pieces, pbase, item_col, bnd, (u32)n_items,
                                                              n_loci, n_haps, n_ecs, colcnt, colbase, colcur, nnz, k0, v0, d_err);
     SortBufs s{{k0, k1}, {v0, v1}};
     // stable, on the EC alone: what left column by column arrives row by row with its loci ascending
-    if (radix_sort_pairs64(st, s, nnz, ss, msb_mask(n_ecs - 1) << 32) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "sort");
+    CALLCHK(c, radix_sort_pairs64(st, s, nnz, ss, msb_mask(n_ecs - 1) << 32));
     k_split_out<<<nblk(nnz, TPB), TPB, 0, st>>>(s.keys(), s.vals(), nnz, (int*)d_indices, (int*)d_data);
     k_row_ptr<<<nblk((u64)n_ecs + 1, TPB), TPB, 0, st>>>(s.keys(), nnz, n_ecs, (int*)d_indptr);
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "csc -> csr");
+    CALLCHK(c, hipStreamSynchronize(st));
     *nnz_out = nnz;
     return ECB_OK;
 }
@@ -4363,26 +4402,26 @@ extern "C" int ecb_hapcsc_to_csr_device(int device, uint32_t n_ecs, uint32_t n_l
 // that only converts files (alntools ec2emase / emase2ec, the .h5 writer of bam2emase: bin_utils.py:979-1028) needs no device
 // allocator of its own -- and the Python drop-in no PyTorch on that path.
 namespace {
-// every array in a fresh device buffer of max(bytes, 4) bytes (in list order), then the inputs copied in; what failed, or nullptr
+// every array in a fresh device buffer of max(bytes, 4) bytes (in list order), then the inputs copied in
 struct StageIn { DevBuf<>* d; const void* src; u64 bytes; };          // (src null: an output, allocated only)
-const char* stage_in(const std::vector<StageIn>& list) {
-    for (const StageIn& a : list) if (a.d->alloc(a.bytes, 4) != hipSuccess) return "out of device memory";
+int stage_in(const Call& c, const std::vector<StageIn>& list) {
+    for (const StageIn& a : list) CALLCHK(c, a.d->alloc(a.bytes, 4));
     for (const StageIn& a : list)
-        if (a.src && a.bytes && hipMemcpy(a.d->p, a.src, a.bytes, hipMemcpyHostToDevice) != hipSuccess) return "copy to the device";
-    return nullptr;
+        if (a.src && a.bytes) CALLCHK(c, hipMemcpy(a.d->p, a.src, a.bytes, hipMemcpyHostToDevice));
+    return ECB_OK;
 }
-// the results back: `bytes` of each (none when that is 0); false when a copy fails
+// the results back: `bytes` of each (none when that is 0)
 struct StageOut { void* dst; const DevBuf<>* d; u64 bytes; };
-bool stage_out(const std::vector<StageOut>& list) {
-    for (const StageOut& a : list) if (a.bytes && hipMemcpy(a.dst, a.d->p, a.bytes, hipMemcpyDeviceToHost) != hipSuccess) return false;
-    return true;
+int stage_out(const Call& c, const std::vector<StageOut>& list) {
+    for (const StageOut& a : list) if (a.bytes) CALLCHK(c, hipMemcpy(a.dst, a.d->p, a.bytes, hipMemcpyDeviceToHost));
+    return ECB_OK;
 }
 }  // namespace
 
 extern "C" int ecb_csr_to_hapcsc(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, const int32_t* indptr, const int32_t* indices,
                                  const int32_t* data, int32_t* csc_indptr, int32_t* csc_indices, uint64_t capacity, uint64_t* total) {
     if (!indptr || !total || !n_ecs || !n_loci || !n_haps || n_haps > 31) return fail(nullptr, ECB_ERR_ARG, "bad argument");
-    if (const int rc = use_device(device)) return rc;
+    Call c(device, ""); if (c.rc) return c.rc;
     if (indptr[n_ecs] < 0) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSR: negative row pointer");
     const u64 nnz = (u64)indptr[n_ecs];
     if (nnz && (!indices || !data)) return fail(nullptr, ECB_ERR_ARG, "bad argument");
@@ -4395,19 +4434,17 @@ extern "C" int ecb_csr_to_hapcsc(int device, uint32_t n_ecs, uint32_t n_loci, ui
     }
     DevBuf<> ip, ix, da, cp, ci;
     const u64 nc = (u64)n_haps * (n_loci + 1);
-    if (const char* why = stage_in({{&ip, indptr, ((u64)n_ecs + 1) * 4}, {&ix, indices, nnz * 4}, {&da, data, nnz * 4}, {&cp, nullptr, nc * 4},
-                                    {&ci, nullptr, capacity * 4}}))
-        return fail(nullptr, ECB_ERR_HIP, "%s", why);
+    int rc = stage_in(c, {{&ip, indptr, ((u64)n_ecs + 1) * 4}, {&ix, indices, nnz * 4}, {&da, data, nnz * 4}, {&cp, nullptr, nc * 4},
+                          {&ci, nullptr, capacity * 4}});
     // (the device entry point writes at most one row index per set bit: ask it for the count first when the caller's buffer might be short)
     uint64_t need = 0;
-    int rc = ecb_csr_to_hapcsc_device(device, n_ecs, n_loci, n_haps, ip.p, ix.p, da.p, nullptr, nullptr, &need);
+    if (rc == ECB_OK) rc = ecb_csr_to_hapcsc_device(device, n_ecs, n_loci, n_haps, ip.p, ix.p, da.p, nullptr, nullptr, &need);
     if (rc != ECB_OK) return rc;
     *total = need;
     if (need > capacity) return fail(nullptr, ECB_ERR_ARG, "csc_indices holds %llu entries, the matrix has %llu set bits", (unsigned long long)capacity, (unsigned long long)need);
     rc = ecb_csr_to_hapcsc_device(device, n_ecs, n_loci, n_haps, ip.p, ix.p, da.p, cp.p, ci.p, total);
     if (rc != ECB_OK) return rc;
-    if (!stage_out({{csc_indptr, &cp, nc * 4}, {csc_indices, &ci, *total * 4}})) return fail(nullptr, ECB_ERR_HIP, "copy from the device");
-    return ECB_OK;
+    return stage_out(c, {{csc_indptr, &cp, nc * 4}, {csc_indices, &ci, *total * 4}});
 }
 
 extern "C" int ecb_hapcsc_to_csr(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, const int32_t* csc_indptr, const int32_t* csc_indices,
@@ -4415,16 +4452,13 @@ extern "C" int ecb_hapcsc_to_csr(int device, uint32_t n_ecs, uint32_t n_loci, ui
     if (!csc_indptr || !csc_indices || !indptr || !indices || !data || !nnz || !n_ecs || !n_loci || !n_haps || n_haps > 31 || !total)
         return fail(nullptr, ECB_ERR_ARG, "bad argument");
     if (total >= (1ull << 32)) return fail(nullptr, ECB_ERR_LIMIT, "more than 2^32-1 row indices");
-    if (const int rc = use_device(device)) return rc;
+    Call c(device, ""); if (c.rc) return c.rc;
     DevBuf<> cp, ci, ip, ix, da;
     const u64 nc = (u64)n_haps * (n_loci + 1), rowb = ((u64)n_ecs + 1) * 4;
-    if (const char* why = stage_in({{&cp, csc_indptr, nc * 4}, {&ci, csc_indices, total * 4}, {&ip, nullptr, rowb}, {&ix, nullptr, total * 4},
-                                    {&da, nullptr, total * 4}}))
-        return fail(nullptr, ECB_ERR_HIP, "%s", why);
-    const int rc = ecb_hapcsc_to_csr_device(device, n_ecs, n_loci, n_haps, cp.p, ci.p, total, ip.p, ix.p, da.p, nnz);
+    int rc = stage_in(c, {{&cp, csc_indptr, nc * 4}, {&ci, csc_indices, total * 4}, {&ip, nullptr, rowb}, {&ix, nullptr, total * 4}, {&da, nullptr, total * 4}});
+    if (rc == ECB_OK) rc = ecb_hapcsc_to_csr_device(device, n_ecs, n_loci, n_haps, cp.p, ci.p, total, ip.p, ix.p, da.p, nnz);
     if (rc != ECB_OK) return rc;
-    if (!stage_out({{indptr, &ip, rowb}, {indices, &ix, *nnz * 4}, {data, &da, *nnz * 4}})) return fail(nullptr, ECB_ERR_HIP, "copy from the device");
-    return ECB_OK;
+    return stage_out(c, {{indptr, &ip, rowb}, {indices, &ix, *nnz * 4}, {data, &da, *nnz * 4}});
 }
 
 // ---- apply-genotypes: the haplotype bitmasks of a CSR A ANDed with a per-locus mask, what becomes zero dropped -----------------------------
@@ -4530,6 +4564,12 @@ __global__ __launch_bounds__(TPB) void k_gm_scatter(const int* indptr, u32 n_ecs
         out_data[x[j]] = (int)(d[j] & mask[c[j]]);
     }
 }
+const ErrBit GM_ERRS[] = {
+    {GM_ERR_PTR, ECB_ERR_CONTRACT, "malformed CSR: row pointers do not start at 0, go backwards or do not end at nnz"},
+    {GM_ERR_LOCUS, ECB_ERR_CONTRACT, "malformed CSR: a locus at or beyond n_loci"},
+    {GM_ERR_BITS, ECB_ERR_CONTRACT, "malformed CSR: a haplotype bit at or beyond n_haplotypes"},
+    {GM_ERR_MASK, ECB_ERR_CONTRACT, "a locus mask has a bit at or beyond n_haplotypes"},
+};
 bool gm_overlap(const void* a, u64 na, const void* b, u64 nb) {
     const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
     return na && nb && x < y + nb && y < x + na;
@@ -4550,30 +4590,24 @@ extern "C" int ecb_apply_mask_device(int device, uint32_t n_ecs, uint32_t n_loci
             return fail(nullptr, ECB_ERR_ARG, "an output overlaps an input");
     if (gm_overlap(d_out_indptr, rowb, d_out_indices, nzb) || gm_overlap(d_out_indptr, rowb, d_out_data, nzb) || gm_overlap(d_out_indices, nzb, d_out_data, nzb))
         return fail(nullptr, ECB_ERR_ARG, "the outputs overlap");
-    if (const int rc = use_device(device)) return rc;
-    hipStream_t st = nullptr;
-    std::lock_guard<std::mutex> guard(g_cv_lock);
+    Call c(device, "apply-mask: "); if (c.rc) return c.rc;
+    hipStream_t st = c.st;
     const u64 n_words = GM_SHARD_WORDS * (1 + GM_SHARDS);
-    u64* words = cv_get<u64>(device, CV_WORDS, n_words);
-    u32 *keep = cv_get<u32>(device, CV_X0, nnz), *excl = cv_get<u32>(device, CV_X1, nnz + 1), *sums = cv_get<u32>(device, CV_SUMS2, scan_words(nnz));
-    if (!words || !keep || !excl || !sums) return fail(nullptr, ECB_ERR_HIP, "out of device memory");
-    if (hipMemsetAsync(words, 0, n_words * 8, st) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "memset");
+    u64* words = c.get<u64>(CV_WORDS, n_words);
+    u32 *keep = c.get<u32>(CV_X0, nnz), *excl = c.get<u32>(CV_X1, nnz + 1), *sums = c.get<u32>(CV_SUMS2, scan_words(nnz));
+    if (const int rc = c.missing()) return rc;
+    CALLCHK(c, hipMemsetAsync(words, 0, n_words * 8, st));
     const u64 threads = std::max<u64>(std::max<u64>((u64)n_ecs + 1, n_loci), (nnz + GM_ITEMS - 1) / GM_ITEMS);
     const int* ip = (const int*)d_indptr; const int* ix = (const int*)d_indices; const int* da = (const int*)d_data; const u32* mk = (const u32*)d_mask;
     k_gm_check<<<nblk(threads, TPB), TPB, 0, st>>>(ip, n_ecs, ix, da, nnz, mk, n_loci, n_haps, keep, words);
-    if (hipGetLastError() != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "apply-mask: check launch");
-    if (scan_launch(st, keep, nnz, excl, sums, words + 3, 1, excl + nnz) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "apply-mask: scan launch");
+    CALLCHK(c, hipGetLastError());
+    CALLCHK(c, scan_launch(st, keep, nnz, excl, sums, words + 3, 1, excl + nnz));
     k_gm_scatter<<<nblk(threads, TPB), TPB, 0, st>>>(ip, n_ecs, ix, da, nnz, mk, n_loci, excl, (int*)d_out_indptr, (int*)d_out_indices, (int*)d_out_data);
-    if (hipGetLastError() != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "apply-mask: scatter launch");
+    CALLCHK(c, hipGetLastError());
     std::vector<u64> back(n_words);
-    if (hipMemcpy(back.data(), words, n_words * 8, hipMemcpyDeviceToHost) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "apply-mask: %s", hipGetErrorString(hipGetLastError()));
-    const u32 err = (u32)back[0];
+    if (const int rc = c.read_back(back.data(), words, n_words, GM_ERRS)) return rc;
     u64 balance = 0;
     for (u32 k = 1; k <= GM_SHARDS; ++k) balance += back[GM_SHARD_WORDS * k];
-    if (err & GM_ERR_PTR) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSR: row pointers do not start at 0, go backwards or do not end at nnz");
-    if (err & GM_ERR_LOCUS) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSR: a locus at or beyond n_loci");
-    if (err & GM_ERR_BITS) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSR: a haplotype bit at or beyond n_haplotypes");
-    if (err & GM_ERR_MASK) return fail(nullptr, ECB_ERR_CONTRACT, "a locus mask has a bit at or beyond n_haplotypes");
     if (balance != 0) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSR: columns not strictly ascending within a row (unsorted or duplicate)");
     *kept = back[3];
     return ECB_OK;
@@ -4584,17 +4618,14 @@ extern "C" int ecb_apply_mask(int device, uint32_t n_ecs, uint32_t n_loci, uint3
     if (!indptr || !mask || !out_indptr || !kept || !n_loci || !n_haps || n_haps > 31) return fail(nullptr, ECB_ERR_ARG, "bad argument");
     if (nnz && (!indices || !data || !out_indices || !out_data)) return fail(nullptr, ECB_ERR_ARG, "bad argument");
     if (nnz >= (1ull << 31) || n_ecs >= (1u << 31) - 1u) return fail(nullptr, ECB_ERR_LIMIT, "the CSR exceeds the .bin format's int32 limits");
-    if (const int rc = use_device(device)) return rc;
+    Call c(device, "apply-mask: "); if (c.rc) return c.rc;
     const u64 rowb = ((u64)n_ecs + 1) * 4, nzb = nnz * 4;
     DevBuf<> ip, ix, da, mk, oip, oix, oda;
-    if (const char* why = stage_in({{&ip, indptr, rowb}, {&ix, indices, nzb}, {&da, data, nzb}, {&mk, mask, (u64)n_loci * 4}, {&oip, nullptr, rowb},
-                                    {&oix, nullptr, nzb}, {&oda, nullptr, nzb}}))
-        return fail(nullptr, ECB_ERR_HIP, "%s", why);
-    const int rc = ecb_apply_mask_device(device, n_ecs, n_loci, n_haps, nnz, ip.p, ix.p, da.p, mk.p, oip.p, oix.p, oda.p, kept);
+    int rc = stage_in(c, {{&ip, indptr, rowb}, {&ix, indices, nzb}, {&da, data, nzb}, {&mk, mask, (u64)n_loci * 4}, {&oip, nullptr, rowb},
+                          {&oix, nullptr, nzb}, {&oda, nullptr, nzb}});
+    if (rc == ECB_OK) rc = ecb_apply_mask_device(device, n_ecs, n_loci, n_haps, nnz, ip.p, ix.p, da.p, mk.p, oip.p, oix.p, oda.p, kept);
     if (rc != ECB_OK) return rc;
-    if (!stage_out({{out_indptr, &oip, rowb}, {out_indices, &oix, *kept * 4}, {out_data, &oda, *kept * 4}}))
-        return fail(nullptr, ECB_ERR_HIP, "copy from the device");
-    return ECB_OK;
+    return stage_out(c, {{out_indptr, &oip, rowb}, {out_indices, &oix, *kept * 4}, {out_data, &oda, *kept * 4}});
 }
 
 // ---- ecmerge: several .bin files' A and N combined into one (ecb_combine / ecb_combine_device) ---------------------------------------------
@@ -4849,8 +4880,20 @@ __global__ void k_cb_nptr(const u64* okey, const u64* n_out, u64 n, u32 n_sample
     const u64 s = blockIdx.x * (u64)blockDim.x + threadIdx.x;
     if (s <= n_samples) indptr[s] = (int)lower_bound_u64(okey, min(*n_out, n), s << 32);
 }
-struct StreamGuard { hipStream_t s = nullptr; ~StreamGuard() { if (s) { hipStreamSynchronize(s); hipStreamDestroy(s); } } };
-struct CbHandle { ecb_handle* h = nullptr; ~CbHandle() { if (h) ecb_destroy(h); } };
+const ErrBit CB_ERRS[] = {
+    {CB_ERR_PTR, ECB_ERR_CONTRACT, "malformed CSR A: row pointers do not start at 0, go backwards or do not end at nnz"},
+    {CB_ERR_NPTR, ECB_ERR_CONTRACT, "malformed CSC N: column pointers do not start at 0, go backwards or do not end at nnz"},
+    {CB_ERR_LOCUS, ECB_ERR_CONTRACT, "malformed CSR A: a column at or beyond the part's n_loci"},
+    {CB_ERR_BITS, ECB_ERR_CONTRACT, "malformed CSR A: a stored 0 or a haplotype bit at or beyond n_haplotypes"},
+    {CB_ERR_MAP, ECB_ERR_CONTRACT, "a target map sends a column at or beyond n_loci"},
+    {CB_ERR_ORDER, ECB_ERR_CONTRACT, "malformed CSR A: columns not strictly ascending within a row (unsorted or duplicate, before or after the target map)"},
+    {CB_ERR_NEC, ECB_ERR_CONTRACT, "malformed CSC N: an EC index at or beyond the part's n_ecs"},
+    {CB_ERR_NCOUNT, ECB_ERR_CONTRACT, "malformed CSC N: a negative count"},
+    {CB_ERR_SMAP, ECB_ERR_CONTRACT, "a sample map sends a sample at or beyond n_samples"},
+    {CB_ERR_SUM, ECB_ERR_LIMIT, "a merged count exceeds int32"},
+    {CB_ERR_LOST, ECB_ERR_HIP, "internal: a row found no EC"},
+};
+struct HandleGuard { std::vector<ecb_handle*> h; ~HandleGuard() { for (ecb_handle* x : h) ecb_destroy(x); } };
 }  // namespace
 
 extern "C" int ecb_combine_device(int device, uint32_t n_parts, const ecb_combine_part* parts, uint32_t n_loci, uint32_t n_haps, uint32_t n_samples,
@@ -4884,75 +4927,53 @@ extern "C" int ecb_combine_device(int device, uint32_t n_parts, const ecb_combin
     bool any_map = false;
     for (u32 p = 0; p < n_parts; ++p) any_map |= hp[p].tmap != nullptr;
     if (any_map && NP >= (1ull << 30)) return fail(nullptr, ECB_ERR_LIMIT, "combine: more than 2^30 non-zeros to re-sort after a target map");
-    if (const int rc = use_device(device)) return rc;
-    StreamGuard sg;
-    if (hipStreamCreate(&sg.s) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "combine: stream");
-    hipStream_t st = sg.s;
-    std::vector<DevBuf<>> S;
-    CbPart* d_parts = fresh<CbPart>(S, n_parts);
-    u64* d_base = fresh<u64>(S, base.size());
+    Call c(device, "combine: ", true); if (c.rc) return c.rc;
+    hipStream_t& st = c.st;                              // (the handle's own stream once there is one: it queues the slot ranks)
+    CbPart* d_parts = c.get<CbPart>(n_parts);
+    u64* d_base = c.get<u64>(base.size());
     const u64 n_words = CB_SHARD_WORDS * (1 + CB_SHARDS);
-    u64* words = fresh<u64>(S, n_words);                    // [0] error bits (u32), then the arena shards
+    u64* words = c.get<u64>(n_words);                    // [0] error bits (u32), then the arena shards
     const u64 NK = std::max(NP, NZ);                     // (the sort buffers serve the pairs of A, then the entries of N)
-    u64 *keys0 = fresh<u64>(S, NK), *keys1 = fresh<u64>(S, NK), *rowhash = fresh<u64>(S, R);
-    u32 *vals0 = fresh<u32>(S, NK), *vals1 = fresh<u32>(S, NK);
-    uint2* pairs = fresh<uint2>(S, NP);
-    Entry* ent = fresh<Entry>(S, R);
-    if (missing(S)) return fail(nullptr, ECB_ERR_HIP, "combine: out of device memory");
+    u64 *keys0 = c.get<u64>(NK), *keys1 = c.get<u64>(NK), *rowhash = c.get<u64>(R);
+    u32 *vals0 = c.get<u32>(NK), *vals1 = c.get<u32>(NK);
+    uint2* pairs = c.get<uint2>(NP);
+    Entry* ent = c.get<Entry>(R);
+    int rc = c.missing(); if (rc != ECB_OK) return rc;
     u32* err = reinterpret_cast<u32*>(words);
     std::vector<u64> back(n_words);
-    hipStream_t cur = st;                                // (the handle's own stream once there is one: it queues the slot ranks)
-    auto check = [&](const char* what) -> int {           // one wait: the error word and the shards
-        if (hipMemcpyAsync(back.data(), words, n_words * 8, hipMemcpyDeviceToHost, cur) != hipSuccess || hipStreamSynchronize(cur) != hipSuccess)
-            return fail(nullptr, ECB_ERR_HIP, "combine: %s: %s", what, hipGetErrorString(hipGetLastError()));
-        const u32 e = (u32)back[0];
-        if (e & CB_ERR_PTR) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSR A: row pointers do not start at 0, go backwards or do not end at nnz");
-        if (e & CB_ERR_NPTR) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSC N: column pointers do not start at 0, go backwards or do not end at nnz");
-        if (e & CB_ERR_LOCUS) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSR A: a column at or beyond the part's n_loci");
-        if (e & CB_ERR_BITS) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSR A: a stored 0 or a haplotype bit at or beyond n_haplotypes");
-        if (e & CB_ERR_MAP) return fail(nullptr, ECB_ERR_CONTRACT, "a target map sends a column at or beyond n_loci");
-        if (e & CB_ERR_ORDER) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSR A: columns not strictly ascending within a row (unsorted or duplicate, before or after the target map)");
-        if (e & CB_ERR_NEC) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSC N: an EC index at or beyond the part's n_ecs");
-        if (e & CB_ERR_NCOUNT) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSC N: a negative count");
-        if (e & CB_ERR_SMAP) return fail(nullptr, ECB_ERR_CONTRACT, "a sample map sends a sample at or beyond n_samples");
-        if (e & CB_ERR_SUM) return fail(nullptr, ECB_ERR_LIMIT, "a merged count exceeds int32");
-        if (e & CB_ERR_LOST) return fail(nullptr, ECB_ERR_HIP, "internal: a row found no EC");
-        return ECB_OK;
-    };
-    if (hipMemcpyAsync(d_parts, hp.data(), n_parts * sizeof(CbPart), hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(d_base, base.data(), base.size() * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemsetAsync(words, 0, n_words * 8, st) != hipSuccess || hipMemsetAsync(rowhash, 0, std::max<u64>(R, 1) * 8, st) != hipSuccess)
-        return fail(nullptr, ECB_ERR_HIP, "combine: copy to the device");
+    auto check = [&] { return c.read_back(back.data(), words, n_words, CB_ERRS); };      // one wait: the error word and the shards
+    CALLCHK(c, hipMemcpyAsync(d_parts, hp.data(), n_parts * sizeof(CbPart), hipMemcpyHostToDevice, st));
+    CALLCHK(c, hipMemcpyAsync(d_base, base.data(), base.size() * 8, hipMemcpyHostToDevice, st));
+    CALLCHK(c, hipMemsetAsync(words, 0, n_words * 8, st));
+    CALLCHK(c, hipMemsetAsync(rowhash, 0, std::max<u64>(R, 1) * 8, st));
     // 1. the pointers; 2. the pairs (their binary searches trust checked pointers)
     const u64 n_ptr = std::max(base[CB_APTR * B + n_parts], base[CB_NPTR * B + n_parts]);
     k_cb_check<<<nblk(n_ptr, TPB), TPB, 0, st>>>(d_parts, n_parts, d_base, err);
-    int rc = check("pointer check");
+    rc = check();
     if (rc != ECB_OK) return rc;
     if (NP) k_cb_pairs<<<nblk(NP, TPB), TPB, 0, st>>>(d_parts, n_parts, d_base, n_loci, n_haps, keys0, vals0, err);
-    rc = check("pair check");
+    rc = check();
     if (rc != ECB_OK) return rc;
     // 3. rows that a target map re-numbered are re-sorted: one radix sort of (row, column) over all pairs (parts without a map are sorted already)
     u64* keys = keys0; u32* vals = vals0;
     if (any_map && NP > 1) {
-        SortScratch sc{fresh<u32>(S, rs_words(NP)), fresh<u32>(S, RS_AUX_WORDS), words + 1};
-        if (missing(S)) return fail(nullptr, ECB_ERR_HIP, "combine: out of device memory");
+        SortScratch sc{c.get<u32>(rs_words(NP)), c.get<u32>(RS_AUX_WORDS), words + 1};
+        if ((rc = c.missing()) != ECB_OK) return rc;
         SortBufs s{{keys0, keys1}, {vals0, vals1}};
-        const hipError_t e = radix_sort_pairs64(st, s, NP, sc, msb_mask((R - 1) << 32 | (n_loci - 1)));
-        if (e != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "combine: radix sort: %s", hipGetErrorString(e));
+        CALLCHK(c, radix_sort_pairs64(st, s, NP, sc, msb_mask((R - 1) << 32 | (n_loci - 1))));
         keys = s.keys(); vals = s.vals();
     }
     // 4. key lists and row hashes; 5. the entries, and the key arena's worst wave
     if (NP) k_cb_hash<<<nblk(NP, TPB), TPB, 0, st>>>(keys, vals, NP, pairs, rowhash, err);
     if (R) k_cb_entries<<<nblk(R, TPB), TPB, 0, st>>>(d_parts, n_parts, d_base, rowhash, ent, words);
-    rc = check("entries");
+    rc = check();
     if (rc != ECB_OK) return rc;
     u64 wmax = 0, wsum = 0;
     for (u32 k = 1; k <= CB_SHARDS; ++k) { wmax = std::max<u64>(wmax, back[CB_SHARD_WORDS * k]); wsum += back[CB_SHARD_WORDS * k + 1]; }
     u64 E = 0, nnz_a = 0, nnz_n = 0;
-    DevBuf<u32> ecr;                                     // EC of every global row
-    if (ecr.alloc(std::max<u64>(R, 1) * 4, 4) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "combine: out of device memory");
-    u32* ec_of_row = ecr;
-    CbHandle hg;
+    u32* ec_of_row = c.get<u32>(R);                      // EC of every global row
+    if ((rc = c.missing()) != ECB_OK) return rc;
+    HandleGuard hg;
     if (R) {
         // 6. one table: room for every row being an EC of its own (half full at most: no growth), and a key arena in which every wave's one
         //    reservation fits one of its 64 regions whatever the others took (arena_alloc: a region that cannot take a reservation is skipped)
@@ -4963,56 +4984,52 @@ extern "C" int ecb_combine_device(int device, uint32_t n_parts, const ecb_combin
         ecb_handle* h = nullptr;
         rc = ecb_create(&cfg, &h);
         if (rc != ECB_OK) return rc;
-        hg.h = h;
-        auto hfail = [&](int code) { return fail(nullptr, code, "combine: %s", h->err.c_str()); };
+        hg.h.push_back(h);
         ecb_add_counters(h, 0, R, R);                     // R "reads", all valid: the ranking's bitmap spans the rows
         rc = ecb_table_merge_device(h, ent, R, pairs, NP);
-        if (rc != ECB_OK) return hfail(rc);
         ecb_sizes sz{};
-        rc = ecb_finalize(h, &sz);
-        if (rc != ECB_OK) return hfail(rc);
+        if (rc == ECB_OK) rc = ecb_finalize(h, &sz);
+        if (rc == ECB_OK) rc = ecb_export_device(h, d_out_indptr_a, d_out_indices_a, d_out_data_a, nullptr, nullptr, nullptr);
+        if (rc == ECB_OK) rc = ensure_slot_ranks(h, sz.n_ecs);
+        if (rc != ECB_OK) return fail(nullptr, rc, "combine: %s", h->err.c_str());
         E = sz.n_ecs; nnz_a = sz.nnz_a;
-        rc = ecb_export_device(h, d_out_indptr_a, d_out_indices_a, d_out_data_a, nullptr, nullptr, nullptr);
-        if (rc != ECB_OK) return hfail(rc);
-        rc = ensure_slot_ranks(h, E);
-        if (rc != ECB_OK) return hfail(rc);
-        cur = h->stream;
+        st = h->stream;
         // 7. every row's EC
-        k_cb_lookup<<<nblk(R, TPB), TPB, 0, cur>>>(ent, R, pairs, h->table, h->cap - 1, h->arena, h->rank_of_slot, ec_of_row, err);
+        k_cb_lookup<<<nblk(R, TPB), TPB, 0, st>>>(ent, R, pairs, h->table, h->cap - 1, h->arena, h->rank_of_slot, ec_of_row, err);
     } else {
-        if (hipMemsetAsync(d_out_indptr_a, 0, 4, st) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "combine: memset");
+        CALLCHK(c, hipMemsetAsync(d_out_indptr_a, 0, 4, st));
     }
     // 8. N: (sample, EC) keys sorted, summed per key, zeros dropped, CSC
     if (NZ) {
-        u32 *flag = fresh<u32>(S, NZ), *pos = fresh<u32>(S, NZ + 1), *keep = fresh<u32>(S, NZ), *opos = fresh<u32>(S, NZ + 1);
-        u32 *sums1 = fresh<u32>(S, scan_words(NZ)), *sums2 = fresh<u32>(S, scan_words(NZ));
-        u64 *rsum = fresh<u64>(S, NZ), *rkey = fresh<u64>(S, NZ), *okey = fresh<u64>(S, NZ), *tot = fresh<u64>(S, 2);
-        SortScratch sc{fresh<u32>(S, rs_words(NZ)), fresh<u32>(S, RS_AUX_WORDS), words + 1};
-        if (missing(S)) return fail(nullptr, ECB_ERR_HIP, "combine: out of device memory");
-        k_cb_ntrip<<<nblk(NZ, TPB), TPB, 0, cur>>>(d_parts, n_parts, d_base, n_samples, ec_of_row, keys0, vals0, err);
-        rc = check("N check");
+        u32 *flag = c.get<u32>(NZ), *pos = c.get<u32>(NZ + 1), *keep = c.get<u32>(NZ), *opos = c.get<u32>(NZ + 1);
+        u32 *sums1 = c.get<u32>(scan_words(NZ)), *sums2 = c.get<u32>(scan_words(NZ));
+        u64 *rsum = c.get<u64>(NZ), *rkey = c.get<u64>(NZ), *okey = c.get<u64>(NZ), *tot = c.get<u64>(2);
+        SortScratch sc{c.get<u32>(rs_words(NZ)), c.get<u32>(RS_AUX_WORDS), words + 1};
+        if ((rc = c.missing()) != ECB_OK) return rc;
+        k_cb_ntrip<<<nblk(NZ, TPB), TPB, 0, st>>>(d_parts, n_parts, d_base, n_samples, ec_of_row, keys0, vals0, err);
+        rc = check();
         if (rc != ECB_OK) return rc;
         SortBufs s{{keys0, keys1}, {vals0, vals1}};
-        hipError_t e = radix_sort_pairs64(cur, s, NZ, sc, msb_mask(((u64)n_samples - 1) << 32 | (E ? E - 1 : 0)));
-        if (e != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "combine: radix sort: %s", hipGetErrorString(e));
+        CALLCHK(c, radix_sort_pairs64(st, s, NZ, sc, msb_mask(((u64)n_samples - 1) << 32 | (E ? E - 1 : 0))));
         const u64* sk = s.keys(); const u32* sv = s.vals();
-        if (hipMemsetAsync(rsum, 0, NZ * 8, cur) != hipSuccess || hipMemsetAsync(tot, 0, 16, cur) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "combine: memset");
-        k_run_heads<<<nblk(NZ, TPB), TPB, 0, cur>>>(sk, NZ, flag);
-        if (scan_launch(cur, flag, NZ, pos, sums1, tot) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "combine: scan");
-        k_cb_nsum<<<nblk(NZ, TPB), TPB, 0, cur>>>(sk, sv, flag, pos, NZ, rsum, rkey);
-        k_cb_nkeep<<<nblk(NZ, TPB), TPB, 0, cur>>>(rsum, tot, NZ, keep, err);
-        if (scan_launch(cur, keep, NZ, opos, sums2, tot + 1) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "combine: scan");
-        k_cb_nemit<<<nblk(NZ, TPB), TPB, 0, cur>>>(rsum, rkey, keep, opos, tot, NZ, (int*)d_out_indices_n, (int*)d_out_data_n, okey);
-        k_cb_nptr<<<nblk((u64)n_samples + 1, TPB), TPB, 0, cur>>>(okey, tot + 1, NZ, n_samples, (int*)d_out_indptr_n);
+        CALLCHK(c, hipMemsetAsync(rsum, 0, NZ * 8, st));
+        CALLCHK(c, hipMemsetAsync(tot, 0, 16, st));
+        k_run_heads<<<nblk(NZ, TPB), TPB, 0, st>>>(sk, NZ, flag);
+        CALLCHK(c, scan_launch(st, flag, NZ, pos, sums1, tot));
+        k_cb_nsum<<<nblk(NZ, TPB), TPB, 0, st>>>(sk, sv, flag, pos, NZ, rsum, rkey);
+        k_cb_nkeep<<<nblk(NZ, TPB), TPB, 0, st>>>(rsum, tot, NZ, keep, err);
+        CALLCHK(c, scan_launch(st, keep, NZ, opos, sums2, tot + 1));
+        k_cb_nemit<<<nblk(NZ, TPB), TPB, 0, st>>>(rsum, rkey, keep, opos, tot, NZ, (int*)d_out_indices_n, (int*)d_out_data_n, okey);
+        k_cb_nptr<<<nblk((u64)n_samples + 1, TPB), TPB, 0, st>>>(okey, tot + 1, NZ, n_samples, (int*)d_out_indptr_n);
         u64 t2[2] = {0, 0};
-        if ((e = hipMemcpyAsync(t2, tot, 16, hipMemcpyDeviceToHost, cur)) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "combine: copy: %s", hipGetErrorString(e));
-        rc = check("N");
+        CALLCHK(c, hipMemcpyAsync(t2, tot, 16, hipMemcpyDeviceToHost, st));
+        rc = check();
         if (rc != ECB_OK) return rc;
         if (t2[1] > NZ) return fail(nullptr, ECB_ERR_HIP, "internal: %llu N entries from %llu", (unsigned long long)t2[1], (unsigned long long)NZ);
         nnz_n = t2[1];
     } else {
-        if (hipMemsetAsync(d_out_indptr_n, 0, ((u64)n_samples + 1) * 4, cur) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "combine: memset");
-        rc = check("lookup");
+        CALLCHK(c, hipMemsetAsync(d_out_indptr_n, 0, ((u64)n_samples + 1) * 4, st));
+        rc = check();
         if (rc != ECB_OK) return rc;
     }
     out_sizes[0] = E; out_sizes[1] = nnz_a; out_sizes[2] = nnz_n;
@@ -5023,7 +5040,7 @@ extern "C" int ecb_combine(int device, uint32_t n_parts, const ecb_combine_part*
                            int32_t* out_indptr_a, int32_t* out_indices_a, int32_t* out_data_a, int32_t* out_indptr_n, int32_t* out_indices_n,
                            int32_t* out_data_n, uint64_t* out_sizes) {
     if (!parts || !n_parts || !out_sizes || !out_indptr_a || !out_indptr_n) return fail(nullptr, ECB_ERR_ARG, "combine: bad argument");
-    if (const int rc = use_device(device)) return rc;
+    Call c(device, "combine: "); if (c.rc) return c.rc;
     std::vector<ecb_combine_part> dp(parts, parts + n_parts);
     std::vector<DevBuf<>> bufs((u64)n_parts * 8);
     std::vector<StageIn> in;
@@ -5041,20 +5058,17 @@ extern "C" int ecb_combine(int device, uint32_t n_parts, const ecb_combine_part*
             if (src[k]) { in.push_back({&bufs[(u64)p * 8 + k], src[k], len[k]}); at.push_back(dst[k]); }
         R += c.n_ecs; NP += c.nnz_a; NZ += c.nnz_n;
     }
-    if (stage_in(in)) return fail(nullptr, ECB_ERR_HIP, "combine: copy to the device");
+    int rc = stage_in(c, in); if (rc != ECB_OK) return rc;
     for (size_t i = 0; i < in.size(); ++i) *at[i] = in[i].d->p;
     DevBuf<> oia, oxa, oda, oin, oxn, odn;
     const u64 nptr = ((u64)n_samples + 1) * 4;
-    if (stage_in({{&oia, nullptr, (R + 1) * 4}, {&oxa, nullptr, NP * 4}, {&oda, nullptr, NP * 4}, {&oin, nullptr, nptr}, {&oxn, nullptr, NZ * 4},
-                  {&odn, nullptr, NZ * 4}}))
-        return fail(nullptr, ECB_ERR_HIP, "combine: out of device memory");
-    const int rc = ecb_combine_device(device, n_parts, dp.data(), n_loci, n_haps, n_samples, oia.p, oxa.p, oda.p, oin.p, oxn.p, odn.p, out_sizes);
+    rc = stage_in(c, {{&oia, nullptr, (R + 1) * 4}, {&oxa, nullptr, NP * 4}, {&oda, nullptr, NP * 4}, {&oin, nullptr, nptr}, {&oxn, nullptr, NZ * 4},
+                      {&odn, nullptr, NZ * 4}});
+    if (rc == ECB_OK) rc = ecb_combine_device(device, n_parts, dp.data(), n_loci, n_haps, n_samples, oia.p, oxa.p, oda.p, oin.p, oxn.p, odn.p, out_sizes);
     if (rc != ECB_OK) return rc;
     const u64 E = out_sizes[0], nnz_a = out_sizes[1], nnz_n = out_sizes[2];
-    if (!stage_out({{out_indptr_a, &oia, (E + 1) * 4}, {out_indptr_n, &oin, nptr}, {out_indices_a, &oxa, nnz_a * 4}, {out_data_a, &oda, nnz_a * 4},
-                    {out_indices_n, &oxn, nnz_n * 4}, {out_data_n, &odn, nnz_n * 4}}))
-        return fail(nullptr, ECB_ERR_HIP, "combine: copy from the device");
-    return ECB_OK;
+    return stage_out(c, {{out_indptr_a, &oia, (E + 1) * 4}, {out_indptr_n, &oin, nptr}, {out_indices_a, &oxa, nnz_a * 4}, {out_data_a, &oda, nnz_a * 4},
+                         {out_indices_n, &oxn, nnz_n * 4}, {out_data_n, &odn, nnz_n * 4}});
 }
 
 // ---- salmon2ec: CSR A and N of a salmon eq_classes.txt EC section (ecb_salmon_ecs / ecb_salmon_ecs_device) ------------------------------
@@ -5277,73 +5291,63 @@ extern "C" int ecb_salmon_ecs_device(int device, const void* d_text, uint64_t n_
         return fail(nullptr, ECB_ERR_ARG, "salmon: bad argument");
     if (n_loci >= MAX_LOCI) return fail(nullptr, ECB_ERR_ARG, "salmon: n_loci out of range (1 .. 2^26-3)");
     if (n_ecs >= (1u << 31) - 1u || n_targets >= (1u << 31)) return fail(nullptr, ECB_ERR_LIMIT, "salmon: E or T beyond int32");
-    if (const int rc = use_device(device)) return rc;
+    Call c(device, "salmon: ", true); if (c.rc) return c.rc;
     auto refuse = [](u64 e) { const u32 r = (u32)(e & 255u); return fail(nullptr, ECB_ERR_CONTRACT, "EC line %llu: %s (reason %u)", (unsigned long long)(e >> 8), sl_reason(r), r); };
-    StreamGuard sg;
-    if (hipStreamCreate(&sg.s) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "salmon: stream");
-    hipStream_t st = sg.s;
+    hipStream_t st = c.st;
     const u8* text = (const u8*)d_text;
     const u32 *tcol = (const u32*)d_target_col, *thap = (const u32*)d_target_hap;
     const u64 L = n_bytes, nb = std::max<u64>(1, (L + SL_TILE - 1) / SL_TILE);
     if (nb >= (1ull << 31)) return fail(nullptr, ECB_ERR_LIMIT, "salmon: text too long");
-    std::vector<DevBuf<>> S;
-    u32 *blk_nl = fresh<u32>(S, nb), *blk_fs = fresh<u32>(S, nb), *nl_ex = fresh<u32>(S, nb), *fs_ex = fresh<u32>(S, nb);
-    u32 *sc1 = fresh<u32>(S, scan_words(nb)), *sc2 = fresh<u32>(S, scan_words(nb));
-    u64* words = fresh<u64>(S, 8);                        // [0] lowest (line << 8 | reason), [1] [2] line ends, field starts, [3] bad target map, [4] [5] scan totals
-    if (missing(S)) return fail(nullptr, ECB_ERR_HIP, "salmon: out of device memory");
+    u32 *blk_nl = c.get<u32>(nb), *blk_fs = c.get<u32>(nb), *nl_ex = c.get<u32>(nb), *fs_ex = c.get<u32>(nb);
+    u32 *sc1 = c.get<u32>(scan_words(nb)), *sc2 = c.get<u32>(scan_words(nb));
+    u64* words = c.get<u64>(8);                        // [0] lowest (line << 8 | reason), [1] [2] line ends, field starts, [3] bad target map, [4] [5] scan totals
+    int rc = c.missing(); if (rc != ECB_OK) return rc;
     u64* err = words;
     u32* bad = reinterpret_cast<u32*>(words + 3);
     u64 back[8] = {0};
     u8 last = 10;
-    auto sync = [&](const char* what) -> int {
-        if (hipMemcpyAsync(back, words, 64, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-            return fail(nullptr, ECB_ERR_HIP, "salmon: %s: %s", what, hipGetErrorString(hipGetLastError()));
-        return ECB_OK;
-    };
-    if (hipMemsetAsync(words, 0, 64, st) != hipSuccess || hipMemsetAsync(err, 0xFF, 8, st) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "salmon: memset");
+    CALLCHK(c, hipMemsetAsync(words, 0, 64, st));
+    CALLCHK(c, hipMemsetAsync(err, 0xFF, 8, st));
     // 1. the target map; line ends and field starts per tile, placed
     if (n_targets) k_sl_targets<<<nblk(n_targets, TPB), TPB, 0, st>>>(tcol, thap, n_targets, n_loci, n_haps, bad);
     if (L) {
         k_sl_count<<<(unsigned)nb, TPB, 0, st>>>(text, L, blk_nl, blk_fs);
-        if (scan_launch(st, blk_nl, nb, nl_ex, sc1, words + 1) != hipSuccess || scan_launch(st, blk_fs, nb, fs_ex, sc2, words + 2) != hipSuccess)
-            return fail(nullptr, ECB_ERR_HIP, "salmon: scan");
-        if (hipMemcpyAsync(&last, text + L - 1, 1, hipMemcpyDeviceToHost, st) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "salmon: copy");
+        CALLCHK(c, scan_launch(st, blk_nl, nb, nl_ex, sc1, words + 1));
+        CALLCHK(c, scan_launch(st, blk_fs, nb, fs_ex, sc2, words + 2));
+        CALLCHK(c, hipMemcpyAsync(&last, text + L - 1, 1, hipMemcpyDeviceToHost, st));
     }
-    int rc = sync("count");
-    if (rc != ECB_OK) return rc;
+    if ((rc = c.read_back(back, words, 8)) != ECB_OK) return rc;
     if (back[3]) return fail(nullptr, ECB_ERR_CONTRACT, "salmon: the target map has a column at or beyond n_loci or a haplotype at or beyond n_haps");
     const u64 n_lines = back[1] + (L && last != 10), NF = back[2];
     if (NF >= (1ull << 30) || n_lines >= (1ull << 31) - 1) return fail(nullptr, ECB_ERR_LIMIT, "salmon: %llu fields in %llu lines: beyond the limits (2^30, 2^31-1)",
                                                                        (unsigned long long)NF, (unsigned long long)n_lines);
     const u64 count_err = n_lines != n_ecs ? (std::min<u64>(n_lines, n_ecs) << 8 | SL_R_COUNT) : SL_NO_ERR;
     // 2. bytes checked, fields parsed; 3. fields classified, targets to keys (dense slots)
-    u32 *fval = fresh<u32>(S, NF), *fline = fresh<u32>(S, NF), *fend = fresh<u32>(S, n_lines), *cnt = fresh<u32>(S, n_lines);
-    u64 *keys0 = fresh<u64>(S, NF), *keys1 = fresh<u64>(S, NF);
-    u32 *vals0 = fresh<u32>(S, NF), *vals1 = fresh<u32>(S, NF), *flag = fresh<u32>(S, NF), *pos = fresh<u32>(S, NF + 1), *sc3 = fresh<u32>(S, scan_words(NF));
-    SortScratch ss{fresh<u32>(S, rs_words(NF)), fresh<u32>(S, RS_AUX_WORDS), words + 6};
-    if (missing(S)) return fail(nullptr, ECB_ERR_HIP, "salmon: out of device memory");
+    u32 *fval = c.get<u32>(NF), *fline = c.get<u32>(NF), *fend = c.get<u32>(n_lines), *cnt = c.get<u32>(n_lines);
+    u64 *keys0 = c.get<u64>(NF), *keys1 = c.get<u64>(NF);
+    u32 *vals0 = c.get<u32>(NF), *vals1 = c.get<u32>(NF), *flag = c.get<u32>(NF), *pos = c.get<u32>(NF + 1), *sc3 = c.get<u32>(scan_words(NF));
+    SortScratch ss{c.get<u32>(rs_words(NF)), c.get<u32>(RS_AUX_WORDS), words + 6};
+    if ((rc = c.missing()) != ECB_OK) return rc;
     if (L) k_sl_place<<<(unsigned)nb, TPB, 0, st>>>(text, L, nl_ex, fs_ex, (u32)NF, fval, fline, fend, err);
     const u64 NP = NF >= 2 * n_lines ? NF - 2 * n_lines : 0;
     if (NF) k_sl_fields<<<nblk(NF, TPB), TPB, 0, st>>>(fval, fline, fend, (u32)NF, n_targets, tcol, thap, true, NP, keys0, vals0, cnt, err);
-    if ((rc = sync("parse")) != ECB_OK) return rc;
+    if ((rc = c.read_back(back, words, 8)) != ECB_OK) return rc;
     SortBufs s{{keys0, keys1}, {vals0, vals1}};
     if (back[0] != SL_NO_ERR) {
         // a malformed line: every field in a slot of its own, sorted on all bits, so that repeats in the lines before it are found too
         k_sl_fields<<<nblk(NF, TPB), TPB, 0, st>>>(fval, fline, fend, (u32)NF, n_targets, tcol, thap, false, NF, keys0, vals0, cnt, err);
-        const hipError_t e = radix_sort_pairs64(st, s, NF, ss);
-        if (e != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "salmon: radix sort: %s", hipGetErrorString(e));
+        CALLCHK(c, radix_sort_pairs64(st, s, NF, ss));
         k_sl_heads<<<nblk(NF, TPB), TPB, 0, st>>>(s.keys(), NF, flag, err);
-        if ((rc = sync("repeats")) != ECB_OK) return rc;
+        if ((rc = c.read_back(back, words, 8)) != ECB_OK) return rc;
         return refuse(std::min(back[0], count_err));
     }
     // 4. sort within rows (the row and column bits only); runs, repeats refused
     const u64 mask = msb_mask(n_lines ? n_lines - 1 : 0) << 32 | msb_mask((u64)(n_loci - 1) << 5 | 31u);
-    const hipError_t e = radix_sort_pairs64(st, s, NP, ss, mask);
-    if (e != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "salmon: radix sort: %s", hipGetErrorString(e));
+    CALLCHK(c, radix_sort_pairs64(st, s, NP, ss, mask));
     const u64* keys = s.keys(); const u32* vals = s.vals();
     if (NP) k_sl_heads<<<nblk(NP, TPB), TPB, 0, st>>>(keys, NP, flag, err);
-    if (scan_launch(st, flag, NP, pos, sc3, words + 4, 1, pos + NP) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "salmon: scan");
-    if ((rc = sync("runs")) != ECB_OK) return rc;
+    CALLCHK(c, scan_launch(st, flag, NP, pos, sc3, words + 4, 1, pos + NP));
+    if ((rc = c.read_back(back, words, 8)) != ECB_OK) return rc;
     if (std::min(back[0], count_err) != SL_NO_ERR) return refuse(std::min(back[0], count_err));
     const u64 nnz = NP ? back[4] : 0;
     if (nnz > capacity) return fail(nullptr, ECB_ERR_LIMIT, "salmon: %llu non-zeros, room for %llu", (unsigned long long)nnz, (unsigned long long)capacity);
@@ -5353,10 +5357,10 @@ extern "C" int ecb_salmon_ecs_device(int device, const void* d_text, uint64_t n_
     k_sl_rowptr<<<nblk((u64)n_ecs + 1, TPB), TPB, 0, st>>>(keys, NP, pos, n_ecs, (int*)d_out_indptr);
     if (n_ecs) {
         k_sl_nkeep<<<nblk(n_ecs, TPB), TPB, 0, st>>>(cnt, n_ecs, flag);
-        if (scan_launch(st, flag, n_ecs, pos, sc3, words + 5) != hipSuccess) return fail(nullptr, ECB_ERR_HIP, "salmon: scan");
+        CALLCHK(c, scan_launch(st, flag, n_ecs, pos, sc3, words + 5));
         k_sl_nemit<<<nblk(n_ecs, TPB), TPB, 0, st>>>(cnt, flag, pos, n_ecs, (int*)d_out_n_indices, (int*)d_out_n_data);
     }
-    if ((rc = sync("emit")) != ECB_OK) return rc;
+    if ((rc = c.read_back(back, words, 8)) != ECB_OK) return rc;
     out_sizes[0] = nnz;
     out_sizes[1] = n_ecs ? back[5] : 0;
     return ECB_OK;
@@ -5369,18 +5373,15 @@ extern "C" int ecb_salmon_ecs(int device, const char* text, uint64_t n_bytes, ui
         (n_ecs && (!out_n_indices || !out_n_data)))
         return fail(nullptr, ECB_ERR_ARG, "salmon: bad argument");
     if (n_ecs >= (1u << 31) - 1u || capacity >= (1ull << 31)) return fail(nullptr, ECB_ERR_LIMIT, "salmon: E or the capacity beyond int32");
-    if (const int rc = use_device(device)) return rc;
+    Call c(device, "salmon: "); if (c.rc) return c.rc;
     DevBuf<> dt, dc, dh, oip, oix, oda, onx, ond;
     const u64 rowb = ((u64)n_ecs + 1) * 4;
-    if (const char* why = stage_in({{&dt, text, n_bytes}, {&dc, target_col, (u64)n_targets * 4}, {&dh, target_hap, (u64)n_targets * 4}, {&oip, nullptr, rowb},
-                                    {&oix, nullptr, capacity * 4}, {&oda, nullptr, capacity * 4}, {&onx, nullptr, (u64)n_ecs * 4}, {&ond, nullptr, (u64)n_ecs * 4}}))
-        return fail(nullptr, ECB_ERR_HIP, "salmon: %s", why);
-    const int rc = ecb_salmon_ecs_device(device, dt.p, n_bytes, n_ecs, n_targets, dc.p, dh.p, n_loci, n_haps, capacity, oip.p, oix.p, oda.p, onx.p, ond.p, out_sizes);
+    int rc = stage_in(c, {{&dt, text, n_bytes}, {&dc, target_col, (u64)n_targets * 4}, {&dh, target_hap, (u64)n_targets * 4}, {&oip, nullptr, rowb},
+                          {&oix, nullptr, capacity * 4}, {&oda, nullptr, capacity * 4}, {&onx, nullptr, (u64)n_ecs * 4}, {&ond, nullptr, (u64)n_ecs * 4}});
+    if (rc == ECB_OK) rc = ecb_salmon_ecs_device(device, dt.p, n_bytes, n_ecs, n_targets, dc.p, dh.p, n_loci, n_haps, capacity, oip.p, oix.p, oda.p, onx.p, ond.p, out_sizes);
     if (rc != ECB_OK) return rc;
-    if (!stage_out({{out_indptr, &oip, rowb}, {out_indices, &oix, out_sizes[0] * 4}, {out_data, &oda, out_sizes[0] * 4}, {out_n_indices, &onx, out_sizes[1] * 4},
-                    {out_n_data, &ond, out_sizes[1] * 4}}))
-        return fail(nullptr, ECB_ERR_HIP, "salmon: copy from the device");
-    return ECB_OK;
+    return stage_out(c, {{out_indptr, &oip, rowb}, {out_indices, &oix, out_sizes[0] * 4}, {out_data, &oda, out_sizes[0] * 4}, {out_n_indices, &onx, out_sizes[1] * 4},
+                         {out_n_data, &ond, out_sizes[1] * 4}});
 }
 
 // ---- ecb_merge: the multi-GPU merge for ONE process that drives several GPUs ----------------------------------------------
@@ -5391,9 +5392,14 @@ extern "C" int ecb_salmon_ecs(int device, const char* text, uint64_t n_bytes, ui
 // (bam_utils.py:646-724: contiguous chunks per worker, the workers' dicts merged in order.)  Everything is built from the entry points above;
 // the devices work one after the other here -- a host that wants them side by side runs one thread or one process per GPU over the same calls.
 namespace {
-// max(bytes, 16) bytes on device `device` (left current); true when that fails
-bool take(DevBuf<>& b, int device, u64 bytes) { return hipSetDevice(device) != hipSuccess || b.alloc(bytes, 16) != hipSuccess; }
-struct HandleGuard { std::vector<ecb_handle*> h; ~HandleGuard() { for (ecb_handle* x : h) ecb_destroy(x); } };
+#define MERGECHK(call) HIPCHK_AS(root, "ecb_merge: ", call)
+// max(bytes, 16) bytes on device `device` (left current)
+int take(ecb_handle* root, DevBuf<>& b, int device, u64 bytes) { MERGECHK(hipSetDevice(device)); MERGECHK(b.alloc(bytes, 16)); return ECB_OK; }
+// one key range's finished result: row pointers, columns, masks, counts and first reads, each in a buffer of its own
+struct Piece {
+    DevBuf<> buf[5]; u64 n_ecs = 0, nnz = 0;
+    u64 bytes(int k) const { return k == 0 ? (n_ecs + 1) * 4 : (k <= 2 ? nnz : n_ecs) * 4; }
+};
 }  // namespace
 
 extern "C" int ecb_merge(ecb_handle* const* shards, uint32_t n, ecb_handle* root, ecb_sizes* out) {
@@ -5410,17 +5416,14 @@ extern "C" int ecb_merge(ecb_handle* const* shards, uint32_t n, ecb_handle* root
     std::vector<DevBuf<>> ent(n), prs(n);
     std::vector<std::vector<uint64_t>> eoff(n, std::vector<uint64_t>(n + 1, 0)), poff(n, std::vector<uint64_t>(n + 1, 0));
     for (u32 r = 0; r < n; ++r) {
-        uint64_t a = 0, b = 0, c = 0;
+        uint64_t a = 0, b = 0, c = 0, ca = 0, cv = 0, cr = 0;
         int rc = ecb_table_sizes(shards[r], &a, &b, &c);
+        if (rc == ECB_OK) rc = ecb_counters(shards[r], &ca, &cv, &cr);
         if (rc != ECB_OK) return fail(root, rc, "ecb_merge: shard %u: %s", r, ecb_last_error(shards[r]));
-        ne[r] = a; np[r] = b; nr[r] = c;
-        uint64_t ca = 0, cv = 0, cr = 0;
-        rc = ecb_counters(shards[r], &ca, &cv, &cr);
-        if (rc != ECB_OK) return fail(root, rc, "ecb_merge: shard %u: %s", r, ecb_last_error(shards[r]));
-        all[r] = ca; valid[r] = cv;
+        ne[r] = a; np[r] = b; nr[r] = c; all[r] = ca; valid[r] = cv;
         base[r + 1] = base[r] + nr[r];
-        if (take(ent[r], shards[r]->device, std::max<u64>(ne[r], 1) * sizeof(Entry)) || take(prs[r], shards[r]->device, std::max<u64>(np[r], 1) * sizeof(uint2)))
-            return fail(root, ECB_ERR_HIP, "ecb_merge: out of device memory on device %d", shards[r]->device);
+        if ((rc = take(root, ent[r], shards[r]->device, std::max<u64>(ne[r], 1) * sizeof(Entry))) != ECB_OK) return rc;
+        if ((rc = take(root, prs[r], shards[r]->device, std::max<u64>(np[r], 1) * sizeof(uint2))) != ECB_OK) return rc;
         if (ne[r]) {
             rc = ecb_table_export_parts_device(shards[r], ent[r].p, prs[r].p, 0, n, eoff[r].data(), poff[r].data());
             if (rc != ECB_OK) return fail(root, rc, "ecb_merge: shard %u: %s", r, ecb_last_error(shards[r]));
@@ -5431,7 +5434,6 @@ extern "C" int ecb_merge(ecb_handle* const* shards, uint32_t n, ecb_handle* root
     const u64 t_reads = base[n];
     // 2. range q: its pieces to device q (the device of shard q), merged in shard order on a handle of its own, finalized there
     HandleGuard parts;
-    struct Piece { DevBuf<> ip, ix, da, cn, fi; u64 n_ecs = 0, nnz = 0; };
     std::vector<Piece> piece(n);
     for (u32 q = 0; q < n; ++q) {
         const int dq = shards[q]->device;
@@ -5450,10 +5452,10 @@ extern "C" int ecb_merge(ecb_handle* const* shards, uint32_t n, ecb_handle* root
         for (u32 r = 0; r < n; ++r) {
             const u64 e_n = eoff[r][q + 1] - eoff[r][q], p_n = poff[r][q + 1] - poff[r][q];
             if (!e_n) continue;
-            if (take(pe[r], dq, e_n * sizeof(Entry)) || take(pp[r], dq, std::max<u64>(p_n, 1) * sizeof(uint2))) return fail(root, ECB_ERR_HIP, "ecb_merge: out of device memory on device %d", dq);
-            if (hipMemcpyPeer(pe[r].p, dq, (const char*)ent[r].p + eoff[r][q] * sizeof(Entry), shards[r]->device, e_n * sizeof(Entry)) != hipSuccess ||
-                (p_n && hipMemcpyPeer(pp[r].p, dq, (const char*)prs[r].p + poff[r][q] * sizeof(uint2), shards[r]->device, p_n * sizeof(uint2)) != hipSuccess))
-                return fail(root, ECB_ERR_HIP, "ecb_merge: peer copy from device %d to device %d failed", shards[r]->device, dq);
+            if ((rc = take(root, pe[r], dq, e_n * sizeof(Entry))) != ECB_OK) return rc;
+            if ((rc = take(root, pp[r], dq, std::max<u64>(p_n, 1) * sizeof(uint2))) != ECB_OK) return rc;
+            MERGECHK(hipMemcpyPeer(pe[r].p, dq, (const char*)ent[r].p + eoff[r][q] * sizeof(Entry), shards[r]->device, e_n * sizeof(Entry)));
+            if (p_n) MERGECHK(hipMemcpyPeer(pp[r].p, dq, (const char*)prs[r].p + poff[r][q] * sizeof(uint2), shards[r]->device, p_n * sizeof(uint2)));
             if (base[r]) { rc = ecb_table_rebase_device(part, pe[r].p, e_n, base[r]); if (rc != ECB_OK) return fail(root, rc, "ecb_merge: %s", ecb_last_error(part)); }
             le.push_back(pe[r].p); lp.push_back(pp[r].p); lne.push_back(e_n); lnp.push_back(p_n);
         }
@@ -5464,34 +5466,31 @@ extern "C" int ecb_merge(ecb_handle* const* shards, uint32_t n, ecb_handle* root
         if (rc != ECB_OK) return fail(root, rc, "ecb_merge: range %u: %s", q, ecb_last_error(part));
         Piece& P = piece[q];
         P.n_ecs = s.n_ecs; P.nnz = s.nnz_a;
-        if (take(P.ip, dq, (s.n_ecs + 1) * 4) || take(P.ix, dq, s.nnz_a * 4) || take(P.da, dq, s.nnz_a * 4) || take(P.cn, dq, s.n_ecs * 4) || take(P.fi, dq, s.n_ecs * 4))
-            return fail(root, ECB_ERR_HIP, "ecb_merge: out of device memory on device %d", dq);
-        rc = ecb_export_device(part, P.ip.p, P.ix.p, P.da.p, nullptr, nullptr, P.cn.p);
-        if (rc == ECB_OK) rc = ecb_export_firsts_device(part, P.fi.p);
+        for (int k = 0; k < 5; ++k) if ((rc = take(root, P.buf[k], dq, P.bytes(k))) != ECB_OK) return rc;
+        rc = ecb_export_device(part, P.buf[0].p, P.buf[1].p, P.buf[2].p, nullptr, nullptr, P.buf[3].p);
+        if (rc == ECB_OK) rc = ecb_export_firsts_device(part, P.buf[4].p);
         if (rc != ECB_OK) return fail(root, rc, "ecb_merge: range %u: %s", q, ecb_last_error(part));
     }
     // 3. the finished pieces to the root's device, placed by first read
     const int d0 = root->device;
     std::vector<Piece> at_root(n);
-    std::vector<const void*> lip, lix, lda, lcn, lfi; std::vector<uint64_t> lne2, lnz;
+    std::vector<const void*> lst[5]; std::vector<uint64_t> lne2, lnz;
     for (u32 q = 0; q < n; ++q) {
         Piece& S = piece[q];
         if (!S.n_ecs) continue;
         Piece* use = &S;
-        if (S.ip.dev != d0) {
+        if (S.buf[0].dev != d0) {
             Piece& D = at_root[q];
-            if (take(D.ip, d0, (S.n_ecs + 1) * 4) || take(D.ix, d0, S.nnz * 4) || take(D.da, d0, S.nnz * 4) || take(D.cn, d0, S.n_ecs * 4) || take(D.fi, d0, S.n_ecs * 4))
-                return fail(root, ECB_ERR_HIP, "ecb_merge: out of device memory on device %d", d0);
-            if (hipMemcpyPeer(D.ip.p, d0, S.ip.p, S.ip.dev, (S.n_ecs + 1) * 4) != hipSuccess || hipMemcpyPeer(D.ix.p, d0, S.ix.p, S.ip.dev, S.nnz * 4) != hipSuccess ||
-                hipMemcpyPeer(D.da.p, d0, S.da.p, S.ip.dev, S.nnz * 4) != hipSuccess || hipMemcpyPeer(D.cn.p, d0, S.cn.p, S.ip.dev, S.n_ecs * 4) != hipSuccess ||
-                hipMemcpyPeer(D.fi.p, d0, S.fi.p, S.ip.dev, S.n_ecs * 4) != hipSuccess)
-                return fail(root, ECB_ERR_HIP, "ecb_merge: peer copy from device %d to device %d failed", S.ip.dev, d0);
             D.n_ecs = S.n_ecs; D.nnz = S.nnz;
+            for (int k = 0; k < 5; ++k) {
+                if (const int rc = take(root, D.buf[k], d0, D.bytes(k))) return rc;
+                MERGECHK(hipMemcpyPeer(D.buf[k].p, d0, S.buf[k].p, S.buf[0].dev, S.bytes(k)));
+            }
             use = &D;
         }
-        lip.push_back(use->ip.p); lix.push_back(use->ix.p); lda.push_back(use->da.p); lcn.push_back(use->cn.p); lfi.push_back(use->fi.p);
+        for (int k = 0; k < 5; ++k) lst[k].push_back(use->buf[k].p);
         lne2.push_back(use->n_ecs); lnz.push_back(use->nnz);
     }
-    return ecb_assemble_ranges_device(root, (uint32_t)lip.size(), lip.data(), lix.data(), lda.data(), lcn.data(), lfi.data(), lne2.data(), lnz.data(),
+    return ecb_assemble_ranges_device(root, (uint32_t)lst[0].size(), lst[0].data(), lst[1].data(), lst[2].data(), lst[3].data(), lst[4].data(), lne2.data(), lnz.data(),
                                       t_reads, t_all, t_valid, out);
 }

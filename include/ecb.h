@@ -98,7 +98,9 @@ int  ecb_device_count(void);
 int  ecb_create(const ecb_config* cfg, ecb_handle** out);
 void ecb_destroy(ecb_handle* h);
 int  ecb_reset(ecb_handle* h);                      /* forget all input and results, keep the allocations */
-const char* ecb_last_error(const ecb_handle* h);   /* h may be NULL: error of the last failed ecb_create */
+const char* ecb_last_error(const ecb_handle* h);   /* h may be NULL: the text of the calling thread's last failing call that took no
+                                                      handle (ecb_create and the entry points that take a device), valid until that
+                                                      thread's next such failure */
 
 /* Streaming input -- replaces the per-alignment loop of process_convert_bam (bam_utils.py:258-344).
  * ecb_push: host pointers; batches may cut a read anywhere (the library carries the open read over).

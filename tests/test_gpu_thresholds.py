@@ -149,10 +149,10 @@ def test_reads_carrying_cmax_and_one_more_entries_over_a_tile_end(cmax, monkeypa
 
 
 def test_reads_of_a_whole_tile_and_tiles_of_many_reads(monkeypatch):
-    """WT = 64 * RPL = 512 (``ecb.hip:334``) and WMAXR = 64 / 128 (``k_stream.inc:17``): reads of exactly 512 records that start on a tile
+    """WT = 64 * RPL = 512 (``ecb.hip: WT``) and WMAXR = 64 / 128 (``k_stream.inc:17``): reads of exactly 512 records that start on a tile
     start and one record before it, on distinct loci (open at the tile end with 512 entries: deferred) and on 40 loci repeated (carried);
     tiles of 65, 129 and 200 one-record reads (more than a pass of either kernel takes: the tile is visited again); and a read of 2 600
-    records, longer than a slice.  The slice size is not in the ABI: ``plan_stream`` (``ecb.hip:2620-2628``) cuts n records into
+    records, longer than a slice.  The slice size is not in the ABI: ``plan_stream`` (``ecb.hip: plan_stream``) cuts n records into
     min(resident waves x 24, max(n / (32 x 512), resident waves), ceil(n / 1024)) slices of ceil(n / slices) records rounded up to whole
     tiles; with 26 k records and the thousands of waves an MI355X holds that is ceil(n / 1024) slices of 1 024 records, so the read spans two
     whole slices and the slice after them starts inside it."""
@@ -191,7 +191,7 @@ def test_reads_of_a_whole_tile_and_tiles_of_many_reads(monkeypatch):
 
 @pytest.mark.parametrize("distinct", [True, False])
 def test_k_slow_lds_limit(distinct, monkeypatch):
-    """SLOW_LDS = 4096 (``ecb.hip:870``): k_slow keeps a read's table in LDS when 2 x its records <= SLOW_LDS (``ecb.hip:1041``), so reads of
+    """SLOW_LDS = 4096 (``ecb.hip: SLOW_LDS``): k_slow keeps a read's table in LDS when 2 x its records <= SLOW_LDS (``ecb.hip: k_slow``), so reads of
     2 047 and 2 048 records take the LDS body and 2 049 the global one.  All loci distinct, or 700 loci repeated round (every whole tile of
     such a read holds 512 distinct loci: open at the tile's end with more than CMAX entries, so all six are deferred).  Host and device
     pushes against the C oracle; the exactness pass sends exactly those six reads to k_slow."""
@@ -223,8 +223,8 @@ def test_k_slow_lds_limit(distinct, monkeypatch):
 
 @pytest.mark.parametrize("compilation", ["std", "short"])
 def test_every_read_deferred(compilation, monkeypatch):
-    """QSTRIPES = 64 (``ecb.hip:56``): the deferred-read queue is 64 hash-picked stripes of need_q / 64 heads, need_q = pwaves x (WT + 1) +
-    n / 64 + 16 (``ecb.hip:2633``), and a full stripe is fatal.  A launch defers at most one read per tile end (the one open there), so no
+    """QSTRIPES = 64 (``ecb.hip: QSTRIPES``): the deferred-read queue is 64 hash-picked stripes of need_q / 64 heads, need_q = pwaves x (WT + 1) +
+    n / 64 + 16 (``ecb.hip: need_q``), and a full stripe is fatal.  A launch defers at most one read per tile end (the one open there), so no
     stream defers more than n / 512 reads.  Here every read does: 12 M records in reads of 2 x WT + 1 = 1 025 distinct loci -- each covers a
     whole tile and is still open at its end, holding 512 entries > CMAX -- 11 707 deferred reads through ks_std and (forced) ks_short, one
     device push, against the C oracle.  (Passed as the queue stood: 183 heads a stripe on average against 4 k and more of room.)"""
@@ -268,8 +268,8 @@ KEY_SIZES = (4, 5, 6, 15, 16, 17, 2047, 2048, 2049, 5003)
 
 
 def test_key_lengths_through_finalize_merge_adopt_and_ecb_merge():
-    """INL = 5 (``ecb.hip:60``: pairs held in the table slot), RANKED_MAX = 16 (``ecb.hip:218``: keys of more go one wave each through
-    export and emit) and BIG_LDS = 2048 (``ecb.hip:252``: keys of more are walked in memory by the emit and k_parts_sort_big): ECs of
+    """INL = 5 (``ecb.hip: INL``: pairs held in the table slot), RANKED_MAX = 16 (``ecb.hip: RANKED_MAX``: keys of more go one wave each through
+    export and emit) and BIG_LDS = 2048 (``ecb.hip: BIG_LDS``: keys of more are walked in memory by the emit and k_parts_sort_big): ECs of
     4/5/6, 15/16/17, 2047/2048/2049 and 5003 pairs, each read twice or three times, in contiguous read shards that share ECs.  One handle
     over the whole stream (host and device push) against the C oracle; 2 and 3 shards on one GPU through table_export_parts ->
     table_merge_batch_device -> table_adopt_device and through ecb_merge (EcBuilder.merge_from), each == the oracle."""
@@ -413,7 +413,7 @@ def _combine(ms):
 
 @pytest.mark.parametrize("H", [1, 31])
 def test_ecmerge_long_rows_one_and_31_haplotypes(H):
-    """``ecb_combine`` with H = 1 and H = 31 (every mask with bit 30 set), rows of 2 047 / 2 048 / 2 049 (BIG_LDS = 2048, ``ecb.hip:252``)
+    """``ecb_combine`` with H = 1 and H = 31 (every mask with bit 30 set), rows of 2 047 / 2 048 / 2 049 (BIG_LDS = 2048, ``ecb.hip: BIG_LDS``)
     and 5 000 pairs in two parts that share them, one part under a shuffled target list, and a part whose rows are all empty: against
     ec_merge_checker."""
     rng = np.random.default_rng(40 + H)
@@ -478,9 +478,9 @@ def test_apply_genotypes_long_rows_and_bit_30():
 
 @pytest.mark.parametrize("n_col", [2304, 2305, 3072, 3073])
 def test_per_haplotype_csc_columns_on_the_piece_limits(n_col):
-    """CVU_PIECE = 1536, CVU_MAX = 3072 (``ecb.hip:1677-1678``): a column of more than 1.5 x CVU_PIECE = 2 304 row indices (summed over
+    """CVU_PIECE = 1536, CVU_MAX = 3072 (``ecb.hip: CVU_PIECE, CVU_MAX``): a column of more than 1.5 x CVU_PIECE = 2 304 row indices (summed over
     the haplotypes) is cut into ceil(n / 1536) pieces by EC range (``k_cvu_pieces``); a piece of more than CVU_MAX goes entry by entry
-    (``ecb.hip:1766``).  Columns of exactly 2 304 / 2 305 / 3 072 / 3 073 row indices over three haplotypes, with ECs spread over all ids
+    (``ecb.hip: k_cvu_union``).  Columns of exactly 2 304 / 2 305 / 3 072 / 3 073 row indices over three haplotypes, with ECs spread over all ids
     and bunched into the first quarter (every index in the first piece: 3 072 fill the LDS table, 3 073 take the entry path), both
     directions on the device and on host arrays, against scipy.  (A piece of exactly 3 072 once sized its table at 8 192 slots of
     CVU_TSZ = 4 096 and came back with ECs listed twice.)"""

@@ -522,3 +522,210 @@ def test_bench_dump_outputs_stays_in_budget_and_samples_reproducibly(tmp_path):
     bench.dump_outputs(str(whole), arrays)                                   # the default budget holds all of it
     for n, a in arrays.items():
         assert np.array_equal(np.load(whole / (n + ".npy")), a.astype(np.float64)), n
+
+
+def _stateless_calls(lib):
+    """(label, call) for every refusal of the ten stateless entry points that answers before a device is touched.  The device is -1
+    throughout, so a call whose arguments pass ends at "no such device" on every machine and nothing is ever dereferenced."""
+    import ctypes as C
+    from alntools_amd import ecb
+    a = np.zeros(64, np.int32)                                       # stands in for every array: never read, never written
+    p, q, r, s = (a.ctypes.data + 64 * k for k in range(4))         # four disjoint 64-byte stretches of it
+    out = C.c_uint64(0)
+    sizes = (C.c_uint64 * 3)()
+    MAX_LOCI, two31, two32 = (1 << 26) - 2, 1 << 31, 1 << 32
+    calls = []
+
+    def add(label, f, *args):
+        calls.append((label, lambda: f(-1, *args)))
+
+    for name, extra in (("ecb_csr_to_hapcsc_device", ()), ("ecb_csr_to_hapcsc", (8,))):
+        f = getattr(lib, name)
+        ok = dict(n_ecs=4, n_loci=8, n_haps=2, indptr=p, total=C.byref(out))
+        for label, ch in (("null indptr", dict(indptr=None)), ("null total", dict(total=None)), ("no ECs", dict(n_ecs=0)), ("no loci", dict(n_loci=0)),
+                          ("0 haplotypes", dict(n_haps=0)), ("32 haplotypes", dict(n_haps=32)), ("haplotypes x loci at 2^32", dict(n_loci=two31)),
+                          ("no device", {})):
+            k = dict(ok, **ch)
+            add("%s: %s" % (name, label), f, k["n_ecs"], k["n_loci"], k["n_haps"], k["indptr"], q, r, s, s + 64, *extra, k["total"])
+    for name in ("ecb_hapcsc_to_csr_device", "ecb_hapcsc_to_csr"):
+        f = getattr(lib, name)
+        ok = dict(n_haps=2, cscptr=p, total=4, nnz=C.byref(out))
+        for label, ch in (("null cscptr", dict(cscptr=None)), ("null nnz", dict(nnz=None)), ("0 haplotypes", dict(n_haps=0)), ("32 haplotypes", dict(n_haps=32)),
+                          ("total 0", dict(total=0)), ("total 2^32", dict(total=two32)), ("no device", {})):
+            k = dict(ok, **ch)
+            add("%s: %s" % (name, label), f, 4, 8, k["n_haps"], k["cscptr"], q, k["total"], r, s, s + 64, k["nnz"])
+    for name in ("ecb_apply_mask_device", "ecb_apply_mask"):
+        f = getattr(lib, name)
+        # (n_ecs 3, nnz 4: row pointers, columns, masks and the locus mask of 16 bytes each, 64 bytes apart)
+        ok = dict(n_ecs=3, n_loci=4, n_haps=2, nnz=4, ins=[p, p + 64, p + 128, p + 192], outs=[q + 256, q + 320, q + 384], kept=C.byref(out))
+        for label, ch in (("null indptr", dict(ins=[None, p + 64, p + 128, p + 192])), ("null kept", dict(kept=None)), ("0 haplotypes", dict(n_haps=0)),
+                          ("32 haplotypes", dict(n_haps=32)), ("no loci", dict(n_loci=0)), ("non-zeros without indices", dict(ins=[p, None, p + 128, p + 192])),
+                          ("nnz 2^31", dict(nnz=two31)), ("n_ecs 2^31-1", dict(n_ecs=two31 - 1)), ("an output on an input", dict(outs=[p + 8, q + 320, q + 384])),
+                          ("two outputs on each other", dict(outs=[q + 256, q + 260, q + 384])), ("no device", {})):
+            k = dict(ok, **ch)
+            add("%s: %s" % (name, label), f, k["n_ecs"], k["n_loci"], k["n_haps"], k["nnz"], *k["ins"], *k["outs"], k["kept"])
+    for name in ("ecb_combine_device", "ecb_combine"):
+        f = getattr(lib, name)
+
+        def part(**ch):
+            k = dict(dict(struct_size=C.sizeof(ecb.CombinePart), n_ecs=3, n_samples=1, n_loci=8, nnz_a=4, nnz_n=2, indptr_a=p, indices_a=p + 64, data_a=p + 128,
+                          indptr_n=q, indices_n=q + 64, data_n=q + 128, target_map=None, sample_map=r), **ch)
+            return (ecb.CombinePart * 1)(ecb.CombinePart(**k))
+        ok = dict(n_parts=1, parts=part(), n_loci=8, n_haps=2, outs=[s, s + 64, s + 128, s + 192, s + 256, s + 320], sizes=sizes)
+        for label, ch in (("null parts", dict(parts=None)), ("no parts", dict(n_parts=0)), ("null sizes", dict(sizes=None)), ("0 haplotypes", dict(n_haps=0)),
+                          ("32 haplotypes", dict(n_haps=32)), ("n_loci at MAX_LOCI", dict(n_loci=MAX_LOCI)), ("bad struct_size", dict(parts=part(struct_size=8))),
+                          ("null array in a part", dict(parts=part(indices_a=None))), ("no sample map", dict(parts=part(sample_map=None))),
+                          ("no target map, other loci", dict(parts=part(n_loci=7))), ("a part's nnz at 2^31", dict(parts=part(nnz_a=two31))),
+                          ("null output", dict(outs=[s, None, s + 128, s + 192, s + 256, s + 320])), ("no device", {})):
+            k = dict(ok, **ch)
+            add("%s: %s" % (name, label), f, k["n_parts"], k["parts"], k["n_loci"], k["n_haps"], 1, *k["outs"], k["sizes"])
+    for name in ("ecb_salmon_ecs_device", "ecb_salmon_ecs"):
+        f = getattr(lib, name)
+        ok = dict(text=p, n_ecs=3, n_targets=4, n_loci=8, n_haps=2, capacity=16, sizes=sizes)
+        for label, ch in (("null sizes", dict(sizes=None)), ("bytes without a text", dict(text=None)), ("0 haplotypes", dict(n_haps=0)), ("32 haplotypes", dict(n_haps=32)),
+                          ("n_loci at MAX_LOCI", dict(n_loci=MAX_LOCI)), ("n_ecs 2^31-1", dict(n_ecs=two31 - 1)), ("n_targets 2^31", dict(n_targets=two31)),
+                          ("capacity 2^31", dict(capacity=two31)), ("no device", {})):
+            k = dict(ok, **ch)
+            add("%s: %s" % (name, label), f, k["text"], 32, k["n_ecs"], k["n_targets"], q, q + 64, k["n_loci"], k["n_haps"], k["capacity"],
+                r, r + 64, r + 128, s, s + 64, k["sizes"])
+    return calls, a
+
+
+_BAD, _NODEV, _INT32 = (-1, "bad argument"), (-3, "no such device"), (-8, "the CSR exceeds the .bin format's int32 limits")
+_STATELESS_REFUSALS = {
+    "ecb_csr_to_hapcsc_device: null indptr": _BAD,
+    "ecb_csr_to_hapcsc_device: null total": _BAD,
+    "ecb_csr_to_hapcsc_device: no ECs": _BAD,
+    "ecb_csr_to_hapcsc_device: no loci": _BAD,
+    "ecb_csr_to_hapcsc_device: 0 haplotypes": _BAD,
+    "ecb_csr_to_hapcsc_device: 32 haplotypes": _BAD,
+    "ecb_csr_to_hapcsc_device: haplotypes x loci at 2^32": (-8, "haplotypes x loci does not fit 32 bits"),
+    "ecb_csr_to_hapcsc_device: no device": _NODEV,
+    "ecb_csr_to_hapcsc: null indptr": _BAD,
+    "ecb_csr_to_hapcsc: null total": _BAD,
+    "ecb_csr_to_hapcsc: no ECs": _BAD,
+    "ecb_csr_to_hapcsc: no loci": _BAD,
+    "ecb_csr_to_hapcsc: 0 haplotypes": _BAD,
+    "ecb_csr_to_hapcsc: 32 haplotypes": _BAD,
+    "ecb_csr_to_hapcsc: haplotypes x loci at 2^32": _NODEV,
+    "ecb_csr_to_hapcsc: no device": _NODEV,
+    "ecb_hapcsc_to_csr_device: null cscptr": _BAD,
+    "ecb_hapcsc_to_csr_device: null nnz": _BAD,
+    "ecb_hapcsc_to_csr_device: 0 haplotypes": _BAD,
+    "ecb_hapcsc_to_csr_device: 32 haplotypes": _BAD,
+    "ecb_hapcsc_to_csr_device: total 0": _BAD,
+    "ecb_hapcsc_to_csr_device: total 2^32": (-8, "more than 2^32-1 row indices"),
+    "ecb_hapcsc_to_csr_device: no device": _NODEV,
+    "ecb_hapcsc_to_csr: null cscptr": _BAD,
+    "ecb_hapcsc_to_csr: null nnz": _BAD,
+    "ecb_hapcsc_to_csr: 0 haplotypes": _BAD,
+    "ecb_hapcsc_to_csr: 32 haplotypes": _BAD,
+    "ecb_hapcsc_to_csr: total 0": _BAD,
+    "ecb_hapcsc_to_csr: total 2^32": (-8, "more than 2^32-1 row indices"),
+    "ecb_hapcsc_to_csr: no device": _NODEV,
+    "ecb_apply_mask_device: null indptr": _BAD,
+    "ecb_apply_mask_device: null kept": _BAD,
+    "ecb_apply_mask_device: 0 haplotypes": _BAD,
+    "ecb_apply_mask_device: 32 haplotypes": _BAD,
+    "ecb_apply_mask_device: no loci": _BAD,
+    "ecb_apply_mask_device: non-zeros without indices": _BAD,
+    "ecb_apply_mask_device: nnz 2^31": _INT32,
+    "ecb_apply_mask_device: n_ecs 2^31-1": _INT32,
+    "ecb_apply_mask_device: an output on an input": (-1, "an output overlaps an input"),
+    "ecb_apply_mask_device: two outputs on each other": (-1, "the outputs overlap"),
+    "ecb_apply_mask_device: no device": _NODEV,
+    "ecb_apply_mask: null indptr": _BAD,
+    "ecb_apply_mask: null kept": _BAD,
+    "ecb_apply_mask: 0 haplotypes": _BAD,
+    "ecb_apply_mask: 32 haplotypes": _BAD,
+    "ecb_apply_mask: no loci": _BAD,
+    "ecb_apply_mask: non-zeros without indices": _BAD,
+    "ecb_apply_mask: nnz 2^31": _INT32,
+    "ecb_apply_mask: n_ecs 2^31-1": _INT32,
+    "ecb_apply_mask: an output on an input": _NODEV,
+    "ecb_apply_mask: two outputs on each other": _NODEV,
+    "ecb_apply_mask: no device": _NODEV,
+    "ecb_combine_device: null parts": (-1, "combine: bad argument"),
+    "ecb_combine_device: no parts": (-1, "combine: bad argument"),
+    "ecb_combine_device: null sizes": (-1, "combine: bad argument"),
+    "ecb_combine_device: 0 haplotypes": (-1, "combine: bad argument"),
+    "ecb_combine_device: 32 haplotypes": (-1, "combine: bad argument"),
+    "ecb_combine_device: n_loci at MAX_LOCI": (-1, "combine: n_loci out of range (1 .. 2^26-3)"),
+    "ecb_combine_device: bad struct_size": (-1, "combine: part 0: bad struct_size"),
+    "ecb_combine_device: null array in a part": (-1, "combine: part 0: null array"),
+    "ecb_combine_device: no sample map": (-1, "combine: part 0: no sample map"),
+    "ecb_combine_device: no target map, other loci": (-1, "combine: part 0: no target map, but 7 loci against 8"),
+    "ecb_combine_device: a part's nnz at 2^31": (-8, "combine: part 0 exceeds the .bin format's int32 limits"),
+    "ecb_combine_device: null output": (-1, "combine: null output"),
+    "ecb_combine_device: no device": _NODEV,
+    "ecb_combine: null parts": (-1, "combine: bad argument"),
+    "ecb_combine: no parts": (-1, "combine: bad argument"),
+    "ecb_combine: null sizes": (-1, "combine: bad argument"),
+    "ecb_combine: 0 haplotypes": _NODEV,
+    "ecb_combine: 32 haplotypes": _NODEV,
+    "ecb_combine: n_loci at MAX_LOCI": _NODEV,
+    "ecb_combine: bad struct_size": _NODEV,
+    "ecb_combine: null array in a part": _NODEV,
+    "ecb_combine: no sample map": _NODEV,
+    "ecb_combine: no target map, other loci": _NODEV,
+    "ecb_combine: a part's nnz at 2^31": _NODEV,
+    "ecb_combine: null output": _NODEV,
+    "ecb_combine: no device": _NODEV,
+    "ecb_salmon_ecs_device: null sizes": (-1, "salmon: bad argument"),
+    "ecb_salmon_ecs_device: bytes without a text": (-1, "salmon: bad argument"),
+    "ecb_salmon_ecs_device: 0 haplotypes": (-1, "salmon: bad argument"),
+    "ecb_salmon_ecs_device: 32 haplotypes": (-1, "salmon: bad argument"),
+    "ecb_salmon_ecs_device: n_loci at MAX_LOCI": (-1, "salmon: n_loci out of range (1 .. 2^26-3)"),
+    "ecb_salmon_ecs_device: n_ecs 2^31-1": (-8, "salmon: E or T beyond int32"),
+    "ecb_salmon_ecs_device: n_targets 2^31": (-8, "salmon: E or T beyond int32"),
+    "ecb_salmon_ecs_device: capacity 2^31": _NODEV,
+    "ecb_salmon_ecs_device: no device": _NODEV,
+    "ecb_salmon_ecs: null sizes": (-1, "salmon: bad argument"),
+    "ecb_salmon_ecs: bytes without a text": (-1, "salmon: bad argument"),
+    "ecb_salmon_ecs: 0 haplotypes": _NODEV,
+    "ecb_salmon_ecs: 32 haplotypes": _NODEV,
+    "ecb_salmon_ecs: n_loci at MAX_LOCI": _NODEV,
+    "ecb_salmon_ecs: n_ecs 2^31-1": (-8, "salmon: E or the capacity beyond int32"),
+    "ecb_salmon_ecs: n_targets 2^31": _NODEV,
+    "ecb_salmon_ecs: capacity 2^31": (-8, "salmon: E or the capacity beyond int32"),
+    "ecb_salmon_ecs: no device": _NODEV,
+}
+
+
+def test_stateless_entry_points_refuse_as_before_and_keep_their_text_per_thread():
+    """Every refusal of the ten entry points that take a device instead of a handle which is decided before a device is touched --
+    null pointers, 0 and 32 haplotypes, n_loci at MAX_LOCI, sizes at 2^31 and 2^32, overlapping outputs, a bad struct_size, a missing
+    map, no device -- as ``(code, ecb_last_error(NULL))``.  The literals were recorded by running these same calls against a library
+    built from the commit before the stateless entry points were given one scaffold (90c453b), not from the code under test.
+    Then the one thing that commit could not do: ``ecb_last_error(NULL)`` is the calling thread's own text, so two threads that are
+    refused at the same time for different reasons each read back their own."""
+    import threading
+    from alntools_amd import ecb
+    lib = ecb.load()
+    calls, keep = _stateless_calls(lib)
+    assert {label for label, _ in calls} == set(_STATELESS_REFUSALS)
+    assert {label.split(":")[0] for label, _ in calls} == {s for s in ecb.SYMBOLS if s.split("_")[1] in ("csr", "hapcsc", "apply", "combine", "salmon")}
+    for label, call in calls:
+        got = (call(), lib.ecb_last_error(None).decode())
+        print(label, got)
+        assert got == _STATELESS_REFUSALS[label], label
+
+    by_label = dict(calls)
+    wrong = []
+
+    def provoke(label, n=3000):
+        call, want = by_label[label], _STATELESS_REFUSALS[label]
+        for _ in range(n):
+            got = (call(), lib.ecb_last_error(None).decode())
+            if got != want:
+                wrong.append((label, got))
+                return
+    labels = ("ecb_csr_to_hapcsc_device: 0 haplotypes", "ecb_combine_device: n_loci at MAX_LOCI")
+    assert _STATELESS_REFUSALS[labels[0]][1] != _STATELESS_REFUSALS[labels[1]][1]
+    threads = [threading.Thread(target=provoke, args=(l,)) for l in labels]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not wrong, wrong[:4]
+    del keep
