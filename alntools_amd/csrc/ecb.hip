@@ -2438,55 +2438,81 @@ template <class T> hipError_t pin(Pinned<T>& out) {
 // =============================================================================================
 // host side
 // =============================================================================================
+// Where a handle's stream stands (in this order: a stage is never left for an earlier one, except by ecb_reset) ...
+enum class Stage { OPEN,              // takes pushes
+                   COUNTED,           // Slot::count / first_inv hold the reads pushed (k_count ran, or entries were adopted): closed to pushes
+                   FINAL };           // a result is there to export
+// ... and where its table's entries came from
+enum class Origin { OWN,              // its own reads (and what ecb_table_merge_device added to them)
+                    ADOPTED,          // adopted entries in consecutive slots (no hashing): finalize / export only
+                    ASSEMBLED };      // no table: the result was put together from per-range results (ecb_assemble_ranges_device)
+// whose (EC, cell, file) triples Run::tri holds
+enum class Triples { NONE, OWN /* ms_reduce, of the handle's own reads */, ADOPTED /* ecb_ms_adopt_triples_device (multi-GPU) */ };
+
 struct ecb_handle {
     ecb_config cfg{};
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;
-    bool finalized = false;
-    bool counted = false;             // Slot::count / first_inv hold the reads pushed so far (k_count ran)
     u64 wave_arena_n = 0;             // see StreamArgs::wave_arena
     bool scatter_attr_set = false, count_attr_set = false;
-    bool list_from_counts = false;             // finalize: k_count_bins listed the occupied slots (no k_compact pass)
-    bool assembled = false;                    // the result was put together from per-range results (ecb_assemble_ranges_device)
-    bool list_counted = false;                 // ... and so it did for a table export (the list alone; its length at *d_list_n)
-    u64* d_list_n = nullptr;
     u64 resident_blocks = 0, resident_blocks_rg = 0, resident_blocks_sh = 0, rounds = 24, min_tiles = 32;     // k_stream's launch shape (queried once)
     bool short_reads = false;         // this batch goes through ks_short::k_stream (set per batch by process_batch)
     bool par_stream = false;          // ... through ks_par::k_stream: the batch before met loci that displace each other in the LDS table (sticky per handle)
     u64 resident_blocks_par = 0;
-    u64 records_pushed = 0;           // records of the batches so far (with n_reads: how many records a read brings)
     bool ctr_synced = false;          // hctr is what the device holds (no kernel that counts has been queued since the last read-back)
-    bool adopted = false;             // the table holds adopted entries in consecutive slots (no hashing): finalize / export only
 
     u64 cap = 0, arena_cap = 0;       // slots of table, pairs of arena
     Counters hctr{};                  // last read-back
     struct PinOut { Counters c; u64 tot[8]; };
     u64 read_slot_cap = 0;
-    u64 meta_cap = 0, meta_hi = 0;    // multisample: cell | file << 22 per read
-    u64 n_triples = 0; u64* ms_okey = nullptr; u32 *ms_ofirst = nullptr, *ms_ostart = nullptr, *ms_ocount = nullptr;
-    bool ms_adopted = false;          // the triples came from ecb_ms_adopt_triples_device (multi-GPU)
-    // ecb_ms_filter's results (device): kept cells in sample order, rows of A of the kept ECs, CSC N
-    bool ms_filtered = false; ecb_ms_sizes msf{};
-    u32* f_cells = nullptr; int *f_ipa = nullptr, *f_ixa = nullptr, *f_daa = nullptr, *f_ipn = nullptr, *f_ixn = nullptr, *f_dan = nullptr;
+    u64 meta_cap = 0;                 // multisample: cell | file << 22 per read
     u64 queue_cap = 0;
     u64 n_ecs() const { return hctr.n_ecs; }
-    u32 prev_rid = 0xFFFFFFFFu;       // read_id of the last record pushed so far
-    u64 n_reads = 0;
-    u64 reads_hi = 0;                 // read_slot entries [0, reads_hi) may be set (n_reads, or more mid-batch)
     u64 reads_hint = 0;               // ecb_hint_reads: the stream holds at most this many reads (0 = not said)
-    u64 extra_all = 0, extra_valid = 0, extra_reads = 0;   // counters merged in from other ranks
-    u64 n_mismatch = 0;               // ECB_F_VERIFY: reads the exactness pass found in a wrong EC, over all pushes
 
     // host-pointer staging (the streams behind st_rid, in its allocation)
     u32 *st_loc = nullptr, *st_hf = nullptr; int* st_pos = nullptr; u64 st_cap = 0;
-    std::vector<u32> c_rid, c_loc, c_hf; std::vector<int> c_pos;   // open read carried between pushes
 
-    // results
-    u32* list = nullptr; u64 n_list = 0;
-    u32 *order = nullptr, *rank_of_slot = nullptr, *indptr = nullptr;
-    int *indices = nullptr, *data = nullptr, *counts = nullptr;
-    ecb_sizes sizes{};
+    // Everything that describes the stream being built and its results, and nothing that outlives it: ecb_reset ends in run = Run{}.
+    // (The pointers are views into pool buffers, which stay; a null one says that what it would show has not been made.)
+    struct Run {
+        Stage stage = Stage::OPEN;
+        Origin origin = Origin::OWN;
+        u32 prev_rid = 0xFFFFFFFFu;       // read_id of the last record pushed so far
+        u64 n_reads = 0;
+        u64 reads_hi = 0;                 // read_slot entries [0, reads_hi) may be set (n_reads, or more mid-batch)
+        u64 records_pushed = 0;           // records of the batches so far (with n_reads: how many records a read brings)
+        u64 meta_hi = 0;                  // meta entries [0, meta_hi) are set
+        u64 extra_all = 0, extra_valid = 0, extra_reads = 0;   // counters merged in from other ranks
+        u64 n_mismatch = 0;               // ECB_F_VERIFY: reads the exactness pass found in a wrong EC, over all pushes
+        std::vector<u32> c_rid, c_loc, c_hf; std::vector<int> c_pos;   // open read carried between pushes
+        // the occupied slots, listed in pool[P_LIST]: current when d_list_n is set, which is where its length sits on the device
+        // (null: not listed, or slot ids have changed since)
+        u64* d_list_n = nullptr;
+        // finalize's / assemble's result: A as CSR and the reads per EC (n_list: the slots finalize found occupied, pool[P_LIST])
+        struct Csr { u32 *order = nullptr, *rank_of_slot = nullptr /* made on demand: ensure_slot_ranks */, *indptr = nullptr;
+                     int *indices = nullptr, *data = nullptr, *counts = nullptr; } csr;
+        u64 n_list = 0;
+        ecb_sizes sizes{};
+        // multisample: the distinct (EC, cell, file) triples, sorted (ocount null: the counts are the differences of ostart)
+        struct Tri { u64 n = 0; u64* okey = nullptr; u32 *ofirst = nullptr, *ostart = nullptr, *ocount = nullptr; } tri;
+        Triples triples = Triples::NONE;
+        // ecb_ms_filter's result: kept cells in sample order, rows of A of the kept ECs, CSC N (cells null: none is current)
+        struct Filtered { u32* cells = nullptr; int *ipa = nullptr, *ixa = nullptr, *daa = nullptr, *ipn = nullptr, *ixn = nullptr, *dan = nullptr; } flt;
+        ecb_ms_sizes msf{};
+    } run;
+    // what the entry points ask of the lifecycle
+    bool multisample() const { return (cfg.flags & ECB_F_MULTISAMPLE) != 0; }
+    bool can_push() const { return run.stage == Stage::OPEN; }
+    bool counted() const { return run.stage >= Stage::COUNTED; }
+    bool has_result() const { return run.stage == Stage::FINAL; }
+    bool has_ms_result() const { return has_result() && multisample(); }
+    bool open_read() const { return !run.c_rid.empty(); }                          // a host push left a read open
+    bool holds_nothing() const { return !n_ecs() && !run.n_reads && !open_read(); }
+    bool entries_from_elsewhere() const { return run.origin != Origin::OWN; }      // (multi-GPU: its triples come by ecb_ms_adopt_triples_device)
+    u32* slot_list() const { return pool[P_LIST].as<u32>(); }
+    bool awaits_triples() const { return entries_from_elsewhere() && run.triples != Triples::ADOPTED; }
 
     // device scratch reused across calls (grown on demand: POOL)
     enum { P_RESUME, P_SUMS, P_HIST, P_OFFS, P_PAIRS, P_CNT, P_PARTS, P_WORK, P_LIST, P_BITMAP, P_WPOP, P_WPREFIX, P_ROWLEN, P_ORDER,
@@ -2537,6 +2563,8 @@ int fail(ecb_handle* h, int code, const char* fmt, ...) {
 #define HIPCHK_AS(h, prefix, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) \
     return fail(h, ECB_ERR_HIP, "%s%s: %s", prefix, #call, hipGetErrorString(e_)); } while (0)
 #define HIPCHK(h, call) HIPCHK_AS(h, "", call)
+// ... and so does a call of the library's own that does not return ECB_OK (it has set the text)
+#define RCCHK(call) do { const int rc_ = (call); if (rc_ != ECB_OK) return rc_; } while (0)
 
 // Error bits a kernel leaves behind, as data: the first entry of `table` with a bit in `bits` is the refusal (ECB_OK when none is
 // set), so the table's order says which one wins.  `arg` fills the one %llu a text may hold.
@@ -2610,20 +2638,17 @@ int grow_table(ecb_handle* h, u64 new_cap) {
     if (new_cap > (1ull << 32)) return fail(h, ECB_ERR_LIMIT, "EC table beyond 2^32 slots");
     POOL(h, P_REMAP, remap, h->cap);
     HIPCHK(h, nt.alloc(new_cap * sizeof(Slot)));
-    hipError_t e = hipMemsetAsync(nt, 0, new_cap * sizeof(Slot), h->stream);
+    HIPCHK_AS(h, "grow_table: ", hipMemsetAsync(nt, 0, new_cap * sizeof(Slot), h->stream));
     // (slots the old table did not hold map to PENDING: read_slot may hold slot ids of an EARLIER stream beyond the reads processed so far --
     //  ecb_reset leaves them, ecb_hint_reads makes reads_hi run ahead of the stream -- and what such an entry maps to must not be pool garbage)
-    if (e == hipSuccess) e = hipMemsetAsync(remap, 0xFF, h->cap * sizeof(u32), h->stream);
-    if (e == hipSuccess) {
-        k_rehash<<<2048, TPB, 0, h->stream>>>(h->table, h->cap, nt, new_cap - 1, remap);
-        if (h->reads_hi)
-            k_remap_read_slot<<<2048, TPB, 0, h->stream>>>(h->read_slot, h->reads_hi, remap);
-        e = hipStreamSynchronize(h->stream);
-    }
-    if (e != hipSuccess) return fail(h, ECB_ERR_HIP, "grow_table: %s", hipGetErrorString(e));
+    HIPCHK_AS(h, "grow_table: ", hipMemsetAsync(remap, 0xFF, h->cap * sizeof(u32), h->stream));
+    k_rehash<<<2048, TPB, 0, h->stream>>>(h->table, h->cap, nt, new_cap - 1, remap);
+    if (h->run.reads_hi)
+        k_remap_read_slot<<<2048, TPB, 0, h->stream>>>(h->read_slot, h->run.reads_hi, remap);
+    HIPCHK_AS(h, "grow_table: ", hipStreamSynchronize(h->stream));
     HIPCHK(h, h->table.reset());
     h->table = std::move(nt);
-    h->cap = new_cap; h->list_counted = false;     // (slot ids changed)
+    h->cap = new_cap; h->run.d_list_n = nullptr;   // (slot ids changed)
     return ECB_OK;
 }
 
@@ -2631,7 +2656,7 @@ int ensure_read_slot(ecb_handle* h, u64 need) {
     if (need <= h->read_slot_cap) return ECB_OK;
     u64 nc = std::max<u64>(need, h->read_slot_cap * 2);
     nc = std::max<u64>(nc, 1024);
-    HIPCHK(h, h->read_slot.grow(nc * sizeof(u32), 0xFF, h->n_reads * sizeof(u32), h->stream));
+    HIPCHK(h, h->read_slot.grow(nc * sizeof(u32), 0xFF, h->run.n_reads * sizeof(u32), h->stream));
     h->read_slot_cap = nc;
     return ECB_OK;
 }
@@ -2640,7 +2665,7 @@ int ensure_read_slot(ecb_handle* h, u64 need) {
 int ensure_meta(ecb_handle* h, u64 need) {
     if (need <= h->meta_cap) return ECB_OK;
     const u64 nc = std::max<u64>(need, h->meta_cap * 2);
-    HIPCHK(h, h->meta.grow(nc * sizeof(u32), -1, h->meta_hi * sizeof(u32), h->stream));
+    HIPCHK(h, h->meta.grow(nc * sizeof(u32), -1, h->run.meta_hi * sizeof(u32), h->stream));
     h->meta_cap = nc;
     return ECB_OK;
 }
@@ -2672,7 +2697,7 @@ int run_slow(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* d_hf,
         if (bm.bytes != had_m) HIPCHK(h, hipMemsetAsync(sm, 0, bm.bytes, h->stream));
         HIPCHK(h, hipMemcpyAsync(d_off, off.data(), nq * sizeof(u64), hipMemcpyHostToDevice, h->stream));
         SlowArgs a{d_rid, d_loc, d_hf, d_q, d_len, d_off, sk, sm, h->cfg.n_loci, h->cfg.n_haplotypes,
-                   h->table, h->cap - 1, h->arena, h->arena_cap, h->ctr, h->read_slot, h->reads_hi, nre_buf, d_nre, verify ? 1u : 0u};
+                   h->table, h->cap - 1, h->arena, h->arena_cap, h->ctr, h->read_slot, h->run.reads_hi, nre_buf, d_nre, verify ? 1u : 0u};
         k_slow<<<(unsigned)nq, TPB, 2 * SLOW_LDS * sizeof(u32), h->stream>>>(a);
         u64 nre = 0;
         HIPCHK(h, hipMemcpyAsync(&nre, d_nre, sizeof(u64), hipMemcpyDeviceToHost, h->stream));
@@ -2751,8 +2776,7 @@ int run_deferred(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* d
 // took the long path.
 int verify_batch(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* d_hf, u64 n, u32 prev_rid, u64* n_mismatch, u64* n_long, u32 tw = 512u) {
     StreamPlan P;
-    int rc = plan_stream(h, n, &P);
-    if (rc != ECB_OK) return rc;
+    RCCHK(plan_stream(h, n, &P));
     u64* d_resume = nullptr; u32* d_wcounts = nullptr;
     POOL(h, P_RESUME, d_resume, 2 * P.slices); POOL(h, P_WCOUNTS, d_wcounts, 3 * P.pwaves);
     k_init_resume<<<nblk(P.slices, TPB), TPB, 0, h->stream>>>(d_resume, P.slices, P.chunk);
@@ -2764,15 +2788,13 @@ int verify_batch(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* d
     *h->pin_cold = StreamCold{h->arena, h->arena_cap, h->queue, h->queue_cap, d_resume, d_wcounts, nullptr, nullptr, P.chunk, prev_rid,
                               nullptr, nullptr, 0u, 0u};
     HIPCHK(h, hipMemcpyAsync(h->d_cold, h->pin_cold.get(), sizeof(StreamCold), hipMemcpyHostToDevice, h->stream));
-    StreamArgs a{d_rid, d_loc, d_hf, n, h->table, h->cap - 1, h->ctr, h->read_slot, h->reads_hi, h->d_cold, 0u};
+    StreamArgs a{d_rid, d_loc, d_hf, n, h->table, h->cap - 1, h->ctr, h->read_slot, h->run.reads_hi, h->d_cold, 0u};
     ks_std::k_stream<true><<<(unsigned)P.blocks, TPB, 0, h->stream>>>(a);
     k_sum_counts<<<1, 1024, 0, h->stream>>>(d_wcounts, P.pwaves, h->ctr, 1u, 0ull, h->queue_cap);
     HIPCHK(h, hipGetLastError());
-    rc = sync_counters(h);
-    if (rc != ECB_OK) return rc;
+    RCCHK(sync_counters(h));
     u64 nq = 0;
-    rc = run_deferred(h, d_rid, d_loc, d_hf, n, true, tw, &nq);
-    if (rc != ECB_OK) return rc;
+    RCCHK(run_deferred(h, d_rid, d_loc, d_hf, n, true, tw, &nq));
     *n_mismatch = h->hctr.n_mismatch;
     *n_long = nq;
     HIPCHK(h, hipMemsetAsync(&h->ctr->n_queue, 0, (1 + QSTRIPES) * sizeof(u64), h->stream));
@@ -2788,31 +2810,29 @@ int process_batch(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* 
     // exact number with the counters, at the batch's one wait.
     const bool hinted = h->reads_hint != 0;
     u32 last_rid = 0;
-    u64 reads_after = std::max<u64>(h->reads_hint, h->n_reads);
+    u64 reads_after = std::max<u64>(h->reads_hint, h->run.n_reads);
     if (!hinted) {
         HIPCHK(h, hipMemcpyAsync(&last_rid, d_rid + rec_at(n - 1, tw), sizeof(u32), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         reads_after = (u64)(u32)(last_rid + 1u);
-        if (reads_after < h->n_reads) return fail(h, ECB_ERR_CONTRACT, "read_id went backwards across pushes");
+        if (reads_after < h->run.n_reads) return fail(h, ECB_ERR_CONTRACT, "read_id went backwards across pushes");
     }
-    int rc = ensure_read_slot(h, reads_after);
-    if (rc != ECB_OK) return rc;
-    h->reads_hi = reads_after;
+    RCCHK(ensure_read_slot(h, reads_after));
+    h->run.reads_hi = reads_after;
     // keep the table at most half full before a batch (it grows again, via k_slow, if a batch overfills it)
-    while (h->n_ecs() * 2 > h->cap) { rc = grow_table(h, h->cap * 4); if (rc != ECB_OK) return rc; }
+    while (h->n_ecs() * 2 > h->cap) { RCCHK(grow_table(h, h->cap * 4)); }
     // Short reads (a 512-record tile holds more reads than a pass of 64 takes): the kernel with passes of 128 reads.  Known only when the
     // caller has said how many reads the stream holds (ecb_hint_reads) -- the records-per-read of this batch is then n / (its share of them).
     // (records per read: of the batches before this one where there are any; a first batch is judged as if it were the whole stream -- it must
     //  then hold at least one record per announced read -- so that a long-read stream pushed in many batches is not taken for a short-read one)
-    const bool few = h->n_reads ? h->records_pushed < 7 * h->n_reads : (n >= h->reads_hint && n < 7 * h->reads_hint);
+    const bool few = h->run.n_reads ? h->run.records_pushed < 7 * h->run.n_reads : (n >= h->reads_hint && n < 7 * h->reads_hint);
     h->short_reads = hinted && !h->rng && h->cfg.n_loci < MAX_LOCI_SHORT && h->cfg.n_haplotypes <= 8 && !getenv("ECB_NO_SHORT") &&
                      (getenv("ECB_FORCE_SHORT") || few);
     // Loci that displace each other in the LDS table (paralogs: target ids anywhere): the compilation whose key compare settles displaced pairs
     // in registers, once a batch has shown that more than a quarter of its tiles took the probe-on path (and back below a sixteenth).
     const bool par = !h->short_reads && !h->rng && !getenv("ECB_NO_PAR") && (getenv("ECB_FORCE_PAR") || h->par_stream);
     StreamPlan P;
-    rc = plan_stream(h, n, &P, h->rng != nullptr, h->short_reads, par);
-    if (rc != ECB_OK) return rc;
+    RCCHK(plan_stream(h, n, &P, h->rng != nullptr, h->short_reads, par));
     const u64 waves = P.slices, chunk = P.chunk, blocks = P.blocks, pwaves = P.pwaves;
     u64* d_resume = nullptr;
     POOL(h, P_RESUME, d_resume, 2 * waves);
@@ -2823,7 +2843,7 @@ int process_batch(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* 
         HIPCHK(h, h->wave_arena.grow(2 * pwaves * sizeof(u64), 0, 2 * h->wave_arena_n * sizeof(u64), h->stream));
         h->wave_arena_n = pwaves;
     }
-    StreamCold cold{h->arena, h->arena_cap, h->queue, h->queue_cap, d_resume, d_wcounts, h->wave_arena, nullptr, chunk, h->prev_rid,
+    StreamCold cold{h->arena, h->arena_cap, h->queue, h->queue_cap, d_resume, d_wcounts, h->wave_arena, nullptr, chunk, h->run.prev_rid,
                     d_pos, h->rng, h->cfg.n_loci, h->cfg.n_haplotypes};
 #ifdef ECB_TIMING
     HIPCHK(h, hipMalloc(&cold.timing, 8 * sizeof(u64)));
@@ -2831,11 +2851,12 @@ int process_batch(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* 
 #endif
     *h->pin_cold = cold;      // (pinned: rewritten by the next batch, which starts after this one's host wait)
     HIPCHK(h, hipMemcpyAsync(h->d_cold, h->pin_cold.get(), sizeof(StreamCold), hipMemcpyHostToDevice, h->stream));
-    StreamArgs a{d_rid, d_loc, d_hf, n, h->table, h->cap - 1, h->ctr, h->read_slot, h->reads_hi, h->d_cold,
+    StreamArgs a{d_rid, d_loc, d_hf, n, h->table, h->cap - 1, h->ctr, h->read_slot, h->run.reads_hi, h->d_cold,
                  getenv("ECB_ABLATE") ? (u32)atoi(getenv("ECB_ABLATE")) : 0u, d_pos, h->rng};
     h->ctr_synced = false;
     const u64 probe_before = h->hctr.n_probe_tiles;
     u64 offered = n;                                    // records offered to the filter (bam_utils.py:261): all of the batch
+    int rc = ECB_OK;
     for (u32 launch = 0;; ++launch) {
         if (launch) {                                   // per launch (the first one's: k_init_resume)
             HIPCHK(h, hipMemsetAsync(&h->ctr->n_queue, 0, (1 + QSTRIPES) * sizeof(u64), h->stream));
@@ -2877,7 +2898,7 @@ int process_batch(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* 
         fprintf(stderr, "\n");
     }
 #endif
-    if (rc != ECB_OK) return rc;
+    RCCHK(rc);
     {
         const u64 tiles = (n + WT - 1) / WT, on_path = h->hctr.n_probe_tiles - probe_before;
         if (on_path * 4 > tiles) h->par_stream = true; else if (on_path * 16 < tiles) h->par_stream = false;
@@ -2885,19 +2906,18 @@ int process_batch(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* 
     if (h->prof) h->prof_records += n;
     if (h->cfg.flags & ECB_F_VERIFY) {                  // belt and braces: the grouping is exact by construction (Slot), this re-derives it
         u64 bad = 0, nl = 0;
-        rc = verify_batch(h, d_rid, d_loc, d_hf, n, h->prev_rid, &bad, &nl, tw);
-        if (rc != ECB_OK) return rc;
-        h->n_mismatch += bad;
+        RCCHK(verify_batch(h, d_rid, d_loc, d_hf, n, h->run.prev_rid, &bad, &nl, tw));
+        h->run.n_mismatch += bad;
         if (bad) return fail(h, ECB_ERR_VERIFY, "exactness pass: %llu read(s) of this batch sit in an EC whose key is not their target set", (unsigned long long)bad);
     }
     if (hinted) {
         last_rid = h->hctr.last_rid;
         reads_after = (u64)(u32)(last_rid + 1u);
-        if (reads_after < h->n_reads) return fail(h, ECB_ERR_CONTRACT, "read_id went backwards across pushes");
+        if (reads_after < h->run.n_reads) return fail(h, ECB_ERR_CONTRACT, "read_id went backwards across pushes");
     }
-    h->prev_rid = last_rid;
-    h->n_reads = reads_after;
-    h->records_pushed += n;
+    h->run.prev_rid = last_rid;
+    h->run.n_reads = reads_after;
+    h->run.records_pushed += n;
     return ECB_OK;
 }
 
@@ -2919,17 +2939,16 @@ int ensure_staging(ecb_handle* h, u64 need) {
 
 // send carry[0..nc) ++ src[0..m) as one batch
 int stage_and_process(ecb_handle* h, const u32* rid, const u32* loc, const u32* hf, const int* pos, u64 m) {
-    const u64 nc = h->c_rid.size();
+    const u64 nc = h->run.c_rid.size();
     const u64 n = nc + m;
     if (!n) return ECB_OK;
-    int rc = ensure_staging(h, n);
-    if (rc != ECB_OK) return rc;
+    RCCHK(ensure_staging(h, n));
     const bool rg = (h->cfg.flags & ECB_F_RANGES) != 0;
     if (nc) {
-        HIPCHK(h, hipMemcpyAsync(h->st_rid, h->c_rid.data(), nc * 4, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->st_loc, h->c_loc.data(), nc * 4, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->st_hf, h->c_hf.data(), nc * 4, hipMemcpyHostToDevice, h->stream));
-        if (rg) HIPCHK(h, hipMemcpyAsync(h->st_pos, h->c_pos.data(), nc * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->st_rid, h->run.c_rid.data(), nc * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->st_loc, h->run.c_loc.data(), nc * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->st_hf, h->run.c_hf.data(), nc * 4, hipMemcpyHostToDevice, h->stream));
+        if (rg) HIPCHK(h, hipMemcpyAsync(h->st_pos, h->run.c_pos.data(), nc * 4, hipMemcpyHostToDevice, h->stream));
     }
     if (m) {
         HIPCHK(h, hipMemcpyAsync(h->st_rid + nc, rid, m * 4, hipMemcpyHostToDevice, h->stream));
@@ -2938,13 +2957,8 @@ int stage_and_process(ecb_handle* h, const u32* rid, const u32* loc, const u32* 
         if (rg) HIPCHK(h, hipMemcpyAsync(h->st_pos + nc, pos, m * 4, hipMemcpyHostToDevice, h->stream));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));   // the carry vectors may be rewritten by the caller next
-    h->c_rid.clear(); h->c_loc.clear(); h->c_hf.clear(); h->c_pos.clear();
+    h->run.c_rid.clear(); h->run.c_loc.clear(); h->run.c_hf.clear(); h->run.c_pos.clear();
     return process_batch(h, h->st_rid, h->st_loc, h->st_hf, rg ? h->st_pos : nullptr, n);
-}
-
-void free_results(ecb_handle* h) {   // result buffers live in the pool: nothing to free, just forget them
-    h->list = h->order = h->rank_of_slot = h->indptr = nullptr;
-    h->indices = h->data = h->counts = nullptr;
 }
 
 // exclusive scan of u32 values, queued on the handle's stream; the sum (64 bits) is left in *d_total on the device
@@ -2959,8 +2973,7 @@ int excl_scan_dev(ecb_handle* h, const u32* in, u64 n, u32* out, u64* d_total, u
 int excl_scan(ecb_handle* h, const u32* in, u64 n, u32* out, u64* total) {
     u64* d_tot = nullptr;
     POOL(h, P_TOTALS, d_tot, 8);
-    int rc = excl_scan_dev(h, in, n, out, d_tot + 7);
-    if (rc != ECB_OK) return rc;
+    RCCHK(excl_scan_dev(h, in, n, out, d_tot + 7));
     HIPCHK(h, hipMemcpyAsync(total, d_tot + 7, sizeof(u64), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return ECB_OK;
@@ -3024,38 +3037,37 @@ int handle_sort(ecb_handle* h, SortBufs& b, u64 n, u64 bit_mask = ~0ull) {
     u64* tot = nullptr;
     POOL(h, P_RS_HIST, sc.hist, rs_words(n)); POOL(h, P_RS_OFFS, sc.offs, RS_AUX_WORDS); POOL(h, P_TOTALS, tot, 8);
     sc.d_word = tot + 6;
-    const hipError_t e = radix_sort_pairs64(h->stream, b, n, sc, bit_mask);
-    if (e != hipSuccess) return fail(h, ECB_ERR_HIP, "radix sort: %s", hipGetErrorString(e));
+    HIPCHK_AS(h, "radix sort: ", radix_sort_pairs64(h->stream, b, n, sc, bit_mask));
     return ECB_OK;
 }
 // ... and its runs of equal keys: flag[i] = 1 where one starts, pos = the exclusive scan of the flags, *n_runs their number (one wait)
 int sorted_runs(ecb_handle* h, SortBufs& b, u64 n, u32* flag, u32* pos, u64* n_runs) {
-    const int rc = handle_sort(h, b, n);
-    if (rc != ECB_OK) return rc;
+    RCCHK(handle_sort(h, b, n));
     k_run_heads<<<nblk(n, TPB), TPB, 0, h->stream>>>(b.keys(), n, flag);
     return excl_scan(h, flag, n, pos, n_runs);
 }
 
 int ensure_slot_ranks(ecb_handle* h, u64 E) {
-    if (h->rank_of_slot) return ECB_OK;
-    POOL(h, P_RANK, h->rank_of_slot, h->cap);
-    k_slot_ranks<<<nblk(E, TPB), TPB, 0, h->stream>>>(h->order, E, h->rank_of_slot);
+    if (h->run.csr.rank_of_slot) return ECB_OK;                     // (null: not made yet)
+    POOL(h, P_RANK, h->run.csr.rank_of_slot, h->cap);
+    k_slot_ranks<<<nblk(E, TPB), TPB, 0, h->stream>>>(h->run.csr.order, E, h->run.csr.rank_of_slot);
     HIPCHK(h, hipGetLastError());
     return ECB_OK;
 }
 
 // reads per EC / first appearance, from read_slot[0, n_reads) (once, when the stream is closed).  Only queues kernels:
-// the totals and the work list of k_count_bins stay on the device.
-int ensure_counts(ecb_handle* h, const CompactSink* sink = nullptr) {
-    if (h->counted) return ECB_OK;
-    const u64 R = h->n_reads;
+// the totals and the work list of k_count_bins stay on the device.  *listed (finalize's): k_count_bins filled the caller's sink as it went.
+int ensure_counts(ecb_handle* h, const CompactSink* sink = nullptr, bool* listed = nullptr) {
+    if (h->counted()) return ECB_OK;
+    const u64 R = h->run.n_reads;
     CompactSink own{nullptr, 0, nullptr, nullptr, 0, nullptr};
-    if (R && !sink && !h->adopted && h->n_ecs()) {         // (a table export follows: it wants the list of occupied slots, see k_count_bins)
+    if (R && !sink && h->run.origin != Origin::ADOPTED && h->n_ecs()) {         // (a table export follows: it wants the list of occupied slots, see k_count_bins)
+        u32* list = nullptr;
         u64* d_n = nullptr;
-        POOL(h, P_LIST, h->list, h->n_ecs());
+        POOL(h, P_LIST, list, h->n_ecs());
         POOL(h, P_CNT, d_n, 1);
         HIPCHK(h, hipMemsetAsync(d_n, 0, sizeof(u64), h->stream));
-        own = CompactSink{h->list, h->n_ecs(), d_n, nullptr, 0, nullptr};
+        own = CompactSink{list, h->n_ecs(), d_n, nullptr, 0, nullptr};
         sink = &own;
     }
     if (R) {
@@ -3087,8 +3099,7 @@ int ensure_counts(ecb_handle* h, const CompactSink* sink = nullptr) {
         POOL(h, P_TOTALS, d_tot, 8);
         k_part_hist<<<G, TPB_PART, nb * 4, h->stream>>>(h->read_slot, R, nb, bb, hist);
         d_tot += 6;                                 // ([0..3] are finalize's, which may run this with its own totals already zeroed; [7] is excl_scan's)
-        int rc = excl_scan_dev(h, hist, (u64)nb * G, offs, d_tot);
-        if (rc != ECB_OK) return rc;
+        RCCHK(excl_scan_dev(h, hist, (u64)nb * G, offs, d_tot));
         if (nb <= STAGE_MAX_BUCKETS) {
             if (!h->scatter_attr_set) {             // (per handle = per device: more than 64 KB of dynamic LDS has to be asked for)
                 HIPCHK(h, hipFuncSetAttribute((const void*)k_part_scatter_staged, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -3106,58 +3117,53 @@ int ensure_counts(ecb_handle* h, const CompactSink* sink = nullptr) {
         u32* d_nwork = reinterpret_cast<u32*>(d_work + max_work);
         k_build_work<<<1, 1024, 0, h->stream>>>(offs, G, d_tot, nb, piece, d_work, max_work, d_nwork);
         k_count_bins<<<max_work, TPB_COUNT, 4u << bb, h->stream>>>(pairs, d_work, d_nwork, bb, h->table, sink ? *sink : CompactSink{nullptr, 0, nullptr, nullptr, 0, nullptr});
-        if (sink == &own) { h->list_counted = true; h->d_list_n = own.n_list; }
-        else if (sink) h->list_from_counts = true;
+        if (sink == &own) h->run.d_list_n = own.n_list;
+        else if (sink && listed) *listed = true;
         HIPCHK(h, hipGetLastError());
     }
-    h->counted = true;
+    h->run.stage = Stage::COUNTED;
     return ECB_OK;
 }
 
-// occupied slots -> h->list (+ first-appearance bitmap and (first, key length) per entry for finalize); the number found
+// occupied slots -> pool[P_LIST] (+ first-appearance bitmap and (first, key length) per entry for finalize); the number found
 // is left in *d_n on the device
 int compact_table_dev(ecb_handle* h, u64* d_n, u32* bitmap = nullptr, u64 n_bits = 0, uint2* list_fn = nullptr) {
+    u32* list = nullptr;
     HIPCHK(h, hipMemsetAsync(d_n, 0, sizeof(u64), h->stream));
-    POOL(h, P_LIST, h->list, h->n_ecs());
-    k_compact<<<(unsigned)std::min<u64>(2048, (h->cap + 4 * TPB_COMPACT - 1) / (4 * TPB_COMPACT)), TPB_COMPACT, 0, h->stream>>>(h->table, h->cap, h->list, std::max<u64>(h->n_ecs(), 1), d_n, bitmap, n_bits, list_fn);
+    POOL(h, P_LIST, list, h->n_ecs());
+    k_compact<<<(unsigned)std::min<u64>(2048, (h->cap + 4 * TPB_COMPACT - 1) / (4 * TPB_COMPACT)), TPB_COMPACT, 0, h->stream>>>(h->table, h->cap, list, std::max<u64>(h->n_ecs(), 1), d_n, bitmap, n_bits, list_fn);
     return ECB_OK;
 }
 int compact_table(ecb_handle* h) {
-    u64* d_n = nullptr;
-    int rc = ECB_OK;
-    if (h->list_counted) {                               // the counting pass listed them: no scan of the table
-        POOL(h, P_LIST, h->list, h->n_ecs());            // (the pool's buffer, contents and all)
-        d_n = h->d_list_n;
-    } else {
+    u64* d_n = h->run.d_list_n;                          // the counting pass listed them: no scan of the table
+    if (!d_n) {
         POOL(h, P_CNT, d_n, 1);
-        rc = compact_table_dev(h, d_n);
-        if (rc != ECB_OK) return rc;
+        RCCHK(compact_table_dev(h, d_n));
     }
-    HIPCHK(h, hipMemcpyAsync(&h->n_list, d_n, sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&h->run.n_list, d_n, sizeof(u64), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->n_list != h->n_ecs()) return fail(h, ECB_ERR_HIP, "internal: %llu occupied slots but %llu ECs created",
-                                             (unsigned long long)h->n_list, (unsigned long long)h->n_ecs());
+    if (h->run.n_list != h->n_ecs()) return fail(h, ECB_ERR_HIP, "internal: %llu occupied slots but %llu ECs created",
+                                             (unsigned long long)h->run.n_list, (unsigned long long)h->n_ecs());
     return ECB_OK;
 }
 
 // distinct (EC, cell, file) triples of this handle's reads: sort the per-read keys (EC id << 32 | meta), run-length encode.
 // ec_of_slot maps a table slot to the EC id to use (the handle's own ranks, or global ranks in a multi-GPU run).
 int ms_reduce(ecb_handle* h, const u32* ec_of_slot) {
-    const u64 R = h->n_reads;
-    if (h->meta_hi < R) return fail(h, ECB_ERR_STATE, "ecb_push_cells covered %llu of %llu reads",
-                                    (unsigned long long)h->meta_hi, (unsigned long long)R);
+    const u64 R = h->run.n_reads;
+    if (h->run.meta_hi < R) return fail(h, ECB_ERR_STATE, "ecb_push_cells covered %llu of %llu reads",
+                                    (unsigned long long)h->run.meta_hi, (unsigned long long)R);
     u64 *keys = nullptr, *keys2 = nullptr; u32 *vals = nullptr, *vals2 = nullptr, *flag = nullptr, *pos = nullptr;
     POOL(h, P_MS_KEYS, keys, R); POOL(h, P_MS_KEYS2, keys2, R); POOL(h, P_MS_VALS, vals, R); POOL(h, P_MS_VALS2, vals2, R);
     POOL(h, P_MS_FLAG, flag, R); POOL(h, P_MS_POS, pos, R);
     k_ms_keys<<<nblk(R, TPB), TPB, 0, h->stream>>>(h->read_slot, ec_of_slot, h->meta, R, keys, vals);
     SortBufs s{{keys, keys2}, {vals, vals2}};
     u64 nt = 0;
-    const int rc = sorted_runs(h, s, R, flag, pos, &nt);
-    if (rc != ECB_OK) return rc;
-    POOL(h, P_MS_OKEY, h->ms_okey, nt); POOL(h, P_MS_OFIRST, h->ms_ofirst, nt); POOL(h, P_MS_OSTART, h->ms_ostart, (u64)nt + 1);
-    k_ms_emit<<<nblk(R, TPB), TPB, 0, h->stream>>>(s.keys(), s.vals(), flag, pos, R, nt, h->ms_okey, h->ms_ofirst, h->ms_ostart);
+    RCCHK(sorted_runs(h, s, R, flag, pos, &nt));
+    POOL(h, P_MS_OKEY, h->run.tri.okey, nt); POOL(h, P_MS_OFIRST, h->run.tri.ofirst, nt); POOL(h, P_MS_OSTART, h->run.tri.ostart, (u64)nt + 1);
+    k_ms_emit<<<nblk(R, TPB), TPB, 0, h->stream>>>(s.keys(), s.vals(), flag, pos, R, nt, h->run.tri.okey, h->run.tri.ofirst, h->run.tri.ostart);
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->n_triples = nt; h->ms_ocount = nullptr;
+    h->run.tri.n = nt; h->run.tri.ocount = nullptr; h->run.triples = Triples::OWN;
     return ECB_OK;
 }
 
@@ -3220,6 +3226,86 @@ __global__ void k_piece_rows(const PieceDesc* P, u32 n_pieces, const uint4* plac
     for (int i = s0; i < s1; ++i) { indices[d0 + (u32)(i - s0)] = sj[i]; data[d0 + (u32)(i - s0)] = sd[i]; }
 }
 
+// ---- what entry points share -----------------------------------------------------------------------------------------------------------
+// the three pushes: a handle, a stream that still takes records, and the records themselves
+int push_refused(ecb_handle* h, size_t n, bool streams_given) {
+    if (!h) return ECB_ERR_ARG;
+    if (!h->can_push()) return fail(h, ECB_ERR_STATE, "push after finalize / table export");
+    if (n && !streams_given) return fail(h, ECB_ERR_ARG, "null tuple stream");
+    return ECB_OK;
+}
+// ... and the two that take device memory (ptr_bits: their pointers, or-ed)
+int device_push_refused(ecb_handle* h, const char* who, uintptr_t ptr_bits) {
+    if (ptr_bits & 15) return fail(h, ECB_ERR_ARG, "device streams must be 16-byte aligned");
+    if (h->open_read()) return fail(h, ECB_ERR_STATE, "%s while a host push has an open read", who);
+    HIPCHK(h, hipSetDevice(h->device));
+    return ECB_OK;
+}
+// ecb_verify_device / ecb_verify_device_tiled: the exactness pass over one batch, as three streams or as tiles (tw: verify_batch)
+int verify_streams(ecb_handle* h, const void* d_rid, const void* d_loc, const void* d_hf, size_t n, u32 tw, u64* n_mismatch, u64* n_long) {
+    if (!n || !d_rid || !d_loc || !d_hf) return fail(h, ECB_ERR_ARG, "null tuple stream");
+    if (((uintptr_t)d_rid | (uintptr_t)d_loc | (uintptr_t)d_hf) & 15) return fail(h, ECB_ERR_ARG, "device streams must be 16-byte aligned");
+    HIPCHK(h, hipSetDevice(h->device));
+    return verify_batch(h, (const u32*)d_rid, (const u32*)d_loc, (const u32*)d_hf, n, 0xFFFFFFFFu, n_mismatch, n_long, tw);
+}
+// ecb_push_cells / ecb_push_cells_device: meta of reads [first_read, first_read + n), from the host or from device memory (`kind`)
+int push_cells(ecb_handle* h, const void* meta, uint64_t first_read, size_t n, hipMemcpyKind kind) {
+    if (!h) return ECB_ERR_ARG;
+    if (!h->multisample()) return fail(h, ECB_ERR_STATE, "handle was created without ECB_F_MULTISAMPLE");
+    if (h->has_result()) return fail(h, ECB_ERR_STATE, "push after finalize");
+    if (!n) return ECB_OK;
+    if (!meta) return fail(h, ECB_ERR_ARG, "null meta");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (first_read >= (1ull << 32) - 1 || (u64)n >= (1ull << 32) - 1 - first_read) return fail(h, ECB_ERR_LIMIT, "more than 2^32-2 reads");
+    const u64 need = first_read + n;
+    RCCHK(ensure_meta(h, need));
+    // (from device memory: ordered on the handle's own stream, behind nothing of the caller's: it must be COMPLETE when this is called -- see
+    //  ecb.h -- and nothing is waited for; from the host: the caller may rewrite its array next)
+    HIPCHK(h, hipMemcpyAsync(h->meta + first_read, meta, n * sizeof(u32), kind, h->stream));
+    if (kind == hipMemcpyHostToDevice) HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->run.meta_hi = std::max<u64>(h->run.meta_hi, need);
+    return ECB_OK;
+}
+// ecb_finalize / ecb_assemble_ranges_device: what neither builds a result from ...
+int refuse_no_ecs(ecb_handle* h, u64 E, u64 valid) {
+    if (E == 0 || valid == 0) return fail(h, ECB_ERR_EMPTY, "no valid alignments: nothing to build (the reference fails here too)");
+    if (E >= (1ull << 31) - 1) return fail(h, ECB_ERR_LIMIT, "more than 2^31-2 equivalence classes");
+    return ECB_OK;
+}
+int refuse_nnz(ecb_handle* h, u64 nnz) {
+    if (nnz >= (1ull << 31)) return fail(h, ECB_ERR_LIMIT, "A has more than 2^31-1 non-zeros");
+    return ECB_OK;
+}
+// ... and the sizes of what they built: one sample, N = the count of every EC (a multisample handle then says what its N is)
+ecb_sizes result_sizes(u64 E, u64 nnz, u64 all, u64 valid, u64 reads) {
+    ecb_sizes s{};
+    s.n_ecs = E; s.nnz_a = nnz; s.n_samples = 1; s.nnz_n = E;
+    s.all_alignments = all; s.valid_alignments = valid; s.n_reads = reads;
+    return s;
+}
+// ecb_export / ecb_export_device: A's three arrays and the counts are copied out on the stream (`kind`: to the host, or within the device);
+// N's other two arrays are trivial -- one column: {0, E} and 0 .. E-1 -- and written where the output lives
+int export_result(ecb_handle* h, void* ia, void* ja, void* da, void* in_, void* jn, void* dn, hipMemcpyKind kind) {
+    HIPCHK(h, hipSetDevice(h->device));
+    const bool on_device = kind == hipMemcpyDeviceToDevice;
+    const u64 E = h->run.sizes.n_ecs, nnz = h->run.sizes.nnz_a;
+    const ecb_handle::Run::Csr& r = h->run.csr;
+    if (ia) HIPCHK(h, hipMemcpyAsync(ia, r.indptr, (E + 1) * 4, kind, h->stream));
+    if (ja) HIPCHK(h, hipMemcpyAsync(ja, r.indices, nnz * 4, kind, h->stream));
+    if (da) HIPCHK(h, hipMemcpyAsync(da, r.data, nnz * 4, kind, h->stream));
+    if (on_device) {
+        if (in_) { const int v[2] = {0, (int)E}; HIPCHK(h, hipMemcpyAsync(in_, v, 8, hipMemcpyHostToDevice, h->stream)); }
+        if (jn) k_iota<<<nblk(E, TPB), TPB, 0, h->stream>>>((u32*)jn, E);
+    }
+    if (dn) HIPCHK(h, hipMemcpyAsync(dn, r.counts, E * 4, kind, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (!on_device) {
+        if (in_) { ((int32_t*)in_)[0] = 0; ((int32_t*)in_)[1] = (int32_t)E; }
+        if (jn) for (u64 i = 0; i < E; ++i) ((int32_t*)jn)[i] = (int32_t)i;
+    }
+    return ECB_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3241,7 +3327,8 @@ int ecb_create(const ecb_config* cfg, ecb_handle** out) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, ECB_ERR_NO_DEVICE, "no HIP device: libecb has no CPU path");
     if (cfg->device < 0 || cfg->device >= ndev) return fail(nullptr, ECB_ERR_ARG, "device %d out of range (%d present)", cfg->device, ndev);
-    std::unique_ptr<ecb_handle> h(new ecb_handle());      // (an early return frees what was built so far)
+    std::unique_ptr<ecb_handle> owner(new ecb_handle());  // (an early return frees what was built so far)
+    ecb_handle* const h = owner.get();
     h->cfg = *cfg;
     h->device = cfg->device;
     if (!h->cfg.ec_capacity) h->cfg.ec_capacity = 1ull << 22;
@@ -3249,26 +3336,28 @@ int ecb_create(const ecb_config* cfg, ecb_handle** out) {
     if (!h->cfg.max_batch_records) h->cfg.max_batch_records = 1ull << 24;
     h->cap = std::max<u64>(next_pow2(h->cfg.ec_capacity), 1024);
     h->arena_cap = std::min<u64>(h->cfg.arena_capacity, 1ull << 32);
-    auto bail = [](const char* what, hipError_t e) { return fail(nullptr, ECB_ERR_HIP, "%s: %s", what, hipGetErrorString(e)); };
-    hipError_t e;
-    if ((e = hipSetDevice(h->device)) != hipSuccess) return bail("hipSetDevice", e);
-    if ((e = hipStreamCreate(&h->stream)) != hipSuccess) return bail("hipStreamCreate", e);
-    if ((e = h->table.alloc(h->cap * sizeof(Slot))) != hipSuccess) return bail("hipMalloc(table)", e);
-    if ((e = h->arena.alloc(h->arena_cap * sizeof(uint2))) != hipSuccess) return bail("hipMalloc(arena)", e);
-    if ((e = h->ctr.alloc(sizeof(Counters))) != hipSuccess) return bail("hipMalloc(counters)", e);
-    if ((e = pin(h->pin_ctr)) != hipSuccess || (e = pin(h->pin_cold)) != hipSuccess || (e = pin(h->pin_out)) != hipSuccess) return bail("hipHostMalloc", e);
-    if ((e = h->d_cold.alloc(sizeof(StreamCold))) != hipSuccess) return bail("hipMalloc(args)", e);
-    hipMemsetAsync(h->table, 0, h->cap * sizeof(Slot), h->stream);
-    hipMemsetAsync(h->arena, 0, h->arena_cap * sizeof(uint2), h->stream);     // stale arena bytes must never look like a key (see ecb_reset)
-    clear_counters(h.get());
+#define CREATECHK(call) HIPCHK_AS(nullptr, "ecb_create: ", call)      // (the text of a handle that is about to go would go with it)
+    CREATECHK(hipSetDevice(h->device));
+    CREATECHK(hipStreamCreate(&h->stream));
+    CREATECHK(h->table.alloc(h->cap * sizeof(Slot)));
+    CREATECHK(h->arena.alloc(h->arena_cap * sizeof(uint2)));
+    CREATECHK(h->ctr.alloc(sizeof(Counters)));
+    CREATECHK(pin(h->pin_ctr));
+    CREATECHK(pin(h->pin_cold));
+    CREATECHK(pin(h->pin_out));
+    CREATECHK(h->d_cold.alloc(sizeof(StreamCold)));
+    CREATECHK(hipMemsetAsync(h->table, 0, h->cap * sizeof(Slot), h->stream));
+    CREATECHK(hipMemsetAsync(h->arena, 0, h->arena_cap * sizeof(uint2), h->stream));     // stale arena bytes must never look like a key (see ecb_reset)
+    if (const int rc = clear_counters(h); rc != ECB_OK) return fail(nullptr, rc, "ecb_create: %s", h->err.c_str());
     if (cfg->flags & ECB_F_RANGES) {
         const u64 ns = (u64)cfg->n_loci * cfg->n_haplotypes;
-        if ((e = h->rng.alloc(ns * sizeof(int2))) != hipSuccess) return bail("hipMalloc(ranges)", e);
+        CREATECHK(h->rng.alloc(ns * sizeof(int2)));
         k_fill_minmax<<<nblk(ns, TPB), TPB, 0, h->stream>>>(h->rng, ns);
     }
     hipEventCreate(&h->ev0); hipEventCreate(&h->ev1);
-    if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return bail("init", e);
-    *out = h.release();
+    CREATECHK(hipStreamSynchronize(h->stream));
+#undef CREATECHK
+    *out = owner.release();
     return ECB_OK;
 }
 
@@ -3282,11 +3371,8 @@ void ecb_destroy(ecb_handle* h) {
 int ecb_verify_device(ecb_handle* h, const void* d_read_id, const void* d_locus, const void* d_hapflag, size_t n,
                       uint64_t* n_mismatch, uint64_t* n_long) {
     if (!h || !n_mismatch || !n_long) return ECB_ERR_ARG;
-    if (!n || !d_read_id || !d_locus || !d_hapflag) return fail(h, ECB_ERR_ARG, "null tuple stream");
-    if (((uintptr_t)d_read_id | (uintptr_t)d_locus | (uintptr_t)d_hapflag) & 15) return fail(h, ECB_ERR_ARG, "device streams must be 16-byte aligned");
-    HIPCHK(h, hipSetDevice(h->device));
     u64 bad = 0, nl = 0;
-    const int rc = verify_batch(h, (const u32*)d_read_id, (const u32*)d_locus, (const u32*)d_hapflag, n, 0xFFFFFFFFu, &bad, &nl);
+    const int rc = verify_streams(h, d_read_id, d_locus, d_hapflag, n, 512u, &bad, &nl);
     *n_mismatch = bad; *n_long = nl;
     return rc;
 }
@@ -3294,9 +3380,8 @@ int ecb_verify_device(ecb_handle* h, const void* d_read_id, const void* d_locus,
 int ecb_reset(ecb_handle* h) {
     if (!h) return ECB_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
-    const u32* occupied = h->finalized ? h->list : nullptr;     // (a finalized handle knows its occupied slots: every one of them, checked)
-    const u64 n_occupied = h->n_list;
-    free_results(h);
+    const u32* occupied = h->has_result() ? h->slot_list() : nullptr;     // (a finalized handle knows its occupied slots: every one of them, checked)
+    const u64 n_occupied = h->run.n_list;
     // The used stretches of the key arena go back to zero: a key pair is only ever compared against bytes that are either
     // zero (no haplotype mask: never equal to a pair) or final, whatever a cache still holds of them.
     if (!h->ctr_synced) sync_counters(h);               // (the cursors; an error the run already reported is not this call's)
@@ -3322,14 +3407,14 @@ int ecb_reset(ecb_handle* h) {
 #endif
     {
         // a sparsely filled table is cleared slot by slot from that list (config 3: 3.7 M of 16.8 M slots, 0.24 of 1 GB)
-        if (h->assembled) {
+        if (h->run.origin == Origin::ASSEMBLED) {
             // (a result assembled from per-range pieces never touched this handle's table)
         } else if (occupied && n_occupied && n_occupied == h->n_ecs() && !h->hctr.err && n_occupied * 3 < h->cap)
             k_clear_slots<<<nblk(n_occupied, TPB), TPB, 0, h->stream>>>(h->table, occupied, n_occupied);
         else
             HIPCHK(h, hipMemsetAsync(h->table, 0, h->cap * sizeof(Slot), h->stream));
     }
-    { int rc_ = clear_counters(h); if (rc_ != ECB_OK) return rc_; }
+    RCCHK(clear_counters(h));
     if (h->wave_arena) HIPCHK(h, hipMemsetAsync(h->wave_arena, 0, 2 * h->wave_arena_n * sizeof(u64), h->stream));
     // (read_slot keeps the last run's slot ids: every read of the next stream has its entry written by k_stream or k_slow
     //  before anything reads it -- k_count, the exports and the exactness pass look at reads [0, n_reads) of a stream that was
@@ -3342,12 +3427,7 @@ int ecb_reset(ecb_handle* h) {
         k_fill_minmax<<<nblk(ns, TPB), TPB, 0, h->stream>>>(h->rng, ns);
     }
     // (no wait: everything above is ordered on the handle's stream, where all later work goes too)
-    h->prev_rid = 0xFFFFFFFFu; h->n_reads = 0; h->records_pushed = 0; h->reads_hi = 0; h->meta_hi = 0; h->n_triples = 0; h->ms_ocount = nullptr; h->ms_adopted = false;
-    h->extra_all = h->extra_valid = h->extra_reads = 0;
-    h->c_rid.clear(); h->c_loc.clear(); h->c_hf.clear(); h->c_pos.clear();
-    h->finalized = false; h->counted = false; h->adopted = false; h->sizes = ecb_sizes{}; h->n_list = 0;
-    h->list_counted = false; h->list_from_counts = false; h->assembled = false;
-    h->n_mismatch = 0; h->ms_filtered = false;
+    h->run = ecb_handle::Run{};
     return ECB_OK;
 }
 
@@ -3360,13 +3440,9 @@ int ecb_hint_reads(ecb_handle* h, uint64_t max_reads) {
 
 int ecb_push_device(ecb_handle* h, const void* d_read_id, const void* d_locus, const void* d_hapflag,
                     const void* d_pos, size_t n) {
-    if (!h) return ECB_ERR_ARG;
-    if (h->finalized || h->counted) return fail(h, ECB_ERR_STATE, "push after finalize / table export");
-    if (n && (!d_read_id || !d_locus || !d_hapflag)) return fail(h, ECB_ERR_ARG, "null tuple stream");
+    RCCHK(push_refused(h, n, d_read_id && d_locus && d_hapflag));
     if ((h->cfg.flags & ECB_F_RANGES) && n && !d_pos) return fail(h, ECB_ERR_ARG, "ECB_F_RANGES needs pos");
-    if (((uintptr_t)d_read_id | (uintptr_t)d_locus | (uintptr_t)d_hapflag | (uintptr_t)d_pos) & 15) return fail(h, ECB_ERR_ARG, "device streams must be 16-byte aligned");
-    if (!h->c_rid.empty()) return fail(h, ECB_ERR_STATE, "ecb_push_device while a host push has an open read");
-    HIPCHK(h, hipSetDevice(h->device));
+    RCCHK(device_push_refused(h, "ecb_push_device", (uintptr_t)d_read_id | (uintptr_t)d_locus | (uintptr_t)d_hapflag | (uintptr_t)d_pos));
     return process_batch(h, (const u32*)d_read_id, (const u32*)d_locus, (const u32*)d_hapflag, (const int*)d_pos, n);
 }
 
@@ -3376,35 +3452,25 @@ int ecb_push_device(ecb_handle* h, const void* d_read_id, const void* d_locus, c
 // reads alone said three streams side by side were the sensitive part -- and measured: it narrows the spread, 7.7 - 8.7 ms against 7.7 - 9.3 on
 // config 3, but does not remove it: DESIGN.md section 6.  Kept as a second way in for callers whose tuples sit in one buffer.)
 int ecb_push_device_tiled(ecb_handle* h, const void* d_tiles, size_t n) {
-    if (!h) return ECB_ERR_ARG;
-    if (h->finalized || h->counted) return fail(h, ECB_ERR_STATE, "push after finalize / table export");
-    if (n && !d_tiles) return fail(h, ECB_ERR_ARG, "null tuple stream");
+    RCCHK(push_refused(h, n, d_tiles != nullptr));
     if (h->cfg.flags & ECB_F_RANGES) return fail(h, ECB_ERR_STATE, "ECB_F_RANGES takes the four streams of ecb_push_device");
-    if ((uintptr_t)d_tiles & 15) return fail(h, ECB_ERR_ARG, "device streams must be 16-byte aligned");
-    if (!h->c_rid.empty()) return fail(h, ECB_ERR_STATE, "ecb_push_device_tiled while a host push has an open read");
-    HIPCHK(h, hipSetDevice(h->device));
+    RCCHK(device_push_refused(h, "ecb_push_device_tiled", (uintptr_t)d_tiles));
     const u32* d = (const u32*)d_tiles;
     return process_batch(h, d, d + 512, d + 1024, nullptr, n, 1536u);
 }
 
 int ecb_verify_device_tiled(ecb_handle* h, const void* d_tiles, size_t n, uint64_t* n_mismatch, uint64_t* n_long_reads) {
     if (!h || !n_mismatch) return ECB_ERR_ARG;
-    if (!n || !d_tiles) return fail(h, ECB_ERR_ARG, "null tuple stream");
-    if ((uintptr_t)d_tiles & 15) return fail(h, ECB_ERR_ARG, "device streams must be 16-byte aligned");
-    HIPCHK(h, hipSetDevice(h->device));
     u64 bad = 0, nl = 0;
     const u32* d = (const u32*)d_tiles;
-    const int rc = verify_batch(h, d, d + 512, d + 1024, n, 0xFFFFFFFFu, &bad, &nl, 1536u);
-    if (rc != ECB_OK) return rc;
+    RCCHK(verify_streams(h, d, d ? d + 512 : d, d ? d + 1024 : d, n, 1536u, &bad, &nl));
     *n_mismatch = bad;
     if (n_long_reads) *n_long_reads = nl;
     return ECB_OK;
 }
 
 int ecb_push(ecb_handle* h, const uint32_t* rid, const uint32_t* loc, const uint32_t* hf, const int32_t* pos, size_t n) {
-    if (!h) return ECB_ERR_ARG;
-    if (h->finalized || h->counted) return fail(h, ECB_ERR_STATE, "push after finalize / table export");
-    if (n && (!rid || !loc || !hf)) return fail(h, ECB_ERR_ARG, "null tuple stream");
+    RCCHK(push_refused(h, n, rid && loc && hf));
     const bool rg = (h->cfg.flags & ECB_F_RANGES) != 0;
     if (rg && n && !pos) return fail(h, ECB_ERR_ARG, "ECB_F_RANGES needs pos");
     HIPCHK(h, hipSetDevice(h->device));
@@ -3417,19 +3483,18 @@ int ecb_push(ecb_handle* h, const uint32_t* rid, const uint32_t* loc, const uint
         const u32 last = r[m - 1];
         u64 cut = m;
         while (cut > 0 && r[cut - 1] == last) --cut;
-        const bool carry_continues = !h->c_rid.empty() && h->c_rid.back() == last;
-        if (cut == 0 && (carry_continues || h->c_rid.empty())) {
-            h->c_rid.insert(h->c_rid.end(), r, r + m);
-            h->c_loc.insert(h->c_loc.end(), l, l + m);
-            h->c_hf.insert(h->c_hf.end(), f, f + m);
-            if (rg) h->c_pos.insert(h->c_pos.end(), ps, ps + m);
+        const bool carry_continues = !h->run.c_rid.empty() && h->run.c_rid.back() == last;
+        if (cut == 0 && (carry_continues || h->run.c_rid.empty())) {
+            h->run.c_rid.insert(h->run.c_rid.end(), r, r + m);
+            h->run.c_loc.insert(h->run.c_loc.end(), l, l + m);
+            h->run.c_hf.insert(h->run.c_hf.end(), f, f + m);
+            if (rg) h->run.c_pos.insert(h->run.c_pos.end(), ps, ps + m);
         } else {
-            int rc = stage_and_process(h, r, l, f, ps, cut);      // carry ++ window[0, cut): whole reads
-            if (rc != ECB_OK) return rc;
-            h->c_rid.assign(r + cut, r + m);
-            h->c_loc.assign(l + cut, l + m);
-            h->c_hf.assign(f + cut, f + m);
-            if (rg) h->c_pos.assign(ps + cut, ps + m);
+            RCCHK(stage_and_process(h, r, l, f, ps, cut));      // carry ++ window[0, cut): whole reads
+            h->run.c_rid.assign(r + cut, r + m);
+            h->run.c_loc.assign(l + cut, l + m);
+            h->run.c_hf.assign(f + cut, f + m);
+            if (rg) h->run.c_pos.assign(ps + cut, ps + m);
         }
         done += m;
     }
@@ -3437,59 +3502,28 @@ int ecb_push(ecb_handle* h, const uint32_t* rid, const uint32_t* loc, const uint
 }
 
 int ecb_push_cells(ecb_handle* h, const uint32_t* meta, uint64_t first_read, size_t n) {
-    if (!h) return ECB_ERR_ARG;
-    if (!(h->cfg.flags & ECB_F_MULTISAMPLE)) return fail(h, ECB_ERR_STATE, "handle was created without ECB_F_MULTISAMPLE");
-    if (h->finalized) return fail(h, ECB_ERR_STATE, "push after finalize");
-    if (!n) return ECB_OK;
-    if (!meta) return fail(h, ECB_ERR_ARG, "null meta");
-    HIPCHK(h, hipSetDevice(h->device));
-    if (first_read >= (1ull << 32) - 1 || (u64)n >= (1ull << 32) - 1 - first_read) return fail(h, ECB_ERR_LIMIT, "more than 2^32-2 reads");
-    const u64 need = first_read + n;
-    const int rc = ensure_meta(h, need);
-    if (rc != ECB_OK) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->meta + first_read, meta, n * sizeof(u32), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->meta_hi = std::max<u64>(h->meta_hi, need);
-    return ECB_OK;
+    return push_cells(h, meta, first_read, n, hipMemcpyHostToDevice);
 }
 
 int ecb_push_cells_device(ecb_handle* h, const void* d_meta, uint64_t first_read, size_t n) {
-    if (!h) return ECB_ERR_ARG;
-    if (!(h->cfg.flags & ECB_F_MULTISAMPLE)) return fail(h, ECB_ERR_STATE, "handle was created without ECB_F_MULTISAMPLE");
-    if (h->finalized) return fail(h, ECB_ERR_STATE, "push after finalize");
-    if (!n) return ECB_OK;
-    if (!d_meta) return fail(h, ECB_ERR_ARG, "null meta");
-    HIPCHK(h, hipSetDevice(h->device));
-    if (first_read >= (1ull << 32) - 1 || (u64)n >= (1ull << 32) - 1 - first_read) return fail(h, ECB_ERR_LIMIT, "more than 2^32-2 reads");
-    const u64 need = first_read + n;
-    const int rc = ensure_meta(h, need);
-    if (rc != ECB_OK) return rc;
-    // (the copy is ordered on the handle's own stream, behind nothing of the caller's: d_meta must be COMPLETE when this is called -- see ecb.h)
-    HIPCHK(h, hipMemcpyAsync(h->meta + first_read, d_meta, n * sizeof(u32), hipMemcpyDeviceToDevice, h->stream));
-    h->meta_hi = std::max<u64>(h->meta_hi, need);
-    return ECB_OK;
+    return push_cells(h, d_meta, first_read, n, hipMemcpyDeviceToDevice);
 }
 
 int ecb_finalize(ecb_handle* h, ecb_sizes* out) {
     if (!h || !out) return ECB_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
-    if (h->assembled) { *out = h->sizes; return ECB_OK; }   // (the result of ecb_assemble_ranges_device: nothing left to rank)
-    if (!h->finalized) {
-        if (!h->c_rid.empty()) {                     // the stream ends here: the carried read is complete
-            int rc = stage_and_process(h, nullptr, nullptr, nullptr, nullptr, 0);
-            if (rc != ECB_OK) return rc;
-        }
-        int rc = h->ctr_synced ? ECB_OK : sync_counters(h);
-        if (rc != ECB_OK) return rc;
+    if (h->run.origin == Origin::ASSEMBLED) { *out = h->run.sizes; return ECB_OK; }   // (the result of ecb_assemble_ranges_device: nothing left to rank)
+    if (!h->has_result()) {
+        if (h->open_read()) RCCHK(stage_and_process(h, nullptr, nullptr, nullptr, nullptr, 0));   // the stream ends here: the carried read is complete
+        if (!h->ctr_synced) RCCHK(sync_counters(h));
     }
     const u64 E = h->n_ecs();
-    const u64 valid = h->hctr.valid + h->extra_valid;
-    if (E == 0 || valid == 0) return fail(h, ECB_ERR_EMPTY, "no valid alignments: nothing to build (the reference fails here too)");
-    if (E >= (1ull << 31) - 1) return fail(h, ECB_ERR_LIMIT, "more than 2^31-2 equivalence classes");
-    free_results(h);
+    const u64 valid = h->hctr.valid + h->run.extra_valid;
+    RCCHK(refuse_no_ecs(h, E, valid));
+    h->run.csr = {};                                 // (rank_of_slot: made on demand, ensure_slot_ranks)
     // Everything below is queued on the stream; the host waits once, at the end, and checks what the device counted.
     // rank by first appearance: bitmap over read indices (marked while the table is compacted), popcount prefix
-    const u64 total_reads = h->n_reads + h->extra_reads;
+    const u64 total_reads = h->run.n_reads + h->run.extra_reads;
     const u64 words = bitmap_words(total_reads), lines = words / BM_LINE;
     const u64 nnz_max = std::min<u64>(E * INL + arena_used(h), (1ull << 32) - 1);     // every key pair there can be
     u32 *bitmap = nullptr, *wpop = nullptr, *wprefix = nullptr, *ord2_raw = nullptr;
@@ -3498,83 +3532,68 @@ int ecb_finalize(ecb_handle* h, ecb_sizes* out) {
     POOL(h, P_BITMAP, bitmap, words); POOL(h, P_WPOP, wpop, lines); POOL(h, P_WPREFIX, wprefix, lines);
     POOL(h, P_ROWLEN, ord2_raw, 2 * E); POOL(h, P_LISTFN, list_fn, E);
     uint2* ord2 = reinterpret_cast<uint2*>(ord2_raw);           // (slot, row length) by rank
-    POOL(h, P_ORDER, h->order, E);
-    h->rank_of_slot = nullptr;                       // (made on demand: ensure_slot_ranks)
-    POOL(h, P_INDPTR, h->indptr, E + 1); POOL(h, P_COUNTS, h->counts, E);
-    POOL(h, P_INDICES, h->indices, nnz_max); POOL(h, P_DATA, h->data, nnz_max);
+    POOL(h, P_ORDER, h->run.csr.order, E);
+    POOL(h, P_INDPTR, h->run.csr.indptr, E + 1); POOL(h, P_COUNTS, h->run.csr.counts, E);
+    POOL(h, P_INDICES, h->run.csr.indices, nnz_max); POOL(h, P_DATA, h->run.csr.data, nnz_max);
     POOL(h, P_TOTALS, d_tot, 8);
     u32* big = nullptr;
     POOL(h, P_MS_X, big, E);
     u32* d_nbig = reinterpret_cast<u32*>(d_tot + 3);
     HIPCHK(h, hipMemsetAsync(bitmap, 0, words * 4, h->stream));
     HIPCHK(h, hipMemsetAsync(d_tot, 0, 8 * sizeof(u64), h->stream));
-    int rc = ECB_OK;
-    h->list_from_counts = false;
-    if (!h->finalized && !h->counted && h->n_reads) {  // the usual case: the counting pass lists the occupied slots as it goes
-        POOL(h, P_LIST, h->list, E);
-        const CompactSink sink{h->list, E, d_tot, bitmap, total_reads, list_fn};
-        rc = ensure_counts(h, &sink);
-        if (rc != ECB_OK) return rc;
-    } else if (!h->finalized) {
-        rc = ensure_counts(h);
-        if (rc != ECB_OK) return rc;
+    bool listed = false;
+    if (h->can_push() && h->run.n_reads) {             // the usual case: the counting pass lists the occupied slots as it goes
+        u32* list = nullptr;
+        POOL(h, P_LIST, list, E);
+        const CompactSink sink{list, E, d_tot, bitmap, total_reads, list_fn};
+        RCCHK(ensure_counts(h, &sink, &listed));
+    } else if (!h->has_result()) {
+        RCCHK(ensure_counts(h));
     }
-    if (!h->list_from_counts) {                        // (counts were made earlier -- a table export, a merge -- or there were none to make)
-        if (!h->finalized && h->list_counted) {        // ... and the list with them (a merged key range): no scan of the table
-            POOL(h, P_LIST, h->list, E);               // (the pool's buffer, contents and all)
-            k_list_fn<<<nblk(E, TPB), TPB, 0, h->stream>>>(h->table, h->list, E, h->d_list_n, d_tot, bitmap, total_reads, list_fn);
-        } else {
-            rc = compact_table_dev(h, d_tot, bitmap, total_reads, list_fn);
-            if (rc != ECB_OK) return rc;
-        }
+    if (!listed) {                                     // (counts were made earlier -- a table export, a merge -- or there were none to make)
+        if (!h->has_result() && h->run.d_list_n)       // ... and the list with them (a merged key range): no scan of the table
+            k_list_fn<<<nblk(E, TPB), TPB, 0, h->stream>>>(h->table, h->slot_list(), E, h->run.d_list_n, d_tot, bitmap, total_reads, list_fn);
+        else
+            RCCHK(compact_table_dev(h, d_tot, bitmap, total_reads, list_fn));
     }
     k_popc<<<nblk(lines, TPB), TPB, 0, h->stream>>>(bitmap, lines, wpop);
-    rc = excl_scan_dev(h, wpop, lines, wprefix, d_tot + 1);
-    if (rc != ECB_OK) return rc;
-    k_rank<<<nblk(E, TPB), TPB, 0, h->stream>>>(h->list, list_fn, E, total_reads, bitmap, wprefix, ord2);
-    rc = excl_scan_dev(h, ord2_raw + 1, E, h->indptr, d_tot + 2, 2, h->indptr + E);
-    if (rc != ECB_OK) return rc;
-    k_emit_small<<<nblk(E, TPB), TPB, 0, h->stream>>>(h->table, ord2, h->order, E, h->arena, h->indptr, h->indices, h->data,
-                                                       h->counts, h->cfg.n_loci, h->cfg.n_haplotypes, big, d_nbig, h->ctr);
+    RCCHK(excl_scan_dev(h, wpop, lines, wprefix, d_tot + 1));
+    k_rank<<<nblk(E, TPB), TPB, 0, h->stream>>>(h->slot_list(), list_fn, E, total_reads, bitmap, wprefix, ord2);
+    RCCHK(excl_scan_dev(h, ord2_raw + 1, E, h->run.csr.indptr, d_tot + 2, 2, h->run.csr.indptr + E));
+    k_emit_small<<<nblk(E, TPB), TPB, 0, h->stream>>>(h->table, ord2, h->run.csr.order, E, h->arena, h->run.csr.indptr, h->run.csr.indices, h->run.csr.data,
+                                                       h->run.csr.counts, h->cfg.n_loci, h->cfg.n_haplotypes, big, d_nbig, h->ctr);
     // long rows, one wave each: a fixed launch that walks the queue (its length stays on the device)
-    k_emit_big<<<(unsigned)std::min<u64>(nblk(E * 64, TPB), 2048), TPB, 0, h->stream>>>(h->table, h->order, big, d_nbig, h->arena, h->indptr,
-                                                                                       h->indices, h->data, h->cfg.n_loci, h->cfg.n_haplotypes, h->ctr);
+    k_emit_big<<<(unsigned)std::min<u64>(nblk(E * 64, TPB), 2048), TPB, 0, h->stream>>>(h->table, h->run.csr.order, big, d_nbig, h->arena, h->run.csr.indptr,
+                                                                                       h->run.csr.indices, h->run.csr.data, h->cfg.n_loci, h->cfg.n_haplotypes, h->ctr);
     u64* const tot = h->pin_out->tot;
     HIPCHK(h, hipMemcpyAsync(tot, d_tot, 4 * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
-    rc = sync_counters(h);                           // the one wait
-    if (rc != ECB_OK) return rc;
-    h->n_list = tot[0];
+    RCCHK(sync_counters(h));                           // the one wait
+    h->run.n_list = tot[0];
     if (tot[0] != E) return fail(h, ECB_ERR_HIP, "internal: %llu occupied slots but %llu ECs created", (unsigned long long)tot[0], (unsigned long long)E);
     if (tot[1] != E) return fail(h, ECB_ERR_HIP, "internal: %llu distinct first-appearance indices for %llu ECs", (unsigned long long)tot[1], (unsigned long long)E);
-    if (tot[2] >= (1ull << 31)) return fail(h, ECB_ERR_LIMIT, "A has more than 2^31-1 non-zeros");
-    const u64 nnz = tot[2];
-    h->sizes.n_ecs = E; h->sizes.nnz_a = nnz; h->sizes.n_samples = 1; h->sizes.nnz_n = E;
-    if (h->cfg.flags & ECB_F_MULTISAMPLE) {
-        if (h->adopted) {                            // multi-GPU: the triples arrive through ecb_ms_adopt_triples_device
-            h->n_triples = 0; h->sizes.n_samples = 0; h->sizes.nnz_n = 0;
+    RCCHK(refuse_nnz(h, tot[2]));
+    h->run.sizes = result_sizes(E, tot[2], h->hctr.all + h->run.extra_all, valid, total_reads);
+    if (h->multisample()) {
+        if (h->run.origin == Origin::ADOPTED) {                            // multi-GPU: the triples arrive through ecb_ms_adopt_triples_device
+            h->run.tri.n = 0; h->run.sizes.n_samples = 0; h->run.sizes.nnz_n = 0;
         } else {
-            if (h->extra_reads) return fail(h, ECB_ERR_STATE, "multisample across GPUs: adopt the merged ECs (ecb_table_adopt_device), then ecb_ms_adopt_triples_device");
-            rc = ensure_slot_ranks(h, E);
-            if (rc != ECB_OK) return rc;
-            rc = ms_reduce(h, h->rank_of_slot);
-            if (rc != ECB_OK) return rc;
-            h->sizes.n_samples = 0; h->sizes.nnz_n = h->n_triples;
+            if (h->run.extra_reads) return fail(h, ECB_ERR_STATE, "multisample across GPUs: adopt the merged ECs (ecb_table_adopt_device), then ecb_ms_adopt_triples_device");
+            RCCHK(ensure_slot_ranks(h, E));
+            RCCHK(ms_reduce(h, h->run.csr.rank_of_slot));
+            h->run.sizes.n_samples = 0; h->run.sizes.nnz_n = h->run.tri.n;
         }
     }
-    h->sizes.all_alignments = h->hctr.all + h->extra_all;
-    h->sizes.valid_alignments = valid;
-    h->sizes.n_reads = total_reads;
-    h->finalized = true;
-    *out = h->sizes;
+    h->run.stage = Stage::FINAL;
+    *out = h->run.sizes;
     return ECB_OK;
 }
 
 int ecb_export_firsts_device(ecb_handle* h, void* d_firsts) {
     if (!h || !d_firsts) return ECB_ERR_ARG;
-    if (!h->finalized || h->assembled) return fail(h, ECB_ERR_STATE, "first reads are exported from a finalized table");
+    if (!h->has_result() || h->run.origin == Origin::ASSEMBLED) return fail(h, ECB_ERR_STATE, "first reads are exported from a finalized table");
     HIPCHK(h, hipSetDevice(h->device));
-    const u64 E = h->sizes.n_ecs;
-    k_export_firsts<<<nblk(E, TPB), TPB, 0, h->stream>>>(h->table, h->order, E, (u32*)d_firsts);
+    const u64 E = h->run.sizes.n_ecs;
+    k_export_firsts<<<nblk(E, TPB), TPB, 0, h->stream>>>(h->table, h->run.csr.order, E, (u32*)d_firsts);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return ECB_OK;
 }
@@ -3584,7 +3603,7 @@ int ecb_assemble_ranges_device(ecb_handle* h, uint32_t n_pieces, const void* con
                                const uint64_t* n_ecs, const uint64_t* nnz, uint64_t total_reads, uint64_t all_alignments,
                                uint64_t valid_alignments, ecb_sizes* out) {
     if (!h || !out) return ECB_ERR_ARG;
-    if (h->finalized || h->adopted || h->n_reads || !h->c_rid.empty() || h->n_ecs()) return fail(h, ECB_ERR_STATE, "assembling needs an empty handle");
+    if (h->has_result() || h->run.origin == Origin::ADOPTED || !h->holds_nothing()) return fail(h, ECB_ERR_STATE, "assembling needs an empty handle");
     if (n_pieces && (!d_indptr || !d_indices || !d_data || !d_counts || !d_firsts || !n_ecs || !nnz)) return fail(h, ECB_ERR_ARG, "null piece lists");
     if (n_pieces > 65535u) return fail(h, ECB_ERR_LIMIT, "at most 65535 pieces");
     u64 E = 0, NNZ = 0;
@@ -3592,26 +3611,24 @@ int ecb_assemble_ranges_device(ecb_handle* h, uint32_t n_pieces, const void* con
         if (n_ecs[q] && (!d_indptr[q] || !d_counts[q] || !d_firsts[q] || (nnz[q] && (!d_indices[q] || !d_data[q])))) return fail(h, ECB_ERR_ARG, "null piece buffers");
         E += n_ecs[q]; NNZ += nnz[q];
     }
-    if (E == 0 || valid_alignments == 0) return fail(h, ECB_ERR_EMPTY, "no valid alignments: nothing to build (the reference fails here too)");
-    if (E >= (1ull << 31) - 1) return fail(h, ECB_ERR_LIMIT, "more than 2^31-2 equivalence classes");
-    if (NNZ >= (1ull << 31)) return fail(h, ECB_ERR_LIMIT, "A has more than 2^31-1 non-zeros");
+    RCCHK(refuse_no_ecs(h, E, valid_alignments));
+    RCCHK(refuse_nnz(h, NNZ));
     if (total_reads >= (1ull << 32) - 1) return fail(h, ECB_ERR_LIMIT, "more than 2^32-2 reads in total");
     HIPCHK(h, hipSetDevice(h->device));
-    free_results(h);
+    h->run.csr = {};
     const u64 words = bitmap_words(total_reads), lines = words / BM_LINE;
     u32 *bitmap = nullptr, *wpop = nullptr, *wprefix = nullptr, *place_raw = nullptr;
     u64* d_tot = nullptr;
     POOL(h, P_BITMAP, bitmap, words); POOL(h, P_WPOP, wpop, lines); POOL(h, P_WPREFIX, wprefix, lines);
     POOL(h, P_ROWLEN, place_raw, 4 * E);
     uint4* place = reinterpret_cast<uint4*>(place_raw);         // {EC within its piece + 1, row length, count, piece} by rank
-    POOL(h, P_INDPTR, h->indptr, E + 1); POOL(h, P_COUNTS, h->counts, E);
-    POOL(h, P_INDICES, h->indices, std::max<u64>(NNZ, 1)); POOL(h, P_DATA, h->data, std::max<u64>(NNZ, 1));
+    POOL(h, P_INDPTR, h->run.csr.indptr, E + 1); POOL(h, P_COUNTS, h->run.csr.counts, E);
+    POOL(h, P_INDICES, h->run.csr.indices, std::max<u64>(NNZ, 1)); POOL(h, P_DATA, h->run.csr.data, std::max<u64>(NNZ, 1));
     POOL(h, P_TOTALS, d_tot, 8);
     HIPCHK(h, hipMemsetAsync(bitmap, 0, words * 4, h->stream));
     HIPCHK(h, hipMemsetAsync(d_tot, 0, 8 * sizeof(u64), h->stream));
     HIPCHK(h, hipMemsetAsync(place_raw, 0, E * 16, h->stream));
-    int rc = clear_counters(h);
-    if (rc != ECB_OK) return rc;
+    RCCHK(clear_counters(h));
     std::vector<PieceDesc> desc;
     u64 most = 0;
     for (u32 q = 0, at = 0; q < n_pieces; ++q) {
@@ -3627,60 +3644,38 @@ int ecb_assemble_ranges_device(ecb_handle* h, uint32_t n_pieces, const void* con
     const dim3 grid((unsigned)nblk(most, TPB), (unsigned)desc.size());
     k_mark_bits<<<grid, TPB, 0, h->stream>>>(d_desc, total_reads, bitmap, h->ctr);
     k_popc<<<nblk(lines, TPB), TPB, 0, h->stream>>>(bitmap, lines, wpop);
-    rc = excl_scan_dev(h, wpop, lines, wprefix, d_tot + 1);
-    if (rc != ECB_OK) return rc;
+    RCCHK(excl_scan_dev(h, wpop, lines, wprefix, d_tot + 1));
     k_piece_place<<<grid, TPB, 0, h->stream>>>(d_desc, E, total_reads, bitmap, wprefix, place, h->ctr);
-    rc = excl_scan_dev(h, place_raw + 1, E, h->indptr, d_tot + 2, 4, h->indptr + E);
-    if (rc != ECB_OK) return rc;
-    k_piece_rows<<<nblk(E, TPB), TPB, 0, h->stream>>>(d_desc, (u32)desc.size(), place, E, h->indptr, h->indices, h->data, h->counts);
+    RCCHK(excl_scan_dev(h, place_raw + 1, E, h->run.csr.indptr, d_tot + 2, 4, h->run.csr.indptr + E));
+    k_piece_rows<<<nblk(E, TPB), TPB, 0, h->stream>>>(d_desc, (u32)desc.size(), place, E, h->run.csr.indptr, h->run.csr.indices, h->run.csr.data, h->run.csr.counts);
     u64 tot[8];
     HIPCHK(h, hipMemcpyAsync(tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, h->stream));
     h->ctr_synced = false;
-    rc = sync_counters(h);                                   // (waits)
+    const int rc = sync_counters(h);                         // (waits)
     if (rc == ECB_ERR_CONTRACT) return fail(h, rc, "a piece is malformed: a first read beyond the run's reads, or row offsets that are not its own");
-    if (rc != ECB_OK) return rc;
+    RCCHK(rc);
     if (tot[1] != E) return fail(h, ECB_ERR_CONTRACT, "the pieces hold %llu ECs but %llu distinct first reads: ranges overlap or a first read is missing",
                                  (unsigned long long)E, (unsigned long long)tot[1]);
     if (tot[2] != NNZ) return fail(h, ECB_ERR_HIP, "internal: %llu non-zeros placed, %llu received", (unsigned long long)tot[2], (unsigned long long)NNZ);
-    h->sizes = ecb_sizes{};
-    h->sizes.n_ecs = E; h->sizes.nnz_a = NNZ; h->sizes.n_samples = 1; h->sizes.nnz_n = E;
-    if (h->cfg.flags & ECB_F_MULTISAMPLE) { h->sizes.n_samples = 0; h->sizes.nnz_n = 0; h->n_triples = 0; h->ms_adopted = false; }   // (N comes with the shards' triples: ecb_ms_adopt_triples_device)
-    h->sizes.all_alignments = all_alignments; h->sizes.valid_alignments = valid_alignments; h->sizes.n_reads = total_reads;
-    h->finalized = true; h->assembled = true; h->counted = true;
-    *out = h->sizes;
+    h->run.sizes = result_sizes(E, NNZ, all_alignments, valid_alignments, total_reads);
+    if (h->multisample()) { h->run.sizes.n_samples = 0; h->run.sizes.nnz_n = 0; h->run.tri.n = 0; h->run.triples = Triples::NONE; }   // (N comes with the shards' triples: ecb_ms_adopt_triples_device)
+    h->run.stage = Stage::FINAL; h->run.origin = Origin::ASSEMBLED;
+    *out = h->run.sizes;
     return ECB_OK;
 }
 
 int ecb_export_device(ecb_handle* h, void* ia, void* ja, void* da, void* in_, void* jn, void* dn) {
     if (!h) return ECB_ERR_ARG;
-    if (!h->finalized) return fail(h, ECB_ERR_STATE, "export before finalize");
-    HIPCHK(h, hipSetDevice(h->device));
-    const u64 E = h->sizes.n_ecs, nnz = h->sizes.nnz_a;
-    if (ia) HIPCHK(h, hipMemcpyAsync(ia, h->indptr, (E + 1) * 4, hipMemcpyDeviceToDevice, h->stream));
-    if (ja) HIPCHK(h, hipMemcpyAsync(ja, h->indices, nnz * 4, hipMemcpyDeviceToDevice, h->stream));
-    if (da) HIPCHK(h, hipMemcpyAsync(da, h->data, nnz * 4, hipMemcpyDeviceToDevice, h->stream));
-    if (in_) { const int v[2] = {0, (int)E}; HIPCHK(h, hipMemcpyAsync(in_, v, 8, hipMemcpyHostToDevice, h->stream)); }
-    if (jn) k_iota<<<nblk(E, TPB), TPB, 0, h->stream>>>((u32*)jn, E);
-    if (dn) HIPCHK(h, hipMemcpyAsync(dn, h->counts, E * 4, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return ECB_OK;
+    if (!h->has_result()) return fail(h, ECB_ERR_STATE, "export before finalize");
+    return export_result(h, ia, ja, da, in_, jn, dn, hipMemcpyDeviceToDevice);
 }
 
 int ecb_export(ecb_handle* h, int32_t* ia, int32_t* ja, int32_t* da, int32_t* in_, int32_t* jn, int32_t* dn) {
     if (!h) return ECB_ERR_ARG;
-    if (!h->finalized) return fail(h, ECB_ERR_STATE, "export before finalize");
-    if ((h->cfg.flags & ECB_F_MULTISAMPLE) && (in_ || jn || dn))
+    if (!h->has_result()) return fail(h, ECB_ERR_STATE, "export before finalize");
+    if (h->multisample() && (in_ || jn || dn))
         return fail(h, ECB_ERR_STATE, "multisample: N comes from ecb_export_pairs");
-    HIPCHK(h, hipSetDevice(h->device));
-    const u64 E = h->sizes.n_ecs, nnz = h->sizes.nnz_a;
-    if (ia) HIPCHK(h, hipMemcpyAsync(ia, h->indptr, (E + 1) * 4, hipMemcpyDeviceToHost, h->stream));
-    if (ja) HIPCHK(h, hipMemcpyAsync(ja, h->indices, nnz * 4, hipMemcpyDeviceToHost, h->stream));
-    if (da) HIPCHK(h, hipMemcpyAsync(da, h->data, nnz * 4, hipMemcpyDeviceToHost, h->stream));
-    if (dn) HIPCHK(h, hipMemcpyAsync(dn, h->counts, E * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (in_) { in_[0] = 0; in_[1] = (int32_t)E; }
-    if (jn) for (u64 i = 0; i < E; ++i) jn[i] = (int32_t)i;
-    return ECB_OK;
+    return export_result(h, ia, ja, da, in_, jn, dn, hipMemcpyDeviceToHost);
 }
 
 int ecb_export_ranges(ecb_handle* h, int64_t* out) {
@@ -3712,31 +3707,31 @@ int ecb_export_range_minmax(ecb_handle* h, int32_t* mn, int32_t* mx) {
 
 int ecb_export_pairs(ecb_handle* h, uint32_t* ec, uint32_t* meta, uint32_t* count, uint32_t* first_read) {
     if (!h || !ec || !meta || !count || !first_read) return ECB_ERR_ARG;
-    if (!h->finalized || !(h->cfg.flags & ECB_F_MULTISAMPLE)) return fail(h, ECB_ERR_STATE, "no multisample result");
+    if (!h->has_ms_result()) return fail(h, ECB_ERR_STATE, "no multisample result");
     HIPCHK(h, hipSetDevice(h->device));
-    const u64 nt = h->n_triples;
+    const u64 nt = h->run.tri.n;
     u32* x = nullptr;
     POOL(h, P_MS_X, x, 3 * nt);
-    if ((h->adopted || h->assembled) && !h->ms_adopted) return fail(h, ECB_ERR_STATE, "multisample across GPUs: no triples adopted yet (ecb_ms_adopt_triples_device)");
-    k_ms_split<<<nblk(nt, TPB), TPB, 0, h->stream>>>(h->ms_okey, h->ms_ostart, h->ms_ocount, nt, x, x + nt, x + 2 * nt);
+    if (h->awaits_triples()) return fail(h, ECB_ERR_STATE, "multisample across GPUs: no triples adopted yet (ecb_ms_adopt_triples_device)");
+    k_ms_split<<<nblk(nt, TPB), TPB, 0, h->stream>>>(h->run.tri.okey, h->run.tri.ostart, h->run.tri.ocount, nt, x, x + nt, x + 2 * nt);
     HIPCHK(h, hipMemcpyAsync(ec, x, nt * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(meta, x + nt, nt * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(count, x + 2 * nt, nt * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(first_read, h->ms_ofirst, nt * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(first_read, h->run.tri.ofirst, nt * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return ECB_OK;
 }
 
 int ecb_export_read_ec(ecb_handle* h, int32_t* out) {
     if (!h || !out) return ECB_ERR_ARG;
-    if (!h->finalized) return fail(h, ECB_ERR_STATE, "export before finalize");
-    if (h->extra_reads || h->assembled) return fail(h, ECB_ERR_STATE, "per-read EC ids are not kept across a multi-GPU merge");
+    if (!h->has_result()) return fail(h, ECB_ERR_STATE, "export before finalize");
+    if (h->run.extra_reads || h->run.origin == Origin::ASSEMBLED) return fail(h, ECB_ERR_STATE, "per-read EC ids are not kept across a multi-GPU merge");
     HIPCHK(h, hipSetDevice(h->device));
     int* d = nullptr;
-    POOL(h, P_EXPORT, d, h->n_reads);
-    { const int rc_ = ensure_slot_ranks(h, h->sizes.n_ecs); if (rc_ != ECB_OK) return rc_; }
-    k_read_ec<<<nblk(h->n_reads, TPB), TPB, 0, h->stream>>>(h->read_slot, h->n_reads, h->rank_of_slot, d);
-    HIPCHK(h, hipMemcpyAsync(out, d, h->n_reads * 4, hipMemcpyDeviceToHost, h->stream));
+    POOL(h, P_EXPORT, d, h->run.n_reads);
+    RCCHK(ensure_slot_ranks(h, h->run.sizes.n_ecs));
+    k_read_ec<<<nblk(h->run.n_reads, TPB), TPB, 0, h->stream>>>(h->read_slot, h->run.n_reads, h->run.csr.rank_of_slot, d);
+    HIPCHK(h, hipMemcpyAsync(out, d, h->run.n_reads * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return ECB_OK;
 }
@@ -3744,17 +3739,12 @@ int ecb_export_read_ec(ecb_handle* h, int32_t* out) {
 int ecb_table_sizes(ecb_handle* h, uint64_t* n_entries, uint64_t* n_pairs, uint64_t* n_reads) {
     if (!h) return ECB_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
-    if (!h->c_rid.empty()) {
-        int rc = stage_and_process(h, nullptr, nullptr, nullptr, nullptr, 0);
-        if (rc != ECB_OK) return rc;
-    }
-    int rc = sync_counters(h);
-    if (rc != ECB_OK) return rc;
-    rc = ensure_counts(h);
-    if (rc != ECB_OK) return rc;
+    if (h->open_read()) RCCHK(stage_and_process(h, nullptr, nullptr, nullptr, nullptr, 0));
+    RCCHK(sync_counters(h));
+    RCCHK(ensure_counts(h));
     if (n_entries) *n_entries = h->n_ecs();
     if (n_pairs) *n_pairs = h->n_ecs() * INL + arena_used(h);      // (an upper bound: up to INL pairs per EC sit in its slot)
-    if (n_reads) *n_reads = h->n_reads;
+    if (n_reads) *n_reads = h->run.n_reads;
     return ECB_OK;
 }
 
@@ -3766,8 +3756,8 @@ int ecb_table_export_device(ecb_handle* h, void* d_entries, void* d_pairs, uint6
 int ecb_table_merge_batch_device(ecb_handle* h, uint32_t n_tables, const void* const* d_entries, const uint64_t* n_entries,
                                 const void* const* d_pairs, const uint64_t* n_pairs) {
     if (!h) return ECB_ERR_ARG;
-    if (h->finalized) return fail(h, ECB_ERR_STATE, "merge after finalize");
-    if (h->adopted) return fail(h, ECB_ERR_STATE, "merge into a table that adopted entries");
+    if (h->has_result()) return fail(h, ECB_ERR_STATE, "merge after finalize");
+    if (h->run.origin == Origin::ADOPTED) return fail(h, ECB_ERR_STATE, "merge into a table that adopted entries");
     if (n_tables && (!d_entries || !n_entries || !d_pairs || !n_pairs)) return fail(h, ECB_ERR_ARG, "null table lists");
     u64 total = 0;
     for (u32 t = 0; t < n_tables; ++t) {
@@ -3776,24 +3766,21 @@ int ecb_table_merge_batch_device(ecb_handle* h, uint32_t n_tables, const void* c
     }
     if (!total) return ECB_OK;
     HIPCHK(h, hipSetDevice(h->device));
-    int rc = sync_counters(h);
-    if (rc != ECB_OK) return rc;
-    rc = ensure_counts(h);                       // own reads first: merged counts are added on top
-    if (rc != ECB_OK) return rc;
+    RCCHK(sync_counters(h));
+    RCCHK(ensure_counts(h));                       // own reads first: merged counts are added on top
     // room for every entry being new: one growth up front, then the merges queue up behind each other with one sync at the end
-    while ((h->n_ecs() + total) * 2 > h->cap) { rc = grow_table(h, h->cap * 4); if (rc != ECB_OK) return rc; }
+    while ((h->n_ecs() + total) * 2 > h->cap) { RCCHK(grow_table(h, h->cap * 4)); }
     HIPCHK(h, hipMemsetAsync(&h->ctr->n_queue, 0, sizeof(u64), h->stream));
     // New ECs may join.  The list of occupied slots is carried along when it can be: the table is empty (the handle that merges one
     // key range), or its list is current and has room (a buffer that had to grow would lose what it holds).
     u32* mlist = nullptr;
     const u64 list_need = h->n_ecs() + total;
-    if (h->n_ecs() == 0 || (h->list_counted && h->pool[ecb_handle::P_LIST].bytes >= list_need * sizeof(u32))) {
+    if (h->n_ecs() == 0 || (h->run.d_list_n && h->pool[ecb_handle::P_LIST].bytes >= list_need * sizeof(u32))) {
         const bool fresh = h->n_ecs() == 0;
-        POOL(h, P_LIST, h->list, list_need);
-        if (fresh) { POOL(h, P_CNT, h->d_list_n, 1); HIPCHK(h, hipMemsetAsync(h->d_list_n, 0, sizeof(u64), h->stream)); }
-        mlist = h->list;
-    }
-    h->list_counted = mlist != nullptr;
+        POOL(h, P_LIST, mlist, list_need);
+        if (fresh) { POOL(h, P_CNT, h->run.d_list_n, 1); HIPCHK(h, hipMemsetAsync(h->run.d_list_n, 0, sizeof(u64), h->stream)); }
+    } else
+        h->run.d_list_n = nullptr;
     std::vector<MergeDesc> desc;
     u64 most = 0;
     for (u32 t = 0; t < n_tables; ++t)
@@ -3804,9 +3791,8 @@ int ecb_table_merge_batch_device(ecb_handle* h, uint32_t n_tables, const void* c
     HIPCHK(h, hipMemcpyAsync(d_desc, desc.data(), desc.size() * sizeof(MergeDesc), hipMemcpyHostToDevice, h->stream));
     k_merge<<<dim3((unsigned)nblk(most, MERGE_PER_BLOCK), (unsigned)desc.size()), TPB, 0, h->stream>>>(reinterpret_cast<const MergeDesc*>(d_desc), h->table, h->cap - 1,
                                                                                                         h->arena, h->arena_cap, h->ctr,
-                                                                                                        mlist, list_need, mlist ? h->d_list_n : nullptr);
-    rc = sync_counters(h);
-    if (rc != ECB_OK) return rc;
+                                                                                                        mlist, list_need, h->run.d_list_n);
+    RCCHK(sync_counters(h));
     if (h->hctr.n_queue) return fail(h, ECB_ERR_TABLE_FULL, "internal: merge found no slot in a half-empty table");
     return ECB_OK;
 }
@@ -3832,18 +3818,15 @@ int ecb_table_export_parts_device(ecb_handle* h, void* d_entries, void* d_pairs,
     if (!h || !d_entries || !d_pairs || !entry_offsets || !pair_offsets) return ECB_ERR_ARG;
     if (n_parts == 0 || n_parts > MAX_PARTS) return fail(h, ECB_ERR_LIMIT, "1 .. %u parts", MAX_PARTS);
     HIPCHK(h, hipSetDevice(h->device));
-    int rc = sync_counters(h);
-    if (rc != ECB_OK) return rc;
-    if (read_base + h->n_reads >= (1ull << 32) - 1) return fail(h, ECB_ERR_LIMIT, "more than 2^32-2 reads in total");
-    rc = ensure_counts(h);
-    if (rc != ECB_OK) return rc;
-    rc = compact_table(h);
-    if (rc != ECB_OK) return rc;
+    RCCHK(sync_counters(h));
+    if (read_base + h->run.n_reads >= (1ull << 32) - 1) return fail(h, ECB_ERR_LIMIT, "more than 2^32-2 reads in total");
+    RCCHK(ensure_counts(h));
+    RCCHK(compact_table(h));
     const u64 E = h->n_ecs();
     u64* d_cnt = nullptr;                              // [0, 2P): counts, then cursors; [2P, 3P): first pair of every part
     POOL(h, P_PARTS, d_cnt, 3 * (u64)n_parts);
     HIPCHK(h, hipMemsetAsync(d_cnt, 0, 2 * n_parts * sizeof(u64), h->stream));
-    if (E) k_parts_count<<<nblk(E, PARTS_PER_BLOCK), TPB, 0, h->stream>>>(h->table, h->list, E, n_parts, d_cnt);
+    if (E) k_parts_count<<<nblk(E, PARTS_PER_BLOCK), TPB, 0, h->stream>>>(h->table, h->slot_list(), E, n_parts, d_cnt);
     std::vector<u64> cnt(2 * n_parts), cur(3 * n_parts);
     HIPCHK(h, hipMemcpyAsync(cnt.data(), d_cnt, 2 * n_parts * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -3859,7 +3842,7 @@ int ecb_table_export_parts_device(ecb_handle* h, void* d_entries, void* d_pairs,
         POOL(h, P_BIG, big, 2 * E + 1);
         u32* d_nbig = reinterpret_cast<u32*>(big + 2 * E);
         HIPCHK(h, hipMemsetAsync(d_nbig, 0, sizeof(u64), h->stream));
-        k_parts_export<<<nblk(E, PARTS_PER_BLOCK), TPB, 0, h->stream>>>(h->table, h->list, E, h->arena, n_parts, d_cnt, d_cnt + 2 * n_parts,
+        k_parts_export<<<nblk(E, PARTS_PER_BLOCK), TPB, 0, h->stream>>>(h->table, h->slot_list(), E, h->arena, n_parts, d_cnt, d_cnt + 2 * n_parts,
                                                                    (Entry*)d_entries, (uint2*)d_pairs, (u32)read_base, big, d_nbig);
         u32 n_big = 0;
         HIPCHK(h, hipMemcpyAsync(&n_big, d_nbig, sizeof(u32), hipMemcpyDeviceToHost, h->stream));
@@ -3873,19 +3856,18 @@ int ecb_table_export_parts_device(ecb_handle* h, void* d_entries, void* d_pairs,
 int ecb_table_adopt_batch_device(ecb_handle* h, uint32_t n_tables, const void* const* d_entries, const uint64_t* n_entries,
                                 const void* const* d_pairs, const uint64_t* n_pairs) {
     if (!h) return ECB_ERR_ARG;
-    if (h->finalized) return fail(h, ECB_ERR_STATE, "adopt after finalize");
+    if (h->has_result()) return fail(h, ECB_ERR_STATE, "adopt after finalize");
     if (n_tables && (!d_entries || !n_entries || !d_pairs || !n_pairs)) return fail(h, ECB_ERR_ARG, "null table lists");
     HIPCHK(h, hipSetDevice(h->device));
-    int rc = sync_counters(h);
-    if (rc != ECB_OK) return rc;
-    if (!h->adopted && (h->n_ecs() || h->n_reads || !h->c_rid.empty()))
+    RCCHK(sync_counters(h));
+    if (h->run.origin != Origin::ADOPTED && !h->holds_nothing())
         return fail(h, ECB_ERR_STATE, "adopt needs an empty handle (use ecb_table_merge_device to add to a built table)");
     u64 add_e = 0, add_p = 0;
     for (u32 t = 0; t < n_tables; ++t) {
         if (n_entries[t] && (!d_entries[t] || (n_pairs[t] && !d_pairs[t]))) return fail(h, ECB_ERR_ARG, "null table buffers");
         if (n_entries[t]) { add_e += n_entries[t]; add_p += n_pairs[t]; }
     }
-    h->adopted = true; h->counted = true; h->list_counted = false;
+    h->run.origin = Origin::ADOPTED; h->run.stage = Stage::COUNTED; h->run.d_list_n = nullptr;
     if (!add_e) return ECB_OK;
     u64 have = h->n_ecs(), top = h->hctr.arena_top;
     if (top + add_p > h->arena_cap || top + add_p >= (1ull << 32))
@@ -3915,11 +3897,11 @@ int ecb_table_adopt_device(ecb_handle* h, const void* d_entries, uint64_t n_entr
 
 int ecb_export_ec_keys_device(ecb_handle* h, void* d_keys) {
     if (!h || !d_keys) return ECB_ERR_ARG;
-    if (!h->finalized) return fail(h, ECB_ERR_STATE, "export before finalize");
+    if (!h->has_result()) return fail(h, ECB_ERR_STATE, "export before finalize");
     HIPCHK(h, hipSetDevice(h->device));
-    const u64 E = h->sizes.n_ecs;
-    if (h->assembled) k_row_keys<<<nblk(E, TPB), TPB, 0, h->stream>>>(h->indptr, h->indices, h->data, E, (u64*)d_keys);     // (no table behind an assembled result)
-    else k_export_keys<<<nblk(E, TPB), TPB, 0, h->stream>>>(h->table, h->order, E, (u64*)d_keys);
+    const u64 E = h->run.sizes.n_ecs;
+    if (h->run.origin == Origin::ASSEMBLED) k_row_keys<<<nblk(E, TPB), TPB, 0, h->stream>>>(h->run.csr.indptr, h->run.csr.indices, h->run.csr.data, E, (u64*)d_keys);     // (no table behind an assembled result)
+    else k_export_keys<<<nblk(E, TPB), TPB, 0, h->stream>>>(h->table, h->run.csr.order, E, (u64*)d_keys);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return ECB_OK;
 }
@@ -3927,33 +3909,28 @@ int ecb_export_ec_keys_device(ecb_handle* h, void* d_keys) {
 int ecb_ms_local_triples_device(ecb_handle* h, const void* d_keys, const void* d_indptr_a, const void* d_indices_a, const void* d_data_a,
                                 uint64_t n_ecs, uint64_t read_base, void* d_key, void* d_count, void* d_first, uint64_t* n_triples) {
     if (!h || !n_triples) return ECB_ERR_ARG;
-    if (!(h->cfg.flags & ECB_F_MULTISAMPLE)) return fail(h, ECB_ERR_STATE, "handle was created without ECB_F_MULTISAMPLE");
-    if (h->finalized || h->adopted) return fail(h, ECB_ERR_STATE, "a shard's triples come from the handle its reads were pushed into");
+    if (!h->multisample()) return fail(h, ECB_ERR_STATE, "handle was created without ECB_F_MULTISAMPLE");
+    if (h->has_result() || h->run.origin == Origin::ADOPTED) return fail(h, ECB_ERR_STATE, "a shard's triples come from the handle its reads were pushed into");
     *n_triples = 0;
     HIPCHK(h, hipSetDevice(h->device));
-    if (!h->c_rid.empty()) {                         // the stream ends here: the carried read is complete
-        int rc0 = stage_and_process(h, nullptr, nullptr, nullptr, nullptr, 0);
-        if (rc0 != ECB_OK) return rc0;
-    }
-    if (!h->n_reads) return ECB_OK;
+    if (h->open_read()) RCCHK(stage_and_process(h, nullptr, nullptr, nullptr, nullptr, 0));   // the stream ends here: the carried read is complete
+    if (!h->run.n_reads) return ECB_OK;
     if (!d_keys || !d_indptr_a || !d_indices_a || !d_data_a || !d_key || !d_count || !d_first) return fail(h, ECB_ERR_ARG, "null buffers");
-    if (read_base + h->n_reads >= (1ull << 32) - 1) return fail(h, ECB_ERR_LIMIT, "more than 2^32-2 reads in total");
+    if (read_base + h->run.n_reads >= (1ull << 32) - 1) return fail(h, ECB_ERR_LIMIT, "more than 2^32-2 reads in total");
     HIPCHK(h, hipSetDevice(h->device));
-    int rc = sync_counters(h);
-    if (rc != ECB_OK) return rc;
+    RCCHK(sync_counters(h));
     u32* grank = nullptr;
     POOL(h, P_MS_GRANK, grank, h->cap);
     HIPCHK(h, hipMemsetAsync(grank, 0xFF, h->cap * sizeof(u32), h->stream));
     k_set_global_rank<<<nblk(n_ecs, TPB), TPB, 0, h->stream>>>((const u64*)d_keys, (const int*)d_indptr_a, (const int*)d_indices_a, (const int*)d_data_a,
                                                               n_ecs, h->table, h->cap - 1, h->arena, grank);
-    rc = ms_reduce(h, grank);
-    if (rc != ECB_OK) return rc;
-    const u64 nt = h->n_triples;
+    RCCHK(ms_reduce(h, grank));
+    const u64 nt = h->run.tri.n;
     u64 last = 0;                                     // keys are sorted: an EC id of 0xFFFFFFFF would be the last one
-    HIPCHK(h, hipMemcpyAsync(&last, h->ms_okey + (nt - 1), sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&last, h->run.tri.okey + (nt - 1), sizeof(u64), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if ((last >> 32) == 0xFFFFFFFFull) return fail(h, ECB_ERR_CONTRACT, "a read's EC is missing from the merged EC list");
-    k_ms_out<<<nblk(nt, TPB), TPB, 0, h->stream>>>(h->ms_okey, h->ms_ofirst, h->ms_ostart, nt, (u32)read_base, (u64*)d_key, (u32*)d_count, (u32*)d_first);
+    k_ms_out<<<nblk(nt, TPB), TPB, 0, h->stream>>>(h->run.tri.okey, h->run.tri.ofirst, h->run.tri.ostart, nt, (u32)read_base, (u64*)d_key, (u32*)d_count, (u32*)d_first);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     *n_triples = nt;
     return ECB_OK;
@@ -3962,8 +3939,8 @@ int ecb_ms_local_triples_device(ecb_handle* h, const void* d_keys, const void* d
 int ecb_ms_adopt_triples_device(ecb_handle* h, uint32_t n_tables, const void* const* d_key, const void* const* d_count,
                                 const void* const* d_first, const uint64_t* n, uint64_t* n_triples) {
     if (!h) return ECB_ERR_ARG;
-    if (!(h->cfg.flags & ECB_F_MULTISAMPLE)) return fail(h, ECB_ERR_STATE, "handle was created without ECB_F_MULTISAMPLE");
-    if (!h->finalized || !(h->adopted || h->assembled)) return fail(h, ECB_ERR_STATE, "triples are adopted by the finalized handle that adopted the merged ECs (or assembled their ranges)");
+    if (!h->multisample()) return fail(h, ECB_ERR_STATE, "handle was created without ECB_F_MULTISAMPLE");
+    if (!h->has_result() || !h->entries_from_elsewhere()) return fail(h, ECB_ERR_STATE, "triples are adopted by the finalized handle that adopted the merged ECs (or assembled their ranges)");
     if (n_tables && (!d_key || !d_count || !d_first || !n)) return fail(h, ECB_ERR_ARG, "null lists");
     HIPCHK(h, hipSetDevice(h->device));
     u64 tot = 0;
@@ -3985,32 +3962,32 @@ int ecb_ms_adopt_triples_device(ecb_handle* h, uint32_t n_tables, const void* co
         k_ms_swz_keys<<<nblk(tot, TPB), TPB, 0, h->stream>>>(keys, tot);      // (sorted as (EC, cell, file), like a handle's own triples)
         k_iota<<<nblk(tot, TPB), TPB, 0, h->stream>>>(vals, tot);
         SortBufs s{{keys, keys2}, {vals, vals2}};
-        const int rc = sorted_runs(h, s, tot, flag, pos, &nt);
-        if (rc != ECB_OK) return rc;
-        POOL(h, P_MS_OKEY, h->ms_okey, nt); POOL(h, P_MS_OFIRST, h->ms_ofirst, nt); POOL(h, P_MS_OCOUNT, h->ms_ocount, nt);
-        HIPCHK(h, hipMemsetAsync(h->ms_ocount, 0, (u64)nt * 4, h->stream));
-        HIPCHK(h, hipMemsetAsync(h->ms_ofirst, 0xFF, (u64)nt * 4, h->stream));
-        k_ms_combine<<<nblk(tot, TPB), TPB, 0, h->stream>>>(s.keys(), s.vals(), flag, pos, tot, cin, fin, h->ms_okey, h->ms_ocount, h->ms_ofirst);
+        RCCHK(sorted_runs(h, s, tot, flag, pos, &nt));
+        POOL(h, P_MS_OKEY, h->run.tri.okey, nt); POOL(h, P_MS_OFIRST, h->run.tri.ofirst, nt); POOL(h, P_MS_OCOUNT, h->run.tri.ocount, nt);
+        HIPCHK(h, hipMemsetAsync(h->run.tri.ocount, 0, (u64)nt * 4, h->stream));
+        HIPCHK(h, hipMemsetAsync(h->run.tri.ofirst, 0xFF, (u64)nt * 4, h->stream));
+        k_ms_combine<<<nblk(tot, TPB), TPB, 0, h->stream>>>(s.keys(), s.vals(), flag, pos, tot, cin, fin, h->run.tri.okey, h->run.tri.ocount, h->run.tri.ofirst);
         u64 last = 0;
         HIPCHK(h, hipMemcpyAsync(&last, s.keys() + (tot - 1), sizeof(u64), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        if ((last >> 32) >= h->sizes.n_ecs) return fail(h, ECB_ERR_CONTRACT, "triple with an EC id beyond the merged ECs");
+        if ((last >> 32) >= h->run.sizes.n_ecs) return fail(h, ECB_ERR_CONTRACT, "triple with an EC id beyond the merged ECs");
     }
-    h->n_triples = nt; h->ms_adopted = true;
-    h->sizes.n_samples = 0; h->sizes.nnz_n = nt;
+    h->run.tri.n = nt; h->run.triples = Triples::ADOPTED;
+    h->run.sizes.n_samples = 0; h->run.sizes.nnz_n = nt;
     if (n_triples) *n_triples = nt;
     return ECB_OK;
 }
 
 int ecb_ms_filter(ecb_handle* h, uint32_t n_cells, int64_t minimum_count, ecb_ms_sizes* out) {
     if (!h || !out) return ECB_ERR_ARG;
-    if (!h->finalized || !(h->cfg.flags & ECB_F_MULTISAMPLE)) return fail(h, ECB_ERR_STATE, "no multisample result");
-    if ((h->adopted || h->assembled) && !h->ms_adopted) return fail(h, ECB_ERR_STATE, "multisample across GPUs: no triples adopted yet (ecb_ms_adopt_triples_device)");
+    if (!h->has_ms_result()) return fail(h, ECB_ERR_STATE, "no multisample result");
+    if (h->awaits_triples()) return fail(h, ECB_ERR_STATE, "multisample across GPUs: no triples adopted yet (ecb_ms_adopt_triples_device)");
     if (!n_cells || n_cells > (1u << ECB_CELL_BITS)) return fail(h, ECB_ERR_ARG, "n_cells out of range");
     HIPCHK(h, hipSetDevice(h->device));
-    h->ms_filtered = false;                          // (until this call succeeds: its pool buffers are regrown under the last result)
+    h->run.flt = {};                                 // (until this call succeeds: its pool buffers are regrown under the last result)
+    ecb_handle::Run::Filtered f;
     hipStream_t st = h->stream;
-    const u64 T = h->n_triples, E = h->sizes.n_ecs;
+    const u64 T = h->run.tri.n, E = h->run.sizes.n_ecs;
     const u64 min_count = minimum_count <= 0 ? 1ull : (u64)minimum_count;          // bam_utils_multisample.py:596-597
     if (!T) return fail(h, ECB_ERR_EMPTY, "no (EC, cell) counts: nothing to filter");
     // The triples are sorted by (EC, cell, file) (ms_reduce / ecb_ms_adopt_triples_device).  Everything read-sized below is a
@@ -4022,8 +3999,8 @@ int ecb_ms_filter(ecb_handle* h, uint32_t n_cells, int64_t minimum_count, ecb_ms
     POOL(h, P_MS_FLAG, flag, std::max<u64>(T, n_cells)); POOL(h, P_MS_POS, pos, std::max<u64>(T, n_cells));
     POOL(h, P_MS_KEYS, k0, T); POOL(h, P_MS_KEYS2, k1, T); POOL(h, P_MS_VALS, v0, T); POOL(h, P_MS_VALS2, v1, T);
     u32 *ec = x, *meta = x + T, *cnt = x + 2 * T;
-    k_ms_split<<<nblk(T, TPB), TPB, 0, st>>>(h->ms_okey, h->ms_ostart, h->ms_ocount, T, ec, meta, cnt);
-    const u32* first = h->ms_ofirst;
+    k_ms_split<<<nblk(T, TPB), TPB, 0, st>>>(h->run.tri.okey, h->run.tri.ostart, h->run.tri.ocount, T, ec, meta, cnt);
+    const u32* first = h->run.tri.ofirst;
     std::vector<DevBuf<>> sc;                                              // (cell- and EC-sized scratch: small)
     u64 *total = fresh<u64>(sc, n_cells), *cellkey = fresh<u64>(sc, n_cells);
     u32 *firstfile = fresh<u32>(sc, n_cells), *seg = fresh<u32>(sc, E + 1), *keep_ec = fresh<u32>(sc, E), *new_rank = fresh<u32>(sc, E), *new_cell = fresh<u32>(sc, n_cells);
@@ -4056,10 +4033,9 @@ int ecb_ms_filter(ecb_handle* h, uint32_t n_cells, int64_t minimum_count, ecb_ms
         k_msf2_giant_offer<<<1024, TPB, 0, st>>>(meta, first, seg, giant, giant + max_giant, n_cells, firstfile, gfec, cellkey);
     }
     // 3. cell order: by (first appearance of the EC in the cell's first file, first read), then -- stable -- by that file
-    int rc;
     k_msf2_cellflag<<<nblk(n_cells, TPB), TPB, 0, st>>>(total, n_cells, flag);
     u64 C = 0;
-    rc = excl_scan(h, flag, n_cells, pos, &C); if (rc != ECB_OK) return rc;
+    RCCHK(excl_scan(h, flag, n_cells, pos, &C));
     // (the bits come in the table's order: 1 and 2 from the passes above, 4 from k_msf2_pairs below, behind this check)
     static const ErrBit MSF_ERRS[] = {
         {1u, ECB_ERR_CONTRACT, "triple with an EC id beyond the finalized ECs"},
@@ -4069,7 +4045,7 @@ int ecb_ms_filter(ecb_handle* h, uint32_t n_cells, int64_t minimum_count, ecb_ms
     u32 err = 0;
     HIPCHK(h, hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));
-    rc = refuse_bits(h, MSF_ERRS, err); if (rc != ECB_OK) return rc;
+    RCCHK(refuse_bits(h, MSF_ERRS, err));
     if (!C) return fail(h, ECB_ERR_EMPTY, "no (EC, cell) counts: nothing to filter");
     u32 *cell_id = fresh<u32>(sc, C), *corder = fresh<u32>(sc, C), *corder2 = fresh<u32>(sc, C), *cflag = fresh<u32>(sc, C), *cpos = fresh<u32>(sc, C);
     u64 *ctotal = fresh<u64>(sc, C), *bhi = fresh<u64>(sc, C), *blo = fresh<u64>(sc, C), *ck0 = fresh<u64>(sc, C), *ck1 = fresh<u64>(sc, C);
@@ -4078,66 +4054,66 @@ int ecb_ms_filter(ecb_handle* h, uint32_t n_cells, int64_t minimum_count, ecb_ms
     k_iota<<<nblk(C, TPB), TPB, 0, st>>>(corder, C);
     HIPCHK(h, hipMemcpyAsync(ck0, blo, C * 8, hipMemcpyDeviceToDevice, st));
     u32* ord = nullptr;
-    { SortBufs s{{ck0, ck1}, {corder, corder2}}; rc = handle_sort(h, s, C); if (rc != ECB_OK) return rc;
+    { SortBufs s{{ck0, ck1}, {corder, corder2}}; RCCHK(handle_sort(h, s, C));
       k_msf_gather64<<<nblk(C, TPB), TPB, 0, st>>>(bhi, s.vals(), C, s.spare_keys());   // (the second key, in the first sort's order)
-      SortBufs s2{{s.spare_keys(), s.keys()}, {s.vals(), s.spare_vals()}}; rc = handle_sort(h, s2, C); if (rc != ECB_OK) return rc;
+      SortBufs s2{{s.spare_keys(), s.keys()}, {s.vals(), s.spare_vals()}}; RCCHK(handle_sort(h, s2, C));
       ord = s2.vals(); }
     k_msf_keepflag<<<nblk(C, TPB), TPB, 0, st>>>(ord, ctotal, C, min_count, cflag);
     u64 S = 0;
-    rc = excl_scan(h, cflag, C, cpos, &S); if (rc != ECB_OK) return rc;
+    RCCHK(excl_scan(h, cflag, C, cpos, &S));
     if (!S) return fail(h, ECB_ERR_EMPTY, "no cell reaches the minimum count");
-    POOL(h, P_F_CELLS, h->f_cells, S);
+    POOL(h, P_F_CELLS, f.cells, S);
     HIPCHK(h, hipMemsetAsync(new_cell, 0xFF, (u64)n_cells * 4, st));
-    k_msf_newcell<<<nblk(C, TPB), TPB, 0, st>>>(ord, cflag, cpos, cell_id, C, new_cell, h->f_cells);
+    k_msf_newcell<<<nblk(C, TPB), TPB, 0, st>>>(ord, cflag, cpos, cell_id, C, new_cell, f.cells);
     // 4. ECs that keep a cell, re-ranked (bam_utils_multisample.py:611-636)
     u64 E2 = 0, K = 0;
-    rc = excl_scan(h, keep_ec, E, new_rank, &E2); if (rc != ECB_OK) return rc;
+    RCCHK(excl_scan(h, keep_ec, E, new_rank, &E2));
     // 5. N as CSC over (kept EC, kept cell): the surviving (EC, cell) pairs, the reads of their files added up (:737-791), come
     //    in EC order; a stable sort on the cell's digits makes them the columns
     k_msf2_pairflag<<<nblk(T, TPB), TPB, 0, st>>>(ec, meta, T, new_cell, flag);
-    rc = excl_scan(h, flag, T, pos, &K); if (rc != ECB_OK) return rc;
+    RCCHK(excl_scan(h, flag, T, pos, &K));
     if (K >= (1ull << 31)) return fail(h, ECB_ERR_LIMIT, "N has more than 2^31-1 non-zeros");
     k_msf2_pairs<<<nblk(T, TPB), TPB, 0, st>>>(ec, meta, cnt, flag, pos, T, new_cell, new_rank, k0, v0, d_err);
     const u64 nnz_n = K;
     {
         SortBufs s{{k0, k1}, {v0, v1}};
-        rc = handle_sort(h, s, K, msb_mask(S - 1) << 32);
-        if (rc != ECB_OK) return rc;
-        POOL(h, P_F_IPN, h->f_ipn, S + 1); POOL(h, P_F_IXN, h->f_ixn, nnz_n); POOL(h, P_F_DAN, h->f_dan, nnz_n);
-        k_split_out<<<nblk(K, TPB), TPB, 0, st>>>(s.keys(), s.vals(), K, h->f_ixn, h->f_dan);
-        k_row_ptr<<<nblk(S + 1, TPB), TPB, 0, st>>>(s.keys(), K, (u32)S, h->f_ipn);
+        RCCHK(handle_sort(h, s, K, msb_mask(S - 1) << 32));
+        POOL(h, P_F_IPN, f.ipn, S + 1); POOL(h, P_F_IXN, f.ixn, nnz_n); POOL(h, P_F_DAN, f.dan, nnz_n);
+        k_split_out<<<nblk(K, TPB), TPB, 0, st>>>(s.keys(), s.vals(), K, f.ixn, f.dan);
+        k_row_ptr<<<nblk(S + 1, TPB), TPB, 0, st>>>(s.keys(), K, (u32)S, f.ipn);
     }
     // 6. the rows of A of the ECs that are left
     u32* rowlen2 = fresh<u32>(sc, E2 + 1);
     if (missing(sc)) return fail(h, ECB_ERR_HIP, "out of device memory");
-    POOL(h, P_F_IPA, h->f_ipa, E2 + 1);
-    k_msf_rowlen<<<nblk(E, TPB), TPB, 0, st>>>(h->indptr, keep_ec, new_rank, E, rowlen2);
+    POOL(h, P_F_IPA, f.ipa, E2 + 1);
+    k_msf_rowlen<<<nblk(E, TPB), TPB, 0, st>>>(h->run.csr.indptr, keep_ec, new_rank, E, rowlen2);
     u64 nnz_a = 0;
-    rc = excl_scan(h, rowlen2, E2, reinterpret_cast<u32*>(h->f_ipa), &nnz_a); if (rc != ECB_OK) return rc;
-    { const u32 last = (u32)nnz_a; HIPCHK(h, hipMemcpyAsync(h->f_ipa + E2, &last, 4, hipMemcpyHostToDevice, st)); HIPCHK(h, hipStreamSynchronize(st)); }
-    POOL(h, P_F_IXA, h->f_ixa, nnz_a); POOL(h, P_F_DAA, h->f_daa, nnz_a);
-    k_msf_rows<<<nblk(E, TPB), TPB, 0, st>>>(h->indptr, h->indices, h->data, keep_ec, new_rank, reinterpret_cast<const u32*>(h->f_ipa), E, h->f_ixa, h->f_daa);
+    RCCHK(excl_scan(h, rowlen2, E2, reinterpret_cast<u32*>(f.ipa), &nnz_a));
+    { const u32 last = (u32)nnz_a; HIPCHK(h, hipMemcpyAsync(f.ipa + E2, &last, 4, hipMemcpyHostToDevice, st)); HIPCHK(h, hipStreamSynchronize(st)); }
+    POOL(h, P_F_IXA, f.ixa, nnz_a); POOL(h, P_F_DAA, f.daa, nnz_a);
+    k_msf_rows<<<nblk(E, TPB), TPB, 0, st>>>(h->run.csr.indptr, h->run.csr.indices, h->run.csr.data, keep_ec, new_rank, reinterpret_cast<const u32*>(f.ipa), E, f.ixa, f.daa);
     HIPCHK(h, hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));
-    rc = refuse_bits(h, MSF_ERRS, err); if (rc != ECB_OK) return rc;
-    h->msf.n_cells_seen = C; h->msf.n_cells_kept = S; h->msf.n_ecs_kept = E2; h->msf.nnz_a = nnz_a; h->msf.nnz_n = nnz_n;
-    h->ms_filtered = true;
-    *out = h->msf;
+    RCCHK(refuse_bits(h, MSF_ERRS, err));
+    h->run.msf.n_cells_seen = C; h->run.msf.n_cells_kept = S; h->run.msf.n_ecs_kept = E2; h->run.msf.nnz_a = nnz_a; h->run.msf.nnz_n = nnz_n;
+    h->run.flt = f;
+    *out = h->run.msf;
     return ECB_OK;
 }
 
 int ecb_ms_export(ecb_handle* h, uint32_t* kept_cells, int32_t* ia, int32_t* ja, int32_t* da, int32_t* in_, int32_t* jn, int32_t* dn) {
     if (!h) return ECB_ERR_ARG;
-    if (!h->ms_filtered) return fail(h, ECB_ERR_STATE, "ecb_ms_export before ecb_ms_filter");
+    if (!h->run.flt.cells) return fail(h, ECB_ERR_STATE, "ecb_ms_export before ecb_ms_filter");
     HIPCHK(h, hipSetDevice(h->device));
-    const ecb_ms_sizes& m = h->msf;
-    if (kept_cells) HIPCHK(h, hipMemcpyAsync(kept_cells, h->f_cells, m.n_cells_kept * 4, hipMemcpyDeviceToHost, h->stream));
-    if (ia) HIPCHK(h, hipMemcpyAsync(ia, h->f_ipa, (m.n_ecs_kept + 1) * 4, hipMemcpyDeviceToHost, h->stream));
-    if (ja) HIPCHK(h, hipMemcpyAsync(ja, h->f_ixa, m.nnz_a * 4, hipMemcpyDeviceToHost, h->stream));
-    if (da) HIPCHK(h, hipMemcpyAsync(da, h->f_daa, m.nnz_a * 4, hipMemcpyDeviceToHost, h->stream));
-    if (in_) HIPCHK(h, hipMemcpyAsync(in_, h->f_ipn, (m.n_cells_kept + 1) * 4, hipMemcpyDeviceToHost, h->stream));
-    if (jn) HIPCHK(h, hipMemcpyAsync(jn, h->f_ixn, m.nnz_n * 4, hipMemcpyDeviceToHost, h->stream));
-    if (dn) HIPCHK(h, hipMemcpyAsync(dn, h->f_dan, m.nnz_n * 4, hipMemcpyDeviceToHost, h->stream));
+    const ecb_ms_sizes& m = h->run.msf;
+    const ecb_handle::Run::Filtered& f = h->run.flt;
+    if (kept_cells) HIPCHK(h, hipMemcpyAsync(kept_cells, f.cells, m.n_cells_kept * 4, hipMemcpyDeviceToHost, h->stream));
+    if (ia) HIPCHK(h, hipMemcpyAsync(ia, f.ipa, (m.n_ecs_kept + 1) * 4, hipMemcpyDeviceToHost, h->stream));
+    if (ja) HIPCHK(h, hipMemcpyAsync(ja, f.ixa, m.nnz_a * 4, hipMemcpyDeviceToHost, h->stream));
+    if (da) HIPCHK(h, hipMemcpyAsync(da, f.daa, m.nnz_a * 4, hipMemcpyDeviceToHost, h->stream));
+    if (in_) HIPCHK(h, hipMemcpyAsync(in_, f.ipn, (m.n_cells_kept + 1) * 4, hipMemcpyDeviceToHost, h->stream));
+    if (jn) HIPCHK(h, hipMemcpyAsync(jn, f.ixn, m.nnz_n * 4, hipMemcpyDeviceToHost, h->stream));
+    if (dn) HIPCHK(h, hipMemcpyAsync(dn, f.dan, m.nnz_n * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return ECB_OK;
 }
@@ -4145,21 +4121,17 @@ int ecb_ms_export(ecb_handle* h, uint32_t* kept_cells, int32_t* ia, int32_t* ja,
 int ecb_counters(ecb_handle* h, uint64_t* all_alignments, uint64_t* valid_alignments, uint64_t* n_reads) {
     if (!h) return ECB_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
-    if (!h->finalized && !h->c_rid.empty()) {
-        int rc = stage_and_process(h, nullptr, nullptr, nullptr, nullptr, 0);
-        if (rc != ECB_OK) return rc;
-    }
-    int rc = sync_counters(h);
-    if (rc != ECB_OK) return rc;
-    if (all_alignments) *all_alignments = h->hctr.all + h->extra_all;
-    if (valid_alignments) *valid_alignments = h->hctr.valid + h->extra_valid;
-    if (n_reads) *n_reads = h->n_reads + h->extra_reads;
+    if (!h->has_result() && h->open_read()) RCCHK(stage_and_process(h, nullptr, nullptr, nullptr, nullptr, 0));
+    RCCHK(sync_counters(h));
+    if (all_alignments) *all_alignments = h->hctr.all + h->run.extra_all;
+    if (valid_alignments) *valid_alignments = h->hctr.valid + h->run.extra_valid;
+    if (n_reads) *n_reads = h->run.n_reads + h->run.extra_reads;
     return ECB_OK;
 }
 
 int ecb_add_counters(ecb_handle* h, uint64_t all_alignments, uint64_t valid_alignments, uint64_t n_reads) {
     if (!h) return ECB_ERR_ARG;
-    h->extra_all += all_alignments; h->extra_valid += valid_alignments; h->extra_reads += n_reads;
+    h->run.extra_all += all_alignments; h->run.extra_valid += valid_alignments; h->run.extra_reads += n_reads;
     return ECB_OK;
 }
 
@@ -4439,11 +4411,10 @@ extern "C" int ecb_csr_to_hapcsc(int device, uint32_t n_ecs, uint32_t n_loci, ui
     // (the device entry point writes at most one row index per set bit: ask it for the count first when the caller's buffer might be short)
     uint64_t need = 0;
     if (rc == ECB_OK) rc = ecb_csr_to_hapcsc_device(device, n_ecs, n_loci, n_haps, ip.p, ix.p, da.p, nullptr, nullptr, &need);
-    if (rc != ECB_OK) return rc;
+    RCCHK(rc);
     *total = need;
     if (need > capacity) return fail(nullptr, ECB_ERR_ARG, "csc_indices holds %llu entries, the matrix has %llu set bits", (unsigned long long)capacity, (unsigned long long)need);
-    rc = ecb_csr_to_hapcsc_device(device, n_ecs, n_loci, n_haps, ip.p, ix.p, da.p, cp.p, ci.p, total);
-    if (rc != ECB_OK) return rc;
+    RCCHK(ecb_csr_to_hapcsc_device(device, n_ecs, n_loci, n_haps, ip.p, ix.p, da.p, cp.p, ci.p, total));
     return stage_out(c, {{csc_indptr, &cp, nc * 4}, {csc_indices, &ci, *total * 4}});
 }
 
@@ -4457,7 +4428,7 @@ extern "C" int ecb_hapcsc_to_csr(int device, uint32_t n_ecs, uint32_t n_loci, ui
     const u64 nc = (u64)n_haps * (n_loci + 1), rowb = ((u64)n_ecs + 1) * 4;
     int rc = stage_in(c, {{&cp, csc_indptr, nc * 4}, {&ci, csc_indices, total * 4}, {&ip, nullptr, rowb}, {&ix, nullptr, total * 4}, {&da, nullptr, total * 4}});
     if (rc == ECB_OK) rc = ecb_hapcsc_to_csr_device(device, n_ecs, n_loci, n_haps, cp.p, ci.p, total, ip.p, ix.p, da.p, nnz);
-    if (rc != ECB_OK) return rc;
+    RCCHK(rc);
     return stage_out(c, {{indptr, &ip, rowb}, {indices, &ix, *nnz * 4}, {data, &da, *nnz * 4}});
 }
 
@@ -4624,7 +4595,7 @@ extern "C" int ecb_apply_mask(int device, uint32_t n_ecs, uint32_t n_loci, uint3
     int rc = stage_in(c, {{&ip, indptr, rowb}, {&ix, indices, nzb}, {&da, data, nzb}, {&mk, mask, (u64)n_loci * 4}, {&oip, nullptr, rowb},
                           {&oix, nullptr, nzb}, {&oda, nullptr, nzb}});
     if (rc == ECB_OK) rc = ecb_apply_mask_device(device, n_ecs, n_loci, n_haps, nnz, ip.p, ix.p, da.p, mk.p, oip.p, oix.p, oda.p, kept);
-    if (rc != ECB_OK) return rc;
+    RCCHK(rc);
     return stage_out(c, {{out_indptr, &oip, rowb}, {out_indices, &oix, *kept * 4}, {out_data, &oda, *kept * 4}});
 }
 
@@ -4938,7 +4909,7 @@ extern "C" int ecb_combine_device(int device, uint32_t n_parts, const ecb_combin
     u32 *vals0 = c.get<u32>(NK), *vals1 = c.get<u32>(NK);
     uint2* pairs = c.get<uint2>(NP);
     Entry* ent = c.get<Entry>(R);
-    int rc = c.missing(); if (rc != ECB_OK) return rc;
+    RCCHK(c.missing());
     u32* err = reinterpret_cast<u32*>(words);
     std::vector<u64> back(n_words);
     auto check = [&] { return c.read_back(back.data(), words, n_words, CB_ERRS); };      // one wait: the error word and the shards
@@ -4949,16 +4920,14 @@ extern "C" int ecb_combine_device(int device, uint32_t n_parts, const ecb_combin
     // 1. the pointers; 2. the pairs (their binary searches trust checked pointers)
     const u64 n_ptr = std::max(base[CB_APTR * B + n_parts], base[CB_NPTR * B + n_parts]);
     k_cb_check<<<nblk(n_ptr, TPB), TPB, 0, st>>>(d_parts, n_parts, d_base, err);
-    rc = check();
-    if (rc != ECB_OK) return rc;
+    RCCHK(check());
     if (NP) k_cb_pairs<<<nblk(NP, TPB), TPB, 0, st>>>(d_parts, n_parts, d_base, n_loci, n_haps, keys0, vals0, err);
-    rc = check();
-    if (rc != ECB_OK) return rc;
+    RCCHK(check());
     // 3. rows that a target map re-numbered are re-sorted: one radix sort of (row, column) over all pairs (parts without a map are sorted already)
     u64* keys = keys0; u32* vals = vals0;
     if (any_map && NP > 1) {
         SortScratch sc{c.get<u32>(rs_words(NP)), c.get<u32>(RS_AUX_WORDS), words + 1};
-        if ((rc = c.missing()) != ECB_OK) return rc;
+        RCCHK(c.missing());
         SortBufs s{{keys0, keys1}, {vals0, vals1}};
         CALLCHK(c, radix_sort_pairs64(st, s, NP, sc, msb_mask((R - 1) << 32 | (n_loci - 1))));
         keys = s.keys(); vals = s.vals();
@@ -4966,13 +4935,12 @@ extern "C" int ecb_combine_device(int device, uint32_t n_parts, const ecb_combin
     // 4. key lists and row hashes; 5. the entries, and the key arena's worst wave
     if (NP) k_cb_hash<<<nblk(NP, TPB), TPB, 0, st>>>(keys, vals, NP, pairs, rowhash, err);
     if (R) k_cb_entries<<<nblk(R, TPB), TPB, 0, st>>>(d_parts, n_parts, d_base, rowhash, ent, words);
-    rc = check();
-    if (rc != ECB_OK) return rc;
+    RCCHK(check());
     u64 wmax = 0, wsum = 0;
     for (u32 k = 1; k <= CB_SHARDS; ++k) { wmax = std::max<u64>(wmax, back[CB_SHARD_WORDS * k]); wsum += back[CB_SHARD_WORDS * k + 1]; }
     u64 E = 0, nnz_a = 0, nnz_n = 0;
     u32* ec_of_row = c.get<u32>(R);                      // EC of every global row
-    if ((rc = c.missing()) != ECB_OK) return rc;
+    RCCHK(c.missing());
     HandleGuard hg;
     if (R) {
         // 6. one table: room for every row being an EC of its own (half full at most: no growth), and a key arena in which every wave's one
@@ -4982,11 +4950,10 @@ extern "C" int ecb_combine_device(int device, uint32_t n_parts, const ecb_combin
         cfg.ec_capacity = 2 * R;
         cfg.arena_capacity = std::max<u64>(1ull << 22, (u64)ARENA_REGIONS * (wmax + wsum / ARENA_REGIONS + 2));
         ecb_handle* h = nullptr;
-        rc = ecb_create(&cfg, &h);
-        if (rc != ECB_OK) return rc;
+        RCCHK(ecb_create(&cfg, &h));
         hg.h.push_back(h);
         ecb_add_counters(h, 0, R, R);                     // R "reads", all valid: the ranking's bitmap spans the rows
-        rc = ecb_table_merge_device(h, ent, R, pairs, NP);
+        int rc = ecb_table_merge_device(h, ent, R, pairs, NP);
         ecb_sizes sz{};
         if (rc == ECB_OK) rc = ecb_finalize(h, &sz);
         if (rc == ECB_OK) rc = ecb_export_device(h, d_out_indptr_a, d_out_indices_a, d_out_data_a, nullptr, nullptr, nullptr);
@@ -4995,7 +4962,7 @@ extern "C" int ecb_combine_device(int device, uint32_t n_parts, const ecb_combin
         E = sz.n_ecs; nnz_a = sz.nnz_a;
         st = h->stream;
         // 7. every row's EC
-        k_cb_lookup<<<nblk(R, TPB), TPB, 0, st>>>(ent, R, pairs, h->table, h->cap - 1, h->arena, h->rank_of_slot, ec_of_row, err);
+        k_cb_lookup<<<nblk(R, TPB), TPB, 0, st>>>(ent, R, pairs, h->table, h->cap - 1, h->arena, h->run.csr.rank_of_slot, ec_of_row, err);
     } else {
         CALLCHK(c, hipMemsetAsync(d_out_indptr_a, 0, 4, st));
     }
@@ -5005,10 +4972,9 @@ extern "C" int ecb_combine_device(int device, uint32_t n_parts, const ecb_combin
         u32 *sums1 = c.get<u32>(scan_words(NZ)), *sums2 = c.get<u32>(scan_words(NZ));
         u64 *rsum = c.get<u64>(NZ), *rkey = c.get<u64>(NZ), *okey = c.get<u64>(NZ), *tot = c.get<u64>(2);
         SortScratch sc{c.get<u32>(rs_words(NZ)), c.get<u32>(RS_AUX_WORDS), words + 1};
-        if ((rc = c.missing()) != ECB_OK) return rc;
+        RCCHK(c.missing());
         k_cb_ntrip<<<nblk(NZ, TPB), TPB, 0, st>>>(d_parts, n_parts, d_base, n_samples, ec_of_row, keys0, vals0, err);
-        rc = check();
-        if (rc != ECB_OK) return rc;
+        RCCHK(check());
         SortBufs s{{keys0, keys1}, {vals0, vals1}};
         CALLCHK(c, radix_sort_pairs64(st, s, NZ, sc, msb_mask(((u64)n_samples - 1) << 32 | (E ? E - 1 : 0))));
         const u64* sk = s.keys(); const u32* sv = s.vals();
@@ -5023,14 +4989,12 @@ extern "C" int ecb_combine_device(int device, uint32_t n_parts, const ecb_combin
         k_cb_nptr<<<nblk((u64)n_samples + 1, TPB), TPB, 0, st>>>(okey, tot + 1, NZ, n_samples, (int*)d_out_indptr_n);
         u64 t2[2] = {0, 0};
         CALLCHK(c, hipMemcpyAsync(t2, tot, 16, hipMemcpyDeviceToHost, st));
-        rc = check();
-        if (rc != ECB_OK) return rc;
+        RCCHK(check());
         if (t2[1] > NZ) return fail(nullptr, ECB_ERR_HIP, "internal: %llu N entries from %llu", (unsigned long long)t2[1], (unsigned long long)NZ);
         nnz_n = t2[1];
     } else {
         CALLCHK(c, hipMemsetAsync(d_out_indptr_n, 0, ((u64)n_samples + 1) * 4, st));
-        rc = check();
-        if (rc != ECB_OK) return rc;
+        RCCHK(check());
     }
     out_sizes[0] = E; out_sizes[1] = nnz_a; out_sizes[2] = nnz_n;
     return ECB_OK;
@@ -5058,14 +5022,14 @@ extern "C" int ecb_combine(int device, uint32_t n_parts, const ecb_combine_part*
             if (src[k]) { in.push_back({&bufs[(u64)p * 8 + k], src[k], len[k]}); at.push_back(dst[k]); }
         R += c.n_ecs; NP += c.nnz_a; NZ += c.nnz_n;
     }
-    int rc = stage_in(c, in); if (rc != ECB_OK) return rc;
+    RCCHK(stage_in(c, in));
     for (size_t i = 0; i < in.size(); ++i) *at[i] = in[i].d->p;
     DevBuf<> oia, oxa, oda, oin, oxn, odn;
     const u64 nptr = ((u64)n_samples + 1) * 4;
-    rc = stage_in(c, {{&oia, nullptr, (R + 1) * 4}, {&oxa, nullptr, NP * 4}, {&oda, nullptr, NP * 4}, {&oin, nullptr, nptr}, {&oxn, nullptr, NZ * 4},
+    int rc = stage_in(c, {{&oia, nullptr, (R + 1) * 4}, {&oxa, nullptr, NP * 4}, {&oda, nullptr, NP * 4}, {&oin, nullptr, nptr}, {&oxn, nullptr, NZ * 4},
                       {&odn, nullptr, NZ * 4}});
     if (rc == ECB_OK) rc = ecb_combine_device(device, n_parts, dp.data(), n_loci, n_haps, n_samples, oia.p, oxa.p, oda.p, oin.p, oxn.p, odn.p, out_sizes);
-    if (rc != ECB_OK) return rc;
+    RCCHK(rc);
     const u64 E = out_sizes[0], nnz_a = out_sizes[1], nnz_n = out_sizes[2];
     return stage_out(c, {{out_indptr_a, &oia, (E + 1) * 4}, {out_indptr_n, &oin, nptr}, {out_indices_a, &oxa, nnz_a * 4}, {out_data_a, &oda, nnz_a * 4},
                          {out_indices_n, &oxn, nnz_n * 4}, {out_data_n, &odn, nnz_n * 4}});
@@ -5301,7 +5265,7 @@ extern "C" int ecb_salmon_ecs_device(int device, const void* d_text, uint64_t n_
     u32 *blk_nl = c.get<u32>(nb), *blk_fs = c.get<u32>(nb), *nl_ex = c.get<u32>(nb), *fs_ex = c.get<u32>(nb);
     u32 *sc1 = c.get<u32>(scan_words(nb)), *sc2 = c.get<u32>(scan_words(nb));
     u64* words = c.get<u64>(8);                        // [0] lowest (line << 8 | reason), [1] [2] line ends, field starts, [3] bad target map, [4] [5] scan totals
-    int rc = c.missing(); if (rc != ECB_OK) return rc;
+    RCCHK(c.missing());
     u64* err = words;
     u32* bad = reinterpret_cast<u32*>(words + 3);
     u64 back[8] = {0};
@@ -5316,7 +5280,7 @@ extern "C" int ecb_salmon_ecs_device(int device, const void* d_text, uint64_t n_
         CALLCHK(c, scan_launch(st, blk_fs, nb, fs_ex, sc2, words + 2));
         CALLCHK(c, hipMemcpyAsync(&last, text + L - 1, 1, hipMemcpyDeviceToHost, st));
     }
-    if ((rc = c.read_back(back, words, 8)) != ECB_OK) return rc;
+    RCCHK(c.read_back(back, words, 8));
     if (back[3]) return fail(nullptr, ECB_ERR_CONTRACT, "salmon: the target map has a column at or beyond n_loci or a haplotype at or beyond n_haps");
     const u64 n_lines = back[1] + (L && last != 10), NF = back[2];
     if (NF >= (1ull << 30) || n_lines >= (1ull << 31) - 1) return fail(nullptr, ECB_ERR_LIMIT, "salmon: %llu fields in %llu lines: beyond the limits (2^30, 2^31-1)",
@@ -5327,18 +5291,18 @@ extern "C" int ecb_salmon_ecs_device(int device, const void* d_text, uint64_t n_
     u64 *keys0 = c.get<u64>(NF), *keys1 = c.get<u64>(NF);
     u32 *vals0 = c.get<u32>(NF), *vals1 = c.get<u32>(NF), *flag = c.get<u32>(NF), *pos = c.get<u32>(NF + 1), *sc3 = c.get<u32>(scan_words(NF));
     SortScratch ss{c.get<u32>(rs_words(NF)), c.get<u32>(RS_AUX_WORDS), words + 6};
-    if ((rc = c.missing()) != ECB_OK) return rc;
+    RCCHK(c.missing());
     if (L) k_sl_place<<<(unsigned)nb, TPB, 0, st>>>(text, L, nl_ex, fs_ex, (u32)NF, fval, fline, fend, err);
     const u64 NP = NF >= 2 * n_lines ? NF - 2 * n_lines : 0;
     if (NF) k_sl_fields<<<nblk(NF, TPB), TPB, 0, st>>>(fval, fline, fend, (u32)NF, n_targets, tcol, thap, true, NP, keys0, vals0, cnt, err);
-    if ((rc = c.read_back(back, words, 8)) != ECB_OK) return rc;
+    RCCHK(c.read_back(back, words, 8));
     SortBufs s{{keys0, keys1}, {vals0, vals1}};
     if (back[0] != SL_NO_ERR) {
         // a malformed line: every field in a slot of its own, sorted on all bits, so that repeats in the lines before it are found too
         k_sl_fields<<<nblk(NF, TPB), TPB, 0, st>>>(fval, fline, fend, (u32)NF, n_targets, tcol, thap, false, NF, keys0, vals0, cnt, err);
         CALLCHK(c, radix_sort_pairs64(st, s, NF, ss));
         k_sl_heads<<<nblk(NF, TPB), TPB, 0, st>>>(s.keys(), NF, flag, err);
-        if ((rc = c.read_back(back, words, 8)) != ECB_OK) return rc;
+        RCCHK(c.read_back(back, words, 8));
         return refuse(std::min(back[0], count_err));
     }
     // 4. sort within rows (the row and column bits only); runs, repeats refused
@@ -5347,7 +5311,7 @@ extern "C" int ecb_salmon_ecs_device(int device, const void* d_text, uint64_t n_
     const u64* keys = s.keys(); const u32* vals = s.vals();
     if (NP) k_sl_heads<<<nblk(NP, TPB), TPB, 0, st>>>(keys, NP, flag, err);
     CALLCHK(c, scan_launch(st, flag, NP, pos, sc3, words + 4, 1, pos + NP));
-    if ((rc = c.read_back(back, words, 8)) != ECB_OK) return rc;
+    RCCHK(c.read_back(back, words, 8));
     if (std::min(back[0], count_err) != SL_NO_ERR) return refuse(std::min(back[0], count_err));
     const u64 nnz = NP ? back[4] : 0;
     if (nnz > capacity) return fail(nullptr, ECB_ERR_LIMIT, "salmon: %llu non-zeros, room for %llu", (unsigned long long)nnz, (unsigned long long)capacity);
@@ -5360,7 +5324,7 @@ extern "C" int ecb_salmon_ecs_device(int device, const void* d_text, uint64_t n_
         CALLCHK(c, scan_launch(st, flag, n_ecs, pos, sc3, words + 5));
         k_sl_nemit<<<nblk(n_ecs, TPB), TPB, 0, st>>>(cnt, flag, pos, n_ecs, (int*)d_out_n_indices, (int*)d_out_n_data);
     }
-    if ((rc = c.read_back(back, words, 8)) != ECB_OK) return rc;
+    RCCHK(c.read_back(back, words, 8));
     out_sizes[0] = nnz;
     out_sizes[1] = n_ecs ? back[5] : 0;
     return ECB_OK;
@@ -5379,7 +5343,7 @@ extern "C" int ecb_salmon_ecs(int device, const char* text, uint64_t n_bytes, ui
     int rc = stage_in(c, {{&dt, text, n_bytes}, {&dc, target_col, (u64)n_targets * 4}, {&dh, target_hap, (u64)n_targets * 4}, {&oip, nullptr, rowb},
                           {&oix, nullptr, capacity * 4}, {&oda, nullptr, capacity * 4}, {&onx, nullptr, (u64)n_ecs * 4}, {&ond, nullptr, (u64)n_ecs * 4}});
     if (rc == ECB_OK) rc = ecb_salmon_ecs_device(device, dt.p, n_bytes, n_ecs, n_targets, dc.p, dh.p, n_loci, n_haps, capacity, oip.p, oix.p, oda.p, onx.p, ond.p, out_sizes);
-    if (rc != ECB_OK) return rc;
+    RCCHK(rc);
     return stage_out(c, {{out_indptr, &oip, rowb}, {out_indices, &oix, out_sizes[0] * 4}, {out_data, &oda, out_sizes[0] * 4}, {out_n_indices, &onx, out_sizes[1] * 4},
                          {out_n_data, &ond, out_sizes[1] * 4}});
 }
@@ -5422,8 +5386,8 @@ extern "C" int ecb_merge(ecb_handle* const* shards, uint32_t n, ecb_handle* root
         if (rc != ECB_OK) return fail(root, rc, "ecb_merge: shard %u: %s", r, ecb_last_error(shards[r]));
         ne[r] = a; np[r] = b; nr[r] = c; all[r] = ca; valid[r] = cv;
         base[r + 1] = base[r] + nr[r];
-        if ((rc = take(root, ent[r], shards[r]->device, std::max<u64>(ne[r], 1) * sizeof(Entry))) != ECB_OK) return rc;
-        if ((rc = take(root, prs[r], shards[r]->device, std::max<u64>(np[r], 1) * sizeof(uint2))) != ECB_OK) return rc;
+        RCCHK(take(root, ent[r], shards[r]->device, std::max<u64>(ne[r], 1) * sizeof(Entry)));
+        RCCHK(take(root, prs[r], shards[r]->device, std::max<u64>(np[r], 1) * sizeof(uint2)));
         if (ne[r]) {
             rc = ecb_table_export_parts_device(shards[r], ent[r].p, prs[r].p, 0, n, eoff[r].data(), poff[r].data());
             if (rc != ECB_OK) return fail(root, rc, "ecb_merge: shard %u: %s", r, ecb_last_error(shards[r]));
@@ -5452,8 +5416,8 @@ extern "C" int ecb_merge(ecb_handle* const* shards, uint32_t n, ecb_handle* root
         for (u32 r = 0; r < n; ++r) {
             const u64 e_n = eoff[r][q + 1] - eoff[r][q], p_n = poff[r][q + 1] - poff[r][q];
             if (!e_n) continue;
-            if ((rc = take(root, pe[r], dq, e_n * sizeof(Entry))) != ECB_OK) return rc;
-            if ((rc = take(root, pp[r], dq, std::max<u64>(p_n, 1) * sizeof(uint2))) != ECB_OK) return rc;
+            RCCHK(take(root, pe[r], dq, e_n * sizeof(Entry)));
+            RCCHK(take(root, pp[r], dq, std::max<u64>(p_n, 1) * sizeof(uint2)));
             MERGECHK(hipMemcpyPeer(pe[r].p, dq, (const char*)ent[r].p + eoff[r][q] * sizeof(Entry), shards[r]->device, e_n * sizeof(Entry)));
             if (p_n) MERGECHK(hipMemcpyPeer(pp[r].p, dq, (const char*)prs[r].p + poff[r][q] * sizeof(uint2), shards[r]->device, p_n * sizeof(uint2)));
             if (base[r]) { rc = ecb_table_rebase_device(part, pe[r].p, e_n, base[r]); if (rc != ECB_OK) return fail(root, rc, "ecb_merge: %s", ecb_last_error(part)); }
@@ -5466,7 +5430,7 @@ extern "C" int ecb_merge(ecb_handle* const* shards, uint32_t n, ecb_handle* root
         if (rc != ECB_OK) return fail(root, rc, "ecb_merge: range %u: %s", q, ecb_last_error(part));
         Piece& P = piece[q];
         P.n_ecs = s.n_ecs; P.nnz = s.nnz_a;
-        for (int k = 0; k < 5; ++k) if ((rc = take(root, P.buf[k], dq, P.bytes(k))) != ECB_OK) return rc;
+        for (int k = 0; k < 5; ++k) RCCHK(take(root, P.buf[k], dq, P.bytes(k)));
         rc = ecb_export_device(part, P.buf[0].p, P.buf[1].p, P.buf[2].p, nullptr, nullptr, P.buf[3].p);
         if (rc == ECB_OK) rc = ecb_export_firsts_device(part, P.buf[4].p);
         if (rc != ECB_OK) return fail(root, rc, "ecb_merge: range %u: %s", q, ecb_last_error(part));
