@@ -2448,6 +2448,8 @@ enum class Origin { OWN,              // its own reads (and what ecb_table_merge
                     ASSEMBLED };      // no table: the result was put together from per-range results (ecb_assemble_ranges_device)
 // whose (EC, cell, file) triples Run::tri holds
 enum class Triples { NONE, OWN /* ms_reduce, of the handle's own reads */, ADOPTED /* ecb_ms_adopt_triples_device (multi-GPU) */ };
+// the instantiations of k_stream that are launched, one row of STREAM_VARIANTS each
+enum StreamVariant { SV_STD, SV_STD_RANGES, SV_SHORT, SV_PAR, SV_VERIFY, SV_N };
 
 struct ecb_handle {
     ecb_config cfg{};
@@ -2456,10 +2458,8 @@ struct ecb_handle {
     std::string err;
     u64 wave_arena_n = 0;             // see StreamArgs::wave_arena
     bool scatter_attr_set = false, count_attr_set = false;
-    u64 resident_blocks = 0, resident_blocks_rg = 0, resident_blocks_sh = 0, rounds = 24, min_tiles = 32;     // k_stream's launch shape (queried once)
-    bool short_reads = false;         // this batch goes through ks_short::k_stream (set per batch by process_batch)
-    bool par_stream = false;          // ... through ks_par::k_stream: the batch before met loci that displace each other in the LDS table (sticky per handle)
-    u64 resident_blocks_par = 0;
+    u64 resident_blocks[SV_VERIFY] = {}, rounds = 24, min_tiles = 32;     // k_stream's launch shape, per variant (queried once: plan_stream)
+    bool par_stream = false;          // batches go through ks_par::k_stream: the batch before met loci that displace each other in the LDS table (sticky per handle)
     bool ctr_synced = false;          // hctr is what the device holds (no kernel that counts has been queued since the last read-back)
 
     u64 cap = 0, arena_cap = 0;       // slots of table, pairs of arena
@@ -2523,7 +2523,7 @@ struct ecb_handle {
 
     // profiling
     bool prof = false; double prof_ms = 0; u64 prof_launches = 0, prof_records = 0;
-    const char* last_kernel = "";     // which compilation of the stream kernel the last batch launched (ecb_profile_kernel)
+    int last_variant = SV_N;          // which variant of the stream kernel the last batch launched (ecb_profile_kernel; SV_N: no batch yet)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 
     // The memory the handle owns, freed when it is deleted, after the stream (members go last to first: the table first, the staging last)
@@ -2711,28 +2711,34 @@ int run_slow(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* d_hf,
 
 int excl_scan(ecb_handle* h, const u32* in, u64 n, u32* out, u64* total);
 
+// The launched instantiations of k_stream (k_stream.inc, compiled three times): the kernel, the name rocprofv3 gives it (ecb_profile_kernel;
+// the exactness pass is not reported) and the workgroups per CU assumed when the occupancy query fails.
+struct StreamVariantRow { void (*kernel)(StreamArgs); const char* name; int blocks_per_cu; };
+const StreamVariantRow STREAM_VARIANTS[SV_N] = {
+    {ks_std::k_stream<false>, "ks_std::k_stream<false, false>", 4},
+    {ks_std::k_stream<false, true>, "ks_std::k_stream<false, true>", 4},      // with the range update fused in: fewer waves resident
+    {ks_short::k_stream<false>, "ks_short::k_stream<false, false>", 4},       // short reads: 9.9 KB of LDS per wave, four workgroups per CU
+    {ks_par::k_stream<false>, "ks_par::k_stream<false, false>", 5},
+    {ks_std::k_stream<true>, "", 0},                                          // SV_VERIFY: planned with SV_STD's residency
+};
+
 // Launch shape of k_stream over n records: the stream is cut into ECB_ROUNDS x as many slices as waves are resident at
 // once; the launch holds the resident waves only, which claim slice after slice.
 struct StreamPlan { u64 slices, chunk, blocks, pwaves; };
-int plan_stream(ecb_handle* h, u64 n, StreamPlan* P, bool ranges = false, bool short_reads = false, bool par = false) {
-    if (!h->resident_blocks) {                         // (asked once per handle: two runtime queries per batch add up on a streamed BAM)
-        int cus = 256, bpc = 4;
+int plan_stream(ecb_handle* h, u64 n, StreamPlan* P, StreamVariant v) {
+    if (!h->resident_blocks[SV_STD]) {                 // (asked once per handle: two runtime queries per batch add up on a streamed BAM)
+        int cus = 256;
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, ks_std::k_stream<false>, TPB, 0);
-        h->resident_blocks = (u64)std::max(cus, 1) * std::max(bpc, 1);
-        int bpr = 4;                                   // (the variant with the range update has fewer waves resident)
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpr, ks_std::k_stream<false, true>, TPB, 0);
-        h->resident_blocks_rg = (u64)std::max(cus, 1) * std::max(bpr, 1);
-        int bps = 4;                                   // (the variant for short reads: 9.9 KB of LDS per wave, four workgroups per CU)
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&bps, ks_short::k_stream<false>, TPB, 0);
-        h->resident_blocks_sh = (u64)std::max(cus, 1) * std::max(bps, 1);
-        int bpp = 5;
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpp, ks_par::k_stream<false>, TPB, 0);
-        h->resident_blocks_par = (u64)std::max(cus, 1) * std::max(bpp, 1);
+        for (int i = 0; i < SV_VERIFY; ++i) {
+            int bpc = STREAM_VARIANTS[i].blocks_per_cu;
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, STREAM_VARIANTS[i].kernel, TPB, 0);
+            h->resident_blocks[i] = (u64)std::max(cus, 1) * std::max(bpc, 1);
+        }
         h->rounds = getenv("ECB_ROUNDS") ? std::max(1, atoi(getenv("ECB_ROUNDS"))) : 24;   // (16 .. 32 measure alike on C3; fewer slices = fewer slice tails read twice)
         h->min_tiles = getenv("ECB_MIN_TILES") ? std::max(2, atoi(getenv("ECB_MIN_TILES"))) : 32;
     }
-    const u64 rounds = h->rounds, resident_blocks = short_reads ? h->resident_blocks_sh : (ranges ? h->resident_blocks_rg : (par ? h->resident_blocks_par : h->resident_blocks));
+    // (k_stream<true> is not asked: the exactness pass keeps the hot kernel's shape)
+    const u64 rounds = h->rounds, resident_blocks = h->resident_blocks[v == SV_VERIFY ? SV_STD : v];
     // slices: `rounds` per resident wave for balance, but not shorter than MIN_TILES tiles while every resident wave still gets
     // one -- a wave runs on past its slice's end to finish its open read, so every slice costs about one tile read twice
     // (at 5 tiles per slice, an eighth of config 3 on one of 8 GPUs, that was a fifth of the kernel)
@@ -2770,34 +2776,84 @@ int run_deferred(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* d
     return run_slow(h, d_rid, d_loc, d_hf, n, d_q, nq, verify, tw);
 }
 
+// Which variant a batch of n records takes: ranges first, then short reads, then par.
+StreamVariant pick_variant(const ecb_handle* h, u64 n) {
+    if (h->rng) return SV_STD_RANGES;
+    // Short reads (a 512-record tile holds more reads than a pass of 64 takes): the kernel with passes of 128 reads.  Known only when the
+    // caller has said how many reads the stream holds (ecb_hint_reads) -- the records-per-read of this batch is then n / (its share of them).
+    // (records per read: of the batches before this one where there are any; a first batch is judged as if it were the whole stream -- it must
+    //  then hold at least one record per announced read -- so that a long-read stream pushed in many batches is not taken for a short-read one)
+    const bool few = h->run.n_reads ? h->run.records_pushed < 7 * h->run.n_reads : (n >= h->reads_hint && n < 7 * h->reads_hint);
+    if (h->reads_hint != 0 && h->cfg.n_loci < MAX_LOCI_SHORT && h->cfg.n_haplotypes <= 8 && !getenv("ECB_NO_SHORT") &&
+        (getenv("ECB_FORCE_SHORT") || few)) return SV_SHORT;
+    // Loci that displace each other in the LDS table (paralogs: target ids anywhere): the compilation whose key compare settles displaced pairs
+    // in registers, once a batch has shown that more than a quarter of its tiles took the probe-on path (and back below a sixteenth).
+    if (!getenv("ECB_NO_PAR") && (getenv("ECB_FORCE_PAR") || h->par_stream)) return SV_PAR;
+    return SV_STD;
+}
+
+// zero the words of the counters every launch of k_stream starts from: the deferred reads' total with the stripes' counters behind it, the
+// park flag and the slice cursor
+int zero_launch_words(ecb_handle* h) {
+    HIPCHK(h, hipMemsetAsync(&h->ctr->n_queue, 0, (1 + QSTRIPES) * sizeof(u64), h->stream));
+    HIPCHK(h, hipMemsetAsync(&h->ctr->full, 0, sizeof(u32), h->stream));
+    HIPCHK(h, hipMemsetAsync(&h->ctr->next_slice, 0, sizeof(u64), h->stream));
+    return ECB_OK;
+}
+
+// One launch of variant v of k_stream over a batch of whole reads (read ids continuing from prev_rid), with k_sum_counts queued behind it.
+// The batch's first launch (launch 0) sets the batch up: resume points, wave counts, StreamCold staged through pin_cold.  A relaunch after a park
+// takes up what the parked launch left and zeroes the per-launch words only.  A push lets k_init_resume zero those, reserves the wave arena and
+// has its k_stream bracketed by the profiling events; the exactness pass (SV_VERIFY) inserts nothing -- no wave arena, no ranges -- and
+// counts the reads that differ: its wave counts and n_mismatch are cleared.  d_last: where k_sum_counts finds the batch's last read id (or null).
+int launch_stream(ecb_handle* h, StreamVariant v, const StreamPlan& P, const u32* d_rid, const u32* d_loc, const u32* d_hf, const int* d_pos, u64 n,
+                  u32 prev_rid, const u32* d_last, u32 launch, u64 offered, u64* timing = nullptr) {
+    const bool verify = v == SV_VERIFY;
+    int2* const rng = verify ? nullptr : (int2*)h->rng;
+    u64* d_resume = nullptr; u32* d_wcounts = nullptr;
+    POOL(h, P_RESUME, d_resume, 2 * P.slices);
+    if (!launch) k_init_resume<<<nblk(P.slices, TPB), TPB, 0, h->stream>>>(d_resume, P.slices, P.chunk, verify ? nullptr : (Counters*)h->ctr);
+    POOL(h, P_WCOUNTS, d_wcounts, 3 * P.pwaves);       // (every wave of a push's launch stores its three words when it ends)
+    if (launch) RCCHK(zero_launch_words(h));
+    else {
+        if (verify) {
+            HIPCHK(h, hipMemsetAsync(d_wcounts, 0, 3 * P.pwaves * sizeof(u32), h->stream));
+            RCCHK(zero_launch_words(h));
+            HIPCHK(h, hipMemsetAsync(&h->ctr->n_mismatch, 0, sizeof(u64), h->stream));
+        } else if (h->wave_arena_n < P.pwaves) {        // (only ever grows to the resident wave count; zero = nothing reserved)
+            HIPCHK(h, h->wave_arena.grow(2 * P.pwaves * sizeof(u64), 0, 2 * h->wave_arena_n * sizeof(u64), h->stream));
+            h->wave_arena_n = P.pwaves;
+        }
+        // (pinned: rewritten by the next batch, which starts after this one's host wait)
+        *h->pin_cold = StreamCold{h->arena, h->arena_cap, h->queue, h->queue_cap, d_resume, d_wcounts, verify ? nullptr : (u64*)h->wave_arena, timing,
+                                  P.chunk, prev_rid, d_pos, rng, verify ? 0u : h->cfg.n_loci, verify ? 0u : h->cfg.n_haplotypes};
+        HIPCHK(h, hipMemcpyAsync(h->d_cold, h->pin_cold.get(), sizeof(StreamCold), hipMemcpyHostToDevice, h->stream));
+    }
+    const StreamArgs a{d_rid, d_loc, d_hf, n, h->table, h->cap - 1, h->ctr, h->read_slot, h->run.reads_hi, h->d_cold,
+                       !verify && getenv("ECB_ABLATE") ? (u32)atoi(getenv("ECB_ABLATE")) : 0u, d_pos, rng};
+    if (h->prof && !verify) hipEventRecord(h->ev0, h->stream);
+    STREAM_VARIANTS[v].kernel<<<(unsigned)P.blocks, TPB, 0, h->stream>>>(a);
+    if (h->prof && !verify) hipEventRecord(h->ev1, h->stream);
+    k_sum_counts<<<1, 1024, 0, h->stream>>>(d_wcounts, P.pwaves, h->ctr, verify ? 1u : 0u, offered, h->queue_cap, d_last);
+    HIPCHK(h, hipGetLastError());
+    if (!verify) h->last_variant = v;
+    return ECB_OK;
+}
+
 // The exactness pass over one device-resident batch (whole reads, read ids continuing from prev_rid): every read's target
 // set is derived again from its records and compared, pair by pair, with the key of the EC the read was given.
 // Reads longer than a tile go through k_slow's compare.  *n_mismatch = reads in a wrong EC (0 = exact); *n_long = how many
 // took the long path.
 int verify_batch(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* d_hf, u64 n, u32 prev_rid, u64* n_mismatch, u64* n_long, u32 tw = 512u) {
     StreamPlan P;
-    RCCHK(plan_stream(h, n, &P));
-    u64* d_resume = nullptr; u32* d_wcounts = nullptr;
-    POOL(h, P_RESUME, d_resume, 2 * P.slices); POOL(h, P_WCOUNTS, d_wcounts, 3 * P.pwaves);
-    k_init_resume<<<nblk(P.slices, TPB), TPB, 0, h->stream>>>(d_resume, P.slices, P.chunk);
-    HIPCHK(h, hipMemsetAsync(d_wcounts, 0, 3 * P.pwaves * sizeof(u32), h->stream));
-    HIPCHK(h, hipMemsetAsync(&h->ctr->n_queue, 0, (1 + QSTRIPES) * sizeof(u64), h->stream));      // (the total and the stripes' counters behind it)
-    HIPCHK(h, hipMemsetAsync(&h->ctr->full, 0, sizeof(u32), h->stream));
-    HIPCHK(h, hipMemsetAsync(&h->ctr->next_slice, 0, sizeof(u64), h->stream));
-    HIPCHK(h, hipMemsetAsync(&h->ctr->n_mismatch, 0, sizeof(u64), h->stream));
-    *h->pin_cold = StreamCold{h->arena, h->arena_cap, h->queue, h->queue_cap, d_resume, d_wcounts, nullptr, nullptr, P.chunk, prev_rid,
-                              nullptr, nullptr, 0u, 0u};
-    HIPCHK(h, hipMemcpyAsync(h->d_cold, h->pin_cold.get(), sizeof(StreamCold), hipMemcpyHostToDevice, h->stream));
-    StreamArgs a{d_rid, d_loc, d_hf, n, h->table, h->cap - 1, h->ctr, h->read_slot, h->run.reads_hi, h->d_cold, 0u};
-    ks_std::k_stream<true><<<(unsigned)P.blocks, TPB, 0, h->stream>>>(a);
-    k_sum_counts<<<1, 1024, 0, h->stream>>>(d_wcounts, P.pwaves, h->ctr, 1u, 0ull, h->queue_cap);
-    HIPCHK(h, hipGetLastError());
+    RCCHK(plan_stream(h, n, &P, SV_VERIFY));
+    RCCHK(launch_stream(h, SV_VERIFY, P, d_rid, d_loc, d_hf, nullptr, n, prev_rid, nullptr, 0, 0));
     RCCHK(sync_counters(h));
     u64 nq = 0;
     RCCHK(run_deferred(h, d_rid, d_loc, d_hf, n, true, tw, &nq));
     *n_mismatch = h->hctr.n_mismatch;
     *n_long = nq;
-    HIPCHK(h, hipMemsetAsync(&h->ctr->n_queue, 0, (1 + QSTRIPES) * sizeof(u64), h->stream));
+    HIPCHK(h, hipMemsetAsync(&h->ctr->n_queue, 0, (1 + QSTRIPES) * sizeof(u64), h->stream));      // (the queue is drained: not a launch, the other per-launch words stay)
     h->hctr.n_queue = 0;
     return ECB_OK;
 }
@@ -2821,58 +2877,21 @@ int process_batch(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* 
     h->run.reads_hi = reads_after;
     // keep the table at most half full before a batch (it grows again, via k_slow, if a batch overfills it)
     while (h->n_ecs() * 2 > h->cap) { RCCHK(grow_table(h, h->cap * 4)); }
-    // Short reads (a 512-record tile holds more reads than a pass of 64 takes): the kernel with passes of 128 reads.  Known only when the
-    // caller has said how many reads the stream holds (ecb_hint_reads) -- the records-per-read of this batch is then n / (its share of them).
-    // (records per read: of the batches before this one where there are any; a first batch is judged as if it were the whole stream -- it must
-    //  then hold at least one record per announced read -- so that a long-read stream pushed in many batches is not taken for a short-read one)
-    const bool few = h->run.n_reads ? h->run.records_pushed < 7 * h->run.n_reads : (n >= h->reads_hint && n < 7 * h->reads_hint);
-    h->short_reads = hinted && !h->rng && h->cfg.n_loci < MAX_LOCI_SHORT && h->cfg.n_haplotypes <= 8 && !getenv("ECB_NO_SHORT") &&
-                     (getenv("ECB_FORCE_SHORT") || few);
-    // Loci that displace each other in the LDS table (paralogs: target ids anywhere): the compilation whose key compare settles displaced pairs
-    // in registers, once a batch has shown that more than a quarter of its tiles took the probe-on path (and back below a sixteenth).
-    const bool par = !h->short_reads && !h->rng && !getenv("ECB_NO_PAR") && (getenv("ECB_FORCE_PAR") || h->par_stream);
+    const StreamVariant v = pick_variant(h, n);
     StreamPlan P;
-    RCCHK(plan_stream(h, n, &P, h->rng != nullptr, h->short_reads, par));
-    const u64 waves = P.slices, chunk = P.chunk, blocks = P.blocks, pwaves = P.pwaves;
-    u64* d_resume = nullptr;
-    POOL(h, P_RESUME, d_resume, 2 * waves);
-    k_init_resume<<<nblk(waves, TPB), TPB, 0, h->stream>>>(d_resume, waves, chunk, h->ctr);
-    u32* d_wcounts = nullptr;
-    POOL(h, P_WCOUNTS, d_wcounts, 3 * pwaves);
-    if (h->wave_arena_n < pwaves) {                 // (only ever grows to the resident wave count; zero = nothing reserved)
-        HIPCHK(h, h->wave_arena.grow(2 * pwaves * sizeof(u64), 0, 2 * h->wave_arena_n * sizeof(u64), h->stream));
-        h->wave_arena_n = pwaves;
-    }
-    StreamCold cold{h->arena, h->arena_cap, h->queue, h->queue_cap, d_resume, d_wcounts, h->wave_arena, nullptr, chunk, h->run.prev_rid,
-                    d_pos, h->rng, h->cfg.n_loci, h->cfg.n_haplotypes};
+    RCCHK(plan_stream(h, n, &P, v));
+    u64* timing = nullptr;
 #ifdef ECB_TIMING
-    HIPCHK(h, hipMalloc(&cold.timing, 8 * sizeof(u64)));
-    HIPCHK(h, hipMemset(cold.timing, 0, 8 * sizeof(u64)));
+    HIPCHK(h, hipMalloc(&timing, 8 * sizeof(u64)));
+    HIPCHK(h, hipMemset(timing, 0, 8 * sizeof(u64)));
 #endif
-    *h->pin_cold = cold;      // (pinned: rewritten by the next batch, which starts after this one's host wait)
-    HIPCHK(h, hipMemcpyAsync(h->d_cold, h->pin_cold.get(), sizeof(StreamCold), hipMemcpyHostToDevice, h->stream));
-    StreamArgs a{d_rid, d_loc, d_hf, n, h->table, h->cap - 1, h->ctr, h->read_slot, h->run.reads_hi, h->d_cold,
-                 getenv("ECB_ABLATE") ? (u32)atoi(getenv("ECB_ABLATE")) : 0u, d_pos, h->rng};
     h->ctr_synced = false;
     const u64 probe_before = h->hctr.n_probe_tiles;
-    u64 offered = n;                                    // records offered to the filter (bam_utils.py:261): all of the batch
     int rc = ECB_OK;
     for (u32 launch = 0;; ++launch) {
-        if (launch) {                                   // per launch (the first one's: k_init_resume)
-            HIPCHK(h, hipMemsetAsync(&h->ctr->n_queue, 0, (1 + QSTRIPES) * sizeof(u64), h->stream));
-            HIPCHK(h, hipMemsetAsync(&h->ctr->full, 0, sizeof(u32), h->stream));
-            HIPCHK(h, hipMemsetAsync(&h->ctr->next_slice, 0, sizeof(u64), h->stream));
-        }
-        a.table = h->table; a.cap_mask = h->cap - 1;     // (d_wcounts: every wave of the launch stores its three words when it ends)
-        if (h->prof) hipEventRecord(h->ev0, h->stream);
-        if (h->rng) { ks_std::k_stream<false, true><<<(unsigned)blocks, TPB, 0, h->stream>>>(a); h->last_kernel = "ks_std::k_stream<false, true>"; }     // ... with the range update fused in
-        else if (h->short_reads) { ks_short::k_stream<false><<<(unsigned)blocks, TPB, 0, h->stream>>>(a); h->last_kernel = "ks_short::k_stream<false, false>"; }
-        else if (par) { ks_par::k_stream<false><<<(unsigned)blocks, TPB, 0, h->stream>>>(a); h->last_kernel = "ks_par::k_stream<false, false>"; }
-        else { ks_std::k_stream<false><<<(unsigned)blocks, TPB, 0, h->stream>>>(a); h->last_kernel = "ks_std::k_stream<false, false>"; }
-        if (h->prof) hipEventRecord(h->ev1, h->stream);
-        k_sum_counts<<<1, 1024, 0, h->stream>>>(d_wcounts, pwaves, h->ctr, 0u, offered, h->queue_cap, d_rid + rec_at(n - 1, tw));
-        offered = 0;                                    // (a relaunch after a park continues the same batch)
-        HIPCHK(h, hipGetLastError());
+        // records offered to the filter (bam_utils.py:261): all of the batch, once (a relaunch after a park continues the same batch)
+        rc = launch_stream(h, v, P, d_rid, d_loc, d_hf, d_pos, n, h->run.prev_rid, d_rid + rec_at(n - 1, tw), launch, launch ? 0 : n, timing);
+        if (rc != ECB_OK) break;
         rc = sync_counters(h);
         if (h->prof) {
             float ms = 0; hipEventElapsedTime(&ms, h->ev0, h->ev1);
@@ -2889,11 +2908,11 @@ int process_batch(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* 
 #ifdef ECB_TIMING
     {
         u64 t[8];
-        hipMemcpy(t, cold.timing, sizeof(t), hipMemcpyDeviceToHost); hipFree(cold.timing);
+        hipMemcpy(t, timing, sizeof(t), hipMemcpyDeviceToHost); hipFree(timing);
         static const char* nm[8] = {"(a) filter+heads", "tile decisions", "prefetch issue+clear+geometry", "(b) LDS tables", "hash entries", "(c) lookup", "publish/settle/slot stores", "-"};
         u64 tot = 0; for (int i = 0; i < 7; ++i) tot += t[i];
-        fprintf(stderr, "[ecb timing] %llu waves, clocks per wave:", (unsigned long long)waves);
-        for (int i = 0; i < 7; ++i) fprintf(stderr, "  %s %.0f (%.1f%%)", nm[i], (double)t[i] / waves, 100.0 * t[i] / std::max<u64>(tot, 1));
+        fprintf(stderr, "[ecb timing] %llu waves, clocks per wave:", (unsigned long long)P.slices);
+        for (int i = 0; i < 7; ++i) fprintf(stderr, "  %s %.0f (%.1f%%)", nm[i], (double)t[i] / P.slices, 100.0 * t[i] / std::max<u64>(tot, 1));
         fprintf(stderr, "  tile visits on the probe-on path %llu of %llu tiles", (unsigned long long)t[7], (unsigned long long)((n + WT - 1) / WT));
         fprintf(stderr, "\n");
     }
@@ -2944,18 +2963,12 @@ int stage_and_process(ecb_handle* h, const u32* rid, const u32* loc, const u32* 
     if (!n) return ECB_OK;
     RCCHK(ensure_staging(h, n));
     const bool rg = (h->cfg.flags & ECB_F_RANGES) != 0;
-    if (nc) {
-        HIPCHK(h, hipMemcpyAsync(h->st_rid, h->run.c_rid.data(), nc * 4, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->st_loc, h->run.c_loc.data(), nc * 4, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->st_hf, h->run.c_hf.data(), nc * 4, hipMemcpyHostToDevice, h->stream));
-        if (rg) HIPCHK(h, hipMemcpyAsync(h->st_pos, h->run.c_pos.data(), nc * 4, hipMemcpyHostToDevice, h->stream));
-    }
-    if (m) {
-        HIPCHK(h, hipMemcpyAsync(h->st_rid + nc, rid, m * 4, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->st_loc + nc, loc, m * 4, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->st_hf + nc, hf, m * 4, hipMemcpyHostToDevice, h->stream));
-        if (rg) HIPCHK(h, hipMemcpyAsync(h->st_pos + nc, pos, m * 4, hipMemcpyHostToDevice, h->stream));
-    }
+    // the staged streams {where on the device, the carried read's part, the caller's window}: all the carries are sent, then all the windows
+    const struct { void* st; const void *carry, *window; } streams[4] = {
+        {h->st_rid, h->run.c_rid.data(), rid}, {h->st_loc, h->run.c_loc.data(), loc}, {h->st_hf, h->run.c_hf.data(), hf}, {h->st_pos, h->run.c_pos.data(), pos}};
+    for (int w = 0; w < 2; ++w)
+        for (int i = 0; i < (rg ? 4 : 3) && (w ? m : nc); ++i)
+            HIPCHK(h, hipMemcpyAsync((u32*)streams[i].st + (w ? nc : 0), w ? streams[i].window : streams[i].carry, (w ? m : nc) * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));   // the carry vectors may be rewritten by the caller next
     h->run.c_rid.clear(); h->run.c_loc.clear(); h->run.c_hf.clear(); h->run.c_pos.clear();
     return process_batch(h, h->st_rid, h->st_loc, h->st_hf, rg ? h->st_pos : nullptr, n);
@@ -4150,8 +4163,8 @@ int ecb_profile_read(ecb_handle* h, double* ms, uint64_t* launches, uint64_t* re
 }
 
 // the stream kernel the last batch launched, as rocprofv3 names it (k_stream.inc is compiled more than once: which compilation a
-// batch takes is decided per batch, in process_batch)
-const char* ecb_profile_kernel(const ecb_handle* h) { return h ? h->last_kernel : ""; }
+// batch takes is decided per batch, in pick_variant)
+const char* ecb_profile_kernel(const ecb_handle* h) { return h && h->last_variant != SV_N ? STREAM_VARIANTS[h->last_variant].name : ""; }
 
 }  // extern "C"
 
