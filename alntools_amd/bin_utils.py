@@ -204,6 +204,66 @@ def apply_genotypes(ec_filename, gt_filename, grp_filename, out_filename, device
         LOG.error("Error: {}".format(str(e)))
 
 
+def counts_table(lname, hname, aln, uniq, locus_uniq):
+    """The text of the reference's ``report_alignment_counts`` (``AlignmentPropertyMatrix.py:450-462``): a header ``locus, aln_<h>...,
+    uniq_<h>..., locus_uniq`` and one tab-separated line per target, every number as the reference's float64 sums print (``12.0``)."""
+    cnt = np.vstack((np.asarray(aln), np.asarray(uniq), np.asarray(locus_uniq)[None, :]))
+    out = ["locus\t" + "\t".join('aln_%s' % h for h in hname) + "\t" + "\t".join('uniq_%s' % h for h in hname) + "\t" + "locus_uniq" + "\n"]
+    for t, name in enumerate(lname):
+        out.append("\t".join([name] + [str(float(v)) for v in cnt[:, t]]) + "\n")
+    return "".join(out)
+
+
+def count_alignments(ec_filename, out_filename, sample=None, device=0):
+    """``alntools count-alignments`` (EMASE's command of that name; ``AlignmentPropertyMatrix.report_alignment_counts``): the ``.bin``'s
+    alignment counts, allele-unique counts and locus-unique counts per target, counted on the GPU (``ecb.count_alignments``) and written
+    as the reference's table.  A multisample file, on which the reference raises, is counted over all its samples, or over the one
+    named ``sample``.  A failure is logged as ``Error: ...`` and raised again."""
+    import time
+    from . import ecb, utils
+    LOG = utils.get_logger()
+    try:
+        start_time = time.time()
+        LOG.info("Loading {}...".format(ec_filename))
+        m = ecload(ec_filename)
+        col = None
+        if sample is not None:
+            if sample not in m.sname:
+                raise KeyError("sample {} is not in {}".format(sample, ec_filename))
+            col = m.sname.index(sample)
+        LOG.info("Counting alignments...")
+        aln, uniq, locus_uniq = ecb.count_alignments(m.indptrA, m.indicesA, m.dataA, m.num_loci, m.num_haplotypes, m.indptrN, m.indicesN,
+                                                     m.dataN, sample=col, device=device)
+        with open(out_filename, 'w') as fh:
+            fh.write(counts_table(m.lname, m.hname, aln, uniq, locus_uniq))
+        LOG.info("{} created in total time: {}".format(out_filename, utils.format_time(start_time, time.time())))
+    except Exception as e:
+        LOG.error("Error: {}".format(e.args[0] if isinstance(e, KeyError) and e.args else str(e)))
+        raise
+
+
+def ecdump(ec_filename):
+    """``alntools ecdump`` (``bin_utils.py:959-976``): the shapes of a ``.bin``, as the reference's log lines.  Host only."""
+    from . import utils
+    LOG = utils.get_logger()
+    try:
+        LOG.info("Loading {}...".format(ec_filename))
+        m = ecload(ec_filename)
+        LOG.info("Number of reference transcripts (or targets): {:,}".format(m.num_loci))
+        LOG.info("Number of haplotypes: {:,}".format(m.num_haplotypes))
+        LOG.info("Number of samples: {:,}".format(m.num_samples))
+        LOG.info("Number of ECs (or reads): {:,}".format(m.num_reads))
+        LOG.info("Shape of alignment incidence matrix: {:,} x {:,} x {:,}".format(*m.shape))
+        if m.num_samples > 1:
+            LOG.info("Shape of EC count matrix: {:,} x {:,}".format(m.num_reads, m.num_samples))
+        elif m.num_samples == 1:
+            LOG.info("Shape of EC count matrix: {:,} x {:,}".format(m.num_reads, 1))
+        else:
+            LOG.error("Error: Something is wrong with EC count matrix")
+    except Exception as e:
+        LOG.error("Error: {}".format(str(e)))
+
+
 class MergePlan(object):
     """What ``plan_merge`` decides from the headers alone: the output's names and lengths and, per input, the maps of its
     columns and samples into the output's (``target_maps[k]`` is None when every input has the same target list)."""

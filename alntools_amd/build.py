@@ -15,11 +15,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wal
 
 
 def inputs():
-    """What libecb.so is compiled from: ecb.hip, the files under csrc/ it includes, and the public header."""
+    """What libecb.so is compiled from: ecb.hip, the files under csrc/ it includes, and the public headers."""
     import re
     csrc = os.path.dirname(SRC)
     local = set(re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(SRC).read(), re.M))
-    return [SRC] + [p for p in (os.path.normpath(os.path.join(csrc, n)) for n in sorted(local)) if os.path.dirname(p) == csrc] + [os.path.join(HERE, "..", "include", "ecb.h")]
+    return [SRC] + [p for p in (os.path.normpath(os.path.join(csrc, n)) for n in sorted(local)) if os.path.dirname(p) == csrc] + [os.path.join(HERE, "..", "include", h) for h in ("ecb.h", "ecb_count.h")]
 
 
 def needs_build():

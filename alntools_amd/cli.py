@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
 """Command line with the reference's hot-path sub-commands and options (``alntools/cli.py:43-113``):
-``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``, ``apply-genotypes``, ``ecmerge``, ``salmon2ec``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
+``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``, ``apply-genotypes``, ``ecmerge``, ``salmon2ec``, ``count-alignments``, ``ecdump``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
 from __future__ import annotations
 
 import glob
@@ -140,6 +140,33 @@ def salmon2ec(salmon_dir, ec_file, sample, targets, verbose):
         methods.salmon2ec(salmon_dir, ec_file, sample, targets)
     except Exception:
         sys.exit(1)                                                  # (logged as "Error: ..." by salmon_utils.convert)
+
+
+@cli.command('count-alignments', options_metavar='<options>', short_help='count the alignments of an EC file per target')
+@click.argument('ec_file', metavar='ec_file', type=click.Path(exists=True, resolve_path=True, dir_okay=False))
+@click.argument('out_file', metavar='out_file', type=click.Path(resolve_path=True, dir_okay=False, writable=True))
+@click.option('-s', '--sample', metavar='sample', default=None, help="count one sample of a multisample file (default: all of them)")
+@click.option('-v', '--verbose', count=True, help='enables verbose mode')
+def count_alignments(ec_file, out_file, sample, verbose):
+    """
+    Write the alignment, allele-unique and locus-unique read counts per target of a binary EC file (ec_file) to a table (out_file)
+    """
+    utils.configure_logging(verbose)
+    try:
+        methods.count_alignments(ec_file, out_file, sample)
+    except Exception:
+        sys.exit(1)                                                  # (logged as "Error: ..." by bin_utils.count_alignments)
+
+
+@cli.command('ecdump', options_metavar='<options>', short_help='show the shapes of an EC file')
+@click.argument('ec_file', metavar='ec_file', type=click.Path(exists=True, resolve_path=True, dir_okay=False))
+@click.option('-v', '--verbose', count=True, help='enables verbose mode')
+def ecdump(ec_file, verbose):
+    """
+    Show the number of targets, haplotypes, samples and ECs of a binary EC file (ec_file)
+    """
+    utils.configure_logging(verbose)
+    methods.ecdump(ec_file)
 
 
 if __name__ == '__main__':

@@ -4455,11 +4455,13 @@ extern "C" int ecb_hapcsc_to_csr(int device, uint32_t n_ecs, uint32_t n_loci, ui
 namespace {
 constexpr int GM_ITEMS = 4;                            // non-zeros per thread (16-byte loads)
 constexpr u32 GM_SHARDS = 256, GM_SHARD_WORDS = 16;    // descent balance: 256 counters, one 128-byte line each
-enum : u32 { GM_ERR_PTR = 1u, GM_ERR_LOCUS = 2u, GM_ERR_BITS = 4u, GM_ERR_MASK = 8u };
+enum : u32 { GM_ERR_PTR = 1u, GM_ERR_LOCUS = 2u, GM_ERR_BITS = 4u, GM_ERR_MASK = 8u, GM_SAW_ZERO = 16u };      // (GM_SAW_ZERO is no error: GM_ERRS does not list it)
 // words: [0] error bits, [3] kept non-zeros (the scan's total), then from word 16 the shards: shard s at word 16 + 16 s holds, summed over
 // the workgroups b with b % 256 == s, (descents among the non-zeros) - (descents at a row's first non-zero), mod 2^64.  The balance of the
 // whole CSR is 0 exactly when it is ascending.  (One counter for the whole grid took every wave's add: 1.3 ms at 13 M non-zeros.)
 // thread t: row pointer t (t <= E), mask word t (t < T), non-zeros [4t, 4t + 4) (< nnz)
+// COUNT: the same check for count-alignments, which has no mask: keep[i] = the set bits of non-zero i, and GM_SAW_ZERO when one holds none
+template <bool COUNT>
 __global__ __launch_bounds__(TPB) void k_gm_check(const int* indptr, u32 n_ecs, const int* indices, const int* data, u64 nnz, const u32* mask,
                                                   u32 n_loci, u32 n_haps, u32* keep, u64* words) {
     const u64 t = blockIdx.x * (u64)TPB + threadIdx.x;
@@ -4473,7 +4475,7 @@ __global__ __launch_bounds__(TPB) void k_gm_check(const int* indptr, u32 n_ecs, 
             else if (b > a && a > 0 && (u32)indices[a] <= (u32)indices[a - 1]) desc_row = 1;
         }
     }
-    if (t < n_loci && (mask[t] >> n_haps) != 0u) err |= GM_ERR_MASK;
+    if (!COUNT && t < n_loci && (mask[t] >> n_haps) != 0u) err |= GM_ERR_MASK;
     const u64 i0 = t * GM_ITEMS;
     if (i0 < nnz) {
         u32 c[GM_ITEMS], d[GM_ITEMS], k[GM_ITEMS];
@@ -4494,6 +4496,7 @@ __global__ __launch_bounds__(TPB) void k_gm_check(const int* indptr, u32 n_ecs, 
             prev = c[j];
             if ((d[j] >> n_haps) != 0u) err |= GM_ERR_BITS;
             if (c[j] >= n_loci) err |= GM_ERR_LOCUS;
+            else if (COUNT) { k[j] = (u32)__popc(d[j]); if (!d[j]) err |= GM_SAW_ZERO; }
             else k[j] = (d[j] & mask[c[j]]) != 0u;
         }
         if (whole && (reinterpret_cast<uintptr_t>(keep) & 15u) == 0u) reinterpret_cast<uint4*>(keep + i0)[0] = make_uint4(k[0], k[1], k[2], k[3]);
@@ -4583,7 +4586,7 @@ extern "C" int ecb_apply_mask_device(int device, uint32_t n_ecs, uint32_t n_loci
     CALLCHK(c, hipMemsetAsync(words, 0, n_words * 8, st));
     const u64 threads = std::max<u64>(std::max<u64>((u64)n_ecs + 1, n_loci), (nnz + GM_ITEMS - 1) / GM_ITEMS);
     const int* ip = (const int*)d_indptr; const int* ix = (const int*)d_indices; const int* da = (const int*)d_data; const u32* mk = (const u32*)d_mask;
-    k_gm_check<<<nblk(threads, TPB), TPB, 0, st>>>(ip, n_ecs, ix, da, nnz, mk, n_loci, n_haps, keep, words);
+    k_gm_check<false><<<nblk(threads, TPB), TPB, 0, st>>>(ip, n_ecs, ix, da, nnz, mk, n_loci, n_haps, keep, words);
     CALLCHK(c, hipGetLastError());
     CALLCHK(c, scan_launch(st, keep, nnz, excl, sums, words + 3, 1, excl + nnz));
     k_gm_scatter<<<nblk(threads, TPB), TPB, 0, st>>>(ip, n_ecs, ix, da, nnz, mk, n_loci, excl, (int*)d_out_indptr, (int*)d_out_indices, (int*)d_out_data);
@@ -4610,6 +4613,236 @@ extern "C" int ecb_apply_mask(int device, uint32_t n_ecs, uint32_t n_loci, uint3
     if (rc == ECB_OK) rc = ecb_apply_mask_device(device, n_ecs, n_loci, n_haps, nnz, ip.p, ix.p, da.p, mk.p, oip.p, oix.p, oda.p, kept);
     RCCHK(rc);
     return stage_out(c, {{out_indptr, &oip, rowb}, {out_indices, &oix, *kept * 4}, {out_data, &oda, *kept * 4}});
+}
+
+// ---- count-alignments: per-target read counts of a CSR A weighted by N (ecb_count_alignments / ecb_count_alignments_device) --------------
+// (AlignmentPropertyMatrix.count_alignments / count_unique_reads, AlignmentPropertyMatrix.py:429-448.)  A weighted scatter-add of every set
+// bit onto 2 H T + T int64 counters.  Global atomics run at the memory side, one 64-byte request per scattered lane (MI355X: a set bit each
+// would be ~30 M requests at config 3), so the non-zeros are first put in the order of their locus WINDOW -- CA window loci whose
+// (2 H + 1) x 8-byte counters fit LDS -- by ONE pass of the library's radix sort (the window number is a digit of its own in the key),
+// and a workgroup then adds a stretch of that order into LDS and sends each counter it touched to memory once, as consecutive 8-byte adds.
+// No loop over a row: the weight and the two row flags travel as one word per EC (ww), the flags from prefix sums over the non-zeros, and
+// the key pass finds a non-zero's row by bisecting the row pointers between its workgroup's first and last row.
+// Steps: k_ca_weights (N -> ww, N checked) | k_gm_check<true> (apply-mask's CSR check; set bits per non-zero) | k_scan_lb | [zero masks
+// present: k_ca_nonzero, k_scan_lb] | k_ca_rows | k_ca_keys | k_rs_* (one pass per 8 bits of window number) | k_ca_accum.
+namespace {
+constexpr u32 CA_LDS_BYTES = 80u << 10;              // of the window's counters: two workgroups per CU
+constexpr u32 CA_TPB = 512, CA_CHUNK = 32768;        // k_ca_accum: threads, and sorted non-zeros per workgroup
+constexpr u32 CA_KEY_ITEMS = 4;                      // k_ca_keys: non-zeros per thread
+constexpr u32 CA_WIN_SHIFT = 40;                     // key = window << 40 | locus within the window << H | mask   (H + log2 window <= 38)
+constexpr u64 CA_LEN1 = 1ull << 63, CA_POP1 = 1ull << 62, CA_WEIGHT = CA_POP1 - 1ull;      // ww[e]: row flags over the weight (< 2^62)
+enum : u32 { CA_ERR_NPTR = 1u, CA_ERR_EC = 2u, CA_ERR_NEG = 4u };
+// log2 of the loci per window: the largest power of two whose 2 H + 1 counters per locus fit CA_LDS_BYTES (H = 31: 128 loci, H = 1: 2048)
+inline u32 ca_window_bits(u32 n_haps) {
+    const u32 fit = CA_LDS_BYTES / 8u / (2u * n_haps + 1u);
+    return 31u - (u32)__builtin_clz(fit);
+}
+// thread j: column pointer j of N (j <= S) and entry j (j < nnz_n): everything checked, the entries of the sample(s) asked for added to ww
+__global__ __launch_bounds__(TPB) void k_ca_weights(const int* indptr_n, u32 n_samples, const int* indices_n, const int* data_n, u64 nnz_n,
+                                                    u32 n_ecs, long long sample, u64* ww, u64* words) {
+    const u64 j = blockIdx.x * (u64)TPB + threadIdx.x;
+    u32 err = 0;
+    if (j <= n_samples) {
+        const long long a = indptr_n[j];
+        if (a < 0 || (u64)a > nnz_n || (j == 0 && a != 0) || (j == n_samples && (u64)a != nnz_n)) err |= CA_ERR_NPTR;
+        else if (j < n_samples && indptr_n[j + 1] < a) err |= CA_ERR_NPTR;
+    }
+    if (j < nnz_n) {
+        const int e = indices_n[j], c = data_n[j];
+        if (e < 0 || (u32)e >= n_ecs) err |= CA_ERR_EC;
+        else if (c < 0) err |= CA_ERR_NEG;
+        else if (c > 0 && (sample < 0 || ((long long)j >= indptr_n[sample] && (long long)j < indptr_n[sample + 1])))
+            atomicAdd(reinterpret_cast<unsigned long long*>(ww + e), (unsigned long long)c);
+    }
+    if (err) atomicOr(reinterpret_cast<u32*>(words + 1), err);
+}
+// bits[i] = set bits of non-zero i  ->  1 where it has any (in place: the second prefix sum, taken only when a mask of 0 was seen)
+__global__ __launch_bounds__(TPB) void k_ca_nonzero(u32* bits, u64 nnz) {
+    const u64 i = blockIdx.x * (u64)TPB + threadIdx.x;
+    if (i < nnz) bits[i] = bits[i] != 0u;
+}
+// row e: CA_POP1 when its masks hold one set bit in all, CA_LEN1 when one of its non-zeros has a mask other than 0 (nz_excl null: no mask
+// is 0, and that is the row's length); excl arrays are exclusive prefix sums with nnz + 1 values
+__global__ __launch_bounds__(TPB) void k_ca_rows(const int* indptr, u32 n_ecs, u64 nnz, const u32* bits_excl, const u32* nz_excl, u64* ww) {
+    const u64 e = blockIdx.x * (u64)TPB + threadIdx.x;
+    if (e >= n_ecs) return;
+    const long long a = indptr[e], b = indptr[e + 1];
+    if (a < 0 || b <= a || (u64)b > nnz) return;
+    u64 f = 0;
+    if (bits_excl[b] - bits_excl[a] == 1u) f |= CA_POP1;
+    if ((nz_excl ? nz_excl[b] - nz_excl[a] : (u32)(b - a)) == 1u) f |= CA_LEN1;
+    if (f) ww[e] |= f;
+}
+// the last row of [lo, hi] whose pointer is at or below i (row pointers never fall: checked before this runs)
+__device__ __forceinline__ u32 ca_row_of(const int* indptr, u32 lo, u32 hi, u64 i) {
+    while (lo < hi) {
+        const u32 mid = lo + (hi - lo + 1u) / 2u;
+        if ((u64)(u32)indptr[mid] <= i) lo = mid; else hi = mid - 1u;
+    }
+    return lo;
+}
+// thread t: non-zeros [4t, 4t + 4) -> key (window, locus within it, mask) and value (row)
+__global__ __launch_bounds__(TPB) void k_ca_keys(const int* indptr, u32 n_ecs, const int* indices, const int* data, u64 nnz, u32 lgw, u32 n_haps,
+                                                 u64* keys, u32* rows) {
+    __shared__ u32 s_row[2];
+    const u64 b0 = blockIdx.x * (u64)(TPB * CA_KEY_ITEMS), b1 = std::min<u64>(nnz, b0 + TPB * CA_KEY_ITEMS) - 1;
+    if (threadIdx.x == 0) s_row[0] = ca_row_of(indptr, 0, n_ecs - 1, b0);
+    if (threadIdx.x == 64) s_row[1] = ca_row_of(indptr, 0, n_ecs - 1, b1);
+    __syncthreads();
+    const u64 i0 = b0 + (u64)threadIdx.x * CA_KEY_ITEMS;
+    if (i0 >= nnz) return;
+    const u32 hi = s_row[1];
+    u32 r = ca_row_of(indptr, s_row[0], hi, i0);
+#pragma unroll
+    for (u32 j = 0; j < CA_KEY_ITEMS; ++j) {
+        const u64 i = i0 + j;
+        if (i >= nnz) break;
+        if (r < hi && (u64)(u32)indptr[r + 1] <= i) r = ca_row_of(indptr, r + 1, hi, i);
+        const u32 t = (u32)indices[i];
+        keys[i] = (u64)(t >> lgw) << CA_WIN_SHIFT | (u64)(t & ((1u << lgw) - 1u)) << n_haps | (u32)data[i];
+        rows[i] = r;
+    }
+}
+// workgroup b: sorted non-zeros [b CA_CHUNK, (b + 1) CA_CHUNK), one window's stretch at a time: its counters zeroed in LDS (planes aln[H],
+// uniq[H], locus_uniq, each a window wide), every set bit added there, then every counter that is not 0 added to memory.  A counter is thus
+// sent once per (workgroup, window): at most nnz / CA_CHUNK + windows times the table, in runs of consecutive addresses.
+__global__ __launch_bounds__(CA_TPB) void k_ca_accum(const u64* keys, const u32* rows, u64 nnz, const u64* ww, u32 n_loci, u32 n_haps, u32 lgw,
+                                                     long long* aln, long long* uniq, long long* locus_uniq) {
+    extern __shared__ u64 s_tab[];
+    const u32 W = 1u << lgw, n_tab = W * (2u * n_haps + 1u), tid = threadIdx.x;
+    const u64 hmask = (1ull << n_haps) - 1ull;
+    const u64 c0 = blockIdx.x * (u64)CA_CHUNK, c1 = std::min<u64>(nnz, c0 + CA_CHUNK);
+    for (u64 pos = c0; pos < c1;) {
+        const u64 win = keys[pos] >> CA_WIN_SHIFT;
+        u64 lo = pos, end = c1;                      // keys[lo] is of this window; keys[end] is not, or end = c1
+        while (lo + 1 < end) {
+            const u64 mid = (lo + end) / 2;
+            if ((keys[mid] >> CA_WIN_SHIFT) == win) lo = mid; else end = mid;
+        }
+        for (u32 k = tid; k < n_tab; k += CA_TPB) s_tab[k] = 0;
+        __syncthreads();
+        for (u64 i = pos + tid; i < end; i += CA_TPB) {
+            const u64 key = keys[i], g = ww[rows[i]], w = g & CA_WEIGHT;
+            u32 m = (u32)(key & hmask);
+            if (!w || !m) continue;
+            const u32 lw = (u32)(key >> n_haps) & (W - 1u);
+            if (g & CA_LEN1) atomicAdd(reinterpret_cast<unsigned long long*>(&s_tab[2u * n_haps * W + lw]), (unsigned long long)w);
+            for (; m; m &= m - 1u) {
+                const u32 h = (u32)__ffs((int)m) - 1u;
+                atomicAdd(reinterpret_cast<unsigned long long*>(&s_tab[h * W + lw]), (unsigned long long)w);
+                if (g & CA_POP1) atomicAdd(reinterpret_cast<unsigned long long*>(&s_tab[(n_haps + h) * W + lw]), (unsigned long long)w);
+            }
+        }
+        __syncthreads();
+        for (u32 k = tid; k < n_tab; k += CA_TPB) {
+            const u64 v = s_tab[k];
+            const u64 t = (win << lgw) + (k & (W - 1u));
+            if (!v || t >= n_loci) continue;
+            const u32 plane = k >> lgw;
+            long long* dst = plane < n_haps ? aln : plane < 2u * n_haps ? uniq : locus_uniq;
+            const u32 h = plane < n_haps ? plane : plane < 2u * n_haps ? plane - n_haps : 0u;
+            if (dst) atomicAdd(reinterpret_cast<unsigned long long*>(dst + (u64)h * n_loci + t), (unsigned long long)v);
+        }
+        __syncthreads();
+        pos = end;
+    }
+}
+const ErrBit CA_ERRS[] = {
+    {CA_ERR_NPTR, ECB_ERR_CONTRACT, "malformed N: column pointers do not start at 0, go backwards or do not end at nnz_n"},
+    {CA_ERR_EC, ECB_ERR_CONTRACT, "malformed N: an EC index at or beyond n_ecs"},
+    {CA_ERR_NEG, ECB_ERR_CONTRACT, "malformed N: a negative count"},
+};
+// what both entry points refuse before anything is allocated
+int ca_check_args(uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, uint64_t nnz_a, const void* indptr_a, const void* indices_a, const void* data_a,
+                  uint32_t n_samples, uint64_t nnz_n, const void* indptr_n, const void* indices_n, const void* data_n, int64_t sample) {
+    if (!indptr_a || !indptr_n || !n_loci || !n_haps || n_haps > 31 || !n_samples) return fail(nullptr, ECB_ERR_ARG, "bad argument");
+    if ((nnz_a && (!indices_a || !data_a)) || (nnz_n && (!indices_n || !data_n))) return fail(nullptr, ECB_ERR_ARG, "bad argument");
+    if (n_ecs >= (1u << 31) - 1u || nnz_n >= (1ull << 31) || n_samples >= (1u << 31) - 1u)
+        return fail(nullptr, ECB_ERR_LIMIT, "the matrices exceed the .bin format's int32 limits");
+    if (nnz_a >= (1ull << 30)) return fail(nullptr, ECB_ERR_LIMIT, "count-alignments: 2^30 non-zeros or more");       // (radix_sort_pairs64)
+    if (sample < -1 || sample >= (int64_t)n_samples) return fail(nullptr, ECB_ERR_CONTRACT, "count-alignments: no such sample (%lld of %u)", (long long)sample, n_samples);
+    return ECB_OK;
+}
+}  // namespace
+
+extern "C" int ecb_count_alignments_device(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, uint64_t nnz, const void* d_indptr_a,
+                                           const void* d_indices_a, const void* d_data_a, uint32_t n_samples, uint64_t nnz_n, const void* d_indptr_n,
+                                           const void* d_indices_n, const void* d_data_n, int64_t sample, void* d_aln, void* d_uniq,
+                                           void* d_locus_uniq) {
+    RCCHK(ca_check_args(n_ecs, n_loci, n_haps, nnz, d_indptr_a, d_indices_a, d_data_a, n_samples, nnz_n, d_indptr_n, d_indices_n, d_data_n, sample));
+    Call c(device, "count-alignments: "); if (c.rc) return c.rc;
+    hipStream_t st = c.st;
+    const u64 n_words = GM_SHARD_WORDS * (1 + GM_SHARDS);          // apply-mask's words; [1] the error bits of N, [2] the second scan's total
+    u64* words = c.get<u64>(CV_WORDS, n_words);
+    u32 *bits = c.get<u32>(CV_X0, nnz), *bits_excl = c.get<u32>(CV_X1, nnz + 1), *sums = c.get<u32>(CV_SUMS2, scan_words(nnz));
+    u64* ww = c.get<u64>(CV_X2, n_ecs);
+    if (const int rc = c.missing()) return rc;
+    const int* ip = (const int*)d_indptr_a; const int* ix = (const int*)d_indices_a; const int* da = (const int*)d_data_a;
+    CALLCHK(c, hipMemsetAsync(words, 0, n_words * 8, st));
+    CALLCHK(c, hipMemsetAsync(ww, 0, std::max<u64>(n_ecs, 1) * 8, st));
+    k_ca_weights<<<nblk(std::max<u64>(nnz_n, (u64)n_samples + 1), TPB), TPB, 0, st>>>((const int*)d_indptr_n, n_samples, (const int*)d_indices_n,
+                                                                                     (const int*)d_data_n, nnz_n, n_ecs, sample, ww, words);
+    k_gm_check<true><<<nblk(std::max<u64>((u64)n_ecs + 1, (nnz + GM_ITEMS - 1) / GM_ITEMS), TPB), TPB, 0, st>>>(ip, n_ecs, ix, da, nnz, nullptr, n_loci,
+                                                                                                             n_haps, bits, words);
+    CALLCHK(c, hipGetLastError());
+    CALLCHK(c, scan_launch(st, bits, nnz, bits_excl, sums, words + 3, 1, bits_excl + nnz));
+    std::vector<u64> back(n_words);
+    if (const int rc = c.read_back(back.data(), words, n_words, GM_ERRS)) return rc;
+    u64 balance = 0;
+    for (u32 k = 1; k <= GM_SHARDS; ++k) balance += back[GM_SHARD_WORDS * k];
+    if (balance != 0) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSR: columns not strictly ascending within a row (unsorted or duplicate)");
+    if (const int rc = refuse_bits(nullptr, CA_ERRS, (u32)back[1])) return rc;
+    if (back[3] >= (1ull << 32)) return fail(nullptr, ECB_ERR_LIMIT, "more than 2^32-1 set haplotype bits");
+    // the input is well formed: from here on the outputs are written
+    u32* nz_excl = nullptr;
+    if ((u32)back[0] & GM_SAW_ZERO) {
+        nz_excl = c.get<u32>(CV_X3, nnz + 1);
+        if (const int rc = c.missing()) return rc;
+        k_ca_nonzero<<<nblk(nnz, TPB), TPB, 0, st>>>(bits, nnz);
+        CALLCHK(c, scan_launch(st, bits, nnz, nz_excl, sums, words + 2, 1, nz_excl + nnz));
+    }
+    if (n_ecs) k_ca_rows<<<nblk(n_ecs, TPB), TPB, 0, st>>>(ip, n_ecs, nnz, bits_excl, nz_excl, ww);
+    const u64 plane = (u64)n_haps * n_loci * 8;
+    if (d_aln) CALLCHK(c, hipMemsetAsync(d_aln, 0, plane, st));
+    if (d_uniq) CALLCHK(c, hipMemsetAsync(d_uniq, 0, plane, st));
+    if (d_locus_uniq) CALLCHK(c, hipMemsetAsync(d_locus_uniq, 0, (u64)n_loci * 8, st));
+    if (nnz) {
+        const u32 lgw = ca_window_bits(n_haps);
+        u64 *k0 = c.get<u64>(CV_KEYS0, nnz), *k1 = c.get<u64>(CV_KEYS1, nnz);
+        u32 *v0 = c.get<u32>(CV_VALS0, nnz), *v1 = c.get<u32>(CV_VALS1, nnz);
+        SortScratch ss{c.get<u32>(CV_HIST, rs_words(nnz)), c.get<u32>(CV_OFFS, RS_AUX_WORDS), words + 4};
+        if (const int rc = c.missing()) return rc;
+        k_ca_keys<<<nblk(nnz, TPB * CA_KEY_ITEMS), TPB, 0, st>>>(ip, n_ecs, ix, da, nnz, lgw, n_haps, k0, v0);
+        SortBufs s{{k0, k1}, {v0, v1}};
+        CALLCHK(c, radix_sort_pairs64(st, s, nnz, ss, msb_mask((u64)(n_loci - 1) >> lgw) << CA_WIN_SHIFT));
+        const u32 lds = ((2u * n_haps + 1u) << lgw) * 8u;
+        // (more than the 64 KB a kernel may take unasked; per device, so asked for on every call)
+        CALLCHK(c, hipFuncSetAttribute((const void*)k_ca_accum, hipFuncAttributeMaxDynamicSharedMemorySize, CA_LDS_BYTES));
+        k_ca_accum<<<nblk(nnz, CA_CHUNK), CA_TPB, lds, st>>>(s.keys(), s.vals(), nnz, ww, n_loci, n_haps, lgw, (long long*)d_aln, (long long*)d_uniq,
+                                                             (long long*)d_locus_uniq);
+        CALLCHK(c, hipGetLastError());
+    }
+    CALLCHK(c, hipStreamSynchronize(st));
+    return ECB_OK;
+}
+
+extern "C" int ecb_count_alignments(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, uint64_t nnz, const int32_t* indptr_a,
+                                    const int32_t* indices_a, const int32_t* data_a, uint32_t n_samples, uint64_t nnz_n, const int32_t* indptr_n,
+                                    const int32_t* indices_n, const int32_t* data_n, int64_t sample, int64_t* aln, int64_t* uniq, int64_t* locus_uniq) {
+    RCCHK(ca_check_args(n_ecs, n_loci, n_haps, nnz, indptr_a, indices_a, data_a, n_samples, nnz_n, indptr_n, indices_n, data_n, sample));
+    Call c(device, "count-alignments: "); if (c.rc) return c.rc;
+    const u64 plane = (u64)n_haps * n_loci * 8;
+    DevBuf<> ipa, ixa, daa, ipn, ixn, dan, oa, ou, ol;
+    std::vector<StageIn> in = {{&ipa, indptr_a, ((u64)n_ecs + 1) * 4}, {&ixa, indices_a, nnz * 4}, {&daa, data_a, nnz * 4},
+                               {&ipn, indptr_n, ((u64)n_samples + 1) * 4}, {&ixn, indices_n, nnz_n * 4}, {&dan, data_n, nnz_n * 4}};
+    if (aln) in.push_back({&oa, nullptr, plane});
+    if (uniq) in.push_back({&ou, nullptr, plane});
+    if (locus_uniq) in.push_back({&ol, nullptr, (u64)n_loci * 8});
+    int rc = stage_in(c, in);
+    if (rc == ECB_OK) rc = ecb_count_alignments_device(device, n_ecs, n_loci, n_haps, nnz, ipa.p, ixa.p, daa.p, n_samples, nnz_n, ipn.p, ixn.p, dan.p,
+                                                       sample, oa.p, ou.p, ol.p);
+    RCCHK(rc);
+    return stage_out(c, {{aln, &oa, aln ? plane : 0}, {uniq, &ou, uniq ? plane : 0}, {locus_uniq, &ol, locus_uniq ? (u64)n_loci * 8 : 0}});
 }
 
 // ---- ecmerge: several .bin files' A and N combined into one (ecb_combine / ecb_combine_device) ---------------------------------------------

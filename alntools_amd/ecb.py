@@ -38,6 +38,8 @@ SYMBOLS = ("ecb_abi_version", "ecb_device_count", "ecb_create", "ecb_destroy", "
            "ecb_csr_to_hapcsc", "ecb_hapcsc_to_csr", "ecb_merge", "ecb_push_device_tiled", "ecb_verify_device_tiled",
            "ecb_apply_mask_device", "ecb_apply_mask", "ecb_combine_device", "ecb_combine",
            "ecb_salmon_ecs_device", "ecb_salmon_ecs")
+#: every symbol include/ecb_count.h declares (ecb.h includes it)
+COUNT_SYMBOLS = ("ecb_count_alignments_device", "ecb_count_alignments")
 ABI_VERSION = 4            # include/ecb.h: ECB_ABI_VERSION
 
 
@@ -166,6 +168,9 @@ def load():
     if not ab or hasattr(lib, "ecb_salmon_ecs"):
         for f in (lib.ecb_salmon_ecs_device, lib.ecb_salmon_ecs):
             f.argtypes = [C.c_int, vp, u64, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, u64] + [vp] * 5 + [C.POINTER(u64)]
+    if not ab or hasattr(lib, "ecb_count_alignments"):
+        for f in (lib.ecb_count_alignments_device, lib.ecb_count_alignments):
+            f.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.c_uint32, u64, vp, vp, vp, C.c_int64, vp, vp, vp]
     lib.ecb_csr_to_hapcsc_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.POINTER(u64)]
     lib.ecb_hapcsc_to_csr_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, u64, vp, vp, vp, C.POINTER(u64)]
     _lib = lib
@@ -298,6 +303,40 @@ def apply_mask(indptr, indices, data, mask, n_haps, device=0):
     kept = C.c_uint64()
     _check(lib, lib.ecb_apply_mask(device, E, T, n_haps, nnz, _ptr(ip), _ptr(ix), _ptr(da), _ptr(mk), _ptr(oip), _ptr(oix), _ptr(oda), C.byref(kept)))
     return oip, oix[:kept.value], oda[:kept.value]
+
+
+def count_alignments(indptr, indices, data, n_loci, n_haps, indptr_n, indices_n, data_n, sample=None, device=0):
+    """count-alignments on the GPU: the per-target read counts of CSR A (``.bin``'s bitmask values) weighted by CSC N -- the reference's
+    ``count_alignments()``, ``count_unique_reads(ignore_haplotype=False)`` and ``count_unique_reads(ignore_haplotype=True)``
+    (``AlignmentPropertyMatrix.py:429-448``).  ``sample``: None = every EC weighs the sum of its row of N, else the index of one column.
+    numpy arrays go through ``ecb_count_alignments`` (host arrays, no PyTorch), CUDA tensors through ``ecb_count_alignments_device``
+    (``device`` is then the tensors' own).  Returns ``(aln[H, T], uniq[H, T], locus_uniq[T])``, int64, of the same kind as the input.
+    Malformed input or an unknown sample raises :class:`EcbError` (``ECB_ERR_CONTRACT``)."""
+    lib = load()
+    s = -1 if sample is None else int(sample)
+    if hasattr(indptr, "data_ptr"):
+        import torch
+        dev = indptr.device
+        ip, ix, da, pn, xn, dn = (t.contiguous().to(torch.int32) for t in (indptr, indices, data, indptr_n, indices_n, data_n))
+        E, nnz, S, nnz_n = ip.numel() - 1, ix.numel(), pn.numel() - 1, xn.numel()
+        if da.numel() != nnz or dn.numel() != nnz_n:
+            raise ValueError("indices and data differ in length")
+        aln = torch.empty((n_haps, n_loci), dtype=torch.int64, device=dev)
+        uniq = torch.empty((n_haps, n_loci), dtype=torch.int64, device=dev)
+        lu = torch.empty(n_loci, dtype=torch.int64, device=dev)
+        _check(lib, lib.ecb_count_alignments_device(dev.index or 0, E, n_loci, n_haps, nnz, _dev_ptr(ip), _dev_ptr(ix), _dev_ptr(da), S, nnz_n,
+                                                    _dev_ptr(pn), _dev_ptr(xn), _dev_ptr(dn), s, _dev_ptr(aln), _dev_ptr(uniq), _dev_ptr(lu)))
+        return aln, uniq, lu
+    ip, ix, da, pn, xn, dn = (np.ascontiguousarray(a, dtype=np.int32) for a in (indptr, indices, data, indptr_n, indices_n, data_n))
+    E, nnz, S, nnz_n = len(ip) - 1, len(ix), len(pn) - 1, len(xn)
+    if len(da) != nnz or len(dn) != nnz_n:
+        raise ValueError("indices and data differ in length")
+    aln = np.empty((n_haps, n_loci), dtype=np.int64)
+    uniq = np.empty((n_haps, n_loci), dtype=np.int64)
+    lu = np.empty(n_loci, dtype=np.int64)
+    _check(lib, lib.ecb_count_alignments(device, E, n_loci, n_haps, nnz, _ptr(ip), _ptr(ix), _ptr(da), S, nnz_n, _ptr(pn), _ptr(xn), _ptr(dn), s,
+                                         _ptr(aln), _ptr(uniq), _ptr(lu)))
+    return aln, uniq, lu
 
 
 def combine(parts, n_loci, n_haps, n_samples, device=0):

@@ -375,4 +375,8 @@ const char* ecb_profile_kernel(const ecb_handle* h);
 #ifdef __cplusplus
 }
 #endif
+
+/* The entry points that read a .bin back (count-alignments) are declared in a header of their own, part of this ABI. */
+#include "ecb_count.h"
+
 #endif /* ECB_H */
