@@ -139,6 +139,73 @@ def load_groups(m, grp_filename):
     return gname, groups
 
 
+def group_map(m, grp_filename):
+    """Group file -> ``(gname, map_ptr, map_idx, lengths)``: what ``ecbundle`` hands to ``ecb.bundle``.  The file is read by
+    ``load_groups`` (every line ``gene, tx1, tx2, ...``; a transcript that is not a target is a KeyError); group ``g`` is line ``g``.
+    ``map_ptr`` (T + 1) / ``map_idx``: per target the ids of its groups, ascending -- a transcript may be in several groups, or in none; one
+    listed twice on a line counts once.  ``lengths[g, h]`` is the largest length of ``g``'s members for haplotype ``h``, 0 for a group
+    without members.  A group name on two lines is a ValueError naming it (the reference would write two targets of one name)."""
+    gname, groups = load_groups(m, grp_filename)
+    seen = set()
+    for g in gname:
+        if g in seen:
+            raise ValueError("{}: group {} is listed more than once".format(grp_filename, g))
+        seen.add(g)
+    T, H, G = m.num_loci, m.num_haplotypes, len(gname)
+    gid = np.repeat(np.arange(G, dtype=np.int64), [len(t) for t in groups])
+    tid = np.array([t for tids in groups for t in tids], dtype=np.int64)
+    pair = np.unique(tid * max(G, 1) + gid)                            # (target, group) pairs, once each, by target then group
+    tid, gid = pair // max(G, 1), pair % max(G, 1)
+    map_ptr = np.searchsorted(tid, np.arange(T + 1)).astype(np.int32)
+    lens = np.asarray(m.lengths).astype(np.int64).reshape(T, H)
+    lengths = np.zeros((G, H), dtype=np.int64)
+    np.maximum.at(lengths, gid, lens[tid])
+    return gname, map_ptr, gid.astype(np.int32), lengths
+
+
+def ecbundle(ec_filename, grp_filename, out_filename, device=0):
+    """``alntools ecbundle``: the targets of a ``.bin`` collapsed into the groups of a group file (isoforms into genes) -- the
+    reference's ``AlignmentPropertyMatrix.bundle(reset=True)`` (``AlignmentPropertyMatrix.py:219-275``), then the rows that have become
+    equal folded into one EC as ``ecmerge`` folds them.  The group file is parsed here (``group_map``) before libecb is loaded; A and
+    N are bundled on the GPU (``ecb.bundle``): the mask at (row, group) is the OR of the row's masks over the group's transcripts, rows
+    with equal (group, mask) sets are one EC, numbered by first appearance, counts add per (EC, sample).  The output's targets are the
+    groups in file order, each as long as its longest member; haplotypes and samples are copied.  Any failure is logged as
+    ``Error: ...``, no file is written and the exception is raised again (the command line exits with status 1)."""
+    import time
+    from . import utils
+    LOG = utils.get_logger()
+    try:
+        start_time = time.time()
+        LOG.info("Loading {}...".format(ec_filename))
+        m = ecload(ec_filename)
+        gname, map_ptr, map_idx, lengths = group_map(m, grp_filename)
+        if not gname:
+            raise ValueError("{}: no groups".format(grp_filename))
+        LOG.info("Bundling {:,} targets into {:,} groups...".format(m.num_loci, len(gname)))
+        from . import ecb
+        A_N = ecb.bundle(m.indptrA, m.indicesA, m.dataA, m.indptrN, m.indicesN, m.dataN, m.num_loci, m.num_haplotypes, len(gname),
+                         map_ptr, map_idx, device=device)
+        out = ECMatrices(m.hname, gname, lengths, m.sname, *A_N)
+        LOG.info("Saving to {}...".format(out_filename))
+        LOG.info("Number of haplotypes: {:,}".format(out.num_haplotypes))
+        LOG.info("Number of reference targets: {:,}".format(out.num_loci))
+        LOG.info("Number of samples: {:,}".format(out.num_samples))
+        LOG.info("Number of equivalence classes: {:,} (from {:,} rows)".format(out.num_reads, m.num_reads))
+        b = ecsave2_bytes(out)
+        try:
+            with open(out_filename, 'wb') as fh:
+                fh.write(b)
+        except BaseException:
+            if os.path.exists(out_filename):
+                os.remove(out_filename)
+            raise
+        LOG.info("Saving completed")
+        LOG.info("{} created in total time: {}".format(out_filename, utils.format_time(start_time, time.time())))
+    except Exception as e:
+        LOG.error("Error: {}".format(e.args[0] if isinstance(e, KeyError) and e.args else str(e)))
+        raise
+
+
 def genotype_mask(m, gt_filename, gname, groups):
     """Genotype file -> ``mask u32[T]`` (bit h = haplotype h allowed at that locus) -- ``AlignmentPropertyMatrix.apply_genotypes``
     (``AlignmentPropertyMatrix.py:483-505``): the leading lines that start with ``#`` are skipped; every later line gives ``gene,

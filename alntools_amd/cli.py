@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
 """Command line with the reference's hot-path sub-commands and options (``alntools/cli.py:43-113``):
-``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``, ``apply-genotypes``, ``ecmerge``, ``salmon2ec``, ``count-alignments``, ``ecdump``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
+``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``, ``apply-genotypes``, ``ecmerge``, ``ecbundle``, ``salmon2ec``, ``count-alignments``, ``ecdump``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
 from __future__ import annotations
 
 import glob
@@ -123,6 +123,22 @@ def ecmerge(inputs, directory, output, verbose):
         methods.ecmerge(input_files, output)
     except Exception:
         sys.exit(1)                                                  # (logged as "Error: ..." by bin_utils.ecmerge)
+
+
+@cli.command('ecbundle', options_metavar='<options>', short_help='collapse the targets of an EC file into groups')
+@click.argument('ec_file', metavar='ec_file', type=click.Path(exists=True, resolve_path=True, dir_okay=False))
+@click.argument('grp_file', metavar='grp_file', type=click.Path(exists=True, resolve_path=True, dir_okay=False))
+@click.argument('out_file', metavar='out_file', type=click.Path(resolve_path=True, dir_okay=False, writable=True))
+@click.option('-v', '--verbose', count=True, help='enables verbose mode')
+def ecbundle(ec_file, grp_file, out_file, verbose):
+    """
+    Collapse the targets of a binary EC file (ec_file) into the groups of grp_file (isoforms into genes) and write the result (out_file)
+    """
+    utils.configure_logging(verbose)
+    try:
+        methods.ecbundle(ec_file, grp_file, out_file)
+    except Exception:
+        sys.exit(1)                                                  # (logged as "Error: ..." by bin_utils.ecbundle)
 
 
 @cli.command('salmon2ec', options_metavar='<options>', short_help='convert a salmon eq_classes file to EC')

@@ -4864,7 +4864,8 @@ struct CbPart {                                  // one part, device pointers, a
 // base arrays (u64, n_parts + 1 each, exclusive sums): rows, pairs, N non-zeros, row pointers (E + 1 per part), N column pointers (S + 1)
 enum { CB_ROWS = 0, CB_PAIRS, CB_NZ, CB_APTR, CB_NPTR, CB_BASES };
 enum : u32 { CB_ERR_PTR = 1u, CB_ERR_LOCUS = 2u, CB_ERR_BITS = 4u, CB_ERR_ORDER = 8u, CB_ERR_MAP = 16u, CB_ERR_NPTR = 32u, CB_ERR_NEC = 64u,
-             CB_ERR_NCOUNT = 128u, CB_ERR_SMAP = 256u, CB_ERR_LOST = 512u, CB_ERR_SUM = 1024u };
+             CB_ERR_NCOUNT = 128u, CB_ERR_SMAP = 256u, CB_ERR_LOST = 512u, CB_ERR_SUM = 1024u,
+             BD_ERR_MPTR = 2048u, BD_ERR_MIDX = 4096u, BD_ERR_MORDER = 8192u, BD_ERR_WIDE = 16384u };      // (ecb_bundle's group map)
 constexpr u32 CB_SHARDS = 256, CB_SHARD_WORDS = 16;    // arena sizing: per shard (its own 128-byte line) the largest and the summed wave demand
 // the largest p < n with base[p] <= x (x below base[n]: an empty part never wins, the part after it starts at the same place)
 __device__ __forceinline__ u32 cb_find(const u64* base, u32 n, u64 x) {
@@ -4899,6 +4900,29 @@ __device__ __forceinline__ void cb_run_sum(u64 key, u64 v, bool valid, u64 i, u6
     if (before || after) atomicAdd(reinterpret_cast<unsigned long long*>(dst + at), (unsigned long long)v);
     else dst[at] = v;
 }
+// pointer k of the n + 1 of a CSR / CSC with nnz entries: from 0 to nnz, never falling
+__device__ __forceinline__ bool cb_ptr_bad(const int* ptr, u64 k, u64 n, u64 nnz) {
+    const long long a = ptr[k];
+    if (a < 0 || (u64)a > nnz || (k == 0 && a != 0) || (k == n && (u64)a != nnz)) return true;
+    return k < n && ptr[k + 1] < a;
+}
+// non-zero li of row r of a part's A (checked pointers): its mask, its column, its place after the one before it
+__device__ __forceinline__ u32 cb_nz_bad(const CbPart& q, long long li, u32 r, u32 n_haps, int c, u32 d) {
+    u32 e = 0;
+    if (d == 0u || (d >> n_haps) != 0u) e |= CB_ERR_BITS;
+    if (c < 0 || (u32)c >= q.n_loci) e |= CB_ERR_LOCUS;
+    if (li > q.ipa[r] && q.ixa[li - 1] >= c) e |= CB_ERR_ORDER;                          // ascending as the part stores it
+    return e;
+}
+// the error bits of a wave's lanes into the call's error word: one atomic per wave that has any
+__device__ __forceinline__ void cb_raise(u32 e, u32* err) {
+    if (__ballot(e != 0u)) {
+        u32 w = e;
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) w |= (u32)__shfl_xor((int)w, d);
+        if ((threadIdx.x & 63u) == 0u) atomicOr(err, w);
+    }
+}
 // row pointers of A (one thread per pointer of every part) and column pointers of N
 __global__ __launch_bounds__(TPB) void k_cb_check(const CbPart* P, u32 n_parts, const u64* base, u32* err) {
     const u64 t = blockIdx.x * (u64)TPB + threadIdx.x;
@@ -4909,17 +4933,13 @@ __global__ __launch_bounds__(TPB) void k_cb_check(const CbPart* P, u32 n_parts, 
         const u32 p = cb_find(ab, n_parts, t);
         const CbPart& q = P[p];
         const u64 k = t - ab[p];
-        const long long a = q.ipa[k];
-        if (a < 0 || (u64)a > q.nnz_a || (k == 0 && a != 0) || (k == q.n_ecs && (u64)a != q.nnz_a)) e |= CB_ERR_PTR;
-        else if (k < q.n_ecs && q.ipa[k + 1] < a) e |= CB_ERR_PTR;
+        if (cb_ptr_bad(q.ipa, k, q.n_ecs, q.nnz_a)) e |= CB_ERR_PTR;
     }
     if (t < nb[n_parts]) {
         const u32 p = cb_find(nb, n_parts, t);
         const CbPart& q = P[p];
         const u64 k = t - nb[p];
-        const long long a = q.ipn[k];
-        if (a < 0 || (u64)a > q.nnz_n || (k == 0 && a != 0) || (k == q.n_samples && (u64)a != q.nnz_n)) e |= CB_ERR_NPTR;
-        else if (k < q.n_samples && q.ipn[k + 1] < a) e |= CB_ERR_NPTR;
+        if (cb_ptr_bad(q.ipn, k, q.n_samples, q.nnz_n)) e |= CB_ERR_NPTR;
     }
     if (__ballot(e != 0u)) {
         u32 w = e;
@@ -4941,13 +4961,11 @@ __global__ __launch_bounds__(TPB) void k_cb_pairs(const CbPart* P, u32 n_parts, 
         const int c = q.ixa[li];
         const u32 d = (u32)q.daa[li];
         u32 m = 0;
-        if (d == 0u || (d >> n_haps) != 0u) e |= CB_ERR_BITS;
-        if (c < 0 || (u32)c >= q.n_loci) e |= CB_ERR_LOCUS;
-        else {
+        e = cb_nz_bad(q, li, r, n_haps, c, d);
+        if (!(e & CB_ERR_LOCUS)) {
             m = q.tmap ? q.tmap[c] : (u32)c;
             if (m >= n_loci) e |= CB_ERR_MAP;
         }
-        if (li > q.ipa[r] && q.ixa[li - 1] >= c) e |= CB_ERR_ORDER;                      // ascending as the part stores it
         keys[i] = ((base[CB_ROWS * (n_parts + 1) + p] + r) << 32) | m;
         vals[i] = d;
     }
@@ -4992,18 +5010,26 @@ __global__ __launch_bounds__(TPB) void k_cb_hash(const u64* keys, const u32* val
     else rowhash[row] = v;
 }
 // one Entry per global row (k_merge's exchange format), and per aligned 64 rows -- one k_merge wave -- the arena pairs it reserves
-__global__ __launch_bounds__(TPB) void k_cb_entries(const CbPart* P, u32 n_parts, const u64* base, const u64* rowhash, Entry* ent, u64* words) {
+// (rowptr: the global rows' places in the pair list when it is not the parts' own pairs one after the other -- ecb_bundle's folded rows)
+__global__ __launch_bounds__(TPB) void k_cb_entries(const CbPart* P, u32 n_parts, const u64* base, const u32* rowptr, const u64* rowhash, Entry* ent,
+                                                    u64* words) {
     const u64 g = blockIdx.x * (u64)TPB + threadIdx.x;
     const u64* rb = base + CB_ROWS * (n_parts + 1);
     u32 over = 0;
     if (g < rb[n_parts]) {
-        const u32 p = cb_find(rb, n_parts, g);
-        const CbPart& q = P[p];
-        const u64 r = g - rb[p];
-        const u32 a = (u32)q.ipa[r], n = (u32)q.ipa[r + 1] - a;
+        u32 off, n;
+        if (rowptr) { off = rowptr[g]; n = rowptr[g + 1] - off; }
+        else {
+            const u32 p = cb_find(rb, n_parts, g);
+            const CbPart& q = P[p];
+            const u64 r = g - rb[p];
+            const u32 a = (u32)q.ipa[r];
+            n = (u32)q.ipa[r + 1] - a;
+            off = (u32)(base[CB_PAIRS * (n_parts + 1) + p] + a);
+        }
         Entry en;
         en.lo = finish_hash(rowhash[g], n); en.reserved = 0; en.count = 0; en.first_inv = ~(u32)g;
-        en.off = (u32)(base[CB_PAIRS * (n_parts + 1) + p] + a); en.n = n;
+        en.off = off; en.n = n;
         ent[g] = en;
         over = n > INL ? n - INL : 0u;
     }
@@ -5108,9 +5134,108 @@ const ErrBit CB_ERRS[] = {
     {CB_ERR_NCOUNT, ECB_ERR_CONTRACT, "malformed CSC N: a negative count"},
     {CB_ERR_SMAP, ECB_ERR_CONTRACT, "a sample map sends a sample at or beyond n_samples"},
     {CB_ERR_SUM, ECB_ERR_LIMIT, "a merged count exceeds int32"},
+    {BD_ERR_MPTR, ECB_ERR_CONTRACT, "malformed group map: pointers do not start at 0, go backwards or do not end at the number of group ids"},
+    {BD_ERR_MIDX, ECB_ERR_CONTRACT, "malformed group map: a group id at or beyond n_groups"},
+    {BD_ERR_MORDER, ECB_ERR_CONTRACT, "malformed group map: group ids not strictly ascending within a locus (unsorted or duplicate)"},
+    {BD_ERR_WIDE, ECB_ERR_LIMIT, "group map: a locus in more than 65535 groups"},
     {CB_ERR_LOST, ECB_ERR_HIP, "internal: a row found no EC"},
 };
 struct HandleGuard { std::vector<ecb_handle*> h; ~HandleGuard() { for (ecb_handle* x : h) ecb_destroy(x); } };
+// What ecb_combine and ecb_bundle hand to the steps they share (cb_finish): the rows of all parts as one index space, their pairs as
+// sorted (row << 32 | column, mask) keys, and the scratch both sides use.
+constexpr u64 CB_WORDS = CB_SHARD_WORDS * (1 + CB_SHARDS);     // status words: [0] error bits (u32), then the arena shards
+struct CbRun {
+    u32 n_parts, n_loci, n_haps, n_samples;          // (n_loci: the output's columns)
+    u64 R, NP, NZ;                                   // rows, pairs in `keys`, N non-zeros of all parts
+    const CbPart* d_parts; const u64* d_base;
+    u64* words;
+    u64 *keys0, *keys1; u32 *vals0, *vals1;          // sort buffers of max(NP, NZ): free for N once the pairs have been read
+    const u64* keys; const u32* vals;                // the NP pairs in (row, column) order
+    const u32* rowptr;                               // R + 1 places of the rows in them, or null: the parts' own row pointers
+    u64* rowhash; uint2* pairs; Entry* ent;          // R zeroed, NP, R
+    u32* err() const { return reinterpret_cast<u32*>(words); }
+};
+// one wait: the error word (refused by CB_ERRS) and the shards
+int cb_refusal(Call& c, const CbRun& w, u64* back = nullptr) {
+    std::vector<u64> own(back ? 0 : CB_WORDS);
+    return c.read_back(back ? back : own.data(), w.words, CB_WORDS, CB_ERRS);
+}
+// steps 4-8 of the merge: key lists and row hashes, entries, one table, its ECs ranked and exported as A, every row's EC, N
+int cb_finish(Call& c, const CbRun& w, void* d_out_indptr_a, void* d_out_indices_a, void* d_out_data_a, void* d_out_indptr_n, void* d_out_indices_n,
+              void* d_out_data_n, uint64_t* out_sizes) {
+    hipStream_t& st = c.st;                              // (the handle's own stream once there is one: it queues the slot ranks)
+    const u32 n_parts = w.n_parts, n_samples = w.n_samples;
+    const u64 R = w.R, NP = w.NP, NZ = w.NZ;
+    u32* err = w.err();
+    std::vector<u64> back(CB_WORDS);
+    auto check = [&] { return cb_refusal(c, w, back.data()); };
+    // 4. key lists and row hashes; 5. the entries, and the key arena's worst wave
+    if (NP) k_cb_hash<<<nblk(NP, TPB), TPB, 0, st>>>(w.keys, w.vals, NP, w.pairs, w.rowhash, err);
+    if (R) k_cb_entries<<<nblk(R, TPB), TPB, 0, st>>>(w.d_parts, n_parts, w.d_base, w.rowptr, w.rowhash, w.ent, w.words);
+    RCCHK(check());
+    u64 wmax = 0, wsum = 0;
+    for (u32 k = 1; k <= CB_SHARDS; ++k) { wmax = std::max<u64>(wmax, back[CB_SHARD_WORDS * k]); wsum += back[CB_SHARD_WORDS * k + 1]; }
+    u64 E = 0, nnz_a = 0, nnz_n = 0;
+    u32* ec_of_row = c.get<u32>(R);                      // EC of every global row
+    RCCHK(c.missing());
+    HandleGuard hg;
+    if (R) {
+        // 6. one table: room for every row being an EC of its own (half full at most: no growth), and a key arena in which every wave's one
+        //    reservation fits one of its 64 regions whatever the others took (arena_alloc: a region that cannot take a reservation is skipped)
+        ecb_config cfg{};
+        cfg.struct_size = sizeof(ecb_config); cfg.device = c.device; cfg.n_loci = w.n_loci; cfg.n_haplotypes = w.n_haps;
+        cfg.ec_capacity = 2 * R;
+        cfg.arena_capacity = std::max<u64>(1ull << 22, (u64)ARENA_REGIONS * (wmax + wsum / ARENA_REGIONS + 2));
+        ecb_handle* h = nullptr;
+        RCCHK(ecb_create(&cfg, &h));
+        hg.h.push_back(h);
+        ecb_add_counters(h, 0, R, R);                     // R "reads", all valid: the ranking's bitmap spans the rows
+        int rc = ecb_table_merge_device(h, w.ent, R, w.pairs, NP);
+        ecb_sizes sz{};
+        if (rc == ECB_OK) rc = ecb_finalize(h, &sz);
+        if (rc == ECB_OK) rc = ecb_export_device(h, d_out_indptr_a, d_out_indices_a, d_out_data_a, nullptr, nullptr, nullptr);
+        if (rc == ECB_OK) rc = ensure_slot_ranks(h, sz.n_ecs);
+        if (rc != ECB_OK) return fail(nullptr, rc, "%s%s", c.prefix, h->err.c_str());
+        E = sz.n_ecs; nnz_a = sz.nnz_a;
+        st = h->stream;
+        // 7. every row's EC
+        k_cb_lookup<<<nblk(R, TPB), TPB, 0, st>>>(w.ent, R, w.pairs, h->table, h->cap - 1, h->arena, h->run.csr.rank_of_slot, ec_of_row, err);
+    } else {
+        CALLCHK(c, hipMemsetAsync(d_out_indptr_a, 0, 4, st));
+    }
+    // 8. N: (sample, EC) keys sorted, summed per key, zeros dropped, CSC
+    if (NZ) {
+        u32 *flag = c.get<u32>(NZ), *pos = c.get<u32>(NZ + 1), *keep = c.get<u32>(NZ), *opos = c.get<u32>(NZ + 1);
+        u32 *sums1 = c.get<u32>(scan_words(NZ)), *sums2 = c.get<u32>(scan_words(NZ));
+        u64 *rsum = c.get<u64>(NZ), *rkey = c.get<u64>(NZ), *okey = c.get<u64>(NZ), *tot = c.get<u64>(2);
+        SortScratch sc{c.get<u32>(rs_words(NZ)), c.get<u32>(RS_AUX_WORDS), w.words + 1};
+        RCCHK(c.missing());
+        k_cb_ntrip<<<nblk(NZ, TPB), TPB, 0, st>>>(w.d_parts, n_parts, w.d_base, n_samples, ec_of_row, w.keys0, w.vals0, err);
+        RCCHK(check());
+        SortBufs s{{w.keys0, w.keys1}, {w.vals0, w.vals1}};
+        CALLCHK(c, radix_sort_pairs64(st, s, NZ, sc, msb_mask(((u64)n_samples - 1) << 32 | (E ? E - 1 : 0))));
+        const u64* sk = s.keys(); const u32* sv = s.vals();
+        CALLCHK(c, hipMemsetAsync(rsum, 0, NZ * 8, st));
+        CALLCHK(c, hipMemsetAsync(tot, 0, 16, st));
+        k_run_heads<<<nblk(NZ, TPB), TPB, 0, st>>>(sk, NZ, flag);
+        CALLCHK(c, scan_launch(st, flag, NZ, pos, sums1, tot));
+        k_cb_nsum<<<nblk(NZ, TPB), TPB, 0, st>>>(sk, sv, flag, pos, NZ, rsum, rkey);
+        k_cb_nkeep<<<nblk(NZ, TPB), TPB, 0, st>>>(rsum, tot, NZ, keep, err);
+        CALLCHK(c, scan_launch(st, keep, NZ, opos, sums2, tot + 1));
+        k_cb_nemit<<<nblk(NZ, TPB), TPB, 0, st>>>(rsum, rkey, keep, opos, tot, NZ, (int*)d_out_indices_n, (int*)d_out_data_n, okey);
+        k_cb_nptr<<<nblk((u64)n_samples + 1, TPB), TPB, 0, st>>>(okey, tot + 1, NZ, n_samples, (int*)d_out_indptr_n);
+        u64 t2[2] = {0, 0};
+        CALLCHK(c, hipMemcpyAsync(t2, tot, 16, hipMemcpyDeviceToHost, st));
+        RCCHK(check());
+        if (t2[1] > NZ) return fail(nullptr, ECB_ERR_HIP, "internal: %llu N entries from %llu", (unsigned long long)t2[1], (unsigned long long)NZ);
+        nnz_n = t2[1];
+    } else {
+        CALLCHK(c, hipMemsetAsync(d_out_indptr_n, 0, ((u64)n_samples + 1) * 4, st));
+        RCCHK(check());
+    }
+    out_sizes[0] = E; out_sizes[1] = nnz_a; out_sizes[2] = nnz_n;
+    return ECB_OK;
+}
 }  // namespace
 
 extern "C" int ecb_combine_device(int device, uint32_t n_parts, const ecb_combine_part* parts, uint32_t n_loci, uint32_t n_haps, uint32_t n_samples,
@@ -5145,105 +5270,39 @@ extern "C" int ecb_combine_device(int device, uint32_t n_parts, const ecb_combin
     for (u32 p = 0; p < n_parts; ++p) any_map |= hp[p].tmap != nullptr;
     if (any_map && NP >= (1ull << 30)) return fail(nullptr, ECB_ERR_LIMIT, "combine: more than 2^30 non-zeros to re-sort after a target map");
     Call c(device, "combine: ", true); if (c.rc) return c.rc;
-    hipStream_t& st = c.st;                              // (the handle's own stream once there is one: it queues the slot ranks)
+    hipStream_t& st = c.st;
+    CbRun w{};
+    w.n_parts = n_parts; w.n_loci = n_loci; w.n_haps = n_haps; w.n_samples = n_samples; w.R = R; w.NP = NP; w.NZ = NZ;
     CbPart* d_parts = c.get<CbPart>(n_parts);
     u64* d_base = c.get<u64>(base.size());
-    const u64 n_words = CB_SHARD_WORDS * (1 + CB_SHARDS);
-    u64* words = c.get<u64>(n_words);                    // [0] error bits (u32), then the arena shards
+    w.d_parts = d_parts; w.d_base = d_base;
+    w.words = c.get<u64>(CB_WORDS);
     const u64 NK = std::max(NP, NZ);                     // (the sort buffers serve the pairs of A, then the entries of N)
-    u64 *keys0 = c.get<u64>(NK), *keys1 = c.get<u64>(NK), *rowhash = c.get<u64>(R);
-    u32 *vals0 = c.get<u32>(NK), *vals1 = c.get<u32>(NK);
-    uint2* pairs = c.get<uint2>(NP);
-    Entry* ent = c.get<Entry>(R);
+    w.keys0 = c.get<u64>(NK); w.keys1 = c.get<u64>(NK); w.rowhash = c.get<u64>(R);
+    w.vals0 = c.get<u32>(NK); w.vals1 = c.get<u32>(NK);
+    w.pairs = c.get<uint2>(NP);
+    w.ent = c.get<Entry>(R);
     RCCHK(c.missing());
-    u32* err = reinterpret_cast<u32*>(words);
-    std::vector<u64> back(n_words);
-    auto check = [&] { return c.read_back(back.data(), words, n_words, CB_ERRS); };      // one wait: the error word and the shards
     CALLCHK(c, hipMemcpyAsync(d_parts, hp.data(), n_parts * sizeof(CbPart), hipMemcpyHostToDevice, st));
     CALLCHK(c, hipMemcpyAsync(d_base, base.data(), base.size() * 8, hipMemcpyHostToDevice, st));
-    CALLCHK(c, hipMemsetAsync(words, 0, n_words * 8, st));
-    CALLCHK(c, hipMemsetAsync(rowhash, 0, std::max<u64>(R, 1) * 8, st));
+    CALLCHK(c, hipMemsetAsync(w.words, 0, CB_WORDS * 8, st));
+    CALLCHK(c, hipMemsetAsync(w.rowhash, 0, std::max<u64>(R, 1) * 8, st));
     // 1. the pointers; 2. the pairs (their binary searches trust checked pointers)
     const u64 n_ptr = std::max(base[CB_APTR * B + n_parts], base[CB_NPTR * B + n_parts]);
-    k_cb_check<<<nblk(n_ptr, TPB), TPB, 0, st>>>(d_parts, n_parts, d_base, err);
-    RCCHK(check());
-    if (NP) k_cb_pairs<<<nblk(NP, TPB), TPB, 0, st>>>(d_parts, n_parts, d_base, n_loci, n_haps, keys0, vals0, err);
-    RCCHK(check());
+    k_cb_check<<<nblk(n_ptr, TPB), TPB, 0, st>>>(d_parts, n_parts, d_base, w.err());
+    RCCHK(cb_refusal(c, w));
+    if (NP) k_cb_pairs<<<nblk(NP, TPB), TPB, 0, st>>>(d_parts, n_parts, d_base, n_loci, n_haps, w.keys0, w.vals0, w.err());
+    RCCHK(cb_refusal(c, w));
     // 3. rows that a target map re-numbered are re-sorted: one radix sort of (row, column) over all pairs (parts without a map are sorted already)
-    u64* keys = keys0; u32* vals = vals0;
+    w.keys = w.keys0; w.vals = w.vals0;
     if (any_map && NP > 1) {
-        SortScratch sc{c.get<u32>(rs_words(NP)), c.get<u32>(RS_AUX_WORDS), words + 1};
+        SortScratch sc{c.get<u32>(rs_words(NP)), c.get<u32>(RS_AUX_WORDS), w.words + 1};
         RCCHK(c.missing());
-        SortBufs s{{keys0, keys1}, {vals0, vals1}};
+        SortBufs s{{w.keys0, w.keys1}, {w.vals0, w.vals1}};
         CALLCHK(c, radix_sort_pairs64(st, s, NP, sc, msb_mask((R - 1) << 32 | (n_loci - 1))));
-        keys = s.keys(); vals = s.vals();
+        w.keys = s.keys(); w.vals = s.vals();
     }
-    // 4. key lists and row hashes; 5. the entries, and the key arena's worst wave
-    if (NP) k_cb_hash<<<nblk(NP, TPB), TPB, 0, st>>>(keys, vals, NP, pairs, rowhash, err);
-    if (R) k_cb_entries<<<nblk(R, TPB), TPB, 0, st>>>(d_parts, n_parts, d_base, rowhash, ent, words);
-    RCCHK(check());
-    u64 wmax = 0, wsum = 0;
-    for (u32 k = 1; k <= CB_SHARDS; ++k) { wmax = std::max<u64>(wmax, back[CB_SHARD_WORDS * k]); wsum += back[CB_SHARD_WORDS * k + 1]; }
-    u64 E = 0, nnz_a = 0, nnz_n = 0;
-    u32* ec_of_row = c.get<u32>(R);                      // EC of every global row
-    RCCHK(c.missing());
-    HandleGuard hg;
-    if (R) {
-        // 6. one table: room for every row being an EC of its own (half full at most: no growth), and a key arena in which every wave's one
-        //    reservation fits one of its 64 regions whatever the others took (arena_alloc: a region that cannot take a reservation is skipped)
-        ecb_config cfg{};
-        cfg.struct_size = sizeof(ecb_config); cfg.device = device; cfg.n_loci = n_loci; cfg.n_haplotypes = n_haps;
-        cfg.ec_capacity = 2 * R;
-        cfg.arena_capacity = std::max<u64>(1ull << 22, (u64)ARENA_REGIONS * (wmax + wsum / ARENA_REGIONS + 2));
-        ecb_handle* h = nullptr;
-        RCCHK(ecb_create(&cfg, &h));
-        hg.h.push_back(h);
-        ecb_add_counters(h, 0, R, R);                     // R "reads", all valid: the ranking's bitmap spans the rows
-        int rc = ecb_table_merge_device(h, ent, R, pairs, NP);
-        ecb_sizes sz{};
-        if (rc == ECB_OK) rc = ecb_finalize(h, &sz);
-        if (rc == ECB_OK) rc = ecb_export_device(h, d_out_indptr_a, d_out_indices_a, d_out_data_a, nullptr, nullptr, nullptr);
-        if (rc == ECB_OK) rc = ensure_slot_ranks(h, sz.n_ecs);
-        if (rc != ECB_OK) return fail(nullptr, rc, "combine: %s", h->err.c_str());
-        E = sz.n_ecs; nnz_a = sz.nnz_a;
-        st = h->stream;
-        // 7. every row's EC
-        k_cb_lookup<<<nblk(R, TPB), TPB, 0, st>>>(ent, R, pairs, h->table, h->cap - 1, h->arena, h->run.csr.rank_of_slot, ec_of_row, err);
-    } else {
-        CALLCHK(c, hipMemsetAsync(d_out_indptr_a, 0, 4, st));
-    }
-    // 8. N: (sample, EC) keys sorted, summed per key, zeros dropped, CSC
-    if (NZ) {
-        u32 *flag = c.get<u32>(NZ), *pos = c.get<u32>(NZ + 1), *keep = c.get<u32>(NZ), *opos = c.get<u32>(NZ + 1);
-        u32 *sums1 = c.get<u32>(scan_words(NZ)), *sums2 = c.get<u32>(scan_words(NZ));
-        u64 *rsum = c.get<u64>(NZ), *rkey = c.get<u64>(NZ), *okey = c.get<u64>(NZ), *tot = c.get<u64>(2);
-        SortScratch sc{c.get<u32>(rs_words(NZ)), c.get<u32>(RS_AUX_WORDS), words + 1};
-        RCCHK(c.missing());
-        k_cb_ntrip<<<nblk(NZ, TPB), TPB, 0, st>>>(d_parts, n_parts, d_base, n_samples, ec_of_row, keys0, vals0, err);
-        RCCHK(check());
-        SortBufs s{{keys0, keys1}, {vals0, vals1}};
-        CALLCHK(c, radix_sort_pairs64(st, s, NZ, sc, msb_mask(((u64)n_samples - 1) << 32 | (E ? E - 1 : 0))));
-        const u64* sk = s.keys(); const u32* sv = s.vals();
-        CALLCHK(c, hipMemsetAsync(rsum, 0, NZ * 8, st));
-        CALLCHK(c, hipMemsetAsync(tot, 0, 16, st));
-        k_run_heads<<<nblk(NZ, TPB), TPB, 0, st>>>(sk, NZ, flag);
-        CALLCHK(c, scan_launch(st, flag, NZ, pos, sums1, tot));
-        k_cb_nsum<<<nblk(NZ, TPB), TPB, 0, st>>>(sk, sv, flag, pos, NZ, rsum, rkey);
-        k_cb_nkeep<<<nblk(NZ, TPB), TPB, 0, st>>>(rsum, tot, NZ, keep, err);
-        CALLCHK(c, scan_launch(st, keep, NZ, opos, sums2, tot + 1));
-        k_cb_nemit<<<nblk(NZ, TPB), TPB, 0, st>>>(rsum, rkey, keep, opos, tot, NZ, (int*)d_out_indices_n, (int*)d_out_data_n, okey);
-        k_cb_nptr<<<nblk((u64)n_samples + 1, TPB), TPB, 0, st>>>(okey, tot + 1, NZ, n_samples, (int*)d_out_indptr_n);
-        u64 t2[2] = {0, 0};
-        CALLCHK(c, hipMemcpyAsync(t2, tot, 16, hipMemcpyDeviceToHost, st));
-        RCCHK(check());
-        if (t2[1] > NZ) return fail(nullptr, ECB_ERR_HIP, "internal: %llu N entries from %llu", (unsigned long long)t2[1], (unsigned long long)NZ);
-        nnz_n = t2[1];
-    } else {
-        CALLCHK(c, hipMemsetAsync(d_out_indptr_n, 0, ((u64)n_samples + 1) * 4, st));
-        RCCHK(check());
-    }
-    out_sizes[0] = E; out_sizes[1] = nnz_a; out_sizes[2] = nnz_n;
-    return ECB_OK;
+    return cb_finish(c, w, d_out_indptr_a, d_out_indices_a, d_out_data_a, d_out_indptr_n, d_out_indices_n, d_out_data_n, out_sizes);
 }
 
 extern "C" int ecb_combine(int device, uint32_t n_parts, const ecb_combine_part* parts, uint32_t n_loci, uint32_t n_haps, uint32_t n_samples,
@@ -5279,6 +5338,210 @@ extern "C" int ecb_combine(int device, uint32_t n_parts, const ecb_combine_part*
     const u64 E = out_sizes[0], nnz_a = out_sizes[1], nnz_n = out_sizes[2];
     return stage_out(c, {{out_indptr_a, &oia, (E + 1) * 4}, {out_indptr_n, &oin, nptr}, {out_indices_a, &oxa, nnz_a * 4}, {out_data_a, &oda, nnz_a * 4},
                          {out_indices_n, &oxn, nnz_n * 4}, {out_data_n, &odn, nnz_n * 4}});
+}
+
+// ---- ecbundle: a .bin's columns collapsed into groups, its rows folded back into ECs (ecb_bundle / ecb_bundle_device) -------------------
+// The reference's AlignmentPropertyMatrix.bundle(reset=True) (AlignmentPropertyMatrix.py:219-275: every haplotype's matrix times a T x G
+// incidence matrix, the values reset to 1) followed by the merge of the one result.  The group map is many-to-one, one-to-none and
+// one-to-many at once, so a non-zero becomes as many (row, group) pairs as its locus has groups, and pairs that land on one (row, group)
+// have their masks OR-ed.  In front of cb_finish:
+//   k_bd_map_ptr / k_bd_map_idx   the map's pointers, then its group ids (range, ascending within a locus)
+//   k_bd_count     one thread per non-zero: checked as k_cb_pairs checks it; its row and the number of groups of its locus
+//   scan           the non-zeros' first places among the expanded pairs
+//   k_bd_expand    one thread per EXPANDED pair: its non-zero by binary search in the scan, key = row << 32 | group, value = mask
+//   radix_sort_pairs64 on the row and group bits;  k_run_heads + scan: the runs of equal (row, group)
+//   k_bd_fold      one thread per sorted pair: the OR of a run's masks by a segmented wave scan (the run's first lane from the ballot of
+//                  the head flags: six 32-bit shuffles, no key compares), one write per run and wave -- a plain store when the run lies
+//                  within the wave, an atomic OR into zeroed storage when it goes on in a neighbouring one
+//   k_bd_rowptr    the folded rows' places: a binary search per row
+// No kernel loops over a row, a group or a locus's group list: 10 000 members of one gene in a row cost what 10 000 rows of one pair do.
+namespace {
+constexpr u32 BD_MAX_GROUPS_PER_LOCUS = 65535;       // (a scan stretch of 16 384 counts sums in 32 bits)
+constexpr int BD_FOLD_TPB = TPB, BD_WAVE = 64;       // the fold's workgroup, and the wave a run is folded within
+__global__ __launch_bounds__(TPB) void k_bd_map_ptr(const u32* mptr, u32 n_loci, u64 n_map, u32* err) {
+    const u64 k = blockIdx.x * (u64)TPB + threadIdx.x;
+    u32 e = 0;
+    if (k <= n_loci) {
+        if (cb_ptr_bad(reinterpret_cast<const int*>(mptr), k, n_loci, n_map)) e |= BD_ERR_MPTR;
+        else if (k < n_loci && mptr[k + 1] - mptr[k] > BD_MAX_GROUPS_PER_LOCUS) e |= BD_ERR_WIDE;
+    }
+    cb_raise(e, err);
+}
+__global__ __launch_bounds__(TPB) void k_bd_map_idx(const u32* mptr, const u32* midx, u32 n_loci, u64 n_map, u32 n_groups, u32* err) {
+    const u64 j = blockIdx.x * (u64)TPB + threadIdx.x;
+    u32 e = 0;
+    if (j < n_map) {
+        const u32 g = midx[j];
+        if (g >= n_groups) e |= BD_ERR_MIDX;
+        const u32 c = cb_row(reinterpret_cast<const int*>(mptr), n_loci, (long long)j);
+        if (j > mptr[c] && midx[j - 1] >= g) e |= BD_ERR_MORDER;
+    }
+    cb_raise(e, err);
+}
+__global__ __launch_bounds__(TPB) void k_bd_count(const CbPart* P, u32 n_haps, const u32* mptr, u32* cnt, u32* row, u32* err) {
+    const u64 i = blockIdx.x * (u64)TPB + threadIdx.x;
+    const CbPart& q = P[0];
+    u32 e = 0;
+    if (i < q.nnz_a) {
+        const u32 r = cb_row(q.ipa, q.n_ecs, (long long)i);
+        const int c = q.ixa[i];
+        e = cb_nz_bad(q, (long long)i, r, n_haps, c, (u32)q.daa[i]);
+        cnt[i] = (e & CB_ERR_LOCUS) ? 0u : mptr[c + 1] - mptr[c];
+        row[i] = r;
+    }
+    cb_raise(e, err);
+}
+// (first[i] = the first expanded pair of non-zero i, first[nnz] = n: the largest i with first[i] <= x is the one that has pair x)
+__global__ __launch_bounds__(TPB) void k_bd_expand(const CbPart* P, const u32* first, const u32* row, const u32* mptr, const u32* midx, u64 n,
+                                                   u64* keys, u32* vals) {
+    const u64 x = blockIdx.x * (u64)TPB + threadIdx.x;
+    if (x >= n) return;
+    const CbPart& q = P[0];
+    u64 a = 0, b = q.nnz_a;
+    while (b - a > 1) { const u64 m = (a + b) >> 1; if (first[m] <= x) a = m; else b = m; }
+    const u32 g = midx[mptr[q.ixa[a]] + ((u32)x - first[a])];
+    keys[x] = ((u64)row[a] << 32) | g;
+    vals[x] = (u32)q.daa[a];
+}
+__global__ __launch_bounds__(BD_FOLD_TPB) void k_bd_fold(const u64* keys, const u32* vals, const u32* flag, const u32* pos, u64 n, u64* okeys,
+                                                         u32* ovals) {
+    const u64 i = blockIdx.x * (u64)BD_FOLD_TPB + threadIdx.x;
+    const u32 lane = threadIdx.x & (BD_WAVE - 1u);
+    const bool valid = i < n;
+    u32 f = 1, v = 0, at = 0;                            // (the lanes past the end are runs of their own)
+    if (valid) {
+        f = flag[i]; v = vals[i];
+        at = pos[i] + f - 1u;
+        if (f) okeys[at] = keys[i];
+    }
+    const u64 heads = __ballot(f != 0u) | 1ull;          // where a run starts within this wave
+    const u32 f0 = (u32)__builtin_amdgcn_readfirstlane((int)f);
+    const u32 s = 63u - (u32)__builtin_clzll(heads & (~0ull >> (63u - lane)));      // the first lane of this lane's run
+#pragma unroll
+    for (u32 d = 1; d < 64; d <<= 1) {
+        const u32 ov = (u32)__shfl_up((int)v, d);
+        if (lane >= s + d) v |= ov;
+    }
+    if (!valid || (lane != 63u && !((heads >> (lane + 1u)) & 1ull))) return;       // not the run's last lane in this wave
+    const bool before = s == 0u && f0 == 0u;             // the run began in the wave before
+    const bool after = lane == 63u && i + 1 < n && flag[i + 1] == 0u;
+    if (before || after) atomicOr(ovals + at, v);
+    else ovals[at] = v;
+}
+__global__ void k_bd_rowptr(const u64* keys, u64 n, u32 n_rows, u32* rowptr) {
+    const u64 r = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+    if (r <= n_rows) rowptr[r] = (u32)lower_bound_u64(keys, n, r << 32);
+}
+}  // namespace
+
+extern "C" int ecb_bundle_device(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, uint32_t n_samples, uint32_t n_groups, uint64_t nnz_a,
+                                 const void* d_indptr_a, const void* d_indices_a, const void* d_data_a, uint64_t nnz_n, const void* d_indptr_n,
+                                 const void* d_indices_n, const void* d_data_n, uint64_t n_map, const void* d_map_ptr, const void* d_map_idx,
+                                 uint64_t a_capacity, void* d_out_indptr_a, void* d_out_indices_a, void* d_out_data_a, void* d_out_indptr_n,
+                                 void* d_out_indices_n, void* d_out_data_n, uint64_t* out_sizes) {
+    if (!out_sizes || !d_indptr_a || !d_indptr_n || !d_map_ptr || !d_out_indptr_a || !d_out_indptr_n || !n_loci || !n_groups || !n_haps || n_haps > 31 ||
+        (nnz_a && (!d_indices_a || !d_data_a)) || (nnz_n && (!d_indices_n || !d_data_n)) || (n_map && !d_map_idx))
+        return fail(nullptr, ECB_ERR_ARG, "bundle: bad argument");
+    if (n_groups >= MAX_LOCI) return fail(nullptr, ECB_ERR_ARG, "bundle: n_groups out of range (1 .. 2^26-3)");
+    if (nnz_a >= (1ull << 31) || nnz_n >= (1ull << 30) || n_map >= (1ull << 31) || n_ecs >= (1u << 31) - 1u || n_loci >= (1u << 31) - 1u ||
+        n_samples >= (1u << 31) - 1u)
+        return fail(nullptr, ECB_ERR_LIMIT, "bundle: the sizes exceed the .bin format's int32 limits");
+    if ((n_ecs && a_capacity && (!d_out_indices_a || !d_out_data_a)) || (nnz_n && (!d_out_indices_n || !d_out_data_n)))
+        return fail(nullptr, ECB_ERR_ARG, "bundle: null output");
+    const u32 *mptr = (const u32*)d_map_ptr, *midx = (const u32*)d_map_idx;
+    const CbPart hp{(const int*)d_indptr_a, (const int*)d_indices_a, (const int*)d_data_a, (const int*)d_indptr_n, (const int*)d_indices_n,
+                    (const int*)d_data_n, nullptr, nullptr, n_ecs, n_loci, n_samples, 0u, nnz_a, nnz_n};
+    u64 base[CB_BASES * 2];                              // one part: every base array is {0, its size}
+    const u64 add[CB_BASES] = {n_ecs, nnz_a, nnz_n, (u64)n_ecs + 1, (u64)n_samples + 1};
+    for (int k = 0; k < CB_BASES; ++k) { base[2 * k] = 0; base[2 * k + 1] = add[k]; }
+    Call c(device, "bundle: ", true); if (c.rc) return c.rc;
+    hipStream_t& st = c.st;
+    CbRun w{};
+    w.n_parts = 1; w.n_loci = n_groups; w.n_haps = n_haps; w.n_samples = n_samples; w.R = n_ecs; w.NZ = nnz_n;
+    CbPart* d_parts = c.get<CbPart>(1);
+    u64 *d_base = c.get<u64>(CB_BASES * 2), *tot = c.get<u64>(2);
+    w.d_parts = d_parts; w.d_base = d_base;
+    w.words = c.get<u64>(CB_WORDS);
+    u32 *cnt = c.get<u32>(nnz_a), *first = c.get<u32>(nnz_a + 1), *row = c.get<u32>(nnz_a), *sums = c.get<u32>(scan_words(nnz_a));
+    RCCHK(c.missing());
+    CALLCHK(c, hipMemcpyAsync(d_parts, &hp, sizeof(CbPart), hipMemcpyHostToDevice, st));
+    CALLCHK(c, hipMemcpyAsync(d_base, base, sizeof(base), hipMemcpyHostToDevice, st));
+    CALLCHK(c, hipMemsetAsync(w.words, 0, CB_WORDS * 8, st));
+    CALLCHK(c, hipMemsetAsync(tot, 0, 16, st));
+    // 1. the pointers of A, N and the map; then what trusts them: the map's group ids, and 2. the non-zeros
+    k_cb_check<<<nblk(std::max<u64>(n_ecs, n_samples) + 1, TPB), TPB, 0, st>>>(d_parts, 1, d_base, w.err());
+    k_bd_map_ptr<<<nblk((u64)n_loci + 1, TPB), TPB, 0, st>>>(mptr, n_loci, n_map, w.err());
+    RCCHK(cb_refusal(c, w));
+    if (n_map) k_bd_map_idx<<<nblk(n_map, TPB), TPB, 0, st>>>(mptr, midx, n_loci, n_map, n_groups, w.err());
+    if (nnz_a) k_bd_count<<<nblk(nnz_a, TPB), TPB, 0, st>>>(d_parts, n_haps, mptr, cnt, row, w.err());
+    RCCHK(cb_refusal(c, w));
+    // 3. the expanded pairs
+    u64 X = 0, NC = 0;
+    if (nnz_a) {
+        CALLCHK(c, scan_launch(st, cnt, nnz_a, first, sums, tot, 1, first + nnz_a));
+        CALLCHK(c, hipMemcpyAsync(&X, tot, 8, hipMemcpyDeviceToHost, st));
+        CALLCHK(c, hipStreamSynchronize(st));
+    }
+    if (X >= (1ull << 30)) return fail(nullptr, ECB_ERR_LIMIT, "bundle: 2^30 (row, group) pairs or more before the fold");      // (radix_sort_pairs64)
+    const u64 NK = std::max<u64>(X, nnz_n);
+    w.keys0 = c.get<u64>(NK); w.keys1 = c.get<u64>(NK); w.vals0 = c.get<u32>(NK); w.vals1 = c.get<u32>(NK);
+    u32* rowptr = c.get<u32>((u64)n_ecs + 1);
+    w.rowhash = c.get<u64>(n_ecs); w.ent = c.get<Entry>(n_ecs);
+    RCCHK(c.missing());
+    u64* ckeys = nullptr; u32* cvals = nullptr;
+    if (X) {
+        u32 *flag = c.get<u32>(X), *pos = c.get<u32>(X + 1), *sums2 = c.get<u32>(scan_words(X));
+        SortScratch sc{c.get<u32>(rs_words(X)), c.get<u32>(RS_AUX_WORDS), w.words + 1};
+        RCCHK(c.missing());
+        k_bd_expand<<<nblk(X, TPB), TPB, 0, st>>>(d_parts, first, row, mptr, midx, X, w.keys0, w.vals0);
+        // 4. (row, group) order; 5. the runs of equal (row, group)
+        SortBufs s{{w.keys0, w.keys1}, {w.vals0, w.vals1}};
+        CALLCHK(c, radix_sort_pairs64(st, s, X, sc, msb_mask((u64)(n_ecs - 1) << 32 | (n_groups - 1))));
+        k_run_heads<<<nblk(X, TPB), TPB, 0, st>>>(s.keys(), X, flag);
+        CALLCHK(c, scan_launch(st, flag, X, pos, sums2, tot + 1));
+        CALLCHK(c, hipMemcpyAsync(&NC, tot + 1, 8, hipMemcpyDeviceToHost, st));
+        CALLCHK(c, hipStreamSynchronize(st));
+        if (NC > X) return fail(nullptr, ECB_ERR_HIP, "internal: %llu runs from %llu pairs", (unsigned long long)NC, (unsigned long long)X);
+        if (NC > a_capacity)
+            return fail(nullptr, ECB_ERR_ARG, "bundle: %llu non-zeros after the fold, room for %llu", (unsigned long long)NC, (unsigned long long)a_capacity);
+        // 6. one mask per run, the compacted pairs
+        ckeys = c.get<u64>(NC); cvals = c.get<u32>(NC);
+        RCCHK(c.missing());
+        CALLCHK(c, hipMemsetAsync(cvals, 0, NC * 4, st));
+        k_bd_fold<<<nblk(X, BD_FOLD_TPB), BD_FOLD_TPB, 0, st>>>(s.keys(), s.vals(), flag, pos, X, ckeys, cvals);
+    } else {
+        ckeys = c.get<u64>(0); cvals = c.get<u32>(0);
+    }
+    w.pairs = c.get<uint2>(NC);
+    RCCHK(c.missing());
+    k_bd_rowptr<<<nblk((u64)n_ecs + 1, TPB), TPB, 0, st>>>(ckeys, NC, n_ecs, rowptr);
+    CALLCHK(c, hipMemsetAsync(w.rowhash, 0, std::max<u64>(n_ecs, 1) * 8, st));
+    CALLCHK(c, hipGetLastError());
+    w.NP = NC; w.keys = ckeys; w.vals = cvals; w.rowptr = rowptr;
+    return cb_finish(c, w, d_out_indptr_a, d_out_indices_a, d_out_data_a, d_out_indptr_n, d_out_indices_n, d_out_data_n, out_sizes);
+}
+
+extern "C" int ecb_bundle(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, uint32_t n_samples, uint32_t n_groups, uint64_t nnz_a,
+                          const int32_t* indptr_a, const int32_t* indices_a, const int32_t* data_a, uint64_t nnz_n, const int32_t* indptr_n,
+                          const int32_t* indices_n, const int32_t* data_n, uint64_t n_map, const uint32_t* map_ptr, const uint32_t* map_idx,
+                          uint64_t a_capacity, int32_t* out_indptr_a, int32_t* out_indices_a, int32_t* out_data_a, int32_t* out_indptr_n,
+                          int32_t* out_indices_n, int32_t* out_data_n, uint64_t* out_sizes) {
+    if (!out_sizes || !indptr_a || !indptr_n || !map_ptr || !out_indptr_a || !out_indptr_n) return fail(nullptr, ECB_ERR_ARG, "bundle: bad argument");
+    if (nnz_a >= (1ull << 31) || nnz_n >= (1ull << 31) || n_map >= (1ull << 31) || a_capacity >= (1ull << 31))
+        return fail(nullptr, ECB_ERR_LIMIT, "bundle: the sizes exceed the .bin format's int32 limits");
+    Call c(device, "bundle: "); if (c.rc) return c.rc;
+    DevBuf<> ipa, ixa, daa, ipn, ixn, dan, mp, mi, oia, oxa, oda, oin, oxn, odn;
+    const u64 nptr = ((u64)n_samples + 1) * 4;
+    int rc = stage_in(c, {{&ipa, indptr_a, ((u64)n_ecs + 1) * 4}, {&ixa, indices_a, nnz_a * 4}, {&daa, data_a, nnz_a * 4}, {&ipn, indptr_n, nptr},
+                          {&ixn, indices_n, nnz_n * 4}, {&dan, data_n, nnz_n * 4}, {&mp, map_ptr, ((u64)n_loci + 1) * 4}, {&mi, map_idx, n_map * 4},
+                          {&oia, nullptr, ((u64)n_ecs + 1) * 4}, {&oxa, nullptr, a_capacity * 4}, {&oda, nullptr, a_capacity * 4}, {&oin, nullptr, nptr},
+                          {&oxn, nullptr, nnz_n * 4}, {&odn, nullptr, nnz_n * 4}});
+    if (rc == ECB_OK) rc = ecb_bundle_device(device, n_ecs, n_loci, n_haps, n_samples, n_groups, nnz_a, ipa.p, ixa.p, daa.p, nnz_n, ipn.p, ixn.p, dan.p,
+                                             n_map, mp.p, mi.p, a_capacity, oia.p, oxa.p, oda.p, oin.p, oxn.p, odn.p, out_sizes);
+    RCCHK(rc);
+    const u64 E = out_sizes[0], na = out_sizes[1], nn = out_sizes[2];
+    return stage_out(c, {{out_indptr_a, &oia, (E + 1) * 4}, {out_indptr_n, &oin, nptr}, {out_indices_a, &oxa, na * 4}, {out_data_a, &oda, na * 4},
+                         {out_indices_n, &oxn, nn * 4}, {out_data_n, &odn, nn * 4}});
 }
 
 // ---- salmon2ec: CSR A and N of a salmon eq_classes.txt EC section (ecb_salmon_ecs / ecb_salmon_ecs_device) ------------------------------

@@ -40,6 +40,8 @@ SYMBOLS = ("ecb_abi_version", "ecb_device_count", "ecb_create", "ecb_destroy", "
            "ecb_salmon_ecs_device", "ecb_salmon_ecs")
 #: every symbol include/ecb_count.h declares (ecb.h includes it)
 COUNT_SYMBOLS = ("ecb_count_alignments_device", "ecb_count_alignments")
+#: every symbol include/ecb_bundle.h declares (ecb.h includes it)
+BUNDLE_SYMBOLS = ("ecb_bundle_device", "ecb_bundle")
 ABI_VERSION = 4            # include/ecb.h: ECB_ABI_VERSION
 
 
@@ -171,6 +173,9 @@ def load():
     if not ab or hasattr(lib, "ecb_count_alignments"):
         for f in (lib.ecb_count_alignments_device, lib.ecb_count_alignments):
             f.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.c_uint32, u64, vp, vp, vp, C.c_int64, vp, vp, vp]
+    if not ab or hasattr(lib, "ecb_bundle"):
+        for f in (lib.ecb_bundle_device, lib.ecb_bundle):
+            f.argtypes = [C.c_int] + [C.c_uint32] * 5 + [u64, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, u64] + [vp] * 6 + [C.POINTER(u64)]
     lib.ecb_csr_to_hapcsc_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.POINTER(u64)]
     lib.ecb_hapcsc_to_csr_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, u64, vp, vp, vp, C.POINTER(u64)]
     _lib = lib
@@ -389,6 +394,52 @@ def combine(parts, n_loci, n_haps, n_samples, device=0):
     _check(lib, entry(device, len(parts), cp, n_loci, n_haps, n_samples, *[ptr(o) for o in out], sizes))
     E, nnz_a, nnz_n = (int(x) for x in sizes)
     return out[0][:E + 1], out[1][:nnz_a], out[2][:nnz_a], out[3], out[4][:nnz_n], out[5][:nnz_n]
+
+
+def bundle(indptrA, indicesA, dataA, indptrN, indicesN, dataN, n_loci, n_haps, n_groups, map_ptr, map_idx, device=0):
+    """ecbundle on the GPU: the columns of one ``.bin``'s CSR A collapsed into groups and its rows folded back into ECs (``ecb_bundle``).
+    ``map_ptr`` (``n_loci + 1``) and ``map_idx`` are the group map as a CSR over the loci: the group ids of every locus, strictly
+    ascending, below ``n_groups``; a locus may have one, none or several.  The mask at (row, group) is the OR of the row's masks over the
+    group's loci; rows with equal (group, mask) sets become one EC, numbered by first appearance; counts add per (EC, sample), zero sums
+    are dropped.  numpy arrays go through ``ecb_bundle`` (host arrays, no PyTorch), CUDA tensors through ``ecb_bundle_device``
+    (``device`` is then the tensors' own).  Returns (indptrA, indicesA, dataA, indptrN, indicesN, dataN), int32, of the same kind as the
+    input.  Malformed input or a malformed map raises :class:`EcbError` (``ECB_ERR_CONTRACT``), sizes beyond the limits ``ECB_ERR_LIMIT``."""
+    lib = load()
+    ins = (indptrA, indicesA, dataA, indptrN, indicesN, dataN, map_ptr, map_idx)
+    on_device = hasattr(indptrA, "data_ptr")
+    if on_device:
+        import torch
+        dev = indptrA.device
+        a = [torch.as_tensor(x).to(device=dev, dtype=torch.int32).contiguous() for x in ins]
+        ptr, entry, device = _dev_ptr, lib.ecb_bundle_device, dev.index or 0
+
+        def empty(n):
+            return torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    else:
+        a = [np.ascontiguousarray(x, dtype=np.int32) for x in ins]      # (a map's values are below 2^31: int32 and uint32 are the same bytes)
+        ptr, entry = _ptr, lib.ecb_bundle
+
+        def empty(n):
+            return np.empty(max(n, 1), dtype=np.int32)
+    ipa, ixa, daa, ipn, ixn, dan, mp, mi = a
+    E, S, nnz, nnz_n = len(ipa) - 1, len(ipn) - 1, len(ixa), len(ixn)
+    if len(daa) != nnz or len(dan) != nnz_n:
+        raise ValueError("indices and data differ in length")
+    if len(mp) != n_loci + 1:
+        raise ValueError("map_ptr has %d entries for %d loci" % (len(mp), n_loci))
+    # room for A: the (row, group) pairs before the fold -- one per non-zero and group of its locus, where the map and the columns can be
+    # indexed at all (otherwise the library refuses before it writes) -- and never more than a full matrix
+    cap = 0
+    if nnz and len(mp) > 1:
+        per = (mp[1:] - mp[:-1]).clamp(min=0) if on_device else np.maximum(np.diff(mp.astype(np.int64)), 0)
+        cols = ixa.long().clamp(0, n_loci - 1) if on_device else np.clip(ixa, 0, n_loci - 1)
+        cap = min(int(per[cols].sum()), E * n_groups, (1 << 31) - 1)
+    out = [empty(E + 1), empty(cap), empty(cap), empty(S + 1), empty(nnz_n), empty(nnz_n)]
+    sizes = (C.c_uint64 * 3)()
+    _check(lib, entry(device, E, n_loci, n_haps, S, n_groups, nnz, ptr(ipa), ptr(ixa), ptr(daa), nnz_n, ptr(ipn), ptr(ixn), ptr(dan),
+                      len(mi), ptr(mp), ptr(mi), cap, *([ptr(o) for o in out] + [sizes])))
+    E2, nnz_a, nnz_n2 = (int(x) for x in sizes)
+    return out[0][:E2 + 1], out[1][:nnz_a], out[2][:nnz_a], out[3], out[4][:nnz_n2], out[5][:nnz_n2]
 
 
 ECB_ERR_CONTRACT = -5      # include/ecb.h

@@ -378,5 +378,7 @@ const char* ecb_profile_kernel(const ecb_handle* h);
 
 /* The entry points that read a .bin back (count-alignments) are declared in a header of their own, part of this ABI. */
 #include "ecb_count.h"
+/* ... and so are the ones that collapse a .bin's targets into groups (ecbundle). */
+#  include "ecb_bundle.h"
 
 #endif /* ECB_H */
