@@ -2376,6 +2376,14 @@ __global__ void k_msf_rows(const u32* indptr, const int* indices, const int* dat
 //   grow   -- a new n-byte buffer, filled with the byte `fill` (-1: not filled), the first `keep` bytes of the old one copied over on `st`
 //             and waited for, then the old one freed (no copy and no wait when there is none).  A failing step leaves the old one in place.
 // alloc and regrow free what the buffer held before they allocate.
+//
+// ECB_POISON_SCRATCH (a debug switch, read where it acts; unset, empty or "0": off): every allocation is filled with POISON_BYTE before it
+// is handed out -- complete when alloc returns, since later work goes to other streams -- and scratch whose contents the library no longer
+// defines is filled again where it dies (the per-device pool at the end of a Call, the handle's pool in ecb_reset: DESIGN.md section 4).
+// What a kernel reads without anybody having written it is then 0x01010101 per word whatever the process did before: never zero, and
+// as a stray count or index below 2^25.
+constexpr int POISON_BYTE = 0x01;
+inline bool poison_scratch() { const char* e = getenv("ECB_POISON_SCRATCH"); return e && *e && strcmp(e, "0") != 0; }
 template <class T = void>
 struct DevBuf {
     void* p = nullptr;
@@ -2406,6 +2414,11 @@ struct DevBuf {
         if (e == hipSuccess) e = hipMalloc(&p, n);
         if (e != hipSuccess) { p = nullptr; return e; }
         bytes = n;
+        if (n && poison_scratch()) {
+            e = hipMemset(p, POISON_BYTE, n);
+            if (e == hipSuccess) e = hipDeviceSynchronize();
+            if (e != hipSuccess) { reset(); return e; }
+        }
         return hipSuccess;
     }
     hipError_t regrow(u64 need, u64 slack) { return bytes >= need ? hipSuccess : alloc(need + slack); }
@@ -3395,6 +3408,15 @@ int ecb_reset(ecb_handle* h) {
     HIPCHK(h, hipSetDevice(h->device));
     const u32* occupied = h->has_result() ? h->slot_list() : nullptr;     // (a finalized handle knows its occupied slots: every one of them, checked)
     const u64 n_occupied = h->run.n_list;
+    // ECB_POISON_SCRATCH: the run's scratch is dead from here on (run = Run{} below drops every view into it).  Not the two buffers k_slow
+    // leaves zeroed for its next launch (run_slow clears them only when they are reallocated), and the list of occupied slots only once
+    // the table has been cleared from it.  The table, the arena, read_slot, meta, the queue and the wave arena are no scratch: what of them a
+    // reset clears, it clears by its own rule below.
+    const bool poison = poison_scratch();
+    if (poison)
+        for (int i = 0; i < ecb_handle::P_N; ++i)
+            if (h->pool[i].p && i != ecb_handle::P_SLOW_KEY && i != ecb_handle::P_SLOW_MASK && i != ecb_handle::P_LIST)
+                HIPCHK(h, hipMemsetAsync(h->pool[i].p, POISON_BYTE, h->pool[i].bytes, h->stream));
     // The used stretches of the key arena go back to zero: a key pair is only ever compared against bytes that are either
     // zero (no haplotype mask: never equal to a pair) or final, whatever a cache still holds of them.
     if (!h->ctr_synced) sync_counters(h);               // (the cursors; an error the run already reported is not this call's)
@@ -3427,6 +3449,8 @@ int ecb_reset(ecb_handle* h) {
         else
             HIPCHK(h, hipMemsetAsync(h->table, 0, h->cap * sizeof(Slot), h->stream));
     }
+    if (poison && h->pool[ecb_handle::P_LIST].p)
+        HIPCHK(h, hipMemsetAsync(h->pool[ecb_handle::P_LIST].p, POISON_BYTE, h->pool[ecb_handle::P_LIST].bytes, h->stream));
     RCCHK(clear_counters(h));
     if (h->wave_arena) HIPCHK(h, hipMemsetAsync(h->wave_arena, 0, 2 * h->wave_arena_n * sizeof(u64), h->stream));
     // (read_slot keeps the last run's slot ids: every read of the next stream has its entry written by k_stream or k_slow
@@ -4192,6 +4216,16 @@ struct Call {
     const int rc;                        // ECB_OK, or why there is no call: the entry point returns it
 
     Call(int device_, const char* prefix_, bool own_stream = false) : device(device_), prefix(prefix_), rc(open(own_stream)) {}
+    // ECB_POISON_SCRATCH: a call that took a pool buffer leaves the device's whole pool filled -- between calls all of it is dead -- once its
+    // own work has finished and while it still holds g_cv_lock (the members go after this body: pool among them)
+    ~Call() {
+        if (!pool || !poison_scratch()) return;
+        hipSetDevice(device);
+        hipStreamSynchronize(st);
+        for (int i = 0; i < CV_N; ++i)
+            if (const DevBuf<>& b = g_cv[device * CV_N + i]; b.p) hipMemset(b.p, POISON_BYTE, b.bytes);
+        hipDeviceSynchronize();
+    }
     int open(bool own_stream) {
         if (device < 0 || device >= CV_MAX_DEV || hipSetDevice(device) != hipSuccess) return fail(nullptr, ECB_ERR_NO_DEVICE, "no such device");
         if (own_stream) { CALLCHK(*this, hipStreamCreate(&own.s)); st = own.s; }
