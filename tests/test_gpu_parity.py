@@ -271,7 +271,14 @@ def test_mid_size_device_vs_c_oracle_properties(paired):
         i = int(torch.nonzero((hf2 & 0x4) == 0)[1000]) if not paired else int(torch.nonzero((hf2 & 0xC3) == 0x43)[1000])
         hf2[i] ^= (1 << 16)
         bad, _ = b.verify_device(t["read_id"], t["locus"], hf2)
-        assert bad >= 1
+        # (exactly that read: one haplotype bit of one valid record -- the checker on the read's records says whether its set changed)
+        from verify_checker import misplaced
+        rid = t["read_id"].cpu().numpy().view(np.uint32)
+        a, z = np.searchsorted(rid, [rid[i], rid[i] + 1])
+        one = {k: t[k][a:z].cpu().numpy().view(np.uint32) for k in ("locus", "hapflag")}
+        one["read_id"] = np.zeros(z - a, np.uint32)
+        assert int(misplaced(one, dict(one, hapflag=hf2[a:z].cpu().numpy().view(np.uint32)), spec.n_haps).sum()) == 1
+        assert bad == 1
     assert np.all(np.diff(out["indptrA"]) > 0)
     for e in (0, 1, s["n_ecs"] // 2, s["n_ecs"] - 1):            # columns ascending within a row
         row = out["indicesA"][out["indptrA"][e]:out["indptrA"][e + 1]]
