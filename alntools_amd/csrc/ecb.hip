@@ -2499,6 +2499,11 @@ struct ecb_handle {
         u64 meta_hi = 0;                  // meta entries [0, meta_hi) are set
         u64 extra_all = 0, extra_valid = 0, extra_reads = 0;   // counters merged in from other ranks
         u64 n_mismatch = 0;               // ECB_F_VERIFY: reads the exactness pass found in a wrong EC, over all pushes
+        // A push, merge or adopt failed after it had begun to change the table: its return code and text (run_refused).  The table may hold ECs
+        // of half a batch, slots whose key is DEAD_KEY and counters that match neither, so until ecb_reset every entry point but ecb_reset,
+        // ecb_destroy, ecb_last_error and ecb_profile* answers ECB_ERR_STATE before it launches or copies anything (refused_run).
+        int refused = ECB_OK;
+        std::string refusal;
         std::vector<u32> c_rid, c_loc, c_hf; std::vector<int> c_pos;   // open read carried between pushes
         // the occupied slots, listed in pool[P_LIST]: current when d_list_n is set, which is where its length sits on the device
         // (null: not listed, or slot ids have changed since)
@@ -2571,6 +2576,17 @@ int fail(ecb_handle* h, int code, const char* fmt, ...) {
     va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
     if (h) h->err = buf; else t_err = buf;
     return code;
+}
+// A building pass (a batch of a push, a merge, an adopt) hands its return code through here once it has begun to change the table: the
+// first one that is not ECB_OK leaves the run refused (ecb_handle::Run::refused) ...
+int run_refused(ecb_handle* h, int rc) {
+    if (rc != ECB_OK && h->run.refused == ECB_OK) { h->run.refused = rc; h->run.refusal = h->err; }
+    return rc;
+}
+// ... and this is what every later call on the handle answers first, until ecb_reset
+int refused_run(ecb_handle* h) {
+    if (h->run.refused == ECB_OK) return ECB_OK;
+    return fail(h, ECB_ERR_STATE, "this run was refused (%d: %s): ecb_reset the handle", h->run.refused, h->run.refusal.c_str());
 }
 // a failing HIP call ends the function: "<prefix><the call>: <what HIP says>"
 #define HIPCHK_AS(h, prefix, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) \
@@ -2871,8 +2887,8 @@ int verify_batch(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* d
     return ECB_OK;
 }
 
-// one batch of whole reads, device-resident
-int process_batch(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* d_hf, const int* d_pos, u64 n, u32 tw = 512u) {
+// one batch of whole reads, device-resident (*launched: the batch's kernels were queued, so a failure leaves the table half built)
+int build_batch(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* d_hf, const int* d_pos, u64 n, u32 tw, bool* launched) {
     if (n == 0) return ECB_OK;
     // How many reads the stream holds after this batch: the read id of its last record, fetched before anything is launched -- or,
     // when the caller has said how many reads the whole stream holds at most (ecb_hint_reads), that bound now and the
@@ -2899,6 +2915,7 @@ int process_batch(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* 
     HIPCHK(h, hipMemset(timing, 0, 8 * sizeof(u64)));
 #endif
     h->ctr_synced = false;
+    *launched = true;
     const u64 probe_before = h->hctr.n_probe_tiles;
     int rc = ECB_OK;
     for (u32 launch = 0;; ++launch) {
@@ -2951,6 +2968,11 @@ int process_batch(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* 
     h->run.n_reads = reads_after;
     h->run.records_pushed += n;
     return ECB_OK;
+}
+int process_batch(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* d_hf, const int* d_pos, u64 n, u32 tw = 512u) {
+    bool launched = false;
+    const int rc = build_batch(h, d_rid, d_loc, d_hf, d_pos, n, tw, &launched);
+    return launched ? run_refused(h, rc) : rc;
 }
 
 int ensure_staging(ecb_handle* h, u64 need) {
@@ -3256,6 +3278,7 @@ __global__ void k_piece_rows(const PieceDesc* P, u32 n_pieces, const uint4* plac
 // the three pushes: a handle, a stream that still takes records, and the records themselves
 int push_refused(ecb_handle* h, size_t n, bool streams_given) {
     if (!h) return ECB_ERR_ARG;
+    RCCHK(refused_run(h));
     if (!h->can_push()) return fail(h, ECB_ERR_STATE, "push after finalize / table export");
     if (n && !streams_given) return fail(h, ECB_ERR_ARG, "null tuple stream");
     return ECB_OK;
@@ -3269,6 +3292,7 @@ int device_push_refused(ecb_handle* h, const char* who, uintptr_t ptr_bits) {
 }
 // ecb_verify_device / ecb_verify_device_tiled: the exactness pass over one batch, as three streams or as tiles (tw: verify_batch)
 int verify_streams(ecb_handle* h, const void* d_rid, const void* d_loc, const void* d_hf, size_t n, u32 tw, u64* n_mismatch, u64* n_long) {
+    RCCHK(refused_run(h));
     if (!n || !d_rid || !d_loc || !d_hf) return fail(h, ECB_ERR_ARG, "null tuple stream");
     if (((uintptr_t)d_rid | (uintptr_t)d_loc | (uintptr_t)d_hf) & 15) return fail(h, ECB_ERR_ARG, "device streams must be 16-byte aligned");
     HIPCHK(h, hipSetDevice(h->device));
@@ -3277,6 +3301,7 @@ int verify_streams(ecb_handle* h, const void* d_rid, const void* d_loc, const vo
 // ecb_push_cells / ecb_push_cells_device: meta of reads [first_read, first_read + n), from the host or from device memory (`kind`)
 int push_cells(ecb_handle* h, const void* meta, uint64_t first_read, size_t n, hipMemcpyKind kind) {
     if (!h) return ECB_ERR_ARG;
+    RCCHK(refused_run(h));
     if (!h->multisample()) return fail(h, ECB_ERR_STATE, "handle was created without ECB_F_MULTISAMPLE");
     if (h->has_result()) return fail(h, ECB_ERR_STATE, "push after finalize");
     if (!n) return ECB_OK;
@@ -3465,11 +3490,13 @@ int ecb_reset(ecb_handle* h) {
     }
     // (no wait: everything above is ordered on the handle's stream, where all later work goes too)
     h->run = ecb_handle::Run{};
+    h->err.clear();                                     // (the text of a refusal goes with the run it was about)
     return ECB_OK;
 }
 
 int ecb_hint_reads(ecb_handle* h, uint64_t max_reads) {
     if (!h) return ECB_ERR_ARG;
+    RCCHK(refused_run(h));
     if (max_reads >= (1ull << 32)) return fail(h, ECB_ERR_LIMIT, "more than 2^32 - 1 reads");
     h->reads_hint = max_reads;
     return ECB_OK;
@@ -3548,6 +3575,7 @@ int ecb_push_cells_device(ecb_handle* h, const void* d_meta, uint64_t first_read
 
 int ecb_finalize(ecb_handle* h, ecb_sizes* out) {
     if (!h || !out) return ECB_ERR_ARG;
+    RCCHK(refused_run(h));
     HIPCHK(h, hipSetDevice(h->device));
     if (h->run.origin == Origin::ASSEMBLED) { *out = h->run.sizes; return ECB_OK; }   // (the result of ecb_assemble_ranges_device: nothing left to rank)
     if (!h->has_result()) {
@@ -3627,6 +3655,7 @@ int ecb_finalize(ecb_handle* h, ecb_sizes* out) {
 
 int ecb_export_firsts_device(ecb_handle* h, void* d_firsts) {
     if (!h || !d_firsts) return ECB_ERR_ARG;
+    RCCHK(refused_run(h));
     if (!h->has_result() || h->run.origin == Origin::ASSEMBLED) return fail(h, ECB_ERR_STATE, "first reads are exported from a finalized table");
     HIPCHK(h, hipSetDevice(h->device));
     const u64 E = h->run.sizes.n_ecs;
@@ -3640,6 +3669,7 @@ int ecb_assemble_ranges_device(ecb_handle* h, uint32_t n_pieces, const void* con
                                const uint64_t* n_ecs, const uint64_t* nnz, uint64_t total_reads, uint64_t all_alignments,
                                uint64_t valid_alignments, ecb_sizes* out) {
     if (!h || !out) return ECB_ERR_ARG;
+    RCCHK(refused_run(h));
     if (h->has_result() || h->run.origin == Origin::ADOPTED || !h->holds_nothing()) return fail(h, ECB_ERR_STATE, "assembling needs an empty handle");
     if (n_pieces && (!d_indptr || !d_indices || !d_data || !d_counts || !d_firsts || !n_ecs || !nnz)) return fail(h, ECB_ERR_ARG, "null piece lists");
     if (n_pieces > 65535u) return fail(h, ECB_ERR_LIMIT, "at most 65535 pieces");
@@ -3703,12 +3733,14 @@ int ecb_assemble_ranges_device(ecb_handle* h, uint32_t n_pieces, const void* con
 
 int ecb_export_device(ecb_handle* h, void* ia, void* ja, void* da, void* in_, void* jn, void* dn) {
     if (!h) return ECB_ERR_ARG;
+    RCCHK(refused_run(h));
     if (!h->has_result()) return fail(h, ECB_ERR_STATE, "export before finalize");
     return export_result(h, ia, ja, da, in_, jn, dn, hipMemcpyDeviceToDevice);
 }
 
 int ecb_export(ecb_handle* h, int32_t* ia, int32_t* ja, int32_t* da, int32_t* in_, int32_t* jn, int32_t* dn) {
     if (!h) return ECB_ERR_ARG;
+    RCCHK(refused_run(h));
     if (!h->has_result()) return fail(h, ECB_ERR_STATE, "export before finalize");
     if (h->multisample() && (in_ || jn || dn))
         return fail(h, ECB_ERR_STATE, "multisample: N comes from ecb_export_pairs");
@@ -3717,6 +3749,7 @@ int ecb_export(ecb_handle* h, int32_t* ia, int32_t* ja, int32_t* da, int32_t* in
 
 int ecb_export_ranges(ecb_handle* h, int64_t* out) {
     if (!h || !out) return ECB_ERR_ARG;
+    RCCHK(refused_run(h));
     if (!(h->cfg.flags & ECB_F_RANGES)) return fail(h, ECB_ERR_STATE, "handle was created without ECB_F_RANGES");
     HIPCHK(h, hipSetDevice(h->device));
     const u64 ns = (u64)h->cfg.n_loci * h->cfg.n_haplotypes;
@@ -3730,6 +3763,7 @@ int ecb_export_ranges(ecb_handle* h, int64_t* out) {
 
 int ecb_export_range_minmax(ecb_handle* h, int32_t* mn, int32_t* mx) {
     if (!h || !mn || !mx) return ECB_ERR_ARG;
+    RCCHK(refused_run(h));
     if (!(h->cfg.flags & ECB_F_RANGES)) return fail(h, ECB_ERR_STATE, "handle was created without ECB_F_RANGES");
     HIPCHK(h, hipSetDevice(h->device));
     const u64 ns = (u64)h->cfg.n_loci * h->cfg.n_haplotypes;
@@ -3744,6 +3778,7 @@ int ecb_export_range_minmax(ecb_handle* h, int32_t* mn, int32_t* mx) {
 
 int ecb_export_pairs(ecb_handle* h, uint32_t* ec, uint32_t* meta, uint32_t* count, uint32_t* first_read) {
     if (!h || !ec || !meta || !count || !first_read) return ECB_ERR_ARG;
+    RCCHK(refused_run(h));
     if (!h->has_ms_result()) return fail(h, ECB_ERR_STATE, "no multisample result");
     HIPCHK(h, hipSetDevice(h->device));
     const u64 nt = h->run.tri.n;
@@ -3761,6 +3796,7 @@ int ecb_export_pairs(ecb_handle* h, uint32_t* ec, uint32_t* meta, uint32_t* coun
 
 int ecb_export_read_ec(ecb_handle* h, int32_t* out) {
     if (!h || !out) return ECB_ERR_ARG;
+    RCCHK(refused_run(h));
     if (!h->has_result()) return fail(h, ECB_ERR_STATE, "export before finalize");
     if (h->run.extra_reads || h->run.origin == Origin::ASSEMBLED) return fail(h, ECB_ERR_STATE, "per-read EC ids are not kept across a multi-GPU merge");
     HIPCHK(h, hipSetDevice(h->device));
@@ -3775,6 +3811,7 @@ int ecb_export_read_ec(ecb_handle* h, int32_t* out) {
 
 int ecb_table_sizes(ecb_handle* h, uint64_t* n_entries, uint64_t* n_pairs, uint64_t* n_reads) {
     if (!h) return ECB_ERR_ARG;
+    RCCHK(refused_run(h));
     HIPCHK(h, hipSetDevice(h->device));
     if (h->open_read()) RCCHK(stage_and_process(h, nullptr, nullptr, nullptr, nullptr, 0));
     RCCHK(sync_counters(h));
@@ -3793,6 +3830,7 @@ int ecb_table_export_device(ecb_handle* h, void* d_entries, void* d_pairs, uint6
 int ecb_table_merge_batch_device(ecb_handle* h, uint32_t n_tables, const void* const* d_entries, const uint64_t* n_entries,
                                 const void* const* d_pairs, const uint64_t* n_pairs) {
     if (!h) return ECB_ERR_ARG;
+    RCCHK(refused_run(h));
     if (h->has_result()) return fail(h, ECB_ERR_STATE, "merge after finalize");
     if (h->run.origin == Origin::ADOPTED) return fail(h, ECB_ERR_STATE, "merge into a table that adopted entries");
     if (n_tables && (!d_entries || !n_entries || !d_pairs || !n_pairs)) return fail(h, ECB_ERR_ARG, "null table lists");
@@ -3829,13 +3867,14 @@ int ecb_table_merge_batch_device(ecb_handle* h, uint32_t n_tables, const void* c
     k_merge<<<dim3((unsigned)nblk(most, MERGE_PER_BLOCK), (unsigned)desc.size()), TPB, 0, h->stream>>>(reinterpret_cast<const MergeDesc*>(d_desc), h->table, h->cap - 1,
                                                                                                         h->arena, h->arena_cap, h->ctr,
                                                                                                         mlist, list_need, h->run.d_list_n);
-    RCCHK(sync_counters(h));
-    if (h->hctr.n_queue) return fail(h, ECB_ERR_TABLE_FULL, "internal: merge found no slot in a half-empty table");
+    RCCHK(run_refused(h, sync_counters(h)));
+    if (h->hctr.n_queue) return run_refused(h, fail(h, ECB_ERR_TABLE_FULL, "internal: merge found no slot in a half-empty table"));
     return ECB_OK;
 }
 
 int ecb_table_rebase_device(ecb_handle* h, void* d_entries, uint64_t n_entries, uint64_t read_base) {
     if (!h || (n_entries && !d_entries)) return ECB_ERR_ARG;
+    RCCHK(refused_run(h));
     if (read_base >= (1ull << 32) - 1) return fail(h, ECB_ERR_LIMIT, "more than 2^32-2 reads in total");
     if (!n_entries || !read_base) return ECB_OK;
     HIPCHK(h, hipSetDevice(h->device));
@@ -3853,6 +3892,7 @@ int ecb_table_merge_device(ecb_handle* h, const void* d_entries, uint64_t n_entr
 int ecb_table_export_parts_device(ecb_handle* h, void* d_entries, void* d_pairs, uint64_t read_base, uint32_t n_parts,
                                   uint64_t* entry_offsets, uint64_t* pair_offsets) {
     if (!h || !d_entries || !d_pairs || !entry_offsets || !pair_offsets) return ECB_ERR_ARG;
+    RCCHK(refused_run(h));
     if (n_parts == 0 || n_parts > MAX_PARTS) return fail(h, ECB_ERR_LIMIT, "1 .. %u parts", MAX_PARTS);
     HIPCHK(h, hipSetDevice(h->device));
     RCCHK(sync_counters(h));
@@ -3893,6 +3933,7 @@ int ecb_table_export_parts_device(ecb_handle* h, void* d_entries, void* d_pairs,
 int ecb_table_adopt_batch_device(ecb_handle* h, uint32_t n_tables, const void* const* d_entries, const uint64_t* n_entries,
                                 const void* const* d_pairs, const uint64_t* n_pairs) {
     if (!h) return ECB_ERR_ARG;
+    RCCHK(refused_run(h));
     if (h->has_result()) return fail(h, ECB_ERR_STATE, "adopt after finalize");
     if (n_tables && (!d_entries || !n_entries || !d_pairs || !n_pairs)) return fail(h, ECB_ERR_ARG, "null table lists");
     HIPCHK(h, hipSetDevice(h->device));
@@ -3907,8 +3948,8 @@ int ecb_table_adopt_batch_device(ecb_handle* h, uint32_t n_tables, const void* c
     h->run.origin = Origin::ADOPTED; h->run.stage = Stage::COUNTED; h->run.d_list_n = nullptr;
     if (!add_e) return ECB_OK;
     u64 have = h->n_ecs(), top = h->hctr.arena_top;
-    if (top + add_p > h->arena_cap || top + add_p >= (1ull << 32))
-        return fail(h, ECB_ERR_TABLE_FULL, "EC key arena exhausted (%llu pairs): raise arena_capacity", (unsigned long long)h->arena_cap);
+    if (top + add_p > h->arena_cap || top + add_p >= (1ull << 32))      // (nothing was copied, but the handle is an adopting one by now and cannot take this table)
+        return run_refused(h, fail(h, ECB_ERR_TABLE_FULL, "EC key arena exhausted (%llu pairs): raise arena_capacity", (unsigned long long)h->arena_cap));
     if (have + add_e > h->cap) {                        // consecutive slots: a bigger array and a copy, no rehash
         u64 nc = h->cap;
         while (nc < have + add_e) nc *= 2;
@@ -3934,6 +3975,7 @@ int ecb_table_adopt_device(ecb_handle* h, const void* d_entries, uint64_t n_entr
 
 int ecb_export_ec_keys_device(ecb_handle* h, void* d_keys) {
     if (!h || !d_keys) return ECB_ERR_ARG;
+    RCCHK(refused_run(h));
     if (!h->has_result()) return fail(h, ECB_ERR_STATE, "export before finalize");
     HIPCHK(h, hipSetDevice(h->device));
     const u64 E = h->run.sizes.n_ecs;
@@ -3946,6 +3988,7 @@ int ecb_export_ec_keys_device(ecb_handle* h, void* d_keys) {
 int ecb_ms_local_triples_device(ecb_handle* h, const void* d_keys, const void* d_indptr_a, const void* d_indices_a, const void* d_data_a,
                                 uint64_t n_ecs, uint64_t read_base, void* d_key, void* d_count, void* d_first, uint64_t* n_triples) {
     if (!h || !n_triples) return ECB_ERR_ARG;
+    RCCHK(refused_run(h));
     if (!h->multisample()) return fail(h, ECB_ERR_STATE, "handle was created without ECB_F_MULTISAMPLE");
     if (h->has_result() || h->run.origin == Origin::ADOPTED) return fail(h, ECB_ERR_STATE, "a shard's triples come from the handle its reads were pushed into");
     *n_triples = 0;
@@ -3976,6 +4019,7 @@ int ecb_ms_local_triples_device(ecb_handle* h, const void* d_keys, const void* d
 int ecb_ms_adopt_triples_device(ecb_handle* h, uint32_t n_tables, const void* const* d_key, const void* const* d_count,
                                 const void* const* d_first, const uint64_t* n, uint64_t* n_triples) {
     if (!h) return ECB_ERR_ARG;
+    RCCHK(refused_run(h));
     if (!h->multisample()) return fail(h, ECB_ERR_STATE, "handle was created without ECB_F_MULTISAMPLE");
     if (!h->has_result() || !h->entries_from_elsewhere()) return fail(h, ECB_ERR_STATE, "triples are adopted by the finalized handle that adopted the merged ECs (or assembled their ranges)");
     if (n_tables && (!d_key || !d_count || !d_first || !n)) return fail(h, ECB_ERR_ARG, "null lists");
@@ -4017,6 +4061,7 @@ int ecb_ms_adopt_triples_device(ecb_handle* h, uint32_t n_tables, const void* co
 
 int ecb_ms_filter(ecb_handle* h, uint32_t n_cells, int64_t minimum_count, ecb_ms_sizes* out) {
     if (!h || !out) return ECB_ERR_ARG;
+    RCCHK(refused_run(h));
     if (!h->has_ms_result()) return fail(h, ECB_ERR_STATE, "no multisample result");
     if (h->awaits_triples()) return fail(h, ECB_ERR_STATE, "multisample across GPUs: no triples adopted yet (ecb_ms_adopt_triples_device)");
     if (!n_cells || n_cells > (1u << ECB_CELL_BITS)) return fail(h, ECB_ERR_ARG, "n_cells out of range");
@@ -4140,6 +4185,7 @@ int ecb_ms_filter(ecb_handle* h, uint32_t n_cells, int64_t minimum_count, ecb_ms
 
 int ecb_ms_export(ecb_handle* h, uint32_t* kept_cells, int32_t* ia, int32_t* ja, int32_t* da, int32_t* in_, int32_t* jn, int32_t* dn) {
     if (!h) return ECB_ERR_ARG;
+    RCCHK(refused_run(h));
     if (!h->run.flt.cells) return fail(h, ECB_ERR_STATE, "ecb_ms_export before ecb_ms_filter");
     HIPCHK(h, hipSetDevice(h->device));
     const ecb_ms_sizes& m = h->run.msf;
@@ -4157,6 +4203,7 @@ int ecb_ms_export(ecb_handle* h, uint32_t* kept_cells, int32_t* ia, int32_t* ja,
 
 int ecb_counters(ecb_handle* h, uint64_t* all_alignments, uint64_t* valid_alignments, uint64_t* n_reads) {
     if (!h) return ECB_ERR_ARG;
+    RCCHK(refused_run(h));
     HIPCHK(h, hipSetDevice(h->device));
     if (!h->has_result() && h->open_read()) RCCHK(stage_and_process(h, nullptr, nullptr, nullptr, nullptr, 0));
     RCCHK(sync_counters(h));
@@ -4168,6 +4215,7 @@ int ecb_counters(ecb_handle* h, uint64_t* all_alignments, uint64_t* valid_alignm
 
 int ecb_add_counters(ecb_handle* h, uint64_t all_alignments, uint64_t valid_alignments, uint64_t n_reads) {
     if (!h) return ECB_ERR_ARG;
+    RCCHK(refused_run(h));
     h->run.extra_all += all_alignments; h->run.extra_valid += valid_alignments; h->run.extra_reads += n_reads;
     return ECB_OK;
 }
@@ -5912,8 +5960,10 @@ struct Piece {
 extern "C" int ecb_merge(ecb_handle* const* shards, uint32_t n, ecb_handle* root, ecb_sizes* out) {
     if (!shards || !n || !root || !out) return fail(root, ECB_ERR_ARG, "ecb_merge: null argument");
     if (n > MAX_PARTS) return fail(root, ECB_ERR_LIMIT, "ecb_merge: at most %u shards", MAX_PARTS);
+    RCCHK(refused_run(root));
     for (u32 r = 0; r < n; ++r) {
         if (!shards[r] || shards[r] == root) return fail(root, ECB_ERR_ARG, "ecb_merge: shard %u is null or the root itself", r);
+        if (const int rc = refused_run(shards[r])) return fail(root, rc, "ecb_merge: shard %u: %s", r, ecb_last_error(shards[r]));
         if (shards[r]->cfg.n_loci != root->cfg.n_loci || shards[r]->cfg.n_haplotypes != root->cfg.n_haplotypes)
             return fail(root, ECB_ERR_ARG, "ecb_merge: shard %u was created for other targets than the root", r);
         if ((shards[r]->cfg.flags | root->cfg.flags) & ECB_F_MULTISAMPLE) return fail(root, ECB_ERR_STATE, "ecb_merge: single-sample handles (the multisample merge has a second exchange: alntools_amd/dist.py)");

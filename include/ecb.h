@@ -59,6 +59,14 @@ extern "C" {
 #define ECB_ERR_EMPTY       -7   /* no valid alignment at all (the reference fails too: bam_utils.py:336-339) */
 #define ECB_ERR_LIMIT       -8   /* result exceeds the .bin format's int32 limits (bin_utils.py:214-232) */
 #define ECB_ERR_VERIFY      -9   /* ECB_F_VERIFY: the exactness pass found a read in an EC whose key is not its target set */
+/* A refused run.  A push, a merge or an adopt that fails once it has begun to build -- anything the device reports for a batch (ECB_ERR_TABLE_FULL,
+ * ECB_ERR_CONTRACT, ECB_ERR_LIMIT, ECB_ERR_VERIFY, ECB_ERR_HIP), a merge that overruns the arena, an adopt whose pairs do not fit it -- leaves the handle's
+ * run REFUSED: its table may hold half a batch.  Until ecb_reset, every entry point that takes the handle answers ECB_ERR_STATE, before it launches or
+ * copies anything, with the text "this run was refused (<code>: <text of the refusal>): ecb_reset the handle"; only ecb_reset, ecb_destroy, ecb_last_error,
+ * ecb_profile, ecb_profile_read and ecb_profile_kernel are exempt (ecb_merge answers so for a refused root or shard).  ecb_reset is the recovery: the handle
+ * is then as good as new -- with a larger arena_capacity or ec_capacity only through a new handle -- and ecb_last_error(h) is empty again.  A call that is
+ * refused before anything was queued (a bad argument, a call out of order, a run counter that falls between two pushes) leaves the run as it was; a refusal
+ * of ecb_verify_device*, which builds nothing, does not make the run a refused one. */
 
 #define ECB_F_RANGES        1u   /* track min/max reference_start per (locus, haplotype) */
 #define ECB_F_MULTISAMPLE   2u   /* per-read cell ids; N becomes EC x cell (bam_utils_multisample.py) */

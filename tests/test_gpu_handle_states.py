@@ -1,11 +1,14 @@
 """The lifecycle of an ``ecb_handle`` (``ecb.hip: ecb_handle::Run``, ``Stage``, ``Origin``, ``Triples``), from outside: what every
-entry point that takes a handle answers in every state a caller can bring one into, and that ``ecb_reset`` forgets all of a run."""
+entry point that takes a handle answers in every state a caller can bring one into, and that ``ecb_reset`` forgets all of a run.
+A run that was refused -- a push or a merge that failed after it had begun to change the table -- is a state too (``Run::refused``)."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from alntools_amd import ecb
+
+import refusal_streams as rs
 
 pytestmark = pytest.mark.gpu
 
@@ -25,6 +28,21 @@ def _stream(seed, n_reads, first=0):
 
 NA, NB = 40, 64
 A, A_NEXT, B = _stream(1, NA), _stream(2, 10, first=NA), _stream(3, NB)      # the first stream, one that continues it, a second, longer one
+BAD = dict(A, read_id=A["read_id"] * 2)                                        # the run counter steps by two
+
+
+def _long_keys(seed, n_reads):
+    """Reads of one record on every locus: keys of L pairs, L - INL of them in the arena, told apart by their haplotypes."""
+    r = np.random.RandomState(seed)
+    n = n_reads * L
+    return dict(read_id=np.repeat(np.arange(n_reads), L).astype(np.uint32), locus=np.tile(np.arange(L), n_reads).astype(np.uint32),
+                hapflag=(r.randint(0, H, n) << 16).astype(np.uint32), pos=r.randint(0, 100000, n).astype(np.int32), n_reads=n_reads,
+                meta=r.randint(0, CELLS, n_reads).astype(np.uint32))
+
+
+TIGHT = rs.ARENA                                                               # pairs of the arena that LONG overruns
+LONG = _long_keys(4, 700)
+assert rs.key_pairs_beyond_the_slot(LONG) >= 4 * TIGHT                         # (the margin of test_gpu_refused_runs.py: no boundary is guessed)
 
 
 class _Fix(object):
@@ -35,7 +53,7 @@ class _Fix(object):
         self.torch, self.dev = torch, torch.device("cuda:0")
         self.lib = ecb.load()
         up = lambda a: torch.from_numpy(a.view(np.int32)).to(self.dev)
-        self.dA, self.dNext, self.dB = ({k: up(t[k]) for k in ("read_id", "locus", "hapflag", "pos", "meta")} for t in (A, A_NEXT, B))
+        self.dA, self.dNext, self.dB, self.dBad, self.dLong = ({k: up(t[k]) for k in ("read_id", "locus", "hapflag", "pos", "meta")} for t in (A, A_NEXT, B, BAD, LONG))
         self.tiles = {id(d): ecb.tile_tuples(d["read_id"], d["locus"], d["hapflag"]) for d in (self.dA, self.dNext)}
         with self.new("plain") as d:                     # the donor: its table as exchanged between GPUs, and its finalized result as one piece
             d.push_device(self.dA["read_id"], self.dA["locus"], self.dA["hapflag"])
@@ -49,6 +67,12 @@ class _Fix(object):
             s = d.finalize()
             self.piece = tuple(torch.zeros(BIG, dtype=torch.int32, device=self.dev) for _ in range(5)) + (s["n_ecs"], s["nnz_a"])
             d.export_piece_device(*self.piece[:5])
+        with self.new("plain", arena=1 << 18, slots=4096) as d:         # a second donor: the table of LONG (fifteen times its pairs of arena)
+            d.push_device(self.dLong["read_id"], self.dLong["locus"], self.dLong["hapflag"])
+            self.long_ne, bound, _ = d.table_sizes()
+            self.long_ent = torch.zeros(4 * self.long_ne, dtype=torch.int64, device=self.dev)
+            self.long_prs = torch.zeros(bound, dtype=torch.int64, device=self.dev)
+            self.long_np = d.table_export_parts_device(self.long_ent, self.long_prs, 0, 1)[1][-1]
         self.dbuf = [torch.zeros(8 * BIG, dtype=torch.int64, device=self.dev) for _ in range(7)]      # device outputs
         self.hbuf = [np.zeros(BIG, np.int64) for _ in range(8)]                                          # host outputs
         self.key1 = torch.zeros(2, dtype=torch.int64, device=self.dev)                                   # one merged EC: row {locus 0: mask 1}
@@ -58,8 +82,8 @@ class _Fix(object):
                     torch.zeros(2, dtype=torch.int32, device=self.dev), 2)
         torch.cuda.synchronize()
 
-    def new(self, kind):
-        return ecb.EcBuilder(L, H, ec_capacity=1024, arena_capacity=1 << 16, track_ranges=kind == "ranges", multisample=kind == "ms")
+    def new(self, kind, arena=1 << 16, slots=1024):
+        return ecb.EcBuilder(L, H, ec_capacity=slots, arena_capacity=arena, track_ranges=kind == "ranges", multisample=kind == "ms")
 
 
 # ---- states -----------------------------------------------------------------------------------------------------------------------------------
@@ -125,6 +149,24 @@ def _filtered(F, b, kind):
     b.ms_filter_sizes(CELLS, 1)
 
 
+def _refused(code, what):
+    with pytest.raises(ecb.EcbError) as e:
+        what()
+    assert e.value.code == code, str(e.value)
+
+
+def _push_refused_contract(F, b, kind):
+    _refused(-5, lambda: _push(F, b, F.dBad, kind))
+
+
+def _push_refused_arena(F, b, kind):
+    _refused(-4, lambda: _push(F, b, F.dLong, kind))
+
+
+def _merge_refused_arena(F, b, kind):
+    _refused(-4, lambda: b.table_merge_device(F.long_ent, F.long_ne, F.long_prs, F.long_np))
+
+
 #: state -> (how a fresh handle gets there, the kinds of handle it is reached with: the first is the one the refusals are recorded for)
 STATES = {
     "fresh": (_fresh, ("plain", "ms", "ranges")), "pushed": (_pushed, ("plain", "ms", "ranges")), "open read": (_open_read, ("plain", "ranges")),
@@ -134,10 +176,22 @@ STATES = {
 }
 
 
+#: the states a refusal leaves: state -> (how a fresh handle gets there, kinds, (key arena, table slots) of the handle, code and text of the
+#: refusal, what ecb_profile_kernel says).  They join STATES below RECORDED, where their rows are written down.
+CONTRACT_TEXT = "read_id run counter violates the tuple contract (see ecb.h)"
+ARENA_TEXT = "EC key arena exhausted (%d pairs): raise arena_capacity" % TIGHT
+REFUSED = {
+    "push refused, contract": (_push_refused_contract, ("plain", "ms", "ranges"), (), -5, CONTRACT_TEXT, "ks_std::k_stream<false, false>"),
+    "push refused, arena": (_push_refused_arena, ("plain", "ms", "ranges"), (TIGHT, 4096), -4, ARENA_TEXT, "ks_std::k_stream<false, false>"),
+    "merge refused, arena": (_merge_refused_arena, ("plain",), (TIGHT, 4096), -4, ARENA_TEXT, ""),
+}
+SHAPE = {s_: v_[2] for s_, v_ in REFUSED.items()}
+
+
 def _enter(F, state, after_reset, kind=None):
     make, kinds = STATES[state]
     kind = kind or kinds[0]
-    b = F.new(kind)
+    b = F.new(kind, *SHAPE.get(state, ()))
     b.kind, b.next = kind, F.dA                            # next: the stream a push continues the handle's with
     make(F, b, kind)
     if after_reset:
@@ -530,11 +584,29 @@ RECORDED = {
 }
 
 
+# The states after a refusal are not recorded from a library -- the parent's ran ecb_finalize's kernels over a half-built table there -- but
+# written down from the rule of include/ecb.h: a refused run answers every call but ecb_reset (ecb_destroy), ecb_last_error and ecb_profile*
+# with ECB_ERR_STATE and a text that names the refusal, before anything else is looked at; the calls that succeed leave the refusal's text
+# in place (ecb_reset forgets it).  After ecb_reset the handle answers as "fresh, reset" does -- as "pushed, reset" where a push was refused,
+# which is the same in every row but ecb_profile_kernel's: the handle keeps naming the last kernel it launched.
+RECORDED = {c_: {k_: list(v_) for k_, v_ in by_.items()} for c_, by_ in RECORDED.items()}       # (ALL was one list)
+for s_, (make_, kinds_, _, code_, text_, kernel_) in REFUSED.items():
+    STATES[s_] = (make_, kinds_)
+    for c_, by_ in RECORDED.items():
+        got_ = {"ecb_reset": (0, ""), "ecb_profile": (0, text_), "ecb_profile_read": (0, text_), "ecb_last_error": (0, text_),
+                "ecb_profile_kernel": (0, kernel_)}.get(c_, (-6, "this run was refused (%d: %s): ecb_reset the handle" % (code_, text_)))
+        by_.setdefault(got_, []).append(s_)
+        twin_ = "pushed, reset" if kernel_ else "fresh, reset"
+        next(v_ for v_ in by_.values() if twin_ in v_).append(s_ + ", reset")
+
+
 def test_every_entry_point_answers_as_before_in_every_state():
     """Every (state, entry point) pair: a new handle is brought into the state -- fresh, pushed, a host push with an open read, counted by a
     table export, merged into, adopted, finalized, finalized multisample with its own triples / adopted without triples / adopted with
     triples, assembled, filtered, and each of these followed by ``ecb_reset`` -- the entry point is called once with arguments that are
     otherwise valid, and the return code and ``ecb_last_error(h)`` are compared with literals recorded from the parent commit's library.
+    The states a refusal leaves -- a push that broke the tuple contract, a push and a merge that overran a key arena of 4 096 pairs -- and
+    their resets are pinned to the rule of ``include/ecb.h`` (the rows are built below ``RECORDED``).
     A pair whose call succeeds is pinned to ECB_OK (0).  No pair is left out: the table is checked against ``ecb.SYMBOLS``."""
     F = _Fix()
     calls = _calls(F)
