@@ -2873,13 +2873,28 @@ int launch_stream(ecb_handle* h, StreamVariant v, const StreamPlan& P, const u32
 // set is derived again from its records and compared, pair by pair, with the key of the EC the read was given.
 // Reads longer than a tile go through k_slow's compare.  *n_mismatch = reads in a wrong EC (0 = exact); *n_long = how many
 // took the long path.
+int verify_pass(ecb_handle* h, const StreamPlan& P, const u32* d_rid, const u32* d_loc, const u32* d_hf, u64 n, u32 prev_rid, u64* n_long, u32 tw) {
+    RCCHK(launch_stream(h, SV_VERIFY, P, d_rid, d_loc, d_hf, nullptr, n, prev_rid, nullptr, 0, 0));
+    RCCHK(sync_counters(h));
+    return run_deferred(h, d_rid, d_loc, d_hf, n, true, tw, n_long);
+}
 int verify_batch(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* d_hf, u64 n, u32 prev_rid, u64* n_mismatch, u64* n_long, u32 tw = 512u) {
     StreamPlan P;
     RCCHK(plan_stream(h, n, &P, SV_VERIFY));
-    RCCHK(launch_stream(h, SV_VERIFY, P, d_rid, d_loc, d_hf, nullptr, n, prev_rid, nullptr, 0, 0));
-    RCCHK(sync_counters(h));
     u64 nq = 0;
-    RCCHK(run_deferred(h, d_rid, d_loc, d_hf, n, true, tw, &nq));
+    if (const int rc = verify_pass(h, P, d_rid, d_loc, d_hf, n, prev_rid, &nq, tw); rc != ECB_OK) {
+        // The pass built nothing, so what it refused is the stream it was shown, not the run (ecb.h): the error bits its kernels left go with the
+        // refusal -- left standing, they were reported once more by whichever call read the counters next, a push or a finalize of sound input.
+        // (No run with a bit of its own gets here: it is a refused run, which verify_streams and process_batch answer first.)
+        if (h->hctr.err) {
+            const std::string refusal = h->err;          // (a clear that fails is its own error; one that succeeds leaves the refusal's text)
+            HIPCHK(h, hipMemsetAsync(&h->ctr->err, 0, sizeof(u32), h->stream));
+            HIPCHK(h, hipMemsetAsync(&h->ctr->n_queue, 0, (1 + QSTRIPES) * sizeof(u64), h->stream));
+            h->hctr.err = 0; h->hctr.n_queue = 0;
+            h->err = refusal;
+        }
+        return rc;
+    }
     *n_mismatch = h->hctr.n_mismatch;
     *n_long = nq;
     HIPCHK(h, hipMemsetAsync(&h->ctr->n_queue, 0, (1 + QSTRIPES) * sizeof(u64), h->stream));      // (the queue is drained: not a launch, the other per-launch words stay)
@@ -3632,7 +3647,7 @@ int ecb_finalize(ecb_handle* h, ecb_sizes* out) {
                                                                                        h->run.csr.indices, h->run.csr.data, h->cfg.n_loci, h->cfg.n_haplotypes, h->ctr);
     u64* const tot = h->pin_out->tot;
     HIPCHK(h, hipMemcpyAsync(tot, d_tot, 4 * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
-    RCCHK(sync_counters(h));                           // the one wait
+    RCCHK(run_refused(h, sync_counters(h)));           // the one wait (an index out of range that only the emit sees, a count beyond int32: the run cannot end)
     h->run.n_list = tot[0];
     if (tot[0] != E) return fail(h, ECB_ERR_HIP, "internal: %llu occupied slots but %llu ECs created", (unsigned long long)tot[0], (unsigned long long)E);
     if (tot[1] != E) return fail(h, ECB_ERR_HIP, "internal: %llu distinct first-appearance indices for %llu ECs", (unsigned long long)tot[1], (unsigned long long)E);

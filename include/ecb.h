@@ -30,12 +30,22 @@
  *                 host numbers those runs 0,1,2,... and every record -- passing or not --
  *                 carries the number of the latest run started at or before it
  *                 (0xFFFFFFFF before the first).  So read_id never decreases, steps by at
- *                 most 1, and steps only on a passing record; the library verifies this.
- *   locus    u32  index of the record's main target (bam_utils.py:596-598 order)
+ *                 most 1, and steps only on a passing record.  The library verifies this within
+ *                 and across pushes (ECB_ERR_CONTRACT from the push whose batch holds the record)
+ *                 over groups of four records: steps that are all even and cancel within one
+ *                 aligned group of four (a, a+2, a, a) are NOT detected, and the result is then
+ *                 undefined.
+ *   locus    u32  index of the record's main target (bam_utils.py:596-598 order), < n_loci
  *   hapflag  u32  bits 0-11 BAM flag; bit 12 = (refID != next_refID); bit 13 = (next_pos < 0)
  *                 (the two fields of the filter that are not in the flag, bam_utils.py:269);
- *                 bits 16-23 haplotype index (bam_utils.py:602 order); other bits 0
+ *                 bits 16-23 haplotype index (bam_utils.py:602 order), < n_haplotypes;
+ *                 bits 24-31 zero; bits 14-15 are ignored
  *   pos      i32  reference_start, only with ECB_F_RANGES (bam_utils.py:282-286)
+ * locus, the haplotype index and bits 24-31 are verified in records that pass the filter (nothing but read_id
+ * is looked at in the others): ECB_ERR_CONTRACT from the push where the stream kernel cannot carry the value
+ * (locus >= 2^26 - 1 -- 2^25 - 1 for batches of short reads, see ecb_hint_reads --, a haplotype
+ * index >= 32 -- >= 8 there --, a bit among 24-31) or the read is longer than a tile of 512 records, and from
+ * ecb_finalize at the latest otherwise; locus 0xFFFFFFFF alone may go unnoticed.  DESIGN.md section 2 lists every check.
  */
 #ifndef ECB_H
 #define ECB_H
@@ -61,12 +71,12 @@ extern "C" {
 #define ECB_ERR_VERIFY      -9   /* ECB_F_VERIFY: the exactness pass found a read in an EC whose key is not its target set */
 /* A refused run.  A push, a merge or an adopt that fails once it has begun to build -- anything the device reports for a batch (ECB_ERR_TABLE_FULL,
  * ECB_ERR_CONTRACT, ECB_ERR_LIMIT, ECB_ERR_VERIFY, ECB_ERR_HIP), a merge that overruns the arena, an adopt whose pairs do not fit it -- leaves the handle's
- * run REFUSED: its table may hold half a batch.  Until ecb_reset, every entry point that takes the handle answers ECB_ERR_STATE, before it launches or
+ * run REFUSED: its table may hold half a batch; so does an ecb_finalize that the device refuses (an index out of range that only the emit sees).  Until ecb_reset, every entry point that takes the handle answers ECB_ERR_STATE, before it launches or
  * copies anything, with the text "this run was refused (<code>: <text of the refusal>): ecb_reset the handle"; only ecb_reset, ecb_destroy, ecb_last_error,
  * ecb_profile, ecb_profile_read and ecb_profile_kernel are exempt (ecb_merge answers so for a refused root or shard).  ecb_reset is the recovery: the handle
  * is then as good as new -- with a larger arena_capacity or ec_capacity only through a new handle -- and ecb_last_error(h) is empty again.  A call that is
  * refused before anything was queued (a bad argument, a call out of order, a run counter that falls between two pushes) leaves the run as it was; a refusal
- * of ecb_verify_device*, which builds nothing, does not make the run a refused one. */
+ * of ecb_verify_device*, which builds nothing, does not make the run a refused one: the run goes on as if the call had not been made. */
 
 #define ECB_F_RANGES        1u   /* track min/max reference_start per (locus, haplotype) */
 #define ECB_F_MULTISAMPLE   2u   /* per-read cell ids; N becomes EC x cell (bam_utils_multisample.py) */

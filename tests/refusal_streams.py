@@ -19,6 +19,8 @@ import numpy as np
 from alntools_amd import synth
 from oracle import ec_oracle as orc
 
+from tuple_contract import obeys_contract              # (the streams of contract_streams.py are held to it too)
+
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "alntools_amd", "csrc")
 ARENA = 4096                     # arena_capacity of the handle that is refused: one region, eight ARENA_CHUNKs
 SEED = 77
@@ -84,19 +86,6 @@ def recovery_need(t):
     four covers): one ARENA_CHUNK per wave of the launch, and the pairs themselves."""
     n = len(t["read_id"])
     return (n + 2 * WT - 1) // (2 * WT) * ARENA_CHUNK + key_pairs_beyond_the_slot(t)
-
-
-def obeys_contract(t, n_loci, n_haps):
-    """The tuple contract of ``include/ecb.h``: the run counter starts at 0xFFFFFFFF or 0, never falls, steps by one and only on a valid
-    record; loci and haplotypes of valid records in range; no bit outside flag, host bits and haplotype."""
-    rid, hf = t["read_id"].astype(np.int64), t["hapflag"].astype(np.int64)
-    v = orc.tuples_valid(t["hapflag"])
-    prev = np.r_[-1, np.where(rid == 0xFFFFFFFF, -1, rid)[:-1]]
-    cur = np.where(rid == 0xFFFFFFFF, -1, rid)
-    step = cur - prev
-    return bool(len(rid) and np.all((step == 0) | ((step == 1) & v)) and np.all(t["locus"][v] < n_loci)
-                and np.all(((hf[v] >> 16) & 0xFF) < n_haps) and np.all((hf & ~0x00FF3FFF) == 0)
-                and all(t[k].dtype == np.uint32 for k in ("read_id", "locus", "hapflag")) and t["pos"].dtype == np.int32)
 
 
 # ---- generators -------------------------------------------------------------------------------------------------------------------------
