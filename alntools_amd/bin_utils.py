@@ -206,6 +206,73 @@ def ecbundle(ec_filename, grp_filename, out_filename, device=0):
         raise
 
 
+def named_samples(m, samples=None, samples_file=None):
+    """What ``ecselect``'s ``-s`` and ``--samples FILE`` name -> a bool array over the ``.bin``'s samples, or None when neither is given
+    (all are named).  The file holds one name per line, blank lines ignored; a name twice counts once; a name that is not in the ``.bin``
+    is a KeyError naming it."""
+    if samples is None and samples_file is None:
+        return None
+    names = list(samples or [])
+    if samples_file is not None:
+        with open(samples_file) as fh:
+            names += [ln.strip() for ln in fh if ln.strip()]
+    sid = dict(zip(m.sname, range(m.num_samples)))
+    keep = np.zeros(m.num_samples, dtype=bool)
+    for n in names:
+        if n not in sid:
+            raise KeyError("sample {} is not in the EC file".format(n))
+        keep[sid[n]] = True
+    return keep
+
+
+def ecselect(ec_filename, out_filename, row_class=None, samples=None, samples_file=None, mincount=None, device=0):
+    """``alntools ecselect``: a part of a ``.bin`` -- the reads of one class (``row_class``: None, ``"unique"``, ``"locus-unique"`` or
+    ``"multi"``: the selection of the reference's ``get_unique_reads``, ``AlignmentPropertyMatrix.py:386-427``) in the named samples that
+    still count ``max(mincount, 1)`` of them (the cell threshold of the reference's ``bam2ec --multisample``,
+    ``bam_utils_multisample.py:596-636``; None: no sample is dropped for its total).  The names are resolved here (``named_samples``)
+    before libecb is loaded; A and N are selected on the GPU (``ecb.select``).  Rows that keep no count leave the file, the others keep
+    their order; targets, lengths and haplotypes are copied, the samples are the kept ones in the input's order.  A result without a
+    sample or without a read is refused.  Any failure is logged as ``Error: ...``, no file is written and the exception is raised again
+    (the command line exits with status 1)."""
+    import time
+    from . import utils
+    LOG = utils.get_logger()
+    try:
+        start_time = time.time()
+        LOG.info("Loading {}...".format(ec_filename))
+        m = ecload(ec_filename)
+        named = named_samples(m, samples, samples_file)
+        from . import ecb
+        if row_class not in ecb.ROW_CLASSES:
+            raise ValueError("no such read class: {}".format(row_class))
+        LOG.info("Selecting {} reads of {:,} samples...".format(row_class or "all", m.num_samples if named is None else int(named.sum())))
+        A_N, kept = ecb.select(m.indptrA, m.indicesA, m.dataA, m.indptrN, m.indicesN, m.dataN, m.num_loci, m.num_haplotypes,
+                               row_class=row_class, sample_keep=named, min_count=mincount, device=device)
+        out = ECMatrices(m.hname, m.lname, m.lengths, [s for s, k in zip(m.sname, kept) if k], *A_N)
+        if out.num_samples == 0:
+            raise ValueError("no sample left")
+        if out.num_reads == 0:
+            raise ValueError("no read left")
+        LOG.info("Saving to {}...".format(out_filename))
+        LOG.info("Number of haplotypes: {:,}".format(out.num_haplotypes))
+        LOG.info("Number of reference targets: {:,}".format(out.num_loci))
+        LOG.info("Number of samples: {:,} (from {:,})".format(out.num_samples, m.num_samples))
+        LOG.info("Number of ECs: {:,} (from {:,} rows)".format(out.num_reads, m.num_reads))
+        b = ecsave2_bytes(out)
+        try:
+            with open(out_filename, 'wb') as fh:
+                fh.write(b)
+        except BaseException:
+            if os.path.exists(out_filename):
+                os.remove(out_filename)
+            raise
+        LOG.info("Saving completed")
+        LOG.info("{} created in total time: {}".format(out_filename, utils.format_time(start_time, time.time())))
+    except Exception as e:
+        LOG.error("Error: {}".format(e.args[0] if isinstance(e, KeyError) and e.args else str(e)))
+        raise
+
+
 def genotype_mask(m, gt_filename, gname, groups):
     """Genotype file -> ``mask u32[T]`` (bit h = haplotype h allowed at that locus) -- ``AlignmentPropertyMatrix.apply_genotypes``
     (``AlignmentPropertyMatrix.py:483-505``): the leading lines that start with ``#`` are skipped; every later line gives ``gene,

@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
 """Command line with the reference's hot-path sub-commands and options (``alntools/cli.py:43-113``):
-``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``, ``apply-genotypes``, ``ecmerge``, ``ecbundle``, ``salmon2ec``, ``count-alignments``, ``ecdump``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
+``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``, ``apply-genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``count-alignments``, ``ecdump``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
 from __future__ import annotations
 
 import glob
@@ -139,6 +139,30 @@ def ecbundle(ec_file, grp_file, out_file, verbose):
         methods.ecbundle(ec_file, grp_file, out_file)
     except Exception:
         sys.exit(1)                                                  # (logged as "Error: ..." by bin_utils.ecbundle)
+
+
+@cli.command('ecselect', options_metavar='<options>', short_help='keep a class of reads and the samples that still count them')
+@click.argument('ec_file', metavar='ec_file', type=click.Path(exists=True, resolve_path=True, dir_okay=False))
+@click.argument('out_file', metavar='out_file', type=click.Path(resolve_path=True, dir_okay=False, writable=True))
+@click.option('--unique', 'classes', flag_value='unique', multiple=True, help='keep the reads with one alignment to one haplotype')
+@click.option('--locus-unique', 'classes', flag_value='locus-unique', multiple=True, help='keep the reads that align to one target')
+@click.option('--multi', 'classes', flag_value='multi', multiple=True, help='keep the reads that align to two targets or more')
+@click.option('-s', '--sample', 'samples', metavar='NAME', multiple=True, help="sample to keep, can specify multiple (default: all)")
+@click.option('--samples', 'samples_file', metavar='FILE', type=click.Path(exists=True, resolve_path=True, dir_okay=False),
+              help="file with the names of the samples to keep, one per line")
+@click.option('-m', '--mincount', default=None, type=int, help='drop the samples that count fewer reads than this')
+@click.option('-v', '--verbose', count=True, help='enables verbose mode')
+def ecselect(ec_file, out_file, classes, samples, samples_file, mincount, verbose):
+    """
+    Pull a class of reads and the samples that still count enough of them out of a binary EC file (ec_file) and write the result (out_file)
+    """
+    if len(classes) > 1:
+        raise click.UsageError('at most one of --unique, --locus-unique and --multi')
+    utils.configure_logging(verbose)
+    try:
+        methods.ecselect(ec_file, out_file, classes[0] if classes else None, list(samples) or None, samples_file, mincount)
+    except Exception:
+        sys.exit(1)                                                  # (logged as "Error: ..." by bin_utils.ecselect)
 
 
 @cli.command('salmon2ec', options_metavar='<options>', short_help='convert a salmon eq_classes file to EC')

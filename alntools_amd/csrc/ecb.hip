@@ -4734,10 +4734,8 @@ inline u32 ca_window_bits(u32 n_haps) {
     const u32 fit = CA_LDS_BYTES / 8u / (2u * n_haps + 1u);
     return 31u - (u32)__builtin_clz(fit);
 }
-// thread j: column pointer j of N (j <= S) and entry j (j < nnz_n): everything checked, the entries of the sample(s) asked for added to ww
-__global__ __launch_bounds__(TPB) void k_ca_weights(const int* indptr_n, u32 n_samples, const int* indices_n, const int* data_n, u64 nnz_n,
-                                                    u32 n_ecs, long long sample, u64* ww, u64* words) {
-    const u64 j = blockIdx.x * (u64)TPB + threadIdx.x;
+// what is wrong with column pointer j of N (j <= S) and with its entry j (j < nnz_n): CA_ERR_* bits (count-alignments and ecselect)
+__device__ __forceinline__ u32 ca_n_errors(u64 j, const int* indptr_n, u32 n_samples, const int* indices_n, const int* data_n, u64 nnz_n, u32 n_ecs) {
     u32 err = 0;
     if (j <= n_samples) {
         const long long a = indptr_n[j];
@@ -4745,10 +4743,20 @@ __global__ __launch_bounds__(TPB) void k_ca_weights(const int* indptr_n, u32 n_s
         else if (j < n_samples && indptr_n[j + 1] < a) err |= CA_ERR_NPTR;
     }
     if (j < nnz_n) {
-        const int e = indices_n[j], c = data_n[j];
+        const int e = indices_n[j];
         if (e < 0 || (u32)e >= n_ecs) err |= CA_ERR_EC;
-        else if (c < 0) err |= CA_ERR_NEG;
-        else if (c > 0 && (sample < 0 || ((long long)j >= indptr_n[sample] && (long long)j < indptr_n[sample + 1])))
+        else if (data_n[j] < 0) err |= CA_ERR_NEG;
+    }
+    return err;
+}
+// thread j: column pointer j of N (j <= S) and entry j (j < nnz_n): everything checked, the entries of the sample(s) asked for added to ww
+__global__ __launch_bounds__(TPB) void k_ca_weights(const int* indptr_n, u32 n_samples, const int* indices_n, const int* data_n, u64 nnz_n,
+                                                    u32 n_ecs, long long sample, u64* ww, u64* words) {
+    const u64 j = blockIdx.x * (u64)TPB + threadIdx.x;
+    const u32 err = ca_n_errors(j, indptr_n, n_samples, indices_n, data_n, nnz_n, n_ecs);
+    if (j < nnz_n && !(err & (CA_ERR_EC | CA_ERR_NEG))) {
+        const int e = indices_n[j], c = data_n[j];
+        if (c > 0 && (sample < 0 || ((long long)j >= indptr_n[sample] && (long long)j < indptr_n[sample + 1])))
             atomicAdd(reinterpret_cast<unsigned long long*>(ww + e), (unsigned long long)c);
     }
     if (err) atomicOr(reinterpret_cast<u32*>(words + 1), err);
@@ -4760,14 +4768,23 @@ __global__ __launch_bounds__(TPB) void k_ca_nonzero(u32* bits, u64 nnz) {
 }
 // row e: CA_POP1 when its masks hold one set bit in all, CA_LEN1 when one of its non-zeros has a mask other than 0 (nz_excl null: no mask
 // is 0, and that is the row's length); excl arrays are exclusive prefix sums with nnz + 1 values
+// (the classifier itself, shared with ecselect: pop = the set bits of row e's masks, nzc = its non-zeros whose mask is not 0; both 0 for an
+//  empty row)
+__device__ __forceinline__ void ca_row_counts(const int* indptr, u64 e, u64 nnz, const u32* bits_excl, const u32* nz_excl, u32& pop, u32& nzc) {
+    pop = nzc = 0;
+    const long long a = indptr[e], b = indptr[e + 1];
+    if (a < 0 || b <= a || (u64)b > nnz) return;
+    pop = bits_excl[b] - bits_excl[a];
+    nzc = nz_excl ? nz_excl[b] - nz_excl[a] : (u32)(b - a);
+}
 __global__ __launch_bounds__(TPB) void k_ca_rows(const int* indptr, u32 n_ecs, u64 nnz, const u32* bits_excl, const u32* nz_excl, u64* ww) {
     const u64 e = blockIdx.x * (u64)TPB + threadIdx.x;
     if (e >= n_ecs) return;
-    const long long a = indptr[e], b = indptr[e + 1];
-    if (a < 0 || b <= a || (u64)b > nnz) return;
+    u32 pop, nzc;
+    ca_row_counts(indptr, e, nnz, bits_excl, nz_excl, pop, nzc);
     u64 f = 0;
-    if (bits_excl[b] - bits_excl[a] == 1u) f |= CA_POP1;
-    if ((nz_excl ? nz_excl[b] - nz_excl[a] : (u32)(b - a)) == 1u) f |= CA_LEN1;
+    if (pop == 1u) f |= CA_POP1;
+    if (nzc == 1u) f |= CA_LEN1;
     if (f) ww[e] |= f;
 }
 // the last row of [lo, hi] whose pointer is at or below i (row pointers never fall: checked before this runs)
@@ -4778,14 +4795,18 @@ __device__ __forceinline__ u32 ca_row_of(const int* indptr, u32 lo, u32 hi, u64 
     }
     return lo;
 }
+// the rows that hold a workgroup's first and last entry (b0, b1), found once per workgroup: every thread of it calls this
+__device__ __forceinline__ void ca_block_rows(const int* indptr, u32 n_rows, u64 b0, u64 b1, u32* s_row) {
+    if (threadIdx.x == 0) s_row[0] = ca_row_of(indptr, 0, n_rows - 1, b0);
+    if (threadIdx.x == 64) s_row[1] = ca_row_of(indptr, 0, n_rows - 1, b1);
+    __syncthreads();
+}
 // thread t: non-zeros [4t, 4t + 4) -> key (window, locus within it, mask) and value (row)
 __global__ __launch_bounds__(TPB) void k_ca_keys(const int* indptr, u32 n_ecs, const int* indices, const int* data, u64 nnz, u32 lgw, u32 n_haps,
                                                  u64* keys, u32* rows) {
     __shared__ u32 s_row[2];
     const u64 b0 = blockIdx.x * (u64)(TPB * CA_KEY_ITEMS), b1 = std::min<u64>(nnz, b0 + TPB * CA_KEY_ITEMS) - 1;
-    if (threadIdx.x == 0) s_row[0] = ca_row_of(indptr, 0, n_ecs - 1, b0);
-    if (threadIdx.x == 64) s_row[1] = ca_row_of(indptr, 0, n_ecs - 1, b1);
-    __syncthreads();
+    ca_block_rows(indptr, n_ecs, b0, b1, s_row);
     const u64 i0 = b0 + (u64)threadIdx.x * CA_KEY_ITEMS;
     if (i0 >= nnz) return;
     const u32 hi = s_row[1];
@@ -4849,13 +4870,27 @@ const ErrBit CA_ERRS[] = {
     {CA_ERR_EC, ECB_ERR_CONTRACT, "malformed N: an EC index at or beyond n_ecs"},
     {CA_ERR_NEG, ECB_ERR_CONTRACT, "malformed N: a negative count"},
 };
-// what both entry points refuse before anything is allocated
-int ca_check_args(uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, uint64_t nnz_a, const void* indptr_a, const void* indices_a, const void* data_a,
-                  uint32_t n_samples, uint64_t nnz_n, const void* indptr_n, const void* indices_n, const void* data_n, int64_t sample) {
+// the pointers and sizes of A and N that count-alignments and ecselect refuse before anything is allocated
+int ca_check_matrices(uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, uint64_t nnz_a, const void* indptr_a, const void* indices_a, const void* data_a,
+                      uint32_t n_samples, uint64_t nnz_n, const void* indptr_n, const void* indices_n, const void* data_n) {
     if (!indptr_a || !indptr_n || !n_loci || !n_haps || n_haps > 31 || !n_samples) return fail(nullptr, ECB_ERR_ARG, "bad argument");
     if ((nnz_a && (!indices_a || !data_a)) || (nnz_n && (!indices_n || !data_n))) return fail(nullptr, ECB_ERR_ARG, "bad argument");
     if (n_ecs >= (1u << 31) - 1u || nnz_n >= (1ull << 31) || n_samples >= (1u << 31) - 1u)
         return fail(nullptr, ECB_ERR_LIMIT, "the matrices exceed the .bin format's int32 limits");
+    return ECB_OK;
+}
+// the status words of k_gm_check<true> and of the check of N, read back: the refusal of a malformed A or N (the error bits of A in word 0
+// have been refused by read_back), or ECB_OK
+int ca_refuse_input(const std::vector<u64>& back) {
+    u64 balance = 0;
+    for (u32 k = 1; k <= GM_SHARDS; ++k) balance += back[GM_SHARD_WORDS * k];
+    if (balance != 0) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSR: columns not strictly ascending within a row (unsorted or duplicate)");
+    return refuse_bits(nullptr, CA_ERRS, (u32)back[1]);
+}
+// what both entry points refuse before anything is allocated
+int ca_check_args(uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, uint64_t nnz_a, const void* indptr_a, const void* indices_a, const void* data_a,
+                  uint32_t n_samples, uint64_t nnz_n, const void* indptr_n, const void* indices_n, const void* data_n, int64_t sample) {
+    RCCHK(ca_check_matrices(n_ecs, n_loci, n_haps, nnz_a, indptr_a, indices_a, data_a, n_samples, nnz_n, indptr_n, indices_n, data_n));
     if (nnz_a >= (1ull << 30)) return fail(nullptr, ECB_ERR_LIMIT, "count-alignments: 2^30 non-zeros or more");       // (radix_sort_pairs64)
     if (sample < -1 || sample >= (int64_t)n_samples) return fail(nullptr, ECB_ERR_CONTRACT, "count-alignments: no such sample (%lld of %u)", (long long)sample, n_samples);
     return ECB_OK;
@@ -4885,10 +4920,7 @@ extern "C" int ecb_count_alignments_device(int device, uint32_t n_ecs, uint32_t 
     CALLCHK(c, scan_launch(st, bits, nnz, bits_excl, sums, words + 3, 1, bits_excl + nnz));
     std::vector<u64> back(n_words);
     if (const int rc = c.read_back(back.data(), words, n_words, GM_ERRS)) return rc;
-    u64 balance = 0;
-    for (u32 k = 1; k <= GM_SHARDS; ++k) balance += back[GM_SHARD_WORDS * k];
-    if (balance != 0) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSR: columns not strictly ascending within a row (unsorted or duplicate)");
-    if (const int rc = refuse_bits(nullptr, CA_ERRS, (u32)back[1])) return rc;
+    RCCHK(ca_refuse_input(back));
     if (back[3] >= (1ull << 32)) return fail(nullptr, ECB_ERR_LIMIT, "more than 2^32-1 set haplotype bits");
     // the input is well formed: from here on the outputs are written
     u32* nz_excl = nullptr;
@@ -4940,6 +4972,303 @@ extern "C" int ecb_count_alignments(int device, uint32_t n_ecs, uint32_t n_loci,
                                                        sample, oa.p, ou.p, ol.p);
     RCCHK(rc);
     return stage_out(c, {{aln, &oa, aln ? plane : 0}, {uniq, &ou, uniq ? plane : 0}, {locus_uniq, &ol, locus_uniq ? (u64)n_loci * 8 : 0}});
+}
+
+// ---- ecselect: the reads of one class and the samples that still count enough of them, pulled out of a .bin (ecb_select / ecb_select_device)
+// (AlignmentPropertyMatrix.get_unique_reads / pull_alignments_from, AlignmentPropertyMatrix.py:386-427, and the cell threshold of
+//  bam2ec --multisample, bam_utils_multisample.py:596-636.)  Linear passes only, no loop over a row or a column: the row flags come from
+// count-alignments' classifier (prefix sums of popcounts over the non-zeros), a pass over N adds up the per-sample totals (a wave whose
+// entries all lie in one column sends one int64 add), a second pass over N marks the entries that stay and, with plain stores, the rows they
+// keep alive; four scans give the new row numbers, the new row pointers of A, the new places of N's entries and the new sample numbers;
+// two gathers copy.  Nothing is written to the caller's arrays before the input has been found well formed.
+// Steps: k_sel_ncheck | k_gm_check<true> | [a class: k_scan_lb] || read back || [a class: (k_ca_nonzero, k_scan_lb), k_sel_rows] |
+// [a threshold: k_sel_totals] | k_sel_samples | k_scan_lb | k_sel_nkeep | k_scan_lb x 2 | k_sel_alen | k_scan_lb | k_sel_ptrs |
+// k_sel_gather_a | k_sel_gather_n || read back the sizes.
+namespace {
+constexpr u32 SEL_TPB = 256, SEL_ITEMS = 4;          // threads of the passes over the entries of A and N, and entries per thread (16-byte loads)
+enum : int { SEL_ALL = 0, SEL_UNIQUE = 1, SEL_LOCUS_UNIQUE = 2, SEL_MULTI = 3 };
+// thread j: column pointer j and entry j of N checked (ecb_count_alignments' contract)
+__global__ __launch_bounds__(TPB) void k_sel_ncheck(const int* indptr_n, u32 n_samples, const int* indices_n, const int* data_n, u64 nnz_n, u32 n_ecs,
+                                                    u64* words) {
+    const u64 j = blockIdx.x * (u64)TPB + threadIdx.x;
+    const u32 err = ca_n_errors(j, indptr_n, n_samples, indices_n, data_n, nnz_n, n_ecs);
+    if (err) atomicOr(reinterpret_cast<u32*>(words + 1), err);
+}
+// in_class[e] = 1 when row e is of the class asked for (SEL_ALL has no such array)
+__global__ __launch_bounds__(TPB) void k_sel_rows(const int* indptr, u32 n_ecs, u64 nnz, const u32* bits_excl, const u32* nz_excl, int row_class,
+                                                  u32* in_class) {
+    const u64 e = blockIdx.x * (u64)TPB + threadIdx.x;
+    if (e >= n_ecs) return;
+    u32 pop, nzc;
+    ca_row_counts(indptr, e, nnz, bits_excl, nz_excl, pop, nzc);
+    in_class[e] = row_class == SEL_UNIQUE ? pop == 1u : row_class == SEL_LOCUS_UNIQUE ? nzc == 1u : nzc >= 2u;
+}
+// four consecutive entries of a CSR's or CSC's index and value arrays, by 16-byte loads where they are whole and aligned
+__device__ __forceinline__ void sel_load4(const int* ix, const int* dx, u64 i0, u64 n, int* x, int* d) {
+    if (i0 + SEL_ITEMS <= n && ((reinterpret_cast<uintptr_t>(ix) | reinterpret_cast<uintptr_t>(dx)) & 15u) == 0u) {
+        const int4 q = reinterpret_cast<const int4*>(ix + i0)[0], r = reinterpret_cast<const int4*>(dx + i0)[0];
+        x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w; d[0] = r.x; d[1] = r.y; d[2] = r.z; d[3] = r.w;
+    } else {
+#pragma unroll
+        for (u32 j = 0; j < SEL_ITEMS; ++j) { x[j] = i0 + j < n ? ix[i0 + j] : 0; d[j] = i0 + j < n ? dx[i0 + j] : 0; }
+    }
+}
+static_assert(SEL_ITEMS == 4, "sel_load4");
+// thread t: entries [4t, 4t + 4) of N; totals[s] += the counts of column s over the rows in class.  A thread adds up within a column; a wave
+// whose lanes all ended in one column (a column of 20 000 entries holds ~80 such waves) sends one add, other lanes their own.
+__global__ __launch_bounds__(SEL_TPB) void k_sel_totals(const int* indptr_n, u32 n_samples, const int* indices_n, const int* data_n, u64 nnz_n,
+                                                        const u32* in_class, u64* totals) {
+    __shared__ u32 s_col[2];
+    const u64 b0 = blockIdx.x * (u64)(SEL_TPB * SEL_ITEMS), b1 = std::min<u64>(nnz_n, b0 + SEL_TPB * SEL_ITEMS) - 1;
+    ca_block_rows(indptr_n, n_samples, b0, b1, s_col);
+    const u64 i0 = b0 + (u64)threadIdx.x * SEL_ITEMS;
+    const u32 hi = s_col[1];
+    u32 col = hi;                                    // (a thread beyond the end: nothing to add, to the last column)
+    u64 acc = 0;
+    if (i0 < nnz_n) {
+        int e[SEL_ITEMS], c[SEL_ITEMS];
+        sel_load4(indices_n, data_n, i0, nnz_n, e, c);
+        col = ca_row_of(indptr_n, s_col[0], hi, i0);
+#pragma unroll
+        for (u32 j = 0; j < SEL_ITEMS; ++j) {
+            const u64 i = i0 + j;
+            if (i >= nnz_n) break;
+            if (col < hi && (u64)(u32)indptr_n[col + 1] <= i) {
+                if (acc) atomicAdd(reinterpret_cast<unsigned long long*>(totals + col), (unsigned long long)acc);
+                acc = 0;
+                col = ca_row_of(indptr_n, col + 1, hi, i);
+            }
+            if (c[j] > 0 && (!in_class || in_class[e[j]])) acc += (u64)c[j];
+        }
+    }
+    const u32 first = (u32)__builtin_amdgcn_readfirstlane((int)col);
+    if (__all(col == first)) {
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d);
+        if ((threadIdx.x & 63u) == 0u && acc) atomicAdd(reinterpret_cast<unsigned long long*>(totals + first), (unsigned long long)acc);
+    } else if (acc) atomicAdd(reinterpret_cast<unsigned long long*>(totals + col), (unsigned long long)acc);
+}
+// sample s stays when it is named (named null: all are) and, with a threshold (totals not null), its total reaches it
+__global__ __launch_bounds__(TPB) void k_sel_samples(u32 n_samples, const unsigned char* named, const u64* totals, u64 least, u32* skeep,
+                                                     unsigned char* out_keep) {
+    const u64 s = blockIdx.x * (u64)TPB + threadIdx.x;
+    if (s >= n_samples) return;
+    const bool k = (!named || named[s]) && (!totals || totals[s] >= least);
+    skeep[s] = k;
+    out_keep[s] = k;
+}
+// thread t: entries [4t, 4t + 4) of N; nkeep[j] = 1 when entry j stays (its row in class, its sample staying, its count above 0), and the row
+// of such an entry is marked -- many entries write the same 1: plain stores
+__global__ __launch_bounds__(SEL_TPB) void k_sel_nkeep(const int* indptr_n, u32 n_samples, const int* indices_n, const int* data_n, u64 nnz_n,
+                                                       const u32* in_class, const u32* skeep, u32* nkeep, u32* row_kept) {
+    __shared__ u32 s_col[2];
+    const u64 b0 = blockIdx.x * (u64)(SEL_TPB * SEL_ITEMS), b1 = std::min<u64>(nnz_n, b0 + SEL_TPB * SEL_ITEMS) - 1;
+    ca_block_rows(indptr_n, n_samples, b0, b1, s_col);
+    const u64 i0 = b0 + (u64)threadIdx.x * SEL_ITEMS;
+    if (i0 >= nnz_n) return;
+    const u32 hi = s_col[1];
+    int e[SEL_ITEMS], c[SEL_ITEMS];
+    u32 k[SEL_ITEMS];
+    sel_load4(indices_n, data_n, i0, nnz_n, e, c);
+    u32 col = ca_row_of(indptr_n, s_col[0], hi, i0), stays = skeep[col];
+#pragma unroll
+    for (u32 j = 0; j < SEL_ITEMS; ++j) {
+        const u64 i = i0 + j;
+        k[j] = 0u;
+        if (i >= nnz_n) continue;
+        if (col < hi && (u64)(u32)indptr_n[col + 1] <= i) { col = ca_row_of(indptr_n, col + 1, hi, i); stays = skeep[col]; }
+        if (stays && c[j] > 0 && (!in_class || in_class[e[j]])) { k[j] = 1u; row_kept[e[j]] = 1u; }
+    }
+    if (i0 + SEL_ITEMS <= nnz_n) reinterpret_cast<uint4*>(nkeep + i0)[0] = make_uint4(k[0], k[1], k[2], k[3]);
+    else {
+#pragma unroll
+        for (u32 j = 0; j < SEL_ITEMS; ++j) if (i0 + j < nnz_n) nkeep[i0 + j] = k[j];
+    }
+}
+// alen[e] = the length of row e when it stays, else 0: its scan is the new row pointers
+__global__ __launch_bounds__(TPB) void k_sel_alen(const int* indptr, u32 n_ecs, const u32* row_kept, u32* alen) {
+    const u64 e = blockIdx.x * (u64)TPB + threadIdx.x;
+    if (e < n_ecs) alen[e] = row_kept[e] ? (u32)(indptr[e + 1] - indptr[e]) : 0u;
+}
+// thread t: the new row pointer of row t when it stays (and the last one, t = E); the new column pointer of sample t when it stays (and the
+// last one, t = S) -- the place the scan over N's entries gives the first entry of its old column
+__global__ __launch_bounds__(TPB) void k_sel_ptrs(u32 n_ecs, const u32* row_kept, const u32* newrow, const u32* apos, const int* indptr_n, u32 n_samples,
+                                                  const u32* skeep, const u32* spos, const u32* npos, int* out_indptr_a, int* out_indptr_n) {
+    const u64 t = blockIdx.x * (u64)TPB + threadIdx.x;
+    if (t <= n_ecs && (t == n_ecs || row_kept[t])) out_indptr_a[newrow[t]] = (int)apos[t];
+    if (t <= n_samples && (t == n_samples || skeep[t])) out_indptr_n[spos[t]] = (int)npos[indptr_n[t]];
+}
+// thread t: non-zeros [4t, 4t + 4) of A, read whole (16-byte loads however long the row), those of rows that stay written to their row's new
+// place; four of one row that land on a 16-byte boundary go out as one store each
+__global__ __launch_bounds__(SEL_TPB) void k_sel_gather_a(const int* indptr, u32 n_ecs, const int* indices, const int* data, u64 nnz, const u32* row_kept,
+                                                         const u32* apos, int* out_indices, int* out_data) {
+    __shared__ u32 s_row[2];
+    const u64 b0 = blockIdx.x * (u64)(SEL_TPB * SEL_ITEMS), b1 = std::min<u64>(nnz, b0 + SEL_TPB * SEL_ITEMS) - 1;
+    ca_block_rows(indptr, n_ecs, b0, b1, s_row);
+    const u64 i0 = b0 + (u64)threadIdx.x * SEL_ITEMS;
+    if (i0 >= nnz) return;
+    const u32 hi = s_row[1];
+    u32 r = ca_row_of(indptr, s_row[0], hi, i0);
+    const bool whole = i0 + SEL_ITEMS <= nnz;
+    const bool one = r == hi || (u64)(u32)indptr[r + 1] >= std::min<u64>(i0 + SEL_ITEMS, nnz);      // all of them in row r
+    if (one && !row_kept[r]) return;
+    int x[SEL_ITEMS], d[SEL_ITEMS];
+    sel_load4(indices, data, i0, nnz, x, d);
+    if (one && whole) {
+        const u64 dst = (u64)apos[r] + (i0 - (u64)(u32)indptr[r]);
+        if ((dst & 3u) == 0u && ((reinterpret_cast<uintptr_t>(out_indices) | reinterpret_cast<uintptr_t>(out_data)) & 15u) == 0u) {
+            reinterpret_cast<int4*>(out_indices + dst)[0] = make_int4(x[0], x[1], x[2], x[3]);
+            reinterpret_cast<int4*>(out_data + dst)[0] = make_int4(d[0], d[1], d[2], d[3]);
+            return;
+        }
+    }
+#pragma unroll
+    for (u32 j = 0; j < SEL_ITEMS; ++j) {
+        const u64 i = i0 + j;
+        if (i >= nnz) break;
+        if (r < hi && (u64)(u32)indptr[r + 1] <= i) r = ca_row_of(indptr, r + 1, hi, i);
+        if (!row_kept[r]) continue;
+        const u64 dst = (u64)apos[r] + (i - (u64)(u32)indptr[r]);
+        out_indices[dst] = x[j];
+        out_data[dst] = d[j];
+    }
+}
+// thread t: entries [4t, 4t + 4) of N: one that stays goes to its new place with its row's new number (npos: nnz_n + 1 values)
+__global__ __launch_bounds__(SEL_TPB) void k_sel_gather_n(const int* indices_n, const int* data_n, u64 nnz_n, const u32* npos, const u32* newrow,
+                                                         int* out_indices_n, int* out_data_n) {
+    const u64 i0 = (blockIdx.x * (u64)SEL_TPB + threadIdx.x) * SEL_ITEMS;
+    if (i0 >= nnz_n) return;
+    int e[SEL_ITEMS], c[SEL_ITEMS];
+    sel_load4(indices_n, data_n, i0, nnz_n, e, c);
+    u32 p = npos[i0];
+#pragma unroll
+    for (u32 j = 0; j < SEL_ITEMS; ++j) {
+        if (i0 + j >= nnz_n) break;
+        const u32 q = npos[i0 + j + 1];
+        if (q != p) { out_indices_n[p] = (int)newrow[e[j]]; out_data_n[p] = c[j]; }
+        p = q;
+    }
+}
+int sel_check_args(uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, uint32_t n_samples, uint64_t nnz_a, const void* indptr_a, const void* indices_a,
+                   const void* data_a, uint64_t nnz_n, const void* indptr_n, const void* indices_n, const void* data_n, int32_t row_class,
+                   const void* out_indptr_a, const void* out_indices_a, const void* out_data_a, const void* out_indptr_n, const void* out_indices_n,
+                   const void* out_data_n, const void* out_sample_keep, const uint64_t* out_sizes) {
+    RCCHK(ca_check_matrices(n_ecs, n_loci, n_haps, nnz_a, indptr_a, indices_a, data_a, n_samples, nnz_n, indptr_n, indices_n, data_n));
+    if (!out_indptr_a || !out_indptr_n || !out_sample_keep || !out_sizes || (nnz_a && (!out_indices_a || !out_data_a)) ||
+        (nnz_n && (!out_indices_n || !out_data_n)))
+        return fail(nullptr, ECB_ERR_ARG, "bad argument");
+    if (row_class < SEL_ALL || row_class > SEL_MULTI) return fail(nullptr, ECB_ERR_ARG, "select: no such row class (%d)", (int)row_class);
+    if (nnz_a >= (1ull << 31)) return fail(nullptr, ECB_ERR_LIMIT, "the matrices exceed the .bin format's int32 limits");
+    return ECB_OK;
+}
+}  // namespace
+
+extern "C" int ecb_select_device(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, uint32_t n_samples, uint64_t nnz_a, const void* d_indptr_a,
+                                 const void* d_indices_a, const void* d_data_a, uint64_t nnz_n, const void* d_indptr_n, const void* d_indices_n,
+                                 const void* d_data_n, int32_t row_class, const void* d_sample_keep, int64_t min_count, void* d_out_indptr_a,
+                                 void* d_out_indices_a, void* d_out_data_a, void* d_out_indptr_n, void* d_out_indices_n, void* d_out_data_n,
+                                 void* d_out_sample_keep, uint64_t* out_sizes) {
+    RCCHK(sel_check_args(n_ecs, n_loci, n_haps, n_samples, nnz_a, d_indptr_a, d_indices_a, d_data_a, nnz_n, d_indptr_n, d_indices_n, d_data_n, row_class,
+                         d_out_indptr_a, d_out_indices_a, d_out_data_a, d_out_indptr_n, d_out_indices_n, d_out_data_n, d_out_sample_keep, out_sizes));
+    const u64 E = n_ecs, S = n_samples;
+    const void* ins[7] = {d_indptr_a, d_indices_a, d_data_a, d_indptr_n, d_indices_n, d_data_n, d_sample_keep};
+    const u64 inb[7] = {(E + 1) * 4, nnz_a * 4, nnz_a * 4, (S + 1) * 4, nnz_n * 4, nnz_n * 4, d_sample_keep ? S : 0};
+    void* outs[7] = {d_out_indptr_a, d_out_indices_a, d_out_data_a, d_out_indptr_n, d_out_indices_n, d_out_data_n, d_out_sample_keep};
+    const u64 outb[7] = {(E + 1) * 4, nnz_a * 4, nnz_a * 4, (S + 1) * 4, nnz_n * 4, nnz_n * 4, S};
+    for (int o = 0; o < 7; ++o) {
+        for (int i = 0; i < 7; ++i)
+            if (gm_overlap(outs[o], outb[o], ins[i], inb[i])) return fail(nullptr, ECB_ERR_ARG, "an output overlaps an input");
+        for (int p = 0; p < o; ++p)
+            if (gm_overlap(outs[o], outb[o], outs[p], outb[p])) return fail(nullptr, ECB_ERR_ARG, "the outputs overlap");
+    }
+    Call c(device, "select: "); if (c.rc) return c.rc;
+    hipStream_t st = c.st;
+    const bool classed = row_class != SEL_ALL, threshold = min_count >= 0;
+    // apply-mask's words: [0] the error bits of A, [1] of N, [2] [3] the totals of the classifier's scans, [4 .. 8) the sizes of the result
+    const u64 n_words = GM_SHARD_WORDS * (1 + GM_SHARDS);
+    u64* words = c.get<u64>(n_words);
+    u32* bits = c.get<u32>(nnz_a);
+    u32 *bits_excl = classed ? c.get<u32>(nnz_a + 1) : nullptr, *in_class = classed ? c.get<u32>(E) : nullptr;
+    u64* totals = threshold ? c.get<u64>(S) : nullptr;
+    u32 *skeep = c.get<u32>(S), *spos = c.get<u32>(S + 1), *nkeep = c.get<u32>(nnz_n), *npos = c.get<u32>(nnz_n + 1);
+    u32 *row_kept = c.get<u32>(E), *newrow = c.get<u32>(E + 1), *alen = c.get<u32>(E), *apos = c.get<u32>(E + 1);
+    u32* sums = c.get<u32>(scan_words(std::max<u64>(std::max<u64>(nnz_a, nnz_n), std::max<u64>(E, S))));
+    if (const int rc = c.missing()) return rc;
+    const int *ipa = (const int*)d_indptr_a, *ixa = (const int*)d_indices_a, *daa = (const int*)d_data_a;
+    const int *ipn = (const int*)d_indptr_n, *ixn = (const int*)d_indices_n, *dan = (const int*)d_data_n;
+    CALLCHK(c, hipMemsetAsync(words, 0, n_words * 8, st));
+    k_sel_ncheck<<<nblk(std::max<u64>(nnz_n, S + 1), TPB), TPB, 0, st>>>(ipn, n_samples, ixn, dan, nnz_n, n_ecs, words);
+    k_gm_check<true><<<nblk(std::max<u64>(E + 1, (nnz_a + GM_ITEMS - 1) / GM_ITEMS), TPB), TPB, 0, st>>>(ipa, n_ecs, ixa, daa, nnz_a, nullptr, n_loci, n_haps,
+                                                                                                       bits, words);
+    CALLCHK(c, hipGetLastError());
+    if (classed) CALLCHK(c, scan_launch(st, bits, nnz_a, bits_excl, sums, words + 3, 1, bits_excl + nnz_a));
+    std::vector<u64> back(n_words);
+    if (const int rc = c.read_back(back.data(), words, n_words, GM_ERRS)) return rc;
+    RCCHK(ca_refuse_input(back));
+    if (classed && back[3] >= (1ull << 32)) return fail(nullptr, ECB_ERR_LIMIT, "more than 2^32-1 set haplotype bits");
+    // the input is well formed: from here on the outputs are written
+    if (classed) {
+        u32* nz_excl = nullptr;
+        if ((u32)back[0] & GM_SAW_ZERO) {
+            nz_excl = c.get<u32>(nnz_a + 1);
+            if (const int rc = c.missing()) return rc;
+            k_ca_nonzero<<<nblk(nnz_a, TPB), TPB, 0, st>>>(bits, nnz_a);      // (a stored 0 was seen: nnz_a > 0)
+            CALLCHK(c, scan_launch(st, bits, nnz_a, nz_excl, sums, words + 2, 1, nz_excl + nnz_a));
+        }
+        if (E) k_sel_rows<<<nblk(E, TPB), TPB, 0, st>>>(ipa, n_ecs, nnz_a, bits_excl, nz_excl, row_class, in_class);
+    }
+    const unsigned n_blocks = nblk(nnz_n, SEL_TPB * SEL_ITEMS);
+    if (threshold) {
+        CALLCHK(c, hipMemsetAsync(totals, 0, S * 8, st));
+        if (nnz_n) k_sel_totals<<<n_blocks, SEL_TPB, 0, st>>>(ipn, n_samples, ixn, dan, nnz_n, in_class, totals);
+    }
+    k_sel_samples<<<nblk(S, TPB), TPB, 0, st>>>(n_samples, (const unsigned char*)d_sample_keep, totals, (u64)std::max<int64_t>(min_count, 1), skeep,
+                                               (unsigned char*)d_out_sample_keep);
+    CALLCHK(c, hipGetLastError());
+    CALLCHK(c, scan_launch(st, skeep, S, spos, sums, words + 6, 1, spos + S));
+    CALLCHK(c, hipMemsetAsync(row_kept, 0, std::max<u64>(E, 1) * 4, st));
+    if (nnz_n) k_sel_nkeep<<<n_blocks, SEL_TPB, 0, st>>>(ipn, n_samples, ixn, dan, nnz_n, in_class, skeep, nkeep, row_kept);
+    CALLCHK(c, scan_launch(st, nkeep, nnz_n, npos, sums, words + 7, 1, npos + nnz_n));
+    CALLCHK(c, scan_launch(st, row_kept, E, newrow, sums, words + 4, 1, newrow + E));
+    if (E) k_sel_alen<<<nblk(E, TPB), TPB, 0, st>>>(ipa, n_ecs, row_kept, alen);
+    CALLCHK(c, scan_launch(st, alen, E, apos, sums, words + 5, 1, apos + E));
+    k_sel_ptrs<<<nblk(std::max<u64>(E, S) + 1, TPB), TPB, 0, st>>>(n_ecs, row_kept, newrow, apos, ipn, n_samples, skeep, spos, npos, (int*)d_out_indptr_a,
+                                                             (int*)d_out_indptr_n);
+    if (nnz_a) k_sel_gather_a<<<nblk(nnz_a, SEL_TPB * SEL_ITEMS), SEL_TPB, 0, st>>>(ipa, n_ecs, ixa, daa, nnz_a, row_kept, apos, (int*)d_out_indices_a,
+                                                                                   (int*)d_out_data_a);
+    if (nnz_n) k_sel_gather_n<<<n_blocks, SEL_TPB, 0, st>>>(ixn, dan, nnz_n, npos, newrow, (int*)d_out_indices_n, (int*)d_out_data_n);
+    CALLCHK(c, hipGetLastError());
+    u64 sizes[4];
+    if (const int rc = c.read_back(sizes, words + 4, 4)) return rc;
+    for (int k = 0; k < 4; ++k) out_sizes[k] = sizes[k];
+    return ECB_OK;
+}
+
+extern "C" int ecb_select(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, uint32_t n_samples, uint64_t nnz_a, const int32_t* indptr_a,
+                          const int32_t* indices_a, const int32_t* data_a, uint64_t nnz_n, const int32_t* indptr_n, const int32_t* indices_n,
+                          const int32_t* data_n, int32_t row_class, const uint8_t* sample_keep, int64_t min_count, int32_t* out_indptr_a,
+                          int32_t* out_indices_a, int32_t* out_data_a, int32_t* out_indptr_n, int32_t* out_indices_n, int32_t* out_data_n,
+                          uint8_t* out_sample_keep, uint64_t* out_sizes) {
+    RCCHK(sel_check_args(n_ecs, n_loci, n_haps, n_samples, nnz_a, indptr_a, indices_a, data_a, nnz_n, indptr_n, indices_n, data_n, row_class,
+                         out_indptr_a, out_indices_a, out_data_a, out_indptr_n, out_indices_n, out_data_n, out_sample_keep, out_sizes));
+    Call c(device, "select: "); if (c.rc) return c.rc;
+    const u64 rowb = ((u64)n_ecs + 1) * 4, colb = ((u64)n_samples + 1) * 4;
+    DevBuf<> ipa, ixa, daa, ipn, ixn, dan, sk, oia, oxa, oda, oin, oxn, odn, osk;
+    std::vector<StageIn> in = {{&ipa, indptr_a, rowb}, {&ixa, indices_a, nnz_a * 4}, {&daa, data_a, nnz_a * 4}, {&ipn, indptr_n, colb},
+                               {&ixn, indices_n, nnz_n * 4}, {&dan, data_n, nnz_n * 4}, {&oia, nullptr, rowb}, {&oxa, nullptr, nnz_a * 4},
+                               {&oda, nullptr, nnz_a * 4}, {&oin, nullptr, colb}, {&oxn, nullptr, nnz_n * 4}, {&odn, nullptr, nnz_n * 4},
+                               {&osk, nullptr, n_samples}};
+    if (sample_keep) in.push_back({&sk, sample_keep, n_samples});
+    int rc = stage_in(c, in);
+    uint64_t sizes[4] = {0, 0, 0, 0};
+    if (rc == ECB_OK) rc = ecb_select_device(device, n_ecs, n_loci, n_haps, n_samples, nnz_a, ipa.p, ixa.p, daa.p, nnz_n, ipn.p, ixn.p, dan.p, row_class,
+                                             sample_keep ? sk.p : nullptr, min_count, oia.p, oxa.p, oda.p, oin.p, oxn.p, odn.p, osk.p, sizes);
+    RCCHK(rc);
+    RCCHK(stage_out(c, {{out_indptr_a, &oia, (sizes[0] + 1) * 4}, {out_indices_a, &oxa, sizes[1] * 4}, {out_data_a, &oda, sizes[1] * 4},
+                        {out_indptr_n, &oin, (sizes[2] + 1) * 4}, {out_indices_n, &oxn, sizes[3] * 4}, {out_data_n, &odn, sizes[3] * 4},
+                        {out_sample_keep, &osk, n_samples}}));
+    for (int k = 0; k < 4; ++k) out_sizes[k] = sizes[k];
+    return ECB_OK;
 }
 
 // ---- ecmerge: several .bin files' A and N combined into one (ecb_combine / ecb_combine_device) ---------------------------------------------

@@ -42,6 +42,10 @@ SYMBOLS = ("ecb_abi_version", "ecb_device_count", "ecb_create", "ecb_destroy", "
 COUNT_SYMBOLS = ("ecb_count_alignments_device", "ecb_count_alignments")
 #: every symbol include/ecb_bundle.h declares (ecb.h includes it)
 BUNDLE_SYMBOLS = ("ecb_bundle_device", "ecb_bundle")
+#: every symbol include/ecb_select.h declares (ecb.h includes it)
+SELECT_SYMBOLS = ("ecb_select_device", "ecb_select")
+#: ``ecb_select``'s row classes (include/ecb_select.h)
+ROW_CLASSES = {None: 0, "all": 0, "unique": 1, "locus-unique": 2, "multi": 3}
 ABI_VERSION = 4            # include/ecb.h: ECB_ABI_VERSION
 
 
@@ -176,6 +180,9 @@ def load():
     if not ab or hasattr(lib, "ecb_bundle"):
         for f in (lib.ecb_bundle_device, lib.ecb_bundle):
             f.argtypes = [C.c_int] + [C.c_uint32] * 5 + [u64, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, u64] + [vp] * 6 + [C.POINTER(u64)]
+    if not ab or hasattr(lib, "ecb_select"):
+        for f in (lib.ecb_select_device, lib.ecb_select):
+            f.argtypes = [C.c_int] + [C.c_uint32] * 4 + [u64, vp, vp, vp, u64, vp, vp, vp, C.c_int32, vp, C.c_int64] + [vp] * 7 + [C.POINTER(u64)]
     lib.ecb_csr_to_hapcsc_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.POINTER(u64)]
     lib.ecb_hapcsc_to_csr_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, u64, vp, vp, vp, C.POINTER(u64)]
     _lib = lib
@@ -440,6 +447,54 @@ def bundle(indptrA, indicesA, dataA, indptrN, indicesN, dataN, n_loci, n_haps, n
                       len(mi), ptr(mp), ptr(mi), cap, *([ptr(o) for o in out] + [sizes])))
     E2, nnz_a, nnz_n2 = (int(x) for x in sizes)
     return out[0][:E2 + 1], out[1][:nnz_a], out[2][:nnz_a], out[3], out[4][:nnz_n2], out[5][:nnz_n2]
+
+
+def select(indptrA, indicesA, dataA, indptrN, indicesN, dataN, n_loci, n_haps, row_class=None, sample_keep=None, min_count=None, device=0):
+    """ecselect on the GPU: the reads of one class and the samples that still count enough of them, pulled out of one ``.bin``'s CSR A and
+    CSC N (``ecb_select``).  ``row_class``: None or ``"all"`` (every row), ``"unique"`` (one set bit in the whole row), ``"locus-unique"`` (one
+    non-zero with a mask other than 0) or ``"multi"`` (two or more), or its number 0 .. 3.  ``sample_keep``: per sample whether it is named
+    (None: all are).  ``min_count``: None, or the threshold a named sample's total over the rows in class must reach (``max(min_count, 1)``,
+    the reference's rule).  Entries of N stay when their row is in class, their sample stays and their count is above 0; rows stay when an
+    entry of theirs does, in order, renumbered from 0.  numpy arrays go through ``ecb_select`` (host arrays, no PyTorch), CUDA tensors
+    through ``ecb_select_device`` (``device`` is then the tensors' own).  Returns ``((indptrA, indicesA, dataA, indptrN, indicesN, dataN),
+    kept)``: int32 arrays of the same kind as the input, and a bool array, per sample of the input whether it stayed.  A result without a
+    sample or without a row is returned as it is.  Malformed input raises :class:`EcbError` (``ECB_ERR_CONTRACT``)."""
+    lib = load()
+    rc = ROW_CLASSES[row_class] if row_class is None or isinstance(row_class, str) else int(row_class)
+    mc = -1 if min_count is None else max(int(min_count), 0)
+    ins = (indptrA, indicesA, dataA, indptrN, indicesN, dataN)
+    on_device = hasattr(indptrA, "data_ptr")
+    if on_device:
+        import torch
+        dev = indptrA.device
+        a = [torch.as_tensor(x).to(device=dev, dtype=torch.int32).contiguous() for x in ins]
+        sk = None if sample_keep is None else (torch.as_tensor(sample_keep).to(device=dev) != 0).to(torch.uint8).contiguous()
+        ptr, entry, device = _dev_ptr, lib.ecb_select_device, dev.index or 0
+
+        def empty(n, dt=torch.int32):
+            return torch.empty(max(n, 1), dtype=dt, device=dev)
+        u8 = torch.uint8
+    else:
+        a = [np.ascontiguousarray(x, dtype=np.int32) for x in ins]
+        sk = None if sample_keep is None else np.ascontiguousarray(np.asarray(sample_keep) != 0, dtype=np.uint8)
+        ptr, entry = _ptr, lib.ecb_select
+
+        def empty(n, dt=np.int32):
+            return np.empty(max(n, 1), dtype=dt)
+        u8 = np.uint8
+    ipa, ixa, daa, ipn, ixn, dan = a
+    E, S, nnz, nnz_n = len(ipa) - 1, len(ipn) - 1, len(ixa), len(ixn)
+    if len(daa) != nnz or len(dan) != nnz_n:
+        raise ValueError("indices and data differ in length")
+    if sk is not None and len(sk) != S:
+        raise ValueError("sample_keep has %d entries for %d samples" % (len(sk), S))
+    out = [empty(E + 1), empty(nnz), empty(nnz), empty(S + 1), empty(nnz_n), empty(nnz_n)]
+    kept = empty(S, u8)
+    sizes = (C.c_uint64 * 4)()
+    _check(lib, entry(device, E, n_loci, n_haps, S, nnz, ptr(ipa), ptr(ixa), ptr(daa), nnz_n, ptr(ipn), ptr(ixn), ptr(dan), rc, ptr(sk), mc,
+                      *([ptr(o) for o in out] + [ptr(kept), sizes])))
+    E2, nnz_a, S2, nnz_n2 = (int(x) for x in sizes)
+    return (out[0][:E2 + 1], out[1][:nnz_a], out[2][:nnz_a], out[3][:S2 + 1], out[4][:nnz_n2], out[5][:nnz_n2]), kept[:S] != 0
 
 
 ECB_ERR_CONTRACT = -5      # include/ecb.h

@@ -1,5 +1,5 @@
 # -*- coding: utf-8 -*-
-"""Same driver functions as the reference's ``alntools/methods.py:32-53, 205-210``, ``apply_genotypes``, ``ecmerge``, ``ecbundle``, ``salmon2ec``, ``count_alignments`` and ``ecdump`` for the hot path."""
+"""Same driver functions as the reference's ``alntools/methods.py:32-53, 205-210``, ``apply_genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``count_alignments`` and ``ecdump`` for the hot path."""
 from __future__ import annotations
 
 from . import bam_utils, bin_utils
@@ -57,6 +57,10 @@ def ecmerge(input_files, out_file):
 
 def ecbundle(ec_file, grp_file, out_file):
     bin_utils.ecbundle(ec_file, grp_file, out_file)
+
+
+def ecselect(ec_file, out_file, row_class=None, samples=None, samples_file=None, mincount=None):
+    bin_utils.ecselect(ec_file, out_file, row_class=row_class, samples=samples, samples_file=samples_file, mincount=mincount)
 
 
 def count_alignments(ec_file, out_file, sample=None):

@@ -398,5 +398,7 @@ const char* ecb_profile_kernel(const ecb_handle* h);
 #include "ecb_count.h"
 /* ... and so are the ones that collapse a .bin's targets into groups (ecbundle). */
 #  include "ecb_bundle.h"
+/* ... and the ones that pull a class of reads and the samples that still count them out of a .bin (ecselect). */
+#   include "ecb_select.h"
 
 #endif /* ECB_H */
