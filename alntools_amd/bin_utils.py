@@ -376,6 +376,63 @@ def count_alignments(ec_filename, out_filename, sample=None, device=0):
         raise
 
 
+def quant_table(lname, hname, theta):
+    """The text ``ecquant`` writes: a header ``locus, <haplotype names>, total`` and one tab-separated line per target, every number as
+    :func:`counts_table` writes them (``str(float(v))``, which reads back to the same float64)."""
+    theta = np.asarray(theta, dtype=np.float64)
+    out = ["locus\t" + "\t".join(hname) + "\ttotal\n"]
+    for t, name in enumerate(lname):
+        out.append("\t".join([name] + [str(float(v)) for v in theta[:, t]] + [str(float(theta[:, t].sum()))]) + "\n")
+    return "".join(out)
+
+
+def length_scale(m, aln):
+    """``ecquant -l``: ``scale[h, t] = 1 / length[t, h]``.  A (target, haplotype) with alignments (``aln[h, t] > 0``) and a length <= 0 is a
+    ValueError naming it; any other with a length <= 0 gets scale 0."""
+    lens = np.asarray(m.lengths, dtype=np.float64)[:, :m.num_haplotypes].T
+    bad = np.argwhere((lens <= 0) & (np.asarray(aln) > 0))
+    if len(bad):
+        h, t = bad[0]
+        raise ValueError("target {} haplotype {} has alignments and length {:g}: cannot scale by its length".format(m.lname[t], m.hname[h], lens[h, t]))
+    scale = np.zeros_like(lens)
+    np.divide(1.0, lens, out=scale, where=lens > 0)
+    return scale
+
+
+def ecquant(ec_filename, out_filename, sample=None, use_lengths=False, max_iters=1000, tol=1e-6, device=0):
+    """``alntools ecquant``: EM abundance estimates of a ``.bin`` (``ecb.quantify``: the reference's ``multiply`` / ``normalize_reads`` /
+    ``sum`` iterated on the GPU), written as a table of ``locus, <haplotypes>, total`` in read units.  A multisample file is quantified over
+    all its samples pooled, or over the one named ``sample``.  ``use_lengths``: every abundance is weighted by 1 / its target's length
+    (:func:`length_scale`).  A failure is logged as ``Error: ...`` and raised again; no file is written then."""
+    import time
+    from . import ecb, utils
+    LOG = utils.get_logger()
+    try:
+        start_time = time.time()
+        LOG.info("Loading {}...".format(ec_filename))
+        m = ecload(ec_filename)
+        col = None
+        if sample is not None:
+            if sample not in m.sname:
+                raise KeyError("sample {} is not in {}".format(sample, ec_filename))
+            col = m.sname.index(sample)
+        args = (m.indptrA, m.indicesA, m.dataA, m.num_loci, m.num_haplotypes, m.indptrN, m.indicesN, m.dataN)
+        scale = None
+        if use_lengths:
+            aln = ecb.count_alignments(*args, sample=col, device=device)[0]       # (theta_0 is this aln: no need for ecquant's own set-up twice)
+            scale = length_scale(m, aln)
+        LOG.info("Estimating abundances...")
+        theta, info = ecb.quantify(*args, sample=col, scale=scale, max_iters=max_iters, tol=tol, device=device)
+        LOG.info("iterations: {:,}; delta: {!r}; explained reads: {:,}; {}".format(info["n_iter"], info["delta"], info["explained"],
+                                                                                  "converged" if info["converged"] else "not converged"))
+        with open(out_filename, 'w') as fh:
+            fh.write(quant_table(m.lname, m.hname, theta))
+        LOG.info("{} created in total time: {}".format(out_filename, utils.format_time(start_time, time.time())))
+    except Exception as e:
+        LOG.error("Error: {}".format(e.args[0] if isinstance(e, KeyError) and e.args else str(e)))
+        raise
+
+
 def ecdump(ec_filename):
     """``alntools ecdump`` (``bin_utils.py:959-976``): the shapes of a ``.bin``, as the reference's log lines.  Host only."""
     from . import utils

@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
 """Command line with the reference's hot-path sub-commands and options (``alntools/cli.py:43-113``):
-``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``, ``apply-genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``count-alignments``, ``ecdump``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
+``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``, ``apply-genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``count-alignments``, ``ecquant``, ``ecdump``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
 from __future__ import annotations
 
 import glob
@@ -196,6 +196,25 @@ def count_alignments(ec_file, out_file, sample, verbose):
         methods.count_alignments(ec_file, out_file, sample)
     except Exception:
         sys.exit(1)                                                  # (logged as "Error: ..." by bin_utils.count_alignments)
+
+
+@cli.command('ecquant', options_metavar='<options>', short_help='estimate abundances from an EC file by EM')
+@click.argument('ec_file', metavar='ec_file', type=click.Path(exists=True, resolve_path=True, dir_okay=False))
+@click.argument('out_file', metavar='out_file', type=click.Path(resolve_path=True, dir_okay=False, writable=True))
+@click.option('-s', '--sample', metavar='sample', default=None, help="quantify one sample of a multisample file (default: all of them pooled)")
+@click.option('-l', '--use-lengths', is_flag=True, help='weight every abundance by 1 / the length of its target')
+@click.option('-i', '--max-iters', default=1000, type=click.IntRange(min=0), help='EM steps at the most (default: 1000)')
+@click.option('-t', '--tolerance', 'tol', default=1e-6, type=float, help='stop when one step changes less than this share of the reads (default: 1e-6)')
+@click.option('-v', '--verbose', count=True, help='enables verbose mode')
+def ecquant(ec_file, out_file, sample, use_lengths, max_iters, tol, verbose):
+    """
+    Estimate the abundance of every target and haplotype of a binary EC file (ec_file) by EM and write them, in reads, to a table (out_file)
+    """
+    utils.configure_logging(verbose)
+    try:
+        methods.ecquant(ec_file, out_file, sample, use_lengths, max_iters, tol)
+    except Exception:
+        sys.exit(1)                                                  # (logged as "Error: ..." by bin_utils.ecquant)
 
 
 @cli.command('ecdump', options_metavar='<options>', short_help='show the shapes of an EC file')

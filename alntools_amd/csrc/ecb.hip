@@ -4974,6 +4974,9 @@ extern "C" int ecb_count_alignments(int device, uint32_t n_ecs, uint32_t n_loci,
     return stage_out(c, {{aln, &oa, aln ? plane : 0}, {uniq, &ou, uniq ? plane : 0}, {locus_uniq, &ol, locus_uniq ? (u64)n_loci * 8 : 0}});
 }
 
+// ecquant (ecb_quantify / ecb_quantify_device): the EM on count-alignments' checks and weights and the conversion's column order
+#include "quant.inc"
+
 // ---- ecselect: the reads of one class and the samples that still count enough of them, pulled out of a .bin (ecb_select / ecb_select_device)
 // (AlignmentPropertyMatrix.get_unique_reads / pull_alignments_from, AlignmentPropertyMatrix.py:386-427, and the cell threshold of
 //  bam2ec --multisample, bam_utils_multisample.py:596-636.)  Linear passes only, no loop over a row or a column: the row flags come from

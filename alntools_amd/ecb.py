@@ -44,6 +44,8 @@ COUNT_SYMBOLS = ("ecb_count_alignments_device", "ecb_count_alignments")
 BUNDLE_SYMBOLS = ("ecb_bundle_device", "ecb_bundle")
 #: every symbol include/ecb_select.h declares (ecb.h includes it)
 SELECT_SYMBOLS = ("ecb_select_device", "ecb_select")
+#: every symbol include/ecb_quant.h declares (ecb.h includes it)
+QUANT_SYMBOLS = ("ecb_quantify_device", "ecb_quantify")
 #: ``ecb_select``'s row classes (include/ecb_select.h)
 ROW_CLASSES = {None: 0, "all": 0, "unique": 1, "locus-unique": 2, "multi": 3}
 ABI_VERSION = 4            # include/ecb.h: ECB_ABI_VERSION
@@ -183,6 +185,10 @@ def load():
     if not ab or hasattr(lib, "ecb_select"):
         for f in (lib.ecb_select_device, lib.ecb_select):
             f.argtypes = [C.c_int] + [C.c_uint32] * 4 + [u64, vp, vp, vp, u64, vp, vp, vp, C.c_int32, vp, C.c_int64] + [vp] * 7 + [C.POINTER(u64)]
+    if not ab or hasattr(lib, "ecb_quantify"):
+        for f in (lib.ecb_quantify_device, lib.ecb_quantify):
+            f.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.c_uint32, u64, vp, vp, vp, C.c_int64, vp, vp, C.c_uint32,
+                          C.c_double, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_uint32)]
     lib.ecb_csr_to_hapcsc_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.POINTER(u64)]
     lib.ecb_hapcsc_to_csr_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, u64, vp, vp, vp, C.POINTER(u64)]
     _lib = lib
@@ -349,6 +355,48 @@ def count_alignments(indptr, indices, data, n_loci, n_haps, indptr_n, indices_n,
     _check(lib, lib.ecb_count_alignments(device, E, n_loci, n_haps, nnz, _ptr(ip), _ptr(ix), _ptr(da), S, nnz_n, _ptr(pn), _ptr(xn), _ptr(dn), s,
                                          _ptr(aln), _ptr(uniq), _ptr(lu)))
     return aln, uniq, lu
+
+
+def quantify(indptr, indices, data, n_loci, n_haps, indptr_n, indices_n, data_n, sample=None, scale=None, theta_in=None, max_iters=1000,
+             tol=1e-6, device=0):
+    """ecquant on the GPU: EM abundance estimates of CSR A (``.bin``'s bitmask values) weighted by CSC N -- the reference's ``multiply(axis=2)``,
+    ``normalize_reads(axis=READ)``, ``sum(axis=READ)`` (``AlignmentPropertyMatrix.py:277-384``) iterated until the change of one step,
+    summed over all entries, is at most ``tol`` times the reads that align, or ``max_iters`` steps have run.  ``sample`` as for
+    :func:`count_alignments`; ``scale`` and ``theta_in``: float64 ``[H, T]`` or None (1 everywhere; the alignment counts).  numpy arrays go
+    through ``ecb_quantify`` (host arrays, no PyTorch), CUDA tensors through ``ecb_quantify_device`` (``device`` is then the tensors' own).
+    Returns ``(theta[H, T] float64, info)``, theta of the same kind as the input, ``info`` a dict with ``n_iter``, ``delta``, ``explained``
+    and ``converged``.  Malformed input, an unknown sample or a NaN, infinite or negative entry of ``scale`` / ``theta_in`` raises
+    :class:`EcbError` (``ECB_ERR_CONTRACT``)."""
+    lib = load()
+    s = -1 if sample is None else int(sample)
+    it, dl, ex, cv = C.c_uint32(), C.c_double(), C.c_int64(), C.c_uint32()
+    tail = (int(max_iters), float(tol))
+    outs = (C.byref(it), C.byref(dl), C.byref(ex), C.byref(cv))
+    if hasattr(indptr, "data_ptr"):
+        import torch
+        dev = indptr.device
+        ip, ix, da, pn, xn, dn = (t.contiguous().to(torch.int32) for t in (indptr, indices, data, indptr_n, indices_n, data_n))
+        E, nnz, S, nnz_n = ip.numel() - 1, ix.numel(), pn.numel() - 1, xn.numel()
+        if da.numel() != nnz or dn.numel() != nnz_n:
+            raise ValueError("indices and data differ in length")
+        tabs = [None if t is None else t.to(device=dev, dtype=torch.float64).contiguous() for t in (scale, theta_in)]
+        if any(t is not None and tuple(t.shape) != (n_haps, n_loci) for t in tabs):
+            raise ValueError("scale and theta_in are [n_haps, n_loci]")
+        theta = torch.empty((n_haps, n_loci), dtype=torch.float64, device=dev)
+        _check(lib, lib.ecb_quantify_device(dev.index or 0, E, n_loci, n_haps, nnz, _dev_ptr(ip), _dev_ptr(ix), _dev_ptr(da), S, nnz_n, _dev_ptr(pn),
+                                            _dev_ptr(xn), _dev_ptr(dn), s, _dev_ptr(tabs[0]), _dev_ptr(tabs[1]), tail[0], tail[1], _dev_ptr(theta), *outs))
+    else:
+        ip, ix, da, pn, xn, dn = (np.ascontiguousarray(a, dtype=np.int32) for a in (indptr, indices, data, indptr_n, indices_n, data_n))
+        E, nnz, S, nnz_n = len(ip) - 1, len(ix), len(pn) - 1, len(xn)
+        if len(da) != nnz or len(dn) != nnz_n:
+            raise ValueError("indices and data differ in length")
+        tabs = [None if t is None else np.ascontiguousarray(t, dtype=np.float64) for t in (scale, theta_in)]
+        if any(t is not None and t.shape != (n_haps, n_loci) for t in tabs):
+            raise ValueError("scale and theta_in are [n_haps, n_loci]")
+        theta = np.empty((n_haps, n_loci), dtype=np.float64)
+        _check(lib, lib.ecb_quantify(device, E, n_loci, n_haps, nnz, _ptr(ip), _ptr(ix), _ptr(da), S, nnz_n, _ptr(pn), _ptr(xn), _ptr(dn), s,
+                                     _ptr(tabs[0]), _ptr(tabs[1]), tail[0], tail[1], _ptr(theta), *outs))
+    return theta, {"n_iter": it.value, "delta": dl.value, "explained": ex.value, "converged": bool(cv.value)}
 
 
 def combine(parts, n_loci, n_haps, n_samples, device=0):

@@ -1,5 +1,5 @@
 # -*- coding: utf-8 -*-
-"""Same driver functions as the reference's ``alntools/methods.py:32-53, 205-210``, ``apply_genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``count_alignments`` and ``ecdump`` for the hot path."""
+"""Same driver functions as the reference's ``alntools/methods.py:32-53, 205-210``, ``apply_genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``count_alignments``, ``ecquant`` and ``ecdump`` for the hot path."""
 from __future__ import annotations
 
 from . import bam_utils, bin_utils
@@ -65,6 +65,10 @@ def ecselect(ec_file, out_file, row_class=None, samples=None, samples_file=None,
 
 def count_alignments(ec_file, out_file, sample=None):
     bin_utils.count_alignments(ec_file, out_file, sample=sample)
+
+
+def ecquant(ec_file, out_file, sample=None, use_lengths=False, max_iters=1000, tol=1e-6):
+    bin_utils.ecquant(ec_file, out_file, sample=sample, use_lengths=use_lengths, max_iters=max_iters, tol=tol)
 
 
 def ecdump(ec_file):

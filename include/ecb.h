@@ -400,5 +400,7 @@ const char* ecb_profile_kernel(const ecb_handle* h);
 #  include "ecb_bundle.h"
 /* ... and the ones that pull a class of reads and the samples that still count them out of a .bin (ecselect). */
 #   include "ecb_select.h"
+/* ... and the ones that iterate the EM a .bin exists to feed (ecquant). */
+#    include "ecb_quant.h"
 
 #endif /* ECB_H */
