@@ -4616,8 +4616,8 @@ __global__ __launch_bounds__(TPB) void k_gm_check(const int* indptr, u32 n_ecs, 
     }
 }
 // excl = exclusive scan of keep, nnz + 1 values (excl[nnz] = kept): non-zero i is kept when excl[i + 1] != excl[i] and goes to excl[i];
-// row e starts at excl[indptr[e]].  Every write stays inside its array whatever the input held (a malformed CSR has been flagged and the
-// call reports it: the outputs are then not used).
+// row e starts at excl[indptr[e]].  Every write stays inside its array whatever the input held (and a malformed CSR never gets here: the
+// call reads the check's verdict first, so that a refused call leaves the caller's outputs as they were).
 __global__ __launch_bounds__(TPB) void k_gm_scatter(const int* indptr, u32 n_ecs, const int* indices, const int* data, u64 nnz, const u32* mask,
                                                     u32 n_loci, const u32* excl, int* out_indptr, int* out_indices, int* out_data) {
     const u64 t = blockIdx.x * (u64)TPB + threadIdx.x;
@@ -4686,13 +4686,15 @@ extern "C" int ecb_apply_mask_device(int device, uint32_t n_ecs, uint32_t n_loci
     k_gm_check<false><<<nblk(threads, TPB), TPB, 0, st>>>(ip, n_ecs, ix, da, nnz, mk, n_loci, n_haps, keep, words);
     CALLCHK(c, hipGetLastError());
     CALLCHK(c, scan_launch(st, keep, nnz, excl, sums, words + 3, 1, excl + nnz));
-    k_gm_scatter<<<nblk(threads, TPB), TPB, 0, st>>>(ip, n_ecs, ix, da, nnz, mk, n_loci, excl, (int*)d_out_indptr, (int*)d_out_indices, (int*)d_out_data);
-    CALLCHK(c, hipGetLastError());
+    // the verdict first: a refused call writes nothing into the caller's outputs (one more wait; the scatter is then a launch of its own)
     std::vector<u64> back(n_words);
     if (const int rc = c.read_back(back.data(), words, n_words, GM_ERRS)) return rc;
     u64 balance = 0;
     for (u32 k = 1; k <= GM_SHARDS; ++k) balance += back[GM_SHARD_WORDS * k];
     if (balance != 0) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSR: columns not strictly ascending within a row (unsorted or duplicate)");
+    k_gm_scatter<<<nblk(threads, TPB), TPB, 0, st>>>(ip, n_ecs, ix, da, nnz, mk, n_loci, excl, (int*)d_out_indptr, (int*)d_out_indices, (int*)d_out_data);
+    CALLCHK(c, hipGetLastError());
+    CALLCHK(c, hipStreamSynchronize(st));
     *kept = back[3];
     return ECB_OK;
 }

@@ -19,6 +19,9 @@
  * and hands back the CSR A matrix (value = haplotype bitmask, bin_utils.py:208-211) and the
  * N matrix that alntools' writers (bin_utils.ecsave2, APM.save) consume.
  *
+ * Device pointers (every entry point whose name ends in _device) need only the alignment of their element type -- 4 bytes for the int32 / uint32
+ * arrays, 8 for int64 / double arrays, the 8-byte pairs, keys and hashes and the 32-byte table entries, 1 for a text -- except the streams of
+ * ecb_push_device* and ecb_verify_device*, which must be 16-byte aligned (ECB_ERR_ARG otherwise).
  * Conventions: plain C types only; caller owns every buffer it passes; the library owns
  * the device memory behind the opaque handle; return 0 = OK, < 0 = error code and
  * ecb_last_error() explains.  A handle is bound to one GPU and is not thread-safe.
@@ -319,7 +322,7 @@ int ecb_hapcsc_to_csr(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_ha
  * the non-zeros that become 0 removed, every row kept (empty rows too), columns ascending -- what the reference's
  * AlignmentPropertyMatrix.apply_genotypes + ecsave2 write (AlignmentPropertyMatrix.py:483-505, bin_utils.py:1031-1051).
  * indptr n_ecs + 1, indices / data nnz, mask n_loci values (bit h = haplotype h allowed at that locus), all int32 / uint32.
- * The input must be well formed; otherwise ECB_ERR_CONTRACT and nothing is reported kept: row pointers from 0 to nnz, never falling;
+ * The input must be well formed; otherwise ECB_ERR_CONTRACT, nothing is reported kept and no output is written: row pointers from 0 to nnz, never falling;
  * loci below n_loci; columns strictly ascending within a row (an unsorted or duplicate column is refused); no data or mask bit at or above
  * n_haps (<= 31).
  * ecb_apply_mask_device: device pointers; the outputs (out_indptr n_ecs + 1, out_indices / out_data room for nnz) must not overlap the
