@@ -399,16 +399,48 @@ def length_scale(m, aln):
     return scale
 
 
-def ecquant(ec_filename, out_filename, sample=None, use_lengths=False, max_iters=1000, tol=1e-6, device=0):
+def gene_ids(m, grp_filename):
+    """Group file -> ``(gene, names)``: ``gene[t]`` (int32, T) is the gene of target ``t``, what ``ecquant -M 1..3`` hands to
+    ``ecb.quantify_model``, and ``names`` the genes' names.  The file is read by :func:`load_groups` (a transcript that is not a target is a
+    KeyError).  Genes are numbered in file order, a line with no members adds none; a target on no line is a gene of its own, named after
+    itself and numbered after the file's genes in target order.  A target in two groups, or a group name on two lines, is a ValueError
+    naming it (one listed twice on a line counts once)."""
+    gname, groups = load_groups(m, grp_filename)
+    gene = np.full(m.num_loci, -1, dtype=np.int32)
+    names, seen = [], set()
+    for g, tids in zip(gname, groups):
+        if g in seen:
+            raise ValueError("{}: group {} is listed more than once".format(grp_filename, g))
+        seen.add(g)
+        if not tids:
+            continue
+        for t in tids:
+            if gene[t] not in (-1, len(names)):
+                raise ValueError("{}: target {} is in two groups ({} and {})".format(grp_filename, m.lname[t], names[gene[t]], g))
+            gene[t] = len(names)
+        names.append(g)
+    for t in np.flatnonzero(gene < 0):
+        gene[t] = len(names)
+        names.append(m.lname[t])
+    return gene, names
+
+
+def ecquant(ec_filename, out_filename, sample=None, use_lengths=False, max_iters=1000, tol=1e-6, device=0, model=4, groups=None):
     """``alntools ecquant``: EM abundance estimates of a ``.bin`` (``ecb.quantify``: the reference's ``multiply`` / ``normalize_reads`` /
     ``sum`` iterated on the GPU), written as a table of ``locus, <haplotypes>, total`` in read units.  A multisample file is quantified over
     all its samples pooled, or over the one named ``sample``.  ``use_lengths``: every abundance is weighted by 1 / its target's length
-    (:func:`length_scale`).  A failure is logged as ``Error: ...`` and raised again; no file is written then."""
+    (:func:`length_scale`).  ``model`` 1, 2 or 3: one of EMASE's hierarchical models over the genes of the group file ``groups``
+    (:func:`gene_ids`, ``ecb.quantify_model``); without ``groups`` they are refused by name.  ``model`` 4, the default, is the flat step, and
+    ``groups`` then changes nothing.  A failure is logged as ``Error: ...`` and raised again; no file is written then."""
     import time
     from . import ecb, utils
     LOG = utils.get_logger()
     try:
         start_time = time.time()
+        if model not in (1, 2, 3, 4):
+            raise ValueError("model {} is not one of 1, 2, 3, 4".format(model))
+        if model != 4 and groups is None:
+            raise ValueError("model {} needs a group file (-g/--groups)".format(model))
         LOG.info("Loading {}...".format(ec_filename))
         m = ecload(ec_filename)
         col = None
@@ -417,12 +449,20 @@ def ecquant(ec_filename, out_filename, sample=None, use_lengths=False, max_iters
                 raise KeyError("sample {} is not in {}".format(sample, ec_filename))
             col = m.sname.index(sample)
         args = (m.indptrA, m.indicesA, m.dataA, m.num_loci, m.num_haplotypes, m.indptrN, m.indicesN, m.dataN)
+        gene = names = None
+        if model != 4:
+            gene, names = gene_ids(m, groups)
         scale = None
         if use_lengths:
             aln = ecb.count_alignments(*args, sample=col, device=device)[0]       # (theta_0 is this aln: no need for ecquant's own set-up twice)
             scale = length_scale(m, aln)
-        LOG.info("Estimating abundances...")
-        theta, info = ecb.quantify(*args, sample=col, scale=scale, max_iters=max_iters, tol=tol, device=device)
+        if model == 4:
+            LOG.info("Estimating abundances...")
+            theta, info = ecb.quantify(*args, sample=col, scale=scale, max_iters=max_iters, tol=tol, device=device)
+        else:
+            LOG.info("Estimating abundances (model {}, {:,} genes)...".format(model, len(names)))
+            theta, info = ecb.quantify_model(*args, gene=gene, n_genes=len(names), model=model, sample=col, scale=scale, max_iters=max_iters,
+                                             tol=tol, device=device)
         LOG.info("iterations: {:,}; delta: {!r}; explained reads: {:,}; {}".format(info["n_iter"], info["delta"], info["explained"],
                                                                                   "converged" if info["converged"] else "not converged"))
         with open(out_filename, 'w') as fh:

@@ -205,14 +205,19 @@ def count_alignments(ec_file, out_file, sample, verbose):
 @click.option('-l', '--use-lengths', is_flag=True, help='weight every abundance by 1 / the length of its target')
 @click.option('-i', '--max-iters', default=1000, type=click.IntRange(min=0), help='EM steps at the most (default: 1000)')
 @click.option('-t', '--tolerance', 'tol', default=1e-6, type=float, help='stop when one step changes less than this share of the reads (default: 1e-6)')
+@click.option('-M', '--model', default='4', type=click.Choice(['1', '2', '3', '4']),
+              help='EMASE model: 1 gene->allele->isoform, 2 gene->isoform->allele, 3 gene->isoform x allele (each needs -g), 4 flat (default: 4)')
+@click.option('-g', '--groups', metavar='<grp_file>', default=None, type=click.Path(exists=True, resolve_path=True, dir_okay=False),
+              help='group file (gene, transcripts...) for models 1 to 3')
 @click.option('-v', '--verbose', count=True, help='enables verbose mode')
-def ecquant(ec_file, out_file, sample, use_lengths, max_iters, tol, verbose):
+def ecquant(ec_file, out_file, sample, use_lengths, max_iters, tol, model, groups, verbose):
     """
     Estimate the abundance of every target and haplotype of a binary EC file (ec_file) by EM and write them, in reads, to a table (out_file)
     """
     utils.configure_logging(verbose)
     try:
-        methods.ecquant(ec_file, out_file, sample, use_lengths, max_iters, tol)
+        more = () if model == '4' and groups is None else (int(model), groups)
+        methods.ecquant(ec_file, out_file, sample, use_lengths, max_iters, tol, *more)
     except Exception:
         sys.exit(1)                                                  # (logged as "Error: ..." by bin_utils.ecquant)
 

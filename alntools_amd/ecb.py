@@ -46,6 +46,8 @@ BUNDLE_SYMBOLS = ("ecb_bundle_device", "ecb_bundle")
 SELECT_SYMBOLS = ("ecb_select_device", "ecb_select")
 #: every symbol include/ecb_quant.h declares (ecb.h includes it)
 QUANT_SYMBOLS = ("ecb_quantify_device", "ecb_quantify")
+#: every symbol include/ecb_quant_model.h declares (ecb_quant.h includes it)
+QUANT_MODEL_SYMBOLS = ("ecb_quantify_model_device", "ecb_quantify_model")
 #: ``ecb_select``'s row classes (include/ecb_select.h)
 ROW_CLASSES = {None: 0, "all": 0, "unique": 1, "locus-unique": 2, "multi": 3}
 ABI_VERSION = 4            # include/ecb.h: ECB_ABI_VERSION
@@ -189,6 +191,11 @@ def load():
         for f in (lib.ecb_quantify_device, lib.ecb_quantify):
             f.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.c_uint32, u64, vp, vp, vp, C.c_int64, vp, vp, C.c_uint32,
                           C.c_double, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_uint32)]
+    if not ab or hasattr(lib, "ecb_quantify_model"):
+        for f in (lib.ecb_quantify_model_device, lib.ecb_quantify_model):
+            f.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.c_uint32, u64, vp, vp, vp, C.c_int64, vp, vp, C.c_uint32,
+                          C.c_double, C.c_uint32, vp, C.c_uint32, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_int64),
+                          C.POINTER(C.c_uint32)]
     lib.ecb_csr_to_hapcsc_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.POINTER(u64)]
     lib.ecb_hapcsc_to_csr_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, u64, vp, vp, vp, C.POINTER(u64)]
     _lib = lib
@@ -396,6 +403,51 @@ def quantify(indptr, indices, data, n_loci, n_haps, indptr_n, indices_n, data_n,
         theta = np.empty((n_haps, n_loci), dtype=np.float64)
         _check(lib, lib.ecb_quantify(device, E, n_loci, n_haps, nnz, _ptr(ip), _ptr(ix), _ptr(da), S, nnz_n, _ptr(pn), _ptr(xn), _ptr(dn), s,
                                      _ptr(tabs[0]), _ptr(tabs[1]), tail[0], tail[1], _ptr(theta), *outs))
+    return theta, {"n_iter": it.value, "delta": dl.value, "explained": ex.value, "converged": bool(cv.value)}
+
+
+def quantify_model(indptr, indices, data, n_loci, n_haps, indptr_n, indices_n, data_n, gene, n_genes, model, sample=None, scale=None,
+                   theta_in=None, max_iters=1000, tol=1e-6, device=0):
+    """ecquant with one of EMASE's models over a gene grouping (``ecb_quantify_model`` / ``ecb_quantify_model_device``): :func:`quantify`
+    with ``gene`` (int32 ``[T]``, ``gene[t]`` in ``[0, n_genes)``) and ``model`` -- 1 gene -> allele -> isoform, 2 gene -> isoform -> allele,
+    3 gene -> isoform x allele, 4 the flat step of :func:`quantify`, whose bytes it then returns.  Everything else, the kinds of the arrays
+    and the result as for :func:`quantify`.  A gene id outside ``[0, n_genes)`` raises :class:`EcbError` (``ECB_ERR_CONTRACT``), a model
+    outside 1..4 ``ECB_ERR_ARG``."""
+    lib = load()
+    s = -1 if sample is None else int(sample)
+    it, dl, ex, cv = C.c_uint32(), C.c_double(), C.c_int64(), C.c_uint32()
+    tail = (int(max_iters), float(tol), int(n_genes))
+    outs = (C.byref(it), C.byref(dl), C.byref(ex), C.byref(cv))
+    if hasattr(indptr, "data_ptr"):
+        import torch
+        dev = indptr.device
+        ip, ix, da, pn, xn, dn = (t.contiguous().to(torch.int32) for t in (indptr, indices, data, indptr_n, indices_n, data_n))
+        gn = torch.as_tensor(gene).to(device=dev, dtype=torch.int32).contiguous()
+        E, nnz, S, nnz_n = ip.numel() - 1, ix.numel(), pn.numel() - 1, xn.numel()
+        if da.numel() != nnz or dn.numel() != nnz_n:
+            raise ValueError("indices and data differ in length")
+        if gn.numel() != n_loci:
+            raise ValueError("gene is [n_loci]")
+        tabs = [None if t is None else t.to(device=dev, dtype=torch.float64).contiguous() for t in (scale, theta_in)]
+        if any(t is not None and tuple(t.shape) != (n_haps, n_loci) for t in tabs):
+            raise ValueError("scale and theta_in are [n_haps, n_loci]")
+        theta = torch.empty((n_haps, n_loci), dtype=torch.float64, device=dev)
+        _check(lib, lib.ecb_quantify_model_device(dev.index or 0, E, n_loci, n_haps, nnz, _dev_ptr(ip), _dev_ptr(ix), _dev_ptr(da), S, nnz_n,
+                                                  _dev_ptr(pn), _dev_ptr(xn), _dev_ptr(dn), s, _dev_ptr(tabs[0]), _dev_ptr(tabs[1]), tail[0], tail[1],
+                                                  tail[2], _dev_ptr(gn), int(model), _dev_ptr(theta), *outs))
+    else:
+        ip, ix, da, pn, xn, dn, gn = (np.ascontiguousarray(a, dtype=np.int32) for a in (indptr, indices, data, indptr_n, indices_n, data_n, gene))
+        E, nnz, S, nnz_n = len(ip) - 1, len(ix), len(pn) - 1, len(xn)
+        if len(da) != nnz or len(dn) != nnz_n:
+            raise ValueError("indices and data differ in length")
+        if gn.shape != (n_loci,):
+            raise ValueError("gene is [n_loci]")
+        tabs = [None if t is None else np.ascontiguousarray(t, dtype=np.float64) for t in (scale, theta_in)]
+        if any(t is not None and t.shape != (n_haps, n_loci) for t in tabs):
+            raise ValueError("scale and theta_in are [n_haps, n_loci]")
+        theta = np.empty((n_haps, n_loci), dtype=np.float64)
+        _check(lib, lib.ecb_quantify_model(device, E, n_loci, n_haps, nnz, _ptr(ip), _ptr(ix), _ptr(da), S, nnz_n, _ptr(pn), _ptr(xn), _ptr(dn), s,
+                                           _ptr(tabs[0]), _ptr(tabs[1]), tail[0], tail[1], tail[2], _ptr(gn), int(model), _ptr(theta), *outs))
     return theta, {"n_iter": it.value, "delta": dl.value, "explained": ex.value, "converged": bool(cv.value)}
 
 

@@ -45,4 +45,8 @@ int ecb_quantify(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, u
 #ifdef __cplusplus
 }
 #endif
+
+/* the same EM with EMASE's hierarchical models over a gene grouping (ecb_quantify_model / ecb_quantify_model_device): a header of its own */
+#include "ecb_quant_model.h"
+
 #endif /* ECB_QUANT_H */
