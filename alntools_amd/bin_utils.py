@@ -473,6 +473,64 @@ def ecquant(ec_filename, out_filename, sample=None, use_lengths=False, max_iters
         raise
 
 
+def cells_table(sname, lname, hname, cell_ptr, slot_locus, theta):
+    """The text ``ecquant-cells`` writes: a header ``sample, locus, <haplotype names>, total`` and one tab-separated line per slot -- a target
+    in the support of a cell -- in cell order, every number as :func:`quant_table` writes them (``str(float(v))``)."""
+    theta = np.asarray(theta, dtype=np.float64)
+    out = ["sample\tlocus\t" + "\t".join(hname) + "\ttotal\n"]
+    for c, name in enumerate(sname):
+        for s in range(int(cell_ptr[c]), int(cell_ptr[c + 1])):
+            out.append("\t".join([name, lname[int(slot_locus[s])]] + [str(float(v)) for v in theta[s]] + [str(float(theta[s].sum()))]) + "\n")
+    return "".join(out)
+
+
+def cells_report(sname, info, keep=None):
+    """The text of ``ecquant-cells --report``: ``sample, n_iter, delta, explained, converged`` (0 or 1), one line per quantified cell."""
+    out = ["sample\tn_iter\tdelta\texplained\tconverged\n"]
+    for c, name in enumerate(sname):
+        if keep is None or keep[c]:
+            out.append("%s\t%d\t%s\t%d\t%d\n" % (name, int(info["n_iter"][c]), str(float(info["delta"][c])), int(info["explained"][c]),
+                                                 int(bool(info["converged"][c]))))
+    return "".join(out)
+
+
+def ecquant_cells(ec_filename, out_filename, samples=None, samples_file=None, use_lengths=False, max_iters=1000, tol=1e-6, report=None, device=0):
+    """``alntools ecquant-cells``: one EM abundance estimate per sample (cell) of a multisample ``.bin`` (``ecb.quantify_cells``: every cell
+    over its own support, all iterated together on the GPU), written as :func:`cells_table`; ``report``: a second file, :func:`cells_report`.
+    ``samples`` / ``samples_file`` name the cells as for ``ecselect`` (:func:`named_samples`; default: all).  ``use_lengths``: every abundance
+    is weighted by 1 / its target's length (:func:`length_scale` on the alignment counts of all samples pooled: what ``ecquant -l`` refuses is
+    refused here by the same name).  A failure is logged as ``Error: ...`` and raised again; no file is written then."""
+    import time
+    from . import utils
+    LOG = utils.get_logger()
+    try:
+        start_time = time.time()
+        LOG.info("Loading {}...".format(ec_filename))
+        m = ecload(ec_filename)
+        keep = named_samples(m, samples, samples_file)
+        from . import ecb
+        args = (m.indptrA, m.indicesA, m.dataA, m.num_loci, m.num_haplotypes, m.indptrN, m.indicesN, m.dataN)
+        scale = None
+        if use_lengths:
+            scale = length_scale(m, ecb.count_alignments(*args, device=device)[0])
+        LOG.info("Estimating abundances of {:,} cells...".format(m.num_samples if keep is None else int(keep.sum())))
+        cell_ptr, slot_locus, theta, info = ecb.quantify_cells(*args, cell_keep=keep, scale=scale, max_iters=max_iters, tol=tol, device=device)
+        ran = np.ones(m.num_samples, dtype=bool) if keep is None else keep
+        LOG.info("slots: {:,}; most iterations: {:,}; explained reads: {:,}; cells not converged: {:,}".format(
+            len(slot_locus), int(np.max(info["n_iter"], initial=0)), int(np.sum(info["explained"])), int(np.sum(~np.asarray(info["converged"])[ran]))))
+        table = cells_table(m.sname, m.lname, m.hname, cell_ptr, slot_locus, theta)
+        rep = cells_report(m.sname, info, keep) if report is not None else None
+        with open(out_filename, 'w') as fh:
+            fh.write(table)
+        if rep is not None:
+            with open(report, 'w') as fh:
+                fh.write(rep)
+        LOG.info("{} created in total time: {}".format(out_filename, utils.format_time(start_time, time.time())))
+    except Exception as e:
+        LOG.error("Error: {}".format(e.args[0] if isinstance(e, KeyError) and e.args else str(e)))
+        raise
+
+
 def ecdump(ec_filename):
     """``alntools ecdump`` (``bin_utils.py:959-976``): the shapes of a ``.bin``, as the reference's log lines.  Host only."""
     from . import utils

@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
 """Command line with the reference's hot-path sub-commands and options (``alntools/cli.py:43-113``):
-``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``, ``apply-genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``count-alignments``, ``ecquant``, ``ecdump``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
+``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``, ``apply-genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``count-alignments``, ``ecquant``, ``ecquant-cells``, ``ecdump``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
 from __future__ import annotations
 
 import glob
@@ -220,6 +220,31 @@ def ecquant(ec_file, out_file, sample, use_lengths, max_iters, tol, model, group
         methods.ecquant(ec_file, out_file, sample, use_lengths, max_iters, tol, *more)
     except Exception:
         sys.exit(1)                                                  # (logged as "Error: ..." by bin_utils.ecquant)
+
+
+@cli.command('ecquant-cells', options_metavar='<options>', short_help='estimate abundances per sample (cell) of a multisample EC file by EM')
+@click.argument('ec_file', metavar='ec_file', type=click.Path(exists=True, resolve_path=True, dir_okay=False))
+@click.argument('out_file', metavar='out_file', type=click.Path(resolve_path=True, dir_okay=False, writable=True))
+@click.option('-s', '--sample', 'samples', metavar='NAME', multiple=True, help="sample to quantify, can specify multiple (default: all)")
+@click.option('--samples', 'samples_file', metavar='FILE', type=click.Path(exists=True, resolve_path=True, dir_okay=False),
+              help="file with the names of the samples to quantify, one per line")
+@click.option('-l', '--use-lengths', is_flag=True, help='weight every abundance by 1 / the length of its target')
+@click.option('-i', '--max-iters', default=1000, type=click.IntRange(min=0), help='EM steps per sample at the most (default: 1000)')
+@click.option('-t', '--tolerance', 'tol', default=1e-6, type=float,
+              help="stop a sample when one step changes less than this share of its reads (default: 1e-6)")
+@click.option('--report', metavar='FILE', default=None, type=click.Path(resolve_path=True, dir_okay=False, writable=True),
+              help='write n_iter, delta, explained and converged per sample to this file')
+@click.option('-v', '--verbose', count=True, help='enables verbose mode')
+def ecquant_cells(ec_file, out_file, samples, samples_file, use_lengths, max_iters, tol, report, verbose):
+    """
+    Estimate, for every sample of a binary EC file (ec_file), the abundance of every target it touches by an EM of its own and write them, in
+    reads, to a table with one line per sample and target (out_file)
+    """
+    utils.configure_logging(verbose)
+    try:
+        methods.ecquant_cells(ec_file, out_file, list(samples) or None, samples_file, use_lengths, max_iters, tol, report)
+    except Exception:
+        sys.exit(1)                                                  # (logged as "Error: ..." by bin_utils.ecquant_cells)
 
 
 @cli.command('ecdump', options_metavar='<options>', short_help='show the shapes of an EC file')

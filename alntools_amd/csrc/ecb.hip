@@ -4980,6 +4980,8 @@ extern "C" int ecb_count_alignments(int device, uint32_t n_ecs, uint32_t n_loci,
 #include "quant.inc"
 // ... and its hierarchical models over a gene grouping (ecb_quantify_model / ecb_quantify_model_device)
 #include "quant_model.inc"
+// ... and one EM per cell of a multisample N, batched (ecb_cell_support* / ecb_quantify_cells*)
+#include "quant_cells.inc"
 
 // ---- ecselect: the reads of one class and the samples that still count enough of them, pulled out of a .bin (ecb_select / ecb_select_device)
 // (AlignmentPropertyMatrix.get_unique_reads / pull_alignments_from, AlignmentPropertyMatrix.py:386-427, and the cell threshold of

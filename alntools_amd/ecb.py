@@ -48,6 +48,8 @@ SELECT_SYMBOLS = ("ecb_select_device", "ecb_select")
 QUANT_SYMBOLS = ("ecb_quantify_device", "ecb_quantify")
 #: every symbol include/ecb_quant_model.h declares (ecb_quant.h includes it)
 QUANT_MODEL_SYMBOLS = ("ecb_quantify_model_device", "ecb_quantify_model")
+#: every symbol include/ecb_quant_cells.h declares (ecb_quant.h includes it)
+QUANT_CELLS_SYMBOLS = ("ecb_cell_support_device", "ecb_cell_support", "ecb_quantify_cells_device", "ecb_quantify_cells")
 #: ``ecb_select``'s row classes (include/ecb_select.h)
 ROW_CLASSES = {None: 0, "all": 0, "unique": 1, "locus-unique": 2, "multi": 3}
 ABI_VERSION = 4            # include/ecb.h: ECB_ABI_VERSION
@@ -196,6 +198,12 @@ def load():
             f.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.c_uint32, u64, vp, vp, vp, C.c_int64, vp, vp, C.c_uint32,
                           C.c_double, C.c_uint32, vp, C.c_uint32, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_int64),
                           C.POINTER(C.c_uint32)]
+    if not ab or hasattr(lib, "ecb_quantify_cells"):
+        head = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.c_uint32, u64, vp, vp, vp, vp]
+        for f in (lib.ecb_cell_support_device, lib.ecb_cell_support):
+            f.argtypes = head + [vp, vp, u64, C.POINTER(u64)]
+        for f in (lib.ecb_quantify_cells_device, lib.ecb_quantify_cells):
+            f.argtypes = head + [vp, vp, C.c_uint32, C.c_double, u64, u64] + [vp] * 7
     lib.ecb_csr_to_hapcsc_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.POINTER(u64)]
     lib.ecb_hapcsc_to_csr_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, u64, vp, vp, vp, C.POINTER(u64)]
     _lib = lib
@@ -449,6 +457,95 @@ def quantify_model(indptr, indices, data, n_loci, n_haps, indptr_n, indices_n, d
         _check(lib, lib.ecb_quantify_model(device, E, n_loci, n_haps, nnz, _ptr(ip), _ptr(ix), _ptr(da), S, nnz_n, _ptr(pn), _ptr(xn), _ptr(dn), s,
                                            _ptr(tabs[0]), _ptr(tabs[1]), tail[0], tail[1], tail[2], _ptr(gn), int(model), _ptr(theta), *outs))
     return theta, {"n_iter": it.value, "delta": dl.value, "explained": ex.value, "converged": bool(cv.value)}
+
+
+def _cells_args(indptr, indices, data, indptr_n, indices_n, data_n, cell_keep):
+    """The matrices and ``cell_keep`` as the per-cell entry points take them: (tensors?, device or None, arrays, E, nnz, S, nnz_n)."""
+    if hasattr(indptr, "data_ptr"):
+        import torch
+        dev = indptr.device
+        arrs = [t.contiguous().to(torch.int32) for t in (indptr, indices, data, indptr_n, indices_n, data_n)]
+        keep = None if cell_keep is None else torch.as_tensor(cell_keep).to(device=dev).ne(0).to(torch.uint8).contiguous()
+        sizes = (arrs[0].numel() - 1, arrs[1].numel(), arrs[3].numel() - 1, arrs[4].numel())
+        if arrs[2].numel() != sizes[1] or arrs[5].numel() != sizes[3]:
+            raise ValueError("indices and data differ in length")
+        if keep is not None and keep.numel() != sizes[2]:
+            raise ValueError("cell_keep is [n_samples]")
+        return True, dev, arrs + [keep], sizes
+    arrs = [np.ascontiguousarray(a, dtype=np.int32) for a in (indptr, indices, data, indptr_n, indices_n, data_n)]
+    keep = None if cell_keep is None else np.ascontiguousarray(np.asarray(cell_keep) != 0, dtype=np.uint8)
+    sizes = (len(arrs[0]) - 1, len(arrs[1]), len(arrs[3]) - 1, len(arrs[4]))
+    if len(arrs[2]) != sizes[1] or len(arrs[5]) != sizes[3]:
+        raise ValueError("indices and data differ in length")
+    if keep is not None and keep.shape != (sizes[2],):
+        raise ValueError("cell_keep is [n_samples]")
+    return False, None, arrs + [keep], sizes
+
+
+def cell_support(indptr, indices, data, n_loci, n_haps, indptr_n, indices_n, data_n, cell_keep=None, device=0, count_only=False):
+    """The targets detected per cell (``ecb_cell_support`` / ``ecb_cell_support_device``): for every column c of CSC N, the loci at which an EC
+    the cell counts (> 0) holds a mask other than 0, ascending.  ``cell_keep``: ``[n_samples]``, non-zero = this cell, None = every cell.
+    numpy arrays go through the host entry point, CUDA tensors through the device one.  Returns ``(cell_ptr int64 [S + 1], slot_locus int32
+    [n_slots])`` of the same kind as the input: cell c owns ``slot_locus[cell_ptr[c]:cell_ptr[c + 1]]``.  ``count_only``: one pass instead of
+    two, ``slot_locus`` is then None."""
+    lib = load()
+    tensors, dev, (ip, ix, da, pn, xn, dn, keep), (E, nnz, S, nnz_n) = _cells_args(indptr, indices, data, indptr_n, indices_n, data_n, cell_keep)
+    ns = C.c_uint64()
+    if tensors:
+        import torch
+        fn, p, d = lib.ecb_cell_support_device, _dev_ptr, dev.index or 0
+        new = lambda n, dt: torch.empty(n, dtype=dt, device=dev)          # noqa: E731
+        i64, i32 = torch.int64, torch.int32
+    else:
+        fn, p, d = lib.ecb_cell_support, _ptr, device
+        new = lambda n, dt: np.empty(n, dtype=dt)                         # noqa: E731
+        i64, i32 = np.int64, np.int32
+    head = (d, E, n_loci, n_haps, nnz, p(ip), p(ix), p(da), S, nnz_n, p(pn), p(xn), p(dn), p(keep))
+    cell_ptr = new(S + 1, i64)
+    _check(lib, fn(*(head + (p(cell_ptr), None, 0, C.byref(ns)))))       # (the sizes first ...
+    if count_only:
+        return cell_ptr, None
+    slot_locus = new(ns.value, i32)
+    if ns.value:
+        _check(lib, fn(*(head + (p(cell_ptr), p(slot_locus), ns.value, C.byref(ns)))))      # ... then the loci, into an array that fits)
+    return cell_ptr, slot_locus
+
+
+def quantify_cells(indptr, indices, data, n_loci, n_haps, indptr_n, indices_n, data_n, cell_keep=None, scale=None, theta_in=None, max_iters=1000,
+                   tol=1e-6, budget_bytes=0, device=0, n_slots=None):
+    """ecquant per cell on the GPU (``ecb_quantify_cells`` / ``ecb_quantify_cells_device``): one EM of :func:`quantify` for every column of N
+    that ``cell_keep`` names (None: all), each over its own support and stopping at its own step, all iterated by the same launches.
+    ``scale`` and ``theta_in``: float64 ``[H, T]`` or None, shared by every cell.  ``budget_bytes``: the device memory a batch of cells aims at
+    (0: half of what is free); the result does not depend on it.  numpy arrays go through the host entry point, CUDA tensors through the
+    device one.  Returns ``(cell_ptr int64 [S + 1], slot_locus int32 [n_slots], theta float64 [n_slots, H], info)`` of the same kind as the
+    input; ``info`` is a dict of per-cell arrays ``n_iter`` (uint32; int64 for tensors), ``delta`` (float64), ``explained`` (int64) and ``converged`` (bool).
+    The support is sized by :func:`cell_support` first, unless the caller passes the ``n_slots`` it learned there."""
+    lib = load()
+    tensors, dev, (ip, ix, da, pn, xn, dn, keep), (E, nnz, S, nnz_n) = _cells_args(indptr, indices, data, indptr_n, indices_n, data_n, cell_keep)
+    if tensors:
+        import torch
+        tabs = [None if t is None else t.to(device=dev, dtype=torch.float64).contiguous() for t in (scale, theta_in)]
+    else:
+        tabs = [None if t is None else np.ascontiguousarray(t, dtype=np.float64) for t in (scale, theta_in)]
+    if any(t is not None and tuple(t.shape) != (n_haps, n_loci) for t in tabs):
+        raise ValueError("scale and theta_in are [n_haps, n_loci]")
+    if n_slots is None:
+        n_slots = int(cell_support(ip, ix, da, n_loci, n_haps, pn, xn, dn, keep, device, count_only=True)[0][-1])
+    if tensors:
+        fn, p, d = lib.ecb_quantify_cells_device, _dev_ptr, dev.index or 0
+        new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)  # noqa: E731
+        i64, i32, u32, f64, u8 = torch.int64, torch.int32, torch.int32, torch.float64, torch.uint8
+    else:
+        fn, p, d = lib.ecb_quantify_cells, _ptr, device
+        new = lambda shape, dt: np.empty(shape, dtype=dt)                 # noqa: E731
+        i64, i32, u32, f64, u8 = np.int64, np.int32, np.uint32, np.float64, np.uint8
+    cell_ptr, slot_locus, theta = new(S + 1, i64), new(n_slots, i32), new((n_slots, n_haps), f64)
+    it, dl, ex, cv = new(S, u32), new(S, f64), new(S, i64), new(S, u8)
+    _check(lib, fn(d, E, n_loci, n_haps, nnz, p(ip), p(ix), p(da), S, nnz_n, p(pn), p(xn), p(dn), p(keep), p(tabs[0]), p(tabs[1]), int(max_iters),
+                   float(tol), int(budget_bytes), n_slots, p(cell_ptr), p(slot_locus), p(theta), p(it), p(dl), p(ex), p(cv)))
+    if tensors:
+        it = it.to(torch.int64).bitwise_and(0xFFFFFFFF)                  # (the uint32 the library wrote, in a type torch computes with)
+    return cell_ptr, slot_locus, theta, {"n_iter": it, "delta": dl, "explained": ex, "converged": cv != 0}
 
 
 def combine(parts, n_loci, n_haps, n_samples, device=0):

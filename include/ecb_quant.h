@@ -48,5 +48,7 @@ int ecb_quantify(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, u
 
 /* the same EM with EMASE's hierarchical models over a gene grouping (ecb_quantify_model / ecb_quantify_model_device): a header of its own */
 #include "ecb_quant_model.h"
+/* ... and one EM per cell of a multisample N, batched, the result sparse (ecb_cell_support* / ecb_quantify_cells*): likewise */
+#include "ecb_quant_cells.h"
 
 #endif /* ECB_QUANT_H */

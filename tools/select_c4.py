@@ -21,30 +21,32 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 E, T, H, S = 3000000, 80000, 2, 5000
 
 
-def inputs(seed=4):
+def inputs(seed=4, device="cuda", sizes=(10000, 30001)):
+    """The six arrays on ``device`` (tools/quant_c4.py rehearses on the CPU at a toy size)."""
     import torch
-    g = torch.Generator(device="cuda")
+    g = torch.Generator(device=device)
     g.manual_seed(seed)
     i32 = torch.int32
-    lens = torch.randint(1, 8, (E,), generator=g, device="cuda")
-    ipa = torch.zeros(E + 1, dtype=torch.int64, device="cuda")
+    lens = torch.randint(1, 8, (E,), generator=g, device=device)
+    ipa = torch.zeros(E + 1, dtype=torch.int64, device=device)
     ipa[1:] = torch.cumsum(lens, 0)
-    row = torch.repeat_interleave(torch.arange(E, device="cuda"), lens)
-    start = torch.randint(0, T - 8, (E,), generator=g, device="cuda")
-    ixa = torch.arange(int(ipa[-1]), device="cuda") - ipa[:-1][row] + start[row]
-    daa = torch.randint(1, 1 << H, (int(ipa[-1]),), generator=g, device="cuda")
-    daa[torch.rand(len(daa), generator=g, device="cuda") < 0.5] = 1          # half the non-zeros carry one haplotype
-    sizes = torch.randint(10000, 30001, (S,), generator=g, device="cuda")
-    ipn = torch.zeros(S + 1, dtype=torch.int64, device="cuda")
+    row = torch.repeat_interleave(torch.arange(E, device=device), lens)
+    start = torch.randint(0, T - 8, (E,), generator=g, device=device)
+    ixa = torch.arange(int(ipa[-1]), device=device) - ipa[:-1][row] + start[row]
+    daa = torch.randint(1, 1 << H, (int(ipa[-1]),), generator=g, device=device)
+    daa[torch.rand(len(daa), generator=g, device=device) < 0.5] = 1          # half the non-zeros carry one haplotype
+    sizes = torch.randint(sizes[0], sizes[1], (S,), generator=g, device=device)
+    ipn = torch.zeros(S + 1, dtype=torch.int64, device=device)
     ipn[1:] = torch.cumsum(sizes, 0)
     n = int(ipn[-1])
-    col = torch.repeat_interleave(torch.arange(S, device="cuda"), sizes)
-    key, _ = torch.sort(col * E + torch.randint(0, E, (n,), generator=g, device="cuda"))
+    col = torch.repeat_interleave(torch.arange(S, device=device), sizes)
+    key, _ = torch.sort(col * E + torch.randint(0, E, (n,), generator=g, device=device))
     ixn = key - col * E
-    dan = torch.randint(1, 20, (n,), generator=g, device="cuda")
+    dan = torch.randint(1, 20, (n,), generator=g, device=device)
     del key, col, row
     out = [x.to(i32).contiguous() for x in (ipa, ixa, daa, ipn, ixn, dan)]
-    torch.cuda.synchronize()
+    if device == "cuda":
+        torch.cuda.synchronize()
     return out
 
 
