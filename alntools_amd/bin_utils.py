@@ -494,17 +494,25 @@ def cells_report(sname, info, keep=None):
     return "".join(out)
 
 
-def ecquant_cells(ec_filename, out_filename, samples=None, samples_file=None, use_lengths=False, max_iters=1000, tol=1e-6, report=None, device=0):
+def ecquant_cells(ec_filename, out_filename, samples=None, samples_file=None, use_lengths=False, max_iters=1000, tol=1e-6, report=None, device=0,
+                  model=4, groups=None):
     """``alntools ecquant-cells``: one EM abundance estimate per sample (cell) of a multisample ``.bin`` (``ecb.quantify_cells``: every cell
     over its own support, all iterated together on the GPU), written as :func:`cells_table`; ``report``: a second file, :func:`cells_report`.
     ``samples`` / ``samples_file`` name the cells as for ``ecselect`` (:func:`named_samples`; default: all).  ``use_lengths``: every abundance
     is weighted by 1 / its target's length (:func:`length_scale` on the alignment counts of all samples pooled: what ``ecquant -l`` refuses is
-    refused here by the same name).  A failure is logged as ``Error: ...`` and raised again; no file is written then."""
+    refused here by the same name).  ``model`` 1, 2 or 3: one of EMASE's hierarchical models over the genes of the group file ``groups``, run
+    per cell (:func:`gene_ids`, ``ecb.quantify_cells_model``: the sums over a gene run over the cell's own targets); without ``groups`` they
+    are refused by name.  ``model`` 4, the default, is the flat step, and ``groups`` then changes nothing.  A failure is logged as
+    ``Error: ...`` and raised again; no file is written then."""
     import time
     from . import utils
     LOG = utils.get_logger()
     try:
         start_time = time.time()
+        if model not in (1, 2, 3, 4):
+            raise ValueError("model {} is not one of 1, 2, 3, 4".format(model))
+        if model != 4 and groups is None:
+            raise ValueError("model {} needs a group file (-g/--groups)".format(model))
         LOG.info("Loading {}...".format(ec_filename))
         m = ecload(ec_filename)
         keep = named_samples(m, samples, samples_file)
@@ -513,8 +521,15 @@ def ecquant_cells(ec_filename, out_filename, samples=None, samples_file=None, us
         scale = None
         if use_lengths:
             scale = length_scale(m, ecb.count_alignments(*args, device=device)[0])
-        LOG.info("Estimating abundances of {:,} cells...".format(m.num_samples if keep is None else int(keep.sum())))
-        cell_ptr, slot_locus, theta, info = ecb.quantify_cells(*args, cell_keep=keep, scale=scale, max_iters=max_iters, tol=tol, device=device)
+        n_cells = m.num_samples if keep is None else int(keep.sum())
+        if model == 4:
+            LOG.info("Estimating abundances of {:,} cells...".format(n_cells))
+            cell_ptr, slot_locus, theta, info = ecb.quantify_cells(*args, cell_keep=keep, scale=scale, max_iters=max_iters, tol=tol, device=device)
+        else:
+            gene, names = gene_ids(m, groups)
+            LOG.info("Estimating abundances of {:,} cells (model {}, {:,} genes)...".format(n_cells, model, len(names)))
+            cell_ptr, slot_locus, theta, info = ecb.quantify_cells_model(*args, gene=gene, n_genes=len(names), model=model, cell_keep=keep, scale=scale,
+                                                                         max_iters=max_iters, tol=tol, device=device)
         ran = np.ones(m.num_samples, dtype=bool) if keep is None else keep
         LOG.info("slots: {:,}; most iterations: {:,}; explained reads: {:,}; cells not converged: {:,}".format(
             len(slot_locus), int(np.max(info["n_iter"], initial=0)), int(np.sum(info["explained"])), int(np.sum(~np.asarray(info["converged"])[ran]))))

@@ -234,15 +234,20 @@ def ecquant(ec_file, out_file, sample, use_lengths, max_iters, tol, model, group
               help="stop a sample when one step changes less than this share of its reads (default: 1e-6)")
 @click.option('--report', metavar='FILE', default=None, type=click.Path(resolve_path=True, dir_okay=False, writable=True),
               help='write n_iter, delta, explained and converged per sample to this file')
+@click.option('-M', '--model', default='4', type=click.Choice(['1', '2', '3', '4']),
+              help='EMASE model, per sample: 1 gene->allele->isoform, 2 gene->isoform->allele, 3 gene->isoform x allele (each needs -g), 4 flat (default: 4)')
+@click.option('-g', '--groups', metavar='<grp_file>', default=None, type=click.Path(exists=True, resolve_path=True, dir_okay=False),
+              help='group file (gene, transcripts...) for models 1 to 3')
 @click.option('-v', '--verbose', count=True, help='enables verbose mode')
-def ecquant_cells(ec_file, out_file, samples, samples_file, use_lengths, max_iters, tol, report, verbose):
+def ecquant_cells(ec_file, out_file, samples, samples_file, use_lengths, max_iters, tol, report, model, groups, verbose):
     """
     Estimate, for every sample of a binary EC file (ec_file), the abundance of every target it touches by an EM of its own and write them, in
     reads, to a table with one line per sample and target (out_file)
     """
     utils.configure_logging(verbose)
     try:
-        methods.ecquant_cells(ec_file, out_file, list(samples) or None, samples_file, use_lengths, max_iters, tol, report)
+        more = () if model == '4' and groups is None else (int(model), groups)
+        methods.ecquant_cells(ec_file, out_file, list(samples) or None, samples_file, use_lengths, max_iters, tol, report, *more)
     except Exception:
         sys.exit(1)                                                  # (logged as "Error: ..." by bin_utils.ecquant_cells)
 

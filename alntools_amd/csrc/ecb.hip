@@ -4982,6 +4982,8 @@ extern "C" int ecb_count_alignments(int device, uint32_t n_ecs, uint32_t n_loci,
 #include "quant_model.inc"
 // ... and one EM per cell of a multisample N, batched (ecb_cell_support* / ecb_quantify_cells*)
 #include "quant_cells.inc"
+// ... and the hierarchical models per cell (ecb_quantify_cells_model*)
+#include "quant_cells_model.inc"
 
 // ---- ecselect: the reads of one class and the samples that still count enough of them, pulled out of a .bin (ecb_select / ecb_select_device)
 // (AlignmentPropertyMatrix.get_unique_reads / pull_alignments_from, AlignmentPropertyMatrix.py:386-427, and the cell threshold of

@@ -293,6 +293,32 @@ struct QcBufs {
 };
 struct QcKept { DevBuf<> locus, theta; u64 slot0, n_slots; };      // a batch's results until the whole support is known
 
+// The hierarchical models per cell (ecb_quantify_cells_model*, quant_cells_model.inc, included after this file) run on a batch as qc_run
+// set it up: what it hands them (QcView), what they add to the set-up (QcmTabs, the batch's buffers) and their step in place of the E- and
+// M-step kernels.  mdl = nullptr: the flat step, this file's own.
+struct QcModel { u32 model, n_genes; const int* gene; };
+struct QcView {
+    hipStream_t st;
+    u32 j0, n_ent, nc, n_x, n_slots, n_haps, hp, nlr, nlc, nq;
+    const int* data_n;
+    const u32 *done, *ent_cell, *off, *long_rows, *x_ent, *x_mask, *row_slot, *col_mask, *slot_ptr, *slot_locus, *slot_cell, *long_cols, *cell_slot0,
+        *chunk_cell, *chunk_ptr;
+    u32 *flag, *pos;                 // free once the slots stand: the set-up's scans
+    const double* scale;
+    double *theta, *phi, *acc_long, *partial;
+    uint8_t* expl;
+};
+struct QcmTabs {
+    u32 n_groups, n_segs, n_long_groups;
+    u32 *slot_group, *gptr, *gmem, *group_cell, *long_groups;          // the (cell, gene) groups: every slot's, and their members as a CSR
+    u32 *segid, *seg_start, *seg_group, *seg_cell, *gx, *x_seg;        // the (entry, group) segments of the rows, over the gene-ordered view
+    u32 *x_b0, *col_b0;                                                // where the coefficients of a non-zero start: row view, column view
+    double *phi_gh, *phi_g, *phi_t, *seg_c, *seg_x, *coef;
+};
+u64 qcm_x_bytes(u32 n_haps);
+int qcm_setup(Call& c, QcBufs& q, const QcView& v, const QcModel& mdl, SortBufs& s, const SortScratch& ss, u32* sums, QcmTabs& t);
+void qcm_step(const QcView& v, const QcmTabs& t, u32 model);
+
 int qc_check_args(uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, uint64_t nnz_a, const void* indptr_a, const void* indices_a, const void* data_a,
                   uint32_t n_samples, uint64_t nnz_n, const void* indptr_n, const void* indices_n, const void* data_n, const char* what) {
     // (no sample is no refusal here: there is then nothing to quantify)
@@ -306,7 +332,7 @@ int qc_check_args(uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, uint64_t nnz
 int qc_run(bool quant, int device, u32 n_ecs, u32 n_loci, u32 n_haps, u64 nnz, const void* d_indptr_a, const void* d_indices_a, const void* d_data_a,
            u32 n_samples, u64 nnz_n, const void* d_indptr_n, const void* d_indices_n, const void* d_data_n, const void* d_cell_keep, const void* d_scale,
            const void* d_theta_in, u32 max_iters, double tol, u64 budget_bytes, u64 n_slots_in, void* d_cell_ptr, void* d_slot_locus, void* d_theta,
-           void* d_n_iter, void* d_delta, void* d_explained, void* d_converged, uint64_t* n_slots_out) {
+           void* d_n_iter, void* d_delta, void* d_explained, void* d_converged, uint64_t* n_slots_out, const QcModel* mdl = nullptr) {
     const char* what = quant ? "ecquant-cells" : "cell-support";
     Call c(device, quant ? "ecquant-cells: " : "cell-support: "); if (c.rc) return c.rc;
     hipStream_t st = c.st;
@@ -335,12 +361,13 @@ int qc_run(bool quant, int device, u32 n_ecs, u32 n_loci, u32 n_haps, u64 nnz, c
     CALLCHK(c, scan_launch(st, bits, nnz, bits_excl, sums, words + 3, 1, bits_excl + nnz));
     if (tab_scale) k_q_tab<<<nblk(n_tab, TPB), TPB, 0, st>>>((const double*)d_scale, n_loci, n_haps, tab_scale, Q_ERR_SCALE, reinterpret_cast<u32*>(words + 5));
     if (tab_theta) k_q_tab<<<nblk(n_tab, TPB), TPB, 0, st>>>((const double*)d_theta_in, n_loci, n_haps, tab_theta, Q_ERR_THETA, reinterpret_cast<u32*>(words + 5));
+    if (mdl && n_loci) k_qm_gkeys<<<nblk(n_loci, TPB), TPB, 0, st>>>(mdl->gene, n_loci, mdl->n_genes, nullptr, nullptr, reinterpret_cast<u32*>(words + 5));
     CALLCHK(c, hipGetLastError());
     std::vector<u64> back(n_words);
     if (const int rc = c.read_back(back.data(), words, n_words, GM_ERRS)) return rc;
     RCCHK(ca_refuse_input(back));
     if (back[3] >= (1ull << 32)) return fail(nullptr, ECB_ERR_LIMIT, "more than 2^32-1 set haplotype bits");
-    RCCHK(refuse_bits(nullptr, Q_ERRS, (u32)back[5]));
+    RCCHK(refuse_bits(nullptr, QM_ERRS, (u32)back[5]));                // (Q_ERRS and the gene ids' bit, which the flat step never sets)
     // the input is well formed.  The cells' sizes, and from them the batches
     std::vector<u64> hx(S);
     if (S) {
@@ -358,7 +385,8 @@ int qc_run(bool quant, int device, u32 n_ecs, u32 n_loci, u32 n_haps, u64 nnz, c
         CALLCHK(c, hipMemGetInfo(&fr, &tot));
         budget_bytes = std::max<u64>(fr / 2, 1);
     }
-    const u64 x_limit = std::min<u64>((1ull << 30) - 1, std::max<u64>(1, budget_bytes / (QC_X_BYTES + QC_SLOT_TABLES * 8 * n_haps)));
+    u64 x_limit = std::min<u64>((1ull << 30) - 1, std::max<u64>(1, budget_bytes / (QC_X_BYTES + QC_SLOT_TABLES * 8 * n_haps + (mdl ? qcm_x_bytes(n_haps) : 0))));
+    if (mdl) x_limit = std::min<u64>(x_limit, ((1ull << 32) - 1) / std::max<u32>(n_haps, 1u));          // (a batch's coefficients, one per set bit, are indexed in 32 bits)
     struct Batch { u32 c0, c1; u64 x; };
     std::vector<Batch> batches;
     u64 max_x = 0, max_ent = 0, max_cells = 0;
@@ -435,6 +463,10 @@ int qc_run(bool quant, int device, u32 n_ecs, u32 n_loci, u32 n_haps, u64 nnz, c
             u32* chunk_cell = q.get<u32>(nq);
             uint8_t* expl = q.get<uint8_t>(n_ent);
             if (q.short_of) return fail(nullptr, ECB_ERR_HIP, "%sout of device memory", c.prefix);
+            const QcView view{st, j0, n_ent, nc, n_x, n_slots, n_haps, hp, nlr, nlc, nq, dn, done, ent_cell, off, long_rows, x_ent, x_mask, row_slot, col_mask,
+                              slot_ptr, slot_locus, slot_cell, long_cols, cell_slot0, chunk_cell, chunk_ptr, flag, pos, scale, theta, phi, acc_long, partial, expl};
+            QcmTabs mt{};
+            if (mdl) RCCHK(qcm_setup(c, q, view, *mdl, s, ss, sums, mt));          // (before anything else sorts: it reads the column view's order)
             k_qc_chunks<<<nblk(nq, TPB), TPB, 0, st>>>(chunk_ptr, nc, nq, chunk_cell);
             if (tab_scale || tab_theta) k_qc_tabs<<<nblk(n_items, TPB), TPB, 0, st>>>(slot_locus, n_items, n_haps, tab_scale, tab_theta, scale, theta, phi);
             if (!tab_theta) {
@@ -446,11 +478,14 @@ int qc_run(bool quant, int device, u32 n_ecs, u32 n_loci, u32 n_haps, u64 nnz, c
             u32 running = q0.running;
             for (u32 queued = 0; running && queued < max_iters;) {
                 for (u32 k = 0; k < Q_BATCH && queued < max_iters; ++k, ++queued) {
-                    if (nlr) k_qc_elong<<<nlr, TPB, 0, st>>>(done, ent_cell, long_rows, off, row_slot, x_mask, dn, j0, phi, n_haps, r, expl);
-                    k_qc_estep<<<n_eblk, TPB, 0, st>>>(done, ent_cell, off, n_ent, row_slot, x_mask, dn, j0, phi, n_haps, r, expl);
-                    if (nlc) k_qc_mlong<false><<<nlc, TPB, 0, st>>>(done, slot_cell, long_cols, slot_ptr, col_ent, col_mask, r, dn, j0, n_haps, hp, acc_long);
-                    k_qc_mstep<false><<<nq, TPB, 0, st>>>(done, chunk_cell, chunk_ptr, cell_slot0, slot_ptr, col_ent, col_mask, r, dn, j0, acc_long, scale,
-                                                          n_haps, theta, phi, partial);
+                    if (mdl) qcm_step(view, mt, mdl->model);
+                    else {
+                        if (nlr) k_qc_elong<<<nlr, TPB, 0, st>>>(done, ent_cell, long_rows, off, row_slot, x_mask, dn, j0, phi, n_haps, r, expl);
+                        k_qc_estep<<<n_eblk, TPB, 0, st>>>(done, ent_cell, off, n_ent, row_slot, x_mask, dn, j0, phi, n_haps, r, expl);
+                        if (nlc) k_qc_mlong<false><<<nlc, TPB, 0, st>>>(done, slot_cell, long_cols, slot_ptr, col_ent, col_mask, r, dn, j0, n_haps, hp, acc_long);
+                        k_qc_mstep<false><<<nq, TPB, 0, st>>>(done, chunk_cell, chunk_ptr, cell_slot0, slot_ptr, col_ent, col_mask, r, dn, j0, acc_long, scale,
+                                                              n_haps, theta, phi, partial);
+                    }
                     k_qc_conv<<<nc, TPB, 0, st>>>(done, chunk_ptr, partial, pn, dn, j0, b.c0, expl, len, stop, max_iters, qs, it, dl, ex, cv);
                 }
                 CALLCHK(c, hipGetLastError());

@@ -50,6 +50,8 @@ QUANT_SYMBOLS = ("ecb_quantify_device", "ecb_quantify")
 QUANT_MODEL_SYMBOLS = ("ecb_quantify_model_device", "ecb_quantify_model")
 #: every symbol include/ecb_quant_cells.h declares (ecb_quant.h includes it)
 QUANT_CELLS_SYMBOLS = ("ecb_cell_support_device", "ecb_cell_support", "ecb_quantify_cells_device", "ecb_quantify_cells")
+#: every symbol include/ecb_quant_cells_model.h declares (ecb_quant.h includes it)
+QUANT_CELLS_MODEL_SYMBOLS = ("ecb_quantify_cells_model_device", "ecb_quantify_cells_model")
 #: ``ecb_select``'s row classes (include/ecb_select.h)
 ROW_CLASSES = {None: 0, "all": 0, "unique": 1, "locus-unique": 2, "multi": 3}
 ABI_VERSION = 4            # include/ecb.h: ECB_ABI_VERSION
@@ -204,6 +206,10 @@ def load():
             f.argtypes = head + [vp, vp, u64, C.POINTER(u64)]
         for f in (lib.ecb_quantify_cells_device, lib.ecb_quantify_cells):
             f.argtypes = head + [vp, vp, C.c_uint32, C.c_double, u64, u64] + [vp] * 7
+    if not ab or hasattr(lib, "ecb_quantify_cells_model"):
+        for f in (lib.ecb_quantify_cells_model_device, lib.ecb_quantify_cells_model):
+            f.argtypes = ([C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.c_uint32, u64, vp, vp, vp, vp]
+                          + [vp, vp, C.c_uint32, C.c_double, u64, C.c_uint32, vp, C.c_uint32, u64] + [vp] * 7)
     lib.ecb_csr_to_hapcsc_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.POINTER(u64)]
     lib.ecb_hapcsc_to_csr_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, u64, vp, vp, vp, C.POINTER(u64)]
     _lib = lib
@@ -543,6 +549,47 @@ def quantify_cells(indptr, indices, data, n_loci, n_haps, indptr_n, indices_n, d
     it, dl, ex, cv = new(S, u32), new(S, f64), new(S, i64), new(S, u8)
     _check(lib, fn(d, E, n_loci, n_haps, nnz, p(ip), p(ix), p(da), S, nnz_n, p(pn), p(xn), p(dn), p(keep), p(tabs[0]), p(tabs[1]), int(max_iters),
                    float(tol), int(budget_bytes), n_slots, p(cell_ptr), p(slot_locus), p(theta), p(it), p(dl), p(ex), p(cv)))
+    if tensors:
+        it = it.to(torch.int64).bitwise_and(0xFFFFFFFF)                  # (the uint32 the library wrote, in a type torch computes with)
+    return cell_ptr, slot_locus, theta, {"n_iter": it, "delta": dl, "explained": ex, "converged": cv != 0}
+
+
+def quantify_cells_model(indptr, indices, data, n_loci, n_haps, indptr_n, indices_n, data_n, gene, n_genes, model, cell_keep=None, scale=None,
+                         theta_in=None, max_iters=1000, tol=1e-6, budget_bytes=0, device=0, n_slots=None):
+    """ecquant per cell with one of EMASE's models over a gene grouping (``ecb_quantify_cells_model`` / ``ecb_quantify_cells_model_device``):
+    :func:`quantify_cells` with ``gene`` (int32 ``[T]``, ``gene[t]`` in ``[0, n_genes)``) and ``model`` as :func:`quantify_model` numbers them;
+    model 4 returns the bytes of :func:`quantify_cells`.  Every cell is a problem of its own: the sums over a gene run over the cell's support
+    only, so a member the cell does not touch contributes nothing, whatever ``theta_in`` holds there.  Everything else, the kinds of the
+    arrays and the result as for :func:`quantify_cells`.  A gene id outside ``[0, n_genes)`` raises :class:`EcbError` (``ECB_ERR_CONTRACT``),
+    a model outside 1..4 ``ECB_ERR_ARG``."""
+    lib = load()
+    tensors, dev, (ip, ix, da, pn, xn, dn, keep), (E, nnz, S, nnz_n) = _cells_args(indptr, indices, data, indptr_n, indices_n, data_n, cell_keep)
+    if tensors:
+        import torch
+        tabs = [None if t is None else t.to(device=dev, dtype=torch.float64).contiguous() for t in (scale, theta_in)]
+        gn = torch.as_tensor(gene).to(device=dev, dtype=torch.int32).contiguous()
+    else:
+        tabs = [None if t is None else np.ascontiguousarray(t, dtype=np.float64) for t in (scale, theta_in)]
+        gn = np.ascontiguousarray(gene, dtype=np.int32)
+    if any(t is not None and tuple(t.shape) != (n_haps, n_loci) for t in tabs):
+        raise ValueError("scale and theta_in are [n_haps, n_loci]")
+    if tuple(gn.shape) != (n_loci,):
+        raise ValueError("gene is [n_loci]")
+    if n_slots is None:
+        n_slots = int(cell_support(ip, ix, da, n_loci, n_haps, pn, xn, dn, keep, device, count_only=True)[0][-1])
+    if tensors:
+        fn, p, d = lib.ecb_quantify_cells_model_device, _dev_ptr, dev.index or 0
+        new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)  # noqa: E731
+        i64, i32, u32, f64, u8 = torch.int64, torch.int32, torch.int32, torch.float64, torch.uint8
+    else:
+        fn, p, d = lib.ecb_quantify_cells_model, _ptr, device
+        new = lambda shape, dt: np.empty(shape, dtype=dt)                 # noqa: E731
+        i64, i32, u32, f64, u8 = np.int64, np.int32, np.uint32, np.float64, np.uint8
+    cell_ptr, slot_locus, theta = new(S + 1, i64), new(n_slots, i32), new((n_slots, n_haps), f64)
+    it, dl, ex, cv = new(S, u32), new(S, f64), new(S, i64), new(S, u8)
+    _check(lib, fn(d, E, n_loci, n_haps, nnz, p(ip), p(ix), p(da), S, nnz_n, p(pn), p(xn), p(dn), p(keep), p(tabs[0]), p(tabs[1]), int(max_iters),
+                   float(tol), int(budget_bytes), int(n_genes), p(gn), int(model), n_slots, p(cell_ptr), p(slot_locus), p(theta), p(it), p(dl), p(ex),
+                   p(cv)))
     if tensors:
         it = it.to(torch.int64).bitwise_and(0xFFFFFFFF)                  # (the uint32 the library wrote, in a type torch computes with)
     return cell_ptr, slot_locus, theta, {"n_iter": it, "delta": dl, "explained": ex, "converged": cv != 0}

@@ -71,9 +71,9 @@ def ecquant(ec_file, out_file, sample=None, use_lengths=False, max_iters=1000, t
     bin_utils.ecquant(ec_file, out_file, sample=sample, use_lengths=use_lengths, max_iters=max_iters, tol=tol, model=model, groups=groups)
 
 
-def ecquant_cells(ec_file, out_file, samples=None, samples_file=None, use_lengths=False, max_iters=1000, tol=1e-6, report=None):
+def ecquant_cells(ec_file, out_file, samples=None, samples_file=None, use_lengths=False, max_iters=1000, tol=1e-6, report=None, model=4, groups=None):
     bin_utils.ecquant_cells(ec_file, out_file, samples=samples, samples_file=samples_file, use_lengths=use_lengths, max_iters=max_iters, tol=tol,
-                            report=report)
+                            report=report, model=model, groups=groups)
 
 
 def ecdump(ec_file):

@@ -50,5 +50,7 @@ int ecb_quantify(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, u
 #include "ecb_quant_model.h"
 /* ... and one EM per cell of a multisample N, batched, the result sparse (ecb_cell_support* / ecb_quantify_cells*): likewise */
 #include "ecb_quant_cells.h"
+/* ... and the hierarchical models per cell (ecb_quantify_cells_model*): likewise */
+#include "ecb_quant_cells_model.h"
 
 #endif /* ECB_QUANT_H */

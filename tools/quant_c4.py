@@ -9,8 +9,14 @@ over 80 000 targets, 2 haplotypes; 5 000 samples of 10 000 - 30 000 entries of N
                                              the HBM peak; the share of the launched work that fell on cells already done; and the yardstick, the
                                              code as it was: ecb.quantify(sample=c, tol=1e-6) on a seeded sample of 64 cells, scaled by S / 64.
                                              S: the first S samples only (default: all 5 000)
-    python tools/quant_c4.py one [S] [K]     one call of K steps (default 16), tol 0, for a kernel trace of its own
-    python tools/quant_c4.py rehearse        the same path at a toy size on the CPU, the numpy checker standing in for the device: no times
+    python tools/quant_c4.py one [S] [K] [M]  one call of K steps (default 16), tol 0, for a kernel trace of its own; M: model 1, 2 or 3 over the
+                                             gene map of ``models`` (default: the flat step)
+    python tools/quant_c4.py models [S]      profiles/ecquant_cells_models_c4.txt: ``ecb_quantify_cells_model_device`` over a seeded gene map (T / 4
+                                             genes, ids drawn per target, so a gene's members are scattered) -- per model, two cells checked against
+                                             tests/cell_model_checker.py first; then, warm, in one process on one build, the flat cells step and
+                                             every model's: 0 steps (the set-up), 8 and 24 steps, the time per step while every cell still runs
+                                             (24 against 8 steps), and its ratio to the flat step's
+    python tools/quant_c4.py rehearse        the same paths at a toy size on the CPU, the numpy checkers standing in for the device: no times
 """
 import os
 import socket
@@ -125,6 +131,55 @@ def report(a, T, H, S, E, quantify_cells, cell_support, quantify, wall, sample=6
     print("steps of those cells, the batched call against the loop: largest difference %d" % int(np.abs(dn - np.array(its)).max()))
 
 
+def gene_map(T, seed=4):
+    """(gene[t], G): T / 4 genes, every target's drawn with a seed; ids renumbered so that none is empty."""
+    rng = np.random.default_rng(seed)
+    ids, gene = np.unique(rng.integers(0, max(T // 4, 1), size=T), return_inverse=True)
+    return gene.astype(np.int32), len(ids)
+
+
+def report_models(a, T, H, S, quantify_cells, quantify_cells_model, cell_support, wall):
+    ipa, ixa, daa, ipn, ixn, dan = a
+    host = [np.asarray(t.cpu() if hasattr(t, "cpu") else t) for t in a]
+    args = (ipa, ixa, daa, T, H, ipn, ixn, dan)
+    gene, G = gene_map(T)
+    n_slots = int(cell_support(*args)[0][-1])
+    members = np.bincount(gene, minlength=G)
+    print("%d cells, %d entries of N, %d slots (x %d haplotypes); %d genes over %d targets, %d to %d members"
+          % (S, len(host[4]), n_slots, H, G, T, members.min(), members.max()))
+    import cell_model_checker as cm
+    import cell_quant_checker as cq
+    import quant_checker as qchk
+    picks = [0, S - 1]
+    keep = np.zeros(S, dtype=np.uint8)
+    keep[picks] = 1
+    qs = {c: cm.CellGrouping(cq.Cell(host[0], host[1], host[2], T, H, host[3], host[4], host[5], c), gene, G) for c in picks}
+    np_ = lambda v: np.asarray(v.cpu() if hasattr(v, "cpu") else v)      # noqa: E731
+    for model in (1, 2, 3):
+        one = quantify_cells_model(*args, gene=gene, n_genes=G, model=model, cell_keep=keep, max_iters=1, tol=0.0)
+        for c in picks:
+            q = qs[c]
+            ref, ex = q.step(model, q.p.aln())
+            p1, th1 = np_(one[0]), np_(one[2])
+            worst = qchk.agree(q.cell.scatter(th1[p1[c]:p1[c + 1]]), ref, q.tolerance(model))
+            print("model %d, cell %d: one step within %.3g of the checker's (bound %.3g; M %d, R %d), explained %d = %d"
+                  % (model, c, worst, q.tolerance(model), q.M, q.R, int(np_(one[3]["explained"])[c]), ex))
+    print("wall time of the call with its waits, warm, ms (0 steps = the set-up; per step = (24 steps - 8 steps) / 16, medians, every cell running):")
+    runs = [("flat (quantify_cells)", lambda **kw: quantify_cells(*args, n_slots=n_slots, **kw))]
+    runs += [("model %d" % model, lambda model=model, **kw: quantify_cells_model(*args, gene=gene, n_genes=G, model=model, n_slots=n_slots, **kw)) for model in (1, 2, 3)]
+    flat = None
+    for name, call in runs:
+        call(max_iters=8, tol=0.0)                                      # (warm: every kernel of this path loaded, the scratch grown)
+        t0, t8, t24 = (wall(lambda: call(max_iters=k, tol=0.0)) for k in (0, 8, 24))
+        per_step = (np.median(t24) - np.median(t8)) / 16
+        flat = flat or (per_step, float(np.median(t0)))
+        print("  %-22s  0 steps %s" % (name, _fmt(t0)))
+        print("  %-22s  8 steps %s" % ("", _fmt(t8)))
+        print("  %-22s 24 steps %s" % ("", _fmt(t24)))
+        print("  %-22s per step %.2f ms = %.2f x the flat step; set-up %.1f ms = %.2f x the flat set-up"
+              % ("", per_step, per_step / flat[0], np.median(t0), np.median(t0) / flat[1]))
+
+
 def main():
     mode = sys.argv[1]
     import select_c4
@@ -138,6 +193,9 @@ def main():
             return qchk.run(qchk.Problem(*args, sample=sample), **kw)
         report(a, 400, 2, 12, 3000, lambda *x, n_slots=None, **kw: cq.quantify_cells(*x, **kw), lambda *x: cq.quantify_cells(*x, max_iters=0)[:2],
                fake_quantify, _cpu_wall, sample=4)
+        import cell_model_checker as cm
+        report_models(a, 400, 2, 12, lambda *x, n_slots=None, **kw: cq.quantify_cells(*x, **kw), lambda *x, n_slots=None, **kw: cm.quantify_cells_model(*x, **kw),
+                      lambda *x: cq.quantify_cells(*x, max_iters=0)[:2], _cpu_wall)
         return
     import torch
     from alntools_amd import ecb
@@ -149,9 +207,17 @@ def main():
     print("box %s, %s" % (socket.gethostname(), torch.cuda.get_device_name(0)))
     if mode == "one":
         K = int(sys.argv[3]) if len(sys.argv) > 3 else 16
-        r = ecb.quantify_cells(a[0], a[1], a[2], select_c4.T, select_c4.H, a[3], a[4], a[5], max_iters=K, tol=0.0)
+        if len(sys.argv) > 4:
+            gene, G = gene_map(select_c4.T)
+            r = ecb.quantify_cells_model(a[0], a[1], a[2], select_c4.T, select_c4.H, a[3], a[4], a[5], gene=gene, n_genes=G, model=int(sys.argv[4]),
+                                         max_iters=K, tol=0.0)
+        else:
+            r = ecb.quantify_cells(a[0], a[1], a[2], select_c4.T, select_c4.H, a[3], a[4], a[5], max_iters=K, tol=0.0)
         torch.cuda.synchronize()
         print(int(r[0][-1]), "slots")
+        return
+    if mode == "models":
+        report_models(a, select_c4.T, select_c4.H, S, ecb.quantify_cells, ecb.quantify_cells_model, ecb.cell_support, _wall)
         return
     report(a, select_c4.T, select_c4.H, S, select_c4.E, ecb.quantify_cells, ecb.cell_support, ecb.quantify, _wall)
 
