@@ -425,16 +425,22 @@ def gene_ids(m, grp_filename):
     return gene, names
 
 
-def ecquant(ec_filename, out_filename, sample=None, use_lengths=False, max_iters=1000, tol=1e-6, device=0, model=4, groups=None):
+def ecquant(ec_filename, out_filename, sample=None, use_lengths=False, max_iters=1000, tol=1e-6, device=0, model=4, groups=None,
+            posterior_file=None, hapcsc=None):
     """``alntools ecquant``: EM abundance estimates of a ``.bin`` (``ecb.quantify``: the reference's ``multiply`` / ``normalize_reads`` /
     ``sum`` iterated on the GPU), written as a table of ``locus, <haplotypes>, total`` in read units.  A multisample file is quantified over
     all its samples pooled, or over the one named ``sample``.  ``use_lengths``: every abundance is weighted by 1 / its target's length
     (:func:`length_scale`).  ``model`` 1, 2 or 3: one of EMASE's hierarchical models over the genes of the group file ``groups``
     (:func:`gene_ids`, ``ecb.quantify_model``); without ``groups`` they are refused by name.  ``model`` 4, the default, is the flat step, and
-    ``groups`` then changes nothing.  A failure is logged as ``Error: ...`` and raised again; no file is written then."""
+    ``groups`` then changes nothing.  ``posterior_file``: an EMASE ``.h5`` as ``ec2emase`` writes it whose per-haplotype ``data`` is the
+    posterior probability of every alignment at the theta the table holds (``ecb.posterior`` with the run's scale, model and genes, then
+    ``ecb_csr_to_hapcsc_values``), zeros stored, so the file's incidence is the ``.bin``'s (``hapcsc``: tests may pass a factory that takes
+    the values in bit order and returns the conversion ``emase_h5.save`` is to use).  A failure is logged as ``Error: ...`` and raised again; no file is written then: when
+    either file cannot be written, neither is left behind."""
     import time
     from . import ecb, utils
     LOG = utils.get_logger()
+    written = []
     try:
         start_time = time.time()
         if model not in (1, 2, 3, 4):
@@ -465,10 +471,26 @@ def ecquant(ec_filename, out_filename, sample=None, use_lengths=False, max_iters
                                              tol=tol, device=device)
         LOG.info("iterations: {:,}; delta: {!r}; explained reads: {:,}; {}".format(info["n_iter"], info["delta"], info["explained"],
                                                                                   "converged" if info["converged"] else "not converged"))
+        table = quant_table(m.lname, m.hname, theta)
+        if posterior_file is not None:
+            from . import emase_h5
+            LOG.info("Computing the posterior of every alignment...")
+            post = ecb.posterior(m.indptrA, m.indicesA, m.dataA, m.num_loci, m.num_haplotypes, theta, scale=scale, gene=gene,
+                                 n_genes=0 if names is None else len(names), model=model, device=device)[0]
+            convert = hapcsc(post) if hapcsc is not None else emase_h5.device_hapcsc_values(post, device)
+            with open(posterior_file, 'wb'):           # (created or truncated: from here on the file is this run's, and goes if the run fails)
+                written.append(posterior_file)
+            emase_h5.save(posterior_file, m, title='Posterior from {}'.format(ec_filename), incidence_only=False, hapcsc=convert)
         with open(out_filename, 'w') as fh:
-            fh.write(quant_table(m.lname, m.hname, theta))
+            written.append(out_filename)
+            fh.write(table)
         LOG.info("{} created in total time: {}".format(out_filename, utils.format_time(start_time, time.time())))
     except Exception as e:
+        for f in written:                      # (a file that could not be finished, and the one written before it; never one this run did not open)
+            try:
+                os.remove(f)
+            except OSError:
+                pass
         LOG.error("Error: {}".format(e.args[0] if isinstance(e, KeyError) and e.args else str(e)))
         raise
 

@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
 """Command line with the reference's hot-path sub-commands and options (``alntools/cli.py:43-113``):
-``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``, ``apply-genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``count-alignments``, ``ecquant``, ``ecquant-cells``, ``ecdump``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
+``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``, ``apply-genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``count-alignments``, ``ecquant`` (``-w``: the posterior of every alignment too), ``ecquant-cells``, ``ecdump``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
 from __future__ import annotations
 
 import glob
@@ -209,15 +209,18 @@ def count_alignments(ec_file, out_file, sample, verbose):
               help='EMASE model: 1 gene->allele->isoform, 2 gene->isoform->allele, 3 gene->isoform x allele (each needs -g), 4 flat (default: 4)')
 @click.option('-g', '--groups', metavar='<grp_file>', default=None, type=click.Path(exists=True, resolve_path=True, dir_okay=False),
               help='group file (gene, transcripts...) for models 1 to 3')
+@click.option('-w', '--posterior', 'posterior', metavar='<h5_file>', default=None, type=click.Path(resolve_path=True, dir_okay=False, writable=True),
+              help='also write the posterior probability of every alignment at the estimate, as an EMASE file')
 @click.option('-v', '--verbose', count=True, help='enables verbose mode')
-def ecquant(ec_file, out_file, sample, use_lengths, max_iters, tol, model, groups, verbose):
+def ecquant(ec_file, out_file, sample, use_lengths, max_iters, tol, model, groups, posterior, verbose):
     """
     Estimate the abundance of every target and haplotype of a binary EC file (ec_file) by EM and write them, in reads, to a table (out_file)
     """
     utils.configure_logging(verbose)
     try:
         more = () if model == '4' and groups is None else (int(model), groups)
-        methods.ecquant(ec_file, out_file, sample, use_lengths, max_iters, tol, *more)
+        named = {} if posterior is None else {"posterior_file": posterior}
+        methods.ecquant(ec_file, out_file, sample, use_lengths, max_iters, tol, *more, **named)
     except Exception:
         sys.exit(1)                                                  # (logged as "Error: ..." by bin_utils.ecquant)
 

@@ -1922,8 +1922,12 @@ __global__ __launch_bounds__(TPB) void k_cv_cnt(const u32* masks, u64 nnz, u32 n
 }
 // scan[h * nb + b]: set bits of haplotype h before block b, counted on from the haplotypes before it -- the place of the block's
 // first such bit in the row-index array.  headval[h * n_loci + t]: where column t of haplotype h starts within h's own block.
+// VAL: a payload goes along -- base[i]: where the values of sorted non-zero i start in `values` (bit order: its set bits lowest first);
+// the value of bit h lands in cscdata where its row index lands in cscidx
+template <bool VAL>
 __global__ __launch_bounds__(TPB) void k_cv_emit(const u64* keys, const u32* masks, u64 nnz, u32 n_haps, u32 n_loci, u32 nb,
-                                                 const u32* scan, int* cscidx, u32* headval) {
+                                                 const u32* scan, int* cscidx, u32* headval, const u32* base, const double* values,
+                                                 double* cscdata) {
     __shared__ u32 run[32], wcnt[TPB / 64][32];
     const u32 tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
     if (tid < 32) run[tid] = tid < n_haps ? scan[(u64)tid * nb + blockIdx.x] : 0u;
@@ -1945,7 +1949,10 @@ __global__ __launch_bounds__(TPB) void k_cv_emit(const u64* keys, const u32* mas
             const u64 bm = __ballot((m >> h) & 1u);
             u32 at = run[h] + (u32)__popcll(bm & lt);
             for (u32 k = 0; k < w; ++k) at += wcnt[k][h];
-            if ((m >> h) & 1u) cscidx[at] = (int)(u32)key;
+            if ((m >> h) & 1u) {
+                cscidx[at] = (int)(u32)key;
+                if (VAL) cscdata[at] = values[base[i] + (u32)__popc(m & ((1u << h) - 1u))];
+            }
             if (head) headval[(u64)h * n_loci + lc] = at - scan[(u64)h * nb];
         }
         __syncthreads();
@@ -1963,6 +1970,19 @@ __global__ void k_cv_ptr(const u64* keys, u64 nnz, u32 n_loci, u32 n_haps, u32 n
         const u32 tot = (h + 1 < n_haps ? scan[(u64)(h + 1) * nb] : (u32)*grand) - scan[(u64)h * nb];
         cscptr[(u64)h * (n_loci + 1) + t] = (int)(at < nnz ? headval[(u64)h * n_loci + t2] : tot);
     }
+}
+
+// the payload's twin of the sort's value: sorted non-zero p is non-zero idx[p] of the CSR -- its mask, and where its values start
+__global__ __launch_bounds__(TPB) void k_cvv_bits(const int* data, u64 nnz, u32* bits) {
+    const u64 i = blockIdx.x * (u64)TPB + threadIdx.x;
+    if (i < nnz) bits[i] = (u32)__popc((u32)data[i]);
+}
+__global__ __launch_bounds__(TPB) void k_cvv_gather(const u32* idx, const int* data, const u32* bits_excl, u64 nnz, u32* masks, u32* base) {
+    const u64 p = blockIdx.x * (u64)TPB + threadIdx.x;
+    if (p >= nnz) return;
+    const u32 i = idx[p];
+    masks[p] = (u32)data[i];
+    base[p] = bits_excl[i];
 }
 
 __global__ void k_iota(u32* out, u64 n) {
@@ -4359,9 +4379,10 @@ extern "C" int ecb_release_scratch(int device) {
     return ECB_OK;
 }
 
-extern "C" int ecb_csr_to_hapcsc_device(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, const void* d_indptr,
-                                        const void* d_indices, const void* d_data, void* d_cscptr, void* d_cscidx,
-                                        uint64_t* total) {
+namespace {
+// both conversions CSR -> per-haplotype CSC: d_values / d_cscdata null = the incidence alone
+int csr_to_hapcsc_any(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, const void* d_indptr, const void* d_indices, const void* d_data,
+                      const void* d_values, void* d_cscptr, void* d_cscidx, void* d_cscdata, bool payload, uint64_t* total) {
     if (!d_indptr || !total || !n_ecs || !n_loci || !n_haps || n_haps > 31) return fail(nullptr, ECB_ERR_ARG, "bad argument");
     if ((u64)n_haps * n_loci >= (1ull << 32)) return fail(nullptr, ECB_ERR_LIMIT, "haplotypes x loci does not fit 32 bits");
     Call c(device, ""); if (c.rc) return c.rc;
@@ -4373,7 +4394,7 @@ extern "C" int ecb_csr_to_hapcsc_device(int device, uint32_t n_ecs, uint32_t n_l
     if (nnz && (!d_indices || !d_data)) return fail(nullptr, ECB_ERR_ARG, "bad argument");       // (a matrix without non-zeros has no arrays to point at)
     u64* words = c.get<u64>(CV_WORDS, 4);                          // [0] set bits, [1] the scan's total, [2] error bits
     if (const int rc = c.missing()) return rc;
-    if (!d_cscidx || !d_cscptr) {                                  // the first call: how many row indices there will be
+    if (!d_cscidx || !d_cscptr || (payload && !d_cscdata)) {       // the first call: how many row indices there will be
         u64 tot = 0;
         CALLCHK(c, hipMemsetAsync(words, 0, 8, st));
         if (nnz) k_cv_bits<<<(unsigned)std::min<u64>(2048, nblk(nnz, TPB)), TPB, 0, st>>>((const int*)d_data, nnz, words);
@@ -4393,15 +4414,29 @@ extern "C" int ecb_csr_to_hapcsc_device(int device, uint32_t n_ecs, uint32_t n_l
     u32 *v0 = c.get<u32>(CV_VALS0, nnz), *v1 = c.get<u32>(CV_VALS1, nnz);
     SortScratch ss{c.get<u32>(CV_HIST, rs_words(nnz)), c.get<u32>(CV_OFFS, RS_AUX_WORDS), words + 3};
     u32 *blk = c.get<u32>(CV_BLK, (u64)n_haps * nb), *scan = c.get<u32>(CV_SCAN, (u64)n_haps * nb);
-    u32 *sums2 = c.get<u32>(CV_SUMS2, scan_words((u64)n_haps * nb) + 2), *headval = c.get<u32>(CV_HEAD, (u64)n_haps * n_loci);
+    u32 *sums2 = c.get<u32>(CV_SUMS2, scan_words(std::max<u64>((u64)n_haps * nb, payload ? nnz + 1 : 0)) + 2);
+    u32* headval = c.get<u32>(CV_HEAD, (u64)n_haps * n_loci);
+    u32 *bits = nullptr, *bits_excl = nullptr, *base = nullptr;
+    if (payload) { bits = c.get<u32>(CV_X0, nnz); bits_excl = c.get<u32>(CV_X1, nnz + 1); base = c.get<u32>(CV_X2, nnz); }
     if (const int rc = c.missing()) return rc;
     CALLCHK(c, hipMemsetAsync(words, 0, 24, st));
     k_cv_keys<<<nblk(n_ecs, TPB), TPB, 0, st>>>((const int*)d_indptr, n_ecs, (const int*)d_indices, (const int*)d_data, nnz, n_loci, n_haps,
                                                k0, v0, reinterpret_cast<u32*>(words + 2));
+    if (payload) {
+        // the sort carries the non-zero's index in place of its mask; where each non-zero's values start: the scan of the popcounts
+        k_iota<<<nblk(nnz, TPB), TPB, 0, st>>>(v0, nnz);
+        k_cvv_bits<<<nblk(nnz, TPB), TPB, 0, st>>>((const int*)d_data, nnz, bits);
+        CALLCHK(c, scan_launch(st, bits, nnz, bits_excl, sums2, nullptr, 1, bits_excl + nnz));
+    }
     SortBufs s{{k0, k1}, {v0, v1}};
     // stable sort on the locus alone: ECs stay ascending within a column, as scipy's tocsc() leaves them
     CALLCHK(c, radix_sort_pairs64(st, s, nnz, ss, msb_mask(n_loci - 1) << 32));
     const u64* keys = s.keys(); const u32* masks = s.vals();
+    if (payload) {
+        u32* m2 = s.vals() == v0 ? v1 : v0;                         // (the sort's other value buffer is free now)
+        k_cvv_gather<<<nblk(nnz, TPB), TPB, 0, st>>>(s.vals(), (const int*)d_data, bits_excl, nnz, m2, base);
+        masks = m2;
+    }
     k_cv_cnt<<<nb, TPB, 0, st>>>(masks, nnz, n_haps, nb, blk);
     CALLCHK(c, scan_launch(st, blk, (u64)n_haps * nb, scan, sums2, words + 1));
     u64 back[3] = {0, 0, 0};
@@ -4409,10 +4444,27 @@ extern "C" int ecb_csr_to_hapcsc_device(int device, uint32_t n_ecs, uint32_t n_l
     if (const int rc = refuse_bits(nullptr, CV_ERRS, (u32)back[2])) return rc;
     if (back[1] >= (1ull << 32)) return fail(nullptr, ECB_ERR_LIMIT, "more than 2^32-1 set haplotype bits");
     *total = back[1];
-    k_cv_emit<<<nb, TPB, 0, st>>>(keys, masks, nnz, n_haps, n_loci, nb, scan, (int*)d_cscidx, headval);
+    if (payload && back[1] && !d_values) return fail(nullptr, ECB_ERR_ARG, "bad argument");
+    if (payload)
+        k_cv_emit<true><<<nb, TPB, 0, st>>>(keys, masks, nnz, n_haps, n_loci, nb, scan, (int*)d_cscidx, headval, base, (const double*)d_values,
+                                            (double*)d_cscdata);
+    else k_cv_emit<false><<<nb, TPB, 0, st>>>(keys, masks, nnz, n_haps, n_loci, nb, scan, (int*)d_cscidx, headval, nullptr, nullptr, nullptr);
     k_cv_ptr<<<nblk((u64)n_loci + 1, TPB), TPB, 0, st>>>(keys, nnz, n_loci, n_haps, nb, scan, words + 1, headval, (int*)d_cscptr);
     CALLCHK(c, hipStreamSynchronize(st));
     return ECB_OK;
+}
+}  // namespace
+
+extern "C" int ecb_csr_to_hapcsc_device(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, const void* d_indptr,
+                                        const void* d_indices, const void* d_data, void* d_cscptr, void* d_cscidx,
+                                        uint64_t* total) {
+    return csr_to_hapcsc_any(device, n_ecs, n_loci, n_haps, d_indptr, d_indices, d_data, nullptr, d_cscptr, d_cscidx, nullptr, false, total);
+}
+
+extern "C" int ecb_csr_to_hapcsc_values_device(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, const void* d_indptr,
+                                               const void* d_indices, const void* d_data, const void* d_values, void* d_cscptr,
+                                               void* d_cscidx, void* d_cscdata, uint64_t* total) {
+    return csr_to_hapcsc_any(device, n_ecs, n_loci, n_haps, d_indptr, d_indices, d_data, d_values, d_cscptr, d_cscidx, d_cscdata, true, total);
 }
 
 extern "C" int ecb_hapcsc_to_csr_device(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, const void* d_cscptr,
@@ -4526,6 +4578,31 @@ extern "C" int ecb_csr_to_hapcsc(int device, uint32_t n_ecs, uint32_t n_loci, ui
     if (need > capacity) return fail(nullptr, ECB_ERR_ARG, "csc_indices holds %llu entries, the matrix has %llu set bits", (unsigned long long)capacity, (unsigned long long)need);
     RCCHK(ecb_csr_to_hapcsc_device(device, n_ecs, n_loci, n_haps, ip.p, ix.p, da.p, cp.p, ci.p, total));
     return stage_out(c, {{csc_indptr, &cp, nc * 4}, {csc_indices, &ci, *total * 4}});
+}
+
+extern "C" int ecb_csr_to_hapcsc_values(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, const int32_t* indptr, const int32_t* indices,
+                                        const int32_t* data, const double* values, int32_t* csc_indptr, int32_t* csc_indices, double* csc_data,
+                                        uint64_t capacity, uint64_t* total) {
+    if (!csc_indices || !csc_indptr || !csc_data)       // the count alone, as ecb_csr_to_hapcsc gives it
+        return ecb_csr_to_hapcsc(device, n_ecs, n_loci, n_haps, indptr, indices, data, nullptr, nullptr, 0, total);
+    if (!indptr || !total || !n_ecs || !n_loci || !n_haps || n_haps > 31) return fail(nullptr, ECB_ERR_ARG, "bad argument");
+    Call c(device, ""); if (c.rc) return c.rc;
+    if (indptr[n_ecs] < 0) return fail(nullptr, ECB_ERR_CONTRACT, "malformed CSR: negative row pointer");
+    const u64 nnz = (u64)indptr[n_ecs];
+    if (nnz && (!indices || !data)) return fail(nullptr, ECB_ERR_ARG, "bad argument");
+    // the count first, on the host as ecb_csr_to_hapcsc takes it: nothing is allocated for a capacity the matrix does not need
+    u64 need = 0;
+    for (u64 i = 0; i < nnz; ++i) need += (u64)__builtin_popcount((unsigned)data[i]);
+    if (need >= (1ull << 32)) return fail(nullptr, ECB_ERR_LIMIT, "more than 2^32-1 set haplotype bits");
+    *total = need;
+    if (need > capacity) return fail(nullptr, ECB_ERR_ARG, "csc_indices holds %llu entries, the matrix has %llu set bits", (unsigned long long)capacity, (unsigned long long)need);
+    if (need && !values) return fail(nullptr, ECB_ERR_ARG, "bad argument");
+    DevBuf<> ip, ix, da, va, cp, ci, cd;
+    const u64 nc = (u64)n_haps * (n_loci + 1);
+    RCCHK(stage_in(c, {{&ip, indptr, ((u64)n_ecs + 1) * 4}, {&ix, indices, nnz * 4}, {&da, data, nnz * 4}, {&va, values, need * 8}, {&cp, nullptr, nc * 4},
+                       {&ci, nullptr, need * 4}, {&cd, nullptr, need * 8}}));
+    RCCHK(ecb_csr_to_hapcsc_values_device(device, n_ecs, n_loci, n_haps, ip.p, ix.p, da.p, va.p, cp.p, ci.p, cd.p, total));
+    return stage_out(c, {{csc_indptr, &cp, nc * 4}, {csc_indices, &ci, *total * 4}, {csc_data, &cd, *total * 8}});
 }
 
 extern "C" int ecb_hapcsc_to_csr(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, const int32_t* csc_indptr, const int32_t* csc_indices,
@@ -4984,6 +5061,8 @@ extern "C" int ecb_count_alignments(int device, uint32_t n_ecs, uint32_t n_loci,
 #include "quant_cells.inc"
 // ... and the hierarchical models per cell (ecb_quantify_cells_model*)
 #include "quant_cells_model.inc"
+// ... and the posterior of every alignment at a given theta (ecb_posterior*)
+#include "quant_post.inc"
 
 // ---- ecselect: the reads of one class and the samples that still count enough of them, pulled out of a .bin (ecb_select / ecb_select_device)
 // (AlignmentPropertyMatrix.get_unique_reads / pull_alignments_from, AlignmentPropertyMatrix.py:386-427, and the cell threshold of

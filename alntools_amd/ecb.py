@@ -52,6 +52,8 @@ QUANT_MODEL_SYMBOLS = ("ecb_quantify_model_device", "ecb_quantify_model")
 QUANT_CELLS_SYMBOLS = ("ecb_cell_support_device", "ecb_cell_support", "ecb_quantify_cells_device", "ecb_quantify_cells")
 #: every symbol include/ecb_quant_cells_model.h declares (ecb_quant.h includes it)
 QUANT_CELLS_MODEL_SYMBOLS = ("ecb_quantify_cells_model_device", "ecb_quantify_cells_model")
+#: every symbol include/ecb_quant_post.h declares (ecb_quant.h includes it)
+QUANT_POST_SYMBOLS = ("ecb_posterior_device", "ecb_posterior", "ecb_csr_to_hapcsc_values_device", "ecb_csr_to_hapcsc_values")
 #: ``ecb_select``'s row classes (include/ecb_select.h)
 ROW_CLASSES = {None: 0, "all": 0, "unique": 1, "locus-unique": 2, "multi": 3}
 ABI_VERSION = 4            # include/ecb.h: ECB_ABI_VERSION
@@ -210,6 +212,11 @@ def load():
         for f in (lib.ecb_quantify_cells_model_device, lib.ecb_quantify_cells_model):
             f.argtypes = ([C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.c_uint32, u64, vp, vp, vp, vp]
                           + [vp, vp, C.c_uint32, C.c_double, u64, C.c_uint32, vp, C.c_uint32, u64] + [vp] * 7)
+    if not ab or hasattr(lib, "ecb_posterior"):
+        for f in (lib.ecb_posterior_device, lib.ecb_posterior):
+            f.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64, vp, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, u64, vp, vp, vp]
+        lib.ecb_csr_to_hapcsc_values_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64)]
+        lib.ecb_csr_to_hapcsc_values.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64)]
     lib.ecb_csr_to_hapcsc_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.POINTER(u64)]
     lib.ecb_hapcsc_to_csr_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, u64, vp, vp, vp, C.POINTER(u64)]
     _lib = lib
@@ -277,6 +284,47 @@ def csr_to_hapcsc_host(indptr, indices, data, n_loci, n_haps, device=0):
     cidx = np.empty(max(tot.value, 1), dtype=np.int32)
     _check(lib, lib.ecb_csr_to_hapcsc(device, E, n_loci, n_haps, _ptr(ip), _ptr(ix), _ptr(da), _ptr(cptr), _ptr(cidx), len(cidx), C.byref(tot)))
     return cptr, cidx[:tot.value]
+
+
+def csr_to_hapcsc_values(indptr, indices, data, values, n_loci, n_haps):
+    """:func:`csr_to_hapcsc` with a payload, on device tensors (``ecb_csr_to_hapcsc_values_device``): ``values`` float64, one per set bit of
+    the masks in bit order (the non-zeros in storage order, the set bits of one lowest first: :func:`posterior`'s ``post``) ->
+    (csc_indptr [H, T+1], csc_indices [total], csc_data float64 [total]); ``csc_data[k]`` is the value of the entry ``csc_indices[k]`` names."""
+    import torch
+    lib = load()
+    dev = indptr.device
+    E = indptr.numel() - 1
+    va = values.to(device=dev, dtype=torch.float64).contiguous()
+    tot = C.c_uint64()
+    cptr = torch.empty((n_haps, n_loci + 1), dtype=torch.int32, device=dev)
+    cidx = torch.empty(max(va.numel(), 1), dtype=torch.int32, device=dev)
+    cdat = torch.empty(max(va.numel(), 1), dtype=torch.float64, device=dev)
+    _check(lib, lib.ecb_csr_to_hapcsc_values_device(dev.index or 0, E, n_loci, n_haps, _dev_ptr(indptr), _dev_ptr(indices), _dev_ptr(data), None,
+                                                    None, None, None, C.byref(tot)))
+    if tot.value != va.numel():
+        raise ValueError("values holds %d entries, the matrix has %d set bits" % (va.numel(), tot.value))
+    _check(lib, lib.ecb_csr_to_hapcsc_values_device(dev.index or 0, E, n_loci, n_haps, _dev_ptr(indptr), _dev_ptr(indices), _dev_ptr(data),
+                                                    _dev_ptr(va), _dev_ptr(cptr), _dev_ptr(cidx), _dev_ptr(cdat), C.byref(tot)))
+    return cptr, cidx[:tot.value], cdat[:tot.value]
+
+
+def csr_to_hapcsc_values_host(indptr, indices, data, values, n_loci, n_haps, device=0):
+    """:func:`csr_to_hapcsc_host` with a payload (``ecb_csr_to_hapcsc_values``): ``values`` float64, one per set bit in bit order ->
+    (csc_indptr int32 [H, T+1], csc_indices int32 [total], csc_data float64 [total])."""
+    lib = load()
+    ip, ix, da = (np.ascontiguousarray(a, dtype=np.int32) for a in (indptr, indices, data))
+    va = np.ascontiguousarray(values, dtype=np.float64)
+    E = len(ip) - 1
+    tot = C.c_uint64()
+    _check(lib, lib.ecb_csr_to_hapcsc_values(device, E, n_loci, n_haps, _ptr(ip), _ptr(ix), _ptr(da), None, None, None, None, 0, C.byref(tot)))
+    if tot.value != len(va):
+        raise ValueError("values holds %d entries, the matrix has %d set bits" % (len(va), tot.value))
+    cptr = np.empty((n_haps, n_loci + 1), dtype=np.int32)
+    cidx = np.empty(max(tot.value, 1), dtype=np.int32)
+    cdat = np.empty(max(tot.value, 1), dtype=np.float64)
+    _check(lib, lib.ecb_csr_to_hapcsc_values(device, E, n_loci, n_haps, _ptr(ip), _ptr(ix), _ptr(da), _ptr(va), _ptr(cptr), _ptr(cidx), _ptr(cdat),
+                                             len(cidx), C.byref(tot)))
+    return cptr, cidx[:tot.value], cdat[:tot.value]
 
 
 def hapcsc_to_csr_host(csc_indptr, csc_indices, n_ecs, device=0):
@@ -463,6 +511,54 @@ def quantify_model(indptr, indices, data, n_loci, n_haps, indptr_n, indices_n, d
         _check(lib, lib.ecb_quantify_model(device, E, n_loci, n_haps, nnz, _ptr(ip), _ptr(ix), _ptr(da), S, nnz_n, _ptr(pn), _ptr(xn), _ptr(dn), s,
                                            _ptr(tabs[0]), _ptr(tabs[1]), tail[0], tail[1], tail[2], _ptr(gn), int(model), _ptr(theta), *outs))
     return theta, {"n_iter": it.value, "delta": dl.value, "explained": ex.value, "converged": bool(cv.value)}
+
+
+def posterior(indptr, indices, data, n_loci, n_haps, theta, scale=None, gene=None, n_genes=0, model=4, device=0):
+    """The posterior probability of every alignment at ``theta`` (``ecb_posterior`` / ``ecb_posterior_device``): one value per set bit of CSR
+    A (``.bin``'s bitmask values) -- model 4: ``phi[h, t] / d[e]`` with ``phi = theta * scale``; models 1-3: the factor product of
+    :func:`quantify_model` over ``gene`` -- so that the sum over rows of ``w[e]`` times it is one step of :func:`quantify` /
+    :func:`quantify_model` from ``theta``.  ``theta``, ``scale``: float64 ``[H, T]`` (``scale`` may be None); ``gene`` may be None for model 4.
+    numpy arrays go through the host entry point, CUDA tensors through the device one (``device`` is then the tensors' own).  Returns
+    ``(post float64 [n_bits], bit_ptr int64 [nnz + 1], row_mass float64 [E])`` of the same kind as the input: ``post`` in bit order -- the
+    non-zeros in storage order, the set bits of one lowest first, non-zero i owning ``post[bit_ptr[i]:bit_ptr[i + 1]]`` -- and ``row_mass[e]``
+    the row's normalizing sum, 0 for a row nothing explains (all of it is then 0).  A NaN, infinite or negative entry of ``theta`` or
+    ``scale``, a gene id outside ``[0, n_genes)`` or a malformed A raises :class:`EcbError` (``ECB_ERR_CONTRACT``)."""
+    lib = load()
+    tensors = hasattr(indptr, "data_ptr")
+    if tensors:
+        import torch
+        dev = indptr.device
+        ip, ix, da = (t.contiguous().to(torch.int32) for t in (indptr, indices, data))
+        tabs = [None if t is None else torch.as_tensor(t).to(device=dev, dtype=torch.float64).contiguous() for t in (scale, theta)]
+        gn = None if gene is None else torch.as_tensor(gene).to(device=dev, dtype=torch.int32).contiguous()
+        E, nnz = ip.numel() - 1, ix.numel()
+        n_bits = 0
+        if E > 0 and nnz and da.numel() == nnz and int(ip[-1]) == nnz:      # (the conversion's count-only call: one pass over the masks it is told of)
+            tot = C.c_uint64()
+            _check(lib, lib.ecb_csr_to_hapcsc_device(dev.index or 0, E, n_loci, n_haps, _dev_ptr(ip), _dev_ptr(ix), _dev_ptr(da), None, None, C.byref(tot)))
+            n_bits = tot.value
+        fn, p, d = lib.ecb_posterior_device, _dev_ptr, dev.index or 0
+        new = lambda n, dt: torch.zeros(n, dtype=dt, device=dev)         # noqa: E731
+        f64, i64 = torch.float64, torch.int64
+    else:
+        ip, ix, da = (np.ascontiguousarray(a, dtype=np.int32) for a in (indptr, indices, data))
+        tabs = [None if t is None else np.ascontiguousarray(t, dtype=np.float64) for t in (scale, theta)]
+        gn = None if gene is None else np.ascontiguousarray(gene, dtype=np.int32)
+        E, nnz = len(ip) - 1, len(ix)
+        n_bits = int(np.unpackbits(da.view(np.uint8)).sum())
+        fn, p, d = lib.ecb_posterior, _ptr, device
+        new = lambda n, dt: np.zeros(n, dtype=dt)                        # noqa: E731
+        f64, i64 = np.float64, np.int64
+    if len(da) != nnz:
+        raise ValueError("indices and data differ in length")
+    if tabs[1] is None or any(t is not None and tuple(t.shape) != (n_haps, n_loci) for t in tabs):
+        raise ValueError("theta and scale are [n_haps, n_loci]")
+    if gn is not None and tuple(gn.shape) != (n_loci,):
+        raise ValueError("gene is [n_loci]")
+    post, bit_ptr, row_mass = new(n_bits, f64), new(nnz + 1, i64), new(E, f64)
+    _check(lib, fn(d, E, n_loci, n_haps, nnz, p(ip), p(ix), p(da), p(tabs[0]), p(tabs[1]), int(n_genes), p(gn), int(model), n_bits,
+                   p(post) if n_bits else None, p(bit_ptr), p(row_mass)))
+    return post, bit_ptr, row_mass
 
 
 def _cells_args(indptr, indices, data, indptr_n, indices_n, data_n, cell_keep):

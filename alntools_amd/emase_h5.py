@@ -36,9 +36,9 @@ def _backend():
 class _Csc(object):
     """indptr / indices / data of one haplotype's E x T incidence matrix, as ``apm.data[h]`` holds them after ``finalize()``."""
 
-    def __init__(self, indptr, indices):
+    def __init__(self, indptr, indices, data=None):
         self.indptr, self.indices = indptr, indices
-        self.data = np.ones(len(indices), dtype=np.float64)
+        self.data = np.ones(len(indices), dtype=np.float64) if data is None else data
 
 
 def _device(device=None):
@@ -60,6 +60,26 @@ def device_hapcsc(m, device=None):
         out.append(_Csc(cptr[h], cidx[start:start + n]))
         start += n
     return out
+
+
+def split_hapcsc(cptr, cidx, cdata=None):
+    """(csc_indptr [H, T+1], csc_indices [total], csc_data [total] or None) as libecb lays them out -> one :class:`_Csc` per haplotype."""
+    out, start = [], 0
+    for h in range(len(cptr)):
+        n = int(cptr[h][-1])
+        out.append(_Csc(cptr[h], cidx[start:start + n], None if cdata is None else cdata[start:start + n]))
+        start += n
+    return out
+
+
+def device_hapcsc_values(values, device=None):
+    """A ``hapcsc`` for :func:`save` whose matrices carry ``values`` -- float64, one per set bit of A in bit order (``ecb.posterior``'s
+    ``post``) -- as their ``data``, transposed on the GPU (``ecb_csr_to_hapcsc_values``): with ``incidence_only=False`` the file then holds
+    the posterior, zeros included, where ``ec2emase`` writes ones.  Indptr and indices are :func:`device_hapcsc`'s."""
+    def convert(m):
+        from . import ecb
+        return split_hapcsc(*ecb.csr_to_hapcsc_values_host(m.indptrA, m.indicesA, m.dataA, values, m.num_loci, m.num_haplotypes, _device(device)))
+    return convert
 
 
 def device_csr(parts, n_ecs, n_loci, device=None):
@@ -210,6 +230,26 @@ def load(h5file, csr=device_csr, device=None):
     a_ptr, a_idx, a_dat = csr(parts, E, T, device) if csr is device_csr else csr(parts, E, T)
     return ECMatrices(hname, lname, lengths, sname, a_ptr, a_idx, np.asarray(a_dat).astype(np.int64),
                       np.asarray(N[0]).astype(np.int64), np.asarray(N[1]).astype(np.int64), np.asarray(N[2]).astype(np.int64))
+
+
+def load_values(h5file):
+    """EMASE ``.h5`` written with ``incidence_only=False`` -> per haplotype ``(indptr, indices, data)`` as the file holds them (uint32,
+    uint32, float64): the values :func:`save` stored, bit for bit."""
+    be = _backend()
+    if be == "tables":
+        import tables
+        with tables.open_file(h5file, 'r') as f:
+            H = int(f.get_node_attr('/', 'shape')[1])
+            return [tuple(f.get_node('/h%d' % h, n).read() for n in ('indptr', 'indices', 'data')) for h in range(H)]
+    if be == "libhdf5":
+        from . import h5lite
+        with h5lite.File(h5file, 'r') as f:
+            H = int(f.get_attr('/', 'shape')[1])
+            return [tuple(f.read_array('/h%d/%s' % (h, n)) for n in ('indptr', 'indices', 'data')) for h in range(H)]
+    import h5py
+    with h5py.File(h5file, 'r') as f:
+        H = int(f.attrs['shape'][1])
+        return [tuple(f['h%d/%s' % (h, n)][()] for n in ('indptr', 'indices', 'data')) for h in range(H)]
 
 
 def scipy_hapcsc(m):

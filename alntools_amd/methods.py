@@ -67,8 +67,9 @@ def count_alignments(ec_file, out_file, sample=None):
     bin_utils.count_alignments(ec_file, out_file, sample=sample)
 
 
-def ecquant(ec_file, out_file, sample=None, use_lengths=False, max_iters=1000, tol=1e-6, model=4, groups=None):
-    bin_utils.ecquant(ec_file, out_file, sample=sample, use_lengths=use_lengths, max_iters=max_iters, tol=tol, model=model, groups=groups)
+def ecquant(ec_file, out_file, sample=None, use_lengths=False, max_iters=1000, tol=1e-6, model=4, groups=None, posterior_file=None):
+    named = {} if posterior_file is None else {"posterior_file": posterior_file}
+    bin_utils.ecquant(ec_file, out_file, sample=sample, use_lengths=use_lengths, max_iters=max_iters, tol=tol, model=model, groups=groups, **named)
 
 
 def ecquant_cells(ec_file, out_file, samples=None, samples_file=None, use_lengths=False, max_iters=1000, tol=1e-6, report=None, model=4, groups=None):

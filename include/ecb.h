@@ -317,6 +317,8 @@ int ecb_csr_to_hapcsc(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_ha
                       const int32_t* data_a, int32_t* csc_indptr, int32_t* csc_indices, uint64_t capacity, uint64_t* total);
 int ecb_hapcsc_to_csr(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, const int32_t* csc_indptr, const int32_t* csc_indices,
                       uint64_t total, int32_t* indptr_a, int32_t* indices_a, int32_t* data_a, uint64_t* nnz);
+/* The value-carrying twin of the first conversion (ecb_csr_to_hapcsc_values*: a float64 per set bit goes along) is declared with the posterior it
+ * serves, in the posterior's own header among those included at the end of this file ("ecquant -w"). */
 
 /* apply-genotypes (ABI 4, additive): A' = every non-zero of a CSR A (.bin's bitmask values) ANDed with the haplotype mask of its locus,
  * the non-zeros that become 0 removed, every row kept (empty rows too), columns ascending -- what the reference's

@@ -52,5 +52,7 @@ int ecb_quantify(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, u
 #include "ecb_quant_cells.h"
 /* ... and the hierarchical models per cell (ecb_quantify_cells_model*): likewise */
 #include "ecb_quant_cells_model.h"
+/* ... and the posterior probability of every alignment at a given theta (ecb_posterior*): likewise */
+#include "ecb_quant_post.h"
 
 #endif /* ECB_QUANT_H */
