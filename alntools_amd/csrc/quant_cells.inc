@@ -16,6 +16,8 @@
 // spans two cells -- so a cell's bytes do not depend on which cells share its batch.  Converged cells are not compacted out: their
 // workgroups return on the first load (measured share: profiles/ecquant_cells_c4.txt).  The per-cell reduce has one level: thread k of the
 // cell's workgroup adds parts k, k + TPB, ... whatever their number.
+// The validation front is quant.inc's q_front (every sample's counts as the weights); the E- and M-step kernels run quant.inc's bodies
+// (q_tile_pass, q_long_row_sum, q_col_fold, q_theta_next) behind their own per-cell indexing and `done` tests.
 namespace {
 constexpr u32 QC_LONG_ROW = 256;     // an entry whose row has more non-zeros than this is summed by a workgroup, not a lane
 constexpr u32 QC_LONG_COL = 32;      // a slot with more column entries than this likewise
@@ -161,15 +163,7 @@ __global__ __launch_bounds__(TPB) void k_qc_estep(const u32* done, const u32* en
     if (k < n_ent) { a = off[k]; b = off[k + 1]; mine = b > a && b - a <= QC_LONG_ROW && !done[ent_cell[k]]; }
     if (!__syncthreads_or(mine)) return;
     const u32 lo = off[k0], hi = off[std::min<u64>(n_ent, k0 + TPB)];
-    double d = 0.0;
-    for (u32 base = lo; base < hi; base += QC_TILE) {
-        const u32 n = std::min<u32>(QC_TILE, hi - base);
-        for (u32 i = threadIdx.x; i < n; i += TPB) v[i] = q_bits_sum(phi, n_haps, row_slot[base + i], x_mask[base + i], 0.0);
-        __syncthreads();
-        if (mine)
-            for (u32 i = std::max(a, base), y = std::min(b, base + n); i < y; ++i) d += v[i - base];
-        __syncthreads();
-    }
+    const double d = q_tile_pass<QC_TILE>(v, phi, n_haps, row_slot, x_mask, lo, hi, a, b, mine);
     if (mine) {
         u64 got;
         q_row_done((u64)data_n[j0 + k], d, r + k, got);
@@ -182,16 +176,14 @@ __global__ __launch_bounds__(TPB) void k_qc_elong(const u32* done, const u32* en
     __shared__ double s[TPB];
     const u32 k = long_rows[blockIdx.x];
     if (done[ent_cell[k]]) return;
-    double d = 0.0;
-    for (u32 i = off[k] + threadIdx.x, b = off[k + 1]; i < b; i += TPB) d = q_bits_sum(phi, n_haps, row_slot[i], x_mask[i], d);
-    d = q_block_sum(d, s);
+    const double d = q_long_row_sum(s, phi, n_haps, row_slot, x_mask, off[k], off[k + 1]);
     if (threadIdx.x == 0) {
         u64 got;
         q_row_done((u64)data_n[j0 + k], d, r + k, got);
         expl[k] = got != 0;
     }
 }
-// M-step, workgroup b: long column long_cols[b] (a slot), k_q_mlong's scheme: read once for all its haplotypes, TPB entries at a time.
+// M-step, workgroup b: long column long_cols[b] (a slot), k_q_mlong's scheme: q_col_fold over its entries' r.
 // INIT: the sums of the counts instead (theta_0 = the cell's alignment counts), exact in 64-bit integers
 template <bool INIT>
 __global__ __launch_bounds__(TPB) void k_qc_mlong(const u32* done, const u32* slot_cell, const u32* long_cols, const u32* slot_ptr, const u32* col_ent,
@@ -201,22 +193,8 @@ __global__ __launch_bounds__(TPB) void k_qc_mlong(const u32* done, const u32* sl
     __shared__ u32 msk[TPB];
     const u32 t = long_cols[blockIdx.x];
     if (!INIT && done[slot_cell[t]]) return;
-    const u32 h = threadIdx.x & (hp - 1u), lane = threadIdx.x / hp, stride = TPB / hp;
-    const u32 a = slot_ptr[t], b = slot_ptr[t + 1];
-    V acc = 0;
-    for (u32 base = a; base < b; base += TPB) {
-        const u32 n = std::min<u32>(TPB, b - base);
-        if (threadIdx.x < n) {
-            msk[threadIdx.x] = col_mask[base + threadIdx.x];
-            if (INIT) val[threadIdx.x] = (V)data_n[j0 + col_ent[base + threadIdx.x]];
-            else val[threadIdx.x] = (V)r[col_ent[base + threadIdx.x]];
-        }
-        __syncthreads();
-        for (u32 j = lane; j < n; j += stride)
-            if ((msk[j] >> h) & 1u) acc += val[j];
-        __syncthreads();
-    }
-    acc = q_block_sum(acc, s, hp);
+    const V acc = q_col_fold(s, val, msk, col_mask, slot_ptr[t], slot_ptr[t + 1], hp,
+                             [&](u32 k) { if constexpr (INIT) return (V)data_n[j0 + col_ent[k]]; else return (V)r[col_ent[k]]; }, [](V x, u32, u32) { return x; });
     if (threadIdx.x < n_haps) acc_long[(u64)t * n_haps + threadIdx.x] = (double)acc;
 }
 // M-step, workgroup q: chunk q of one cell; lane i one (slot, h) of it: the entries of the slot's column with bit h, in index order (entry
@@ -246,10 +224,7 @@ __global__ __launch_bounds__(TPB) void k_qc_mstep(const u32* done, const u32* ch
             for (u32 k = a; k < b; ++k)
                 if ((col_mask[k] >> h) & 1u) acc += r[col_ent[k]];
         }
-        const double was = INIT ? 0.0 : theta[i], now = INIT ? acc : phi[i] * acc;
-        theta[i] = now;
-        phi[i] = scale ? now * scale[i] : now;
-        diff = fabs(now - was);
+        diff = q_theta_next<INIT>(acc, i, scale, theta, phi);
     }
     if (INIT) return;
     diff = q_block_sum(diff, s);
@@ -296,7 +271,6 @@ struct QcKept { DevBuf<> locus, theta; u64 slot0, n_slots; };      // a batch's 
 // The hierarchical models per cell (ecb_quantify_cells_model*, quant_cells_model.inc, included after this file) run on a batch as qc_run
 // set it up: what it hands them (QcView), what they add to the set-up (QcmTabs, the batch's buffers) and their step in place of the E- and
 // M-step kernels.  mdl = nullptr: the flat step, this file's own.
-struct QcModel { u32 model, n_genes; const int* gene; };
 struct QcView {
     hipStream_t st;
     u32 j0, n_ent, nc, n_x, n_slots, n_haps, hp, nlr, nlc, nq;
@@ -316,58 +290,56 @@ struct QcmTabs {
     double *phi_gh, *phi_g, *phi_t, *seg_c, *seg_x, *coef;
 };
 u64 qcm_x_bytes(u32 n_haps);
-int qcm_setup(Call& c, QcBufs& q, const QcView& v, const QcModel& mdl, SortBufs& s, const SortScratch& ss, u32* sums, QcmTabs& t);
+int qcm_setup(Call& c, QcBufs& q, const QcView& v, const QModel& mdl, SortBufs& s, const SortScratch& ss, u32* sums, QcmTabs& t);
 void qcm_step(const QcView& v, const QcmTabs& t, u32 model);
 
-int qc_check_args(uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, uint64_t nnz_a, const void* indptr_a, const void* indices_a, const void* data_a,
-                  uint32_t n_samples, uint64_t nnz_n, const void* indptr_n, const void* indices_n, const void* data_n, const char* what) {
+int qc_check_args(const QMat& m, const char* what) {
     // (no sample is no refusal here: there is then nothing to quantify)
-    RCCHK(ca_check_matrices(n_ecs, n_loci, n_haps, nnz_a, indptr_a, indices_a, data_a, std::max<uint32_t>(n_samples, 1u), nnz_n, indptr_n, indices_n, data_n));
-    if (nnz_a >= (1ull << 30)) return fail(nullptr, ECB_ERR_LIMIT, "%s: 2^30 non-zeros or more", what);
-    if ((u64)n_haps * n_loci >= (1ull << 31)) return fail(nullptr, ECB_ERR_LIMIT, "%s: haplotypes x loci does not fit 31 bits", what);
+    RCCHK(ca_check_matrices(m.n_ecs, m.n_loci, m.n_haps, m.nnz, m.ip, m.ix, m.da, std::max<uint32_t>(m.n_samples, 1u), m.nnz_n, m.pn, m.xn, m.dn));
+    if (m.nnz >= (1ull << 30)) return fail(nullptr, ECB_ERR_LIMIT, "%s: 2^30 non-zeros or more", what);
+    if ((u64)m.n_haps * m.n_loci >= (1ull << 31)) return fail(nullptr, ECB_ERR_LIMIT, "%s: haplotypes x loci does not fit 31 bits", what);
+    return ECB_OK;
+}
+// ... and what the four ecquant-cells entry points refuse after that
+int qc_check_quant(const QMat& m, const void* cell_ptr, const void* slot_locus, const void* theta, uint64_t n_slots, double tol) {
+    RCCHK(qc_check_args(m, "ecquant-cells"));
+    if (!cell_ptr || (n_slots && (!slot_locus || !theta)) || !(tol >= 0.0))          // (an array of no slots may be null)
+        return fail(nullptr, ECB_ERR_ARG, "ecquant-cells: bad argument (no cell_ptr, slot_locus or theta, or a tolerance that is NaN or negative)");
+    if (n_slots >= (1ull << 31) || n_slots * m.n_haps >= (1ull << 32))
+        return fail(nullptr, ECB_ERR_LIMIT, "ecquant-cells: n_slots is %llu: 2^31 slots or 2^32 values of theta, or more", (unsigned long long)n_slots);
     return ECB_OK;
 }
 
-// Both device entry points.  quant = false: the support alone (d_theta and what follows it unused; n_slots_in = the capacity of d_slot_locus).
-int qc_run(bool quant, int device, u32 n_ecs, u32 n_loci, u32 n_haps, u64 nnz, const void* d_indptr_a, const void* d_indices_a, const void* d_data_a,
-           u32 n_samples, u64 nnz_n, const void* d_indptr_n, const void* d_indices_n, const void* d_data_n, const void* d_cell_keep, const void* d_scale,
-           const void* d_theta_in, u32 max_iters, double tol, u64 budget_bytes, u64 n_slots_in, void* d_cell_ptr, void* d_slot_locus, void* d_theta,
-           void* d_n_iter, void* d_delta, void* d_explained, void* d_converged, uint64_t* n_slots_out, const QcModel* mdl = nullptr) {
+// what a run writes for the caller (device memory; those from n_iter on may be null)
+struct QcOut { void *cell_ptr, *slot_locus, *theta, *n_iter, *delta, *explained, *converged; };
+// All device entry points, their arguments checked.  quant = false: the support alone (of `o` only cell_ptr and slot_locus are used; n_slots_in =
+// the capacity of o.slot_locus).  mdl = nullptr: the flat step; model 4 is that step too, the genes checked first in a call of their own.
+int qc_run(bool quant, int device, const QMat& m, const void* d_cell_keep, const void* d_scale, const void* d_theta_in, u32 max_iters, double tol,
+           u64 budget_bytes, u64 n_slots_in, const QcOut& o, uint64_t* n_slots_out, const QModel* mdl = nullptr) {
+    if (mdl && mdl->model == 4u) {
+        RCCHK(qm_check_genes(device, "ecquant-cells: ", mdl->gene, m.n_loci, mdl->n_genes));
+        mdl = nullptr;
+    }
     const char* what = quant ? "ecquant-cells" : "cell-support";
     Call c(device, quant ? "ecquant-cells: " : "cell-support: "); if (c.rc) return c.rc;
     hipStream_t st = c.st;
-    const u64 n_words = GM_SHARD_WORDS * (1 + GM_SHARDS);          // apply-mask's words; [1] the error bits of N, [5] those of scale and theta_in, [6] [7] a batch's totals
-    const u64 n_tab = (u64)n_haps * n_loci;
-    const u32 S = n_samples;
-    u64* words = c.get<u64>(CV_WORDS, n_words);
-    u32 *bits = c.get<u32>(CV_X0, nnz), *bits_excl = c.get<u32>(CV_X1, nnz + 1), *sums = c.get<u32>(CV_SUMS2, scan_words(nnz));
-    u64* ww = c.get<u64>(CV_X2, n_ecs);
-    double *tab_scale = quant && d_scale ? c.get<double>(n_tab) : nullptr, *tab_theta = quant && d_theta_in ? c.get<double>(n_tab) : nullptr;
+    const u32 S = m.n_samples, n_loci = m.n_loci, n_haps = m.n_haps;
+    const u64 nnz = m.nnz;
+    // the front, every sample's counts as the weights (which only its check of N needs); words [6] [7]: a batch's totals
+    QFront f;
+    RCCHK(q_front(c, m, -1, quant ? d_scale : nullptr, quant ? d_theta_in : nullptr, Q_ERR_THETA, false, mdl ? mdl->gene : nullptr, mdl ? mdl->n_genes : 0u,
+                  false, nnz, Q_ERRS, f));
+    u64* words = f.words;
+    u32 *bits_excl = f.bits_excl, *sums = f.sums;
+    double *tab_scale = f.scale, *tab_theta = f.theta;
     u64 *cell_x = c.get<u64>(S), *cell_w = c.get<u64>(S);
     u32 *cell_slots = c.get<u32>(S), *it = c.get<u32>(S);
     double* dl = c.get<double>(S);
     long long* ex = c.get<long long>(S);
     uint8_t* cv = c.get<uint8_t>(S);
     if (const int rc = c.missing()) return rc;
-    const int* ip = (const int*)d_indptr_a; const int* ix = (const int*)d_indices_a; const int* da = (const int*)d_data_a;
-    const int* pn = (const int*)d_indptr_n; const int* xn = (const int*)d_indices_n; const int* dn = (const int*)d_data_n;
+    const int *ip = m.ip, *ix = m.ix, *da = m.da, *pn = m.pn, *xn = m.xn, *dn = m.dn;
     const uint8_t* keep = (const uint8_t*)d_cell_keep;
-    CALLCHK(c, hipMemsetAsync(words, 0, n_words * 8, st));
-    CALLCHK(c, hipMemsetAsync(ww, 0, std::max<u64>(n_ecs, 1) * 8, st));
-    k_ca_weights<<<nblk(std::max<u64>(nnz_n, (u64)S + 1), TPB), TPB, 0, st>>>(pn, S, xn, dn, nnz_n, n_ecs, -1, ww, words);
-    k_gm_check<true><<<nblk(std::max<u64>((u64)n_ecs + 1, (nnz + GM_ITEMS - 1) / GM_ITEMS), TPB), TPB, 0, st>>>(ip, n_ecs, ix, da, nnz, nullptr, n_loci,
-                                                                                                             n_haps, bits, words);
-    CALLCHK(c, hipGetLastError());
-    CALLCHK(c, scan_launch(st, bits, nnz, bits_excl, sums, words + 3, 1, bits_excl + nnz));
-    if (tab_scale) k_q_tab<<<nblk(n_tab, TPB), TPB, 0, st>>>((const double*)d_scale, n_loci, n_haps, tab_scale, Q_ERR_SCALE, reinterpret_cast<u32*>(words + 5));
-    if (tab_theta) k_q_tab<<<nblk(n_tab, TPB), TPB, 0, st>>>((const double*)d_theta_in, n_loci, n_haps, tab_theta, Q_ERR_THETA, reinterpret_cast<u32*>(words + 5));
-    if (mdl && n_loci) k_qm_gkeys<<<nblk(n_loci, TPB), TPB, 0, st>>>(mdl->gene, n_loci, mdl->n_genes, nullptr, nullptr, reinterpret_cast<u32*>(words + 5));
-    CALLCHK(c, hipGetLastError());
-    std::vector<u64> back(n_words);
-    if (const int rc = c.read_back(back.data(), words, n_words, GM_ERRS)) return rc;
-    RCCHK(ca_refuse_input(back));
-    if (back[3] >= (1ull << 32)) return fail(nullptr, ECB_ERR_LIMIT, "more than 2^32-1 set haplotype bits");
-    RCCHK(refuse_bits(nullptr, QM_ERRS, (u32)back[5]));                // (Q_ERRS and the gene ids' bit, which the flat step never sets)
     // the input is well formed.  The cells' sizes, and from them the batches
     std::vector<u64> hx(S);
     if (S) {
@@ -510,20 +482,43 @@ int qc_run(bool quant, int device, u32 n_ecs, u32 n_loci, u32 n_haps, u64 nnz, c
         CALLCHK(c, hipStreamSynchronize(st));
     }
     for (u32 k = 0; k < S; ++k) hcum[k + 1] = hcum[k] + hs[k];
-    CALLCHK(c, hipMemcpyAsync(d_cell_ptr, hcum.data(), ((u64)S + 1) * 8, hipMemcpyHostToDevice, st));      // (int64, never negative)
-    if (d_slot_locus && (quant || n_slots_in >= total_slots))
-        for (const QcKept& k : kept) CALLCHK(c, hipMemcpyAsync((u32*)d_slot_locus + k.slot0, k.locus.p, k.n_slots * 4, hipMemcpyDeviceToDevice, st));
+    CALLCHK(c, hipMemcpyAsync(o.cell_ptr, hcum.data(), ((u64)S + 1) * 8, hipMemcpyHostToDevice, st));      // (int64, never negative)
+    if (o.slot_locus && (quant || n_slots_in >= total_slots))
+        for (const QcKept& k : kept) CALLCHK(c, hipMemcpyAsync((u32*)o.slot_locus + k.slot0, k.locus.p, k.n_slots * 4, hipMemcpyDeviceToDevice, st));
     if (quant) {
         for (const QcKept& k : kept)
-            CALLCHK(c, hipMemcpyAsync((double*)d_theta + k.slot0 * n_haps, k.theta.p, k.n_slots * n_haps * 8, hipMemcpyDeviceToDevice, st));
-        if (S && d_n_iter) CALLCHK(c, hipMemcpyAsync(d_n_iter, it, (u64)S * 4, hipMemcpyDeviceToDevice, st));
-        if (S && d_delta) CALLCHK(c, hipMemcpyAsync(d_delta, dl, (u64)S * 8, hipMemcpyDeviceToDevice, st));
-        if (S && d_explained) CALLCHK(c, hipMemcpyAsync(d_explained, ex, (u64)S * 8, hipMemcpyDeviceToDevice, st));
-        if (S && d_converged) CALLCHK(c, hipMemcpyAsync(d_converged, cv, (u64)S, hipMemcpyDeviceToDevice, st));
+            CALLCHK(c, hipMemcpyAsync((double*)o.theta + k.slot0 * n_haps, k.theta.p, k.n_slots * n_haps * 8, hipMemcpyDeviceToDevice, st));
+        if (S && o.n_iter) CALLCHK(c, hipMemcpyAsync(o.n_iter, it, (u64)S * 4, hipMemcpyDeviceToDevice, st));
+        if (S && o.delta) CALLCHK(c, hipMemcpyAsync(o.delta, dl, (u64)S * 8, hipMemcpyDeviceToDevice, st));
+        if (S && o.explained) CALLCHK(c, hipMemcpyAsync(o.explained, ex, (u64)S * 8, hipMemcpyDeviceToDevice, st));
+        if (S && o.converged) CALLCHK(c, hipMemcpyAsync(o.converged, cv, (u64)S, hipMemcpyDeviceToDevice, st));
     }
     CALLCHK(c, hipStreamSynchronize(st));
     if (n_slots_out) *n_slots_out = total_slots;
     return ECB_OK;
+}
+// Both host entry points of ecquant-cells, their arguments checked: everything staged, the device run, the results back
+int qc_host(int device, const QMat& m, const uint8_t* cell_keep, const double* scale, const double* theta_in, u32 max_iters, double tol, u64 budget_bytes,
+            const QModel* mdl, u64 n_slots, int64_t* cell_ptr, int32_t* slot_locus, double* theta, uint32_t* n_iter, double* delta, int64_t* explained,
+            uint8_t* converged) {
+    Call c(device, "ecquant-cells: "); if (c.rc) return c.rc;
+    const u64 plane = (u64)m.n_haps * m.n_loci * 8, S = m.n_samples;
+    QStage b;
+    DevBuf<> kp, sc, ti, gn, ocp, osl, oth, oit, odl, oex, ocv;
+    std::vector<StageIn> in = q_stage(b, m);
+    if (mdl) in.push_back({&gn, mdl->gene, (u64)m.n_loci * 4});
+    in.insert(in.end(), {{&ocp, nullptr, (S + 1) * 8}, {&osl, nullptr, n_slots * 4}, {&oth, nullptr, n_slots * m.n_haps * 8},
+                         {&oit, nullptr, S * 4}, {&odl, nullptr, S * 8}, {&oex, nullptr, S * 8}, {&ocv, nullptr, S}});
+    if (cell_keep) in.push_back({&kp, cell_keep, S});
+    if (scale) in.push_back({&sc, scale, plane});
+    if (theta_in) in.push_back({&ti, theta_in, plane});
+    RCCHK(stage_in(c, in));
+    const QModel dm{mdl ? mdl->model : 4u, mdl ? mdl->n_genes : 0u, gn.as<int>()};
+    RCCHK(qc_run(true, device, q_staged(b, m), kp.p, sc.p, ti.p, max_iters, tol, budget_bytes, n_slots, QcOut{ocp.p, osl.p, oth.p, oit.p, odl.p, oex.p, ocv.p},
+                 nullptr, mdl ? &dm : nullptr));
+    return stage_out(c, {{cell_ptr, &ocp, (S + 1) * 8}, {slot_locus, &osl, n_slots * 4}, {theta, &oth, n_slots * m.n_haps * 8},
+                         {n_iter, &oit, n_iter ? S * 4 : 0}, {delta, &odl, delta ? S * 8 : 0}, {explained, &oex, explained ? S * 8 : 0},
+                         {converged, &ocv, converged ? S : 0}});
 }
 }  // namespace
 
@@ -531,30 +526,30 @@ extern "C" int ecb_cell_support_device(int device, uint32_t n_ecs, uint32_t n_lo
                                        const void* d_indices_a, const void* d_data_a, uint32_t n_samples, uint64_t nnz_n, const void* d_indptr_n,
                                        const void* d_indices_n, const void* d_data_n, const void* d_cell_keep, void* d_cell_ptr, void* d_slot_locus,
                                        uint64_t slot_capacity, uint64_t* n_slots) {
-    RCCHK(qc_check_args(n_ecs, n_loci, n_haps, nnz_a, d_indptr_a, d_indices_a, d_data_a, n_samples, nnz_n, d_indptr_n, d_indices_n, d_data_n, "cell-support"));
+    const QMat m{n_ecs, n_loci, n_haps, nnz_a, (const int*)d_indptr_a, (const int*)d_indices_a, (const int*)d_data_a,
+                 n_samples, nnz_n, (const int*)d_indptr_n, (const int*)d_indices_n, (const int*)d_data_n};
+    RCCHK(qc_check_args(m, "cell-support"));
     if (!d_cell_ptr) return fail(nullptr, ECB_ERR_ARG, "cell-support: bad argument (no cell_ptr)");
-    return qc_run(false, device, n_ecs, n_loci, n_haps, nnz_a, d_indptr_a, d_indices_a, d_data_a, n_samples, nnz_n, d_indptr_n, d_indices_n, d_data_n,
-                  d_cell_keep, nullptr, nullptr, 0, 0.0, 0, slot_capacity, d_cell_ptr, d_slot_locus, nullptr, nullptr, nullptr, nullptr, nullptr, n_slots);
+    return qc_run(false, device, m, d_cell_keep, nullptr, nullptr, 0, 0.0, 0, slot_capacity, QcOut{d_cell_ptr, d_slot_locus}, n_slots);
 }
 
 extern "C" int ecb_cell_support(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, uint64_t nnz_a, const int32_t* indptr_a,
                                 const int32_t* indices_a, const int32_t* data_a, uint32_t n_samples, uint64_t nnz_n, const int32_t* indptr_n,
                                 const int32_t* indices_n, const int32_t* data_n, const uint8_t* cell_keep, int64_t* cell_ptr, int32_t* slot_locus,
                                 uint64_t slot_capacity, uint64_t* n_slots) {
-    RCCHK(qc_check_args(n_ecs, n_loci, n_haps, nnz_a, indptr_a, indices_a, data_a, n_samples, nnz_n, indptr_n, indices_n, data_n, "cell-support"));
+    const QMat m{n_ecs, n_loci, n_haps, nnz_a, indptr_a, indices_a, data_a, n_samples, nnz_n, indptr_n, indices_n, data_n};
+    RCCHK(qc_check_args(m, "cell-support"));
     if (!cell_ptr) return fail(nullptr, ECB_ERR_ARG, "cell-support: bad argument (no cell_ptr)");
     Call c(device, "cell-support: "); if (c.rc) return c.rc;
-    DevBuf<> ipa, ixa, daa, ipn, ixn, dan, kp, ocp, osl;
-    std::vector<StageIn> in = {{&ipa, indptr_a, ((u64)n_ecs + 1) * 4}, {&ixa, indices_a, nnz_a * 4}, {&daa, data_a, nnz_a * 4},
-                               {&ipn, indptr_n, ((u64)n_samples + 1) * 4}, {&ixn, indices_n, nnz_n * 4}, {&dan, data_n, nnz_n * 4},
-                               {&ocp, nullptr, ((u64)n_samples + 1) * 8}};
+    QStage b;
+    DevBuf<> kp, ocp, osl;
+    std::vector<StageIn> in = q_stage(b, m);
+    in.push_back({&ocp, nullptr, ((u64)n_samples + 1) * 8});
     if (cell_keep) in.push_back({&kp, cell_keep, n_samples});
     if (slot_locus && slot_capacity) in.push_back({&osl, nullptr, slot_capacity * 4});
-    int rc = stage_in(c, in);
+    RCCHK(stage_in(c, in));
     uint64_t ns = 0;
-    if (rc == ECB_OK) rc = ecb_cell_support_device(device, n_ecs, n_loci, n_haps, nnz_a, ipa.p, ixa.p, daa.p, n_samples, nnz_n, ipn.p, ixn.p, dan.p, kp.p, ocp.p,
-                                                   osl.p, osl.p ? slot_capacity : 0, &ns);
-    RCCHK(rc);
+    RCCHK(qc_run(false, device, q_staged(b, m), kp.p, nullptr, nullptr, 0, 0.0, 0, osl.p ? slot_capacity : 0, QcOut{ocp.p, osl.p}, &ns));
     RCCHK(stage_out(c, {{cell_ptr, &ocp, ((u64)n_samples + 1) * 8}, {slot_locus, &osl, osl.p && slot_capacity >= ns ? ns * 4 : 0}}));
     if (n_slots) *n_slots = ns;
     return ECB_OK;
@@ -566,14 +561,11 @@ extern "C" int ecb_quantify_cells_device(int device, uint32_t n_ecs, uint32_t n_
                                          const void* d_theta_in, uint32_t max_iters, double tol, uint64_t budget_bytes, uint64_t n_slots,
                                          void* d_cell_ptr, void* d_slot_locus, void* d_theta, void* d_n_iter, void* d_delta, void* d_explained,
                                          void* d_converged) {
-    RCCHK(qc_check_args(n_ecs, n_loci, n_haps, nnz_a, d_indptr_a, d_indices_a, d_data_a, n_samples, nnz_n, d_indptr_n, d_indices_n, d_data_n, "ecquant-cells"));
-    if (!d_cell_ptr || (n_slots && (!d_slot_locus || !d_theta)) || !(tol >= 0.0))          // (an array of no slots may be null)
-        return fail(nullptr, ECB_ERR_ARG, "ecquant-cells: bad argument (no cell_ptr, slot_locus or theta, or a tolerance that is NaN or negative)");
-    if (n_slots >= (1ull << 31) || n_slots * n_haps >= (1ull << 32))
-        return fail(nullptr, ECB_ERR_LIMIT, "ecquant-cells: n_slots is %llu: 2^31 slots or 2^32 values of theta, or more", (unsigned long long)n_slots);
-    return qc_run(true, device, n_ecs, n_loci, n_haps, nnz_a, d_indptr_a, d_indices_a, d_data_a, n_samples, nnz_n, d_indptr_n, d_indices_n, d_data_n,
-                  d_cell_keep, d_scale, d_theta_in, max_iters, tol, budget_bytes, n_slots, d_cell_ptr, d_slot_locus, d_theta, d_n_iter, d_delta,
-                  d_explained, d_converged, nullptr);
+    const QMat m{n_ecs, n_loci, n_haps, nnz_a, (const int*)d_indptr_a, (const int*)d_indices_a, (const int*)d_data_a,
+                 n_samples, nnz_n, (const int*)d_indptr_n, (const int*)d_indices_n, (const int*)d_data_n};
+    RCCHK(qc_check_quant(m, d_cell_ptr, d_slot_locus, d_theta, n_slots, tol));
+    return qc_run(true, device, m, d_cell_keep, d_scale, d_theta_in, max_iters, tol, budget_bytes, n_slots,
+                  QcOut{d_cell_ptr, d_slot_locus, d_theta, d_n_iter, d_delta, d_explained, d_converged}, nullptr);
 }
 
 extern "C" int ecb_quantify_cells(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, uint64_t nnz_a, const int32_t* indptr_a,
@@ -581,26 +573,8 @@ extern "C" int ecb_quantify_cells(int device, uint32_t n_ecs, uint32_t n_loci, u
                                   const int32_t* indices_n, const int32_t* data_n, const uint8_t* cell_keep, const double* scale, const double* theta_in,
                                   uint32_t max_iters, double tol, uint64_t budget_bytes, uint64_t n_slots, int64_t* cell_ptr, int32_t* slot_locus,
                                   double* theta, uint32_t* n_iter, double* delta, int64_t* explained, uint8_t* converged) {
-    RCCHK(qc_check_args(n_ecs, n_loci, n_haps, nnz_a, indptr_a, indices_a, data_a, n_samples, nnz_n, indptr_n, indices_n, data_n, "ecquant-cells"));
-    if (!cell_ptr || (n_slots && (!slot_locus || !theta)) || !(tol >= 0.0))
-        return fail(nullptr, ECB_ERR_ARG, "ecquant-cells: bad argument (no cell_ptr, slot_locus or theta, or a tolerance that is NaN or negative)");
-    if (n_slots >= (1ull << 31) || n_slots * n_haps >= (1ull << 32))
-        return fail(nullptr, ECB_ERR_LIMIT, "ecquant-cells: n_slots is %llu: 2^31 slots or 2^32 values of theta, or more", (unsigned long long)n_slots);
-    Call c(device, "ecquant-cells: "); if (c.rc) return c.rc;
-    const u64 plane = (u64)n_haps * n_loci * 8, S = n_samples;
-    DevBuf<> ipa, ixa, daa, ipn, ixn, dan, kp, sc, ti, ocp, osl, oth, oit, odl, oex, ocv;
-    std::vector<StageIn> in = {{&ipa, indptr_a, ((u64)n_ecs + 1) * 4}, {&ixa, indices_a, nnz_a * 4}, {&daa, data_a, nnz_a * 4},
-                               {&ipn, indptr_n, (S + 1) * 4}, {&ixn, indices_n, nnz_n * 4}, {&dan, data_n, nnz_n * 4},
-                               {&ocp, nullptr, (S + 1) * 8}, {&osl, nullptr, n_slots * 4}, {&oth, nullptr, n_slots * n_haps * 8},
-                               {&oit, nullptr, S * 4}, {&odl, nullptr, S * 8}, {&oex, nullptr, S * 8}, {&ocv, nullptr, S}};
-    if (cell_keep) in.push_back({&kp, cell_keep, S});
-    if (scale) in.push_back({&sc, scale, plane});
-    if (theta_in) in.push_back({&ti, theta_in, plane});
-    int rc = stage_in(c, in);
-    if (rc == ECB_OK) rc = ecb_quantify_cells_device(device, n_ecs, n_loci, n_haps, nnz_a, ipa.p, ixa.p, daa.p, n_samples, nnz_n, ipn.p, ixn.p, dan.p, kp.p,
-                                                     sc.p, ti.p, max_iters, tol, budget_bytes, n_slots, ocp.p, osl.p, oth.p, oit.p, odl.p, oex.p, ocv.p);
-    RCCHK(rc);
-    return stage_out(c, {{cell_ptr, &ocp, (S + 1) * 8}, {slot_locus, &osl, n_slots * 4}, {theta, &oth, n_slots * n_haps * 8},
-                         {n_iter, &oit, n_iter ? S * 4 : 0}, {delta, &odl, delta ? S * 8 : 0}, {explained, &oex, explained ? S * 8 : 0},
-                         {converged, &ocv, converged ? S : 0}});
+    const QMat m{n_ecs, n_loci, n_haps, nnz_a, indptr_a, indices_a, data_a, n_samples, nnz_n, indptr_n, indices_n, data_n};
+    RCCHK(qc_check_quant(m, cell_ptr, slot_locus, theta, n_slots, tol));
+    return qc_host(device, m, cell_keep, scale, theta_in, max_iters, tol, budget_bytes, nullptr, n_slots, cell_ptr, slot_locus, theta, n_iter, delta,
+                   explained, converged);
 }

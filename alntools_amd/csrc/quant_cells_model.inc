@@ -18,6 +18,7 @@
 //   [k_qcm_mlong] k_qcm_mstep  theta' = phi x the sum of c over the slot's column, k_qc_mstep's chunks, its fold of the chunk's |delta|
 // No float atomics; every sum one thread's in index order or one workgroup's strided partial sums folded by q_block_sum; no sum spans two
 // cells.  Lanes of k_qcm_seg and k_qcm_row have uneven segment and row lengths, as k_qm_seg's and k_qm_row's do (DESIGN.md section 7).
+// What follows a kernel's `done` test is quant_model.inc's body of the same name (qm_gh_sum .. qm_coefs; a stored zero's QC_NONE is tested here).
 namespace {
 constexpr u64 QCM_X_BYTES = 64;      // device bytes the models add per expanded non-zero: ten 4-byte tables and the segments' two 8-byte ones, besides ...
 constexpr u64 QCM_COEF_BYTES = 8;    // ... a coefficient per set bit (at most H to a non-zero) and, a batch having no more slots than non-zeros, ...
@@ -77,11 +78,7 @@ __global__ __launch_bounds__(TPB) void k_qcm_gh(const u32* done, const u32* grou
     if (i >= (u64)n_groups * n_haps) return;
     const u32 g = (u32)(i / n_haps), h = (u32)(i - (u64)g * n_haps);
     if (done[group_cell[g]]) return;
-    const u32 a = gptr[g], b = gptr[g + 1];
-    if (b - a > Q_LONG_GENE) return;
-    double s = 0.0;
-    for (u32 k = a; k < b; ++k) s += phi[(u64)gmem[k] * n_haps + h];
-    phi_gh[i] = s;
+    qm_gh_sum(gptr, gmem, phi, g, h, n_haps, phi_gh + i);
 }
 // workgroup b: long group long_groups[b], k_qm_ghlong's scheme
 __global__ __launch_bounds__(TPB) void k_qcm_ghlong(const u32* done, const u32* group_cell, const u32* long_groups, const u32* gptr, const u32* gmem,
@@ -89,13 +86,7 @@ __global__ __launch_bounds__(TPB) void k_qcm_ghlong(const u32* done, const u32* 
     __shared__ double s[TPB];
     const u32 g = long_groups[blockIdx.x];
     if (done[group_cell[g]]) return;
-    const u32 h = threadIdx.x & (hp - 1u), lane = threadIdx.x / hp, stride = TPB / hp;
-    const u32 a = gptr[g], b = gptr[g + 1];
-    double acc = 0.0;
-    if (h < n_haps)
-        for (u32 k = a + lane; k < b; k += stride) acc += phi[(u64)gmem[k] * n_haps + h];
-    acc = q_block_sum(acc, s, hp);
-    if (threadIdx.x < n_haps) phi_gh[(u64)g * n_haps + threadIdx.x] = acc;
+    qm_ghlong_sum(s, gptr, gmem, phi, g, n_haps, hp, phi_gh);
 }
 // thread i < n_groups: Phi_g = Phi_gh added over h in order; thread n_groups + s, when phi_t is asked for (model 2): Phi_t of slot s likewise
 __global__ __launch_bounds__(TPB) void k_qcm_g(const u32* done, const u32* group_cell, const u32* slot_cell, const double* phi_gh, const double* phi,
@@ -104,10 +95,7 @@ __global__ __launch_bounds__(TPB) void k_qcm_g(const u32* done, const u32* group
     const bool is_group = i < n_groups;
     if (!is_group && (!phi_t || i - n_groups >= n_slots)) return;
     if (done[is_group ? group_cell[i] : slot_cell[i - n_groups]]) return;
-    const double* p = is_group ? phi_gh + i * n_haps : phi + (i - n_groups) * n_haps;
-    double s = 0.0;
-    for (u32 h = 0; h < n_haps; ++h) s += p[h];
-    (is_group ? phi_g[i] : phi_t[i - n_groups]) = s;
+    (is_group ? phi_g[i] : phi_t[i - n_groups]) = qm_hap_sum(is_group ? phi_gh + i * n_haps : phi + (i - n_groups) * n_haps, n_haps);
 }
 // thread s: segment s = the positions [seg_start[s], seg_start[s + 1]) of the gene-ordered view, all of one entry and one group (models 2
 // and 3; k_qm_seg's definitions, a slot for a target)
@@ -119,15 +107,7 @@ __global__ __launch_bounds__(TPB) void k_qcm_seg(const u32* done, const u32* seg
     if (s >= n_segs || done[seg_cell[s]]) return;
     const u32 g = seg_group[s];
     double d = 0.0, x = 0.0;
-    if (g != QC_NONE)
-        for (u32 p = seg_start[s], b = seg_start[s + 1]; p < b; ++p) {
-            const u32 i = gx[p], t = row_slot[i], m = x_mask[i];
-            if (MODEL == 2) {
-                const double dt = q_bits_sum(phi, n_haps, t, m, 0.0);
-                d += dt;
-                if (dt > 0.0) x += phi_t[t];
-            } else d = q_bits_sum(phi, n_haps, t, m, d);
-        }
+    if (g != QC_NONE) qm_seg_sums<MODEL>(seg_start[s], seg_start[s + 1], gx, row_slot, x_mask, phi, phi_t, n_haps, d, x);
     seg_c[s] = d > 0.0 ? phi_g[g] : 0.0;
     seg_x[s] = MODEL == 2 ? x : d;
 }
@@ -136,7 +116,7 @@ __global__ __launch_bounds__(TPB) void k_qcm_seg1(const u32* done, const u32* se
                                                   const u32* row_slot, const u32* x_mask, const u32* x_b0, const double* phi, const double* phi_gh,
                                                   const double* phi_g, u32 n_haps, u32 hp, double* seg_c, double* seg_x, double* coef) {
     const u64 s = (blockIdx.x * (u64)TPB + threadIdx.x) / hp;
-    const u32 h = threadIdx.x & (hp - 1u), bit = 1u << h;
+    const u32 h = threadIdx.x & (hp - 1u);
     const bool run = s < n_segs && !done[seg_cell[s]];
     if (!__syncthreads_or(run)) return;
     const bool on = run && h < n_haps;
@@ -145,19 +125,7 @@ __global__ __launch_bounds__(TPB) void k_qcm_seg1(const u32* done, const u32* se
         g = seg_group[s];
         if (g != QC_NONE) { a = seg_start[s]; b = seg_start[s + 1]; }
     }
-    double dh = 0.0;
-    for (u32 p = a; p < b; ++p) {
-        const u32 i = gx[p];
-        if (x_mask[i] & bit) dh += phi[(u64)row_slot[i] * n_haps + h];
-    }
-    const double pg = dh > 0.0 ? phi_gh[(u64)g * n_haps + h] : 0.0, f = dh > 0.0 ? pg / dh : 0.0;
-    double x = 0.0;
-    for (u32 k = 0; k < n_haps; ++k) x += __shfl(pg, (int)k, (int)hp);
-    for (u32 p = a; p < b; ++p) {
-        const u32 i = gx[p], m = x_mask[i];
-        if (m & bit) coef[x_b0[i] + __popc(m & (bit - 1u))] = f;
-    }
-    if (on && h == 0u) { seg_c[s] = x > 0.0 ? phi_g[g] : 0.0; seg_x[s] = x; }
+    qm_seg1_lanes(on, s, a, b, g, h, gx, row_slot, x_mask, x_b0, phi, phi_gh, phi_g, n_haps, hp, seg_c, seg_x, coef);
 }
 // thread k: entry k when it is a short row of a running cell; expl[k] = 1 when its reads were explained
 __global__ __launch_bounds__(TPB) void k_qcm_row(const u32* done, const u32* ent_cell, const u32* off, u32 n_ent, const u32* segid, const double* seg_x,
@@ -166,12 +134,7 @@ __global__ __launch_bounds__(TPB) void k_qcm_row(const u32* done, const u32* ent
     if (k >= n_ent) return;
     const u32 a = off[k], b = off[k + 1];
     if (b == a || !(b - a <= QC_LONG_ROW) || done[ent_cell[k]]) return;
-    const u32 s0 = segid[a], s1 = segid[b];
-    double r;
-    u64 got;
-    q_row_done((u64)data_n[j0 + k], qm_gene_sum(seg_c, s0, s1, 0, 1), &r, got);
-    qm_seg_coefs(seg_c, seg_x, r, s0, s1, 0, 1);
-    expl[k] = got != 0;
+    expl[k] = qm_row_short((u64)data_n[j0 + k], segid[a], segid[b], seg_x, seg_c) != 0;
 }
 // workgroup b: long entry long_rows[b], k_qm_rowlong's scheme
 __global__ __launch_bounds__(TPB) void k_qcm_rowlong(const u32* done, const u32* ent_cell, const u32* long_rows, const u32* off, const u32* segid,
@@ -179,12 +142,7 @@ __global__ __launch_bounds__(TPB) void k_qcm_rowlong(const u32* done, const u32*
     __shared__ double s[TPB];
     const u32 k = long_rows[blockIdx.x];
     if (done[ent_cell[k]]) return;
-    const u32 s0 = segid[off[k]], s1 = segid[off[k + 1]];
-    const double gd = q_block_sum(qm_gene_sum(seg_c, s0, s1, threadIdx.x, TPB), s);
-    double r;
-    u64 got;
-    q_row_done((u64)data_n[j0 + k], gd, &r, got);
-    qm_seg_coefs(seg_c, seg_x, r, s0, s1, threadIdx.x, TPB);
+    const u64 got = qm_row_long(s, (u64)data_n[j0 + k], segid[off[k]], segid[off[k + 1]], seg_x, seg_c);
     if (threadIdx.x == 0) expl[k] = got != 0;
 }
 // thread x: expanded non-zero x -- the coefficients of its set bits from its segment's c (k_qm_coef's definitions)
@@ -195,19 +153,7 @@ __global__ __launch_bounds__(TPB) void k_qcm_coef(const u32* done, const u32* se
     if (x >= n_x) return;
     const u32 sg = x_seg[x];
     if (done[seg_cell[sg]]) return;
-    const u32 m = x_mask[x], b0 = x_b0[x], n = (u32)__popc(m);
-    const double c = seg_c[sg];
-    if (MODEL == 1) {
-        for (u32 j = 0; j < n; ++j) coef[b0 + j] = c * coef[b0 + j];
-    } else {
-        double cv = c;
-        if (MODEL == 2 && m) {
-            const u32 t = row_slot[x];
-            const double dt = q_bits_sum(phi, n_haps, t, m, 0.0);
-            cv = dt > 0.0 ? c * phi_t[t] / dt : 0.0;
-        }
-        for (u32 j = 0; j < n; ++j) coef[b0 + j] = cv;
-    }
+    qm_coefs<MODEL>(seg_c, sg, row_slot, x, x_mask[x], x_b0[x], phi, phi_t, n_haps, coef);
 }
 // M-step, workgroup b: long column long_cols[b] (a slot), k_qm_mlong's scheme
 __global__ __launch_bounds__(TPB) void k_qcm_mlong(const u32* done, const u32* slot_cell, const u32* long_cols, const u32* slot_ptr, const u32* col_b0,
@@ -216,18 +162,8 @@ __global__ __launch_bounds__(TPB) void k_qcm_mlong(const u32* done, const u32* s
     __shared__ u32 msk[TPB], b0[TPB];
     const u32 t = long_cols[blockIdx.x];
     if (done[slot_cell[t]]) return;
-    const u32 h = threadIdx.x & (hp - 1u), lane = threadIdx.x / hp, stride = TPB / hp;
-    const u32 a = slot_ptr[t], b = slot_ptr[t + 1];
-    double acc = 0.0;
-    for (u32 base = a; base < b; base += TPB) {
-        const u32 n = std::min<u32>(TPB, b - base);
-        if (threadIdx.x < n) { msk[threadIdx.x] = col_mask[base + threadIdx.x]; b0[threadIdx.x] = col_b0[base + threadIdx.x]; }
-        __syncthreads();
-        for (u32 j = lane; j < n; j += stride)
-            if ((msk[j] >> h) & 1u) acc += qm_coef_at(coef, b0[j], msk[j], h);
-        __syncthreads();
-    }
-    acc = q_block_sum(acc, s, hp);
+    const double acc = q_col_fold(s, b0, msk, col_mask, slot_ptr[t], slot_ptr[t + 1], hp, [&](u32 k) { return col_b0[k]; },
+                                  [&](u32 x, u32 m, u32 h) { return qm_coef_at(coef, x, m, h); });
     if (threadIdx.x < n_haps) acc_long[(u64)t * n_haps + threadIdx.x] = acc;
 }
 // M-step, workgroup q: chunk q of one cell, k_qc_mstep's items: lane i one (slot, h) -- the coefficients of the slot's column entries with
@@ -251,17 +187,14 @@ __global__ __launch_bounds__(TPB) void k_qcm_mstep(const u32* done, const u32* c
                 const u32 m = col_mask[k];
                 if ((m >> h) & 1u) acc += qm_coef_at(coef, col_b0[k], m, h);
             }
-        const double was = theta[i], now = phi[i] * acc;
-        theta[i] = now;
-        phi[i] = scale ? now * scale[i] : now;
-        diff = fabs(now - was);
+        diff = q_theta_next<false>(acc, i, scale, theta, phi);
     }
     diff = q_block_sum(diff, s);
     if (threadIdx.x == 0) partial[blockIdx.x] = diff;
 }
 
 // The models' part of a batch's set-up.  s still holds the sort that made the slots: its values are the column view's expanded non-zeros.
-int qcm_setup(Call& c, QcBufs& q, const QcView& v, const QcModel& mdl, SortBufs& s, const SortScratch& ss, u32* sums, QcmTabs& t) {
+int qcm_setup(Call& c, QcBufs& q, const QcView& v, const QModel& mdl, SortBufs& s, const SortScratch& ss, u32* sums, QcmTabs& t) {
     hipStream_t st = v.st;
     const u32 n_x = v.n_x, n_slots = v.n_slots;
     u64* tot = q.get<u64>(4);                                          // [0] groups, [1] segments, [2] set bits, [3] the long groups' counter
@@ -358,32 +291,13 @@ extern "C" int ecb_quantify_cells_model_device(int device, uint32_t n_ecs, uint3
                                                const void* d_theta_in, uint32_t max_iters, double tol, uint64_t budget_bytes, uint32_t n_genes,
                                                const void* d_gene, uint32_t model, uint64_t n_slots, void* d_cell_ptr, void* d_slot_locus, void* d_theta,
                                                void* d_n_iter, void* d_delta, void* d_explained, void* d_converged) {
+    const QMat m{n_ecs, n_loci, n_haps, nnz_a, (const int*)d_indptr_a, (const int*)d_indices_a, (const int*)d_data_a,
+                 n_samples, nnz_n, (const int*)d_indptr_n, (const int*)d_indices_n, (const int*)d_data_n};
     RCCHK(qcm_check_args(n_loci, n_genes, d_gene, model));
-    RCCHK(qc_check_args(n_ecs, n_loci, n_haps, nnz_a, d_indptr_a, d_indices_a, d_data_a, n_samples, nnz_n, d_indptr_n, d_indices_n, d_data_n, "ecquant-cells"));
-    if (!d_cell_ptr || (n_slots && (!d_slot_locus || !d_theta)) || !(tol >= 0.0))
-        return fail(nullptr, ECB_ERR_ARG, "ecquant-cells: bad argument (no cell_ptr, slot_locus or theta, or a tolerance that is NaN or negative)");
-    if (n_slots >= (1ull << 31) || n_slots * n_haps >= (1ull << 32))
-        return fail(nullptr, ECB_ERR_LIMIT, "ecquant-cells: n_slots is %llu: 2^31 slots or 2^32 values of theta, or more", (unsigned long long)n_slots);
-    if (model == 4u) {
-        // the flat step is ecb_quantify_cells's own: the genes are checked, then it runs as it always has
-        {
-            Call c(device, "ecquant-cells: "); if (c.rc) return c.rc;
-            u64* word = c.get<u64>(1);
-            if (const int rc = c.missing()) return rc;
-            CALLCHK(c, hipMemsetAsync(word, 0, 8, c.st));
-            if (n_loci) k_qm_gkeys<<<nblk(n_loci, TPB), TPB, 0, c.st>>>((const int*)d_gene, n_loci, n_genes, nullptr, nullptr, reinterpret_cast<u32*>(word));
-            CALLCHK(c, hipGetLastError());
-            u64 back = 0;
-            if (const int rc = c.read_back(&back, word, 1, QM_ERRS)) return rc;
-        }
-        return ecb_quantify_cells_device(device, n_ecs, n_loci, n_haps, nnz_a, d_indptr_a, d_indices_a, d_data_a, n_samples, nnz_n, d_indptr_n, d_indices_n,
-                                         d_data_n, d_cell_keep, d_scale, d_theta_in, max_iters, tol, budget_bytes, n_slots, d_cell_ptr, d_slot_locus, d_theta,
-                                         d_n_iter, d_delta, d_explained, d_converged);
-    }
-    const QcModel mdl{model, n_genes, (const int*)d_gene};
-    return qc_run(true, device, n_ecs, n_loci, n_haps, nnz_a, d_indptr_a, d_indices_a, d_data_a, n_samples, nnz_n, d_indptr_n, d_indices_n, d_data_n,
-                  d_cell_keep, d_scale, d_theta_in, max_iters, tol, budget_bytes, n_slots, d_cell_ptr, d_slot_locus, d_theta, d_n_iter, d_delta,
-                  d_explained, d_converged, nullptr, &mdl);
+    RCCHK(qc_check_quant(m, d_cell_ptr, d_slot_locus, d_theta, n_slots, tol));
+    const QModel mdl{model, n_genes, (const int*)d_gene};
+    return qc_run(true, device, m, d_cell_keep, d_scale, d_theta_in, max_iters, tol, budget_bytes, n_slots,
+                  QcOut{d_cell_ptr, d_slot_locus, d_theta, d_n_iter, d_delta, d_explained, d_converged}, nullptr, &mdl);
 }
 
 extern "C" int ecb_quantify_cells_model(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, uint64_t nnz_a, const int32_t* indptr_a,
@@ -392,28 +306,11 @@ extern "C" int ecb_quantify_cells_model(int device, uint32_t n_ecs, uint32_t n_l
                                         const double* theta_in, uint32_t max_iters, double tol, uint64_t budget_bytes, uint32_t n_genes, const int32_t* gene,
                                         uint32_t model, uint64_t n_slots, int64_t* cell_ptr, int32_t* slot_locus, double* theta, uint32_t* n_iter,
                                         double* delta, int64_t* explained, uint8_t* converged) {
+    const QMat m{n_ecs, n_loci, n_haps, nnz_a, indptr_a, indices_a, data_a, n_samples, nnz_n, indptr_n, indices_n, data_n};
     RCCHK(qcm_check_args(n_loci, n_genes, gene, model));
-    RCCHK(qc_check_args(n_ecs, n_loci, n_haps, nnz_a, indptr_a, indices_a, data_a, n_samples, nnz_n, indptr_n, indices_n, data_n, "ecquant-cells"));
-    if (!cell_ptr || (n_slots && (!slot_locus || !theta)) || !(tol >= 0.0))
-        return fail(nullptr, ECB_ERR_ARG, "ecquant-cells: bad argument (no cell_ptr, slot_locus or theta, or a tolerance that is NaN or negative)");
-    if (n_slots >= (1ull << 31) || n_slots * n_haps >= (1ull << 32))
-        return fail(nullptr, ECB_ERR_LIMIT, "ecquant-cells: n_slots is %llu: 2^31 slots or 2^32 values of theta, or more", (unsigned long long)n_slots);
-    Call c(device, "ecquant-cells: "); if (c.rc) return c.rc;
-    const u64 plane = (u64)n_haps * n_loci * 8, S = n_samples;
-    DevBuf<> ipa, ixa, daa, ipn, ixn, dan, kp, sc, ti, gn, ocp, osl, oth, oit, odl, oex, ocv;
-    std::vector<StageIn> in = {{&ipa, indptr_a, ((u64)n_ecs + 1) * 4}, {&ixa, indices_a, nnz_a * 4}, {&daa, data_a, nnz_a * 4},
-                               {&ipn, indptr_n, (S + 1) * 4}, {&ixn, indices_n, nnz_n * 4}, {&dan, data_n, nnz_n * 4}, {&gn, gene, (u64)n_loci * 4},
-                               {&ocp, nullptr, (S + 1) * 8}, {&osl, nullptr, n_slots * 4}, {&oth, nullptr, n_slots * n_haps * 8},
-                               {&oit, nullptr, S * 4}, {&odl, nullptr, S * 8}, {&oex, nullptr, S * 8}, {&ocv, nullptr, S}};
-    if (cell_keep) in.push_back({&kp, cell_keep, S});
-    if (scale) in.push_back({&sc, scale, plane});
-    if (theta_in) in.push_back({&ti, theta_in, plane});
-    int rc = stage_in(c, in);
-    if (rc == ECB_OK) rc = ecb_quantify_cells_model_device(device, n_ecs, n_loci, n_haps, nnz_a, ipa.p, ixa.p, daa.p, n_samples, nnz_n, ipn.p, ixn.p, dan.p, kp.p,
-                                                           sc.p, ti.p, max_iters, tol, budget_bytes, n_genes, gn.p, model, n_slots, ocp.p, osl.p, oth.p, oit.p,
-                                                           odl.p, oex.p, ocv.p);
-    RCCHK(rc);
-    return stage_out(c, {{cell_ptr, &ocp, (S + 1) * 8}, {slot_locus, &osl, n_slots * 4}, {theta, &oth, n_slots * n_haps * 8},
-                         {n_iter, &oit, n_iter ? S * 4 : 0}, {delta, &odl, delta ? S * 8 : 0}, {explained, &oex, explained ? S * 8 : 0},
-                         {converged, &ocv, converged ? S : 0}});
+    RCCHK(qc_check_quant(m, cell_ptr, slot_locus, theta, n_slots, tol));
+    const QModel mdl{model, n_genes, gene};
+    return qc_host(device, m, cell_keep, scale, theta_in, max_iters, tol, budget_bytes, &mdl, n_slots, cell_ptr, slot_locus, theta, n_iter, delta, explained,
+                   converged);
 }
+

@@ -11,6 +11,8 @@
 // gene factor over the segment's divisor), and a twin of k_qm_coef that writes the factor product itself (k_qp_post): rows of weight 0 and
 // entries with phi = 0 come out as defined, no division by phi.  Model 1's Phi_gh / D_h are left by k_qm_seg1 in `post` itself.
 // Every sum by one thread in index order or by one workgroup with q_block_sum's tree: the result is a function of the inputs alone.
+// Host side: quant.inc's q_front without N (theta refused in this entry point's words, the n_bits mismatch after everything else), and for
+// models 1-3 quant_model.inc's qm_gene_view, qm_tables and qm_step with `post` set; the row kernels run quant.inc's q_tile_pass and q_long_row_sum.
 namespace {
 enum : u32 { QP_ERR_THETA = 8u };
 const ErrBit QP_ERRS[] = {
@@ -43,15 +45,7 @@ __global__ __launch_bounds__(TPB) void k_qp_drow(const int* indptr, u32 n_ecs, c
     u32 a = 0, b = 0;
     if (e < n_ecs) { a = (u32)indptr[e]; b = (u32)indptr[e + 1]; }
     const bool mine = e < n_ecs && b - a <= Q_LONG_ROW;
-    double d = 0.0;
-    for (u32 base = lo; base < hi; base += Q_TILE) {
-        const u32 n = std::min<u32>(Q_TILE, hi - base);
-        for (u32 k = threadIdx.x; k < n; k += TPB) v[k] = q_bits_sum(phi, n_haps, (u32)indices[base + k], (u32)data[base + k], 0.0);
-        __syncthreads();
-        if (mine)
-            for (u32 i = std::max(a, base), y = std::min(b, base + n); i < y; ++i) d += v[i - base];
-        __syncthreads();
-    }
+    const double d = q_tile_pass<Q_TILE>(v, phi, n_haps, indices, data, lo, hi, a, b, mine);
     if (mine) d_out[e] = d;
     if (!EMIT) return;
     dl[threadIdx.x] = mine ? d : e < n_ecs ? d_out[e] : 0.0;
@@ -72,10 +66,7 @@ __global__ __launch_bounds__(TPB) void k_qp_dlong(const u32* long_rows, const in
                                                   u32 n_haps, double* d_out) {
     __shared__ double s[TPB];
     const u32 e = long_rows[blockIdx.x];
-    const u32 a = (u32)indptr[e], b = (u32)indptr[e + 1];
-    double d = 0.0;
-    for (u32 i = a + threadIdx.x; i < b; i += TPB) d = q_bits_sum(phi, n_haps, (u32)indices[i], (u32)data[i], d);
-    d = q_block_sum(d, s);
+    const double d = q_long_row_sum(s, phi, n_haps, indices, data, (u32)indptr[e], (u32)indptr[e + 1]);
     if (threadIdx.x == 0) d_out[e] = d;
 }
 // thread i <= nnz: bit_ptr[i] = bits_excl[i], 64 bits wide
@@ -127,118 +118,59 @@ extern "C" int ecb_posterior_device(int device, uint32_t n_ecs, uint32_t n_loci,
     Call c(device, "ecposterior: "); if (c.rc) return c.rc;
     hipStream_t st = c.st;
     const bool grouped = model != 4u;
-    const u64 n_words = GM_SHARD_WORDS * (1 + GM_SHARDS);          // as ecb_quantify_model_device: [3] the set bits, [5] the error bits of the tables and of gene
-    const u64 n_tab = (u64)n_haps * n_loci, n_gtab = grouped ? (u64)n_haps * n_genes : 0;
-    u64* words = c.get<u64>(CV_WORDS, n_words);
-    u32 *bits = c.get<u32>(CV_X0, nnz), *bits_excl = c.get<u32>(CV_X1, nnz + 1), *sums = c.get<u32>(CV_SUMS2, scan_words(nnz + 1));
-    double *theta = c.get<double>(n_tab), *phi = c.get<double>(n_tab), *scale = d_scale ? c.get<double>(n_tab) : nullptr;
-    u64 *gk0 = nullptr, *gk1 = nullptr;
-    u32 *gv0 = nullptr, *gv1 = nullptr;
-    if (grouped) { gk0 = c.get<u64>(n_loci); gk1 = c.get<u64>(n_loci); gv0 = c.get<u32>(n_loci); gv1 = c.get<u32>(n_loci); }
-    if (const int rc = c.missing()) return rc;
-    const int* ip = (const int*)d_indptr_a; const int* ix = (const int*)d_indices_a; const int* da = (const int*)d_data_a;
-    const int* gene = (const int*)d_gene;
-    CALLCHK(c, hipMemsetAsync(words, 0, n_words * 8, st));
-    k_gm_check<true><<<nblk(std::max<u64>((u64)n_ecs + 1, (nnz + GM_ITEMS - 1) / GM_ITEMS), TPB), TPB, 0, st>>>(ip, n_ecs, ix, da, nnz, nullptr, n_loci,
-                                                                                                             n_haps, bits, words);
-    CALLCHK(c, hipGetLastError());
-    CALLCHK(c, scan_launch(st, bits, nnz, bits_excl, sums, words + 3, 1, bits_excl + nnz));
-    // (into the call's own tables, T x H: nothing of the caller's is written yet)
-    if (d_scale) k_q_tab<<<nblk(n_tab, TPB), TPB, 0, st>>>((const double*)d_scale, n_loci, n_haps, scale, Q_ERR_SCALE, reinterpret_cast<u32*>(words + 5));
-    k_q_tab<<<nblk(n_tab, TPB), TPB, 0, st>>>((const double*)d_theta, n_loci, n_haps, theta, QP_ERR_THETA, reinterpret_cast<u32*>(words + 5));
-    if (gene) k_qm_gkeys<<<nblk(n_loci, TPB), TPB, 0, st>>>(gene, n_loci, n_genes, gk0, gv0, reinterpret_cast<u32*>(words + 5));
-    CALLCHK(c, hipGetLastError());
-    std::vector<u64> back(n_words);
-    if (const int rc = c.read_back(back.data(), words, n_words, GM_ERRS)) return rc;
-    RCCHK(ca_refuse_input(back));
-    if (back[3] >= (1ull << 32)) return fail(nullptr, ECB_ERR_LIMIT, "more than 2^32-1 set haplotype bits");
-    RCCHK(refuse_bits(nullptr, QP_ERRS, (u32)back[5]));
-    if (back[3] != n_bits)
-        return fail(nullptr, ECB_ERR_ARG, "ecposterior: n_bits is %llu, the matrix has %llu set bits", (unsigned long long)n_bits, (unsigned long long)back[3]);
+    const QMat m{n_ecs, n_loci, n_haps, nnz, (const int*)d_indptr_a, (const int*)d_indices_a, (const int*)d_data_a, 0, 0, nullptr, nullptr, nullptr};
+    const QModel mdl{model, n_genes, (const int*)d_gene};
+    const u64 n_tab = (u64)n_haps * n_loci;
+    // the front without N: no weights; theta is the caller's, refused in this entry point's words; the genes checked whenever they are given
+    QFront f;
+    RCCHK(q_front(c, m, -1, d_scale, d_theta, QP_ERR_THETA, true, mdl.gene, n_genes, grouped, nnz + 1, QP_ERRS, f));
+    if (f.n_bits != n_bits)
+        return fail(nullptr, ECB_ERR_ARG, "ecposterior: n_bits is %llu, the matrix has %llu set bits", (unsigned long long)n_bits, (unsigned long long)f.n_bits);
     // the input is well formed: from here on the outputs are written
-    if (d_bit_ptr) k_qp_bitptr<<<nblk(nnz + 1, TPB), TPB, 0, st>>>(bits_excl, nnz, (long long*)d_bit_ptr);
+    if (d_bit_ptr) k_qp_bitptr<<<nblk(nnz + 1, TPB), TPB, 0, st>>>(f.bits_excl, nnz, (long long*)d_bit_ptr);
     CALLCHK(c, hipGetLastError());
     if (n_ecs && nnz) {
         double* post = (double*)d_post;
-        const bool flat_d = !grouped || d_row_mass;
         const u32 n_eblk = nblk(n_ecs, TPB);
-        u32 *long_rows = c.get<u32>(nnz / Q_LONG_ROW + 1), *n_long_d = c.get<u32>(2);
+        u32 *long_rows = c.get<u32>(nnz / Q_LONG_ROW + 1), *n_long_d = c.get<u32>(1);
         double* d = !grouped && !d_row_mass ? c.get<double>(CV_X2, n_ecs) : (double*)d_row_mass;          // (from the pool: no allocation of its own when the caller takes no row_mass)
         if (const int rc = c.missing()) return rc;
-        CALLCHK(c, hipMemsetAsync(n_long_d, 0, 8, st));
-        k_q_phi<<<nblk(n_tab, TPB), TPB, 0, st>>>(theta, scale, n_tab, phi);
-        k_qp_rows<<<n_eblk, TPB, 0, st>>>(ip, n_ecs, n_long_d, long_rows);
+        CALLCHK(c, hipMemsetAsync(n_long_d, 0, 4, st));
+        k_q_phi<<<nblk(n_tab, TPB), TPB, 0, st>>>(f.theta, f.scale, n_tab, f.phi);
+        k_qp_rows<<<n_eblk, TPB, 0, st>>>(m.ip, n_ecs, n_long_d, long_rows);
         CALLCHK(c, hipGetLastError());
+        // models 1-3: the members of each gene and the gene-ordered view of the rows with its segments, as ecb_quantify_model_device has them
+        QmTabs mt{};
+        if (grouped) {
+            QSort srt = q_sort_bufs(c, nnz, std::max<u64>(nnz, n_loci), f.words + 4);
+            if (const int rc = c.missing()) return rc;
+            RCCHK(qm_gene_view(c, m, f, mdl.gene, n_genes, srt, mt.g));
+        }
         u32 nlr = 0;
-        if (!grouped) {
-            CALLCHK(c, hipMemcpyAsync(&nlr, n_long_d, 4, hipMemcpyDeviceToHost, st));
-            CALLCHK(c, hipStreamSynchronize(st));
-        }
-        u64* n_segs_d = nullptr;
-        u32 *flag = nullptr, *segid = nullptr, *seg_start = nullptr, *nz_seg = nullptr, *long_genes = nullptr;
-        int *gptr = nullptr, *gmem = nullptr;
-        const u64* rkeys = nullptr; const u32* gnz = nullptr;
-        u32 n_segs = 0, nlg = 0;
-        if (grouped) {
-            // the members of each gene and the gene-ordered view of the rows with its segments, as ecb_quantify_model_device builds them
-            u64 *k0 = c.get<u64>(CV_KEYS0, nnz), *k1 = c.get<u64>(CV_KEYS1, nnz);
-            u32 *v0 = c.get<u32>(CV_VALS0, nnz), *v1 = c.get<u32>(CV_VALS1, nnz);
-            SortScratch ss{c.get<u32>(CV_HIST, rs_words(std::max<u64>(nnz, n_loci))), c.get<u32>(CV_OFFS, RS_AUX_WORDS), words + 4};
-            long_genes = c.get<u32>(n_loci / Q_LONG_GENE + 1);
-            gptr = c.get<int>((u64)n_genes + 1); gmem = c.get<int>(n_loci);
-            flag = c.get<u32>(nnz); segid = c.get<u32>(nnz + 1); seg_start = c.get<u32>(nnz + 1); nz_seg = c.get<u32>(nnz);
-            n_segs_d = c.get<u64>(1);
-            if (const int rc = c.missing()) return rc;
-            SortBufs sg{{gk0, gk1}, {gv0, gv1}};
-            CALLCHK(c, radix_sort_pairs64(st, sg, n_loci, ss, msb_mask(n_genes - 1) << 32));
-            k_split_out<<<nblk(n_loci, TPB), TPB, 0, st>>>(sg.keys(), sg.vals(), n_loci, gmem, gmem);
-            k_row_ptr<<<nblk((u64)n_genes + 1, TPB), TPB, 0, st>>>(sg.keys(), n_loci, n_genes, gptr);
-            k_qm_glist<<<nblk(n_genes, TPB), TPB, 0, st>>>(gptr, n_genes, n_long_d + 1, long_genes);
-            k_qm_rkeys<<<n_eblk, TPB, 0, st>>>(ip, n_ecs, ix, gene, k0, v0);
-            SortBufs s{{k0, k1}, {v0, v1}};
-            CALLCHK(c, radix_sort_pairs64(st, s, nnz, ss, msb_mask(n_ecs - 1) << 32 | msb_mask(n_genes - 1)));
-            rkeys = s.keys(); gnz = s.vals();
-            k_run_heads<<<nblk(nnz, TPB), TPB, 0, st>>>(rkeys, nnz, flag);
-            CALLCHK(c, scan_launch(st, flag, nnz, segid, sums, n_segs_d, 1, segid + nnz));
-            k_qm_segs<<<nblk(nnz + 1, TPB), TPB, 0, st>>>(flag, segid, gnz, nnz, seg_start, nz_seg);
-            CALLCHK(c, hipGetLastError());
-            u32 cnt[2] = {0, 0};
-            u64 n_segs64 = 0;
-            CALLCHK(c, hipMemcpyAsync(cnt, n_long_d, 8, hipMemcpyDeviceToHost, st));
-            CALLCHK(c, hipMemcpyAsync(&n_segs64, n_segs_d, 8, hipMemcpyDeviceToHost, st));
-            CALLCHK(c, hipStreamSynchronize(st));
-            nlr = cnt[0]; nlg = cnt[1]; n_segs = (u32)n_segs64;
-        }
-        if (flat_d) {
-            if (nlr) k_qp_dlong<<<nlr, TPB, 0, st>>>(long_rows, ip, ix, da, phi, n_haps, d);
-            if (grouped) k_qp_drow<false><<<n_eblk, TPB, 0, st>>>(ip, n_ecs, ix, da, phi, n_haps, bits_excl, d, nullptr);
-            else k_qp_drow<true><<<n_eblk, TPB, 0, st>>>(ip, n_ecs, ix, da, phi, n_haps, bits_excl, d, post);
+        u64 gcnt[2] = {0, 0};
+        CALLCHK(c, hipMemcpyAsync(&nlr, n_long_d, 4, hipMemcpyDeviceToHost, st));
+        if (grouped) CALLCHK(c, hipMemcpyAsync(gcnt, mt.g.cnt, 16, hipMemcpyDeviceToHost, st));
+        CALLCHK(c, hipStreamSynchronize(st));
+        mt.g.n_segs = (u32)gcnt[0]; mt.g.n_long_genes = (u32)gcnt[1];
+        if (!grouped || d_row_mass) {
+            if (nlr) k_qp_dlong<<<nlr, TPB, 0, st>>>(long_rows, m.ip, m.ix, m.da, f.phi, n_haps, d);
+            if (grouped) k_qp_drow<false><<<n_eblk, TPB, 0, st>>>(m.ip, n_ecs, m.ix, m.da, f.phi, n_haps, f.bits_excl, d, nullptr);
+            else k_qp_drow<true><<<n_eblk, TPB, 0, st>>>(m.ip, n_ecs, m.ix, m.da, f.phi, n_haps, f.bits_excl, d, post);
         }
         if (grouped) {
-            u64* ww = c.get<u64>(n_ecs);
-            double *phi_gh = c.get<double>(n_gtab), *phi_g = c.get<double>(n_genes), *phi_t = model == 2u ? c.get<double>(n_loci) : nullptr;
-            double *seg_c = c.get<double>(nnz), *seg_x = c.get<double>(nnz);
-            u64* expl_parts = c.get<u64>((u64)n_eblk + nnz / Q_LONG_ROW + 1);
+            // the chain once, with a weight of one in every row and a state that says "running"
+            // (its tables allocated here, while the row kernels run; model 1's Phi_gh / D_h are left in `post` itself)
+            u64 *ww = c.get<u64>(n_ecs), *expl_parts = c.get<u64>((u64)n_eblk + nnz / Q_LONG_ROW + 1);
             QState* qs = c.get<QState>(1);
-            if (const int rc = c.missing()) return rc;
-            u32 hp = 1;
-            while (hp < n_haps) hp <<= 1;
+            RCCHK(qm_tables(c, m, f, mdl, post, mt));
+            QView v{};
+            v.st = st; v.n_ecs = n_ecs; v.n_loci = n_loci; v.n_haps = n_haps; v.n_eblk = n_eblk; v.nlr = nlr; v.nnz = nnz;
+            v.ip = m.ip; v.ix = m.ix; v.da = m.da; v.bits_excl = f.bits_excl; v.long_rows = long_rows; v.ww = ww; v.qs = qs; v.phi = f.phi;
+            v.expl_parts = expl_parts;
+            for (v.hp = 1; v.hp < n_haps;) v.hp <<= 1;
             CALLCHK(c, hipMemsetAsync(qs, 0, sizeof(QState), st));          // (done = 0: the chain's kernels run)
             k_qp_ones<<<n_eblk, TPB, 0, st>>>(ww, n_ecs);
-            k_qm_gh<<<nblk(n_gtab, TPB), TPB, 0, st>>>(qs, gptr, gmem, phi, n_genes, n_haps, phi_gh);
-            if (nlg) k_qm_ghlong<<<nlg, TPB, 0, st>>>(qs, long_genes, gptr, gmem, phi, n_haps, hp, phi_gh);
-            k_qm_g<<<nblk((u64)n_genes + (phi_t ? n_loci : 0u), TPB), TPB, 0, st>>>(qs, phi_gh, phi, n_genes, n_loci, n_haps, phi_g, phi_t);
-            if (model == 1u)
-                k_qm_seg1<<<nblk((u64)n_segs * hp, TPB), TPB, 0, st>>>(qs, seg_start, n_segs, rkeys, gnz, ix, da, bits_excl, phi, phi_gh, phi_g, n_haps, hp,
-                                                                      seg_c, seg_x, post);
-            else if (model == 2u)
-                k_qm_seg<2><<<nblk(n_segs, TPB), TPB, 0, st>>>(qs, seg_start, n_segs, rkeys, gnz, ix, da, phi, phi_g, phi_t, n_haps, seg_c, seg_x);
-            else k_qm_seg<3><<<nblk(n_segs, TPB), TPB, 0, st>>>(qs, seg_start, n_segs, rkeys, gnz, ix, da, phi, phi_g, phi_t, n_haps, seg_c, seg_x);
-            if (nlr) k_qm_rowlong<<<nlr, TPB, 0, st>>>(qs, long_rows, ip, segid, seg_x, ww, seg_c, expl_parts + n_eblk);
-            k_qm_row<<<n_eblk, TPB, 0, st>>>(qs, ip, n_ecs, segid, seg_x, ww, seg_c, expl_parts);
-            if (model == 1u) k_qp_post<1><<<nblk(nnz, TPB), TPB, 0, st>>>(nnz, nz_seg, ix, da, bits_excl, phi, phi_t, seg_c, n_haps, post);
-            else if (model == 2u) k_qp_post<2><<<nblk(nnz, TPB), TPB, 0, st>>>(nnz, nz_seg, ix, da, bits_excl, phi, phi_t, seg_c, n_haps, post);
-            else k_qp_post<3><<<nblk(nnz, TPB), TPB, 0, st>>>(nnz, nz_seg, ix, da, bits_excl, phi, phi_t, seg_c, n_haps, post);
+            qm_step(v, mt, model, true);
         }
         CALLCHK(c, hipGetLastError());
     }
@@ -257,17 +189,16 @@ extern "C" int ecb_posterior(int device, uint32_t n_ecs, uint32_t n_loci, uint32
     u64 have = 0;
     for (u64 i = 0; i < nnz; ++i) have += (u64)__builtin_popcount((unsigned)data_a[i]);
     if (have >= (1ull << 32)) return fail(nullptr, ECB_ERR_LIMIT, "more than 2^32-1 set haplotype bits");
-    DevBuf<> ipa, ixa, daa, sc, th, gn, po, bp, rm;
-    std::vector<StageIn> in = {{&ipa, indptr_a, ((u64)n_ecs + 1) * 4}, {&ixa, indices_a, nnz * 4}, {&daa, data_a, nnz * 4}, {&th, theta, plane},
-                               {&po, nullptr, have * 8}};
+    QStage b;
+    DevBuf<> sc, th, gn, po, bp, rm;
+    std::vector<StageIn> in = q_stage(b, QMat{n_ecs, n_loci, n_haps, nnz, indptr_a, indices_a, data_a, 0, 0, nullptr, nullptr, nullptr});
+    in.insert(in.end(), {{&th, theta, plane}, {&po, nullptr, have * 8}});
     if (scale) in.push_back({&sc, scale, plane});
     if (gene) in.push_back({&gn, gene, (u64)n_loci * 4});
     if (bit_ptr) in.push_back({&bp, nullptr, (nnz + 1) * 8});
     if (row_mass) in.push_back({&rm, nullptr, (u64)n_ecs * 8});
-    int rc = stage_in(c, in);
-    if (rc == ECB_OK) rc = ecb_posterior_device(device, n_ecs, n_loci, n_haps, nnz, ipa.p, ixa.p, daa.p, sc.p, th.p, n_genes, gn.p, model, n_bits, po.p,
-                                                bp.p, rm.p);
-    RCCHK(rc);
+    RCCHK(stage_in(c, in));
+    RCCHK(ecb_posterior_device(device, n_ecs, n_loci, n_haps, nnz, b.ipa.p, b.ixa.p, b.daa.p, sc.p, th.p, n_genes, gn.p, model, n_bits, po.p, bp.p, rm.p));
     const bool any = n_ecs && nnz;
     return stage_out(c, {{bit_ptr, &bp, bit_ptr ? (nnz + 1) * 8 : 0}, {post, &po, any ? n_bits * 8 : 0}, {row_mass, &rm, any && row_mass ? (u64)n_ecs * 8 : 0}});
 }

@@ -436,35 +436,25 @@ def quantify(indptr, indices, data, n_loci, n_haps, indptr_n, indices_n, data_n,
     Returns ``(theta[H, T] float64, info)``, theta of the same kind as the input, ``info`` a dict with ``n_iter``, ``delta``, ``explained``
     and ``converged``.  Malformed input, an unknown sample or a NaN, infinite or negative entry of ``scale`` / ``theta_in`` raises
     :class:`EcbError` (``ECB_ERR_CONTRACT``)."""
+    return _quantify((indptr, indices, data, indptr_n, indices_n, data_n), n_loci, n_haps, sample, scale, theta_in, max_iters, tol, device)
+
+
+def _quantify(mats, n_loci, n_haps, sample, scale, theta_in, max_iters, tol, device, grouping=None):
+    """:func:`quantify` and, with ``grouping = (gene, n_genes, model)``, :func:`quantify_model`: each through its own entry point."""
     lib = load()
+    tensors, dev, (ip, ix, da, pn, xn, dn, _), (E, nnz, S, nnz_n), tabs, gn = _quant_args(mats, n_loci, n_haps, scale=scale, theta_in=theta_in,
+                                                                                          gene=grouping and grouping[0])
     s = -1 if sample is None else int(sample)
     it, dl, ex, cv = C.c_uint32(), C.c_double(), C.c_int64(), C.c_uint32()
-    tail = (int(max_iters), float(tol))
-    outs = (C.byref(it), C.byref(dl), C.byref(ex), C.byref(cv))
-    if hasattr(indptr, "data_ptr"):
+    if tensors:
         import torch
-        dev = indptr.device
-        ip, ix, da, pn, xn, dn = (t.contiguous().to(torch.int32) for t in (indptr, indices, data, indptr_n, indices_n, data_n))
-        E, nnz, S, nnz_n = ip.numel() - 1, ix.numel(), pn.numel() - 1, xn.numel()
-        if da.numel() != nnz or dn.numel() != nnz_n:
-            raise ValueError("indices and data differ in length")
-        tabs = [None if t is None else t.to(device=dev, dtype=torch.float64).contiguous() for t in (scale, theta_in)]
-        if any(t is not None and tuple(t.shape) != (n_haps, n_loci) for t in tabs):
-            raise ValueError("scale and theta_in are [n_haps, n_loci]")
-        theta = torch.empty((n_haps, n_loci), dtype=torch.float64, device=dev)
-        _check(lib, lib.ecb_quantify_device(dev.index or 0, E, n_loci, n_haps, nnz, _dev_ptr(ip), _dev_ptr(ix), _dev_ptr(da), S, nnz_n, _dev_ptr(pn),
-                                            _dev_ptr(xn), _dev_ptr(dn), s, _dev_ptr(tabs[0]), _dev_ptr(tabs[1]), tail[0], tail[1], _dev_ptr(theta), *outs))
+        p, d, theta = _dev_ptr, dev.index or 0, torch.empty((n_haps, n_loci), dtype=torch.float64, device=dev)
     else:
-        ip, ix, da, pn, xn, dn = (np.ascontiguousarray(a, dtype=np.int32) for a in (indptr, indices, data, indptr_n, indices_n, data_n))
-        E, nnz, S, nnz_n = len(ip) - 1, len(ix), len(pn) - 1, len(xn)
-        if len(da) != nnz or len(dn) != nnz_n:
-            raise ValueError("indices and data differ in length")
-        tabs = [None if t is None else np.ascontiguousarray(t, dtype=np.float64) for t in (scale, theta_in)]
-        if any(t is not None and t.shape != (n_haps, n_loci) for t in tabs):
-            raise ValueError("scale and theta_in are [n_haps, n_loci]")
-        theta = np.empty((n_haps, n_loci), dtype=np.float64)
-        _check(lib, lib.ecb_quantify(device, E, n_loci, n_haps, nnz, _ptr(ip), _ptr(ix), _ptr(da), S, nnz_n, _ptr(pn), _ptr(xn), _ptr(dn), s,
-                                     _ptr(tabs[0]), _ptr(tabs[1]), tail[0], tail[1], _ptr(theta), *outs))
+        p, d, theta = _ptr, device, np.empty((n_haps, n_loci), dtype=np.float64)
+    fn = getattr(lib, "ecb_quantify" + ("_model" if grouping else "") + ("_device" if tensors else ""))
+    model_args = (int(grouping[1]), p(gn), int(grouping[2])) if grouping else ()
+    _check(lib, fn(d, E, n_loci, n_haps, nnz, p(ip), p(ix), p(da), S, nnz_n, p(pn), p(xn), p(dn), s, p(tabs[0]), p(tabs[1]), int(max_iters), float(tol),
+                   *model_args, p(theta), C.byref(it), C.byref(dl), C.byref(ex), C.byref(cv)))
     return theta, {"n_iter": it.value, "delta": dl.value, "explained": ex.value, "converged": bool(cv.value)}
 
 
@@ -475,42 +465,8 @@ def quantify_model(indptr, indices, data, n_loci, n_haps, indptr_n, indices_n, d
     3 gene -> isoform x allele, 4 the flat step of :func:`quantify`, whose bytes it then returns.  Everything else, the kinds of the arrays
     and the result as for :func:`quantify`.  A gene id outside ``[0, n_genes)`` raises :class:`EcbError` (``ECB_ERR_CONTRACT``), a model
     outside 1..4 ``ECB_ERR_ARG``."""
-    lib = load()
-    s = -1 if sample is None else int(sample)
-    it, dl, ex, cv = C.c_uint32(), C.c_double(), C.c_int64(), C.c_uint32()
-    tail = (int(max_iters), float(tol), int(n_genes))
-    outs = (C.byref(it), C.byref(dl), C.byref(ex), C.byref(cv))
-    if hasattr(indptr, "data_ptr"):
-        import torch
-        dev = indptr.device
-        ip, ix, da, pn, xn, dn = (t.contiguous().to(torch.int32) for t in (indptr, indices, data, indptr_n, indices_n, data_n))
-        gn = torch.as_tensor(gene).to(device=dev, dtype=torch.int32).contiguous()
-        E, nnz, S, nnz_n = ip.numel() - 1, ix.numel(), pn.numel() - 1, xn.numel()
-        if da.numel() != nnz or dn.numel() != nnz_n:
-            raise ValueError("indices and data differ in length")
-        if gn.numel() != n_loci:
-            raise ValueError("gene is [n_loci]")
-        tabs = [None if t is None else t.to(device=dev, dtype=torch.float64).contiguous() for t in (scale, theta_in)]
-        if any(t is not None and tuple(t.shape) != (n_haps, n_loci) for t in tabs):
-            raise ValueError("scale and theta_in are [n_haps, n_loci]")
-        theta = torch.empty((n_haps, n_loci), dtype=torch.float64, device=dev)
-        _check(lib, lib.ecb_quantify_model_device(dev.index or 0, E, n_loci, n_haps, nnz, _dev_ptr(ip), _dev_ptr(ix), _dev_ptr(da), S, nnz_n,
-                                                  _dev_ptr(pn), _dev_ptr(xn), _dev_ptr(dn), s, _dev_ptr(tabs[0]), _dev_ptr(tabs[1]), tail[0], tail[1],
-                                                  tail[2], _dev_ptr(gn), int(model), _dev_ptr(theta), *outs))
-    else:
-        ip, ix, da, pn, xn, dn, gn = (np.ascontiguousarray(a, dtype=np.int32) for a in (indptr, indices, data, indptr_n, indices_n, data_n, gene))
-        E, nnz, S, nnz_n = len(ip) - 1, len(ix), len(pn) - 1, len(xn)
-        if len(da) != nnz or len(dn) != nnz_n:
-            raise ValueError("indices and data differ in length")
-        if gn.shape != (n_loci,):
-            raise ValueError("gene is [n_loci]")
-        tabs = [None if t is None else np.ascontiguousarray(t, dtype=np.float64) for t in (scale, theta_in)]
-        if any(t is not None and t.shape != (n_haps, n_loci) for t in tabs):
-            raise ValueError("scale and theta_in are [n_haps, n_loci]")
-        theta = np.empty((n_haps, n_loci), dtype=np.float64)
-        _check(lib, lib.ecb_quantify_model(device, E, n_loci, n_haps, nnz, _ptr(ip), _ptr(ix), _ptr(da), S, nnz_n, _ptr(pn), _ptr(xn), _ptr(dn), s,
-                                           _ptr(tabs[0]), _ptr(tabs[1]), tail[0], tail[1], tail[2], _ptr(gn), int(model), _ptr(theta), *outs))
-    return theta, {"n_iter": it.value, "delta": dl.value, "explained": ex.value, "converged": bool(cv.value)}
+    return _quantify((indptr, indices, data, indptr_n, indices_n, data_n), n_loci, n_haps, sample, scale, theta_in, max_iters, tol, device,
+                     grouping=(gene, n_genes, model))
 
 
 def posterior(indptr, indices, data, n_loci, n_haps, theta, scale=None, gene=None, n_genes=0, model=4, device=0):
@@ -584,6 +540,25 @@ def _cells_args(indptr, indices, data, indptr_n, indices_n, data_n, cell_keep):
     return False, None, arrs + [keep], sizes
 
 
+def _quant_args(mats, n_loci, n_haps, cell_keep=None, scale=None, theta_in=None, gene=None, tables_first=False):
+    """What the ecquant entry points take, for tensors or numpy: :func:`_cells_args` of the matrices and ``cell_keep``, then the two tables
+    (float64 ``[H, T]`` or None) and the gene array (int32 ``[T]`` or None), checked in the order the entry point has always checked them."""
+    tensors, dev, arrs, sizes = _cells_args(*mats, cell_keep)
+    if tensors:
+        import torch
+        tabs = [None if t is None else t.to(device=dev, dtype=torch.float64).contiguous() for t in (scale, theta_in)]
+        gn = None if gene is None else torch.as_tensor(gene).to(device=dev, dtype=torch.int32).contiguous()
+    else:
+        tabs = [None if t is None else np.ascontiguousarray(t, dtype=np.float64) for t in (scale, theta_in)]
+        gn = None if gene is None else np.ascontiguousarray(gene, dtype=np.int32)
+    for tables in (tables_first, not tables_first):
+        if tables and any(t is not None and tuple(t.shape) != (n_haps, n_loci) for t in tabs):
+            raise ValueError("scale and theta_in are [n_haps, n_loci]")
+        if not tables and gn is not None and tuple(gn.shape) != (n_loci,):
+            raise ValueError("gene is [n_loci]")
+    return tensors, dev, arrs, sizes, tabs, gn
+
+
 def cell_support(indptr, indices, data, n_loci, n_haps, indptr_n, indices_n, data_n, cell_keep=None, device=0, count_only=False):
     """The targets detected per cell (``ecb_cell_support`` / ``ecb_cell_support_device``): for every column c of CSC N, the loci at which an EC
     the cell counts (> 0) holds a mask other than 0, ascending.  ``cell_keep``: ``[n_samples]``, non-zero = this cell, None = every cell.
@@ -622,29 +597,32 @@ def quantify_cells(indptr, indices, data, n_loci, n_haps, indptr_n, indices_n, d
     device one.  Returns ``(cell_ptr int64 [S + 1], slot_locus int32 [n_slots], theta float64 [n_slots, H], info)`` of the same kind as the
     input; ``info`` is a dict of per-cell arrays ``n_iter`` (uint32; int64 for tensors), ``delta`` (float64), ``explained`` (int64) and ``converged`` (bool).
     The support is sized by :func:`cell_support` first, unless the caller passes the ``n_slots`` it learned there."""
+    return _quantify_cells((indptr, indices, data, indptr_n, indices_n, data_n), n_loci, n_haps, cell_keep, scale, theta_in, max_iters, tol, budget_bytes,
+                           device, n_slots)
+
+
+def _quantify_cells(mats, n_loci, n_haps, cell_keep, scale, theta_in, max_iters, tol, budget_bytes, device, n_slots, grouping=None):
+    """:func:`quantify_cells` and, with ``grouping = (gene, n_genes, model)``, :func:`quantify_cells_model`: each through its own entry point."""
     lib = load()
-    tensors, dev, (ip, ix, da, pn, xn, dn, keep), (E, nnz, S, nnz_n) = _cells_args(indptr, indices, data, indptr_n, indices_n, data_n, cell_keep)
-    if tensors:
-        import torch
-        tabs = [None if t is None else t.to(device=dev, dtype=torch.float64).contiguous() for t in (scale, theta_in)]
-    else:
-        tabs = [None if t is None else np.ascontiguousarray(t, dtype=np.float64) for t in (scale, theta_in)]
-    if any(t is not None and tuple(t.shape) != (n_haps, n_loci) for t in tabs):
-        raise ValueError("scale and theta_in are [n_haps, n_loci]")
+    tensors, dev, (ip, ix, da, pn, xn, dn, keep), (E, nnz, S, nnz_n), tabs, gn = _quant_args(mats, n_loci, n_haps, cell_keep, scale, theta_in,
+                                                                                             gene=grouping and grouping[0], tables_first=True)
     if n_slots is None:
         n_slots = int(cell_support(ip, ix, da, n_loci, n_haps, pn, xn, dn, keep, device, count_only=True)[0][-1])
     if tensors:
-        fn, p, d = lib.ecb_quantify_cells_device, _dev_ptr, dev.index or 0
+        import torch
+        p, d = _dev_ptr, dev.index or 0
         new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)  # noqa: E731
         i64, i32, u32, f64, u8 = torch.int64, torch.int32, torch.int32, torch.float64, torch.uint8
     else:
-        fn, p, d = lib.ecb_quantify_cells, _ptr, device
+        p, d = _ptr, device
         new = lambda shape, dt: np.empty(shape, dtype=dt)                 # noqa: E731
         i64, i32, u32, f64, u8 = np.int64, np.int32, np.uint32, np.float64, np.uint8
+    fn = getattr(lib, "ecb_quantify_cells" + ("_model" if grouping else "") + ("_device" if tensors else ""))
+    model_args = (int(grouping[1]), p(gn), int(grouping[2])) if grouping else ()
     cell_ptr, slot_locus, theta = new(S + 1, i64), new(n_slots, i32), new((n_slots, n_haps), f64)
     it, dl, ex, cv = new(S, u32), new(S, f64), new(S, i64), new(S, u8)
     _check(lib, fn(d, E, n_loci, n_haps, nnz, p(ip), p(ix), p(da), S, nnz_n, p(pn), p(xn), p(dn), p(keep), p(tabs[0]), p(tabs[1]), int(max_iters),
-                   float(tol), int(budget_bytes), n_slots, p(cell_ptr), p(slot_locus), p(theta), p(it), p(dl), p(ex), p(cv)))
+                   float(tol), int(budget_bytes), *model_args, n_slots, p(cell_ptr), p(slot_locus), p(theta), p(it), p(dl), p(ex), p(cv)))
     if tensors:
         it = it.to(torch.int64).bitwise_and(0xFFFFFFFF)                  # (the uint32 the library wrote, in a type torch computes with)
     return cell_ptr, slot_locus, theta, {"n_iter": it, "delta": dl, "explained": ex, "converged": cv != 0}
@@ -658,37 +636,8 @@ def quantify_cells_model(indptr, indices, data, n_loci, n_haps, indptr_n, indice
     only, so a member the cell does not touch contributes nothing, whatever ``theta_in`` holds there.  Everything else, the kinds of the
     arrays and the result as for :func:`quantify_cells`.  A gene id outside ``[0, n_genes)`` raises :class:`EcbError` (``ECB_ERR_CONTRACT``),
     a model outside 1..4 ``ECB_ERR_ARG``."""
-    lib = load()
-    tensors, dev, (ip, ix, da, pn, xn, dn, keep), (E, nnz, S, nnz_n) = _cells_args(indptr, indices, data, indptr_n, indices_n, data_n, cell_keep)
-    if tensors:
-        import torch
-        tabs = [None if t is None else t.to(device=dev, dtype=torch.float64).contiguous() for t in (scale, theta_in)]
-        gn = torch.as_tensor(gene).to(device=dev, dtype=torch.int32).contiguous()
-    else:
-        tabs = [None if t is None else np.ascontiguousarray(t, dtype=np.float64) for t in (scale, theta_in)]
-        gn = np.ascontiguousarray(gene, dtype=np.int32)
-    if any(t is not None and tuple(t.shape) != (n_haps, n_loci) for t in tabs):
-        raise ValueError("scale and theta_in are [n_haps, n_loci]")
-    if tuple(gn.shape) != (n_loci,):
-        raise ValueError("gene is [n_loci]")
-    if n_slots is None:
-        n_slots = int(cell_support(ip, ix, da, n_loci, n_haps, pn, xn, dn, keep, device, count_only=True)[0][-1])
-    if tensors:
-        fn, p, d = lib.ecb_quantify_cells_model_device, _dev_ptr, dev.index or 0
-        new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)  # noqa: E731
-        i64, i32, u32, f64, u8 = torch.int64, torch.int32, torch.int32, torch.float64, torch.uint8
-    else:
-        fn, p, d = lib.ecb_quantify_cells_model, _ptr, device
-        new = lambda shape, dt: np.empty(shape, dtype=dt)                 # noqa: E731
-        i64, i32, u32, f64, u8 = np.int64, np.int32, np.uint32, np.float64, np.uint8
-    cell_ptr, slot_locus, theta = new(S + 1, i64), new(n_slots, i32), new((n_slots, n_haps), f64)
-    it, dl, ex, cv = new(S, u32), new(S, f64), new(S, i64), new(S, u8)
-    _check(lib, fn(d, E, n_loci, n_haps, nnz, p(ip), p(ix), p(da), S, nnz_n, p(pn), p(xn), p(dn), p(keep), p(tabs[0]), p(tabs[1]), int(max_iters),
-                   float(tol), int(budget_bytes), int(n_genes), p(gn), int(model), n_slots, p(cell_ptr), p(slot_locus), p(theta), p(it), p(dl), p(ex),
-                   p(cv)))
-    if tensors:
-        it = it.to(torch.int64).bitwise_and(0xFFFFFFFF)                  # (the uint32 the library wrote, in a type torch computes with)
-    return cell_ptr, slot_locus, theta, {"n_iter": it, "delta": dl, "explained": ex, "converged": cv != 0}
+    return _quantify_cells((indptr, indices, data, indptr_n, indices_n, data_n), n_loci, n_haps, cell_keep, scale, theta_in, max_iters, tol, budget_bytes,
+                           device, n_slots, grouping=(gene, n_genes, model))
 
 
 def combine(parts, n_loci, n_haps, n_samples, device=0):

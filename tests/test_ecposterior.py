@@ -165,7 +165,12 @@ def test_the_constants_the_new_kernels_share_are_the_ones_the_tests_straddle_and
     assert [d.strip() for d in re.findall(r"constexpr\s+u32\s+Q_LONG_GENE\s*=\s*([^;,]+);", open(os.path.join(csrc, "quant_model.inc")).read())] == [str(Q_LONG_GENE)]
     # ... and branches on the shared ones where the row pass does: short rows by a lane through the tile, long rows by a workgroup
     assert len(re.findall(r"b - a <= Q_LONG_ROW", src)) == 1 and len(re.findall(r"> Q_LONG_ROW\)", src)) == 1 and "v[Q_TILE]" in src
-    assert "k_qm_ghlong" in src and "k_qm_rowlong" in src and "q_block_sum" in src
+    # (the long genes and long rows of the chain: quant_model.inc's qm_step, which this file runs once; the long rows' sum: quant.inc's q_long_row_sum)
+    model, flat = (open(os.path.join(csrc, f)).read() for f in ("quant_model.inc", "quant.inc"))
+    step = model.split("void qm_step(")[1].split("\n}\n")[0]
+    assert len(re.findall(r"\bqm_step\(", src)) == 1 and len(re.findall(r"k_qm_ghlong<<<", step)) == 1 and len(re.findall(r"k_qm_rowlong<<<", step)) == 1
+    assert len(re.findall(r"k_qm_ghlong<<<", model)) == 1 and len(re.findall(r"k_qm_rowlong<<<", model)) == 1
+    assert "q_long_row_sum(s, " in src and "q_block_sum" in flat.split("double q_long_row_sum(")[1].split("\n}\n")[0]
     assert [d.strip() for d in re.findall(r"QP_ERR_THETA\s*=\s*([^ ,}]+)", src)] == ["8u"]            # beside Q_ERR_SCALE 1, Q_ERR_THETA 2, Q_ERR_GENE 4
     for text in (src, open(os.path.join(csrc, "ecb.hip")).read().split("k_cvv_bits")[1].split("k_iota")[0]):
         assert "atomicAdd(reinterpret_cast<double" not in text and "unsafeAtomicAdd" not in text and "hipGraph" not in text and not re.search(r"\basm\b", text)

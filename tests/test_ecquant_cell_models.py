@@ -159,7 +159,10 @@ def test_constants_the_cell_model_tests_straddle():
     assert int(re.search(r"constexpr int TPB = (\d+);", main).group(1)) == TPB
     assert main.index('#include "quant_cells.inc"') < main.index('#include "quant_cells_model.inc"') and len(re.findall(r'^#include "quant_cells_model\.inc"', main, re.M)) == 1
     # the thresholds are the ones the kernels branch on; no sum is a float atomic; plain launches
-    assert "b - a > Q_LONG_GENE" in mine and "gptr[g + 1] - gptr[g] > Q_LONG_GENE" in mine and "b - a <= QC_LONG_ROW" in mine and "b - a > QC_LONG_COL" in mine
+    # (a long group is left to its workgroup where a long gene is: in quant_model.inc's qm_gh_sum, the body k_qm_gh and k_qcm_gh share)
+    assert len(re.findall(r"b - a > Q_LONG_GENE", model)) == 1 and "b - a > Q_LONG_GENE" in model.split("void qm_gh_sum(")[1].split("\n}\n")[0]
+    assert "qm_gh_sum(gptr, gmem" in mine.split("void k_qcm_gh(")[1].split("\n}\n")[0]
+    assert "gptr[g + 1] - gptr[g] > Q_LONG_GENE" in mine and "b - a <= QC_LONG_ROW" in mine and "b - a > QC_LONG_COL" in mine
     assert "atomicAdd(reinterpret_cast<double" not in mine and "unsafeAtomicAdd" not in mine and "hipGraph" not in mine and "atomicAdd(&d" not in mine
     assert per_x_bytes(2, 4) == 128 and per_x_bytes(2, 1) == 128 + 104 + 32
 
