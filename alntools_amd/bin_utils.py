@@ -10,10 +10,16 @@ data = haplotype bitmask); N as CSC (``len(indptr)``, ``nnz``, indptr, indices =
 """
 from __future__ import annotations
 
+import contextlib
 import os
+import time
 from struct import pack, unpack_from
 
 import numpy as np
+
+from . import utils
+
+LOG = utils.get_logger()
 
 
 class ECMatrices(object):
@@ -71,6 +77,73 @@ def ecsave2(ec_filename, m):
     """Write ``m`` (:class:`ECMatrices`) as EC format 2 -- same bytes as the reference writer."""
     with open(ec_filename, 'wb') as f:
         f.write(ecsave2_bytes(m))
+
+
+def write_bin(ec_filename, m):
+    """``m`` as ``ec_filename``, whole or not at all: the bytes are made first, and a file that could not be finished is removed
+    before the failure is raised again."""
+    b = ecsave2_bytes(m)
+    try:
+        with open(ec_filename, 'wb') as fh:
+            fh.write(b)
+    except BaseException:
+        if os.path.exists(ec_filename):
+            os.remove(ec_filename)
+        raise
+
+
+#: what a command does with a failure, after its ``Error: ...`` line: raise it again -- a KeyError shown by its argument (``KEY``) or as
+#: ``str()`` shows it (``RAISE``) -- or return normally, as the reference's commands do (``SWALLOW``)
+KEY, RAISE, SWALLOW = "key", "raise", "swallow"
+
+
+@contextlib.contextmanager
+def command(failure, created=None, written=()):
+    """The shell of a command: the clock, the closing ``<created> created in total time`` line (``created`` None: no such line) and,
+    for a failure, the removal of the files in ``written`` -- the ones this run has opened so far, never another -- the ``Error: ...``
+    line and what ``failure`` (``KEY``, ``RAISE`` or ``SWALLOW``) says happens then."""
+    try:
+        start_time = time.time()
+        yield
+        if created is not None:
+            LOG.info("{} created in total time: {}".format(created, utils.format_time(start_time, time.time())))
+    except Exception as e:
+        for f in written:
+            try:
+                os.remove(f)
+            except OSError:
+                pass
+        LOG.error("Error: {}".format(e.args[0] if failure == KEY and isinstance(e, KeyError) and e.args else str(e)))
+        if failure != SWALLOW:
+            raise
+
+
+def log_saving(first, m, *rest, samples="Number of samples: {:,}"):
+    """The lines ahead of a save: ``first``, the haplotypes, the targets, the samples (``samples`` None: not these) and the command's own."""
+    LOG.info(first)
+    LOG.info("Number of haplotypes: {:,}".format(m.num_haplotypes))
+    LOG.info("Number of reference targets: {:,}".format(m.num_loci))
+    if samples is not None:
+        LOG.info(samples.format(m.num_samples))
+    for line in rest:
+        LOG.info(line)
+
+
+def sample_column(m, sample, ec_filename):
+    """The column of the sample named ``sample`` (None stays None: all of them); a name the ``.bin`` does not hold is a KeyError."""
+    if sample is None:
+        return None
+    if sample not in m.sname:
+        raise KeyError("sample {} is not in {}".format(sample, ec_filename))
+    return m.sname.index(sample)
+
+
+def check_model(model, groups):
+    """What ``ecquant`` and ``ecquant-cells`` refuse before they read anything: a model other than 1..4, or 1..3 without a group file."""
+    if model not in (1, 2, 3, 4):
+        raise ValueError("model {} is not one of 1, 2, 3, 4".format(model))
+    if model != 4 and groups is None:
+        raise ValueError("model {} needs a group file (-g/--groups)".format(model))
 
 
 def ecload(ec_filename):
@@ -171,11 +244,7 @@ def ecbundle(ec_filename, grp_filename, out_filename, device=0):
     with equal (group, mask) sets are one EC, numbered by first appearance, counts add per (EC, sample).  The output's targets are the
     groups in file order, each as long as its longest member; haplotypes and samples are copied.  Any failure is logged as
     ``Error: ...``, no file is written and the exception is raised again (the command line exits with status 1)."""
-    import time
-    from . import utils
-    LOG = utils.get_logger()
-    try:
-        start_time = time.time()
+    with command(KEY, created=out_filename):
         LOG.info("Loading {}...".format(ec_filename))
         m = ecload(ec_filename)
         gname, map_ptr, map_idx, lengths = group_map(m, grp_filename)
@@ -186,24 +255,10 @@ def ecbundle(ec_filename, grp_filename, out_filename, device=0):
         A_N = ecb.bundle(m.indptrA, m.indicesA, m.dataA, m.indptrN, m.indicesN, m.dataN, m.num_loci, m.num_haplotypes, len(gname),
                          map_ptr, map_idx, device=device)
         out = ECMatrices(m.hname, gname, lengths, m.sname, *A_N)
-        LOG.info("Saving to {}...".format(out_filename))
-        LOG.info("Number of haplotypes: {:,}".format(out.num_haplotypes))
-        LOG.info("Number of reference targets: {:,}".format(out.num_loci))
-        LOG.info("Number of samples: {:,}".format(out.num_samples))
-        LOG.info("Number of equivalence classes: {:,} (from {:,} rows)".format(out.num_reads, m.num_reads))
-        b = ecsave2_bytes(out)
-        try:
-            with open(out_filename, 'wb') as fh:
-                fh.write(b)
-        except BaseException:
-            if os.path.exists(out_filename):
-                os.remove(out_filename)
-            raise
+        log_saving("Saving to {}...".format(out_filename), out,
+                   "Number of equivalence classes: {:,} (from {:,} rows)".format(out.num_reads, m.num_reads))
+        write_bin(out_filename, out)
         LOG.info("Saving completed")
-        LOG.info("{} created in total time: {}".format(out_filename, utils.format_time(start_time, time.time())))
-    except Exception as e:
-        LOG.error("Error: {}".format(e.args[0] if isinstance(e, KeyError) and e.args else str(e)))
-        raise
 
 
 def named_samples(m, samples=None, samples_file=None):
@@ -234,11 +289,7 @@ def ecselect(ec_filename, out_filename, row_class=None, samples=None, samples_fi
     their order; targets, lengths and haplotypes are copied, the samples are the kept ones in the input's order.  A result without a
     sample or without a read is refused.  Any failure is logged as ``Error: ...``, no file is written and the exception is raised again
     (the command line exits with status 1)."""
-    import time
-    from . import utils
-    LOG = utils.get_logger()
-    try:
-        start_time = time.time()
+    with command(KEY, created=out_filename):
         LOG.info("Loading {}...".format(ec_filename))
         m = ecload(ec_filename)
         named = named_samples(m, samples, samples_file)
@@ -253,24 +304,10 @@ def ecselect(ec_filename, out_filename, row_class=None, samples=None, samples_fi
             raise ValueError("no sample left")
         if out.num_reads == 0:
             raise ValueError("no read left")
-        LOG.info("Saving to {}...".format(out_filename))
-        LOG.info("Number of haplotypes: {:,}".format(out.num_haplotypes))
-        LOG.info("Number of reference targets: {:,}".format(out.num_loci))
-        LOG.info("Number of samples: {:,} (from {:,})".format(out.num_samples, m.num_samples))
-        LOG.info("Number of ECs: {:,} (from {:,} rows)".format(out.num_reads, m.num_reads))
-        b = ecsave2_bytes(out)
-        try:
-            with open(out_filename, 'wb') as fh:
-                fh.write(b)
-        except BaseException:
-            if os.path.exists(out_filename):
-                os.remove(out_filename)
-            raise
+        log_saving("Saving to {}...".format(out_filename), out, "Number of samples: {:,} (from {:,})".format(out.num_samples, m.num_samples),
+                   "Number of ECs: {:,} (from {:,} rows)".format(out.num_reads, m.num_reads), samples=None)
+        write_bin(out_filename, out)
         LOG.info("Saving completed")
-        LOG.info("{} created in total time: {}".format(out_filename, utils.format_time(start_time, time.time())))
-    except Exception as e:
-        LOG.error("Error: {}".format(e.args[0] if isinstance(e, KeyError) and e.args else str(e)))
-        raise
 
 
 def genotype_mask(m, gt_filename, gname, groups):
@@ -303,11 +340,8 @@ def apply_genotypes(ec_filename, gt_filename, grp_filename, out_filename, device
     empty rows.  N: a multisample file's is written back as it was read; a single sample's goes through the reference's dense count
     vector (``ecload`` / ``ecsave2``: duplicates added, zero counts dropped).  Any failure is logged as ``Error: ...`` and no file is
     written, as in the reference (which returns normally then)."""
-    import time
-    from . import ecb, utils
-    LOG = utils.get_logger()
-    try:
-        start_time = time.time()
+    from . import ecb
+    with command(SWALLOW, created=out_filename):
         LOG.info("Loading {}...".format(ec_filename))
         m = ecload(ec_filename)
         gname, groups = load_groups(m, grp_filename)
@@ -323,19 +357,10 @@ def apply_genotypes(ec_filename, gt_filename, grp_filename, out_filename, device
             m.indptrN = np.array([0, len(rows)], dtype=np.int32)
             m.indicesN, m.dataN = rows.astype(np.int32), count[rows].astype(int).astype(np.int32)
             converted = True
-        LOG.info("Saviing to {}...".format(out_filename))             # (sic: the reference's line)
-        LOG.info("Number of haplotypes: {:,}".format(m.num_haplotypes))
-        LOG.info("Number of reference targets: {:,}".format(m.num_loci))
-        LOG.info("Number of samples: {:,}".format(m.num_samples))
-        LOG.info("Saving alignment incidence matrix...")
-        LOG.info("Saving EC count matrix...")
-        if converted:
-            LOG.info('N matrix converted to csc_matrix.')
+        log_saving("Saviing to {}...".format(out_filename), m,          # (sic: the reference's line)
+                   "Saving alignment incidence matrix...", "Saving EC count matrix...", *(['N matrix converted to csc_matrix.'] if converted else []))
         ecsave2(out_filename, m)
         LOG.info("Saving completed")
-        LOG.info("{} created in total time: {}".format(out_filename, utils.format_time(start_time, time.time())))
-    except Exception as e:
-        LOG.error("Error: {}".format(str(e)))
 
 
 def counts_table(lname, hname, aln, uniq, locus_uniq):
@@ -353,27 +378,16 @@ def count_alignments(ec_filename, out_filename, sample=None, device=0):
     alignment counts, allele-unique counts and locus-unique counts per target, counted on the GPU (``ecb.count_alignments``) and written
     as the reference's table.  A multisample file, on which the reference raises, is counted over all its samples, or over the one
     named ``sample``.  A failure is logged as ``Error: ...`` and raised again."""
-    import time
-    from . import ecb, utils
-    LOG = utils.get_logger()
-    try:
-        start_time = time.time()
+    from . import ecb
+    with command(KEY, created=out_filename):
         LOG.info("Loading {}...".format(ec_filename))
         m = ecload(ec_filename)
-        col = None
-        if sample is not None:
-            if sample not in m.sname:
-                raise KeyError("sample {} is not in {}".format(sample, ec_filename))
-            col = m.sname.index(sample)
+        col = sample_column(m, sample, ec_filename)
         LOG.info("Counting alignments...")
         aln, uniq, locus_uniq = ecb.count_alignments(m.indptrA, m.indicesA, m.dataA, m.num_loci, m.num_haplotypes, m.indptrN, m.indicesN,
                                                      m.dataN, sample=col, device=device)
         with open(out_filename, 'w') as fh:
             fh.write(counts_table(m.lname, m.hname, aln, uniq, locus_uniq))
-        LOG.info("{} created in total time: {}".format(out_filename, utils.format_time(start_time, time.time())))
-    except Exception as e:
-        LOG.error("Error: {}".format(e.args[0] if isinstance(e, KeyError) and e.args else str(e)))
-        raise
 
 
 def quant_table(lname, hname, theta):
@@ -437,23 +451,13 @@ def ecquant(ec_filename, out_filename, sample=None, use_lengths=False, max_iters
     ``ecb_csr_to_hapcsc_values``), zeros stored, so the file's incidence is the ``.bin``'s (``hapcsc``: tests may pass a factory that takes
     the values in bit order and returns the conversion ``emase_h5.save`` is to use).  A failure is logged as ``Error: ...`` and raised again; no file is written then: when
     either file cannot be written, neither is left behind."""
-    import time
-    from . import ecb, utils
-    LOG = utils.get_logger()
-    written = []
-    try:
-        start_time = time.time()
-        if model not in (1, 2, 3, 4):
-            raise ValueError("model {} is not one of 1, 2, 3, 4".format(model))
-        if model != 4 and groups is None:
-            raise ValueError("model {} needs a group file (-g/--groups)".format(model))
+    from . import ecb
+    written = []                               # (a file that could not be finished, and the one written before it; never one this run did not open)
+    with command(KEY, created=out_filename, written=written):
+        check_model(model, groups)
         LOG.info("Loading {}...".format(ec_filename))
         m = ecload(ec_filename)
-        col = None
-        if sample is not None:
-            if sample not in m.sname:
-                raise KeyError("sample {} is not in {}".format(sample, ec_filename))
-            col = m.sname.index(sample)
+        col = sample_column(m, sample, ec_filename)
         args = (m.indptrA, m.indicesA, m.dataA, m.num_loci, m.num_haplotypes, m.indptrN, m.indicesN, m.dataN)
         gene = names = None
         if model != 4:
@@ -484,15 +488,6 @@ def ecquant(ec_filename, out_filename, sample=None, use_lengths=False, max_iters
         with open(out_filename, 'w') as fh:
             written.append(out_filename)
             fh.write(table)
-        LOG.info("{} created in total time: {}".format(out_filename, utils.format_time(start_time, time.time())))
-    except Exception as e:
-        for f in written:                      # (a file that could not be finished, and the one written before it; never one this run did not open)
-            try:
-                os.remove(f)
-            except OSError:
-                pass
-        LOG.error("Error: {}".format(e.args[0] if isinstance(e, KeyError) and e.args else str(e)))
-        raise
 
 
 def cells_table(sname, lname, hname, cell_ptr, slot_locus, theta):
@@ -526,15 +521,8 @@ def ecquant_cells(ec_filename, out_filename, samples=None, samples_file=None, us
     per cell (:func:`gene_ids`, ``ecb.quantify_cells_model``: the sums over a gene run over the cell's own targets); without ``groups`` they
     are refused by name.  ``model`` 4, the default, is the flat step, and ``groups`` then changes nothing.  A failure is logged as
     ``Error: ...`` and raised again; no file is written then."""
-    import time
-    from . import utils
-    LOG = utils.get_logger()
-    try:
-        start_time = time.time()
-        if model not in (1, 2, 3, 4):
-            raise ValueError("model {} is not one of 1, 2, 3, 4".format(model))
-        if model != 4 and groups is None:
-            raise ValueError("model {} needs a group file (-g/--groups)".format(model))
+    with command(KEY, created=out_filename):
+        check_model(model, groups)
         LOG.info("Loading {}...".format(ec_filename))
         m = ecload(ec_filename)
         keep = named_samples(m, samples, samples_file)
@@ -562,17 +550,11 @@ def ecquant_cells(ec_filename, out_filename, samples=None, samples_file=None, us
         if rep is not None:
             with open(report, 'w') as fh:
                 fh.write(rep)
-        LOG.info("{} created in total time: {}".format(out_filename, utils.format_time(start_time, time.time())))
-    except Exception as e:
-        LOG.error("Error: {}".format(e.args[0] if isinstance(e, KeyError) and e.args else str(e)))
-        raise
 
 
 def ecdump(ec_filename):
     """``alntools ecdump`` (``bin_utils.py:959-976``): the shapes of a ``.bin``, as the reference's log lines.  Host only."""
-    from . import utils
-    LOG = utils.get_logger()
-    try:
+    with command(SWALLOW):
         LOG.info("Loading {}...".format(ec_filename))
         m = ecload(ec_filename)
         LOG.info("Number of reference transcripts (or targets): {:,}".format(m.num_loci))
@@ -586,8 +568,6 @@ def ecdump(ec_filename):
             LOG.info("Shape of EC count matrix: {:,} x {:,}".format(m.num_reads, 1))
         else:
             LOG.error("Error: Something is wrong with EC count matrix")
-    except Exception as e:
-        LOG.error("Error: {}".format(str(e)))
 
 
 class MergePlan(object):
@@ -659,11 +639,7 @@ def ecmerge(ec_files, ec_out, device=0):
     (``ecb.combine``): rows with equal (column, haplotype mask) sets are one EC, numbered by first appearance over the files in
     order, counts add per (EC, sample) and zero sums are dropped.  Any failure is logged as ``Error: ...``, no file is written and
     the exception is raised again (the command line exits with status 1)."""
-    import time
-    from . import utils
-    LOG = utils.get_logger()
-    try:
-        start_time = time.time()
+    with command(RAISE, created=ec_out):
         ms = []
         for f in ec_files:
             LOG.info("Loading {}...".format(f))
@@ -676,21 +652,7 @@ def ecmerge(ec_files, ec_out, device=0):
                  for m, tm, sm in zip(ms, plan.target_maps, plan.sample_maps)]
         A_N = ecb.combine(parts, len(plan.lname), len(plan.hname), len(plan.sname), device=device)
         out = ECMatrices(plan.hname, plan.lname, plan.lengths, plan.sname, *A_N)
-        LOG.info("Saving to {}...".format(ec_out))
-        LOG.info("Number of haplotypes: {:,}".format(out.num_haplotypes))
-        LOG.info("Number of reference targets: {:,}".format(out.num_loci))
-        LOG.info("Number of samples: {:,}".format(out.num_samples))
-        LOG.info("Number of equivalence classes: {:,} (from {:,} rows)".format(out.num_reads, sum(m.num_reads for m in ms)))
-        b = ecsave2_bytes(out)
-        try:
-            with open(ec_out, 'wb') as fh:
-                fh.write(b)
-        except BaseException:
-            if os.path.exists(ec_out):
-                os.remove(ec_out)
-            raise
+        log_saving("Saving to {}...".format(ec_out), out,
+                   "Number of equivalence classes: {:,} (from {:,} rows)".format(out.num_reads, sum(m.num_reads for m in ms)))
+        write_bin(ec_out, out)
         LOG.info("Saving completed")
-        LOG.info("{} created in total time: {}".format(ec_out, utils.format_time(start_time, time.time())))
-    except Exception as e:
-        LOG.error("Error: {}".format(str(e)))
-        raise

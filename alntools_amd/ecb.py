@@ -57,6 +57,7 @@ QUANT_POST_SYMBOLS = ("ecb_posterior_device", "ecb_posterior", "ecb_csr_to_hapcs
 #: ``ecb_select``'s row classes (include/ecb_select.h)
 ROW_CLASSES = {None: 0, "all": 0, "unique": 1, "locus-unique": 2, "multi": 3}
 ABI_VERSION = 4            # include/ecb.h: ECB_ABI_VERSION
+ECB_ERR_CONTRACT = -5      # include/ecb.h
 
 
 class EcbError(RuntimeError):
@@ -96,6 +97,82 @@ class CombinePart(C.Structure):
                     "indptr_a", "indices_a", "data_a", "indptr_n", "indices_n", "data_n", "target_map", "sample_map")]
 
 
+_vp, _u64, _sz, _u32, _i64, _int, _dbl, _P = C.c_void_p, C.c_uint64, C.c_size_t, C.c_uint32, C.c_int64, C.c_int, C.c_double, C.POINTER
+_HEAD = [_int, _u32, _u32, _u32]                                                  # device, n_ecs, n_loci, n_haps
+_A_N = _HEAD + [_u64, _vp, _vp, _vp, _u32, _u64, _vp, _vp, _vp]                    # ... nnz, CSR A, n_samples, nnz_n, CSC N
+_BATCH = [_vp, _u32, _P(_vp), _P(_u64), _P(_vp), _P(_u64)]
+_INFO = [_P(_u32), _P(_dbl), _P(_i64), _P(_u32)]
+
+
+def _sig(name, argtypes=None, restype=_int, twin=False, optional=False):
+    """One row of :data:`SIGNATURES`.  ``twin``: ``name + "_device"`` has the same signature.  ``optional``: an A/B build named by
+    ``ECB_LIB`` may lack it (a normal build may not)."""
+    return name, argtypes, restype, twin, optional
+
+
+#: what :func:`load` binds: (symbol, argtypes or None, restype, has a ``_device`` twin, optional under ``ECB_LIB``)
+SIGNATURES = (
+    _sig("ecb_abi_version"),
+    _sig("ecb_device_count"),
+    _sig("ecb_create", [_P(Config), _P(_vp)]),
+    _sig("ecb_destroy", [_vp], restype=None),
+    _sig("ecb_reset", [_vp]),
+    _sig("ecb_last_error", [_vp], restype=C.c_char_p),
+    _sig("ecb_push", [_vp, _vp, _vp, _vp, _vp, _sz], twin=True),
+    _sig("ecb_hint_reads", [_vp, _u64]),
+    _sig("ecb_push_cells", [_vp, _vp, _u64, _sz], twin=True),
+    _sig("ecb_verify_device", [_vp, _vp, _vp, _vp, _sz, _P(_u64), _P(_u64)]),
+    _sig("ecb_finalize", [_vp, _P(Sizes)]),
+    _sig("ecb_export", [_vp] * 7, twin=True),
+    _sig("ecb_export_ranges", [_vp, _vp]),
+    _sig("ecb_export_read_ec", [_vp, _vp]),
+    _sig("ecb_export_pairs", [_vp] * 5),
+    _sig("ecb_export_range_minmax", [_vp, _vp, _vp]),
+    _sig("ecb_ms_filter", [_vp, _u32, _i64, _P(MsSizes)]),
+    _sig("ecb_ms_export", [_vp] * 8),
+    _sig("ecb_table_sizes", [_vp, _P(_u64), _P(_u64), _P(_u64)]),
+    _sig("ecb_table_export_device", [_vp, _vp, _vp, _u64]),
+    _sig("ecb_table_merge_device", [_vp, _vp, _u64, _vp, _u64]),
+    _sig("ecb_table_export_parts_device", [_vp, _vp, _vp, _u64, _u32, _P(_u64), _P(_u64)]),
+    _sig("ecb_table_adopt_device", [_vp, _vp, _u64, _vp, _u64]),
+    _sig("ecb_table_rebase_device", [_vp, _vp, _u64, _u64]),
+    _sig("ecb_table_merge_batch_device", _BATCH),
+    _sig("ecb_table_adopt_batch_device", _BATCH),
+    _sig("ecb_export_ec_keys_device", [_vp, _vp]),
+    _sig("ecb_export_firsts_device", [_vp, _vp]),
+    _sig("ecb_assemble_ranges_device", [_vp, _u32] + [_P(_vp)] * 5 + [_P(_u64)] * 2 + [_u64, _u64, _u64, _P(Sizes)]),
+    _sig("ecb_ms_local_triples_device", [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp, _P(_u64)]),
+    _sig("ecb_ms_adopt_triples_device", [_vp, _u32, _P(_vp), _P(_vp), _P(_vp), _P(_u64), _P(_u64)]),
+    _sig("ecb_counters", [_vp, _P(_u64), _P(_u64), _P(_u64)]),
+    _sig("ecb_add_counters", [_vp, _u64, _u64, _u64]),
+    _sig("ecb_profile", [_vp, _int]),
+    _sig("ecb_profile_read", [_vp, _P(_dbl), _P(_u64), _P(_u64)]),
+    _sig("ecb_merge", [_P(_vp), _u32, _vp, _P(Sizes)], optional=True),
+    _sig("ecb_push_device_tiled", [_vp, _vp, _sz], optional=True),
+    _sig("ecb_verify_device_tiled", [_vp, _vp, _sz, _P(_u64), _P(_u64)], optional=True),
+    _sig("ecb_profile_kernel", [_vp], restype=C.c_char_p, optional=True),
+    _sig("ecb_csr_to_hapcsc", _HEAD + [_vp] * 5 + [_u64, _P(_u64)], optional=True),          # (the host entry point is told its room)
+    _sig("ecb_csr_to_hapcsc_device", _HEAD + [_vp] * 5 + [_P(_u64)]),
+    _sig("ecb_hapcsc_to_csr", _HEAD + [_vp, _vp, _u64, _vp, _vp, _vp, _P(_u64)], optional=True),
+    _sig("ecb_hapcsc_to_csr_device", _HEAD + [_vp, _vp, _u64, _vp, _vp, _vp, _P(_u64)]),
+    _sig("ecb_csr_to_hapcsc_values", _HEAD + [_vp] * 7 + [_u64, _P(_u64)], optional=True),
+    _sig("ecb_csr_to_hapcsc_values_device", _HEAD + [_vp] * 7 + [_P(_u64)], optional=True),
+    _sig("ecb_apply_mask", _HEAD + [_u64] + [_vp] * 7 + [_P(_u64)], twin=True, optional=True),
+    _sig("ecb_combine", [_int, _u32, _P(CombinePart), _u32, _u32, _u32] + [_vp] * 6 + [_P(_u64)], twin=True, optional=True),
+    _sig("ecb_salmon_ecs", [_int, _vp, _u64, _u32, _u32, _vp, _vp, _u32, _u32, _u64] + [_vp] * 5 + [_P(_u64)], twin=True, optional=True),
+    _sig("ecb_count_alignments", _A_N + [_i64, _vp, _vp, _vp], twin=True, optional=True),
+    _sig("ecb_bundle", [_int] + [_u32] * 5 + [_u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _u64] + [_vp] * 6 + [_P(_u64)],
+         twin=True, optional=True),
+    _sig("ecb_select", [_int] + [_u32] * 4 + [_u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, C.c_int32, _vp, _i64] + [_vp] * 7 + [_P(_u64)],
+         twin=True, optional=True),
+    _sig("ecb_quantify", _A_N + [_i64, _vp, _vp, _u32, _dbl, _vp] + _INFO, twin=True, optional=True),
+    _sig("ecb_quantify_model", _A_N + [_i64, _vp, _vp, _u32, _dbl, _u32, _vp, _u32, _vp] + _INFO, twin=True, optional=True),
+    _sig("ecb_cell_support", _A_N + [_vp, _vp, _vp, _u64, _P(_u64)], twin=True, optional=True),
+    _sig("ecb_quantify_cells", _A_N + [_vp, _vp, _vp, _u32, _dbl, _u64, _u64] + [_vp] * 7, twin=True, optional=True),
+    _sig("ecb_quantify_cells_model", _A_N + [_vp, _vp, _vp, _u32, _dbl, _u64, _u32, _vp, _u32, _u64] + [_vp] * 7, twin=True, optional=True),
+    _sig("ecb_posterior", _HEAD + [_u64, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _u64, _vp, _vp, _vp], twin=True, optional=True),
+)
+
 _lib = None
 
 
@@ -123,102 +200,14 @@ def load():
     if lib.ecb_abi_version() != ABI_VERSION and not ab:
         raise ImportError("%s has ABI %d, this binding is for ABI %d: rebuild it (python -m alntools_amd.build)"
                           % (LIB_PATH, lib.ecb_abi_version(), ABI_VERSION))
-    vp, u64, sz = C.c_void_p, C.c_uint64, C.c_size_t
-    lib.ecb_abi_version.restype = C.c_int
-    lib.ecb_device_count.restype = C.c_int
-    lib.ecb_create.argtypes = [C.POINTER(Config), C.POINTER(vp)]
-    lib.ecb_destroy.argtypes = [vp]
-    lib.ecb_destroy.restype = None
-    lib.ecb_reset.argtypes = [vp]
-    lib.ecb_last_error.argtypes = [vp]
-    lib.ecb_last_error.restype = C.c_char_p
-    lib.ecb_push.argtypes = [vp, vp, vp, vp, vp, sz]
-    lib.ecb_push_device.argtypes = [vp, vp, vp, vp, vp, sz]
-    lib.ecb_hint_reads.argtypes = [vp, u64]
-    lib.ecb_push_cells.argtypes = [vp, vp, u64, sz]
-    lib.ecb_push_cells_device.argtypes = [vp, vp, u64, sz]
-    lib.ecb_verify_device.argtypes = [vp, vp, vp, vp, sz, C.POINTER(u64), C.POINTER(u64)]
-    lib.ecb_finalize.argtypes = [vp, C.POINTER(Sizes)]
-    lib.ecb_export.argtypes = [vp] + [vp] * 6
-    lib.ecb_export_device.argtypes = [vp] + [vp] * 6
-    lib.ecb_export_ranges.argtypes = [vp, vp]
-    lib.ecb_export_read_ec.argtypes = [vp, vp]
-    lib.ecb_export_pairs.argtypes = [vp, vp, vp, vp, vp]
-    lib.ecb_export_range_minmax.argtypes = [vp, vp, vp]
-    lib.ecb_ms_filter.argtypes = [vp, C.c_uint32, C.c_int64, C.POINTER(MsSizes)]
-    lib.ecb_ms_export.argtypes = [vp] + [vp] * 7
-    lib.ecb_table_sizes.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
-    lib.ecb_table_export_device.argtypes = [vp, vp, vp, u64]
-    lib.ecb_table_merge_device.argtypes = [vp, vp, u64, vp, u64]
-    lib.ecb_table_export_parts_device.argtypes = [vp, vp, vp, u64, C.c_uint32, C.POINTER(u64), C.POINTER(u64)]
-    lib.ecb_table_adopt_device.argtypes = [vp, vp, u64, vp, u64]
-    lib.ecb_table_rebase_device.argtypes = [vp, vp, u64, u64]
-    for f in (lib.ecb_table_merge_batch_device, lib.ecb_table_adopt_batch_device):
-        f.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64)]
-    lib.ecb_export_ec_keys_device.argtypes = [vp, vp]
-    lib.ecb_export_firsts_device.argtypes = [vp, vp]
-    lib.ecb_assemble_ranges_device.argtypes = [vp, C.c_uint32] + [C.POINTER(vp)] * 5 + [C.POINTER(u64)] * 2 + [u64, u64, u64, C.POINTER(Sizes)]
-    lib.ecb_ms_local_triples_device.argtypes = [vp, vp, vp, vp, vp, u64, u64, vp, vp, vp, C.POINTER(u64)]
-    lib.ecb_ms_adopt_triples_device.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
-    lib.ecb_counters.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
-    lib.ecb_add_counters.argtypes = [vp, u64, u64, u64]
-    lib.ecb_profile.argtypes = [vp, C.c_int]
-    lib.ecb_profile_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(u64), C.POINTER(u64)]
-    if not ab or hasattr(lib, "ecb_merge"):
-        lib.ecb_merge.argtypes = [C.POINTER(vp), C.c_uint32, vp, C.POINTER(Sizes)]
-    if not ab or hasattr(lib, "ecb_push_device_tiled"):
-        lib.ecb_push_device_tiled.argtypes = [vp, vp, sz]
-        lib.ecb_verify_device_tiled.argtypes = [vp, vp, sz, C.POINTER(u64), C.POINTER(u64)]
-    if not ab or hasattr(lib, "ecb_profile_kernel"):
-        lib.ecb_profile_kernel.argtypes = [vp]
-        lib.ecb_profile_kernel.restype = C.c_char_p
-    if not ab or hasattr(lib, "ecb_csr_to_hapcsc"):
-        lib.ecb_csr_to_hapcsc.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, u64, C.POINTER(u64)]
-        lib.ecb_hapcsc_to_csr.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, u64, vp, vp, vp, C.POINTER(u64)]
-    if not ab or hasattr(lib, "ecb_apply_mask"):
-        for f in (lib.ecb_apply_mask_device, lib.ecb_apply_mask):
-            f.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64] + [vp] * 7 + [C.POINTER(u64)]
-    if not ab or hasattr(lib, "ecb_combine"):
-        for f in (lib.ecb_combine_device, lib.ecb_combine):
-            f.argtypes = [C.c_int, C.c_uint32, C.POINTER(CombinePart), C.c_uint32, C.c_uint32, C.c_uint32] + [vp] * 6 + [C.POINTER(u64)]
-    if not ab or hasattr(lib, "ecb_salmon_ecs"):
-        for f in (lib.ecb_salmon_ecs_device, lib.ecb_salmon_ecs):
-            f.argtypes = [C.c_int, vp, u64, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, u64] + [vp] * 5 + [C.POINTER(u64)]
-    if not ab or hasattr(lib, "ecb_count_alignments"):
-        for f in (lib.ecb_count_alignments_device, lib.ecb_count_alignments):
-            f.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.c_uint32, u64, vp, vp, vp, C.c_int64, vp, vp, vp]
-    if not ab or hasattr(lib, "ecb_bundle"):
-        for f in (lib.ecb_bundle_device, lib.ecb_bundle):
-            f.argtypes = [C.c_int] + [C.c_uint32] * 5 + [u64, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, u64] + [vp] * 6 + [C.POINTER(u64)]
-    if not ab or hasattr(lib, "ecb_select"):
-        for f in (lib.ecb_select_device, lib.ecb_select):
-            f.argtypes = [C.c_int] + [C.c_uint32] * 4 + [u64, vp, vp, vp, u64, vp, vp, vp, C.c_int32, vp, C.c_int64] + [vp] * 7 + [C.POINTER(u64)]
-    if not ab or hasattr(lib, "ecb_quantify"):
-        for f in (lib.ecb_quantify_device, lib.ecb_quantify):
-            f.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.c_uint32, u64, vp, vp, vp, C.c_int64, vp, vp, C.c_uint32,
-                          C.c_double, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_uint32)]
-    if not ab or hasattr(lib, "ecb_quantify_model"):
-        for f in (lib.ecb_quantify_model_device, lib.ecb_quantify_model):
-            f.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.c_uint32, u64, vp, vp, vp, C.c_int64, vp, vp, C.c_uint32,
-                          C.c_double, C.c_uint32, vp, C.c_uint32, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_int64),
-                          C.POINTER(C.c_uint32)]
-    if not ab or hasattr(lib, "ecb_quantify_cells"):
-        head = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.c_uint32, u64, vp, vp, vp, vp]
-        for f in (lib.ecb_cell_support_device, lib.ecb_cell_support):
-            f.argtypes = head + [vp, vp, u64, C.POINTER(u64)]
-        for f in (lib.ecb_quantify_cells_device, lib.ecb_quantify_cells):
-            f.argtypes = head + [vp, vp, C.c_uint32, C.c_double, u64, u64] + [vp] * 7
-    if not ab or hasattr(lib, "ecb_quantify_cells_model"):
-        for f in (lib.ecb_quantify_cells_model_device, lib.ecb_quantify_cells_model):
-            f.argtypes = ([C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64, vp, vp, vp, C.c_uint32, u64, vp, vp, vp, vp]
-                          + [vp, vp, C.c_uint32, C.c_double, u64, C.c_uint32, vp, C.c_uint32, u64] + [vp] * 7)
-    if not ab or hasattr(lib, "ecb_posterior"):
-        for f in (lib.ecb_posterior_device, lib.ecb_posterior):
-            f.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64, vp, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, u64, vp, vp, vp]
-        lib.ecb_csr_to_hapcsc_values_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64)]
-        lib.ecb_csr_to_hapcsc_values.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64)]
-    lib.ecb_csr_to_hapcsc_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.POINTER(u64)]
-    lib.ecb_hapcsc_to_csr_device.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, u64, vp, vp, vp, C.POINTER(u64)]
+    for name, argtypes, restype, twin, optional in SIGNATURES:
+        for n in ((name + "_device", name) if twin else (name,)):
+            if optional and ab and not hasattr(lib, n):
+                continue
+            f = getattr(lib, n)             # (a normal build that lacks one fails here)
+            f.restype = restype
+            if argtypes is not None:
+                f.argtypes = argtypes
     _lib = lib
     return lib
 
@@ -249,113 +238,173 @@ def tile_tuples(read_id, locus, hapflag, out=None):
     return tiles
 
 
-def csr_to_hapcsc(indptr, indices, data, n_loci, n_haps, nnz=None):
+class _Numpy(object):
+    """What a one-call wrapper asks of the arrays it was handed -- numpy arrays here: the host entry points, on the device the caller
+    numbers.  :func:`_kind` picks this or :class:`_Torch` once per call; the wrapper then has one body for both."""
+    tensors = False
+    i32, i64, u32, f64, u8 = np.int32, np.int64, np.uint32, np.float64, np.uint8
+    ptr = staticmethod(_ptr)
+
+    def __init__(self, device):
+        self.device = device
+
+    def entry(self, lib, name):
+        return getattr(lib, name)
+
+    def arr(self, a, dt):
+        """``a`` as a contiguous array of type ``dt``, of this kind and on this device (None stays None)."""
+        return None if a is None else np.ascontiguousarray(a, dtype=dt)
+
+    def flags(self, a):
+        """uint8 0 / 1, flat, of anything truthy (None stays None)."""
+        return None if a is None else np.ascontiguousarray(np.asarray(a) != 0, dtype=np.uint8).reshape(-1)
+
+    def bytes(self, a):
+        return np.frombuffer(a, dtype=np.uint8) if not isinstance(a, np.ndarray) else np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)
+
+    def empty(self, shape, dt):
+        return np.empty(shape, dtype=dt)
+
+    def zeros(self, shape, dt):
+        return np.zeros(shape, dtype=dt)
+
+
+class _Torch(_Numpy):
+    """The same for tensors: the ``_device`` entry points, on the tensors' own device."""
+    tensors = True
+    ptr = staticmethod(_dev_ptr)
+
+    def __init__(self, dev):
+        import torch
+        self.torch, self.dev, self.device = torch, dev, dev.index or 0
+        self.i32, self.i64, self.f64, self.u8 = torch.int32, torch.int64, torch.float64, torch.uint8
+        self.u32 = torch.int32                  # (torch computes with no uint32: int32 holds the same bytes)
+
+    def entry(self, lib, name):
+        return getattr(lib, name + "_device")
+
+    def arr(self, a, dt):
+        if a is None:
+            return None
+        return (a if isinstance(a, self.torch.Tensor) else self.torch.as_tensor(a)).to(self.dev, dt).contiguous()
+
+    def flags(self, a):
+        return None if a is None else self.torch.as_tensor(a).to(device=self.dev).ne(0).to(self.torch.uint8).contiguous().reshape(-1)
+
+    def bytes(self, a):
+        return a.contiguous().view(self.torch.uint8).reshape(-1)
+
+    def empty(self, shape, dt):
+        return self.torch.empty(shape, dtype=dt, device=self.dev)
+
+    def zeros(self, shape, dt):
+        return self.torch.zeros(shape, dtype=dt, device=self.dev)
+
+
+_torch_kinds = {}
+
+
+def _kind(first, device):
+    """The kind of a call: of its first array, and for numpy arrays on the caller's ``device``."""
+    if not hasattr(first, "data_ptr"):
+        return _Numpy(device)
+    k = _torch_kinds.get(first.device)
+    if k is None:
+        k = _torch_kinds[first.device] = _Torch(first.device)
+    return k
+
+
+def _matrices(k, mats):
+    """CSR A and CSC N ``(indptr, indices, data) x 2`` as int32 of kind ``k`` -> (the six arrays, (E, nnz, S, nnz_n))."""
+    a = [k.arr(x, k.i32) for x in mats]
+    sizes = (len(a[0]) - 1, len(a[1]), len(a[3]) - 1, len(a[4]))
+    if len(a[2]) != sizes[1] or len(a[5]) != sizes[3]:
+        raise ValueError("indices and data differ in length")
+    return a, sizes
+
+
+def _check_tables(tabs, n_loci, n_haps, what):
+    if any(t is not None and tuple(t.shape) != (n_haps, n_loci) for t in tabs):
+        raise ValueError(what + " are [n_haps, n_loci]")
+
+
+def _check_gene(gn, n_loci):
+    if gn is not None and tuple(gn.shape) != (n_loci,):
+        raise ValueError("gene is [n_loci]")
+
+
+def csr_to_hapcsc(indptr, indices, data, n_loci, n_haps, nnz=None, device=0):
     """f-2 on device tensors (int32, CUDA): CSR(bitmask) -> (csc_indptr [H, T+1], csc_indices [total], nnz per haplotype).
     Haplotype h's row indices are ``csc_indices[starts[h]:starts[h+1]]`` (``bin_utils.ec2emase``'s per-haplotype CSC).
     One call when the row-index buffer sized for every non-zero carrying every haplotype (``nnz`` x H) stays below 1 GiB; beyond
-    that (many haplotypes, sparse masks: up to 31 x what is needed) the library is asked for the count of set bits first."""
-    import torch
+    that (many haplotypes, sparse masks: up to 31 x what is needed) the library is asked for the count of set bits first.
+    numpy arrays: :func:`csr_to_hapcsc_host`."""
     lib = load()
-    dev = indptr.device
-    E = indptr.numel() - 1
+    k = _kind(indptr, device)
+    p, fn = k.ptr, k.entry(lib, "ecb_csr_to_hapcsc")
+    ip, ix, da = (k.arr(a, k.i32) for a in (indptr, indices, data))
+    head = (k.device, len(ip) - 1, n_loci, n_haps, p(ip), p(ix), p(da))
+    room = (lambda n: ()) if k.tensors else (lambda n: (n,))      # what differs: only the host entry point is told csc_indices' room
     tot = C.c_uint64()
-    nnz = indices.numel() if nnz is None else int(nnz)
-    cap = nnz * n_haps
-    if cap >= (1 << 28):                             # (a count first: the exact size)
-        _check(lib, lib.ecb_csr_to_hapcsc_device(dev.index or 0, E, n_loci, n_haps, _dev_ptr(indptr), _dev_ptr(indices), _dev_ptr(data),
-                                                 None, None, C.byref(tot)))
+    cap = (len(ix) if nnz is None else int(nnz)) * n_haps
+    if not k.tensors or cap >= (1 << 28):            # what differs: host arrays always get the count first (the exact size)
+        _check(lib, fn(*head, None, None, *room(0), C.byref(tot)))
         cap = tot.value
-    cptr = torch.empty((n_haps, n_loci + 1), dtype=torch.int32, device=dev)
-    cidx = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-    _check(lib, lib.ecb_csr_to_hapcsc_device(dev.index or 0, E, n_loci, n_haps, _dev_ptr(indptr), _dev_ptr(indices), _dev_ptr(data),
-                                             _dev_ptr(cptr), _dev_ptr(cidx), C.byref(tot)))
+    cptr = k.empty((n_haps, n_loci + 1), k.i32)
+    cidx = k.empty(max(cap, 1), k.i32)
+    _check(lib, fn(*head, p(cptr), p(cidx), *room(len(cidx)), C.byref(tot)))
     return cptr, cidx[:tot.value]
 
 
 def csr_to_hapcsc_host(indptr, indices, data, n_loci, n_haps, device=0):
     """f-2 on HOST arrays (``ecb_csr_to_hapcsc``: the library holds the device buffers itself; no PyTorch involved):
     CSR(bitmask) -> (csc_indptr int32 [H, T+1], csc_indices int32 [total])."""
-    lib = load()
-    ip, ix, da = (np.ascontiguousarray(a, dtype=np.int32) for a in (indptr, indices, data))
-    E = len(ip) - 1
-    tot = C.c_uint64()
-    _check(lib, lib.ecb_csr_to_hapcsc(device, E, n_loci, n_haps, _ptr(ip), _ptr(ix), _ptr(da), None, None, 0, C.byref(tot)))
-    cptr = np.empty((n_haps, n_loci + 1), dtype=np.int32)
-    cidx = np.empty(max(tot.value, 1), dtype=np.int32)
-    _check(lib, lib.ecb_csr_to_hapcsc(device, E, n_loci, n_haps, _ptr(ip), _ptr(ix), _ptr(da), _ptr(cptr), _ptr(cidx), len(cidx), C.byref(tot)))
-    return cptr, cidx[:tot.value]
+    return csr_to_hapcsc(indptr, indices, data, n_loci, n_haps, device=device)
 
 
-def csr_to_hapcsc_values(indptr, indices, data, values, n_loci, n_haps):
+def csr_to_hapcsc_values(indptr, indices, data, values, n_loci, n_haps, device=0):
     """:func:`csr_to_hapcsc` with a payload, on device tensors (``ecb_csr_to_hapcsc_values_device``): ``values`` float64, one per set bit of
     the masks in bit order (the non-zeros in storage order, the set bits of one lowest first: :func:`posterior`'s ``post``) ->
-    (csc_indptr [H, T+1], csc_indices [total], csc_data float64 [total]); ``csc_data[k]`` is the value of the entry ``csc_indices[k]`` names."""
-    import torch
+    (csc_indptr [H, T+1], csc_indices [total], csc_data float64 [total]); ``csc_data[k]`` is the value of the entry ``csc_indices[k]`` names.
+    numpy arrays go through ``ecb_csr_to_hapcsc_values`` on ``device``."""
     lib = load()
-    dev = indptr.device
-    E = indptr.numel() - 1
-    va = values.to(device=dev, dtype=torch.float64).contiguous()
+    k = _kind(indptr, device)
+    p, fn = k.ptr, k.entry(lib, "ecb_csr_to_hapcsc_values")
+    ip, ix, da = (k.arr(a, k.i32) for a in (indptr, indices, data))
+    va = k.arr(values, k.f64)
+    head = (k.device, len(ip) - 1, n_loci, n_haps, p(ip), p(ix), p(da))
+    room = (lambda n: ()) if k.tensors else (lambda n: (n,))      # what differs: only the host entry point is told the outputs' room
     tot = C.c_uint64()
-    cptr = torch.empty((n_haps, n_loci + 1), dtype=torch.int32, device=dev)
-    cidx = torch.empty(max(va.numel(), 1), dtype=torch.int32, device=dev)
-    cdat = torch.empty(max(va.numel(), 1), dtype=torch.float64, device=dev)
-    _check(lib, lib.ecb_csr_to_hapcsc_values_device(dev.index or 0, E, n_loci, n_haps, _dev_ptr(indptr), _dev_ptr(indices), _dev_ptr(data), None,
-                                                    None, None, None, C.byref(tot)))
-    if tot.value != va.numel():
-        raise ValueError("values holds %d entries, the matrix has %d set bits" % (va.numel(), tot.value))
-    _check(lib, lib.ecb_csr_to_hapcsc_values_device(dev.index or 0, E, n_loci, n_haps, _dev_ptr(indptr), _dev_ptr(indices), _dev_ptr(data),
-                                                    _dev_ptr(va), _dev_ptr(cptr), _dev_ptr(cidx), _dev_ptr(cdat), C.byref(tot)))
-    return cptr, cidx[:tot.value], cdat[:tot.value]
-
-
-def csr_to_hapcsc_values_host(indptr, indices, data, values, n_loci, n_haps, device=0):
-    """:func:`csr_to_hapcsc_host` with a payload (``ecb_csr_to_hapcsc_values``): ``values`` float64, one per set bit in bit order ->
-    (csc_indptr int32 [H, T+1], csc_indices int32 [total], csc_data float64 [total])."""
-    lib = load()
-    ip, ix, da = (np.ascontiguousarray(a, dtype=np.int32) for a in (indptr, indices, data))
-    va = np.ascontiguousarray(values, dtype=np.float64)
-    E = len(ip) - 1
-    tot = C.c_uint64()
-    _check(lib, lib.ecb_csr_to_hapcsc_values(device, E, n_loci, n_haps, _ptr(ip), _ptr(ix), _ptr(da), None, None, None, None, 0, C.byref(tot)))
+    _check(lib, fn(*head, None, None, None, None, *room(0), C.byref(tot)))
     if tot.value != len(va):
         raise ValueError("values holds %d entries, the matrix has %d set bits" % (len(va), tot.value))
-    cptr = np.empty((n_haps, n_loci + 1), dtype=np.int32)
-    cidx = np.empty(max(tot.value, 1), dtype=np.int32)
-    cdat = np.empty(max(tot.value, 1), dtype=np.float64)
-    _check(lib, lib.ecb_csr_to_hapcsc_values(device, E, n_loci, n_haps, _ptr(ip), _ptr(ix), _ptr(da), _ptr(va), _ptr(cptr), _ptr(cidx), _ptr(cdat),
-                                             len(cidx), C.byref(tot)))
+    cptr = k.empty((n_haps, n_loci + 1), k.i32)
+    cidx = k.empty(max(tot.value, 1), k.i32)
+    cdat = k.empty(max(tot.value, 1), k.f64)
+    _check(lib, fn(*head, p(va), p(cptr), p(cidx), p(cdat), *room(len(cidx)), C.byref(tot)))
     return cptr, cidx[:tot.value], cdat[:tot.value]
 
 
-def hapcsc_to_csr_host(csc_indptr, csc_indices, n_ecs, device=0):
-    """f-2 inverse on HOST arrays (``ecb_hapcsc_to_csr``): per-haplotype CSC -> CSR(bitmask) (indptr, indices, data), int32."""
+csr_to_hapcsc_values_host = csr_to_hapcsc_values       # (the name the host callers know)
+
+
+def hapcsc_to_csr(csc_indptr, csc_indices, n_ecs, device=0):
+    """f-2 inverse on device tensors: per-haplotype CSC -> CSR(bitmask) (``bin_utils.emase2ec``: A = sum 2^h M_h).  numpy arrays go
+    through ``ecb_hapcsc_to_csr`` on ``device``; (indptr, indices, data), int32, of the same kind as the input."""
     lib = load()
-    cptr = np.ascontiguousarray(csc_indptr, dtype=np.int32)
-    cidx = np.ascontiguousarray(csc_indices, dtype=np.int32)
+    k = _kind(csc_indptr, device)
+    p = k.ptr
+    cptr, cidx = k.arr(csc_indptr, k.i32), k.arr(csc_indices, k.i32)
     H, T1 = cptr.shape
     total = len(cidx)
-    ip = np.empty(n_ecs + 1, dtype=np.int32)
-    ix = np.empty(max(total, 1), dtype=np.int32)
-    da = np.empty(max(total, 1), dtype=np.int32)
+    room = total if k.tensors else max(total, 1)     # what differs: tensors have always been sized exactly (an empty one's pointer is null)
+    ip, ix, da = k.empty(n_ecs + 1, k.i32), k.empty(room, k.i32), k.empty(room, k.i32)
     nnz = C.c_uint64()
-    _check(lib, lib.ecb_hapcsc_to_csr(device, n_ecs, T1 - 1, H, _ptr(cptr), _ptr(cidx), total, _ptr(ip), _ptr(ix), _ptr(da), C.byref(nnz)))
+    _check(lib, k.entry(lib, "ecb_hapcsc_to_csr")(k.device, n_ecs, T1 - 1, H, p(cptr), p(cidx), total, p(ip), p(ix), p(da), C.byref(nnz)))
     return ip, ix[:nnz.value], da[:nnz.value]
 
 
-def hapcsc_to_csr(csc_indptr, csc_indices, n_ecs):
-    """f-2 inverse on device tensors: per-haplotype CSC -> CSR(bitmask) (``bin_utils.emase2ec``: A = sum 2^h M_h)."""
-    import torch
-    lib = load()
-    dev = csc_indptr.device
-    H, T1 = csc_indptr.shape
-    total = csc_indices.numel()
-    ip = torch.empty(n_ecs + 1, dtype=torch.int32, device=dev)
-    ix = torch.empty(total, dtype=torch.int32, device=dev)
-    da = torch.empty(total, dtype=torch.int32, device=dev)
-    nnz = C.c_uint64()
-    _check(lib, lib.ecb_hapcsc_to_csr_device(dev.index or 0, n_ecs, T1 - 1, H, _dev_ptr(csc_indptr), _dev_ptr(csc_indices), total,
-                                             _dev_ptr(ip), _dev_ptr(ix), _dev_ptr(da), C.byref(nnz)))
-    return ip, ix[:nnz.value], da[:nnz.value]
+hapcsc_to_csr_host = hapcsc_to_csr                     # (the name the host callers know)
 
 
 def apply_mask(indptr, indices, data, mask, n_haps, device=0):
@@ -364,31 +413,16 @@ def apply_mask(indptr, indices, data, mask, n_haps, device=0):
     arrays, no PyTorch), CUDA tensors through ``ecb_apply_mask_device`` (``device`` is then the tensors' own).  Returns (indptr, indices,
     data), int32, of the same kind as the input.  A malformed CSR or mask raises :class:`EcbError` (``ECB_ERR_CONTRACT``)."""
     lib = load()
-    if hasattr(indptr, "data_ptr"):
-        import torch
-        dev = indptr.device
-        ip, ix, da = (t.contiguous().to(torch.int32) for t in (indptr, indices, data))
-        mk = mask.contiguous().to(torch.int32)
-        E, T, nnz = ip.numel() - 1, mk.numel(), ix.numel()
-        if da.numel() != nnz:
-            raise ValueError("indices and data differ in length")
-        oip = torch.empty(E + 1, dtype=torch.int32, device=dev)
-        oix = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
-        oda = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
-        kept = C.c_uint64()
-        _check(lib, lib.ecb_apply_mask_device(dev.index or 0, E, T, n_haps, nnz, _dev_ptr(ip), _dev_ptr(ix), _dev_ptr(da), _dev_ptr(mk),
-                                              _dev_ptr(oip), _dev_ptr(oix), _dev_ptr(oda), C.byref(kept)))
-        return oip, oix[:kept.value], oda[:kept.value]
-    ip, ix, da = (np.ascontiguousarray(a, dtype=np.int32) for a in (indptr, indices, data))
-    mk = np.ascontiguousarray(mask, dtype=np.uint32)
+    k = _kind(indptr, device)
+    p = k.ptr
+    ip, ix, da = (k.arr(a, k.i32) for a in (indptr, indices, data))
+    mk = k.arr(mask, k.u32)
     E, T, nnz = len(ip) - 1, len(mk), len(ix)
     if len(da) != nnz:
         raise ValueError("indices and data differ in length")
-    oip = np.empty(E + 1, dtype=np.int32)
-    oix = np.empty(max(nnz, 1), dtype=np.int32)
-    oda = np.empty(max(nnz, 1), dtype=np.int32)
+    oip, oix, oda = k.empty(E + 1, k.i32), k.empty(max(nnz, 1), k.i32), k.empty(max(nnz, 1), k.i32)
     kept = C.c_uint64()
-    _check(lib, lib.ecb_apply_mask(device, E, T, n_haps, nnz, _ptr(ip), _ptr(ix), _ptr(da), _ptr(mk), _ptr(oip), _ptr(oix), _ptr(oda), C.byref(kept)))
+    _check(lib, k.entry(lib, "ecb_apply_mask")(k.device, E, T, n_haps, nnz, p(ip), p(ix), p(da), p(mk), p(oip), p(oix), p(oda), C.byref(kept)))
     return oip, oix[:kept.value], oda[:kept.value]
 
 
@@ -400,29 +434,13 @@ def count_alignments(indptr, indices, data, n_loci, n_haps, indptr_n, indices_n,
     (``device`` is then the tensors' own).  Returns ``(aln[H, T], uniq[H, T], locus_uniq[T])``, int64, of the same kind as the input.
     Malformed input or an unknown sample raises :class:`EcbError` (``ECB_ERR_CONTRACT``)."""
     lib = load()
+    k = _kind(indptr, device)
+    p = k.ptr
     s = -1 if sample is None else int(sample)
-    if hasattr(indptr, "data_ptr"):
-        import torch
-        dev = indptr.device
-        ip, ix, da, pn, xn, dn = (t.contiguous().to(torch.int32) for t in (indptr, indices, data, indptr_n, indices_n, data_n))
-        E, nnz, S, nnz_n = ip.numel() - 1, ix.numel(), pn.numel() - 1, xn.numel()
-        if da.numel() != nnz or dn.numel() != nnz_n:
-            raise ValueError("indices and data differ in length")
-        aln = torch.empty((n_haps, n_loci), dtype=torch.int64, device=dev)
-        uniq = torch.empty((n_haps, n_loci), dtype=torch.int64, device=dev)
-        lu = torch.empty(n_loci, dtype=torch.int64, device=dev)
-        _check(lib, lib.ecb_count_alignments_device(dev.index or 0, E, n_loci, n_haps, nnz, _dev_ptr(ip), _dev_ptr(ix), _dev_ptr(da), S, nnz_n,
-                                                    _dev_ptr(pn), _dev_ptr(xn), _dev_ptr(dn), s, _dev_ptr(aln), _dev_ptr(uniq), _dev_ptr(lu)))
-        return aln, uniq, lu
-    ip, ix, da, pn, xn, dn = (np.ascontiguousarray(a, dtype=np.int32) for a in (indptr, indices, data, indptr_n, indices_n, data_n))
-    E, nnz, S, nnz_n = len(ip) - 1, len(ix), len(pn) - 1, len(xn)
-    if len(da) != nnz or len(dn) != nnz_n:
-        raise ValueError("indices and data differ in length")
-    aln = np.empty((n_haps, n_loci), dtype=np.int64)
-    uniq = np.empty((n_haps, n_loci), dtype=np.int64)
-    lu = np.empty(n_loci, dtype=np.int64)
-    _check(lib, lib.ecb_count_alignments(device, E, n_loci, n_haps, nnz, _ptr(ip), _ptr(ix), _ptr(da), S, nnz_n, _ptr(pn), _ptr(xn), _ptr(dn), s,
-                                         _ptr(aln), _ptr(uniq), _ptr(lu)))
+    (ip, ix, da, pn, xn, dn), (E, nnz, S, nnz_n) = _matrices(k, (indptr, indices, data, indptr_n, indices_n, data_n))
+    aln, uniq, lu = k.empty((n_haps, n_loci), k.i64), k.empty((n_haps, n_loci), k.i64), k.empty(n_loci, k.i64)
+    _check(lib, k.entry(lib, "ecb_count_alignments")(k.device, E, n_loci, n_haps, nnz, p(ip), p(ix), p(da), S, nnz_n, p(pn), p(xn), p(dn), s,
+                                                     p(aln), p(uniq), p(lu)))
     return aln, uniq, lu
 
 
@@ -442,18 +460,18 @@ def quantify(indptr, indices, data, n_loci, n_haps, indptr_n, indices_n, data_n,
 def _quantify(mats, n_loci, n_haps, sample, scale, theta_in, max_iters, tol, device, grouping=None):
     """:func:`quantify` and, with ``grouping = (gene, n_genes, model)``, :func:`quantify_model`: each through its own entry point."""
     lib = load()
-    tensors, dev, (ip, ix, da, pn, xn, dn, _), (E, nnz, S, nnz_n), tabs, gn = _quant_args(mats, n_loci, n_haps, scale=scale, theta_in=theta_in,
-                                                                                          gene=grouping and grouping[0])
+    k = _kind(mats[0], device)
+    p = k.ptr
+    (ip, ix, da, pn, xn, dn), (E, nnz, S, nnz_n) = _matrices(k, mats)
+    sc, th, gn = k.arr(scale, k.f64), k.arr(theta_in, k.f64), k.arr(grouping and grouping[0], k.i32)
+    _check_gene(gn, n_loci)                          # (the genes before the tables here, after them per cell: the order each has always had)
+    _check_tables((sc, th), n_loci, n_haps, "scale and theta_in")
     s = -1 if sample is None else int(sample)
     it, dl, ex, cv = C.c_uint32(), C.c_double(), C.c_int64(), C.c_uint32()
-    if tensors:
-        import torch
-        p, d, theta = _dev_ptr, dev.index or 0, torch.empty((n_haps, n_loci), dtype=torch.float64, device=dev)
-    else:
-        p, d, theta = _ptr, device, np.empty((n_haps, n_loci), dtype=np.float64)
-    fn = getattr(lib, "ecb_quantify" + ("_model" if grouping else "") + ("_device" if tensors else ""))
+    theta = k.empty((n_haps, n_loci), k.f64)
+    fn = k.entry(lib, "ecb_quantify" + ("_model" if grouping else ""))
     model_args = (int(grouping[1]), p(gn), int(grouping[2])) if grouping else ()
-    _check(lib, fn(d, E, n_loci, n_haps, nnz, p(ip), p(ix), p(da), S, nnz_n, p(pn), p(xn), p(dn), s, p(tabs[0]), p(tabs[1]), int(max_iters), float(tol),
+    _check(lib, fn(k.device, E, n_loci, n_haps, nnz, p(ip), p(ix), p(da), S, nnz_n, p(pn), p(xn), p(dn), s, p(sc), p(th), int(max_iters), float(tol),
                    *model_args, p(theta), C.byref(it), C.byref(dl), C.byref(ex), C.byref(cv)))
     return theta, {"n_iter": it.value, "delta": dl.value, "explained": ex.value, "converged": bool(cv.value)}
 
@@ -480,83 +498,37 @@ def posterior(indptr, indices, data, n_loci, n_haps, theta, scale=None, gene=Non
     the row's normalizing sum, 0 for a row nothing explains (all of it is then 0).  A NaN, infinite or negative entry of ``theta`` or
     ``scale``, a gene id outside ``[0, n_genes)`` or a malformed A raises :class:`EcbError` (``ECB_ERR_CONTRACT``)."""
     lib = load()
-    tensors = hasattr(indptr, "data_ptr")
-    if tensors:
-        import torch
-        dev = indptr.device
-        ip, ix, da = (t.contiguous().to(torch.int32) for t in (indptr, indices, data))
-        tabs = [None if t is None else torch.as_tensor(t).to(device=dev, dtype=torch.float64).contiguous() for t in (scale, theta)]
-        gn = None if gene is None else torch.as_tensor(gene).to(device=dev, dtype=torch.int32).contiguous()
-        E, nnz = ip.numel() - 1, ix.numel()
-        n_bits = 0
-        if E > 0 and nnz and da.numel() == nnz and int(ip[-1]) == nnz:      # (the conversion's count-only call: one pass over the masks it is told of)
-            tot = C.c_uint64()
-            _check(lib, lib.ecb_csr_to_hapcsc_device(dev.index or 0, E, n_loci, n_haps, _dev_ptr(ip), _dev_ptr(ix), _dev_ptr(da), None, None, C.byref(tot)))
-            n_bits = tot.value
-        fn, p, d = lib.ecb_posterior_device, _dev_ptr, dev.index or 0
-        new = lambda n, dt: torch.zeros(n, dtype=dt, device=dev)         # noqa: E731
-        f64, i64 = torch.float64, torch.int64
-    else:
-        ip, ix, da = (np.ascontiguousarray(a, dtype=np.int32) for a in (indptr, indices, data))
-        tabs = [None if t is None else np.ascontiguousarray(t, dtype=np.float64) for t in (scale, theta)]
-        gn = None if gene is None else np.ascontiguousarray(gene, dtype=np.int32)
-        E, nnz = len(ip) - 1, len(ix)
+    k = _kind(indptr, device)
+    p = k.ptr
+    ip, ix, da = (k.arr(a, k.i32) for a in (indptr, indices, data))
+    sc, th, gn = k.arr(scale, k.f64), k.arr(theta, k.f64), k.arr(gene, k.i32)
+    E, nnz = len(ip) - 1, len(ix)
+    # what differs: how the set bits are counted -- host masks here, device masks by the conversion's count-only call (one pass over the
+    # masks it is told of), and only over a CSR it can walk
+    n_bits = 0
+    if not k.tensors:
         n_bits = int(np.unpackbits(da.view(np.uint8)).sum())
-        fn, p, d = lib.ecb_posterior, _ptr, device
-        new = lambda n, dt: np.zeros(n, dtype=dt)                        # noqa: E731
-        f64, i64 = np.float64, np.int64
+    elif E > 0 and nnz and len(da) == nnz and int(ip[-1]) == nnz:
+        tot = C.c_uint64()
+        _check(lib, lib.ecb_csr_to_hapcsc_device(k.device, E, n_loci, n_haps, p(ip), p(ix), p(da), None, None, C.byref(tot)))
+        n_bits = tot.value
     if len(da) != nnz:
         raise ValueError("indices and data differ in length")
-    if tabs[1] is None or any(t is not None and tuple(t.shape) != (n_haps, n_loci) for t in tabs):
+    if th is None:
         raise ValueError("theta and scale are [n_haps, n_loci]")
-    if gn is not None and tuple(gn.shape) != (n_loci,):
-        raise ValueError("gene is [n_loci]")
-    post, bit_ptr, row_mass = new(n_bits, f64), new(nnz + 1, i64), new(E, f64)
-    _check(lib, fn(d, E, n_loci, n_haps, nnz, p(ip), p(ix), p(da), p(tabs[0]), p(tabs[1]), int(n_genes), p(gn), int(model), n_bits,
-                   p(post) if n_bits else None, p(bit_ptr), p(row_mass)))
+    _check_tables((sc, th), n_loci, n_haps, "theta and scale")
+    _check_gene(gn, n_loci)
+    post, bit_ptr, row_mass = k.zeros(n_bits, k.f64), k.zeros(nnz + 1, k.i64), k.zeros(E, k.f64)
+    _check(lib, k.entry(lib, "ecb_posterior")(k.device, E, n_loci, n_haps, nnz, p(ip), p(ix), p(da), p(sc), p(th), int(n_genes), p(gn), int(model),
+                                              n_bits, p(post) if n_bits else None, p(bit_ptr), p(row_mass)))
     return post, bit_ptr, row_mass
 
 
-def _cells_args(indptr, indices, data, indptr_n, indices_n, data_n, cell_keep):
-    """The matrices and ``cell_keep`` as the per-cell entry points take them: (tensors?, device or None, arrays, E, nnz, S, nnz_n)."""
-    if hasattr(indptr, "data_ptr"):
-        import torch
-        dev = indptr.device
-        arrs = [t.contiguous().to(torch.int32) for t in (indptr, indices, data, indptr_n, indices_n, data_n)]
-        keep = None if cell_keep is None else torch.as_tensor(cell_keep).to(device=dev).ne(0).to(torch.uint8).contiguous()
-        sizes = (arrs[0].numel() - 1, arrs[1].numel(), arrs[3].numel() - 1, arrs[4].numel())
-        if arrs[2].numel() != sizes[1] or arrs[5].numel() != sizes[3]:
-            raise ValueError("indices and data differ in length")
-        if keep is not None and keep.numel() != sizes[2]:
-            raise ValueError("cell_keep is [n_samples]")
-        return True, dev, arrs + [keep], sizes
-    arrs = [np.ascontiguousarray(a, dtype=np.int32) for a in (indptr, indices, data, indptr_n, indices_n, data_n)]
-    keep = None if cell_keep is None else np.ascontiguousarray(np.asarray(cell_keep) != 0, dtype=np.uint8)
-    sizes = (len(arrs[0]) - 1, len(arrs[1]), len(arrs[3]) - 1, len(arrs[4]))
-    if len(arrs[2]) != sizes[1] or len(arrs[5]) != sizes[3]:
-        raise ValueError("indices and data differ in length")
-    if keep is not None and keep.shape != (sizes[2],):
+def _cell_keep(k, cell_keep, n_samples):
+    keep = k.flags(cell_keep)
+    if keep is not None and len(keep) != n_samples:
         raise ValueError("cell_keep is [n_samples]")
-    return False, None, arrs + [keep], sizes
-
-
-def _quant_args(mats, n_loci, n_haps, cell_keep=None, scale=None, theta_in=None, gene=None, tables_first=False):
-    """What the ecquant entry points take, for tensors or numpy: :func:`_cells_args` of the matrices and ``cell_keep``, then the two tables
-    (float64 ``[H, T]`` or None) and the gene array (int32 ``[T]`` or None), checked in the order the entry point has always checked them."""
-    tensors, dev, arrs, sizes = _cells_args(*mats, cell_keep)
-    if tensors:
-        import torch
-        tabs = [None if t is None else t.to(device=dev, dtype=torch.float64).contiguous() for t in (scale, theta_in)]
-        gn = None if gene is None else torch.as_tensor(gene).to(device=dev, dtype=torch.int32).contiguous()
-    else:
-        tabs = [None if t is None else np.ascontiguousarray(t, dtype=np.float64) for t in (scale, theta_in)]
-        gn = None if gene is None else np.ascontiguousarray(gene, dtype=np.int32)
-    for tables in (tables_first, not tables_first):
-        if tables and any(t is not None and tuple(t.shape) != (n_haps, n_loci) for t in tabs):
-            raise ValueError("scale and theta_in are [n_haps, n_loci]")
-        if not tables and gn is not None and tuple(gn.shape) != (n_loci,):
-            raise ValueError("gene is [n_loci]")
-    return tensors, dev, arrs, sizes, tabs, gn
+    return keep
 
 
 def cell_support(indptr, indices, data, n_loci, n_haps, indptr_n, indices_n, data_n, cell_keep=None, device=0, count_only=False):
@@ -566,23 +538,17 @@ def cell_support(indptr, indices, data, n_loci, n_haps, indptr_n, indices_n, dat
     [n_slots])`` of the same kind as the input: cell c owns ``slot_locus[cell_ptr[c]:cell_ptr[c + 1]]``.  ``count_only``: one pass instead of
     two, ``slot_locus`` is then None."""
     lib = load()
-    tensors, dev, (ip, ix, da, pn, xn, dn, keep), (E, nnz, S, nnz_n) = _cells_args(indptr, indices, data, indptr_n, indices_n, data_n, cell_keep)
+    k = _kind(indptr, device)
+    p, fn = k.ptr, k.entry(lib, "ecb_cell_support")
+    (ip, ix, da, pn, xn, dn), (E, nnz, S, nnz_n) = _matrices(k, (indptr, indices, data, indptr_n, indices_n, data_n))
+    keep = _cell_keep(k, cell_keep, S)
     ns = C.c_uint64()
-    if tensors:
-        import torch
-        fn, p, d = lib.ecb_cell_support_device, _dev_ptr, dev.index or 0
-        new = lambda n, dt: torch.empty(n, dtype=dt, device=dev)          # noqa: E731
-        i64, i32 = torch.int64, torch.int32
-    else:
-        fn, p, d = lib.ecb_cell_support, _ptr, device
-        new = lambda n, dt: np.empty(n, dtype=dt)                         # noqa: E731
-        i64, i32 = np.int64, np.int32
-    head = (d, E, n_loci, n_haps, nnz, p(ip), p(ix), p(da), S, nnz_n, p(pn), p(xn), p(dn), p(keep))
-    cell_ptr = new(S + 1, i64)
+    head = (k.device, E, n_loci, n_haps, nnz, p(ip), p(ix), p(da), S, nnz_n, p(pn), p(xn), p(dn), p(keep))
+    cell_ptr = k.empty(S + 1, k.i64)
     _check(lib, fn(*(head + (p(cell_ptr), None, 0, C.byref(ns)))))       # (the sizes first ...
     if count_only:
         return cell_ptr, None
-    slot_locus = new(ns.value, i32)
+    slot_locus = k.empty(ns.value, k.i32)
     if ns.value:
         _check(lib, fn(*(head + (p(cell_ptr), p(slot_locus), ns.value, C.byref(ns)))))      # ... then the loci, into an array that fits)
     return cell_ptr, slot_locus
@@ -604,27 +570,23 @@ def quantify_cells(indptr, indices, data, n_loci, n_haps, indptr_n, indices_n, d
 def _quantify_cells(mats, n_loci, n_haps, cell_keep, scale, theta_in, max_iters, tol, budget_bytes, device, n_slots, grouping=None):
     """:func:`quantify_cells` and, with ``grouping = (gene, n_genes, model)``, :func:`quantify_cells_model`: each through its own entry point."""
     lib = load()
-    tensors, dev, (ip, ix, da, pn, xn, dn, keep), (E, nnz, S, nnz_n), tabs, gn = _quant_args(mats, n_loci, n_haps, cell_keep, scale, theta_in,
-                                                                                             gene=grouping and grouping[0], tables_first=True)
+    k = _kind(mats[0], device)
+    p = k.ptr
+    (ip, ix, da, pn, xn, dn), (E, nnz, S, nnz_n) = _matrices(k, mats)
+    keep = _cell_keep(k, cell_keep, S)
+    sc, th, gn = k.arr(scale, k.f64), k.arr(theta_in, k.f64), k.arr(grouping and grouping[0], k.i32)
+    _check_tables((sc, th), n_loci, n_haps, "scale and theta_in")
+    _check_gene(gn, n_loci)
     if n_slots is None:
         n_slots = int(cell_support(ip, ix, da, n_loci, n_haps, pn, xn, dn, keep, device, count_only=True)[0][-1])
-    if tensors:
-        import torch
-        p, d = _dev_ptr, dev.index or 0
-        new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)  # noqa: E731
-        i64, i32, u32, f64, u8 = torch.int64, torch.int32, torch.int32, torch.float64, torch.uint8
-    else:
-        p, d = _ptr, device
-        new = lambda shape, dt: np.empty(shape, dtype=dt)                 # noqa: E731
-        i64, i32, u32, f64, u8 = np.int64, np.int32, np.uint32, np.float64, np.uint8
-    fn = getattr(lib, "ecb_quantify_cells" + ("_model" if grouping else "") + ("_device" if tensors else ""))
+    fn = k.entry(lib, "ecb_quantify_cells" + ("_model" if grouping else ""))
     model_args = (int(grouping[1]), p(gn), int(grouping[2])) if grouping else ()
-    cell_ptr, slot_locus, theta = new(S + 1, i64), new(n_slots, i32), new((n_slots, n_haps), f64)
-    it, dl, ex, cv = new(S, u32), new(S, f64), new(S, i64), new(S, u8)
-    _check(lib, fn(d, E, n_loci, n_haps, nnz, p(ip), p(ix), p(da), S, nnz_n, p(pn), p(xn), p(dn), p(keep), p(tabs[0]), p(tabs[1]), int(max_iters),
+    cell_ptr, slot_locus, theta = k.empty(S + 1, k.i64), k.empty(n_slots, k.i32), k.empty((n_slots, n_haps), k.f64)
+    it, dl, ex, cv = k.empty(S, k.u32), k.empty(S, k.f64), k.empty(S, k.i64), k.empty(S, k.u8)
+    _check(lib, fn(k.device, E, n_loci, n_haps, nnz, p(ip), p(ix), p(da), S, nnz_n, p(pn), p(xn), p(dn), p(keep), p(sc), p(th), int(max_iters),
                    float(tol), int(budget_bytes), *model_args, n_slots, p(cell_ptr), p(slot_locus), p(theta), p(it), p(dl), p(ex), p(cv)))
-    if tensors:
-        it = it.to(torch.int64).bitwise_and(0xFFFFFFFF)                  # (the uint32 the library wrote, in a type torch computes with)
+    if k.tensors:                                    # what differs: the uint32 the library wrote, in a type torch computes with
+        it = it.to(k.i64).bitwise_and(0xFFFFFFFF)
     return cell_ptr, slot_locus, theta, {"n_iter": it, "delta": dl, "explained": ex, "converged": cv != 0}
 
 
@@ -649,45 +611,25 @@ def combine(parts, n_loci, n_haps, n_samples, device=0):
     the tensors' own).  Returns (indptrA, indicesA, dataA, indptrN, indicesN, dataN), int32, of the same kind as the input.  Malformed
     input raises :class:`EcbError` (``ECB_ERR_CONTRACT``), sizes beyond the format's limits ``ECB_ERR_LIMIT``."""
     lib = load()
-    keys = ("indptrA", "indicesA", "dataA", "indptrN", "indicesN", "dataN")
-    on_device = hasattr(parts[0]["indptrA"], "data_ptr") if parts else False
-    if on_device:
-        import torch
-        dev = parts[0]["indptrA"].device
-
-        def arr(a, dt):
-            return None if a is None else torch.as_tensor(a).to(device=dev, dtype=dt).contiguous()
-
-        def empty(n):
-            return torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        ptr, entry, device = _dev_ptr, lib.ecb_combine_device, dev.index or 0
-    else:
-        def arr(a, dt):                             # (a map's values are below 2^31: int32 and uint32 are the same bytes)
-            return None if a is None else np.ascontiguousarray(a, dtype=np.int32)
-
-        def empty(n):
-            return np.empty(max(n, 1), dtype=np.int32)
-        ptr, entry = _ptr, lib.ecb_combine
-    i32 = torch.int32 if on_device else None
+    k = _kind(parts[0]["indptrA"] if parts else None, device)
     held, cp = [], (CombinePart * max(len(parts), 1))()
     R = NP = NZ = 0
-    for k, p in enumerate(parts):
-        a = [arr(p[n], i32) for n in keys]
-        tm = arr(p.get("target_map"), i32)
-        sm = arr(p.get("sample_map"), i32)
-        held += a + [tm, sm]
+    for i, part in enumerate(parts):
+        a = [k.arr(part[n], k.i32) for n in ("indptrA", "indicesA", "dataA", "indptrN", "indicesN", "dataN")]
+        a += [k.arr(part.get(n), k.i32) for n in ("target_map", "sample_map")]     # (a map's values are below 2^31: int32 and uint32 are the same bytes)
+        held += a
         E, S = len(a[0]) - 1, len(a[3]) - 1
         if len(a[1]) != len(a[2]) or len(a[4]) != len(a[5]):
-            raise ValueError("part %d: indices and data differ in length" % k)
-        c = cp[k]
-        c.struct_size, c.n_ecs, c.n_samples, c.n_loci = C.sizeof(CombinePart), E, S, int(p["n_loci"])
+            raise ValueError("part %d: indices and data differ in length" % i)
+        c = cp[i]
+        c.struct_size, c.n_ecs, c.n_samples, c.n_loci = C.sizeof(CombinePart), E, S, int(part["n_loci"])
         c.nnz_a, c.nnz_n = len(a[1]), len(a[4])
-        for n, x in zip(("indptr_a", "indices_a", "data_a", "indptr_n", "indices_n", "data_n", "target_map", "sample_map"), a + [tm, sm]):
-            setattr(c, n, None if x is None else ptr(x).value)
+        for n, x in zip(("indptr_a", "indices_a", "data_a", "indptr_n", "indices_n", "data_n", "target_map", "sample_map"), a):
+            setattr(c, n, None if x is None else k.ptr(x).value)
         R, NP, NZ = R + E, NP + len(a[1]), NZ + len(a[4])
-    out = [empty(R + 1), empty(NP), empty(NP), empty(n_samples + 1), empty(NZ), empty(NZ)]
+    out = [k.empty(max(n, 1), k.i32) for n in (R + 1, NP, NP, n_samples + 1, NZ, NZ)]
     sizes = (C.c_uint64 * 3)()
-    _check(lib, entry(device, len(parts), cp, n_loci, n_haps, n_samples, *[ptr(o) for o in out], sizes))
+    _check(lib, k.entry(lib, "ecb_combine")(k.device, len(parts), cp, n_loci, n_haps, n_samples, *[k.ptr(o) for o in out], sizes))
     E, nnz_a, nnz_n = (int(x) for x in sizes)
     return out[0][:E + 1], out[1][:nnz_a], out[2][:nnz_a], out[3], out[4][:nnz_n], out[5][:nnz_n]
 
@@ -701,39 +643,23 @@ def bundle(indptrA, indicesA, dataA, indptrN, indicesN, dataN, n_loci, n_haps, n
     (``device`` is then the tensors' own).  Returns (indptrA, indicesA, dataA, indptrN, indicesN, dataN), int32, of the same kind as the
     input.  Malformed input or a malformed map raises :class:`EcbError` (``ECB_ERR_CONTRACT``), sizes beyond the limits ``ECB_ERR_LIMIT``."""
     lib = load()
-    ins = (indptrA, indicesA, dataA, indptrN, indicesN, dataN, map_ptr, map_idx)
-    on_device = hasattr(indptrA, "data_ptr")
-    if on_device:
-        import torch
-        dev = indptrA.device
-        a = [torch.as_tensor(x).to(device=dev, dtype=torch.int32).contiguous() for x in ins]
-        ptr, entry, device = _dev_ptr, lib.ecb_bundle_device, dev.index or 0
-
-        def empty(n):
-            return torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-    else:
-        a = [np.ascontiguousarray(x, dtype=np.int32) for x in ins]      # (a map's values are below 2^31: int32 and uint32 are the same bytes)
-        ptr, entry = _ptr, lib.ecb_bundle
-
-        def empty(n):
-            return np.empty(max(n, 1), dtype=np.int32)
-    ipa, ixa, daa, ipn, ixn, dan, mp, mi = a
-    E, S, nnz, nnz_n = len(ipa) - 1, len(ipn) - 1, len(ixa), len(ixn)
-    if len(daa) != nnz or len(dan) != nnz_n:
-        raise ValueError("indices and data differ in length")
+    k = _kind(indptrA, device)
+    p = k.ptr
+    (ipa, ixa, daa, ipn, ixn, dan), (E, nnz, S, nnz_n) = _matrices(k, (indptrA, indicesA, dataA, indptrN, indicesN, dataN))
+    mp, mi = k.arr(map_ptr, k.i32), k.arr(map_idx, k.i32)             # (a map's values are below 2^31: int32 and uint32 are the same bytes)
     if len(mp) != n_loci + 1:
         raise ValueError("map_ptr has %d entries for %d loci" % (len(mp), n_loci))
     # room for A: the (row, group) pairs before the fold -- one per non-zero and group of its locus, where the map and the columns can be
     # indexed at all (otherwise the library refuses before it writes) -- and never more than a full matrix
     cap = 0
-    if nnz and len(mp) > 1:
-        per = (mp[1:] - mp[:-1]).clamp(min=0) if on_device else np.maximum(np.diff(mp.astype(np.int64)), 0)
-        cols = ixa.long().clamp(0, n_loci - 1) if on_device else np.clip(ixa, 0, n_loci - 1)
+    if nnz and len(mp) > 1:                          # what differs: how each kind spells a clamped difference and a clamped index
+        per = (mp[1:] - mp[:-1]).clamp(min=0) if k.tensors else np.maximum(np.diff(mp.astype(np.int64)), 0)
+        cols = ixa.long().clamp(0, n_loci - 1) if k.tensors else np.clip(ixa, 0, n_loci - 1)
         cap = min(int(per[cols].sum()), E * n_groups, (1 << 31) - 1)
-    out = [empty(E + 1), empty(cap), empty(cap), empty(S + 1), empty(nnz_n), empty(nnz_n)]
+    out = [k.empty(max(n, 1), k.i32) for n in (E + 1, cap, cap, S + 1, nnz_n, nnz_n)]
     sizes = (C.c_uint64 * 3)()
-    _check(lib, entry(device, E, n_loci, n_haps, S, n_groups, nnz, ptr(ipa), ptr(ixa), ptr(daa), nnz_n, ptr(ipn), ptr(ixn), ptr(dan),
-                      len(mi), ptr(mp), ptr(mi), cap, *([ptr(o) for o in out] + [sizes])))
+    _check(lib, k.entry(lib, "ecb_bundle")(k.device, E, n_loci, n_haps, S, n_groups, nnz, p(ipa), p(ixa), p(daa), nnz_n, p(ipn), p(ixn), p(dan),
+                                           len(mi), p(mp), p(mi), cap, *([p(o) for o in out] + [sizes])))
     E2, nnz_a, nnz_n2 = (int(x) for x in sizes)
     return out[0][:E2 + 1], out[1][:nnz_a], out[2][:nnz_a], out[3], out[4][:nnz_n2], out[5][:nnz_n2]
 
@@ -749,44 +675,23 @@ def select(indptrA, indicesA, dataA, indptrN, indicesN, dataN, n_loci, n_haps, r
     kept)``: int32 arrays of the same kind as the input, and a bool array, per sample of the input whether it stayed.  A result without a
     sample or without a row is returned as it is.  Malformed input raises :class:`EcbError` (``ECB_ERR_CONTRACT``)."""
     lib = load()
+    k = _kind(indptrA, device)
+    p = k.ptr
     rc = ROW_CLASSES[row_class] if row_class is None or isinstance(row_class, str) else int(row_class)
     mc = -1 if min_count is None else max(int(min_count), 0)
-    ins = (indptrA, indicesA, dataA, indptrN, indicesN, dataN)
-    on_device = hasattr(indptrA, "data_ptr")
-    if on_device:
-        import torch
-        dev = indptrA.device
-        a = [torch.as_tensor(x).to(device=dev, dtype=torch.int32).contiguous() for x in ins]
-        sk = None if sample_keep is None else (torch.as_tensor(sample_keep).to(device=dev) != 0).to(torch.uint8).contiguous()
-        ptr, entry, device = _dev_ptr, lib.ecb_select_device, dev.index or 0
-
-        def empty(n, dt=torch.int32):
-            return torch.empty(max(n, 1), dtype=dt, device=dev)
-        u8 = torch.uint8
-    else:
-        a = [np.ascontiguousarray(x, dtype=np.int32) for x in ins]
-        sk = None if sample_keep is None else np.ascontiguousarray(np.asarray(sample_keep) != 0, dtype=np.uint8)
-        ptr, entry = _ptr, lib.ecb_select
-
-        def empty(n, dt=np.int32):
-            return np.empty(max(n, 1), dtype=dt)
-        u8 = np.uint8
-    ipa, ixa, daa, ipn, ixn, dan = a
-    E, S, nnz, nnz_n = len(ipa) - 1, len(ipn) - 1, len(ixa), len(ixn)
-    if len(daa) != nnz or len(dan) != nnz_n:
-        raise ValueError("indices and data differ in length")
+    (ipa, ixa, daa, ipn, ixn, dan), (E, nnz, S, nnz_n) = _matrices(k, (indptrA, indicesA, dataA, indptrN, indicesN, dataN))
+    sk = k.flags(sample_keep)
     if sk is not None and len(sk) != S:
         raise ValueError("sample_keep has %d entries for %d samples" % (len(sk), S))
-    out = [empty(E + 1), empty(nnz), empty(nnz), empty(S + 1), empty(nnz_n), empty(nnz_n)]
-    kept = empty(S, u8)
+    out = [k.empty(max(n, 1), k.i32) for n in (E + 1, nnz, nnz, S + 1, nnz_n, nnz_n)]
+    kept = k.empty(max(S, 1), k.u8)
     sizes = (C.c_uint64 * 4)()
-    _check(lib, entry(device, E, n_loci, n_haps, S, nnz, ptr(ipa), ptr(ixa), ptr(daa), nnz_n, ptr(ipn), ptr(ixn), ptr(dan), rc, ptr(sk), mc,
-                      *([ptr(o) for o in out] + [ptr(kept), sizes])))
+    _check(lib, k.entry(lib, "ecb_select")(k.device, E, n_loci, n_haps, S, nnz, p(ipa), p(ixa), p(daa), nnz_n, p(ipn), p(ixn), p(dan), rc, p(sk), mc,
+                                           *([p(o) for o in out] + [p(kept), sizes])))
     E2, nnz_a, S2, nnz_n2 = (int(x) for x in sizes)
     return (out[0][:E2 + 1], out[1][:nnz_a], out[2][:nnz_a], out[3][:S2 + 1], out[4][:nnz_n2], out[5][:nnz_n2]), kept[:S] != 0
 
 
-ECB_ERR_CONTRACT = -5      # include/ecb.h
 #: ``ecb_salmon_ecs``'s reason codes (include/ecb.h)
 SALMON_REASONS = {1: "a byte other than a digit, tab or line end", 2: "an empty field", 3: "a value of 2^31 or more",
                   4: "fewer than 2 fields", 5: "k differs from the number of target ids", 6: "a target id at or beyond the number of targets",
@@ -809,24 +714,18 @@ def salmon_ecs(text, n_ecs, target_col, target_hap, n_loci, n_haps, device=0):
     count and their counts.  A malformed text raises :class:`SalmonFormatError` with the lowest offending line; sizes beyond the
     limits raise :class:`EcbError` (``ECB_ERR_LIMIT``)."""
     lib = load()
+    k = _kind(text, device)
+    p = k.ptr
+    t = k.bytes(text)
+    cap = max(int((t == 9).sum()) - n_ecs, 0)          # (target ids = tabs - E in a well-formed text: the non-zeros' bound)
+    if k.tensors:                                    # what differs: a tensor is made of the ids as int64 (torch takes no uint32 array everywhere)
+        target_col, target_hap = (np.asarray(a, dtype=np.int64) for a in (target_col, target_hap))
+    tc, th = k.arr(target_col, k.u32), k.arr(target_hap, k.u32)
+    if not k.tensors and len(tc) != len(th):         # what differs: only the host arrays have ever been compared
+        raise ValueError("target_col and target_hap differ in length")
+    out = [k.empty(n, k.i32) for n in (n_ecs + 1, max(cap, 1), max(cap, 1), max(n_ecs, 1), max(n_ecs, 1))]
     sizes = (C.c_uint64 * 2)()
-    if hasattr(text, "data_ptr"):
-        import torch
-        dev = text.device
-        t = text.contiguous().view(torch.uint8).reshape(-1)
-        cap = max(int((t == 9).sum().item()) - n_ecs, 0)           # (target ids = tabs - E in a well-formed text: the non-zeros' bound)
-        tc, th = (torch.as_tensor(np.asarray(a, dtype=np.int64)).to(device=dev, dtype=torch.int32).contiguous() for a in (target_col, target_hap))
-        out = [torch.empty(n, dtype=torch.int32, device=dev) for n in (n_ecs + 1, max(cap, 1), max(cap, 1), max(n_ecs, 1), max(n_ecs, 1))]
-        rc = lib.ecb_salmon_ecs_device(dev.index or 0, _dev_ptr(t), t.numel(), n_ecs, tc.numel(), _dev_ptr(tc), _dev_ptr(th), n_loci, n_haps, cap,
-                                       *[_dev_ptr(o) for o in out], sizes)
-    else:
-        t = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text, dtype=np.uint8).reshape(-1)
-        cap = max(int(np.count_nonzero(t == 9)) - n_ecs, 0)
-        tc, th = (np.ascontiguousarray(a, dtype=np.uint32) for a in (target_col, target_hap))
-        if len(tc) != len(th):
-            raise ValueError("target_col and target_hap differ in length")
-        out = [np.empty(n, dtype=np.int32) for n in (n_ecs + 1, max(cap, 1), max(cap, 1), max(n_ecs, 1), max(n_ecs, 1))]
-        rc = lib.ecb_salmon_ecs(device, _ptr(t), len(t), n_ecs, len(tc), _ptr(tc), _ptr(th), n_loci, n_haps, cap, *[_ptr(o) for o in out], sizes)
+    rc = k.entry(lib, "ecb_salmon_ecs")(k.device, p(t), len(t), n_ecs, len(tc), p(tc), p(th), n_loci, n_haps, cap, *[p(o) for o in out], sizes)
     if rc != 0:
         msg = (lib.ecb_last_error(None) or b"").decode()
         m = re.match(r"EC line (\d+): .* \(reason (\d+)\)$", msg)

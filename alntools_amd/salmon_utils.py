@@ -193,25 +193,13 @@ def convert(salmon_dir, ec_filename, sample='NA', target_filename=None, device=0
     LOG.debug('  Sample: {}'.format(sample))
     LOG.debug('  Target file: {}'.format(target_filename))
     LOG.debug('-------------------------------------------')
-    try:
+    with bin_utils.command(bin_utils.RAISE):
         time0 = time.time()
         transcripts, haplotypes, lengths, A, N = parse_salmon_ec(salmon_dir, target_filename, device=device)
         LOG.info("{} parsed in {}".format(ec_filename, utils.format_time(time0, time.time())))
         time1 = time.time()
-        LOG.info("Converting and storing to {}".format(ec_filename))
         m = bin_utils.ECMatrices(haplotypes, transcripts, lengths, [sample], *A, *N)
-        LOG.info("Number of haplotypes: {:,}".format(m.num_haplotypes))
-        LOG.info("Number of reference targets: {:,}".format(m.num_loci))
-        LOG.info("Number of equivalence classes: {:,}".format(m.num_reads))
-        b = bin_utils.ecsave2_bytes(m)
-        try:
-            with open(ec_filename, 'wb') as fh:
-                fh.write(b)
-        except BaseException:
-            if os.path.exists(ec_filename):
-                os.remove(ec_filename)
-            raise
+        bin_utils.log_saving("Converting and storing to {}".format(ec_filename), m, "Number of equivalence classes: {:,}".format(m.num_reads),
+                             samples=None)
+        bin_utils.write_bin(ec_filename, m)
         LOG.info("{} created in {}".format(ec_filename, utils.format_time(time1, time.time())))
-    except Exception as e:
-        LOG.error("Error: {}".format(str(e)))
-        raise

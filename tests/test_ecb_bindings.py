@@ -1,0 +1,200 @@
+# -*- coding: utf-8 -*-
+"""The Python binding of libecb on the CPU, against a stand-in for the library (``tools/ecb_call_trace.py``'s): every one-call wrapper of
+``alntools_amd/ecb.py`` reaches its own symbol -- the ``_device`` one exactly for tensors -- with as many arguments as the signature
+table gives it, and ``load()`` binds the names and ``argtypes`` it bound before the table existed (frozen below as literal data)."""
+import ctypes as C
+import os
+import sys
+
+import pytest
+
+from alntools_amd import bin_utils, ecb
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tools"))
+import ecb_call_trace as tr  # noqa: E402
+
+#: what ``load()`` bound before ``ecb.SIGNATURES``: symbol -> (restype, argtypes).  p = c_void_p, u64 = c_uint64 and c_size_t, *X = POINTER(X)
+FROZEN = {
+    "ecb_abi_version": ("i32", None),
+    "ecb_add_counters": ("i32", "p u64 u64 u64"),
+    "ecb_apply_mask": ("i32", "i32 u32 u32 u32 u64 p p p p p p p *u64"),
+    "ecb_apply_mask_device": ("i32", "i32 u32 u32 u32 u64 p p p p p p p *u64"),
+    "ecb_assemble_ranges_device": ("i32", "p u32 *p *p *p *p *p *u64 *u64 u64 u64 u64 *Sizes"),
+    "ecb_bundle": ("i32", "i32 u32 u32 u32 u32 u32 u64 p p p u64 p p p u64 p p u64 p p p p p p *u64"),
+    "ecb_bundle_device": ("i32", "i32 u32 u32 u32 u32 u32 u64 p p p u64 p p p u64 p p u64 p p p p p p *u64"),
+    "ecb_cell_support": ("i32", "i32 u32 u32 u32 u64 p p p u32 u64 p p p p p p u64 *u64"),
+    "ecb_cell_support_device": ("i32", "i32 u32 u32 u32 u64 p p p u32 u64 p p p p p p u64 *u64"),
+    "ecb_combine": ("i32", "i32 u32 *CombinePart u32 u32 u32 p p p p p p *u64"),
+    "ecb_combine_device": ("i32", "i32 u32 *CombinePart u32 u32 u32 p p p p p p *u64"),
+    "ecb_count_alignments": ("i32", "i32 u32 u32 u32 u64 p p p u32 u64 p p p i64 p p p"),
+    "ecb_count_alignments_device": ("i32", "i32 u32 u32 u32 u64 p p p u32 u64 p p p i64 p p p"),
+    "ecb_counters": ("i32", "p *u64 *u64 *u64"),
+    "ecb_create": ("i32", "*Config *p"),
+    "ecb_csr_to_hapcsc": ("i32", "i32 u32 u32 u32 p p p p p u64 *u64"),
+    "ecb_csr_to_hapcsc_device": ("i32", "i32 u32 u32 u32 p p p p p *u64"),
+    "ecb_csr_to_hapcsc_values": ("i32", "i32 u32 u32 u32 p p p p p p p u64 *u64"),
+    "ecb_csr_to_hapcsc_values_device": ("i32", "i32 u32 u32 u32 p p p p p p p *u64"),
+    "ecb_destroy": ("None", "p"),
+    "ecb_device_count": ("i32", None),
+    "ecb_export": ("i32", "p p p p p p p"),
+    "ecb_export_device": ("i32", "p p p p p p p"),
+    "ecb_export_ec_keys_device": ("i32", "p p"),
+    "ecb_export_firsts_device": ("i32", "p p"),
+    "ecb_export_pairs": ("i32", "p p p p p"),
+    "ecb_export_range_minmax": ("i32", "p p p"),
+    "ecb_export_ranges": ("i32", "p p"),
+    "ecb_export_read_ec": ("i32", "p p"),
+    "ecb_finalize": ("i32", "p *Sizes"),
+    "ecb_hapcsc_to_csr": ("i32", "i32 u32 u32 u32 p p u64 p p p *u64"),
+    "ecb_hapcsc_to_csr_device": ("i32", "i32 u32 u32 u32 p p u64 p p p *u64"),
+    "ecb_hint_reads": ("i32", "p u64"),
+    "ecb_last_error": ("str", "p"),
+    "ecb_merge": ("i32", "*p u32 p *Sizes"),
+    "ecb_ms_adopt_triples_device": ("i32", "p u32 *p *p *p *u64 *u64"),
+    "ecb_ms_export": ("i32", "p p p p p p p p"),
+    "ecb_ms_filter": ("i32", "p u32 i64 *MsSizes"),
+    "ecb_ms_local_triples_device": ("i32", "p p p p p u64 u64 p p p *u64"),
+    "ecb_posterior": ("i32", "i32 u32 u32 u32 u64 p p p p p u32 p u32 u64 p p p"),
+    "ecb_posterior_device": ("i32", "i32 u32 u32 u32 u64 p p p p p u32 p u32 u64 p p p"),
+    "ecb_profile": ("i32", "p i32"),
+    "ecb_profile_kernel": ("str", "p"),
+    "ecb_profile_read": ("i32", "p *f64 *u64 *u64"),
+    "ecb_push": ("i32", "p p p p p u64"),
+    "ecb_push_cells": ("i32", "p p u64 u64"),
+    "ecb_push_cells_device": ("i32", "p p u64 u64"),
+    "ecb_push_device": ("i32", "p p p p p u64"),
+    "ecb_push_device_tiled": ("i32", "p p u64"),
+    "ecb_quantify": ("i32", "i32 u32 u32 u32 u64 p p p u32 u64 p p p i64 p p u32 f64 p *u32 *f64 *i64 *u32"),
+    "ecb_quantify_cells": ("i32", "i32 u32 u32 u32 u64 p p p u32 u64 p p p p p p u32 f64 u64 u64 p p p p p p p"),
+    "ecb_quantify_cells_device": ("i32", "i32 u32 u32 u32 u64 p p p u32 u64 p p p p p p u32 f64 u64 u64 p p p p p p p"),
+    "ecb_quantify_cells_model": ("i32", "i32 u32 u32 u32 u64 p p p u32 u64 p p p p p p u32 f64 u64 u32 p u32 u64 p p p p p p p"),
+    "ecb_quantify_cells_model_device": ("i32", "i32 u32 u32 u32 u64 p p p u32 u64 p p p p p p u32 f64 u64 u32 p u32 u64 p p p p p p p"),
+    "ecb_quantify_device": ("i32", "i32 u32 u32 u32 u64 p p p u32 u64 p p p i64 p p u32 f64 p *u32 *f64 *i64 *u32"),
+    "ecb_quantify_model": ("i32", "i32 u32 u32 u32 u64 p p p u32 u64 p p p i64 p p u32 f64 u32 p u32 p *u32 *f64 *i64 *u32"),
+    "ecb_quantify_model_device": ("i32", "i32 u32 u32 u32 u64 p p p u32 u64 p p p i64 p p u32 f64 u32 p u32 p *u32 *f64 *i64 *u32"),
+    "ecb_reset": ("i32", "p"),
+    "ecb_salmon_ecs": ("i32", "i32 p u64 u32 u32 p p u32 u32 u64 p p p p p *u64"),
+    "ecb_salmon_ecs_device": ("i32", "i32 p u64 u32 u32 p p u32 u32 u64 p p p p p *u64"),
+    "ecb_select": ("i32", "i32 u32 u32 u32 u32 u64 p p p u64 p p p i32 p i64 p p p p p p p *u64"),
+    "ecb_select_device": ("i32", "i32 u32 u32 u32 u32 u64 p p p u64 p p p i32 p i64 p p p p p p p *u64"),
+    "ecb_table_adopt_batch_device": ("i32", "p u32 *p *u64 *p *u64"),
+    "ecb_table_adopt_device": ("i32", "p p u64 p u64"),
+    "ecb_table_export_device": ("i32", "p p p u64"),
+    "ecb_table_export_parts_device": ("i32", "p p p u64 u32 *u64 *u64"),
+    "ecb_table_merge_batch_device": ("i32", "p u32 *p *u64 *p *u64"),
+    "ecb_table_merge_device": ("i32", "p p u64 p u64"),
+    "ecb_table_rebase_device": ("i32", "p p u64 u64"),
+    "ecb_table_sizes": ("i32", "p *u64 *u64 *u64"),
+    "ecb_verify_device": ("i32", "p p p p u64 *u64 *u64"),
+    "ecb_verify_device_tiled": ("i32", "p p u64 *u64 *u64"),
+}
+#: what ``load()`` let a build named by ``ECB_LIB`` lack before the table: the host / device pairs of these, and four single symbols
+OPTIONAL = {n + d for n in ("ecb_apply_mask", "ecb_combine", "ecb_salmon_ecs", "ecb_count_alignments", "ecb_bundle", "ecb_select", "ecb_quantify",
+                            "ecb_quantify_model", "ecb_cell_support", "ecb_quantify_cells", "ecb_quantify_cells_model", "ecb_posterior",
+                            "ecb_csr_to_hapcsc_values") for d in ("", "_device")} | {
+    "ecb_merge", "ecb_push_device_tiled", "ecb_verify_device_tiled", "ecb_profile_kernel", "ecb_csr_to_hapcsc", "ecb_hapcsc_to_csr"}
+#: wrapper -> the symbols it may reach (without ``_device``), its own first
+REACHES = {"csr_to_hapcsc": ["ecb_csr_to_hapcsc"], "csr_to_hapcsc_values": ["ecb_csr_to_hapcsc_values"], "hapcsc_to_csr": ["ecb_hapcsc_to_csr"],
+           "apply_mask": ["ecb_apply_mask"], "count_alignments": ["ecb_count_alignments"], "quantify": ["ecb_quantify"],
+           "quantify_model": ["ecb_quantify_model"], "posterior": ["ecb_posterior", "ecb_csr_to_hapcsc"], "cell_support": ["ecb_cell_support"],
+           "quantify_cells": ["ecb_quantify_cells", "ecb_cell_support"], "quantify_cells_model": ["ecb_quantify_cells_model", "ecb_cell_support"],
+           "combine": ["ecb_combine"], "bundle": ["ecb_bundle"], "select": ["ecb_select"], "salmon_ecs": ["ecb_salmon_ecs"]}
+SHORT = {"c_void_p": "p", "c_uint": "u32", "c_ulong": "u64", "c_int": "i32", "c_long": "i64", "c_double": "f64", "c_char_p": "str"}
+
+
+def short(t):
+    name = "None" if t is None else t.__name__
+    star = "*" if name.startswith("LP_") else ""
+    return star + SHORT.get(name[3 * bool(star):], name[3 * bool(star):])
+
+
+class Build(object):
+    """A library that holds every frozen symbol but ``lacking``, for ``load()`` to bind."""
+
+    class Symbol(object):
+        def __call__(self):
+            return self.abi
+
+    def __init__(self, lacking=(), abi=ecb.ABI_VERSION):
+        self.symbols = {n: Build.Symbol() for n in FROZEN if n not in lacking}
+        self.symbols["ecb_abi_version"].abi = abi
+
+    def __getattr__(self, name):
+        try:
+            return self.__dict__["symbols"][name]
+        except KeyError:
+            raise AttributeError(name)
+
+    def bound(self):
+        return {n: (short(getattr(f, "restype", C.c_int)), " ".join(short(t) for t in f.argtypes) if hasattr(f, "argtypes") else None)
+                for n, f in self.symbols.items()}
+
+
+def load_build(monkeypatch, build, ab):
+    monkeypatch.setattr(ecb, "_lib", None)
+    monkeypatch.setattr(ecb, "LIB_PATH", os.path.abspath(__file__))        # (a file that exists)
+    monkeypatch.setattr(ecb.C, "CDLL", lambda path: build)
+    monkeypatch.delenv("ECB_LIB", raising=False)
+    if ab:
+        monkeypatch.setenv("ECB_LIB", "libecb_other.so")
+    assert ecb.load() is build
+    return build.bound()
+
+
+def test_load_binds_the_names_and_argtypes_it_bound_before_the_table(monkeypatch):
+    assert load_build(monkeypatch, Build(), ab=False) == FROZEN
+
+
+def test_the_table_names_every_symbol_once_and_marks_the_optional_ones():
+    names = [n for name, _, _, twin, _ in ecb.SIGNATURES for n in ((name, name + "_device") if twin else (name,))]
+    assert sorted(names) == sorted(FROZEN)
+    assert {n for name, _, _, twin, optional in ecb.SIGNATURES if optional for n in ((name, name + "_device") if twin else (name,))} == OPTIONAL
+
+
+def test_a_build_named_by_ECB_LIB_may_lack_what_is_optional_and_a_normal_build_may_not(monkeypatch):
+    bound = load_build(monkeypatch, Build(lacking=OPTIONAL), ab=True)
+    assert bound == {n: v for n, v in FROZEN.items() if n not in OPTIONAL}
+    with pytest.raises(AttributeError):
+        load_build(monkeypatch, Build(lacking=OPTIONAL), ab=False)
+    for one in ("ecb_posterior", "ecb_merge", "ecb_select_device"):
+        assert one not in load_build(monkeypatch, Build(lacking=(one,)), ab=True)
+        with pytest.raises(AttributeError):
+            load_build(monkeypatch, Build(lacking=(one,)), ab=False)
+    with pytest.raises(AttributeError):                                     # (what is required is required of every build)
+        load_build(monkeypatch, Build(lacking=("ecb_finalize",)), ab=True)
+
+
+def test_a_build_of_another_abi_is_refused_unless_ECB_LIB_names_it(monkeypatch):
+    other = Build(abi=ecb.ABI_VERSION - 1)
+    with pytest.raises(ImportError, match="has ABI %d, this binding is for ABI %d" % (ecb.ABI_VERSION - 1, ecb.ABI_VERSION)):
+        load_build(monkeypatch, other, ab=False)
+    assert load_build(monkeypatch, other, ab=True) == FROZEN
+
+
+@pytest.mark.parametrize("tensors", [False, True], ids=["numpy", "torch"])
+def test_every_wrapper_reaches_its_own_symbol_with_the_tables_number_of_arguments(monkeypatch, tensors):
+    argtypes = {n: a for name, a, _, twin, _ in ecb.SIGNATURES for n in ((name, name + "_device") if twin else (name,))}
+    lib = tr.StandIn(ecb)
+    monkeypatch.setattr(ecb, "_lib", lib)
+    suffix = "_device" if tensors else ""
+    reached = {}
+    for ec, d in tr.inputs(bin_utils, tensors, False):
+        for label, thunk in tr.calls_of(ecb, d, tensors, lib):
+            wrapper, first = label.split()[0], len(lib.calls)
+            wrapper = wrapper[:-5] if wrapper.endswith("_host") else wrapper
+            try:
+                thunk()
+                if label != "combine none":
+                    reached.setdefault(wrapper, set()).update(c[0] for c in lib.calls[first:])
+            except (ValueError, ecb.EcbError):
+                pass
+            for call in lib.calls[first:]:
+                if label == "combine none":                  # (no part, so no array to take the kind from: the host entry point)
+                    assert call[0] == "ecb_combine"
+                    continue
+                assert call[0] in [s + suffix for s in REACHES[wrapper]], (label, call[0])
+                assert len(call) - 1 == len(argtypes[call[0]]), (label, call[0])
+    assert sorted(reached) == sorted(REACHES)
+    for wrapper, symbols in REACHES.items():
+        assert REACHES[wrapper][0] + suffix in reached[wrapper], wrapper
+        assert reached[wrapper] <= {s + suffix for s in symbols}
