@@ -96,14 +96,22 @@ def write_range_file(range_filename, maps, range_len):
             fw.write(main_target + "\t" + "\t".join(str(int(v)) for v in range_len[l]) + "\n")
 
 
+def header_maps(reader, target_filename, strict=False):
+    """The maps of a file's header, restricted to the targets of ``target_filename`` if one is given (``strict``: a target file
+    that names none is an error, as in the reference's ``convert``)."""
+    targets = list(utils.parse_targets(target_filename).keys()) if target_filename else None
+    if strict and targets is not None and len(targets) == 0:
+        raise ValueError("Unable to parse target file")
+    return HeaderMaps(reader.references, reader.lengths, targets)
+
+
 def stream_bam_to_builder(bam_filename, builder, maps=None, target_filename=None, track_ranges=False,
                           encoder_factory=TupleEncoder):
     """Decode one BAM on the host and push its tuples; returns ``(maps, encoder, n_records)``."""
     reader = open_bam(bam_filename, names=builder is None or encoder_factory is not TupleEncoder)
     try:
         if maps is None:
-            targets = list(utils.parse_targets(target_filename).keys()) if target_filename else None
-            maps = HeaderMaps(reader.references, reader.lengths, targets)
+            maps = header_maps(reader, target_filename)
         enc = encoder_factory(maps)
         if builder is None:
             return maps, enc, reader
@@ -117,11 +125,27 @@ def stream_bam_to_builder(bam_filename, builder, maps=None, target_filename=None
             reader.close()
 
 
+def ec_matrices(maps, samples, out):
+    """A run's exported arrays (``indptrA`` ... ``dataN``) as the ``.bin`` / ``.h5`` writers take them."""
+    return ECMatrices(maps.haplotypes, maps.main_targets, maps.lengths, samples, out["indptrA"], out["indicesA"], out["dataA"],
+                      out["indptrN"], out["indicesN"], out["dataN"])
+
+
+def replace_bin(ec_filename, m):
+    """``ecsave2`` in place of whatever has that name."""
+    try:
+        os.remove(ec_filename)
+    except OSError:
+        pass
+    ecsave2(ec_filename, m)
+
+
 def _write_outputs(maps, sample, sizes, out, range_len, ec_filename, emase_filename, range_filename, device=None):
+    """The single-sample run's files.  The multisample run's ``_finish`` shares the two functions above and no more: it does not say
+    where it saves, leaves an existing ``.h5`` to the writer, and differs in the title and in ``incidence_only``."""
     if range_filename:
         write_range_file(range_filename, maps, range_len)
-    m = ECMatrices(maps.haplotypes, maps.main_targets, maps.lengths, [sample], out["indptrA"], out["indicesA"],
-                   out["dataA"], out["indptrN"], out["indicesN"], out["dataN"])
+    m = ec_matrices(maps, [sample], out)
     if emase_filename:
         LOG.info("Saving to {}...".format(emase_filename))
         from . import emase_h5
@@ -132,11 +156,7 @@ def _write_outputs(maps, sample, sizes, out, range_len, ec_filename, emase_filen
         emase_h5.save(emase_filename, m, title='bam2ec', incidence_only=True, count_2d=True, device=device)     # bam_utils.py:845, 861: count is a csc column
     if ec_filename:
         LOG.info("Saving to {}...".format(ec_filename))
-        try:
-            os.remove(ec_filename)
-        except OSError:
-            pass
-        ecsave2(ec_filename, m)
+        replace_bin(ec_filename, m)
 
 
 def _log_summary(maps, sizes):
@@ -230,39 +250,13 @@ def _deal_out(reader, enc, world, builder, track, group_send):
     return per_rank
 
 
-def _rank_convert(rank, world, port, backend, devices, bam_filename, ec_filename, emase_filename, range_filename, sample,
-                  target_filename, result_path):
-    """One process per GPU (the reference: one process per contiguous chunk range, ``bam_utils.py:646-680``).  Rank 0 decodes the
-    BAM once and deals the records out in contiguous read ranges (:func:`_deal_out`; the tuples travel over the process group --
-    xGMI under RCCL); every rank builds the EC table of its range on its GPU; the tables are merged by key range
-    (``dist.exchange_and_merge``: the ordered merge of ``:680-724``), every rank finalizes its range, rank 0 puts the ranges
-    together and writes."""
-    import json
+def _share_out(rk, reader, maps, b, track):
+    """The deal-out over the wire, inside a ``dist.Rank``: rank 0 reads ``reader`` on and sends every other rank its records
+    (:func:`_deal_out`); the others close theirs and push what arrives into ``b``."""
     import torch
     import torch.distributed as tdist
-    from . import dist as ecdist
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    os.environ["MASTER_PORT"] = str(port)
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    dev_index = devices[rank]
-    device = torch.device("cuda", dev_index)
-    torch.cuda.set_device(device)
-    # (a rank waits in its first receive until the decoder has reached its share of the file: minutes on a large BAM -- the
-    #  process group's default timeout, ten minutes under nccl, would abort the job)
-    import datetime
-    patience = datetime.timedelta(seconds=int(os.environ.get("ALNTOOLS_DIST_TIMEOUT_S", str(24 * 3600))))
-    if backend == "nccl":
-        tdist.init_process_group("nccl", rank=rank, world_size=world, device_id=device, timeout=patience)
-    else:
-        tdist.init_process_group(backend, rank=rank, world_size=world, timeout=patience)
-    wire = device if backend == "nccl" else torch.device("cpu")        # where a message lives while it travels
-    targets = list(utils.parse_targets(target_filename).keys()) if target_filename else None
-    track = range_filename is not None
+    rank, world, device, wire = rk.rank, rk.world, rk.device, rk.wire
     n_cols = 4 if track else 3
-    # every rank reads the header (the maps); only rank 0 reads on
-    reader = open_bam(bam_filename, names=False)
-    maps = HeaderMaps(reader.references, reader.lengths, targets)
-    b = EcBuilder(maps.n_loci, maps.n_haplotypes, device=dev_index, track_ranges=track)
     if rank == 0:
         def send(dst, arrays):
             n = 0 if arrays is None else len(arrays[0])
@@ -294,45 +288,34 @@ def _rank_convert(rank, world, port, backend, devices, bam_filename, ec_filename
                 a = msg.numpy()
                 cols = [a[i * ns:i * ns + n] for i in range(n_cols)]
                 b.push(cols[0].view(np.uint32), cols[1].view(np.uint32), cols[2].view(np.uint32), cols[3] if track else None)
-    wrap = lambda e: e if backend == "nccl" else ecdist.HostStagedEngine(e)
-    eng = wrap(ecdist.GpuEngine(b, device))
-    fresh = lambda: wrap(ecdist.GpuEngine(EcBuilder(maps.n_loci, maps.n_haplotypes, device=dev_index, track_ranges=False), device))
-    merged = ecdist.exchange_and_merge(eng, fresh, fresh, root=0, finalize_ranges=True)     # (every rank ranks and emits its own key range)
-    range_len = None
-    if track:
-        mn, mx = b.export_range_minmax()
-        range_len = ecdist.reduce_ranges(mn, mx, device=device if backend == "nccl" else None)
-    if rank == 0:
-        mb = merged.b
-        sizes = mb.finalize()
-        out = mb.export()
-        _log_summary(maps, sizes)
-        _write_outputs(maps, sample, sizes, out, range_len, ec_filename, emase_filename, range_filename, device=dev_index)
-        with open(result_path, "w") as f:
-            json.dump(sizes, f)
-    tdist.barrier()
-    tdist.destroy_process_group()
 
 
-def _convert_multi(n_gpus, bam_filename, ec_filename, emase_filename, range_filename, sample, target_filename):
-    """``ALNTOOLS_GPUS=N``: N processes, one per GPU, RCCL merge (``ALNTOOLS_DIST_BACKEND=gloo`` + ``ALNTOOLS_GPU_LIST=0,0``
-    rehearses the same protocol with several ranks on one GPU, tables staged through host memory)."""
-    import json
-    import socket
-    import tempfile
-    import torch.multiprocessing as mp
-    backend = os.environ.get("ALNTOOLS_DIST_BACKEND", "nccl")
-    devices = [int(x) for x in os.environ.get("ALNTOOLS_GPU_LIST", ",".join(str(i) for i in range(n_gpus))).split(",")]
-    if len(devices) != n_gpus:
-        raise ValueError("ALNTOOLS_GPU_LIST names %d devices for ALNTOOLS_GPUS=%d" % (len(devices), n_gpus))
-    with socket.socket() as so:
-        so.bind(("127.0.0.1", 0))
-        port = so.getsockname()[1]
-    with tempfile.TemporaryDirectory() as td:
-        result = os.path.join(td, "sizes.json")
-        mp.spawn(_rank_convert, args=(n_gpus, port, backend, devices, bam_filename, ec_filename, emase_filename, range_filename,
-                                      sample, target_filename, result), nprocs=n_gpus, join=True)
-        return json.load(open(result))
+def _rank_convert(rank, job, bam_filename, ec_filename, emase_filename, range_filename, sample, target_filename):
+    """One process per GPU (the reference: one process per contiguous chunk range, ``bam_utils.py:646-680``).  Rank 0 decodes the
+    BAM once and deals the records out in contiguous read ranges (:func:`_deal_out`; the tuples travel over the process group --
+    xGMI under RCCL); every rank builds the EC table of its range on its GPU; the tables are merged by key range
+    (``dist.exchange_and_merge``: the ordered merge of ``:680-724``), every rank finalizes its range, rank 0 puts the ranges
+    together and writes."""
+    from . import dist as ecdist
+    with ecdist.Rank(rank, job) as rk:
+        track = range_filename is not None
+        # every rank reads the header (the maps); only rank 0 reads on
+        reader = open_bam(bam_filename, names=False)
+        maps = header_maps(reader, target_filename)
+        b = EcBuilder(maps.n_loci, maps.n_haplotypes, device=rk.dev_index, track_ranges=track)
+        _share_out(rk, reader, maps, b, track)
+        fresh = rk.fresh(maps.n_loci, maps.n_haplotypes)
+        merged = ecdist.exchange_and_merge(rk.engine(b), fresh, fresh, root=0, finalize_ranges=True)     # (every rank ranks and emits its own key range)
+        range_len = None
+        if track:
+            mn, mx = b.export_range_minmax()
+            range_len = ecdist.reduce_ranges(mn, mx, device=rk.wire)
+        if rank == 0:
+            mb = merged.b
+            rk.result = sizes = mb.finalize()
+            out = mb.export()
+            _log_summary(maps, sizes)
+            _write_outputs(maps, sample, sizes, out, range_len, ec_filename, emase_filename, range_filename, device=rk.dev_index)
 
 
 def convert(bam_filename, ec_filename, emase_filename, num_chunks=0, number_processes=-1, temp_dir=None,
@@ -346,17 +329,13 @@ def convert(bam_filename, ec_filename, emase_filename, num_chunks=0, number_proc
         sample = sample.decode('ascii', 'ignore')
     n_gpus = int(os.environ.get("ALNTOOLS_GPUS", "1"))
     if n_gpus > 1:
-        sizes = _convert_multi(n_gpus, bam_filename, ec_filename, emase_filename, range_filename, sample, target_filename)
+        from .dist import spawn_ranks
+        sizes = spawn_ranks(n_gpus, _rank_convert, (bam_filename, ec_filename, emase_filename, range_filename, sample, target_filename))
         LOG.info("Done, total time: {}".format(utils.format_time(start_time, time.time())))
         return sizes
     LOG.info("Parsing file information ...")
     reader = open_bam(bam_filename, names=False)
-    targets = None
-    if target_filename:
-        targets = list(utils.parse_targets(target_filename).keys())
-        if len(targets) == 0:
-            raise ValueError("Unable to parse target file")
-    maps = HeaderMaps(reader.references, reader.lengths, targets)
+    maps = header_maps(reader, target_filename, strict=True)
     device = int(os.environ.get("ALNTOOLS_GPU", "0"))
     temp_time = time.time()
     with EcBuilder(maps.n_loci, maps.n_haplotypes, device=device, track_ranges=range_filename is not None,

@@ -23,10 +23,9 @@ import time
 import numpy as np
 
 from . import utils
-from .bam_utils import BATCH_RECORDS, open_bam, write_range_file
-from .bin_utils import ECMatrices, ecsave2
+from .bam_utils import BATCH_RECORDS, ec_matrices, header_maps, open_bam, replace_bin, write_range_file
 from .ecb import FLAG_MATE_OTHER_REF, FLAG_NEXT_POS_NEG, HAP_SHIFT, EcBuilder, EcbError
-from .tuples import HeaderMaps, record_valid, trim_name
+from .tuples import record_valid, trim_name
 
 LOG = utils.get_logger()
 CELL_BITS = 22
@@ -137,17 +136,12 @@ def _finish(maps, names, sizes, f, range_len, ec_filename, emase_filename, range
     n_ecs_kept = len(f["indptrA"]) - 1
     LOG.info("Number of ECs after filtering : {:,}".format(n_ecs_kept))
     LOG.info("Number of cells after filtering: {:,}".format(len(kept)))
-    m = ECMatrices(maps.haplotypes, maps.main_targets, maps.lengths, [names[c] for c in kept],
-                   f["indptrA"], f["indicesA"], f["dataA"], f["indptrN"], f["indicesN"], f["dataN"])
-    if emase_filename:
+    m = ec_matrices(maps, [names[c] for c in kept], f)
+    if emase_filename:                                                # (unlike the single-sample run: nothing said, an existing file left to the writer)
         from . import emase_h5
         emase_h5.save(emase_filename, m, title='Multisample APM', incidence_only=False, count_2d=True, device=device)   # :806; N is a csc matrix whatever S is (:783-791)
     if ec_filename:
-        try:
-            os.remove(ec_filename)
-        except OSError:
-            pass
-        ecsave2(ec_filename, m)
+        replace_bin(ec_filename, m)
     LOG.info("Done, total time: {}".format(utils.format_time(start_time, time.time())))
     return dict(all_alignments=n_all, valid_alignments=n_valid, n_ecs=n_ecs_kept, n_cells=len(kept),
                 n_ecs_before=sizes["n_ecs"], n_cells_before=len(names), samples=[names[c] for c in kept])
@@ -173,8 +167,7 @@ def _filter(b, n_cells, minimum_count):
 def _header_maps(bam_files, target_filename):
     LOG.info("Parsing the header of {}...".format(bam_files[0]))
     rd = open_bam(bam_files[0])
-    targets = list(utils.parse_targets(target_filename).keys()) if target_filename else None
-    maps = HeaderMaps(rd.references, rd.lengths, targets)              # header of the first file only (:399-465)
+    maps = header_maps(rd, target_filename)                           # header of the first file only (:399-465)
     rd.close()
     return maps
 
@@ -189,7 +182,8 @@ def convert_files(bam_files, ec_filename, emase_filename, minimum_count=-1, rang
         raise ValueError("more than %d input files" % (1 << (32 - CELL_BITS)))
     n_gpus = int(os.environ.get("ALNTOOLS_GPUS", "1"))
     if n_gpus > 1:
-        return _convert_multi(n_gpus, bam_files, ec_filename, emase_filename, minimum_count, range_filename, target_filename)
+        from .dist import spawn_ranks
+        return spawn_ranks(n_gpus, _rank_convert, (list(bam_files), ec_filename, emase_filename, minimum_count, range_filename, target_filename))
     maps = _header_maps(bam_files, target_filename)
     cell_ids = {}
 
@@ -216,131 +210,82 @@ def convert_files(bam_files, ec_filename, emase_filename, minimum_count=-1, rang
     return _finish(maps, names, sizes, f, range_len, ec_filename, emase_filename, range_filename, device, n_all, n_valid, start_time)
 
 
-def _rank_convert(rank, world, port, backend, devices, bam_files, ec_filename, emase_filename, minimum_count, range_filename,
-                  target_filename, result_path):
+def _rank_convert(rank, job, bam_files, ec_filename, emase_filename, minimum_count, range_filename, target_filename):
     """One process per GPU.  Rank r takes the files ``[r F / world, (r + 1) F / world)`` -- contiguous, so the run's read order is
     the reference's file order -- and builds the EC table of their reads on its GPU; cell ids are agreed on first (names in the
     order the files bring them up: rank 0's cells first, then what rank 1 adds ...: the single process's ids); the tables are
     merged by key range over the process group (``dist.exchange_and_merge``), every rank finalizes the range it merged and rank 0
     places the rows, every rank reduces its reads to (EC, cell, file) triples against the merged ECs
     (``dist.exchange_multisample``), and rank 0 filters and writes."""
-    import json
     import pickle
     import torch
     import torch.distributed as tdist
     from . import dist as ecdist
     start_time = time.time()
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    os.environ["MASTER_PORT"] = str(port)
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    dev_index = devices[rank]
-    device = torch.device("cuda", dev_index)
-    torch.cuda.set_device(device)
-    import datetime
-    patience = datetime.timedelta(seconds=int(os.environ.get("ALNTOOLS_DIST_TIMEOUT_S", str(24 * 3600))))      # (ranks scan files of very different sizes)
-    if backend == "nccl":
-        tdist.init_process_group("nccl", rank=rank, world_size=world, device_id=device, timeout=patience)
-    else:
-        tdist.init_process_group(backend, rank=rank, world_size=world, timeout=patience)
-    red = device if backend == "nccl" else torch.device("cpu")
-    maps = _header_maps(bam_files, target_filename)
-    F = len(bam_files)
-    mine = [(fi, bam_files[fi]) for fi in range(rank * F // world, (rank + 1) * F // world)]
-    track = range_filename is not None
-    local_names = {}
+    with ecdist.Rank(rank, job) as rk:                                # (its patience: ranks scan files of very different sizes)
+        world = rk.world
+        maps = _header_maps(bam_files, target_filename)
+        F = len(bam_files)
+        mine = [(fi, bam_files[fi]) for fi in range(rank * F // world, (rank + 1) * F // world)]
+        track = range_filename is not None
+        local_names = {}
 
-    def cell_of(name):                                                # (local ids for now: this rank's order of first appearance)
-        if name not in local_names:
-            local_names[name] = len(local_names)
-        return local_names[name]
+        def cell_of(name):                                            # (local ids for now: this rank's order of first appearance)
+            if name not in local_names:
+                local_names[name] = len(local_names)
+            return local_names[name]
 
-    # Cell ids must be the run's before the reads' cells go to the device: scan first for names only?  No -- the cells of a read
-    # are pushed with local ids and translated on the device side of the wire: push_cells takes ids, so the files are scanned
-    # into host arrays of local ids per file, the name lists are exchanged, and the ids are mapped before push_cells.
-    b = EcBuilder(maps.n_loci, maps.n_haplotypes, device=dev_index, track_ranges=track, multisample=True)
-    pending = []                                                      # (first read, local cell ids | file << CELL_BITS) per file
+        # Cell ids must be the run's before the reads' cells go to the device: scan first for names only?  No -- the cells of a read
+        # are pushed with local ids and translated on the device side of the wire: push_cells takes ids, so the files are scanned
+        # into host arrays of local ids per file, the name lists are exchanged, and the ids are mapped before push_cells.
+        b = EcBuilder(maps.n_loci, maps.n_haplotypes, device=rk.dev_index, track_ranges=track, multisample=True)
+        pending = []                                                  # (first read, local cell ids | file << CELL_BITS) per file
 
-    class _Deferred(object):                                          # the builder as _push_files sees it: cells wait for their ids
-        def push(self, *a):
-            b.push(*a)
+        class _Deferred(object):                                      # the builder as _push_files sees it: cells wait for their ids
+            def push(self, *a):
+                b.push(*a)
 
-        def push_cells(self, meta, first_read):
-            pending.append((first_read, meta))
+            def push_cells(self, meta, first_read):
+                pending.append((first_read, meta))
 
-    n_all, n_valid, n_reads, host_min, host_max = _push_files(_Deferred(), maps, mine, track, cell_of)
-    # the run's cell ids: names in rank order, each rank's in its own order of first appearance
-    blob = pickle.dumps(list(local_names.keys()))
-    sz = torch.tensor([len(blob)], dtype=torch.int64, device=red)
-    allsz = torch.empty(world, dtype=torch.int64, device=red)
-    tdist.all_gather_into_tensor(allsz, sz)
-    allsz = [int(x) for x in allsz.cpu().tolist()]
-    buf = torch.zeros(max(allsz) or 1, dtype=torch.uint8, device=red)
-    buf[:len(blob)] = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(red)
-    allbuf = torch.empty(world * buf.numel(), dtype=torch.uint8, device=red)
-    tdist.all_gather_into_tensor(allbuf, buf)
-    allbuf = allbuf.cpu().numpy().reshape(world, -1)
-    cell_ids = {}
-    for r in range(world):
-        for name in pickle.loads(allbuf[r, :allsz[r]].tobytes()):
-            if name not in cell_ids:
-                cell_ids[name] = len(cell_ids)
-    if len(cell_ids) > (1 << CELL_BITS):
-        raise ValueError("more than %d distinct cells" % (1 << CELL_BITS))
-    names = list(cell_ids.keys())
-    remap = np.asarray([cell_ids[n] for n in local_names.keys()], dtype=np.uint32) if local_names else np.zeros(0, np.uint32)
-    for first_read, meta in pending:
-        b.push_cells(remap[meta & np.uint32((1 << CELL_BITS) - 1)] | (meta & ~np.uint32((1 << CELL_BITS) - 1)), first_read)
-    wrap = lambda e: e if backend == "nccl" else ecdist.HostStagedEngine(e)
-    eng = wrap(ecdist.GpuEngine(b, device))
-    plain = lambda: wrap(ecdist.GpuEngine(EcBuilder(maps.n_loci, maps.n_haplotypes, device=dev_index), device))
-    root = lambda: wrap(ecdist.GpuEngine(EcBuilder(maps.n_loci, maps.n_haplotypes, device=dev_index, multisample=True), device))
-    # Every rank ranks and emits the key range it merged; the root only places the rows (``ecb_assemble_ranges_device``) and takes the
-    # ECs' hashes off the finished rows for the second exchange -- it no longer adopts every merged table and finalizes alone.
-    # (ALNTOOLS_DIST_FINALIZE=root: the earlier ending, the merged tables adopted by the root.)
-    per_range = os.environ.get("ALNTOOLS_DIST_FINALIZE", "ranges") != "root"
-    merged = ecdist.exchange_and_merge(eng, plain, root, root=0, finalize_ranges=per_range)
-    sizes, n_ecs = None, 0
-    if rank == 0:
-        sizes = merged.b.finalize()
-        n_ecs = sizes["n_ecs"]
-    ecdist.exchange_multisample(eng, merged, n_ecs, root=0)
-    tot = torch.tensor([n_all, n_valid], dtype=torch.int64, device=red)
-    tdist.all_reduce(tot)
-    n_all, n_valid = (int(x) for x in tot.cpu().tolist())
-    range_len = None
-    if track:
-        mn, mx = b.export_range_minmax()
-        mn, mx = np.minimum(mn.astype(np.int64), host_min), np.maximum(mx.astype(np.int64), host_max)
-        range_len = ecdist.reduce_ranges(mn.astype(np.int32), mx.astype(np.int32), device=device if backend == "nccl" else None)
-    if rank == 0:
-        _log_counts(maps, n_valid, sizes, len(names))
-        f = _filter(merged.b, len(names), minimum_count)
-        out = _finish(maps, names, sizes, f, range_len, ec_filename, emase_filename, range_filename, dev_index, n_all, n_valid, start_time)
-        with open(result_path, "w") as fh:
-            json.dump(out, fh)
-    tdist.barrier()
-    tdist.destroy_process_group()
-
-
-def _convert_multi(n_gpus, bam_files, ec_filename, emase_filename, minimum_count, range_filename, target_filename):
-    """``ALNTOOLS_GPUS=N``: N processes, one per GPU (``ALNTOOLS_DIST_BACKEND=gloo`` + ``ALNTOOLS_GPU_LIST=0,0`` rehearses the same
-    protocol with several ranks on one GPU, tables staged through host memory)."""
-    import json
-    import socket
-    import tempfile
-    import torch.multiprocessing as mp
-    backend = os.environ.get("ALNTOOLS_DIST_BACKEND", "nccl")
-    devices = [int(x) for x in os.environ.get("ALNTOOLS_GPU_LIST", ",".join(str(i) for i in range(n_gpus))).split(",")]
-    if len(devices) != n_gpus:
-        raise ValueError("ALNTOOLS_GPU_LIST names %d devices for ALNTOOLS_GPUS=%d" % (len(devices), n_gpus))
-    with socket.socket() as so:
-        so.bind(("127.0.0.1", 0))
-        port = so.getsockname()[1]
-    with tempfile.TemporaryDirectory() as td:
-        result = os.path.join(td, "out.json")
-        mp.spawn(_rank_convert, args=(n_gpus, port, backend, devices, list(bam_files), ec_filename, emase_filename, minimum_count,
-                                      range_filename, target_filename, result), nprocs=n_gpus, join=True)
-        return json.load(open(result))
+        n_all, n_valid, n_reads, host_min, host_max = _push_files(_Deferred(), maps, mine, track, cell_of)
+        # the run's cell ids: names in rank order, each rank's in its own order of first appearance
+        cell_ids = {}
+        for blob in ecdist.all_gather_bytes(pickle.dumps(list(local_names.keys())), rk.wire):
+            for name in pickle.loads(blob):
+                if name not in cell_ids:
+                    cell_ids[name] = len(cell_ids)
+        if len(cell_ids) > (1 << CELL_BITS):
+            raise ValueError("more than %d distinct cells" % (1 << CELL_BITS))
+        names = list(cell_ids.keys())
+        remap = np.asarray([cell_ids[n] for n in local_names.keys()], dtype=np.uint32) if local_names else np.zeros(0, np.uint32)
+        for first_read, meta in pending:
+            b.push_cells(remap[meta & np.uint32((1 << CELL_BITS) - 1)] | (meta & ~np.uint32((1 << CELL_BITS) - 1)), first_read)
+        eng = rk.engine(b)
+        # Every rank ranks and emits the key range it merged; the root only places the rows (``ecb_assemble_ranges_device``) and takes the
+        # ECs' hashes off the finished rows for the second exchange -- it no longer adopts every merged table and finalizes alone.
+        # (ALNTOOLS_DIST_FINALIZE=root: the earlier ending, the merged tables adopted by the root.)
+        per_range = os.environ.get("ALNTOOLS_DIST_FINALIZE", "ranges") != "root"
+        merged = ecdist.exchange_and_merge(eng, rk.fresh(maps.n_loci, maps.n_haplotypes),
+                                           rk.fresh(maps.n_loci, maps.n_haplotypes, multisample=True), root=0, finalize_ranges=per_range)
+        sizes, n_ecs = None, 0
+        if rank == 0:
+            sizes = merged.b.finalize()
+            n_ecs = sizes["n_ecs"]
+        ecdist.exchange_multisample(eng, merged, n_ecs, root=0)
+        tot = torch.tensor([n_all, n_valid], dtype=torch.int64, device=rk.wire)
+        tdist.all_reduce(tot)
+        n_all, n_valid = (int(x) for x in tot.cpu().tolist())
+        range_len = None
+        if track:
+            mn, mx = b.export_range_minmax()
+            mn, mx = np.minimum(mn.astype(np.int64), host_min), np.maximum(mx.astype(np.int64), host_max)
+            range_len = ecdist.reduce_ranges(mn.astype(np.int32), mx.astype(np.int32), device=rk.wire)
+        if rank == 0:
+            _log_counts(maps, n_valid, sizes, len(names))
+            f = _filter(merged.b, len(names), minimum_count)
+            rk.result = _finish(maps, names, sizes, f, range_len, ec_filename, emase_filename, range_filename, rk.dev_index, n_all, n_valid,
+                                start_time)
 
 
 def convert(bam_filename, ec_filename, emase_filename, num_chunks=0, minimum_count=-1, number_processes=-1,

@@ -20,9 +20,12 @@ export), then
 
 The functions only need an *engine* with ``table_sizes/counters/table_export/table_export_parts/table_merge(_many)/
 table_adopt(_many)/table_rebase/add_counters/finalize_range/assemble_ranges`` -- :class:`GpuEngine` wraps an :class:`alntools_amd.ecb.EcBuilder`; the CPU ``gloo`` tests
-plug in an oracle-backed engine.
+plug in an oracle-backed engine.  What the protocol's three endings share -- sizes announced, tensors sent to the root, buffers there --
+is :func:`_gather_to_root`; what both converts' ranks share is at the end (:func:`spawn_ranks`, :class:`Rank`).
 """
 from __future__ import annotations
+
+import os
 
 import torch
 import torch.distributed as dist
@@ -167,61 +170,38 @@ class GpuEngine(object):
 class HostStagedEngine(object):
     """A :class:`GpuEngine` seen through CPU tensors, for process groups that only move host memory (``gloo``): used to
     run the multi-rank protocol with real libecb handles when RCCL cannot be (two ranks sharing one GPU in the tests and
-    in ``bench.py``'s ``ECB_DIST_BACKEND=gloo`` rehearsal).  Every table crosses PCIe twice: never a measurement."""
+    in ``bench.py``'s ``ECB_DIST_BACKEND=gloo`` rehearsal).  Every table crosses PCIe twice: never a measurement.
+    One rule for every method of the interface (``_STAGED``, below the class): tensors among the arguments go up to the device,
+    inside lists of tuples too, and tensors in the result come down."""
     device = torch.device("cpu")
 
     def __init__(self, eng):
         self.e, self.dev, self.b = eng, eng.device, eng.b
 
-    def _up(self, t):
-        return t.to(self.dev)
+    def _move(self, a, to):
+        if isinstance(a, torch.Tensor):
+            return a.to(to)
+        return type(a)(self._move(x, to) for x in a) if isinstance(a, (list, tuple)) else a
 
-    def table_sizes(self):
-        return self.e.table_sizes()
+    def table_rebase(self, ent, n, read_base):       # not the rule: nothing to do leaves ``ent`` where it is, and the result stays on the device
+        return self.e.table_rebase(ent.to(self.dev), n, read_base) if read_base and n else ent      # (for the merge that follows: going up is a no-op then)
 
-    def counters(self):
-        return self.e.counters()
+    def table_export_parts(self, read_base, n_parts):       # not the rule: the offsets are host lists already and are handed on as they are
+        ent, prs, eoff, poff = self.e.table_export_parts(read_base, n_parts)
+        return ent.cpu(), prs.cpu(), eoff, poff
 
-    def add_counters(self, *a):
-        self.e.add_counters(*a)
 
-    def table_export(self, read_base):
-        ent, prs = self.e.table_export(read_base)
-        return ent.cpu(), prs.cpu()
+def _staged(name):
+    def method(self, *a):
+        return self._move(getattr(self.e, name)(*self._move(a, self.dev)), self.device)
+    method.__name__ = name
+    return method
 
-    def table_export_parts(self, read_base, n_parts):
-        ent, prs, eo, po = self.e.table_export_parts(read_base, n_parts)
-        return ent.cpu(), prs.cpu(), eo, po
 
-    def table_merge(self, ent, n, prs, m):
-        self.e.table_merge(self._up(ent), n, self._up(prs), m)
-
-    def table_rebase(self, ent, n, read_base):
-        return self.e.table_rebase(self._up(ent), n, read_base) if read_base and n else ent     # (stays on the device: _up is a no-op then)
-
-    def table_merge_many(self, tables):
-        self.e.table_merge_many([(self._up(a), n, self._up(b), m) for a, n, b, m in tables])
-
-    def table_adopt_many(self, tables):
-        self.e.table_adopt_many([(self._up(a), n, self._up(b), m) for a, n, b, m in tables])
-
-    def finalize_range(self, *a):
-        packed, n_ecs, nnz = self.e.finalize_range(*a)
-        return packed.cpu(), n_ecs, nnz
-
-    def assemble_ranges(self, pieces, *a):
-        return self.e.assemble_ranges([(self._up(p), n, m) for p, n, m in pieces], *a)
-
-    def ec_keys(self, n_ecs):
-        packed, nnz = self.e.ec_keys(n_ecs)
-        return packed.cpu(), nnz
-
-    def ms_local_triples(self, packed, n_ecs, nnz, read_base):
-        k, c, f, n = self.e.ms_local_triples(self._up(packed), n_ecs, nnz, read_base)
-        return k.cpu(), c.cpu(), f.cpu(), n
-
-    def ms_adopt_triples(self, tables):
-        return self.e.ms_adopt_triples([(self._up(k), self._up(c), self._up(f), n) for k, c, f, n in tables])
+_STAGED = ("table_sizes", "counters", "add_counters", "table_export", "table_merge", "table_merge_many", "table_adopt", "table_adopt_many",
+           "finalize_range", "assemble_ranges", "ec_keys", "ms_local_triples", "ms_adopt_triples")
+for _name in _STAGED:
+    setattr(HostStagedEngine, _name, _staged(_name))
 
 
 SECTIONS = None          # measurement only (tools/dist_sections.py): a dict that collects seconds per section of the exchange
@@ -247,6 +227,49 @@ def _p2p(ops):
         req.wait()
 
 
+def _wait(dev):
+    """Waits for torch's stream on ``dev``.  libecb works on its own stream: what a message brought must have landed before a
+    handle reads it, and what a message takes must stay alive until it is on the wire."""
+    if dev.type == "cuda":
+        torch.cuda.current_stream(dev).synchronize()
+
+
+def _gather_rows(row, dev, group):
+    """All-gather of one small row of ints per rank -> the rows as a list of lists, in rank order."""
+    world = dist.get_world_size(group)
+    rows = torch.empty(world * len(row), dtype=torch.int64, device=dev)
+    dist.all_gather_into_tensor(rows, torch.tensor(row, dtype=torch.int64, device=dev), group=group)
+    return rows.view(world, len(row)).cpu().tolist()
+
+
+def _gather_to_root(tensors, sizes, words, keep_one, dev, group, root):
+    """The ending every exchange shares: what the ranks hold goes to the root, one batch of messages.  ``sizes``: the row every rank
+    announced (:func:`_gather_rows`); a rank whose row starts with 0 has nothing to send.  ``tensors``: this rank's, of which the
+    first ``words[i](row)`` elements of tensor i travel (none: no message for it); ``keep_one[i]``: the root's buffer for tensor i has
+    one element even where none travels (as the engines' exports have for an empty table).
+    -> ``None`` off the root; on the root ``[(rank, tensors), ...]`` in rank order for the ranks with something to send: its own
+    ``tensors`` as they are, one fresh set of buffers for every other rank."""
+    rank = dist.get_rank(group)
+    if rank != root:
+        if sizes[rank][0]:
+            _p2p([dist.P2POp(dist.isend, t[:w(sizes[rank])], root, group) for t, w in zip(tensors, words) if w(sizes[rank])])
+            _wait(dev)                            # keep the tensors alive until they are on the wire
+        return None
+    got, ops = [], []
+    for r, row in enumerate(sizes):
+        if not row[0]:
+            continue
+        if r == root:
+            got.append((r, tuple(tensors)))
+            continue
+        bufs = tuple(torch.empty(max(w(row), 1) if one else w(row), dtype=t.dtype, device=dev) for t, w, one in zip(tensors, words, keep_one))
+        ops += [dist.P2POp(dist.irecv, b[:w(row)], r, group) for b, w in zip(bufs, words) if w(row)]
+        got.append((r, bufs))
+    _p2p(ops)
+    _wait(dev)
+    return got
+
+
 def exchange_and_merge(engine, make_part_engine, make_root_engine, group=None, root=0, finalize_ranges=False):
     """All ranks call this after pushing their shard.  Returns the merged engine on ``root`` (ready to finalize; already
     finalized with ``finalize_ranges``, where ``finalize()`` only reports the sizes), ``None`` elsewhere.  Two small
@@ -262,12 +285,8 @@ def exchange_and_merge(engine, make_part_engine, make_root_engine, group=None, r
     ent, prs, eoff, poff = engine.table_export_parts(0, world)
     n_all, n_valid, nreads = engine.counters()
     t = _mark("counts + cut by key range", dev, t)
-    cuts = torch.tensor([eoff[q + 1] - eoff[q] for q in range(world)] + [poff[q + 1] - poff[q] for q in range(world)] +
-                        [nreads, n_all, n_valid], dtype=torch.int64, device=dev)
-    width = 2 * world + 3
-    allcuts = torch.empty(world * width, dtype=torch.int64, device=dev)
-    dist.all_gather_into_tensor(allcuts, cuts, group=group)
-    allcuts = allcuts.view(world, width).cpu().tolist()
+    allcuts = _gather_rows([eoff[q + 1] - eoff[q] for q in range(world)] + [poff[q + 1] - poff[q] for q in range(world)] +
+                           [nreads, n_all, n_valid], dev, group)
     in_e = [allcuts[r][rank] for r in range(world)]
     in_p = [allcuts[r][world + rank] for r in range(world)]
     read_base = [sum(allcuts[x][2 * world] for x in range(r)) for r in range(world)]
@@ -292,9 +311,7 @@ def exchange_and_merge(engine, make_part_engine, make_root_engine, group=None, r
             if in_p[r]:
                 ops.append(dist.P2POp(dist.irecv, piece_p[r][:in_p[r] * PAIR_WORDS], r, group))
     _p2p(ops)
-    if dev.type == "cuda":
-        torch.cuda.current_stream(dev).synchronize()
-
+    _wait(dev)
     t = _mark("exchange of key ranges", dev, t)
 
     # 2. merge my key range, in rank order (= stream order), first reads moved to the run's numbering
@@ -304,74 +321,35 @@ def exchange_and_merge(engine, make_part_engine, make_root_engine, group=None, r
     t = _mark("merge of my range (incl. the range handle's reset)", dev, t)
 
     if finalize_ranges:
-        return _finalize_ranges(part, make_root_engine, totals, world, rank, dev, group, root)
+        return _finalize_ranges(part, make_root_engine, totals, dev, group, root)
 
     # 3. the merged ranges are disjoint: gather them on the root, which adopts them as they are
     pe_n, pp_n, _ = part.table_sizes()
     pe, pp = part.table_export(0)
-    mine2 = torch.tensor([pe_n, pp_n], dtype=torch.int64, device=dev)
-    sz2 = torch.empty(world * 2, dtype=torch.int64, device=dev)
-    dist.all_gather_into_tensor(sz2, mine2, group=group)
-    sz2 = sz2.view(world, 2).cpu().tolist()
-    if rank != root:
-        ops = []
-        if pe_n:
-            ops.append(dist.P2POp(dist.isend, pe[:pe_n * ENTRY_WORDS], root, group))
-            if pp_n:
-                ops.append(dist.P2POp(dist.isend, pp[:pp_n * PAIR_WORDS], root, group))
-        _p2p(ops)
-        if dev.type == "cuda":
-            torch.cuda.current_stream(dev).synchronize()     # keep pe / pp alive until they are on the wire
+    sz2 = _gather_rows([pe_n, pp_n], dev, group)
+    got = _gather_to_root((pe, pp), sz2, (lambda row: row[0] * ENTRY_WORDS, lambda row: row[1] * PAIR_WORDS), (False, True), dev, group, root)
+    if got is None:
         return None
-    bufs, ops = {}, []
-    for r in range(world):
-        e_r, p_r = sz2[r]
-        if r == root or not e_r:
-            continue
-        bufs[r] = (torch.empty(e_r * ENTRY_WORDS, dtype=torch.int64, device=dev),
-                   torch.empty(max(p_r, 1) * PAIR_WORDS, dtype=torch.int64, device=dev))
-        ops.append(dist.P2POp(dist.irecv, bufs[r][0], r, group))
-        if p_r:
-            ops.append(dist.P2POp(dist.irecv, bufs[r][1][:p_r * PAIR_WORDS], r, group))
-    _p2p(ops)
-    if dev.type == "cuda":
-        torch.cuda.current_stream(dev).synchronize()
     merged = make_root_engine()
-    merged.table_adopt_many([(pe, sz2[r][0], pp, sz2[r][1]) if r == root else (bufs[r][0], sz2[r][0], bufs[r][1], sz2[r][1])
-                             for r in range(world) if sz2[r][0]])
+    merged.table_adopt_many([(e, sz2[r][0], p, sz2[r][1]) for r, (e, p) in got])
     merged.add_counters(*totals)
     return merged
 
 
-def _finalize_ranges(part, make_root_engine, totals, world, rank, dev, group, root):
+def _finalize_ranges(part, make_root_engine, totals, dev, group, root):
     """Step 3 of :func:`exchange_and_merge` for single-sample runs: every rank finalizes the key range it merged, the root
     places the finished rows.  One message of ``piece_words`` int32 per rank."""
     t = _mark(None, dev, 0.0)
     packed, n_ecs, nnz = part.finalize_range(*totals)
     t = _mark("finalize of my range", dev, t)
-    mine = torch.tensor([n_ecs, nnz], dtype=torch.int64, device=dev)
-    sz = torch.empty(world * 2, dtype=torch.int64, device=dev)
-    dist.all_gather_into_tensor(sz, mine, group=group)
-    sz = sz.view(world, 2).cpu().tolist()
+    sz = _gather_rows([n_ecs, nnz], dev, group)
     t = _mark("all-gather of piece sizes", dev, t)
-    if rank != root:
-        if n_ecs:
-            _p2p([dist.P2POp(dist.isend, packed, root, group)])
-            if dev.type == "cuda":
-                torch.cuda.current_stream(dev).synchronize()
+    got = _gather_to_root((packed,), sz, (lambda row: piece_words(*row),), (False,), dev, group, root)
+    if got is None:
         return None
-    bufs, ops = {}, []
-    for r in range(world):
-        if r == root or not sz[r][0]:
-            continue
-        bufs[r] = torch.empty(piece_words(*sz[r]), dtype=torch.int32, device=dev)
-        ops.append(dist.P2POp(dist.irecv, bufs[r], r, group))
-    _p2p(ops)
-    if dev.type == "cuda":
-        torch.cuda.current_stream(dev).synchronize()
     t = _mark("pieces to the root", dev, t)
     merged = make_root_engine()
-    merged.assemble_ranges([(packed if r == root else bufs[r], sz[r][0], sz[r][1]) for r in range(world) if sz[r][0]], *totals)
+    merged.assemble_ranges([(piece, sz[r][0], sz[r][1]) for r, (piece,) in got], *totals)
     _mark("assembly on the root (incl. its handle's reset)", dev, t)
     return merged
 
@@ -384,45 +362,23 @@ def exchange_multisample(engine, merged, n_ecs, group=None, root=0):
     root, which adds up the ones a cell has on two ranks.
     ``merged`` / ``n_ecs``: the finalized root engine and its EC count on the root, ignored elsewhere.  Returns the number
     of distinct triples on the root (then ``export_pairs`` works as on one GPU), None elsewhere."""
-    world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     dev = engine.device
     nreads = engine.table_sizes()[2]
     keys, nnz = merged.ec_keys(n_ecs) if rank == root else (None, 0)
-    info = torch.tensor([nreads, n_ecs if rank == root else 0, nnz], dtype=torch.int64, device=dev)
-    allinfo = torch.empty(world * 3, dtype=torch.int64, device=dev)
-    dist.all_gather_into_tensor(allinfo, info, group=group)
-    allinfo = allinfo.view(world, 3).cpu().tolist()
+    allinfo = _gather_rows([nreads, n_ecs if rank == root else 0, nnz], dev, group)
     read_base = sum(a[0] for a in allinfo[:rank])
     n_ecs, nnz = allinfo[root][1], allinfo[root][2]
     if rank != root:
         keys = torch.empty(ec_keys_words(n_ecs, nnz), dtype=torch.int64, device=dev)
     dist.broadcast(keys, src=root, group=group)
-    if dev.type == "cuda":
-        torch.cuda.current_stream(dev).synchronize()     # libecb works on its own stream: the keys must have landed
+    _wait(dev)                                    # the keys must have landed
     key, cnt, first, n = engine.ms_local_triples(keys, n_ecs, nnz, read_base)
-    mine = torch.tensor([n], dtype=torch.int64, device=dev)
-    alln = torch.empty(world, dtype=torch.int64, device=dev)
-    dist.all_gather_into_tensor(alln, mine, group=group)
-    alln = alln.cpu().tolist()
-    if rank != root:
-        if n:
-            _p2p([dist.P2POp(dist.isend, t[:n], root, group) for t in (key, cnt, first)])
-            if dev.type == "cuda":
-                torch.cuda.current_stream(dev).synchronize()
+    alln = _gather_rows([n], dev, group)
+    got = _gather_to_root((key, cnt, first), alln, (lambda row: row[0],) * 3, (False,) * 3, dev, group, root)
+    if got is None:
         return None
-    bufs, ops = {}, []
-    for r in range(world):
-        if r == root or not alln[r]:
-            continue
-        bufs[r] = (torch.empty(alln[r], dtype=torch.int64, device=dev), torch.empty(alln[r], dtype=torch.int32, device=dev),
-                   torch.empty(alln[r], dtype=torch.int32, device=dev))
-        ops += [dist.P2POp(dist.irecv, t, r, group) for t in bufs[r]]
-    _p2p(ops)
-    if dev.type == "cuda":
-        torch.cuda.current_stream(dev).synchronize()
-    tables = [((key, cnt, first) if r == root else bufs[r]) + (alln[r],) for r in range(world) if alln[r]]
-    return merged.ms_adopt_triples(tables)
+    return merged.ms_adopt_triples([triples + (alln[r][0],) for r, triples in got])
 
 
 def reduce_ranges(range_min, range_max, group=None, device=None):
@@ -439,6 +395,20 @@ def reduce_ranges(range_min, range_max, group=None, device=None):
     return np.where(mx >= mn, mx - mn + 1, 0)
 
 
+def all_gather_bytes(blob, device, group=None):
+    """Every rank's ``blob`` (bytes: a pickle, say) -> all of them in rank order, on every rank.  Two all-gathers: the lengths, then
+    the blobs, each padded to the longest."""
+    world = dist.get_world_size(group)
+    sizes = [row[0] for row in _gather_rows([len(blob)], device, group)]
+    buf = torch.zeros(max(sizes) or 1, dtype=torch.uint8, device=device)
+    if blob:
+        buf[:len(blob)] = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(device)
+    allbuf = torch.empty(world * buf.numel(), dtype=torch.uint8, device=device)
+    dist.all_gather_into_tensor(allbuf, buf, group=group)
+    allbuf = allbuf.cpu().numpy().reshape(world, -1)
+    return [allbuf[r, :sizes[r]].tobytes() for r in range(world)]
+
+
 def exchange_and_merge_on_root(engine, make_root_engine, group=None, root=0):
     """The simpler protocol (kept for comparison and as a fallback): every rank sends its whole table to the root, which
     merges them one after the other.  The root's merges are serial: at 8 ranks they cost more than a rank's own shard."""
@@ -447,19 +417,15 @@ def exchange_and_merge_on_root(engine, make_root_engine, group=None, root=0):
     ne, npairs, nreads = engine.table_sizes()
     n_all, n_valid, _ = engine.counters()
     dev = engine.device
-    mine = torch.tensor([ne, npairs, nreads, n_all, n_valid], dtype=torch.int64, device=dev)
-    sizes = torch.empty(world * 5, dtype=torch.int64, device=dev)
-    dist.all_gather_into_tensor(sizes, mine, group=group)
-    sizes = sizes.view(world, 5).cpu().tolist()
+    sizes = _gather_rows([ne, npairs, nreads, n_all, n_valid], dev, group)
     read_base = sum(s[2] for s in sizes[:rank])
     ent, prs = engine.table_export(read_base)
+    # (not :func:`_gather_to_root`: that waits for the whole batch, and the root here merges a table while the later ones still
+    #  arrive; a sender here has never waited for torch's stream after its requests either, and still does not)
     if rank != root:
         if ne:
-            ops = [dist.P2POp(dist.isend, ent[:ne * ENTRY_WORDS], root, group)]
-            if npairs:
-                ops.append(dist.P2POp(dist.isend, prs[:npairs * PAIR_WORDS], root, group))
-            for req in dist.batch_isend_irecv(ops):
-                req.wait()
+            _p2p([dist.P2POp(dist.isend, ent[:ne * ENTRY_WORDS], root, group)] +
+                 ([dist.P2POp(dist.isend, prs[:npairs * PAIR_WORDS], root, group)] if npairs else []))
         return None
     bufs, ops, owner = {}, [], []
     for r in range(world):
@@ -489,8 +455,79 @@ def exchange_and_merge_on_root(engine, make_root_engine, group=None, root=0):
         for req, o in zip(reqs, owner):
             if o == r:
                 req.wait()
-        if dev.type == "cuda":
-            torch.cuda.current_stream(dev).synchronize()
+        _wait(dev)
         merged.table_merge(bufs[r][0], e_r, bufs[r][1], p_r)
     merged.add_counters(sum(s[3] for s in sizes), sum(s[4] for s in sizes), sum(s[2] for s in sizes))
     return merged
+
+
+# --- one process per GPU: the scaffold of ``bam_utils.convert`` and ``bam_utils_multisample.convert_files`` under ALNTOOLS_GPUS=N ----
+
+def spawn_ranks(n_gpus, worker, args):
+    """``ALNTOOLS_GPUS=N``: N processes, one per GPU, each running ``worker(rank, job, *args)`` -- a module-level function that works
+    inside ``with Rank(rank, job) as rk`` -- over RCCL (``ALNTOOLS_DIST_BACKEND=gloo`` + ``ALNTOOLS_GPU_LIST=0,0`` rehearses the same
+    protocol with several ranks on one GPU, tables staged through host memory).  -> what rank 0 left in ``rk.result``."""
+    import json
+    import socket
+    import tempfile
+    import torch.multiprocessing as mp
+    backend = os.environ.get("ALNTOOLS_DIST_BACKEND", "nccl")
+    devices = [int(x) for x in os.environ.get("ALNTOOLS_GPU_LIST", ",".join(str(i) for i in range(n_gpus))).split(",")]
+    if len(devices) != n_gpus:
+        raise ValueError("ALNTOOLS_GPU_LIST names %d devices for ALNTOOLS_GPUS=%d" % (len(devices), n_gpus))
+    with socket.socket() as so:
+        so.bind(("127.0.0.1", 0))
+        port = so.getsockname()[1]
+    with tempfile.TemporaryDirectory() as td:
+        result = os.path.join(td, "result.json")
+        mp.spawn(worker, args=((n_gpus, port, backend, devices, result),) + tuple(args), nprocs=n_gpus, join=True)
+        return json.load(open(result))
+
+
+class Rank(object):
+    """What every rank of :func:`spawn_ranks` opens and closes with.  Entering: the rendezvous address, this rank's GPU, the process
+    group.  Leaving without an exception: rank 0 writes ``result`` for the spawner, then barrier and destroy; a rank that raises
+    does none of it -- it must not leave the others waiting in a barrier, ``mp.spawn`` ends them.
+    ``device`` / ``dev_index``: this rank's GPU; ``wire``: where a message lives while it travels (and where reductions run)."""
+
+    def __init__(self, rank, job):
+        self.rank = rank
+        self.world, self.port, self.backend, devices, self.result_path = job
+        self.dev_index = devices[rank]
+        self.device = torch.device("cuda", self.dev_index)
+        self.wire = self.device if self.backend == "nccl" else torch.device("cpu")
+        self.result = None
+
+    def __enter__(self):
+        import datetime
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        os.environ["MASTER_PORT"] = str(self.port)
+        os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+        torch.cuda.set_device(self.device)
+        # (a rank waits in its first receive until the decoder has reached its share of the file, or until the others have scanned
+        #  files of very different sizes: minutes on a large BAM -- the process group's default timeout, ten minutes under nccl,
+        #  would abort the job)
+        patience = datetime.timedelta(seconds=int(os.environ.get("ALNTOOLS_DIST_TIMEOUT_S", str(24 * 3600))))
+        extra = dict(device_id=self.device) if self.backend == "nccl" else {}
+        dist.init_process_group(self.backend, rank=self.rank, world_size=self.world, timeout=patience, **extra)
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            if self.rank == 0:
+                import json
+                with open(self.result_path, "w") as f:
+                    json.dump(self.result, f)
+            dist.barrier()
+            dist.destroy_process_group()
+        return False
+
+    def engine(self, builder):
+        """``builder`` as the protocol takes it: staged through host memory unless the process group moves device memory."""
+        e = GpuEngine(builder, self.device)
+        return e if self.backend == "nccl" else HostStagedEngine(e)
+
+    def fresh(self, n_loci, n_haps, **kw):
+        """-> a factory of engines around a new ``EcBuilder`` on this rank's GPU (``make_part_engine`` / ``make_root_engine``)."""
+        from .ecb import EcBuilder
+        return lambda: self.engine(EcBuilder(n_loci, n_haps, device=self.dev_index, **kw))
