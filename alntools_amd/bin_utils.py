@@ -490,6 +490,68 @@ def ecquant(ec_filename, out_filename, sample=None, use_lengths=False, max_iters
             fh.write(table)
 
 
+def boot_table(lname, hname, theta, mean, sd, tot_mean, tot_sd):
+    """The text ``ecboot`` writes: a header ``locus``, then per haplotype ``<h>, <h>_mean, <h>_sd``, then ``total, total_mean, total_sd``, and
+    one tab-separated line per target: the point estimate as :func:`quant_table` writes it, the bootstrap's mean and standard deviation beside
+    it; every number ``str(float(v))``."""
+    theta, mean, sd = (np.asarray(a, dtype=np.float64) for a in (theta, mean, sd))
+    tot_mean, tot_sd = np.asarray(tot_mean, dtype=np.float64), np.asarray(tot_sd, dtype=np.float64)
+    out = ["locus\t" + "\t".join("{0}\t{0}_mean\t{0}_sd".format(h) for h in hname) + "\ttotal\ttotal_mean\ttotal_sd\n"]
+    for t, name in enumerate(lname):
+        cells = [name]
+        for h in range(len(hname)):
+            cells += [str(float(theta[h, t])), str(float(mean[h, t])), str(float(sd[h, t]))]
+        out.append("\t".join(cells + [str(float(theta[:, t].sum())), str(float(tot_mean[t])), str(float(tot_sd[t]))]) + "\n")
+    return "".join(out)
+
+
+def ecboot(ec_filename, out_filename, n_boot=None, seed=0, sample=None, use_lengths=False, max_iters=1000, tol=1e-6, device=0, model=4, groups=None,
+           replicates_file=None):
+    """``alntools ecboot``: bootstrap standard errors for ``ecquant``.  ``n_boot`` replicates of the reads of a ``.bin`` (all samples pooled, or
+    the one named ``sample``) are redrawn on the GPU under ``seed`` and each is quantified as ``ecquant`` with the same options would
+    (``ecb_boot.quantify_bootstrap``); the table (:func:`boot_table`) holds ``ecquant``'s own point estimate from these options and, beside
+    it, the mean and the standard deviation over the replicates.  ``replicates_file``: the replicates' estimates, float64 ``[B, H, T]``, as a
+    ``.npy``.  A failure is logged as ``Error: ...`` and raised again; no file is written then."""
+    from . import ecb, ecb_boot
+    written = []
+    with command(KEY, created=out_filename, written=written):
+        check_model(model, groups)
+        if n_boot is None or int(n_boot) < 1:
+            raise ValueError("the number of bootstrap replicates (-b) must be at least 1")
+        if int(seed) < 0 or int(seed) >= 1 << 64:
+            raise ValueError("the seed must be in [0, 2^64)")
+        LOG.info("Loading {}...".format(ec_filename))
+        m = ecload(ec_filename)
+        col = sample_column(m, sample, ec_filename)
+        args = (m.indptrA, m.indicesA, m.dataA, m.num_loci, m.num_haplotypes, m.indptrN, m.indicesN, m.dataN)
+        gene, names = gene_ids(m, groups) if model != 4 else (None, ())
+        scale = None
+        if use_lengths:
+            scale = length_scale(m, ecb.count_alignments(*args, sample=col, device=device)[0])
+        LOG.info("Estimating abundances...")
+        if model == 4:
+            theta, info = ecb.quantify(*args, sample=col, scale=scale, max_iters=max_iters, tol=tol, device=device)
+        else:
+            theta, info = ecb.quantify_model(*args, gene=gene, n_genes=len(names), model=model, sample=col, scale=scale, max_iters=max_iters,
+                                             tol=tol, device=device)
+        LOG.info("iterations: {:,}; delta: {!r}; explained reads: {:,}; {}".format(info["n_iter"], info["delta"], info["explained"],
+                                                                                  "converged" if info["converged"] else "not converged"))
+        LOG.info("Bootstrapping ({:,} replicates, seed {})...".format(int(n_boot), int(seed)))
+        res = ecb_boot.quantify_bootstrap(*args, n_reps=int(n_boot), seed=int(seed), sample=col, scale=scale, max_iters=max_iters, tol=tol, gene=gene,
+                                          n_genes=len(names), model=model, device=device, return_reps=replicates_file is not None)
+        mean, sd, tot_mean, tot_sd, binfo = res[:5]
+        LOG.info("replicates converged: {:,} of {:,}; most iterations: {:,}".format(int(np.sum(binfo["converged"])), int(n_boot),
+                                                                                   int(np.max(binfo["n_iter"]))))
+        table = boot_table(m.lname, m.hname, theta, mean, sd, tot_mean, tot_sd)
+        if replicates_file is not None:
+            with open(replicates_file, 'wb') as fh:
+                written.append(replicates_file)
+                np.save(fh, np.asarray(res[5], dtype=np.float64))
+        with open(out_filename, 'w') as fh:
+            written.append(out_filename)
+            fh.write(table)
+
+
 def cells_table(sname, lname, hname, cell_ptr, slot_locus, theta):
     """The text ``ecquant-cells`` writes: a header ``sample, locus, <haplotype names>, total`` and one tab-separated line per slot -- a target
     in the support of a cell -- in cell order, every number as :func:`quant_table` writes them (``str(float(v))``)."""

@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
 """Command line with the reference's hot-path sub-commands and options (``alntools/cli.py:43-113``):
-``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``, ``apply-genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``count-alignments``, ``ecquant`` (``-w``: the posterior of every alignment too), ``ecquant-cells``, ``ecdump``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
+``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``, ``apply-genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``count-alignments``, ``ecquant`` (``-w``: the posterior of every alignment too), ``ecboot``, ``ecquant-cells``, ``ecdump``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
 from __future__ import annotations
 
 import glob
@@ -223,6 +223,34 @@ def ecquant(ec_file, out_file, sample, use_lengths, max_iters, tol, model, group
         methods.ecquant(ec_file, out_file, sample, use_lengths, max_iters, tol, *more, **named)
     except Exception:
         sys.exit(1)                                                  # (logged as "Error: ..." by bin_utils.ecquant)
+
+
+@cli.command('ecboot', options_metavar='<options>', short_help='bootstrap standard errors for ecquant: the reads redrawn on the GPU')
+@click.argument('ec_file', metavar='ec_file', type=click.Path(exists=True, resolve_path=True, dir_okay=False))
+@click.argument('out_file', metavar='out_file', type=click.Path(resolve_path=True, dir_okay=False, writable=True))
+@click.option('-b', '--bootstraps', 'n_boot', required=True, type=click.IntRange(min=1), help='number of bootstrap replicates')
+@click.option('--seed', default=0, type=click.IntRange(min=0, max=(1 << 64) - 1), help='seed of the resampling (default: 0)')
+@click.option('-s', '--sample', metavar='sample', default=None, help="bootstrap one sample of a multisample file (default: all of them pooled)")
+@click.option('-l', '--use-lengths', is_flag=True, help='weight every abundance by 1 / the length of its target')
+@click.option('-i', '--max-iters', default=1000, type=click.IntRange(min=0), help='EM steps at the most, per replicate too (default: 1000)')
+@click.option('-t', '--tolerance', 'tol', default=1e-6, type=float, help='stop when one step changes less than this share of the reads (default: 1e-6)')
+@click.option('-M', '--model', default='4', type=click.Choice(['1', '2', '3', '4']),
+              help='EMASE model: 1 gene->allele->isoform, 2 gene->isoform->allele, 3 gene->isoform x allele (each needs -g), 4 flat (default: 4)')
+@click.option('-g', '--groups', metavar='<grp_file>', default=None, type=click.Path(exists=True, resolve_path=True, dir_okay=False),
+              help='group file (gene, transcripts...) for models 1 to 3')
+@click.option('--replicates', 'replicates', metavar='<npy_file>', default=None, type=click.Path(resolve_path=True, dir_okay=False, writable=True),
+              help="also write every replicate's estimates, float64 [B, H, T], as a .npy file")
+@click.option('-v', '--verbose', count=True, help='enables verbose mode')
+def ecboot(ec_file, out_file, n_boot, seed, sample, use_lengths, max_iters, tol, model, groups, replicates, verbose):
+    """
+    Redraw the reads of a binary EC file (ec_file) n_boot times, quantify every replicate as ecquant would and write ecquant's estimate with
+    the replicates' mean and standard deviation beside it to a table (out_file)
+    """
+    utils.configure_logging(verbose)
+    try:
+        methods.ecboot(ec_file, out_file, n_boot, seed, sample, use_lengths, max_iters, tol, int(model), groups, replicates)
+    except Exception:
+        sys.exit(1)                                                  # (logged as "Error: ..." by bin_utils.ecboot)
 
 
 @cli.command('ecquant-cells', options_metavar='<options>', short_help='estimate abundances per sample (cell) of a multisample EC file by EM')

@@ -5063,6 +5063,9 @@ extern "C" int ecb_count_alignments(int device, uint32_t n_ecs, uint32_t n_loci,
 #include "quant_cells_model.inc"
 // ... and the posterior of every alignment at a given theta (ecb_posterior*)
 #include "quant_post.inc"
+// ... and bootstrap replicates of N and the moments of their estimates (ecb_resample* / ecb_quantify_bootstrap*)
+#include "boot_draw.h"
+#include "boot.inc"
 
 // ---- ecselect: the reads of one class and the samples that still count enough of them, pulled out of a .bin (ecb_select / ecb_select_device)
 // (AlignmentPropertyMatrix.get_unique_reads / pull_alignments_from, AlignmentPropertyMatrix.py:386-427, and the cell threshold of

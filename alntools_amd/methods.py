@@ -1,5 +1,5 @@
 # -*- coding: utf-8 -*-
-"""Same driver functions as the reference's ``alntools/methods.py:32-53, 205-210``, ``apply_genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``count_alignments``, ``ecquant``, ``ecquant_cells`` and ``ecdump`` for the hot path."""
+"""Same driver functions as the reference's ``alntools/methods.py:32-53, 205-210``, ``apply_genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``count_alignments``, ``ecquant``, ``ecboot``, ``ecquant_cells`` and ``ecdump`` for the hot path."""
 from __future__ import annotations
 
 from . import bam_utils, bin_utils
@@ -70,6 +70,11 @@ def count_alignments(ec_file, out_file, sample=None):
 def ecquant(ec_file, out_file, sample=None, use_lengths=False, max_iters=1000, tol=1e-6, model=4, groups=None, posterior_file=None):
     named = {} if posterior_file is None else {"posterior_file": posterior_file}
     bin_utils.ecquant(ec_file, out_file, sample=sample, use_lengths=use_lengths, max_iters=max_iters, tol=tol, model=model, groups=groups, **named)
+
+
+def ecboot(ec_file, out_file, n_boot=None, seed=0, sample=None, use_lengths=False, max_iters=1000, tol=1e-6, model=4, groups=None, replicates_file=None):
+    bin_utils.ecboot(ec_file, out_file, n_boot=n_boot, seed=seed, sample=sample, use_lengths=use_lengths, max_iters=max_iters, tol=tol, model=model,
+                     groups=groups, replicates_file=replicates_file)
 
 
 def ecquant_cells(ec_file, out_file, samples=None, samples_file=None, use_lengths=False, max_iters=1000, tol=1e-6, report=None, model=4, groups=None):

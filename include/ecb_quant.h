@@ -54,5 +54,7 @@ int ecb_quantify(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, u
 #include "ecb_quant_cells_model.h"
 /* ... and the posterior probability of every alignment at a given theta (ecb_posterior*): likewise */
 #include "ecb_quant_post.h"
+/* ... and bootstrap replicates of N, the mean and standard deviation of their estimates (ecb_resample* / ecb_quantify_bootstrap*): likewise */
+#include "ecb_quant_boot.h"
 
 #endif /* ECB_QUANT_H */
