@@ -552,6 +552,73 @@ def ecboot(ec_filename, out_filename, n_boot=None, seed=0, sample=None, use_leng
             fh.write(table)
 
 
+def clusters_file(lname, comp_of_locus, multi_only=False, source="the .bin"):
+    """The text ``ecclusters`` writes and the components it holds -> ``(text, written)``: a group file as :func:`load_groups` reads it, one
+    line per component in component order -- the name of its lowest-numbered target, then all its targets, that one included, in target
+    order, tab-separated.  ``multi_only``: the components of one target are left out.  ``written``: the components on the lines, ascending.
+    Two targets of one name among those that head a line are a ValueError naming it (``ecbundle`` would refuse the file)."""
+    comp = np.asarray(comp_of_locus, dtype=np.int64)
+    order = np.argsort(comp, kind="stable")                             # by component, then by target
+    sizes = np.bincount(comp, minlength=0)
+    ends = np.cumsum(sizes)
+    written = np.flatnonzero(sizes >= (2 if multi_only else 1))
+    seen = set()
+    out = []
+    for c in written:
+        members = order[ends[c] - sizes[c]:ends[c]]
+        head = lname[members[0]]
+        if head in seen:
+            raise ValueError("{}: two targets named {} would each head a cluster".format(source, head))
+        seen.add(head)
+        out.append("\t".join([head] + [lname[t] for t in members]) + "\n")
+    return "".join(out), written
+
+
+def clusters_stats(written, comp_loci, comp_ecs, comp_reads):
+    """The text of ``ecclusters --stats``: a header ``cluster, targets, ecs, reads`` and one line of integers per written component -- its
+    number, its targets, the ECs that tie them together and the reads of those ECs."""
+    out = ["cluster\ttargets\tecs\treads\n"]
+    for c in written:
+        out.append("{}\t{}\t{}\t{}\n".format(int(c), int(comp_loci[c]), int(comp_ecs[c]), int(comp_reads[c])))
+    return "".join(out)
+
+
+def ecclusters(ec_filename, out_filename, sample=None, min_count=1, stats_file=None, multi_only=False, device=0):
+    """``alntools ecclusters``: the targets of a ``.bin`` grouped by the reads they share -- the connected components of its target-EC
+    incidence, found on the GPU (``ecb_components.components``) -- written as a group file (:func:`clusters_file`) that ``ecbundle`` and
+    ``ecquant -M 1|2|3 -g`` take as it stands.  An EC ties its targets together when it counts ``min_count`` reads or more, over all samples
+    pooled or in the one named ``sample``.  ``stats_file``: the table of :func:`clusters_stats`.  ``multi_only``: the clusters of one
+    target are left out (``gene_ids`` gives an unlisted target a gene of its own, so both files mean the same to ``-M``; ``ecbundle`` drops
+    the alignments of an unlisted target, so only the default file loses nothing there).  A failure is logged as ``Error: ...`` and raised
+    again; no file is written then."""
+    written = []
+    with command(KEY, created=out_filename, written=written):
+        if int(min_count) < 0:
+            raise ValueError("the minimum count (-m) must be at least 0")
+        LOG.info("Loading {}...".format(ec_filename))
+        m = ecload(ec_filename)
+        col = sample_column(m, sample, ec_filename)
+        from . import ecb_components
+        LOG.info("Finding the clusters of {:,} targets...".format(m.num_loci))
+        of_locus, _of_ec, loci, ecs, reads, sizes = ecb_components.components(
+            m.indptrA, m.indicesA, m.dataA, m.num_loci, m.num_haplotypes, m.indptrN, m.indicesN, m.dataN, sample=col, min_count=int(min_count),
+            device=device)
+        n_comp, n_link, largest, n_multi = sizes
+        total = int(np.sum(reads))
+        big = int(np.argmax(loci)) if n_comp else 0
+        LOG.info("Number of clusters: {:,} ({:,} of two targets or more), from {:,} linking ECs".format(n_comp, n_multi, n_link))
+        LOG.info("Largest cluster: {:,} targets ({:.1%} of the targets), {:,} reads ({:.1%} of the linking reads)".format(
+            largest, largest / max(m.num_loci, 1), int(reads[big]) if n_comp else 0, (int(reads[big]) / total) if total else 0.0))
+        text, ids = clusters_file(m.lname, of_locus, multi_only=multi_only, source=ec_filename)
+        if stats_file is not None:
+            with open(stats_file, 'w') as fh:
+                written.append(stats_file)
+                fh.write(clusters_stats(ids, loci, ecs, reads))
+        with open(out_filename, 'w') as fh:
+            written.append(out_filename)
+            fh.write(text)
+
+
 def cells_table(sname, lname, hname, cell_ptr, slot_locus, theta):
     """The text ``ecquant-cells`` writes: a header ``sample, locus, <haplotype names>, total`` and one tab-separated line per slot -- a target
     in the support of a cell -- in cell order, every number as :func:`quant_table` writes them (``str(float(v))``)."""

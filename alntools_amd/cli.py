@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
 """Command line with the reference's hot-path sub-commands and options (``alntools/cli.py:43-113``):
-``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``, ``apply-genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``count-alignments``, ``ecquant`` (``-w``: the posterior of every alignment too), ``ecboot``, ``ecquant-cells``, ``ecdump``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
+``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``, ``apply-genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``count-alignments``, ``ecquant`` (``-w``: the posterior of every alignment too), ``ecboot``, ``ecclusters``, ``ecquant-cells``, ``ecdump``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
 from __future__ import annotations
 
 import glob
@@ -251,6 +251,27 @@ def ecboot(ec_file, out_file, n_boot, seed, sample, use_lengths, max_iters, tol,
         methods.ecboot(ec_file, out_file, n_boot, seed, sample, use_lengths, max_iters, tol, int(model), groups, replicates)
     except Exception:
         sys.exit(1)                                                  # (logged as "Error: ..." by bin_utils.ecboot)
+
+
+@cli.command('ecclusters', options_metavar='<options>', short_help='group the targets of an EC file by the reads they share')
+@click.argument('ec_file', metavar='ec_file', type=click.Path(exists=True, resolve_path=True, dir_okay=False))
+@click.argument('out_file', metavar='out_file', type=click.Path(resolve_path=True, dir_okay=False, writable=True))
+@click.option('-s', '--sample', metavar='sample', default=None, help="weigh the ECs by one sample of a multisample file (default: all of them pooled)")
+@click.option('-m', '--mincount', 'min_count', default=1, type=int, help='an EC of fewer reads than this ties nothing together (default: 1)')
+@click.option('--stats', 'stats', metavar='FILE', default=None, type=click.Path(resolve_path=True, dir_okay=False, writable=True),
+              help='write the targets, ECs and reads of every cluster to this file')
+@click.option('--multi-only', is_flag=True, help='leave the clusters of one target out of the file')
+@click.option('-v', '--verbose', count=True, help='enables verbose mode')
+def ecclusters(ec_file, out_file, sample, min_count, stats, multi_only, verbose):
+    """
+    Group the targets of a binary EC file (ec_file) by the reads they share -- the connected components of its target-EC incidence -- and
+    write them as a group file (out_file) that ecbundle and ecquant -M -g take
+    """
+    utils.configure_logging(verbose)
+    try:
+        methods.ecclusters(ec_file, out_file, sample, min_count, stats, multi_only)
+    except Exception:
+        sys.exit(1)                                                  # (logged as "Error: ..." by bin_utils.ecclusters)
 
 
 @cli.command('ecquant-cells', options_metavar='<options>', short_help='estimate abundances per sample (cell) of a multisample EC file by EM')

@@ -5066,6 +5066,8 @@ extern "C" int ecb_count_alignments(int device, uint32_t n_ecs, uint32_t n_loci,
 // ... and bootstrap replicates of N and the moments of their estimates (ecb_resample* / ecb_quantify_bootstrap*)
 #include "boot_draw.h"
 #include "boot.inc"
+// the connected components of the target-EC incidence, on count-alignments' checks and weights (ecb_components / ecb_components_device)
+#include "components.inc"
 
 // ---- ecselect: the reads of one class and the samples that still count enough of them, pulled out of a .bin (ecb_select / ecb_select_device)
 // (AlignmentPropertyMatrix.get_unique_reads / pull_alignments_from, AlignmentPropertyMatrix.py:386-427, and the cell threshold of

@@ -1,5 +1,5 @@
 # -*- coding: utf-8 -*-
-"""Same driver functions as the reference's ``alntools/methods.py:32-53, 205-210``, ``apply_genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``count_alignments``, ``ecquant``, ``ecboot``, ``ecquant_cells`` and ``ecdump`` for the hot path."""
+"""Same driver functions as the reference's ``alntools/methods.py:32-53, 205-210``, ``apply_genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``count_alignments``, ``ecquant``, ``ecboot``, ``ecclusters``, ``ecquant_cells`` and ``ecdump`` for the hot path."""
 from __future__ import annotations
 
 from . import bam_utils, bin_utils
@@ -75,6 +75,10 @@ def ecquant(ec_file, out_file, sample=None, use_lengths=False, max_iters=1000, t
 def ecboot(ec_file, out_file, n_boot=None, seed=0, sample=None, use_lengths=False, max_iters=1000, tol=1e-6, model=4, groups=None, replicates_file=None):
     bin_utils.ecboot(ec_file, out_file, n_boot=n_boot, seed=seed, sample=sample, use_lengths=use_lengths, max_iters=max_iters, tol=tol, model=model,
                      groups=groups, replicates_file=replicates_file)
+
+
+def ecclusters(ec_file, out_file, sample=None, min_count=1, stats_file=None, multi_only=False):
+    bin_utils.ecclusters(ec_file, out_file, sample=sample, min_count=min_count, stats_file=stats_file, multi_only=multi_only)
 
 
 def ecquant_cells(ec_file, out_file, samples=None, samples_file=None, use_lengths=False, max_iters=1000, tol=1e-6, report=None, model=4, groups=None):

@@ -407,5 +407,7 @@ const char* ecb_profile_kernel(const ecb_handle* h);
 #   include "ecb_select.h"
 /* ... and the ones that iterate the EM a .bin exists to feed (ecquant). */
 #    include "ecb_quant.h"
+/* ... and the ones that group a .bin's targets by the reads they share (ecclusters). */
+#     include "ecb_components.h"
 
 #endif /* ECB_H */
