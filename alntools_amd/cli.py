@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
 """Command line with the reference's hot-path sub-commands and options (``alntools/cli.py:43-113``):
-``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``, ``apply-genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``count-alignments``, ``ecquant`` (``-w``: the posterior of every alignment too), ``ecboot``, ``ecclusters``, ``ecquant-cells``, ``ecdump``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
+``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``, ``apply-genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``bus2ec``, ``count-alignments``, ``ecquant`` (``-w``: the posterior of every alignment too), ``ecboot``, ``ecclusters``, ``ecquant-cells``, ``ecdump``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
 from __future__ import annotations
 
 import glob
@@ -180,6 +180,31 @@ def salmon2ec(salmon_dir, ec_file, sample, targets, verbose):
         methods.salmon2ec(salmon_dir, ec_file, sample, targets)
     except Exception:
         sys.exit(1)                                                  # (logged as "Error: ..." by salmon_utils.convert)
+
+
+@cli.command('bus2ec', options_metavar='<options>', short_help='convert a kallisto BUS directory to a multisample EC file')
+@click.argument('bus_dir', metavar='bus_dir', type=click.Path(exists=True, resolve_path=True, file_okay=False, dir_okay=True))
+@click.argument('ec_file', metavar='ec_file', type=click.Path(resolve_path=True, dir_okay=False, writable=True))
+@click.option('--no-umi', is_flag=True, help='every record is `count` reads of its EC; UMIs are not collapsed and no intersection is taken')
+@click.option('-m', '--mincount', default=1000, type=int, help='drop the cells that count fewer molecules than this (default: 1000)')
+@click.option('--names', 'names_file', metavar='FILE', type=click.Path(exists=True, resolve_path=True, dir_okay=False),
+              help="lines of barcode<TAB>name: the cells to keep, in this order, and their sample names (default: all, named by their sequence)")
+@click.option('-l', '--lengths', 'lengths_file', metavar='FILE', type=click.Path(exists=True, resolve_path=True, dir_okay=False),
+              help="lines of name<TAB>length for every target name (default: every length is 0)")
+@click.option('-H', '--haplotype', metavar='NAME', default=None, help="every target name is a transcript as it stands, of this one haplotype")
+@click.option('-t', '--targets', metavar='FILE', type=click.Path(exists=True, resolve_path=True, file_okay=True, dir_okay=False), help="target file")
+@click.option('--stats', 'stats', metavar='FILE', default=None, type=click.Path(resolve_path=True, dir_okay=False, writable=True),
+              help='write the numbers of records, molecules, new ECs and cells to this file')
+@click.option('-v', '--verbose', count=True, help='enables verbose mode')
+def bus2ec(bus_dir, ec_file, no_umi, mincount, names_file, lengths_file, haplotype, targets, stats, verbose):
+    """
+    Convert the output of kallisto bus (bus_dir: output.bus, matrix.ec, transcripts.txt) to a multisample binary EC file (ec_file)
+    """
+    utils.configure_logging(verbose)
+    try:
+        methods.bus2ec(bus_dir, ec_file, no_umi, mincount, names_file, lengths_file, haplotype, targets, stats)
+    except Exception:
+        sys.exit(1)                                                  # (logged as "Error: ..." by bus_utils.convert)
 
 
 @cli.command('count-alignments', options_metavar='<options>', short_help='count the alignments of an EC file per target')

@@ -6378,6 +6378,10 @@ extern "C" int ecb_salmon_ecs(int device, const char* text, uint64_t n_bytes, ui
                          {out_n_data, &ond, out_sizes[1] * 4}});
 }
 
+// a multisample .bin's rows and cell counts from the records of a kallisto BUS file, on salmon2ec's per-row sort-and-fold kernels
+// (ecb_bus_molecules / ecb_bus_molecules_device)
+#include "bus.inc"
+
 // ---- ecb_merge: the multi-GPU merge for ONE process that drives several GPUs ----------------------------------------------
 // shards[r] holds the reads of contiguous read shard r on its own device; `root` is an empty handle (any device).  The same protocol as
 // alntools_amd/dist.py runs over RCCL with one process per GPU, here with peer copies (hipMemcpyPeerAsync: xGMI between the GPUs of a

@@ -1,5 +1,5 @@
 # -*- coding: utf-8 -*-
-"""Same driver functions as the reference's ``alntools/methods.py:32-53, 205-210``, ``apply_genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``count_alignments``, ``ecquant``, ``ecboot``, ``ecclusters``, ``ecquant_cells`` and ``ecdump`` for the hot path."""
+"""Same driver functions as the reference's ``alntools/methods.py:32-53, 205-210``, ``apply_genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``bus2ec``, ``count_alignments``, ``ecquant``, ``ecboot``, ``ecclusters``, ``ecquant_cells`` and ``ecdump`` for the hot path."""
 from __future__ import annotations
 
 from . import bam_utils, bin_utils
@@ -93,3 +93,9 @@ def ecdump(ec_file):
 def salmon2ec(salmon_dir, ec_filename, sample=None, target_filename=None):
     from . import salmon_utils
     salmon_utils.convert(salmon_dir, ec_filename, sample='NA' if sample is None else sample, target_filename=target_filename)
+
+
+def bus2ec(bus_dir, ec_filename, no_umi=False, mincount=1000, names_file=None, lengths_file=None, haplotype=None, target_filename=None, stats_file=None):
+    from . import bus_utils
+    bus_utils.convert(bus_dir, ec_filename, no_umi=no_umi, mincount=mincount, names_file=names_file, lengths_file=lengths_file, haplotype=haplotype,
+                      target_filename=target_filename, stats_file=stats_file)

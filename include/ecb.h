@@ -409,5 +409,7 @@ const char* ecb_profile_kernel(const ecb_handle* h);
 #    include "ecb_quant.h"
 /* ... and the ones that group a .bin's targets by the reads they share (ecclusters). */
 #     include "ecb_components.h"
+/* ... and the ones that make a multisample .bin's rows and cell counts from a kallisto BUS file (bus2ec). */
+#      include "ecb_bus.h"
 
 #endif /* ECB_H */
