@@ -7,6 +7,10 @@ lengths; the records -- the bulk of the bytes -- go to the GPU as they lie in th
 molecules, intersected where a molecule was seen in several ECs, and turned into rows and cell counts there.  The rows then go through
 ``ecb.combine`` as one part (equal keys become one EC) and ``ecb.select`` (the cell threshold ``-m``), and ``bin_utils.write_bin`` writes
 the result.  The layouts are the ones the bustools documentation gives; no file here was checked against a bustools binary.
+
+``-w/--whitelist FILE`` puts bustools ``correct``'s step in front: the records' barcodes are snapped onto the whitelist on the GPU
+(``ecb_bus_correct.correct``) before anything else sees them.  ``alntools buscorrect`` (:func:`correct_file`) writes the corrected records
+behind the input's header instead, for users who go on with other tools.
 """
 from __future__ import annotations
 
@@ -224,18 +228,90 @@ def read_lengths(path, names):
     return lengths
 
 
+def read_whitelist(path, bclen):
+    """``-w FILE``: one barcode per line, plain or gzipped (a name ending in ``.gz``) -> uint64, sorted ascending; parsed with numpy, no
+    Python loop per line (a kit's list has millions).  ``\\r\\n`` line ends and a missing final line end are taken.  ValueError with the
+    file and line for a barcode of another length than ``bclen`` (an empty line is one), a letter outside ACGT, a barcode listed twice
+    (naming the first line too), and for an empty file."""
+    if path.endswith(".gz"):
+        import gzip
+        with gzip.open(path, 'rb') as fh:
+            data = fh.read()
+    else:
+        with open(path, 'rb') as fh:
+            data = fh.read()
+    if not data:
+        raise ValueError("{}: no barcodes (the file is empty)".format(path))
+    if not data.endswith(b"\n"):
+        data += b"\n"
+    buf = np.frombuffer(data, dtype=np.uint8)
+    cr = np.flatnonzero((buf[:-1] == 13) & (buf[1:] == 10))
+    if len(cr):
+        buf = np.delete(buf, cr)
+    ends = np.flatnonzero(buf == 10)
+    starts = np.concatenate(([0], ends[:-1] + 1))
+
+    def text(line):
+        return bytes(buf[starts[line]:ends[line]]).decode('latin-1')
+    bad = np.flatnonzero(ends - starts != bclen)
+    if len(bad):
+        k = int(bad[0])
+        raise ValueError("{} line {}: barcode {!r} has {} bases; the BUS file's have {}".format(path, k + 1, text(k), int(ends[k] - starts[k]), bclen))
+    code = np.full(256, 255, dtype=np.uint8)
+    code[np.frombuffer(BASES.encode(), dtype=np.uint8)] = np.arange(4, dtype=np.uint8)
+    codes = code[buf.reshape(len(ends), bclen + 1)[:, :bclen]]
+    bad = np.flatnonzero((codes == 255).any(axis=1))
+    if len(bad):
+        raise ValueError("{} line {}: barcode {!r} has a letter outside ACGT".format(path, int(bad[0]) + 1, text(int(bad[0]))))
+    values = np.zeros(len(ends), dtype=np.uint64)
+    for k in range(bclen):                                       # (a pass per base, not per line)
+        values = (values << np.uint64(2)) | codes[:, k]
+    order = np.argsort(values, kind='stable')
+    out = values[order]
+    dup = np.flatnonzero(out[1:] == out[:-1])
+    if len(dup):
+        second = int(order[dup + 1].min())
+        first = int(np.flatnonzero(values == values[second])[0])
+        raise ValueError("{} line {}: barcode {!r} is listed twice (first on line {})".format(path, second + 1, text(second), first + 1))
+    return out
+
+
+def correct_records(records, bclen, whitelist_file, bus_path, device=0):
+    """The records with their barcodes snapped onto the whitelist of ``whitelist_file`` on the GPU (``ecb_bus_correct.correct``) -> (the
+    records kept, uint8 ``[n_out, 32]``, (exact, corrected, without a candidate, ambiguous)).  ValueError naming the file and the record
+    or line for what the library refuses, and when no record is left."""
+    from . import ecb, ecb_bus, ecb_bus_correct
+    whitelist = read_whitelist(whitelist_file, bclen)
+    LOG.info("Correcting the barcodes against the {:,} of {} on the GPU".format(len(whitelist), whitelist_file))
+    try:
+        out, _status, sizes = ecb_bus_correct.correct(records, bclen, whitelist, device=device)
+    except ecb_bus_correct.WhitelistFormatError as e:
+        raise ValueError("{}: {}".format(whitelist_file, str(e.args[0]).split("bus: ", 1)[-1]))
+    except ecb_bus.BusFormatError as e:
+        raise ValueError("{} record {}: {}".format(bus_path, e.index, re.split(r"record \d+: ", str(e.args[0]), maxsplit=1)[-1]))
+    except ecb.EcbError as e:
+        raise ValueError("{}: {}".format(bus_path, e.args[0]))
+    if not len(out):
+        raise ValueError("{}: no record has a barcode on or next to the whitelist".format(bus_path))
+    return out, sizes
+
+
 STATS = ("records", "molecules", "molecules_in_several_ecs", "molecules_discarded", "new_ecs", "cells", "cells_kept")
+WHITELIST_STATS = ("barcodes_exact", "barcodes_corrected", "barcodes_without_candidate", "barcodes_ambiguous")      # ecb_bus_correct's sizes, in order
 
 
 def stats_text(stats):
-    """``--stats FILE``: one ``name<TAB>value`` line for each of :data:`STATS`."""
-    return "".join("{}\t{}\n".format(k, int(stats[k])) for k in STATS)
+    """``--stats FILE``: one ``name<TAB>value`` line for each of :data:`STATS` and, after a whitelist correction (``-w``), for each of
+    :data:`WHITELIST_STATS`."""
+    keys = STATS + (WHITELIST_STATS if all(k in stats for k in WHITELIST_STATS) else ())
+    return "".join("{}\t{}\n".format(k, int(stats[k])) for k in keys)
 
 
 def bus_matrices(bus_dir, no_umi=False, mincount=1000, names_file=None, lengths_file=None, haplotype=None, target_filename=None, want_stats=False,
-                 device=0):
+                 device=0, whitelist_file=None):
     """Everything of :func:`convert` but the writing: -> (:class:`bin_utils.ECMatrices`, stats dict).  Raises ValueError (with the file and
-    the line or record) for every input it refuses."""
+    the line or record) for every input it refuses.  ``whitelist_file``: the records' barcodes are corrected against it first
+    (:func:`correct_records`); everything after sees the corrected records, the keep list of ``names_file`` included."""
     from . import ecb, ecb_bus
     bus_path, ec_path, tx_path = (os.path.join(bus_dir, f) for f in ("output.bus", "matrix.ec", "transcripts.txt"))
     hdr = read_header(bus_path)
@@ -260,6 +336,9 @@ def bus_matrices(bus_dir, no_umi=False, mincount=1000, names_file=None, lengths_
         keep = values[order]
     LOG.info("Reading {:,} records of {}".format(hdr.n_records, bus_path))
     records = read_records(bus_path, hdr)
+    corrected = None
+    if whitelist_file is not None:
+        records, corrected = correct_records(records, hdr.bclen, whitelist_file, bus_path, device=device)
     LOG.info("Collapsing the records into molecules and rows on the GPU")
     try:
         barcodes, A, N, row_line, sizes = ecb_bus.molecules(records, hdr.bclen, hdr.umilen, ec_ptr, ec_targets, col, hap, len(transcripts),
@@ -295,13 +374,15 @@ def bus_matrices(bus_dir, no_umi=False, mincount=1000, names_file=None, lengths_
     m = bin_utils.ECMatrices(haplotypes, transcripts, lengths, [s for s, k in zip(snames, kept) if k], *A_N)
     stats = dict(records=hdr.n_records, molecules=sizes[4], molecules_in_several_ecs=sizes[5], molecules_discarded=sizes[6], new_ecs=new_ecs,
                  cells=n_cells, cells_kept=m.num_samples)
+    if corrected is not None:
+        stats.update(zip(WHITELIST_STATS, corrected))
     if m.num_samples == 0:
         raise ValueError("no sample left")
     return m, stats
 
 
 def convert(bus_dir, ec_filename, no_umi=False, mincount=1000, names_file=None, lengths_file=None, haplotype=None, target_filename=None,
-            stats_file=None, device=0):
+            stats_file=None, device=0, whitelist_file=None):
     """``alntools bus2ec``: the multisample ``.bin`` of a ``kallisto bus`` output directory, written with ``bin_utils.write_bin``.  Any
     failure is logged as ``Error: ...``, no file is left behind, and the exception is raised again (the command line exits with status 1)."""
     LOG.debug('-------------------------------------------')
@@ -314,12 +395,13 @@ def convert(bus_dir, ec_filename, no_umi=False, mincount=1000, names_file=None, 
     LOG.debug('  Lengths file: {}'.format(lengths_file))
     LOG.debug('  Haplotype: {}'.format(haplotype))
     LOG.debug('  Target file: {}'.format(target_filename))
+    LOG.debug('  Whitelist: {}'.format(whitelist_file))
     LOG.debug('-------------------------------------------')
     written = []
     with bin_utils.command(bin_utils.RAISE, written=written):
         time0 = time.time()
         m, stats = bus_matrices(bus_dir, no_umi=no_umi, mincount=mincount, names_file=names_file, lengths_file=lengths_file, haplotype=haplotype,
-                                target_filename=target_filename, want_stats=stats_file is not None, device=device)
+                                target_filename=target_filename, want_stats=stats_file is not None, device=device, whitelist_file=whitelist_file)
         LOG.info("{} parsed in {}".format(bus_dir, utils.format_time(time0, time.time())))
         time1 = time.time()
         bin_utils.log_saving("Converting and storing to {}".format(ec_filename), m,
@@ -331,3 +413,29 @@ def convert(bus_dir, ec_filename, no_umi=False, mincount=1000, names_file=None, 
                 fh.write(stats_text(stats))
         bin_utils.write_bin(ec_filename, m)
         LOG.info("{} created in {}".format(ec_filename, utils.format_time(time1, time.time())))
+
+
+def correct_file(bus_file, out_file, whitelist_file, stats_file=None, device=0):
+    """``alntools buscorrect``: what ``bustools correct`` writes -- the header bytes of ``bus_file`` as they are, text included, then the
+    records whose barcode is on the whitelist or one base from exactly one of its barcodes, that barcode in place, in the file's order.
+    ``stats_file``: the number of records and :data:`WHITELIST_STATS`.  Failures as in :func:`convert`."""
+    written = []
+    with bin_utils.command(bin_utils.RAISE, written=written):
+        time0 = time.time()
+        if os.path.exists(out_file) and os.path.samefile(bus_file, out_file):
+            raise ValueError("{}: the output is the input".format(out_file))
+        hdr = read_header(bus_file)
+        with open(bus_file, 'rb') as fh:
+            head = fh.read(hdr.offset)
+        LOG.info("Reading {:,} records of {}".format(hdr.n_records, bus_file))
+        out, sizes = correct_records(read_records(bus_file, hdr), hdr.bclen, whitelist_file, bus_file, device=device)
+        LOG.info("Storing {:,} of {:,} records to {}".format(len(out), hdr.n_records, out_file))
+        if stats_file is not None:
+            with open(stats_file, 'w') as fh:
+                written.append(stats_file)
+                fh.write("records\t{}\n".format(hdr.n_records) + "".join("{}\t{}\n".format(k, int(v)) for k, v in zip(WHITELIST_STATS, sizes)))
+        with open(out_file, 'wb') as fh:
+            written.append(out_file)
+            fh.write(head)
+            np.ascontiguousarray(out).tofile(fh)
+        LOG.info("{} created in {}".format(out_file, utils.format_time(time0, time.time())))

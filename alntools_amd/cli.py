@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
 """Command line with the reference's hot-path sub-commands and options (``alntools/cli.py:43-113``):
-``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``, ``apply-genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``bus2ec``, ``count-alignments``, ``ecquant`` (``-w``: the posterior of every alignment too), ``ecboot``, ``ecclusters``, ``ecquant-cells``, ``ecdump``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
+``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``, ``apply-genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``bus2ec`` (``-w``: the barcodes corrected against a whitelist first), ``buscorrect``, ``count-alignments``, ``ecquant`` (``-w``: the posterior of every alignment too), ``ecboot``, ``ecclusters``, ``ecquant-cells``, ``ecdump``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
 from __future__ import annotations
 
 import glob
@@ -194,17 +194,41 @@ def salmon2ec(salmon_dir, ec_file, sample, targets, verbose):
 @click.option('-H', '--haplotype', metavar='NAME', default=None, help="every target name is a transcript as it stands, of this one haplotype")
 @click.option('-t', '--targets', metavar='FILE', type=click.Path(exists=True, resolve_path=True, file_okay=True, dir_okay=False), help="target file")
 @click.option('--stats', 'stats', metavar='FILE', default=None, type=click.Path(resolve_path=True, dir_okay=False, writable=True),
-              help='write the numbers of records, molecules, new ECs and cells to this file')
+              help='write the numbers of records, molecules, new ECs and cells (with -w: and of barcodes by outcome) to this file')
+@click.option('-w', '--whitelist', 'whitelist', metavar='FILE', default=None, type=click.Path(exists=True, resolve_path=True, dir_okay=False),
+              help="barcode whitelist, one per line, plain or .gz: a barcode one base from exactly one of its barcodes becomes that one, "
+                   "every other barcode off the list is dropped, before anything else is done (default: the barcodes are taken as they are)")
 @click.option('-v', '--verbose', count=True, help='enables verbose mode')
-def bus2ec(bus_dir, ec_file, no_umi, mincount, names_file, lengths_file, haplotype, targets, stats, verbose):
+def bus2ec(bus_dir, ec_file, no_umi, mincount, names_file, lengths_file, haplotype, targets, stats, whitelist, verbose):
     """
     Convert the output of kallisto bus (bus_dir: output.bus, matrix.ec, transcripts.txt) to a multisample binary EC file (ec_file)
     """
     utils.configure_logging(verbose)
     try:
-        methods.bus2ec(bus_dir, ec_file, no_umi, mincount, names_file, lengths_file, haplotype, targets, stats)
+        named = {} if whitelist is None else {"whitelist_file": whitelist}
+        methods.bus2ec(bus_dir, ec_file, no_umi, mincount, names_file, lengths_file, haplotype, targets, stats, **named)
     except Exception:
         sys.exit(1)                                                  # (logged as "Error: ..." by bus_utils.convert)
+
+
+@cli.command('buscorrect', options_metavar='<options>', short_help='correct the barcodes of a BUS file against a whitelist')
+@click.argument('bus_file', metavar='bus_file', type=click.Path(exists=True, resolve_path=True, dir_okay=False))
+@click.argument('out_file', metavar='out_file', type=click.Path(resolve_path=True, dir_okay=False, writable=True))
+@click.option('-w', '--whitelist', 'whitelist', metavar='FILE', required=True, type=click.Path(exists=True, resolve_path=True, dir_okay=False),
+              help="barcode whitelist, one per line, plain or .gz")
+@click.option('--stats', 'stats', metavar='FILE', default=None, type=click.Path(resolve_path=True, dir_okay=False, writable=True),
+              help='write the numbers of records and of barcodes by outcome to this file')
+@click.option('-v', '--verbose', count=True, help='enables verbose mode')
+def buscorrect(bus_file, out_file, whitelist, stats, verbose):
+    """
+    Write the records of a BUS file (bus_file) whose barcode is on the whitelist, or one base from exactly one of its barcodes and then
+    replaced by it, behind the input's header to a BUS file (out_file), as bustools correct does
+    """
+    utils.configure_logging(verbose)
+    try:
+        methods.buscorrect(bus_file, out_file, whitelist, stats)
+    except Exception:
+        sys.exit(1)                                                  # (logged as "Error: ..." by bus_utils.correct_file)
 
 
 @cli.command('count-alignments', options_metavar='<options>', short_help='count the alignments of an EC file per target')

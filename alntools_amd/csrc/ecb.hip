@@ -6381,6 +6381,8 @@ extern "C" int ecb_salmon_ecs(int device, const char* text, uint64_t n_bytes, ui
 // a multisample .bin's rows and cell counts from the records of a kallisto BUS file, on salmon2ec's per-row sort-and-fold kernels
 // (ecb_bus_molecules / ecb_bus_molecules_device)
 #include "bus.inc"
+// ... and those records' barcodes snapped onto a whitelist first (ecb_bus_correct / ecb_bus_correct_device)
+#include "bus_correct.inc"
 
 // ---- ecb_merge: the multi-GPU merge for ONE process that drives several GPUs ----------------------------------------------
 // shards[r] holds the reads of contiguous read shard r on its own device; `root` is an empty handle (any device).  The same protocol as

@@ -1,5 +1,5 @@
 # -*- coding: utf-8 -*-
-"""Same driver functions as the reference's ``alntools/methods.py:32-53, 205-210``, ``apply_genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``bus2ec``, ``count_alignments``, ``ecquant``, ``ecboot``, ``ecclusters``, ``ecquant_cells`` and ``ecdump`` for the hot path."""
+"""Same driver functions as the reference's ``alntools/methods.py:32-53, 205-210``, ``apply_genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``bus2ec``, ``buscorrect``, ``count_alignments``, ``ecquant``, ``ecboot``, ``ecclusters``, ``ecquant_cells`` and ``ecdump`` for the hot path."""
 from __future__ import annotations
 
 from . import bam_utils, bin_utils
@@ -95,7 +95,13 @@ def salmon2ec(salmon_dir, ec_filename, sample=None, target_filename=None):
     salmon_utils.convert(salmon_dir, ec_filename, sample='NA' if sample is None else sample, target_filename=target_filename)
 
 
-def bus2ec(bus_dir, ec_filename, no_umi=False, mincount=1000, names_file=None, lengths_file=None, haplotype=None, target_filename=None, stats_file=None):
+def bus2ec(bus_dir, ec_filename, no_umi=False, mincount=1000, names_file=None, lengths_file=None, haplotype=None, target_filename=None, stats_file=None,
+           whitelist_file=None):
     from . import bus_utils
     bus_utils.convert(bus_dir, ec_filename, no_umi=no_umi, mincount=mincount, names_file=names_file, lengths_file=lengths_file, haplotype=haplotype,
-                      target_filename=target_filename, stats_file=stats_file)
+                      target_filename=target_filename, stats_file=stats_file, whitelist_file=whitelist_file)
+
+
+def buscorrect(bus_file, out_file, whitelist_file, stats_file=None):
+    from . import bus_utils
+    bus_utils.correct_file(bus_file, out_file, whitelist_file, stats_file=stats_file)

@@ -411,5 +411,7 @@ const char* ecb_profile_kernel(const ecb_handle* h);
 #     include "ecb_components.h"
 /* ... and the ones that make a multisample .bin's rows and cell counts from a kallisto BUS file (bus2ec). */
 #      include "ecb_bus.h"
+/* ... and the ones that snap those records' barcodes onto a whitelist first (bus2ec -w, buscorrect). */
+#       include "ecb_bus_correct.h"
 
 #endif /* ECB_H */
