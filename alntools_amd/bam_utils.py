@@ -9,6 +9,7 @@ Not reproduced: the chunk-file plumbing that only exists to feed one pysam reade
 """
 from __future__ import annotations
 
+import itertools
 import os
 import subprocess
 import time
@@ -86,6 +87,93 @@ def iter_tuple_batches(reader, enc):
         if not len(q):
             return
         yield enc.encode(q, flag, tid, pos, ntid, npos)
+
+
+class BestStrataError(ValueError):
+    """``--best-strata`` cannot run, or a passing record lacks the tag: the command line prints it as ``Error: ...`` and exits 1."""
+
+
+def strata_passes(hapflag):
+    """The filter on the tuple's ``hapflag`` word (``rec_valid`` of ``csrc/ecb.hip``: :func:`tuples.record_valid` with the two host bits)."""
+    hf = np.asarray(hapflag).astype(np.int64)
+    bad = ((hf & 0x80) != 0) | ((hf & 0x2) == 0) | ((hf & (0x1000 | 0x2000)) != 0)
+    return ((hf & 0x4) == 0) & ~(((hf & 0x1) != 0) & bad)
+
+
+class BestStrata(object):
+    """``--best-strata TAG`` on the file path: the score of every record comes from the decoder (``set_score`` / ``scores``), the rule
+    runs on the GPU (:func:`alntools_amd.ecb_strata.best_strata`, the host entry point) in front of the push.  The call needs whole
+    reads, so a batch is cut at its last read boundary (:func:`alntools_amd.ecb_strata.cut_whole_reads`) and the open read is carried
+    into the next one."""
+
+    def __init__(self, tag, device=0):
+        from . import ecb_strata
+        self._es = ecb_strata
+        try:
+            self.tag_a, self.tag_b, self.lowest = ecb_strata.parse_tag(tag)
+        except ValueError as e:
+            raise BestStrataError(str(e))
+        if int(os.environ.get("ALNTOOLS_GPUS", "1") or 1) > 1:
+            raise BestStrataError("--best-strata does not run with ALNTOOLS_GPUS above 1")
+        self.tag, self.device = tag, device
+        self.filename, self.seen, self.held = None, 0, None
+        self.counts = [0, 0, 0, 0]               # passing, kept, dropped, reads whose first passing record was dropped
+
+    def attach(self, reader, filename):
+        """A file begins: its reader is told which tags make the score."""
+        if not hasattr(reader, "set_score"):
+            raise BestStrataError("--best-strata: the pysam reader does not hand out the tags; build libbamdec.so or run with ALNTOOLS_DECODER=py where pysam is not installed")
+        reader.set_score(self.tag_a, self.tag_b)
+        self.filename, self.seen, self.held = filename, 0, None
+
+    def scores(self, reader, hapflag):
+        """The scores of the batch the reader has just handed out; a passing record without the tag ends the run."""
+        score, present = reader.scores()
+        if len(score) != len(hapflag):
+            raise BestStrataError("{}: the decoder handed out {} scores for {} records".format(self.filename, len(score), len(hapflag)))
+        missing = np.flatnonzero(strata_passes(hapflag) & (present == 0))
+        if len(missing):
+            raise BestStrataError("{} record {}: no {} tag".format(self.filename, self.seen + int(missing[0]), self.tag_a))
+        self.seen += len(score)
+        return score
+
+    def apply(self, read_id, hapflag, score):
+        """Whole reads -> ``(read_id, hapflag)`` with the records outside the best stratum rejected."""
+        if not len(read_id):
+            return read_id, hapflag
+        rid, hf, counts = self._es.best_strata(read_id, hapflag, score, lowest=self.lowest, device=self.device)
+        self.counts = [a + b for a, b in zip(self.counts, counts)]
+        return rid, hf
+
+    def scored(self, reader, batches):
+        """``iter_tuple_batches``' batches, each with its ``score`` column: host work only -- the first of them can be looked at, and
+        a file without the tag refused, before a device is opened."""
+        for t in batches:
+            t["score"] = self.scores(reader, t["hapflag"])
+            yield t
+
+    def feed(self, t, final=False):
+        """A scored batch of tuples -> the tuples of its whole reads (with what was carried in front), or None."""
+        cols = [t[k] for k in ("read_id", "locus", "hapflag", "pos", "score")]
+        if self.held is not None:
+            cols = [np.concatenate([h, c]) for h, c in zip(self.held, cols)]
+        k = self._es.cut_whole_reads(cols[0], final)
+        self.held = [c[k:] for c in cols] if k < len(cols[0]) else None
+        if not k:
+            return None
+        rid, hf = self.apply(cols[0][:k], cols[2][:k], cols[4][:k])
+        return dict(read_id=rid, locus=cols[1][:k], hapflag=hf, pos=cols[3][:k])
+
+    def finish(self):
+        """The end of the file: the read still open is whole now."""
+        if self.held is None:
+            return None
+        cols, self.held = self.held, None
+        rid, hf = self.apply(cols[0], cols[2], cols[4])
+        return dict(read_id=rid, locus=cols[1], hapflag=hf, pos=cols[3])
+
+    def log(self):
+        LOG.info("Alignments outside the best stratum: {:,}".format(self.counts[2]))
 
 
 def write_range_file(range_filename, maps, range_len):
@@ -319,9 +407,11 @@ def _rank_convert(rank, job, bam_filename, ec_filename, emase_filename, range_fi
 
 
 def convert(bam_filename, ec_filename, emase_filename, num_chunks=0, number_processes=-1, temp_dir=None,
-            range_filename=None, sample=None, target_filename=None):
-    """BAM -> EC ``.bin`` and/or EMASE ``.h5`` (same arguments and outputs as ``bam_utils.convert``)."""
+            range_filename=None, sample=None, target_filename=None, best_strata=None):
+    """BAM -> EC ``.bin`` and/or EMASE ``.h5`` (same arguments and outputs as ``bam_utils.convert``).  ``best_strata``: a tag of
+    :data:`alntools_amd.ecb_strata.TAGS` -- of every read's alignments only the best-scoring ones count (:class:`BestStrata`)."""
     start_time = time.time()
+    strata = BestStrata(best_strata, int(os.environ.get("ALNTOOLS_GPU", "0"))) if best_strata is not None else None
     if sample is None:
         sample = os.path.basename(bam_filename)                      # bam_utils.py:552-554
         LOG.info("Sample not supplied, using filename: {}".format(sample))
@@ -338,10 +428,23 @@ def convert(bam_filename, ec_filename, emase_filename, num_chunks=0, number_proc
     maps = header_maps(reader, target_filename, strict=True)
     device = int(os.environ.get("ALNTOOLS_GPU", "0"))
     temp_time = time.time()
+    enc = TupleEncoder(maps)
+    batches = iter_tuple_batches(reader, enc)
+    if strata is not None:
+        strata.attach(reader, bam_filename)
+        batches = strata.scored(reader, batches)
+        head = next(batches, None)               # (decoded, and its tags looked at, before the device is opened)
+        batches = itertools.chain([head] if head is not None else [], batches)
     with EcBuilder(maps.n_loci, maps.n_haplotypes, device=device, track_ranges=range_filename is not None,
                    verify=bool(int(os.environ.get("ALNTOOLS_VERIFY", "0")))) as b:
-        enc = TupleEncoder(maps)
-        for t in iter_tuple_batches(reader, enc):
+        for t in batches:
+            if strata is not None:
+                t = strata.feed(t)
+                if t is None:
+                    continue
+            b.push(t["read_id"], t["locus"], t["hapflag"], t["pos"] if range_filename else None)
+        t = strata.finish() if strata is not None else None
+        if t is not None:
             b.push(t["read_id"], t["locus"], t["hapflag"], t["pos"] if range_filename else None)
         reader.close()
         sizes = b.finalize()
@@ -349,6 +452,8 @@ def convert(bam_filename, ec_filename, emase_filename, num_chunks=0, number_proc
         LOG.info("All results combined in {}, total time: {}".format(utils.format_time(temp_time, time.time()),
                                                                      utils.format_time(start_time, time.time())))
         _log_summary(maps, sizes)
+        if strata is not None:
+            strata.log()
         range_len = b.export_ranges() if range_filename else None
     _write_outputs(maps, sample, sizes, out, range_len, ec_filename, emase_filename, range_filename, device=device)
     LOG.info("Done, total time: {}".format(utils.format_time(start_time, time.time())))

@@ -31,12 +31,13 @@ LOG = utils.get_logger()
 CELL_BITS = 22
 
 
-def scan_file(reader, maps):
+def scan_file(reader, maps, scored=False):
     """One BAM file -> (tuples of its counted reads, cell name per counted read, counters, dropped-run records).
 
-    Restates the name logic of ``bam_utils_multisample.py:257-300`` on the valid records of the file.
+    Restates the name logic of ``bam_utils_multisample.py:257-300`` on the valid records of the file.  ``scored``: the reader works
+    out every record's score (``set_score``); the columns then hold ``score`` and ``present`` too.
     """
-    cols = {k: [] for k in ("flag", "tid", "pos", "ntid", "npos", "run")}
+    cols = {k: [] for k in ("flag", "tid", "pos", "ntid", "npos", "run") + (("score", "present") if scored else ())}
     run_cells = []
     tracked, run = None, -1
     n_all = n_valid = 0
@@ -52,6 +53,9 @@ def scan_file(reader, maps):
         n_valid += int(d["valid"].sum())
         for k, v in (("flag", d["flag"]), ("tid", d["tid"]), ("pos", d["pos"]), ("ntid", d["next_tid"]), ("npos", d["next_pos"]), ("run", runs)):
             cols[k].append(np.array(v))
+        if scored:
+            for k, v in zip(("score", "present"), reader.scores()):
+                cols[k].append(v)
     while True:
         q, flag, tid, pos, ntid, npos = reader.read_batch(BATCH_RECORDS)
         if not q:
@@ -80,6 +84,9 @@ def scan_file(reader, maps):
         n_valid += int(valid.sum())
         for k, v in (("flag", flag), ("tid", tid), ("pos", pos), ("ntid", ntid), ("npos", npos), ("run", runs)):
             cols[k].append(v)
+        if scored:
+            for k, v in zip(("score", "present"), reader.scores()):
+                cols[k].append(v)
     c = {k: (np.concatenate(v) if v else np.zeros(0, dtype=np.int64)) for k, v in cols.items()}
     keep = c["run"] < run                                             # the file's last read is never counted (:306-321)
     return c, keep, run_cells[:max(run, 0)], dict(all=n_all, valid=n_valid)
@@ -99,24 +106,32 @@ def _tuples(c, sel, maps, read_base):
             c["pos"][sel].astype(np.int32), valid)
 
 
-def _push_files(b, maps, files, track, cell_of):
+def _push_files(b, maps, files, track, cell_of, strata=None):
     """Scan ``files`` = [(global file index, path), ...] in order and push their counted reads into ``b`` (read ids local to this
     handle, from 0).  ``cell_of(name) -> id`` hands out cell ids.  -> (n_all, n_valid, reads pushed, host-side range extremes of
-    the reads the reference never counts -- the last read of every file, ``:306-321`` -- which its ranges still see, ``:249-253``)."""
+    the reads the reference never counts -- the last read of every file, ``:306-321`` -- which its ranges still see, ``:249-253``).
+    ``strata`` (a :class:`bam_utils.BestStrata`): the rule runs over every file's records, which are held whole, before they are split
+    into counted reads and the last one -- that read, which only the ranges see, by the same rule; ``n_valid`` then counts what is kept."""
     n_all = n_valid = 0
     host_min = np.full((maps.n_loci, maps.n_haplotypes), np.iinfo(np.int32).max, dtype=np.int64)
     host_max = np.full((maps.n_loci, maps.n_haplotypes), np.iinfo(np.int32).min, dtype=np.int64)
     read_base = 0
     for fi, path in files:
         rd = open_bam(path, names=False, ms=True)
-        c, keep, cells, ctr = scan_file(rd, maps)
+        if strata is not None:
+            strata.attach(rd, path)
+        c, keep, cells, ctr = scan_file(rd, maps, scored=strata is not None)
         rd.close()
         n_all += ctr["all"]
-        n_valid += ctr["valid"]
-        rid, loc, hf, pos, _ = _tuples(c, keep, maps, read_base)
-        if len(rid):
-            b.push(rid, loc, hf, pos if track else None)
-        if track and (~keep).any():                               # ranges see every valid alignment, counted or not (:249-253)
+        if strata is not None:
+            _push_file_strata(b, maps, c, keep, track, read_base, strata, host_min, host_max)
+            n_valid = strata.counts[1]
+        else:
+            n_valid += ctr["valid"]
+            rid, loc, hf, pos, _ = _tuples(c, keep, maps, read_base)
+            if len(rid):
+                b.push(rid, loc, hf, pos if track else None)
+        if strata is None and track and (~keep).any():            # ranges see every valid alignment, counted or not (:249-253)
             _, l2, h2, p2, v2 = _tuples(c, ~keep, maps, 0)
             hap = (h2.astype(np.int64) >> HAP_SHIFT) & 0xFF
             np.minimum.at(host_min, (l2[v2].astype(np.int64), hap[v2]), p2[v2])
@@ -126,6 +141,27 @@ def _push_files(b, maps, files, track, cell_of):
             b.push_cells(ids | np.uint32(fi << CELL_BITS), read_base)
         read_base += len(cells)
     return n_all, n_valid, read_base, host_min, host_max
+
+
+def _push_file_strata(b, maps, c, keep, track, read_base, strata, host_min, host_max):
+    """One file's records with ``--best-strata``: the rule over all of them (the file is whole reads), then the counted reads pushed
+    and the last read's kept alignments shown to the host-side ranges."""
+    from .bam_utils import BestStrataError, strata_passes
+    every = np.ones(len(keep), dtype=bool)
+    rid, loc, hf, pos, valid = _tuples(c, every, maps, read_base)
+    if not len(rid):
+        return
+    missing = np.flatnonzero(valid & (c["present"] == 0))
+    if len(missing):
+        raise BestStrataError("{} record {}: no {} tag".format(strata.filename, int(missing[0]), strata.tag_a))
+    rid, hf = strata.apply(rid, hf, c["score"].astype(np.int32))
+    if keep.any():
+        b.push(rid[keep], loc[keep], hf[keep], pos[keep] if track else None)
+    if track and (~keep).any():
+        v2 = ~keep & strata_passes(hf)
+        hap = (hf.astype(np.int64) >> HAP_SHIFT) & 0xFF
+        np.minimum.at(host_min, (loc[v2].astype(np.int64), hap[v2]), pos[v2])
+        np.maximum.at(host_max, (loc[v2].astype(np.int64), hap[v2]), pos[v2])
 
 
 def _finish(maps, names, sizes, f, range_len, ec_filename, emase_filename, range_filename, device, n_all, n_valid, start_time):
@@ -172,7 +208,7 @@ def _header_maps(bam_files, target_filename):
     return maps
 
 
-def convert_files(bam_files, ec_filename, emase_filename, minimum_count=-1, range_filename=None, target_filename=None):
+def convert_files(bam_files, ec_filename, emase_filename, minimum_count=-1, range_filename=None, target_filename=None, best_strata=None):
     """``bam_files`` in the given order -> ``.bin`` / ``.h5``; returns counters.  ``ALNTOOLS_GPUS=N``: the files are dealt out to
     N processes, one per GPU (the reference: one worker per file, ``bam_utils_multisample.py:473-480``)."""
     start_time = time.time()
@@ -180,6 +216,10 @@ def convert_files(bam_files, ec_filename, emase_filename, minimum_count=-1, rang
         raise ValueError("no bam files")
     if len(bam_files) > (1 << (32 - CELL_BITS)):
         raise ValueError("more than %d input files" % (1 << (32 - CELL_BITS)))
+    strata = None
+    if best_strata is not None:                                       # (refused here -- an unknown tag, ALNTOOLS_GPUS above 1 -- before anything starts)
+        from .bam_utils import BestStrata
+        strata = BestStrata(best_strata, int(os.environ.get("ALNTOOLS_GPU", "0")))
     n_gpus = int(os.environ.get("ALNTOOLS_GPUS", "1"))
     if n_gpus > 1:
         from .dist import spawn_ranks
@@ -197,10 +237,12 @@ def convert_files(bam_files, ec_filename, emase_filename, minimum_count=-1, rang
     device = int(os.environ.get("ALNTOOLS_GPU", "0"))
     track = range_filename is not None
     with EcBuilder(maps.n_loci, maps.n_haplotypes, device=device, track_ranges=track, multisample=True) as b:
-        n_all, n_valid, _, host_min, host_max = _push_files(b, maps, list(enumerate(bam_files)), track, cell_of)
+        n_all, n_valid, _, host_min, host_max = _push_files(b, maps, list(enumerate(bam_files)), track, cell_of, strata)
         sizes = b.finalize()
         names = list(cell_ids.keys())
         _log_counts(maps, n_valid, sizes, len(names))
+        if strata is not None:
+            strata.log()
         f = _filter(b, len(names), minimum_count)
         range_len = None
         if track:
@@ -289,7 +331,7 @@ def _rank_convert(rank, job, bam_files, ec_filename, emase_filename, minimum_cou
 
 
 def convert(bam_filename, ec_filename, emase_filename, num_chunks=0, minimum_count=-1, number_processes=-1,
-            temp_dir=None, range_filename=None, target_filename=None):
+            temp_dir=None, range_filename=None, target_filename=None, best_strata=None):
     """Same arguments as the reference (``bam_utils_multisample.py:357``); ``bam_filename`` is a directory."""
     if os.path.isfile(bam_filename):
         LOG.error('bam file must be a directory')
@@ -298,4 +340,4 @@ def convert(bam_filename, ec_filename, emase_filename, num_chunks=0, minimum_cou
     if len(bam_files) == 0:
         LOG.error('No bam files found in directory: {}'.format(bam_filename))
         return None
-    return convert_files(bam_files, ec_filename, emase_filename, minimum_count, range_filename, target_filename)
+    return convert_files(bam_files, ec_filename, emase_filename, minimum_count, range_filename, target_filename, best_strata=best_strata)

@@ -19,7 +19,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libbamdec.so")
 SRC = os.path.join(_HERE, "csrc", "bamdec.c")
 SYMBOLS = ("bd_abi_version", "bd_open", "bd_close", "bd_last_error", "bd_n_references", "bd_reference_name",
-           "bd_reference_length", "bd_header_text", "bd_references", "bd_read", "bd_read_tuples", "bd_read_ms", "bd_ms_cells", "bd_progress")
+           "bd_reference_length", "bd_header_text", "bd_references", "bd_read", "bd_read_tuples", "bd_read_ms", "bd_ms_cells", "bd_progress",
+           "bd_set_score", "bd_scores")
 ABI_VERSION = 4            # include/bamdec.h: bd_abi_version()
 _lib = None
 
@@ -76,6 +77,8 @@ def lib():
         l.bd_read_ms.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 7 + [C.POINTER(C.c_size_t)]
         l.bd_ms_cells.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_size_t)]
         l.bd_progress.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        l.bd_set_score.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
+        l.bd_scores.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
         _lib = l
     return _lib
 
@@ -173,6 +176,22 @@ class NativeBamReader(object):
             cells = [raw[off[i]:off[i + 1]].decode("utf-8") for i in range(nc.value)]
         return dict(flag=self._flag[:k], tid=self._i32[0][:k], pos=self._i32[1][:k], next_tid=self._i32[2][:k],
                     next_pos=self._i32[3][:k], valid=self._u8[0][:k], newrun=self._u8[1][:k]), cells
+
+    def set_score(self, tag_a, tag_b=None):
+        """``bd_set_score``: from here on every read call also works out each record's score -- the integer aux tag ``tag_a``, plus
+        ``tag_b`` where a record has it -- and :meth:`scores` returns them.  ``tag_a`` None switches it off."""
+        enc = lambda t: None if t is None else t.encode("ascii")
+        if self._l.bd_set_score(self._h, enc(tag_a), enc(tag_b)) != 0:
+            raise ValueError("bamdec: %s" % self._l.bd_last_error(self._h).decode())
+
+    def scores(self):
+        """-> ``(score int32, present uint8)`` of the records the last ``read_decoded`` / ``read_tuples`` / ``read_ms`` handed out
+        (``bd_scores``; copies)."""
+        sp, pp, n = C.POINTER(C.c_int32)(), C.POINTER(C.c_uint8)(), C.c_size_t(0)
+        self._l.bd_scores(self._h, C.byref(sp), C.byref(pp), C.byref(n))
+        if not n.value:
+            return np.zeros(0, np.int32), np.zeros(0, np.uint8)
+        return np.ctypeslib.as_array(sp, shape=(n.value,)).copy(), np.ctypeslib.as_array(pp, shape=(n.value,)).copy()
 
     def progress(self):
         """Fraction of the file the records handed out so far reach (compressed bytes; what is read ahead but not parsed yet is not

@@ -119,24 +119,109 @@ def _reg2bin(beg, end):
     return 0
 
 
-def pack_record(qname, flag, ref_id, pos, next_ref_id=-1, next_pos=-1, mapq=255, tlen=0):
-    """One BAM alignment record with an empty CIGAR/SEQ/QUAL (allowed by the spec)."""
+_AUX_FMT = {"c": "<b", "C": "<B", "s": "<h", "S": "<H", "i": "<i", "I": "<I", "f": "<f"}    # the aux types of a fixed size, but 'A'
+_AUX_INT = "cCsSiI"
+
+
+def pack_tags(tags):
+    """The aux fields of a record: ``tags`` = ``(tag, type, value)`` triples, ``type`` one of ``A c C s S i I f Z H B``; the value of a
+    ``B`` is ``(subtype, values)``."""
+    out = bytearray()
+    for tag, typ, value in tags:
+        if len(tag) != 2:
+            raise ValueError("an aux tag is two characters: %r" % (tag,))
+        out += tag.encode("ascii") + typ.encode("ascii")
+        if typ == "A":
+            out += value.encode("ascii")[:1]
+        elif typ in _AUX_FMT:
+            out += struct.pack(_AUX_FMT[typ], value)
+        elif typ in "ZH":
+            out += value.encode("ascii") + b"\x00"
+        elif typ == "B":
+            sub, values = value
+            out += sub.encode("ascii") + struct.pack("<i", len(values)) + b"".join(struct.pack(_AUX_FMT[sub], v) for v in values)
+        else:
+            raise ValueError("unknown aux type %r" % (typ,))
+    return bytes(out)
+
+
+def pack_record(qname, flag, ref_id, pos, next_ref_id=-1, next_pos=-1, mapq=255, tlen=0, tags=None):
+    """One BAM alignment record with an empty CIGAR/SEQ/QUAL (allowed by the spec); ``tags``: its aux fields (:func:`pack_tags`)."""
     name = qname.encode("utf-8") + b"\x00"
     if len(name) > 255:
         raise ValueError("read name too long for BAM")
     body = struct.pack("<iiBBHHHiiii", ref_id, pos, len(name), mapq,
                        _reg2bin(max(pos, 0), max(pos, 0) + 1), 0, flag & 0xFFFF, 0,
                        next_ref_id, next_pos, tlen) + name
+    if tags:
+        body += pack_tags(tags)
     return struct.pack("<i", len(body)) + body
 
 
-def write_bam(path, references, records, header_text=None, level=6):
+def record_score(rec, tag_a, tag_b=None):
+    """``(score, present)`` of the record ``rec`` -- its bytes behind ``block_size`` -- as ``bd_set_score`` / ``bd_scores`` of
+    ``include/bamdec.h`` define them: the aux fields walked behind the name, the CIGAR, the sequence and the qualities, every step
+    bounded by the record; ``tag_a``'s integer value, plus ``tag_b``'s where the record has one, clamped to int32; ``present``: the
+    record has ``tag_a``.  A field that runs past the record, an unknown type or a score tag that is no integer: ``ValueError``."""
+    bs = len(rec)
+    l_name, n_cigar = rec[8], rec[12] | (rec[13] << 8)
+    (l_seq,) = struct.unpack_from("<i", rec, 16)
+    if l_seq < 0:
+        raise ValueError("BAM record: negative sequence length")
+    off = 32 + l_name + 4 * n_cigar + (l_seq + 1) // 2 + l_seq
+    if off > bs:
+        raise ValueError("BAM record: CIGAR, sequence or qualities run past the record")
+    past = ValueError("BAM record: an aux field runs past the record")
+    ta, tb = tag_a.encode("ascii"), (tag_b.encode("ascii") if tag_b else None)
+    a = b = 0
+    has_a = False
+    while off < bs:
+        if off + 3 > bs:
+            raise past
+        tag, typ = rec[off:off + 2], chr(rec[off + 2])
+        off += 3
+        if typ == "A" or typ in _AUX_FMT:
+            size = 1 if typ == "A" else struct.calcsize(_AUX_FMT[typ])
+            if off + size > bs:
+                raise past
+        elif typ in "ZH":
+            z = rec.find(b"\x00", off)
+            if z < 0:
+                raise past
+            size = z - off + 1
+        elif typ == "B":
+            if off + 5 > bs:
+                raise past
+            sub = chr(rec[off])
+            (count,) = struct.unpack_from("<i", rec, off + 1)
+            if sub not in _AUX_FMT or count < 0:
+                raise ValueError("BAM record: an aux array of an unknown type or a negative length")
+            size = 5 + struct.calcsize(_AUX_FMT[sub]) * count
+            if off + size > bs:
+                raise past
+        else:
+            raise ValueError("BAM record: an aux field of an unknown type")
+        if tag == ta or (tb is not None and tag == tb):
+            if typ not in _AUX_INT:
+                raise ValueError("BAM record: the score tag is not an integer")
+            (v,) = struct.unpack_from(_AUX_FMT[typ], rec, off)
+            if tag == ta:
+                a, has_a = v, True
+            else:
+                b = v
+        off += size
+    return max(-(1 << 31), min((1 << 31) - 1, a + b)), has_a
+
+
+def write_bam(path, references, records, header_text=None, level=6, tags=None):
     """Write a BAM file.
 
     ``references``: sequence of ``(name, length)``; ``records``: iterable of
     ``(qname, flag, ref_id, pos, next_ref_id, next_pos)``.  The header ends on a
     BGZF block boundary, as samtools writes it (the reference's single-chunk path
-    relies on that, ``bam_utils.py:87-99,172,184``).
+    relies on that, ``bam_utils.py:87-99,172,184``).  ``tags``: the aux fields of
+    every record, one list of ``(tag, type, value)`` per record (:func:`pack_tags`);
+    without it the records carry none.
     """
     if header_text is None:
         header_text = "@HD\tVN:1.0\tSO:unsorted\n" + "".join(
@@ -150,8 +235,12 @@ def write_bam(path, references, records, header_text=None, level=6):
         hdr += struct.pack("<i", len(nb)) + nb + struct.pack("<i", l)
     w.write(bytes(hdr))
     w.flush_block()
-    for r in records:
-        w.write(pack_record(*r))
+    if tags is None:
+        for r in records:
+            w.write(pack_record(*r))
+    else:
+        for r, t in zip(records, tags):
+            w.write(pack_record(*r, tags=t))
     w.close()
 
 
@@ -172,7 +261,19 @@ class BamReader(object):
         self._blocks = iter_bgzf_blocks(self._fh)
         self._buf = b""
         self._pos = 0
+        self._score_tags = None          # set_score: (tag_a, tag_b or None)
+        self._scores = []                # (score, present) of the records handed out since read_batch last began
         self._read_header()
+
+    def set_score(self, tag_a, tag_b=None):
+        """As ``bd_set_score``: from here on every record's score is worked out (:func:`record_score`), and :meth:`scores` returns
+        those of the records the last :meth:`read_batch` handed out.  ``tag_a`` None switches it off."""
+        self._score_tags = None if tag_a is None else (tag_a, tag_b)
+        self._scores = []
+
+    def scores(self):
+        """-> ``(score int32, present uint8)`` of the records of the last :meth:`read_batch`."""
+        return (np.array([s for s, _ in self._scores], dtype=np.int32), np.array([p for _, p in self._scores], dtype=np.uint8))
 
     # -- byte supply ---------------------------------------------------------
     def _need(self, n):
@@ -221,6 +322,8 @@ class BamReader(object):
         (_, ref_id, pos, l_name, _mq, _bin, _nc, flag, _ls, nref, npos,
          _tl) = _REC_FIXED.unpack_from(self._buf, p)
         qname = self._buf[p + 36:p + 36 + l_name - 1].decode("utf-8")
+        if self._score_tags is not None:
+            self._scores.append(record_score(self._buf[p + 4:p + 4 + bs], *self._score_tags))
         self._pos = p + 4 + bs
         return qname, flag, ref_id, pos, nref, npos
 
@@ -232,6 +335,7 @@ class BamReader(object):
         """Up to ``max_records`` records as column arrays
         ``(qnames list, flag u16, ref_id i32, pos i32, next_ref_id i32, next_pos i32)``."""
         q, cols = [], []
+        self._scores = []
         for _ in range(max_records):
             try:
                 r = self.__next__()

@@ -30,10 +30,41 @@ def _common(f):
                              help='number of processes (accepted for compatibility: the work runs on the GPU)'),
                 click.option('--multisample', is_flag=True, help='BAM_FILE is a directory of per-sample BAM files'),
                 click.option('-m', '--mincount', default=None, type=int, help='minimum reads per cell (multisample)'),
+                click.option('--best-strata', 'best_strata', default=None, metavar='TAG',
+                             help="keep only a read's best-scoring alignments: NM, XM, nM (lowest), AS, AS+YS (highest)"),
                 click.option('-d', '--directory', default=None, type=click.Path(file_okay=False), help='accepted for compatibility; ignored'),
                 click.option('-c', '--chunks', default=0, help='accepted for compatibility; ignored')):
         f = opt(f)
     return f
+
+
+def _strata_option(tag):
+    """``--best-strata TAG`` as the keyword the drivers take (nothing without the option: the call is then today's); an unknown TAG and
+    ``ALNTOOLS_GPUS`` above 1 are refused here, by name, before a file is opened or a process started."""
+    if tag is None:
+        return {}
+    from .ecb_strata import TAGS
+    if tag not in TAGS:
+        click.echo("Error: --best-strata {}: the tag is one of {}".format(tag, ", ".join(TAGS)), err=True)
+        sys.exit(1)
+    if int(os.environ.get("ALNTOOLS_GPUS", "1") or 1) > 1:
+        click.echo("Error: --best-strata does not run with ALNTOOLS_GPUS above 1", err=True)
+        sys.exit(1)
+    return {"best_strata": tag}
+
+
+class _strata_errors(object):
+    """What ``--best-strata`` refuses while it runs (a passing record without the tag): ``Error: ...``, exit status 1, no output file."""
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, kind, e, tb):
+        from .bam_utils import BestStrataError
+        if kind is not None and issubclass(kind, BestStrataError):
+            click.echo("Error: {}".format(e), err=True)
+            sys.exit(1)
+        return False
 
 
 @cli.command('bam2ec', short_help='convert a BAM file to EC')
@@ -41,31 +72,36 @@ def _common(f):
 @click.argument('ec_file', metavar='ec_file', type=click.Path(resolve_path=True, dir_okay=False))
 @click.option('-s', '--sample', default=None, help='sample identifier')
 @_common
-def bam2ec(bam_file, ec_file, chunks, directory, mincount, multisample, processes, rangefile, targets, verbose, sample):
+def bam2ec(bam_file, ec_file, chunks, directory, best_strata, mincount, multisample, processes, rangefile, targets, verbose, sample):
     """Convert a BAM file (bam_file) to a binary file (ec_file)."""
     utils.configure_logging(verbose)
+    named = _strata_option(best_strata)
     if multisample:
         if sample:                                                   # cli.py:60-63
             print('-s, --sample should NOT be specified with --multisample')
             return
-        methods.bam2ec_multisample(bam_file, ec_file, chunks, 1000 if mincount is None else mincount, directory,
-                                   processes, rangefile, targets)
+        with _strata_errors():
+            methods.bam2ec_multisample(bam_file, ec_file, chunks, 1000 if mincount is None else mincount, directory,
+                                       processes, rangefile, targets, **named)
     else:
-        methods.bam2ec(bam_file, ec_file, chunks, directory, processes, rangefile, sample, targets)
+        with _strata_errors():
+            methods.bam2ec(bam_file, ec_file, chunks, directory, processes, rangefile, sample, targets, **named)
 
 
 @cli.command('bam2emase', short_help='convert a BAM file to EMASE')
 @click.argument('bam_file', metavar='bam_file', type=click.Path(exists=True, resolve_path=True))
 @click.argument('emase_file', metavar='emase_file', type=click.Path(resolve_path=True, dir_okay=False))
 @_common
-def bam2emase(bam_file, emase_file, chunks, directory, mincount, multisample, processes, rangefile, targets, verbose):
+def bam2emase(bam_file, emase_file, chunks, directory, best_strata, mincount, multisample, processes, rangefile, targets, verbose):
     """Convert a BAM file (bam_file) to an EMASE file (emase_file)."""
     utils.configure_logging(verbose)
-    if multisample:
-        methods.bam2emase_multisample(bam_file, emase_file, chunks, 2000 if mincount is None else mincount, directory,
-                                      processes, rangefile, targets)
-    else:
-        methods.bam2emase(bam_file, emase_file, chunks, directory, processes, rangefile, targets)
+    named = _strata_option(best_strata)
+    with _strata_errors():
+        if multisample:
+            methods.bam2emase_multisample(bam_file, emase_file, chunks, 2000 if mincount is None else mincount, directory,
+                                          processes, rangefile, targets, **named)
+        else:
+            methods.bam2emase(bam_file, emase_file, chunks, directory, processes, rangefile, targets, **named)
 
 
 @cli.command('ec2emase', short_help='convert an EC file to EMASE')

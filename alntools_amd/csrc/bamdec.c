@@ -46,6 +46,9 @@ typedef struct bd_handle {
     uint8_t* last; size_t last_cap; int32_t last_len; int has_last;
     /* multisample (bd_read_ms): the cell ids of the runs the last call started, back to back, and where each begins */
     uint8_t* cells; size_t cells_cap, cells_len; uint32_t* cell_off; size_t cell_off_cap, n_cells;
+    /* bd_set_score: the tag(s) whose value is a record's score, and the scores of the records the last read call handed out */
+    int score_on, score_two; uint8_t tag_a[2], tag_b[2];
+    int32_t* scores; uint8_t* score_present; size_t score_cap, n_scores;
     char err[256];
 } bd_handle;
 
@@ -184,7 +187,7 @@ void bd_close(bd_handle* h) {
     if (h->f) fclose(h->f);
     free(h->raw); free(h->buf); free(h->text); free(h->last); free(h->cells); free(h->cell_off);
     if (h->names) { for (int32_t i = 0; i < h->n_ref; ++i) free(h->names[i]); free(h->names); }
-    free(h->lens); free(h->ref_blob); free(h->scratch);
+    free(h->lens); free(h->ref_blob); free(h->scratch); free(h->scores); free(h->score_present);
     free(h);
 }
 
@@ -248,12 +251,110 @@ int bd_references(bd_handle* h, const char** blob, size_t* blob_len, const int32
     return BD_OK;
 }
 
+/* ---- the score of a record (bd_set_score / bd_scores) ------------------------------------------------------------------ */
+/* bytes of one value of an aux type with a fixed size (A c C s S i I f), 0 for any other */
+static uint32_t aux_size(uint8_t t) {
+    switch (t) {
+    case 'A': case 'c': case 'C': return 1;
+    case 's': case 'S': return 2;
+    case 'i': case 'I': case 'f': return 4;
+    default: return 0;
+    }
+}
+/* the integer at v of one of the six integer types; 0 and *ok = 0 for any other type */
+static int64_t aux_int(uint8_t t, const uint8_t* v, int* ok) {
+    *ok = 1;
+    switch (t) {
+    case 'c': return (int8_t)v[0];
+    case 'C': return v[0];
+    case 's': { int16_t x; memcpy(&x, v, 2); return x; }
+    case 'S': { uint16_t x; memcpy(&x, v, 2); return x; }
+    case 'i': { int32_t x; memcpy(&x, v, 4); return x; }
+    case 'I': { uint32_t x; memcpy(&x, v, 4); return x; }
+    default: *ok = 0; return 0;
+    }
+}
+/* Walks the aux fields of the record at p (bs bytes: its block_size), behind the name, the CIGAR, the sequence and the qualities,
+ * every step bounded by bs, and appends the record's score: tag_a's value, plus tag_b's where the record has one, clamped to int32;
+ * present = the record has tag_a.  BD_ERR_FORMAT: a field that runs past the record, a type that is none of A c C s S i I f Z H B,
+ * a score tag that is no integer. */
+static int score_record(bd_handle* h, const uint8_t* p, uint32_t bs) {
+    const uint64_t l_name = p[8], n_cigar = (uint64_t)p[12] | ((uint64_t)p[13] << 8);
+    const int32_t l_seq = rd_i32(p + 16);
+    if (l_seq < 0) return fail(h, BD_ERR_FORMAT, "BAM record: negative sequence length");
+    uint64_t off = 32 + l_name + 4 * n_cigar + ((uint64_t)l_seq + 1) / 2 + (uint64_t)l_seq;
+    if (off > bs) return fail(h, BD_ERR_FORMAT, "BAM record: CIGAR, sequence or qualities run past the record");
+    int64_t a = 0, b = 0;
+    int has_a = 0;
+    while (off < bs) {
+        if (off + 3 > bs) return fail(h, BD_ERR_FORMAT, "BAM record: an aux field runs past the record");
+        const uint8_t* tag = p + off;
+        const uint8_t type = p[off + 2];
+        off += 3;
+        uint64_t size = aux_size(type);
+        if (size) {
+            if (off + size > bs) return fail(h, BD_ERR_FORMAT, "BAM record: an aux field runs past the record");
+        } else if (type == 'Z' || type == 'H') {
+            const uint8_t* z = (const uint8_t*)memchr(p + off, 0, (size_t)(bs - off));
+            if (!z) return fail(h, BD_ERR_FORMAT, "BAM record: an aux field runs past the record");
+            size = (uint64_t)(z - (p + off)) + 1;
+        } else if (type == 'B') {
+            if (off + 5 > bs) return fail(h, BD_ERR_FORMAT, "BAM record: an aux field runs past the record");
+            const uint32_t each = p[off] == 'A' ? 0 : aux_size(p[off]);
+            const int32_t count = rd_i32(p + off + 1);
+            if (!each || count < 0) return fail(h, BD_ERR_FORMAT, "BAM record: an aux array of an unknown type or a negative length");
+            size = 5 + (uint64_t)each * (uint64_t)count;
+            if (off + size > bs) return fail(h, BD_ERR_FORMAT, "BAM record: an aux field runs past the record");
+        } else return fail(h, BD_ERR_FORMAT, "BAM record: an aux field of an unknown type");
+        const int is_a = tag[0] == h->tag_a[0] && tag[1] == h->tag_a[1];
+        const int is_b = h->score_two && tag[0] == h->tag_b[0] && tag[1] == h->tag_b[1];
+        if (is_a || is_b) {
+            int ok = 0;
+            const int64_t v = aux_int(type, p + off, &ok);
+            if (!ok) return fail(h, BD_ERR_FORMAT, "BAM record: the score tag is not an integer");
+            if (is_a) { a = v; has_a = 1; } else b = v;
+        }
+        off += size;
+    }
+    if (h->n_scores == h->score_cap) {
+        const size_t nc = h->score_cap * 2 + 4096;
+        int32_t* ns = (int32_t*)realloc(h->scores, nc * sizeof(int32_t));
+        if (ns) h->scores = ns;
+        uint8_t* np = (uint8_t*)realloc(h->score_present, nc);
+        if (np) h->score_present = np;
+        if (!ns || !np) return fail(h, BD_ERR_MEM, "out of memory");
+        h->score_cap = nc;
+    }
+    int64_t sum = a + b;
+    if (sum > INT32_MAX) sum = INT32_MAX;
+    if (sum < INT32_MIN) sum = INT32_MIN;
+    h->scores[h->n_scores] = (int32_t)sum; h->score_present[h->n_scores] = (uint8_t)has_a;
+    ++h->n_scores;
+    return BD_OK;
+}
+
+int bd_set_score(bd_handle* h, const char* tag_a, const char* tag_b) {
+    if (!h) return BD_ERR_ARG;
+    if (!tag_a) { if (tag_b) return fail(h, BD_ERR_ARG, "a second score tag without a first"); h->score_on = 0; h->n_scores = 0; return BD_OK; }
+    if (strlen(tag_a) != 2 || (tag_b && strlen(tag_b) != 2)) return fail(h, BD_ERR_ARG, "a tag is two characters");
+    memcpy(h->tag_a, tag_a, 2);
+    h->score_two = tag_b != NULL;
+    if (tag_b) memcpy(h->tag_b, tag_b, 2);
+    h->score_on = 1; h->n_scores = 0;
+    return BD_OK;
+}
+
+int bd_scores(const bd_handle* h, const int32_t** score, const uint8_t** present, size_t* n) {
+    if (!h || !score || !present || !n) return BD_ERR_ARG;
+    *score = h->scores; *present = h->score_present; *n = h->score_on ? h->n_scores : 0;
+    return BD_OK;
+}
+
 /* Up to max_records records.  Arrays of max_records elements each; *n_out = records written (0 = end of file).
  * valid[i] = the record passes bam_utils.py:264-270; head[i] = it is valid and its (trimmed, if trim != 0) name differs from
  * the previous valid record's -- across calls too. */
-int bd_read(bd_handle* h, size_t max_records, int trim, uint16_t* flag, int32_t* tid, int32_t* pos, int32_t* next_tid, int32_t* next_pos,
-            uint8_t* valid, uint8_t* head, size_t* n_out) {
-    if (!h || !flag || !tid || !pos || !next_tid || !next_pos || !valid || !head || !n_out) return BD_ERR_ARG;
+static int read_records(bd_handle* h, size_t max_records, int trim, uint16_t* flag, int32_t* tid, int32_t* pos, int32_t* next_tid, int32_t* next_pos,
+                        uint8_t* valid, uint8_t* head, size_t* n_out) {
     size_t n = 0;
     while (n < max_records) {
         /* fast path: the whole record is in the buffer (all but one record per 32 MB refill) */
@@ -297,11 +398,19 @@ int bd_read(bd_handle* h, size_t max_records, int trim, uint16_t* flag, int32_t*
             }
         }
         valid[n] = (uint8_t)ok; head[n] = hd;
+        if (h->score_on) { const int rc = score_record(h, p, (uint32_t)bs); if (rc != BD_OK) return rc; }
         h->pos += 4 + (size_t)bs;
         ++n;
     }
     *n_out = n;
     return BD_OK;
+}
+
+int bd_read(bd_handle* h, size_t max_records, int trim, uint16_t* flag, int32_t* tid, int32_t* pos, int32_t* next_tid, int32_t* next_pos,
+            uint8_t* valid, uint8_t* head, size_t* n_out) {
+    if (!h || !flag || !tid || !pos || !next_tid || !next_pos || !valid || !head || !n_out) return BD_ERR_ARG;
+    h->n_scores = 0;
+    return read_records(h, max_records, trim, flag, tid, pos, next_tid, next_pos, valid, head, n_out);
 }
 
 /* The record tuples of include/ecb.h straight from the file (what tuples.TupleEncoder.encode_decoded makes of bd_read's arrays):
@@ -326,10 +435,11 @@ int bd_read_tuples(bd_handle* h, size_t max_records, int trim, const uint32_t* t
     uint8_t* head = valid + TUPLE_CHUNK;
     size_t n = 0, nv = 0;
     uint32_t c = *cur;
+    h->n_scores = 0;
     while (n < max_records) {
         const size_t want = max_records - n < TUPLE_CHUNK ? max_records - n : TUPLE_CHUNK;
         size_t got = 0;
-        const int rc = bd_read(h, want, trim, flag, tid, pos + n, ntid, npos, valid, head, &got);
+        const int rc = read_records(h, want, trim, flag, tid, pos + n, ntid, npos, valid, head, &got);
         if (rc != BD_OK) return rc;
         if (got == 0) break;
         for (size_t i = 0; i < got; ++i) {
@@ -377,7 +487,7 @@ int bd_read_ms(bd_handle* h, size_t max_records, uint16_t* flag, int32_t* tid, i
                uint8_t* valid, uint8_t* newrun, size_t* n_out) {
     if (!h || !flag || !tid || !pos || !next_tid || !next_pos || !valid || !newrun || !n_out) return BD_ERR_ARG;
     size_t n = 0;
-    h->cells_len = 0; h->n_cells = 0;
+    h->cells_len = 0; h->n_cells = 0; h->n_scores = 0;
     while (n < max_records) {
         int rc = need(h, 4);
         if (rc == 1) { if (h->len != h->pos) return fail(h, BD_ERR_FORMAT, "truncated BAM"); break; }
@@ -434,6 +544,7 @@ int bd_read_ms(bd_handle* h, size_t max_records, uint16_t* flag, int32_t* tid, i
             }
         }
         valid[n] = (uint8_t)ok; newrun[n] = nr;
+        if (h->score_on) { rc = score_record(h, p, (uint32_t)bs); if (rc != BD_OK) return rc; }
         h->pos += 4 + (size_t)bs;
         ++n;
     }

@@ -6,16 +6,16 @@ from . import bam_utils, bin_utils
 
 
 def bam2ec(bam_filename, ec_filename, chunks=0, directory=None, number_processes=-1, range_filename=None,
-           sample=None, target_filename=None):
+           sample=None, target_filename=None, best_strata=None):
     return bam_utils.convert(bam_filename, ec_filename, None, num_chunks=chunks, number_processes=number_processes,
                              temp_dir=directory, range_filename=range_filename, sample=sample,
-                             target_filename=target_filename)
+                             target_filename=target_filename, best_strata=best_strata)
 
 
 def bam2emase(bam_filename, emase_filename, chunks=0, directory=None, number_processes=-1, range_filename=None,
-              target_filename=None):
+              target_filename=None, best_strata=None):
     return bam_utils.convert(bam_filename, None, emase_filename, num_chunks=chunks, number_processes=number_processes,
-                             temp_dir=directory, range_filename=range_filename, target_filename=target_filename)
+                             temp_dir=directory, range_filename=range_filename, target_filename=target_filename, best_strata=best_strata)
 
 
 def bam2both(bam_filename, ec_filename, emase_filename, chunks=0, directory=None, number_processes=-1,
@@ -26,17 +26,17 @@ def bam2both(bam_filename, ec_filename, emase_filename, chunks=0, directory=None
 
 
 def bam2ec_multisample(bam_filename, ec_filename, chunks=0, minimum_count=-1, directory=None, number_processes=-1,
-                       range_filename=None, target_filename=None):
+                       range_filename=None, target_filename=None, best_strata=None):
     from . import bam_utils_multisample
     return bam_utils_multisample.convert(bam_filename, ec_filename, None, chunks, minimum_count, number_processes,
-                                         directory, range_filename, target_filename)
+                                         directory, range_filename, target_filename, best_strata=best_strata)
 
 
 def bam2emase_multisample(bam_filename, emase_filename, chunks=0, minimum_count=-1, directory=None,
-                          number_processes=-1, range_filename=None, target_filename=None):
+                          number_processes=-1, range_filename=None, target_filename=None, best_strata=None):
     from . import bam_utils_multisample
     return bam_utils_multisample.convert(bam_filename, None, emase_filename, chunks, minimum_count, number_processes,
-                                         directory, range_filename, target_filename)
+                                         directory, range_filename, target_filename, best_strata=best_strata)
 
 
 def ec2emase(ec_file, emase_file):

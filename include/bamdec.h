@@ -56,6 +56,16 @@ int bd_read_tuples(bd_handle* h, size_t max_records, int trim, const uint32_t* t
 int bd_read_ms(bd_handle* h, size_t max_records, uint16_t* flag, int32_t* tid, int32_t* pos, int32_t* next_tid, int32_t* next_pos,
                uint8_t* valid, uint8_t* newrun, size_t* n_out);
 int bd_ms_cells(const bd_handle* h, const uint8_t** bytes, const uint32_t** off, size_t* n);
+/* The score of a record (ABI 4, additive; --best-strata): bd_set_score names the integer aux tag whose value it is -- tag_a, two
+ * characters, and optionally tag_b, whose value is added where a record has it (bowtie2's pair score: AS plus YS); tag_a NULL switches
+ * it off again, which is how a handle starts.  While it is on, every bd_read / bd_read_tuples / bd_read_ms call also walks each record's
+ * aux fields -- behind the name, the CIGAR, the sequence and the qualities; every type known (A c C s S i I f Z H B), the six integer
+ * types accepted for a score, the sum clamped to int32; every step bounded by the record's block_size -- and bd_scores returns the
+ * scores of the records the LAST such call handed out: score[i], and present[i] = 1 if record i has tag_a (its score is 0 otherwise);
+ * n of them, owned by the handle, valid until the next call.  An aux field that runs past the record, an unknown type or a score tag
+ * that is no integer is BD_ERR_FORMAT from the read call. */
+int bd_set_score(bd_handle* h, const char* tag_a, const char* tag_b);
+int bd_scores(const bd_handle* h, const int32_t** score, const uint8_t** present, size_t* n);
 /* How far the records handed out so far reach into the file (compressed bytes; what has been read ahead and inflated but not
  * parsed yet is not counted) and the file's size -- a monotone measure of progress, for a reader that deals a file's records out
  * to several consumers in order (ABI 4; ABI 3 counted the read-ahead). */

@@ -413,5 +413,7 @@ const char* ecb_profile_kernel(const ecb_handle* h);
 #      include "ecb_bus.h"
 /* ... and the ones that snap those records' barcodes onto a whitelist first (bus2ec -w, buscorrect). */
 #       include "ecb_bus_correct.h"
+/* ... and the ones that keep, of every read's alignments, the best-scoring ones before ecb_push* sees them (--best-strata). */
+#        include "ecb_strata.h"
 
 #endif /* ECB_H */
