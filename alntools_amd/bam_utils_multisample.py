@@ -31,12 +31,32 @@ LOG = utils.get_logger()
 CELL_BITS = 22
 
 
-def scan_file(reader, maps, scored=False):
+class CollapseUmisError(ValueError):
+    """What ``--collapse-umis`` refuses: a combination it does not run with, a run beyond the record limit."""
+
+
+def umi_refusal(multisample=True, range_filename=None):
+    """Why ``--collapse-umis`` does not run as asked, in words that name the option -- or None."""
+    if not multisample:
+        return "--collapse-umis needs --multisample: the cell and the UMI are fields of the multisample read names"
+    if range_filename:
+        return "--collapse-umis does not run with --rangefile: the ranges are defined over alignments that the collapse removes"
+    if int(os.environ.get("ALNTOOLS_GPUS", "1") or 1) > 1:
+        return "--collapse-umis does not run with ALNTOOLS_GPUS above 1"
+    return None
+
+
+def scan_file(reader, maps, scored=False, umis=False):
     """One BAM file -> (tuples of its counted reads, cell name per counted read, counters, dropped-run records).
 
     Restates the name logic of ``bam_utils_multisample.py:257-300`` on the valid records of the file.  ``scored``: the reader works
-    out every record's score (``set_score``); the columns then hold ``score`` and ``present`` too.
+    out every record's score (``set_score``); the columns then hold ``score`` and ``present`` too.  ``umis``: a fifth value follows,
+    the raw UMI of every counted read next to its cell -- field 6 of the same tracked name, as it stands (``--collapse-umis``).
     """
+    run_umis = []
+    done = (lambda *r: r + (run_umis[:max(run, 0)],)) if umis else (lambda *r: r)
+    if umis and hasattr(reader, "read_ms"):
+        reader.set_umi(True)
     cols = {k: [] for k in ("flag", "tid", "pos", "ntid", "npos", "run") + (("score", "present") if scored else ())}
     run_cells = []
     tracked, run = None, -1
@@ -45,10 +65,12 @@ def scan_file(reader, maps, scored=False):
         d, cells = reader.read_ms(BATCH_RECORDS)
         if d is None:
             c = {k: (np.concatenate(v) if v else np.zeros(0, dtype=np.int64)) for k, v in cols.items()}
-            return c, c["run"] < run, run_cells[:max(run, 0)], dict(all=n_all, valid=n_valid)
+            return done(c, c["run"] < run, run_cells[:max(run, 0)], dict(all=n_all, valid=n_valid))
         runs = run + np.cumsum(d["newrun"], dtype=np.int64)
         run = int(runs[-1])
         run_cells.extend(cells)
+        if umis:
+            run_umis.extend(reader.ms_umis())
         n_all += len(runs)
         n_valid += int(d["valid"].sum())
         for k, v in (("flag", d["flag"]), ("tid", d["tid"]), ("pos", d["pos"]), ("ntid", d["next_tid"]), ("npos", d["next_pos"]), ("run", runs)):
@@ -79,6 +101,8 @@ def scan_file(reader, maps, scored=False):
                     if len(fields) < 15:
                         raise ValueError("read name %r has no cell id in '|||' field 14 (bam_utils_multisample.py:270-280)" % tracked)
                     run_cells.append(fields[14])
+                    if umis:
+                        run_umis.append(fields[6])
             runs[i] = run
         n_all += len(q)
         n_valid += int(valid.sum())
@@ -89,7 +113,7 @@ def scan_file(reader, maps, scored=False):
                 cols[k].append(v)
     c = {k: (np.concatenate(v) if v else np.zeros(0, dtype=np.int64)) for k, v in cols.items()}
     keep = c["run"] < run                                             # the file's last read is never counted (:306-321)
-    return c, keep, run_cells[:max(run, 0)], dict(all=n_all, valid=n_valid)
+    return done(c, keep, run_cells[:max(run, 0)], dict(all=n_all, valid=n_valid))
 
 
 def _tuples(c, sel, maps, read_base):
@@ -106,12 +130,51 @@ def _tuples(c, sel, maps, read_base):
             c["pos"][sel].astype(np.int32), valid)
 
 
-def _push_files(b, maps, files, track, cell_of, strata=None):
+class _Gather(object):
+    """The builder as :func:`_push_files` sees it under ``--collapse-umis``: what would be pushed is held -- the records, and every
+    counted read's cell, file and UMI -- until the whole run is in, since a molecule's reads may lie in different files.
+    :meth:`collapse_into` then makes the reads of one molecule one read on the GPU (``ecb_collapse_umis``) and pushes the result, the
+    cells taken from every molecule's first read."""
+
+    def __init__(self):
+        self.streams, self.meta, self.umis, self.n_records, self.counts = [], [], [], 0, None
+
+    def push(self, rid, loc, hf, pos=None):
+        from .ecb_umi import MAX_RECORDS
+        self.n_records += len(rid)
+        if self.n_records > MAX_RECORDS:
+            raise CollapseUmisError("--collapse-umis: more than {:,} records in the run (2^30 - 1: one call collapses them all)".format(MAX_RECORDS))
+        self.streams.append((rid, loc, hf))
+
+    def push_cells(self, meta, first_read, umis=()):
+        self.meta.append(meta)
+        self.umis.extend(umis)
+
+    def collapse_into(self, b, maps, device):
+        from . import ecb_umi
+        if not self.n_records:
+            return
+        rid, loc, hf = (np.concatenate([s[k] for s in self.streams]) for k in range(3))
+        meta = np.concatenate(self.meta) if self.meta else np.zeros(0, np.uint32)
+        keys = ecb_umi.mol_keys(meta & np.uint32((1 << CELL_BITS) - 1), self.umis)
+        rid, loc, hf, first, self.counts = ecb_umi.collapse_umis(rid, loc, hf, keys, maps.n_loci, maps.n_haplotypes, device=device)
+        if len(rid):
+            b.push(rid, loc, hf, None)
+            b.push_cells(meta[first], 0)
+
+    def log(self):
+        from .ecb_umi import COUNT_NAMES
+        if self.counts is not None:
+            LOG.info("--collapse-umis: " + ", ".join("{:,} {}".format(v, k) for k, v in zip(COUNT_NAMES, self.counts)))
+
+
+def _push_files(b, maps, files, track, cell_of, strata=None, umis=False):
     """Scan ``files`` = [(global file index, path), ...] in order and push their counted reads into ``b`` (read ids local to this
     handle, from 0).  ``cell_of(name) -> id`` hands out cell ids.  -> (n_all, n_valid, reads pushed, host-side range extremes of
     the reads the reference never counts -- the last read of every file, ``:306-321`` -- which its ranges still see, ``:249-253``).
     ``strata`` (a :class:`bam_utils.BestStrata`): the rule runs over every file's records, which are held whole, before they are split
-    into counted reads and the last one -- that read, which only the ranges see, by the same rule; ``n_valid`` then counts what is kept."""
+    into counted reads and the last one -- that read, which only the ranges see, by the same rule; ``n_valid`` then counts what is kept.
+    ``umis``: ``push_cells`` is handed every counted read's raw UMI as well (``b`` is then a :class:`_Gather`)."""
     n_all = n_valid = 0
     host_min = np.full((maps.n_loci, maps.n_haplotypes), np.iinfo(np.int32).max, dtype=np.int64)
     host_max = np.full((maps.n_loci, maps.n_haplotypes), np.iinfo(np.int32).min, dtype=np.int64)
@@ -120,7 +183,8 @@ def _push_files(b, maps, files, track, cell_of, strata=None):
         rd = open_bam(path, names=False, ms=True)
         if strata is not None:
             strata.attach(rd, path)
-        c, keep, cells, ctr = scan_file(rd, maps, scored=strata is not None)
+        scanned = scan_file(rd, maps, scored=strata is not None, umis=umis)
+        c, keep, cells, ctr = scanned[:4]
         rd.close()
         n_all += ctr["all"]
         if strata is not None:
@@ -138,7 +202,7 @@ def _push_files(b, maps, files, track, cell_of, strata=None):
             np.maximum.at(host_max, (l2[v2].astype(np.int64), hap[v2]), p2[v2])
         if cells:
             ids = np.asarray([cell_of(name) for name in cells], dtype=np.uint32)
-            b.push_cells(ids | np.uint32(fi << CELL_BITS), read_base)
+            b.push_cells(ids | np.uint32(fi << CELL_BITS), read_base, *scanned[4:])              # (with ``umis``: the reads' UMIs go with their cells)
         read_base += len(cells)
     return n_all, n_valid, read_base, host_min, host_max
 
@@ -208,10 +272,17 @@ def _header_maps(bam_files, target_filename):
     return maps
 
 
-def convert_files(bam_files, ec_filename, emase_filename, minimum_count=-1, range_filename=None, target_filename=None, best_strata=None):
+def convert_files(bam_files, ec_filename, emase_filename, minimum_count=-1, range_filename=None, target_filename=None, best_strata=None,
+                  collapse_umis=False):
     """``bam_files`` in the given order -> ``.bin`` / ``.h5``; returns counters.  ``ALNTOOLS_GPUS=N``: the files are dealt out to
-    N processes, one per GPU (the reference: one worker per file, ``bam_utils_multisample.py:473-480``)."""
+    N processes, one per GPU (the reference: one worker per file, ``bam_utils_multisample.py:473-480``).  ``collapse_umis``: the
+    counted reads of all files -- after the last read of every file has been set aside, and after ``best_strata`` -- are gathered in
+    file order and collapsed in one call (:class:`_Gather`); the minimum count then counts molecules."""
     start_time = time.time()
+    if collapse_umis:                                                 # (refused here, by name, before anything starts)
+        why = umi_refusal(True, range_filename)
+        if why:
+            raise CollapseUmisError(why)
     if not bam_files:
         raise ValueError("no bam files")
     if len(bam_files) > (1 << (32 - CELL_BITS)):
@@ -237,12 +308,17 @@ def convert_files(bam_files, ec_filename, emase_filename, minimum_count=-1, rang
     device = int(os.environ.get("ALNTOOLS_GPU", "0"))
     track = range_filename is not None
     with EcBuilder(maps.n_loci, maps.n_haplotypes, device=device, track_ranges=track, multisample=True) as b:
-        n_all, n_valid, _, host_min, host_max = _push_files(b, maps, list(enumerate(bam_files)), track, cell_of, strata)
+        gather = _Gather() if collapse_umis else None
+        n_all, n_valid, _, host_min, host_max = _push_files(b if gather is None else gather, maps, list(enumerate(bam_files)), track, cell_of, strata, umis=collapse_umis)
+        if gather is not None:
+            gather.collapse_into(b, maps, device)
         sizes = b.finalize()
         names = list(cell_ids.keys())
         _log_counts(maps, n_valid, sizes, len(names))
         if strata is not None:
             strata.log()
+        if gather is not None:
+            gather.log()
         f = _filter(b, len(names), minimum_count)
         range_len = None
         if track:
@@ -331,8 +407,10 @@ def _rank_convert(rank, job, bam_files, ec_filename, emase_filename, minimum_cou
 
 
 def convert(bam_filename, ec_filename, emase_filename, num_chunks=0, minimum_count=-1, number_processes=-1,
-            temp_dir=None, range_filename=None, target_filename=None, best_strata=None):
+            temp_dir=None, range_filename=None, target_filename=None, best_strata=None, collapse_umis=False):
     """Same arguments as the reference (``bam_utils_multisample.py:357``); ``bam_filename`` is a directory."""
+    if collapse_umis and umi_refusal(True, range_filename):
+        raise CollapseUmisError(umi_refusal(True, range_filename))
     if os.path.isfile(bam_filename):
         LOG.error('bam file must be a directory')
         return None
@@ -340,4 +418,5 @@ def convert(bam_filename, ec_filename, emase_filename, num_chunks=0, minimum_cou
     if len(bam_files) == 0:
         LOG.error('No bam files found in directory: {}'.format(bam_filename))
         return None
-    return convert_files(bam_files, ec_filename, emase_filename, minimum_count, range_filename, target_filename, best_strata=best_strata)
+    return convert_files(bam_files, ec_filename, emase_filename, minimum_count, range_filename, target_filename, best_strata=best_strata,
+                         collapse_umis=collapse_umis)

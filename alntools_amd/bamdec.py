@@ -20,7 +20,7 @@ LIB_PATH = os.path.join(_HERE, "libbamdec.so")
 SRC = os.path.join(_HERE, "csrc", "bamdec.c")
 SYMBOLS = ("bd_abi_version", "bd_open", "bd_close", "bd_last_error", "bd_n_references", "bd_reference_name",
            "bd_reference_length", "bd_header_text", "bd_references", "bd_read", "bd_read_tuples", "bd_read_ms", "bd_ms_cells", "bd_progress",
-           "bd_set_score", "bd_scores")
+           "bd_set_score", "bd_scores", "bd_set_umi", "bd_ms_umis")
 ABI_VERSION = 4            # include/bamdec.h: bd_abi_version()
 _lib = None
 
@@ -79,6 +79,8 @@ def lib():
         l.bd_progress.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         l.bd_set_score.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
         l.bd_scores.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
+        l.bd_set_umi.argtypes = [C.c_void_p, C.c_int]
+        l.bd_ms_umis.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_size_t)]
         _lib = l
     return _lib
 
@@ -167,15 +169,30 @@ class NativeBamReader(object):
         k = n.value
         if k == 0:
             return None, []
-        bytes_p, off_p, nc = C.POINTER(C.c_uint8)(), C.POINTER(C.c_uint32)(), C.c_size_t(0)
-        self._l.bd_ms_cells(self._h, C.byref(bytes_p), C.byref(off_p), C.byref(nc))
-        cells = []
-        if nc.value:
-            off = np.ctypeslib.as_array(off_p, shape=(nc.value + 1,))
-            raw = bytes(np.ctypeslib.as_array(bytes_p, shape=(int(off[-1]),))) if off[-1] else b""
-            cells = [raw[off[i]:off[i + 1]].decode("utf-8") for i in range(nc.value)]
+        cells = self._strings(self._l.bd_ms_cells)
         return dict(flag=self._flag[:k], tid=self._i32[0][:k], pos=self._i32[1][:k], next_tid=self._i32[2][:k],
                     next_pos=self._i32[3][:k], valid=self._u8[0][:k], newrun=self._u8[1][:k]), cells
+
+    def _strings(self, getter):
+        """The list of ``str`` one of the decoder's back-to-back string lists holds (``bd_ms_cells``, ``bd_ms_umis``)."""
+        bytes_p, off_p, nc = C.POINTER(C.c_uint8)(), C.POINTER(C.c_uint32)(), C.c_size_t(0)
+        getter(self._h, C.byref(bytes_p), C.byref(off_p), C.byref(nc))
+        if not nc.value:
+            return []
+        off = np.ctypeslib.as_array(off_p, shape=(nc.value + 1,))
+        raw = bytes(np.ctypeslib.as_array(bytes_p, shape=(int(off[-1]),))) if off[-1] else b""
+        return [raw[off[i]:off[i + 1]].decode("utf-8") for i in range(nc.value)]
+
+    def set_umi(self, on=True):
+        """``bd_set_umi``: from here on :meth:`read_ms` also keeps field 6 of every tracked name (the raw UMI), and :meth:`ms_umis`
+        returns them."""
+        if self._l.bd_set_umi(self._h, 1 if on else 0) != 0:
+            raise ValueError("bamdec: %s" % self._l.bd_last_error(self._h).decode())
+
+    def ms_umis(self):
+        """-> field 6 of the runs the last :meth:`read_ms` started, as a list of ``str`` next to its cells (``bd_ms_umis``; empty while
+        :meth:`set_umi` is off)."""
+        return self._strings(self._l.bd_ms_umis)
 
     def set_score(self, tag_a, tag_b=None):
         """``bd_set_score``: from here on every read call also works out each record's score -- the integer aux tag ``tag_a``, plus

@@ -32,10 +32,25 @@ def _common(f):
                 click.option('-m', '--mincount', default=None, type=int, help='minimum reads per cell (multisample)'),
                 click.option('--best-strata', 'best_strata', default=None, metavar='TAG',
                              help="keep only a read's best-scoring alignments: NM, XM, nM (lowest), AS, AS+YS (highest)"),
+                click.option('--collapse-umis', 'collapse_umis', is_flag=True,
+                             help="count molecules, not reads: reads of one cell with one UMI ('|||' field 6 of the read name) become one (multisample)"),
                 click.option('-d', '--directory', default=None, type=click.Path(file_okay=False), help='accepted for compatibility; ignored'),
                 click.option('-c', '--chunks', default=0, help='accepted for compatibility; ignored')):
         f = opt(f)
     return f
+
+
+def _umi_option(collapse_umis, multisample, rangefile):
+    """``--collapse-umis`` as the keyword the multisample drivers take (nothing without the option: the call is then today's); what the
+    option does not run with is refused here, by name, before a file is opened or a process started."""
+    if not collapse_umis:
+        return {}
+    from .bam_utils_multisample import umi_refusal
+    why = umi_refusal(multisample, rangefile)
+    if why:
+        click.echo("Error: {}".format(why), err=True)
+        sys.exit(1)
+    return {"collapse_umis": True}
 
 
 def _strata_option(tag):
@@ -54,14 +69,16 @@ def _strata_option(tag):
 
 
 class _strata_errors(object):
-    """What ``--best-strata`` refuses while it runs (a passing record without the tag): ``Error: ...``, exit status 1, no output file."""
+    """What ``--best-strata`` (a passing record without the tag) and ``--collapse-umis`` (a run beyond the record limit) refuse while
+    they run: ``Error: ...``, exit status 1, no output file."""
 
     def __enter__(self):
         return self
 
     def __exit__(self, kind, e, tb):
         from .bam_utils import BestStrataError
-        if kind is not None and issubclass(kind, BestStrataError):
+        from .bam_utils_multisample import CollapseUmisError
+        if kind is not None and issubclass(kind, (BestStrataError, CollapseUmisError)):
             click.echo("Error: {}".format(e), err=True)
             sys.exit(1)
         return False
@@ -72,17 +89,18 @@ class _strata_errors(object):
 @click.argument('ec_file', metavar='ec_file', type=click.Path(resolve_path=True, dir_okay=False))
 @click.option('-s', '--sample', default=None, help='sample identifier')
 @_common
-def bam2ec(bam_file, ec_file, chunks, directory, best_strata, mincount, multisample, processes, rangefile, targets, verbose, sample):
+def bam2ec(bam_file, ec_file, chunks, directory, best_strata, collapse_umis, mincount, multisample, processes, rangefile, targets, verbose, sample):
     """Convert a BAM file (bam_file) to a binary file (ec_file)."""
     utils.configure_logging(verbose)
     named = _strata_option(best_strata)
+    umis = _umi_option(collapse_umis, multisample, rangefile)
     if multisample:
         if sample:                                                   # cli.py:60-63
             print('-s, --sample should NOT be specified with --multisample')
             return
         with _strata_errors():
             methods.bam2ec_multisample(bam_file, ec_file, chunks, 1000 if mincount is None else mincount, directory,
-                                       processes, rangefile, targets, **named)
+                                       processes, rangefile, targets, **named, **umis)
     else:
         with _strata_errors():
             methods.bam2ec(bam_file, ec_file, chunks, directory, processes, rangefile, sample, targets, **named)
@@ -92,14 +110,15 @@ def bam2ec(bam_file, ec_file, chunks, directory, best_strata, mincount, multisam
 @click.argument('bam_file', metavar='bam_file', type=click.Path(exists=True, resolve_path=True))
 @click.argument('emase_file', metavar='emase_file', type=click.Path(resolve_path=True, dir_okay=False))
 @_common
-def bam2emase(bam_file, emase_file, chunks, directory, best_strata, mincount, multisample, processes, rangefile, targets, verbose):
+def bam2emase(bam_file, emase_file, chunks, directory, best_strata, collapse_umis, mincount, multisample, processes, rangefile, targets, verbose):
     """Convert a BAM file (bam_file) to an EMASE file (emase_file)."""
     utils.configure_logging(verbose)
     named = _strata_option(best_strata)
+    umis = _umi_option(collapse_umis, multisample, rangefile)
     with _strata_errors():
         if multisample:
             methods.bam2emase_multisample(bam_file, emase_file, chunks, 2000 if mincount is None else mincount, directory,
-                                          processes, rangefile, targets, **named)
+                                          processes, rangefile, targets, **named, **umis)
         else:
             methods.bam2emase(bam_file, emase_file, chunks, directory, processes, rangefile, targets, **named)
 

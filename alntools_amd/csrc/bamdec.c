@@ -46,6 +46,8 @@ typedef struct bd_handle {
     uint8_t* last; size_t last_cap; int32_t last_len; int has_last;
     /* multisample (bd_read_ms): the cell ids of the runs the last call started, back to back, and where each begins */
     uint8_t* cells; size_t cells_cap, cells_len; uint32_t* cell_off; size_t cell_off_cap, n_cells;
+    /* bd_set_umi: field 6 of the same names (the raw UMI), kept the same way -- n_cells of them */
+    int umi_on; uint8_t* umis; size_t umis_cap, umis_len; uint32_t* umi_off; size_t umi_off_cap;
     /* bd_set_score: the tag(s) whose value is a record's score, and the scores of the records the last read call handed out */
     int score_on, score_two; uint8_t tag_a[2], tag_b[2];
     int32_t* scores; uint8_t* score_present; size_t score_cap, n_scores;
@@ -185,7 +187,7 @@ int bd_progress(bd_handle* h, uint64_t* consumed, uint64_t* total) {
 void bd_close(bd_handle* h) {
     if (!h) return;
     if (h->f) fclose(h->f);
-    free(h->raw); free(h->buf); free(h->text); free(h->last); free(h->cells); free(h->cell_off);
+    free(h->raw); free(h->buf); free(h->text); free(h->last); free(h->cells); free(h->cell_off); free(h->umis); free(h->umi_off);
     if (h->names) { for (int32_t i = 0; i < h->n_ref; ++i) free(h->names[i]); free(h->names); }
     free(h->lens); free(h->ref_blob); free(h->scratch); free(h->scores); free(h->score_present);
     free(h);
@@ -462,10 +464,10 @@ int bd_read_tuples(bd_handle* h, size_t max_records, int trim, const uint32_t* t
 }
 
 /* ---- multisample scan (alntools/bam_utils_multisample.py:257-300) -------------------------------------------------- */
-/* field 14 of the name split at every "|||" (the cell barcode, :270-280); -1 if there are fewer than 15 fields */
-static int32_t cell_field(const uint8_t* s, int32_t n, int32_t* start) {
+/* field `which` of the name split at every "|||": its length, and where it starts; -1 if there are fewer than which + 1 fields */
+static int32_t name_field(const uint8_t* s, int32_t n, int32_t which, int32_t* start) {
     int32_t pos = 0, field = 0, f0 = 0;
-    while (field < 14) {
+    while (field < which) {
         int32_t k = pos;
         for (; k + 3 <= n; ++k) if (s[k] == '|' && s[k + 1] == '|' && s[k + 2] == '|') break;
         if (k + 3 > n) return -1;
@@ -475,6 +477,28 @@ static int32_t cell_field(const uint8_t* s, int32_t n, int32_t* start) {
     for (; k + 3 <= n; ++k) if (s[k] == '|' && s[k + 1] == '|' && s[k + 2] == '|') break;
     *start = f0;
     return (k + 3 <= n ? k : n) - f0;
+}
+/* field 14 (the cell barcode, :270-280) */
+static int32_t cell_field(const uint8_t* s, int32_t n, int32_t* start) { return name_field(s, n, 14, start); }
+/* `len` bytes appended to a list of strings kept back to back (bytes / off as bd_ms_cells hands them out; `n` strings so far) */
+static int keep_field(bd_handle* h, uint8_t** bytes, size_t* cap, size_t* used, uint32_t** off, size_t* off_cap, size_t n, const uint8_t* src, size_t len) {
+    if (*used + len > *cap) {
+        const size_t nc = (*used + len) * 2 + 4096;
+        uint8_t* nb = (uint8_t*)realloc(*bytes, nc);
+        if (!nb) return fail(h, BD_ERR_MEM, "out of memory");
+        *bytes = nb; *cap = nc;
+    }
+    if (n + 2 > *off_cap) {
+        const size_t nc = (n + 2) * 2 + 1024;
+        uint32_t* no = (uint32_t*)realloc(*off, nc * sizeof(uint32_t));
+        if (!no) return fail(h, BD_ERR_MEM, "out of memory");
+        *off = no; *off_cap = nc;
+    }
+    (*off)[n] = (uint32_t)*used;
+    if (len) memcpy(*bytes + *used, src, len);
+    *used += len;
+    (*off)[n + 1] = (uint32_t)*used;
+    return BD_OK;
 }
 
 /* As bd_read, with the multisample path's run rule instead of `head`: newrun[i] = 1 if the record is valid and starts a run.
@@ -487,7 +511,7 @@ int bd_read_ms(bd_handle* h, size_t max_records, uint16_t* flag, int32_t* tid, i
                uint8_t* valid, uint8_t* newrun, size_t* n_out) {
     if (!h || !flag || !tid || !pos || !next_tid || !next_pos || !valid || !newrun || !n_out) return BD_ERR_ARG;
     size_t n = 0;
-    h->cells_len = 0; h->n_cells = 0; h->n_scores = 0;
+    h->cells_len = 0; h->umis_len = 0; h->n_cells = 0; h->n_scores = 0;
     while (n < max_records) {
         int rc = need(h, 4);
         if (rc == 1) { if (h->len != h->pos) return fail(h, BD_ERR_FORMAT, "truncated BAM"); break; }
@@ -525,22 +549,16 @@ int bd_read_ms(bd_handle* h, size_t max_records, uint16_t* flag, int32_t* tid, i
                 int32_t c0 = 0;
                 const int32_t cl = cell_field(h->last, h->last_len, &c0);
                 if (cl < 0) return fail(h, BD_ERR_FORMAT, "a read name has no cell id in '|||' field 14 (bam_utils_multisample.py:270-280)");
-                if (h->cells_len + (size_t)cl > h->cells_cap) {
-                    const size_t nc = (h->cells_len + (size_t)cl) * 2 + 4096;
-                    uint8_t* nb = (uint8_t*)realloc(h->cells, nc);
-                    if (!nb) return fail(h, BD_ERR_MEM, "out of memory");
-                    h->cells = nb; h->cells_cap = nc;
+                if (h->umi_on) {                                         /* (a name with field 14 has field 6) */
+                    int32_t u0 = 0;
+                    const int32_t ul = name_field(h->last, h->last_len, 6, &u0);
+                    if (ul < 0) return fail(h, BD_ERR_FORMAT, "a read name has no '|||' field 6");
+                    rc = keep_field(h, &h->umis, &h->umis_cap, &h->umis_len, &h->umi_off, &h->umi_off_cap, h->n_cells, h->last + u0, (size_t)ul);
+                    if (rc != BD_OK) return rc;
                 }
-                if (h->n_cells + 2 > h->cell_off_cap) {
-                    const size_t nc = (h->n_cells + 2) * 2 + 1024;
-                    uint32_t* no = (uint32_t*)realloc(h->cell_off, nc * sizeof(uint32_t));
-                    if (!no) return fail(h, BD_ERR_MEM, "out of memory");
-                    h->cell_off = no; h->cell_off_cap = nc;
-                }
-                h->cell_off[h->n_cells++] = (uint32_t)h->cells_len;
-                memcpy(h->cells + h->cells_len, h->last + c0, (size_t)cl);
-                h->cells_len += (size_t)cl;
-                h->cell_off[h->n_cells] = (uint32_t)h->cells_len;
+                rc = keep_field(h, &h->cells, &h->cells_cap, &h->cells_len, &h->cell_off, &h->cell_off_cap, h->n_cells, h->last + c0, (size_t)cl);
+                if (rc != BD_OK) return rc;
+                ++h->n_cells;
             }
         }
         valid[n] = (uint8_t)ok; newrun[n] = nr;
@@ -556,5 +574,18 @@ int bd_read_ms(bd_handle* h, size_t max_records, uint16_t* flag, int32_t* tid, i
 int bd_ms_cells(const bd_handle* h, const uint8_t** bytes, const uint32_t** off, size_t* n) {
     if (!h || !bytes || !off || !n) return BD_ERR_ARG;
     *bytes = h->cells; *off = h->cell_off; *n = h->n_cells;
+    return BD_OK;
+}
+
+/* bd_set_umi: from here on bd_read_ms also keeps field 6 of every tracked name (on != 0), or no longer does (0: how a handle starts) */
+int bd_set_umi(bd_handle* h, int on) {
+    if (!h) return BD_ERR_ARG;
+    h->umi_on = on != 0;
+    return BD_OK;
+}
+/* field 6 of the names whose field 14 bd_ms_cells returns, in the same form; n = 0 while bd_set_umi is off */
+int bd_ms_umis(const bd_handle* h, const uint8_t** bytes, const uint32_t** off, size_t* n) {
+    if (!h || !bytes || !off || !n) return BD_ERR_ARG;
+    *bytes = h->umis; *off = h->umi_off; *n = h->umi_on ? h->n_cells : 0;
     return BD_OK;
 }

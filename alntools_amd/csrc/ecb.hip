@@ -6385,6 +6385,8 @@ extern "C" int ecb_salmon_ecs(int device, const char* text, uint64_t n_bytes, ui
 #include "bus_correct.inc"
 // ... and, for the record streams of bam2ec, a read's best-scoring alignments kept (ecb_best_strata / ecb_best_strata_device)
 #include "strata.inc"
+// ... and the reads of one molecule made one read (ecb_collapse_umis / ecb_collapse_umis_device)
+#include "umi.inc"
 
 // ---- ecb_merge: the multi-GPU merge for ONE process that drives several GPUs ----------------------------------------------
 // shards[r] holds the reads of contiguous read shard r on its own device; `root` is an empty handle (any device).  The same protocol as

@@ -26,17 +26,17 @@ def bam2both(bam_filename, ec_filename, emase_filename, chunks=0, directory=None
 
 
 def bam2ec_multisample(bam_filename, ec_filename, chunks=0, minimum_count=-1, directory=None, number_processes=-1,
-                       range_filename=None, target_filename=None, best_strata=None):
+                       range_filename=None, target_filename=None, best_strata=None, collapse_umis=False):
     from . import bam_utils_multisample
     return bam_utils_multisample.convert(bam_filename, ec_filename, None, chunks, minimum_count, number_processes,
-                                         directory, range_filename, target_filename, best_strata=best_strata)
+                                         directory, range_filename, target_filename, best_strata=best_strata, collapse_umis=collapse_umis)
 
 
 def bam2emase_multisample(bam_filename, emase_filename, chunks=0, minimum_count=-1, directory=None,
-                          number_processes=-1, range_filename=None, target_filename=None, best_strata=None):
+                          number_processes=-1, range_filename=None, target_filename=None, best_strata=None, collapse_umis=False):
     from . import bam_utils_multisample
     return bam_utils_multisample.convert(bam_filename, None, emase_filename, chunks, minimum_count, number_processes,
-                                         directory, range_filename, target_filename, best_strata=best_strata)
+                                         directory, range_filename, target_filename, best_strata=best_strata, collapse_umis=collapse_umis)
 
 
 def ec2emase(ec_file, emase_file):

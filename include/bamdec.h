@@ -66,6 +66,12 @@ int bd_ms_cells(const bd_handle* h, const uint8_t** bytes, const uint32_t** off,
  * that is no integer is BD_ERR_FORMAT from the read call. */
 int bd_set_score(bd_handle* h, const char* tag_a, const char* tag_b);
 int bd_scores(const bd_handle* h, const int32_t** score, const uint8_t** present, size_t* n);
+/* The raw UMI of a run (ABI 4, additive; --collapse-umis): while bd_set_umi is on (on != 0; a handle starts with it off, and then
+ * behaves exactly as before), bd_read_ms also keeps field 6 of every tracked name whose field 14 it keeps -- the same split at "|||";
+ * the bytes as they are, an empty field included -- and bd_ms_umis returns them as bd_ms_cells returns the cells: n of them, one per
+ * run started by the last bd_read_ms, UMI k = bytes [off[k], off[k + 1]), valid until the next call; n = 0 while it is off. */
+int bd_set_umi(bd_handle* h, int on);
+int bd_ms_umis(const bd_handle* h, const uint8_t** bytes, const uint32_t** off, size_t* n);
 /* How far the records handed out so far reach into the file (compressed bytes; what has been read ahead and inflated but not
  * parsed yet is not counted) and the file's size -- a monotone measure of progress, for a reader that deals a file's records out
  * to several consumers in order (ABI 4; ABI 3 counted the read-ahead). */

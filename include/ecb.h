@@ -415,5 +415,7 @@ const char* ecb_profile_kernel(const ecb_handle* h);
 #       include "ecb_bus_correct.h"
 /* ... and the ones that keep, of every read's alignments, the best-scoring ones before ecb_push* sees them (--best-strata). */
 #        include "ecb_strata.h"
+/* ... and the ones that make the reads of one molecule one read, likewise before ecb_push* (--collapse-umis). */
+#         include "ecb_umi.h"
 
 #endif /* ECB_H */
