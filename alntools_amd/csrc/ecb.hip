@@ -173,7 +173,7 @@ __device__ __forceinline__ bool rec_valid(u32 hf) {
 // Read counts and first appearances are NOT maintained here: per-read atomics on a skewed EC distribution run at
 // ~5 G/s chip-wide (measured), so k_stream only records the slot of every read and k_count reduces them afterwards.
 // ---------------------------------------------------------------------------------------------
-enum { ST_NONE = 0, ST_LOOK, ST_HIT, ST_CREATED, ST_PENDING, ST_FULL, ST_OTHER, ST_STUCK };
+enum { ST_NONE = 0, ST_LOOK, ST_HIT, ST_CREATED, ST_PENDING, ST_FULL, ST_OTHER, ST_STUCK, ST_CLAIM };   // (ST_CLAIM: k_stream's flush -- found empty, the claim not yet made)
 enum { CMP_EQUAL = 0, CMP_DIFFERENT, CMP_INCOMPLETE, CMP_UNSURE };
 struct SlotView { u32 n, off; uint2 p[INL]; };
 
@@ -203,6 +203,8 @@ __device__ __forceinline__ uint2 key_pair_fresh(Slot* s, uint2* arena, u32 off, 
 //     Polls with read-modify-write atomics, which execute at the memory side, until the key is whole, and decides.
 //   Callers that create a slot publish it BEFORE any lane of their wave calls table_settle: the creator a lane waits for
 //   may sit in its own wave.
+//   (k_stream's flush does not call table_lookup: it reads lines and claims' answers the same way, but with the loads and the
+//    claims of all its lanes in flight together -- k_stream.inc, phase (c).  k_slow, k_merge and the rehash do.)
 // Read counts and first appearances are NOT maintained here: per-read atomics on a skewed EC distribution run at
 // ~5 G/s chip-wide (measured), so k_stream only records the slot of every read and k_count reduces them afterwards.
 // ---------------------------------------------------------------------------------------------
@@ -2946,8 +2948,8 @@ int build_batch(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* d_
     RCCHK(plan_stream(h, n, &P, v));
     u64* timing = nullptr;
 #ifdef ECB_TIMING
-    HIPCHK(h, hipMalloc(&timing, 8 * sizeof(u64)));
-    HIPCHK(h, hipMemset(timing, 0, 8 * sizeof(u64)));
+    HIPCHK(h, hipMalloc(&timing, 16 * sizeof(u64)));
+    HIPCHK(h, hipMemset(timing, 0, 16 * sizeof(u64)));
 #endif
     h->ctr_synced = false;
     *launched = true;
@@ -2972,13 +2974,17 @@ int build_batch(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* d_
     }
 #ifdef ECB_TIMING
     {
-        u64 t[8];
+        u64 t[16];
         hipMemcpy(t, timing, sizeof(t), hipMemcpyDeviceToHost); hipFree(timing);
         static const char* nm[8] = {"(a) filter+heads", "tile decisions", "prefetch issue+clear+geometry", "(b) LDS tables", "hash entries", "(c) lookup", "publish/settle/slot stores", "-"};
         u64 tot = 0; for (int i = 0; i < 7; ++i) tot += t[i];
         fprintf(stderr, "[ecb timing] %llu waves, clocks per wave:", (unsigned long long)P.slices);
         for (int i = 0; i < 7; ++i) fprintf(stderr, "  %s %.0f (%.1f%%)", nm[i], (double)t[i] / P.slices, 100.0 * t[i] / std::max<u64>(tot, 1));
         fprintf(stderr, "  tile visits on the probe-on path %llu of %llu tiles", (unsigned long long)t[7], (unsigned long long)((n + WT - 1) / WT));
+        // (c)'s trips to the EC table per lookup of up to 64 reads (a flush; two per flush where a pass holds 128): each is one wait on table memory
+        fprintf(stderr, "  table trips per lookup %.3f (claim-only %.3f) over %llu lookups: 1: %.1f%%  2: %.1f%%  3: %.1f%%  4+: %.1f%%", (double)t[12] / std::max<u64>(t[14], 1),
+                (double)t[13] / std::max<u64>(t[14], 1), (unsigned long long)t[14], 100.0 * t[8] / std::max<u64>(t[14], 1), 100.0 * t[9] / std::max<u64>(t[14], 1),
+                100.0 * t[10] / std::max<u64>(t[14], 1), 100.0 * t[11] / std::max<u64>(t[14], 1));
         fprintf(stderr, "\n");
     }
 #endif

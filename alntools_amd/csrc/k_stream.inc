@@ -304,7 +304,7 @@ __global__ __launch_bounds__(TPB, RANGES ? (WAVES_PER_SIMD < 4 ? WAVES_PER_SIMD 
     if (lane == 0) L.ws[7] = 0u;
     if (!VERIFY && lane == 0) { const u64* wa = C->wave_arena; const u64 ca = wa[2 * pw]; L.ws[2] = (u32)ca; L.ws[3] = (u32)(ca >> 32); L.ws[4] = (u32)wa[2 * pw + 1]; }
 #ifdef ECB_TIMING
-    u64 tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = __builtin_readcyclecounter();
+    u64 tacc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast = __builtin_readcyclecounter();
 #endif
     // this wave's per-pass LDS state: table, hash sums, pair counts -- cleared here and behind every flush
     auto clear_pass = [&](u32 ln) {
@@ -691,6 +691,9 @@ __global__ __launch_bounds__(TPB, RANGES ? (WAVES_PER_SIMD < 4 ? WAVES_PER_SIMD 
             u64 j = 0;
             u32 st = ST_NONE, probes = 0, np = 0, fseen = 0;       // fseen: ~(first read) as the slot's line showed it (0 = nothing yet)
             u64 lo = 0;
+#ifdef ECB_TIMING
+            u32 f_rounds = 0, f_claim = 0;                          // trips to the EC table in this lookup; those in which no lane loaded a line
+#endif
             const u32 rx = KS_SHORT ? ln + (half << 6) : ln;       // my read's index within the pass
             const bool on = rx < npend && !ABL(A, 3u);
             const u32 rd = pb + rx;
@@ -727,21 +730,72 @@ __global__ __launch_bounds__(TPB, RANGES ? (WAVES_PER_SIMD < 4 ? WAVES_PER_SIMD 
                     if (st == ST_LOOK) {
                         if (ABL(A, 64u)) { st = ST_HIT; fseen = 0xFFFFFFFFu; }   // (profiling: no table access at all, no first-read atomic)
                         else if (ABL(A, 4u)) st = ST_HIT;
-                        else st = table_lookup(A.table, A.cap_mask, lo, j, probes, cmp, ABL(A, 24u), &fseen);
                     }
-                    if (round == 0u && half == 0u) {
-                        TICK(5);
-                        // Take over the prefetched tile HERE, right behind the lookup's own wait and before this flush issues any store.
-                        // vmcnt counts in order: wherever the compiler first touches these registers it waits for everything issued before
-                        // that point, and at the end of the tile (where the moves sink to if left alone) or at the top of the next one
-                        // (the parked flag) that meant sitting out the round trips of the founders' stores -- ~3000 clocks per tile on C3.
-                        parked = parked_next; taken = true;
-                    #pragma unroll
-                        for (int k = 0; k < RPL; ++k) {
-                            asm volatile("" : "+v"(R.rr[k])); asm volatile("" : "+v"(R.ll[k])); asm volatile("" : "+v"(R.hh[k]));
-                            if constexpr (RANGES) asm volatile("" : "+v"(r_pos[k]));
+                    // The lookup in explicit trips to the table: in every trip EVERY unsettled lane has its memory operation in flight -- the four
+                    // 16-byte loads of the line it looks at (ST_LOOK) or the compare-and-swap on the slot it found empty (ST_CLAIM) -- and the wave
+                    // waits once for the lot.  (table_lookup, one lane's loop run by 64 in lock-step, waited for the first slots' lines, then for the
+                    // claims of the lanes that found theirs empty -- the other lanes idle --, and only then sent the lanes whose slot held another
+                    // key on to the next: the longest probe sequence among 64 lanes plus one trip per flush, 3.0 on config 3, where two or three
+                    // lanes decide the last two of them.  Claims and onward probes now travel together: 2.4.  profiles/flush_rounds_c3.txt)  What a line or a claim's answer means is
+                    // table_lookup's reading of it, word for word.
+                    for (bool first = round == 0u && half == 0u;; first = false) {
+                        const bool look = st == ST_LOOK, claim = st == ST_CLAIM;
+#ifdef ECB_TIMING
+                        if (__ballot(look || claim)) { f_rounds += 1u; if (!__ballot(look)) f_claim += 1u; }
+#endif
+                        Slot* const s = A.table + j;
+                        // (the loads are not under a branch: the lanes that look at nothing load the table's first line, one request for the lot, and ignore it.
+                        //  Loads of the looking lanes alone, merged with zeros for the others, were register copies in the block of the loads -- and a wait
+                        //  for every line in front of them, before the claims were issued.)
+                        const uint4* const q = reinterpret_cast<const uint4*>(look ? s : A.table);
+                        uint4 a = q[0], b = a, c = a, d = a;                  // lo, n1, off | count, first_inv, pair 0 | pairs 1, 2 | pairs 3, 4
+                        if (!ABL(A, 16u)) { b = q[1]; c = q[2]; d = q[3]; }  // (profiling only: 16 = first 16 bytes only, 8 = no key compare)
+                        u64 got = 0;
+                        if (claim) got = atomicCAS(&s->lo, 0ull, lo);
+                        // The loads and the compare-and-swap are issued back to back under their execution masks, and the answers are opaque up to
+                        // here: left alone, the compiler sinks the compare's first steps into the block of the loads and waits for the lines there,
+                        // in front of the claims.
+                        asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w), "+v"(b.x), "+v"(b.y), "+v"(b.z), "+v"(b.w));
+                        asm volatile("" : "+v"(c.x), "+v"(c.y), "+v"(c.z), "+v"(c.w), "+v"(d.x), "+v"(d.y), "+v"(d.z), "+v"(d.w), "+v"(got));
+                        bool adv = false;                                   // on to the next slot
+                        if (look) {
+                            fseen = 0u;
+                            const u64 clo = ((u64)a.y << 32) | a.x;
+                            if (clo == 0ull) st = ST_CLAIM;                  // empty as far as this (possibly old) copy of the line shows: the claim tells
+                            else if (clo != lo) adv = true;
+                            else if (a.z == 0u) st = ST_PENDING;             // claimed with our hash, its key not (visibly) complete
+                            else if (a.z == DEAD_KEY) adv = true;
+                            else {
+                                fseen = b.y;                                 // (what this line -- possibly an old copy -- shows of the EC's first read)
+                                if (ABL(A, 8u)) st = ST_HIT;
+                                else {
+                                    const int r = cmp.quick(make_view(a, b, c, d));
+                                    if (r == CMP_EQUAL) st = ST_HIT;
+                                    else if (r == CMP_DIFFERENT) adv = true;     // (same hash, another key: a true collision takes the next slot)
+                                    else st = ST_PENDING;
+                                }
+                            }
+                        } else if (claim) {
+                            if (got == 0ull) st = ST_CREATED;
+                            else if (got == lo) st = ST_PENDING;             // claimed with our hash a moment ago: its key decides
+                            else adv = true;
                         }
-                        asm volatile("" : "+v"(parked));
+                        if (adv) { j = (j + 1) & A.cap_mask; ++probes; st = probes < MAX_PROBE ? ST_LOOK : ST_FULL; }
+                        if (first) {
+                            TICK(5);
+                            // Take over the prefetched tile HERE, right behind the lookup's own wait and before this flush issues any store.
+                            // vmcnt counts in order: wherever the compiler first touches these registers it waits for everything issued before
+                            // that point, and at the end of the tile (where the moves sink to if left alone) or at the top of the next one
+                            // (the parked flag) that meant sitting out the round trips of the founders' stores -- ~3000 clocks per tile on C3.
+                            parked = parked_next; taken = true;
+                        #pragma unroll
+                            for (int k = 0; k < RPL; ++k) {
+                                asm volatile("" : "+v"(R.rr[k])); asm volatile("" : "+v"(R.ll[k])); asm volatile("" : "+v"(R.hh[k]));
+                                if constexpr (RANGES) asm volatile("" : "+v"(r_pos[k]));
+                            }
+                            asm volatile("" : "+v"(parked));
+                        }
+                        if (!__ballot(st == ST_LOOK || st == ST_CLAIM)) break;
                     }
                     const u64 cmask = __ballot(st == ST_CREATED);
                     if (cmask) {
@@ -792,13 +846,20 @@ __global__ __launch_bounds__(TPB, RANGES ? (WAVES_PER_SIMD < 4 ? WAVES_PER_SIMD 
                     }
                     if (!__ballot(st == ST_PENDING)) break;
                     if (round >= 64u) { if (st == ST_PENDING) { bad |= ERR_INTERNAL; st = ST_NONE; } break; }
+#ifdef ECB_TIMING
+                    f_rounds += 1u;                                      // (a settle polls the slot: a trip at the least)
+#endif
                     if (st == ST_PENDING) {
                         const int r = table_settle(A.table + j, cmp);
                         if (r == ST_HIT) st = ST_HIT;
                         else if (r == ST_STUCK) { bad |= ERR_INTERNAL; st = ST_NONE; atomicExch(&A.ctr->full, 1u); }   // (every wave stops at its next tile)
-                        else { j = (j + 1) & A.cap_mask; ++probes; st = ST_LOOK; }
+                        else { j = (j + 1) & A.cap_mask; ++probes; st = probes < MAX_PROBE ? ST_LOOK : ST_FULL; }
                     }
                 }
+#ifdef ECB_TIMING
+                // trips to the EC table this lookup of up to 64 reads made: a histogram (1, 2, 3, 4 or more), their sum, the claim-only ones, lookups
+                tacc[8] += f_rounds <= 1u; tacc[9] += f_rounds == 2u; tacc[10] += f_rounds == 3u; tacc[11] += f_rounds >= 4u; tacc[12] += f_rounds; tacc[13] += f_claim; tacc[14] += 1;
+#endif
                 if (st == ST_FULL) {                                    // table too full here: defer the read, park
                     atomicExch(&A.ctr->full, 1u);
                     // (its head: the first record of the read among those of my slice up to the tile in hand -- the run counter never decreases)
@@ -860,7 +921,7 @@ __global__ __launch_bounds__(TPB, RANGES ? (WAVES_PER_SIMD < 4 ? WAVES_PER_SIMD 
     // per-wave totals go to their own words: thousands of waves adding to three shared counters serialise (~50 ns each)
     const u32 wn = VERIFY ? wave_sum(my_new) : my_new;
 #ifdef ECB_TIMING
-    if (lane == 0 && C->timing) for (int i = 0; i < 8; ++i) atomicAdd(C->timing + i, tacc[i]);
+    if (lane == 0 && C->timing) for (int i = 0; i < 16; ++i) atomicAdd(C->timing + i, tacc[i]);
 #endif
     if (lane == 0) { u32* wc = C->wave_counts; wc[3 * pw] = wa; wc[3 * pw + 1] = wv; wc[3 * pw + 2] = wn; }
     if (!VERIFY && lane == 0) { u64* wav = C->wave_arena; wav[2 * pw] = ((u64)L.ws[3] << 32) | L.ws[2]; wav[2 * pw + 1] = L.ws[4]; }
