@@ -28,7 +28,6 @@ constexpr u32 BUS_MAX_UMILEN = ECB_BUS_MAX_UMILEN;   // the UMI's 2 bits per bas
 constexpr u32 BUS_WAVE_WORK = 128;                   // candidates x (k - 1) from which a molecule's intersection is a wave's work, not a lane's
 constexpr u32 BUS_MERGE_LEN = 8;                     // a line up to this long is walked, a longer one bisected (bus_has)
 constexpr u32 BUS_NONE = 0xFFFFFFFFu;
-constexpr u64 BUS_NO_ERR = ~0ull;
 enum : u32 { BUS_R_EC = 1, BUS_R_BARCODE, BUS_R_UMI };
 enum : u32 { BUS_L_PTR = 1, BUS_L_TARGET, BUS_L_ORDER };
 enum : u32 { BUS_E_KEEP = 1u, BUS_E_COUNT = 2u };
@@ -52,7 +51,6 @@ const char* bus_line_reason(u32 r) {
     default: return "unknown";
     }
 }
-__device__ __forceinline__ void bus_err(u64* err, u64 at, u32 reason) { atomicMin(reinterpret_cast<unsigned long long*>(err), (unsigned long long)(at << 8 | reason)); }
 // the last r of [0, n) with off[r] <= p (off[0] <= p)
 __device__ __forceinline__ u32 bus_row_of(const u32* off, u32 n, u32 p) {
     u32 lo = 0, hi = n;
@@ -73,16 +71,16 @@ __device__ __forceinline__ bool bus_has(const u32* ids, u32 lo, u32 hi, u32 t) {
 __global__ __launch_bounds__(TPB) void k_bus_lines(const u32* ptr, u32 n_ecs, const u32* ids, u64 nt, u32 n_targets, u64* err) {
     const u64 i = blockIdx.x * (u64)TPB + threadIdx.x;
     if (i <= n_ecs) {
-        if (i == 0 && ptr[0] != 0u) bus_err(err, 0, BUS_L_PTR);
-        if (i < n_ecs && ptr[i] > ptr[i + 1]) bus_err(err, i, BUS_L_PTR);
-        if (i == n_ecs && (u64)ptr[i] != nt) bus_err(err, n_ecs ? n_ecs - 1 : 0, BUS_L_PTR);
+        if (i == 0 && ptr[0] != 0u) offender(err, 0, BUS_L_PTR);
+        if (i < n_ecs && ptr[i] > ptr[i + 1]) offender(err, i, BUS_L_PTR);
+        if (i == n_ecs && (u64)ptr[i] != nt) offender(err, n_ecs ? n_ecs - 1 : 0, BUS_L_PTR);
     }
     if (i >= nt || !n_ecs) return;
     u32 l = bus_row_of(ptr, n_ecs + 1, (u32)i);                 // (on pointers that fall this is some line; those are refused first)
     if (l >= n_ecs) l = n_ecs - 1;
     const u32 t = ids[i];
-    if (t >= n_targets) bus_err(err, l, BUS_L_TARGET);
-    if (i + 1 < nt && i + 1 < (u64)ptr[l + 1] && ids[i + 1] <= t) bus_err(err, l, BUS_L_ORDER);
+    if (t >= n_targets) offender(err, l, BUS_L_TARGET);
+    if (i + 1 < nt && i + 1 < (u64)ptr[l + 1] && ids[i + 1] <= t) offender(err, l, BUS_L_ORDER);
 }
 __global__ __launch_bounds__(TPB) void k_bus_keep(const u64* keep, u64 n_keep, u32* bits) {
     const u64 j = blockIdx.x * (u64)TPB + threadIdx.x;
@@ -95,9 +93,9 @@ __global__ __launch_bounds__(TPB) void k_bus_check(const BusRec* recs, u64 n, u3
     if (i >= n) return;
     const u64 bc = recs[i].barcode, umi = recs[i].umi;
     const int ec = recs[i].ec;
-    if (ec < 0 || (u32)ec >= n_ecs) bus_err(err, i, BUS_R_EC);
-    else if (bcbits < 64u && (bc >> bcbits)) bus_err(err, i, BUS_R_BARCODE);
-    else if (umibits < 64u && (umi >> umibits)) bus_err(err, i, BUS_R_UMI);
+    if (ec < 0 || (u32)ec >= n_ecs) offender(err, i, BUS_R_EC);
+    else if (bcbits < 64u && (bc >> bcbits)) offender(err, i, BUS_R_BARCODE);
+    else if (umibits < 64u && (umi >> umibits)) offender(err, i, BUS_R_UMI);
     if (!keep) { keys[i] = bc; vals[i] = (u32)i; return; }
     const u64 q = lower_bound_u64(keep, n_keep, bc);
     const bool in = q < n_keep && keep[q] == bc;
@@ -295,23 +293,6 @@ __global__ __launch_bounds__(TPB) void k_bus_count_events(const u64* keys, u64 n
     if (blockIdx.x == 0 && threadIdx.x == 0) *out = lower_bound_u64(keys, n_events, (u64)n_cells << 32);
 }
 
-// What has to outlive a sort is cut from ONE pool buffer, sized once from the input's bounds (thirty allocations of up to n words each per
-// call cost more than the kernels: profiles/bus2ec_c4.txt).  A take beyond the room is refused, never handed out.
-struct BusArena {
-    char* p = nullptr;
-    u64 cap = 0, used = 0;
-    bool over = false;
-    static u64 pad(u64 n, u64 size) { return (std::max<u64>(n, 1) * size + 255ull) & ~255ull; }
-    template <class T> T* take(u64 n) {
-        const u64 b = pad(n, sizeof(T));
-        if (!p || used + b > cap) { over = true; return nullptr; }
-        T* q = reinterpret_cast<T*>(p + used);
-        used += b;
-        return q;
-    }
-    int missing(const Call& c) const { return over ? fail(nullptr, ECB_ERR_HIP, "%sthe scratch arena is too small (internal)", c.prefix) : c.missing(); }
-};
-
 int bus_check_args(const void* records, uint64_t n, uint32_t bclen, uint32_t umilen, uint32_t flags, uint32_t n_ecs, uint64_t nt, const void* ec_ptr,
                    const void* ec_targets, uint32_t n_targets, const void* tcol, const void* thap, uint32_t n_loci, uint32_t n_haps, const void* keep,
                    uint64_t n_keep, uint64_t cap_cells, uint64_t cap_rows, uint64_t cap_a, uint64_t cap_n, const void* ob, const void* oipa, const void* oixa,
@@ -349,12 +330,13 @@ extern "C" int ecb_bus_molecules_device(int device, const void* d_records, uint6
     const u32 bcbits = 2 * bclen, umibits = 2 * umilen;
     const u64 nt = n_ec_targets;
     // the sort's buffers are the device's pool's (one sort at a time lives in them); what has to outlive a sort is cut from one more pool
-    // buffer (BusArena), the intersections and the rows' flags, whose sizes the data decides, from three others
+    // buffer (Arena), the intersections and the rows' flags, whose sizes the data decides, from three others
     u64 *k0 = nullptr, *k1 = nullptr;
     u32 *v0 = nullptr, *v1 = nullptr;
     SortScratch ss{};
     // [0] lowest (line << 8 | reason)  [1] lowest (record << 8 | reason)  [2] error bits  [3] the sort's word  [4 ..) scan totals
-    u64* words = c.get<u64>(CV_WORDS, 16);
+    u64* words;
+    RCCHK(c.status_words(words, 16, 2));
     auto sort_room = [&](u64 m) {
         k0 = c.get<u64>(CV_KEYS0, m); k1 = c.get<u64>(CV_KEYS1, m); v0 = c.get<u32>(CV_VALS0, m); v1 = c.get<u32>(CV_VALS1, m);
         ss = SortScratch{c.get<u32>(CV_HIST, rs_words(m)), c.get<u32>(CV_OFFS, RS_AUX_WORDS), words + 3};
@@ -362,16 +344,12 @@ extern "C" int ecb_bus_molecules_device(int device, const void* d_records, uint6
     };
     // the arena's room: every buffer below at its bound -- molecules, distinct (molecule, ec) pairs, events and rows are at most n, the
     // molecules of several ECs at most n / 2
-    BusArena ar;
-    {
-        const u64 nk = keep ? n_keep : 0, e1 = (u64)n_ecs + 1, half = n / 2 + 2;
-        auto pad = BusArena::pad;
-        ar.cap = 6 * pad(n + 1, 4) + pad(n, 8) + (keep ? pad(n, 4) + 2 * pad(nk + 1, 4) : 0) + 2 * pad(e1, 4) +
-                 pad(scan_words(std::max<u64>(std::max<u64>(n, nk), e1)), 4) + (no_umi ? 0 : 5 * pad(n + 1, 4) + 8 * pad(half, 4)) + 3 * pad(n + 1, 4) +
-                 pad(n, 8) + 3 * pad(n + 1, 4) + pad(scan_words(n + 1), 4);
-        ar.p = c.get<char>(CV_X0, ar.cap);
-        RCCHK(c.missing());
-    }
+    const u64 nk = keep ? n_keep : 0, e1 = (u64)n_ecs + 1, half = n / 2 + 2;
+    const auto pad = Arena::pad;
+    Arena ar(c, CV_X0, 6 * pad(n + 1, 4) + pad(n, 8) + (keep ? pad(n, 4) + 2 * pad(nk + 1, 4) : 0) + 2 * pad(e1, 4) +
+                           pad(scan_words(std::max<u64>(std::max<u64>(n, nk), e1)), 4) + (no_umi ? 0 : 5 * pad(n + 1, 4) + 8 * pad(half, 4)) +
+                           3 * pad(n + 1, 4) + pad(n, 8) + 3 * pad(n + 1, 4) + pad(scan_words(n + 1), 4));
+    RCCHK(c.missing());
     u32* cell = ar.take<u32>(n);
     u32 *flag = ar.take<u32>(n), *flag2 = ar.take<u32>(n), *pos = ar.take<u32>(n + 1), *pos2 = ar.take<u32>(n + 1), *ecs = ar.take<u32>(n);
     u64* barcodes = ar.take<u64>(keep ? std::min<u64>(n, n_keep) : n);
@@ -383,8 +361,6 @@ extern "C" int ecb_bus_molecules_device(int device, const void* d_records, uint6
     RCCHK(sort_room(n));
     u64 back[16];
     u32* bits = reinterpret_cast<u32*>(words + 2);
-    CALLCHK(c, hipMemsetAsync(words, 0, 16 * 8, st));
-    CALLCHK(c, hipMemsetAsync(words, 0xFF, 16, st));
     CALLCHK(c, hipMemsetAsync(used, 0, (u64)n_ecs * 4, st));
     if (keep) CALLCHK(c, hipMemsetAsync(present, 0, std::max<u64>(n_keep, 1) * 4, st));
     // 1. the checks
@@ -393,15 +369,13 @@ extern "C" int ecb_bus_molecules_device(int device, const void* d_records, uint6
     if (n_keep > 1) k_bus_keep<<<nblk(n_keep, TPB), TPB, 0, st>>>(keep, n_keep, bits);
     CALLCHK(c, hipGetLastError());
     RCCHK(c.read_back(back, words, 4));
-    if (back[0] != BUS_NO_ERR)      // (the records name lines: not looked at before matrix.ec stands)
-        return fail(nullptr, ECB_ERR_CONTRACT, "bus: matrix.ec line %llu: %s", (unsigned long long)(back[0] >> 8), bus_line_reason((u32)(back[0] & 255u)));
+    RCCHK(refuse_offender(back[0], "bus: matrix.ec line", bus_line_reason));      // (the records name lines: not looked at before matrix.ec stands)
     if (back[2] >> 32) return fail(nullptr, ECB_ERR_CONTRACT, "bus: the target map has a column at or beyond n_loci or a haplotype at or beyond n_haps");
     if ((u32)back[2] & BUS_E_KEEP) return fail(nullptr, ECB_ERR_CONTRACT, "bus: the barcodes to keep are not strictly ascending");
     k_bus_check<<<nblk(n, TPB), TPB, 0, st>>>(recs, n, bcbits, umibits, n_ecs, keep, n_keep, words + 1, k0, v0, kidx, present);
     CALLCHK(c, hipGetLastError());
     RCCHK(c.read_back(back, words, 4));
-    if (back[1] != BUS_NO_ERR)
-        return fail(nullptr, ECB_ERR_CONTRACT, "bus: record %llu: %s", (unsigned long long)(back[1] >> 8), bus_record_reason((u32)(back[1] & 255u)));
+    RCCHK(refuse_offender(back[1], "bus: record", bus_record_reason));
     // 2. the cells
     u64 n_cells64 = 0;
     if (!keep) {
@@ -510,7 +484,7 @@ extern "C" int ecb_bus_molecules_device(int device, const void* d_records, uint6
     if (np) k_sl_heads<<<nblk(np, TPB), TPB, 0, st>>>(sa.keys(), np, aflag, words + 14);
     CALLCHK(c, scan_launch(st, aflag, np, apos, sums3, words + 15, 1, apos + np));
     RCCHK(c.read_back(back, words, 16));
-    if (back[14] != BUS_NO_ERR) return fail(nullptr, ECB_ERR_CONTRACT, "bus: two targets of row %llu share a (column, haplotype)", (unsigned long long)(back[14] >> 8));
+    if (back[14] != NO_OFFENDER) return fail(nullptr, ECB_ERR_CONTRACT, "bus: two targets of row %llu share a (column, haplotype)", (unsigned long long)(back[14] >> 8));
     const u64 nnz_a = np ? back[15] : 0;
     if (nnz_a >= (1ull << 31)) return fail(nullptr, ECB_ERR_LIMIT, "bus: non-zeros beyond int32");
     // every size is known: the capacities, then the outputs

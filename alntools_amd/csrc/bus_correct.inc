@@ -1,8 +1,8 @@
 // ---- bus2ec -w / buscorrect: the barcodes of a BUS file's records snapped onto a whitelist (ecb_bus_correct / ecb_bus_correct_device;
-// included by ecb.hip after bus.inc, whose record layout, lowest-offender word and arena it shares) ------------------------------------------
+// included by ecb.hip after bus.inc, whose record layout and record reasons it shares) ------------------------------------------------------
 // bustools correct's rule (include/ecb_bus_correct.h).  Every step is a map over an array or one of the library's scans (scan_launch);
 // nothing is placed by an atomic, so every output is a function of the input alone.  The only atomics are the atomicMin of the lowest
-// offender (bus_err), which only a refusal reads.
+// offender (offender, ecb.hip), which only a refusal reads.
 //   The lookup.  A real whitelist -- 6.8 M entries, 54 MB -- lives in the Infinity Cache, where a dependent load is some 545 cycles: a
 //      bisection of the whole list is 23 of them in a row.  Instead a DIRECTORY over the barcode's leading bits holds one offset per
 //      prefix: dir[p] = the first entry whose leading `bits` bits are at or above p, dir[2^bits] = n_white (k_busc_dir: a bisection per
@@ -69,8 +69,8 @@ __global__ __launch_bounds__(TPB) void k_busc_white(const u64* white, u64 n_whit
     const u64 j = blockIdx.x * (u64)TPB + threadIdx.x;
     if (j >= n_white) return;
     const u64 w = white[j];
-    if (j > 0 && white[j - 1] >= w) bus_err(err, j, BUSC_W_ORDER);
-    else if (bcbits < 64u && (w >> bcbits)) bus_err(err, j, BUSC_W_BIT);
+    if (j > 0 && white[j - 1] >= w) offender(err, j, BUSC_W_ORDER);
+    else if (bcbits < 64u && (w >> bcbits)) offender(err, j, BUSC_W_BIT);
 }
 // directory entry p of 2^bits + 1
 __global__ __launch_bounds__(TPB) void k_busc_dir(BuscTable t, u64 n_white, u32* dir) {
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(TPB) void k_busc_exact(const BusRec* recs, u64 n, u
     if (i >= n) return;
     const u64 bc = recs[i].barcode;
     bool found = true;
-    if (bcbits < 64u && (bc >> bcbits)) bus_err(err, i, BUS_R_BARCODE);
+    if (bcbits < 64u && (bc >> bcbits)) offender(err, i, BUS_R_BARCODE);
     else found = busc_has(t, bc);
     status[i] = found ? (uint8_t)ECB_BUS_EXACT : (uint8_t)BUSC_MISS;
     miss[i] = !found;
@@ -141,8 +141,8 @@ int busc_check_args(const void* records, uint64_t n, uint32_t bclen, const void*
     if (bclen < 1 || bclen > 32) return fail(nullptr, ECB_ERR_ARG, "bus: bclen is 1 .. 32");
     if (n >= (1ull << 30)) return fail(nullptr, ECB_ERR_LIMIT, "bus: 2^30 records or more");
     if (n_white >= (1ull << 31)) return fail(nullptr, ECB_ERR_LIMIT, "bus: a whitelist of 2^31 entries or more");
-    const uintptr_t a = (uintptr_t)records, b = (uintptr_t)out_records;             // (more room than n records is never written)
-    if (cap_out && a < b + std::min<u64>(cap_out, n) * 32 && b < a + n * 32) return fail(nullptr, ECB_ERR_ARG, "bus: out_records overlaps records");
+    if (spans_overlap({records, n * 32}, {out_records, std::min<u64>(cap_out, n) * 32}))      // (more room than n records is never written)
+        return fail(nullptr, ECB_ERR_ARG, "bus: out_records overlaps records");
     return ECB_OK;
 }
 }  // namespace
@@ -156,37 +156,30 @@ extern "C" int ecb_bus_correct_device(int device, const void* d_records, uint64_
     const u32 bcbits = 2 * bclen, bits = busc_dir_bits(n_white, bclen);
     const u64 n_dir = (1ull << bits) + 1;
     // [0] lowest (whitelist entry << 8 | reason)  [1] lowest (record << 8 | reason)  [2] misses  [3] records kept  [4] ambiguous
-    u64* words = c.get<u64>(CV_WORDS, 8);
+    u64* words;
+    RCCHK(c.status_words(words, 8, 2));
     u32* dir = c.get<u32>(CV_X2, n_dir);
-    BusArena ar;
-    ar.cap = BusArena::pad(n, 1) + 2 * BusArena::pad(n, 4) + 2 * BusArena::pad(n + 1, 4) + BusArena::pad(scan_words(n), 4);
-    ar.p = c.get<char>(CV_X0, ar.cap);
+    Arena ar(c, CV_X0, Arena::pad(n, 1) + 2 * Arena::pad(n, 4) + 2 * Arena::pad(n + 1, 4) + Arena::pad(scan_words(n), 4));
     RCCHK(c.missing());
     uint8_t* status = ar.take<uint8_t>(n);
     u32 *miss = ar.take<u32>(n), *keep = ar.take<u32>(n), *mpos = ar.take<u32>(n + 1), *kpos = ar.take<u32>(n + 1), *sums = ar.take<u32>(scan_words(n));
     RCCHK(ar.missing(c));
     const BuscTable t{(const u64*)d_whitelist, dir, bits, bcbits - bits};
     u64 back[8];
-    CALLCHK(c, hipMemsetAsync(words, 0, 8 * 8, st));
-    CALLCHK(c, hipMemsetAsync(words, 0xFF, 16, st));
     // 0. the whitelist, then its directory
     k_busc_white<<<nblk(n_white, TPB), TPB, 0, st>>>(t.white, n_white, bcbits, words);
     CALLCHK(c, hipGetLastError());
     RCCHK(c.read_back(back, words, 2));
-    if (back[0] != BUS_NO_ERR)      // (the directory of a list that is not ascending would be none)
-        return fail(nullptr, ECB_ERR_CONTRACT, "bus: whitelist entry %llu: %s", (unsigned long long)(back[0] >> 8), busc_white_reason((u32)(back[0] & 255u)));
+    RCCHK(refuse_offender(back[0], "bus: whitelist entry", busc_white_reason));      // (the directory of a list that is not ascending would be none)
     k_busc_dir<<<nblk(n_dir, TPB), TPB, 0, st>>>(t, n_white, dir);
     // 1. the exact lookups; the misses listed
     k_busc_exact<<<nblk(n, TPB), TPB, 0, st>>>(recs, n, bcbits, t, words + 1, status, miss);
     CALLCHK(c, scan_launch(st, miss, n, mpos, sums, words + 2));
     RCCHK(c.read_back(back, words, 3));
-    if (back[1] != BUS_NO_ERR)
-        return fail(nullptr, ECB_ERR_CONTRACT, "bus: record %llu: %s", (unsigned long long)(back[1] >> 8), bus_record_reason((u32)(back[1] & 255u)));
+    RCCHK(refuse_offender(back[1], "bus: record", bus_record_reason));
     const u64 n_miss = back[2];
     // 2. the neighbours of the misses
-    BusArena am;
-    am.cap = BusArena::pad(n_miss, 8) + 2 * BusArena::pad(n_miss, 4) + BusArena::pad(n_miss + 1, 4) + BusArena::pad(scan_words(n_miss), 4);
-    am.p = c.get<char>(CV_X1, am.cap);
+    Arena am(c, CV_X1, Arena::pad(n_miss, 8) + 2 * Arena::pad(n_miss, 4) + Arena::pad(n_miss + 1, 4) + Arena::pad(scan_words(n_miss), 4));
     RCCHK(c.missing());
     u64* newbc = am.take<u64>(n_miss);
     u32 *mlist = am.take<u32>(n_miss), *amb = am.take<u32>(n_miss), *apos = am.take<u32>(n_miss + 1), *sums2 = am.take<u32>(scan_words(n_miss));

@@ -4342,7 +4342,98 @@ struct Call {
         const int r = read_back(host, words, n);
         return r != ECB_OK ? r : refuse_bits(nullptr, table, (u32)host[0]);
     }
+    // the call's n status words -- the pool's, or with own = true a buffer of the call's --, zeroed, the first k of them all-ones: those are
+    // lowest-offender words (NO_OFFENDER)
+    int status_words(u64*& words, u64 n, u64 k, bool own = false) {
+        words = own ? get<u64>(n) : get<u64>(CV_WORDS, n);
+        if (const int r = missing()) return r;
+        CALLCHK(*this, hipMemsetAsync(words, 0, n * 8, st));
+        if (k) CALLCHK(*this, hipMemsetAsync(words, 0xFF, k * 8, st));
+        return ECB_OK;
+    }
 };
+
+// -- what the entry points below and the feature files (bus.inc, bus_correct.inc, strata.inc, umi.inc) share besides Call --
+// every array in a fresh device buffer of max(bytes, 4) bytes (in list order), then the inputs copied in
+struct StageIn { DevBuf<>* d; const void* src; u64 bytes; };          // (src null: an output, allocated only)
+int stage_in(const Call& c, const std::vector<StageIn>& list) {
+    for (const StageIn& a : list) CALLCHK(c, a.d->alloc(a.bytes, 4));
+    for (const StageIn& a : list)
+        if (a.src && a.bytes) CALLCHK(c, hipMemcpy(a.d->p, a.src, a.bytes, hipMemcpyHostToDevice));
+    return ECB_OK;
+}
+// the results back: `bytes` of each (none when that is 0)
+struct StageOut { void* dst; const DevBuf<>* d; u64 bytes; };
+int stage_out(const Call& c, const std::vector<StageOut>& list) {
+    for (const StageOut& a : list) if (a.bytes) CALLCHK(c, hipMemcpy(a.dst, a.d->p, a.bytes, hipMemcpyDeviceToHost));
+    return ECB_OK;
+}
+
+// The lowest offender: every check that finds a breach does an atomicMin of (index << 8 | reason) on one status word, which only a
+// refusal reads; the minimum does not depend on who arrives first.  NO_OFFENDER: nothing was found
+constexpr u64 NO_OFFENDER = ~0ull;
+__device__ __forceinline__ void offender(u64* err, u64 at, u32 reason) { atomicMin(reinterpret_cast<unsigned long long*>(err), (unsigned long long)(at << 8 | reason)); }
+// the word read back: ECB_OK, or the refusal "<what> <index>: <reason>" (what: "bus: record")
+int refuse_offender(u64 word, const char* what, const char* (*reason)(u32)) {
+    if (word == NO_OFFENDER) return ECB_OK;
+    return fail(nullptr, ECB_ERR_CONTRACT, "%s %llu: %s", what, (unsigned long long)(word >> 8), reason((u32)(word & 255u)));
+}
+
+// The tuple contract's step rule for the transforms of a tuple stream (strata.inc, umi.inc; the stream kernel checks tiles and sets error
+// bits: k_stream.inc): 0, or why record `id` may not follow a record of `prev_id` -- the ids ascend in steps of 0 or 1, and a step lands
+// on a record that passes the filter
+enum : u32 { TUPLE_R_FALLS = 1, TUPLE_R_JUMPS, TUPLE_R_FILTERED };
+const char* tuple_reason(u32 r) {
+    switch (r) {
+    case TUPLE_R_FALLS: return "read_id falls";
+    case TUPLE_R_JUMPS: return "read_id steps by more than 1";
+    case TUPLE_R_FILTERED: return "read_id steps on a record that does not pass the filter";
+    default: return "unknown";
+    }
+}
+__device__ __forceinline__ u32 tuple_step(u32 prev_id, u32 id, bool passes) {
+    const u32 d = id - prev_id;
+    if (d == 1u) return passes ? 0u : TUPLE_R_FILTERED;
+    return d == 0u ? 0u : d < 0x80000000u ? TUPLE_R_JUMPS : TUPLE_R_FALLS;
+}
+
+// What has to outlive a sort is cut from ONE pool buffer, sized once from the input's bounds (thirty allocations of up to n words each per
+// call cost more than the kernels: profiles/bus2ec_c4.txt).  A take beyond the room is refused, never handed out.
+struct Arena {
+    char* const p;
+    const u64 cap;
+    u64 used = 0;
+    bool over = false;
+    Arena(Call& c, int id, u64 cap_) : p(c.get<char>(id, cap_)), cap(cap_) {}
+    static u64 pad(u64 n, u64 size) { return (std::max<u64>(n, 1) * size + 255ull) & ~255ull; }
+    template <class T> T* take(u64 n) {
+        const u64 b = pad(n, sizeof(T));
+        if (!p || used + b > cap) { over = true; return nullptr; }
+        T* q = reinterpret_cast<T*>(p + used);
+        used += b;
+        return q;
+    }
+    int missing(const Call& c) const { return over ? fail(nullptr, ECB_ERR_HIP, "%sthe scratch arena is too small (internal)", c.prefix) : c.missing(); }
+};
+
+// Caller memory that may not overlap.  Two byte ranges share a byte (an empty one shares none):
+struct Span { const void* p; u64 bytes; };
+bool spans_overlap(Span a, Span b) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a.p), y = reinterpret_cast<uintptr_t>(b.p);
+    return a.bytes && b.bytes && x < y + b.bytes && y < x + a.bytes;
+}
+// ... and an entry point's arrays, the inputs first, the last n_out of them outputs: each output against every input, then against the
+// outputs before it.  alias[k], where given: the input that output k may be exactly (the same first byte), -1: none
+enum SpanClash { SPANS_APART, SPANS_OUT_IN, SPANS_OUT_OUT };
+SpanClash span_clash(const std::vector<Span>& s, size_t n_out, const std::vector<int>& alias = {}) {
+    const size_t n_in = s.size() - n_out;
+    for (size_t o = n_in; o < s.size(); ++o)
+        for (size_t j = 0; j < o; ++j) {
+            if (o - n_in < alias.size() && alias[o - n_in] == (int)j && s[j].p == s[o].p) continue;
+            if (spans_overlap(s[o], s[j])) return j < n_in ? SPANS_OUT_IN : SPANS_OUT_OUT;
+        }
+    return SPANS_APART;
+}
 
 const ErrBit CV_ERRS[] = {{~0u, ECB_ERR_CONTRACT, "malformed CSR: row pointers out of order, a locus beyond n_loci, or a mask that is zero or beyond n_haplotypes"}};
 const ErrBit CVB_ERRS[] = {      // (CVB_ERR_ORDER is no refusal: the sort-everything path takes such a matrix)
@@ -4540,23 +4631,7 @@ extern "C" int ecb_hapcsc_to_csr_device(int device, uint32_t n_ecs, uint32_t n_l
 
 // ---- the same two conversions from and to HOST arrays: the library allocates, fills and frees its own device buffers, so a host
 // that only converts files (alntools ec2emase / emase2ec, the .h5 writer of bam2emase: bin_utils.py:979-1028) needs no device
-// allocator of its own -- and the Python drop-in no PyTorch on that path.
-namespace {
-// every array in a fresh device buffer of max(bytes, 4) bytes (in list order), then the inputs copied in
-struct StageIn { DevBuf<>* d; const void* src; u64 bytes; };          // (src null: an output, allocated only)
-int stage_in(const Call& c, const std::vector<StageIn>& list) {
-    for (const StageIn& a : list) CALLCHK(c, a.d->alloc(a.bytes, 4));
-    for (const StageIn& a : list)
-        if (a.src && a.bytes) CALLCHK(c, hipMemcpy(a.d->p, a.src, a.bytes, hipMemcpyHostToDevice));
-    return ECB_OK;
-}
-// the results back: `bytes` of each (none when that is 0)
-struct StageOut { void* dst; const DevBuf<>* d; u64 bytes; };
-int stage_out(const Call& c, const std::vector<StageOut>& list) {
-    for (const StageOut& a : list) if (a.bytes) CALLCHK(c, hipMemcpy(a.dst, a.d->p, a.bytes, hipMemcpyDeviceToHost));
-    return ECB_OK;
-}
-}  // namespace
+// allocator of its own -- and the Python drop-in no PyTorch on that path (stage_in / stage_out: next to Call).
 
 extern "C" int ecb_csr_to_hapcsc(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, const int32_t* indptr, const int32_t* indices,
                                  const int32_t* data, int32_t* csc_indptr, int32_t* csc_indices, uint64_t capacity, uint64_t* total) {
@@ -4737,10 +4812,6 @@ const ErrBit GM_ERRS[] = {
     {GM_ERR_BITS, ECB_ERR_CONTRACT, "malformed CSR: a haplotype bit at or beyond n_haplotypes"},
     {GM_ERR_MASK, ECB_ERR_CONTRACT, "a locus mask has a bit at or beyond n_haplotypes"},
 };
-bool gm_overlap(const void* a, u64 na, const void* b, u64 nb) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return na && nb && x < y + nb && y < x + na;
-}
 }  // namespace
 
 extern "C" int ecb_apply_mask_device(int device, uint32_t n_ecs, uint32_t n_loci, uint32_t n_haps, uint64_t nnz, const void* d_indptr,
@@ -4750,13 +4821,9 @@ extern "C" int ecb_apply_mask_device(int device, uint32_t n_ecs, uint32_t n_loci
     if (nnz && (!d_indices || !d_data || !d_out_indices || !d_out_data)) return fail(nullptr, ECB_ERR_ARG, "bad argument");
     if (nnz >= (1ull << 31) || n_ecs >= (1u << 31) - 1u) return fail(nullptr, ECB_ERR_LIMIT, "the CSR exceeds the .bin format's int32 limits");
     const u64 rowb = ((u64)n_ecs + 1) * 4, nzb = nnz * 4;
-    const void* ins[4] = {d_indptr, d_indices, d_data, d_mask};
-    const u64 inb[4] = {rowb, nzb, nzb, (u64)n_loci * 4};
-    for (int i = 0; i < 4; ++i)
-        if (gm_overlap(d_out_indptr, rowb, ins[i], inb[i]) || gm_overlap(d_out_indices, nzb, ins[i], inb[i]) || gm_overlap(d_out_data, nzb, ins[i], inb[i]))
-            return fail(nullptr, ECB_ERR_ARG, "an output overlaps an input");
-    if (gm_overlap(d_out_indptr, rowb, d_out_indices, nzb) || gm_overlap(d_out_indptr, rowb, d_out_data, nzb) || gm_overlap(d_out_indices, nzb, d_out_data, nzb))
-        return fail(nullptr, ECB_ERR_ARG, "the outputs overlap");
+    if (const SpanClash clash = span_clash({{d_indptr, rowb}, {d_indices, nzb}, {d_data, nzb}, {d_mask, (u64)n_loci * 4}, {d_out_indptr, rowb},
+                                            {d_out_indices, nzb}, {d_out_data, nzb}}, 3))
+        return fail(nullptr, ECB_ERR_ARG, "%s", clash == SPANS_OUT_IN ? "an output overlaps an input" : "the outputs overlap");
     Call c(device, "apply-mask: "); if (c.rc) return c.rc;
     hipStream_t st = c.st;
     const u64 n_words = GM_SHARD_WORDS * (1 + GM_SHARDS);
@@ -5272,16 +5339,11 @@ extern "C" int ecb_select_device(int device, uint32_t n_ecs, uint32_t n_loci, ui
     RCCHK(sel_check_args(n_ecs, n_loci, n_haps, n_samples, nnz_a, d_indptr_a, d_indices_a, d_data_a, nnz_n, d_indptr_n, d_indices_n, d_data_n, row_class,
                          d_out_indptr_a, d_out_indices_a, d_out_data_a, d_out_indptr_n, d_out_indices_n, d_out_data_n, d_out_sample_keep, out_sizes));
     const u64 E = n_ecs, S = n_samples;
-    const void* ins[7] = {d_indptr_a, d_indices_a, d_data_a, d_indptr_n, d_indices_n, d_data_n, d_sample_keep};
-    const u64 inb[7] = {(E + 1) * 4, nnz_a * 4, nnz_a * 4, (S + 1) * 4, nnz_n * 4, nnz_n * 4, d_sample_keep ? S : 0};
-    void* outs[7] = {d_out_indptr_a, d_out_indices_a, d_out_data_a, d_out_indptr_n, d_out_indices_n, d_out_data_n, d_out_sample_keep};
-    const u64 outb[7] = {(E + 1) * 4, nnz_a * 4, nnz_a * 4, (S + 1) * 4, nnz_n * 4, nnz_n * 4, S};
-    for (int o = 0; o < 7; ++o) {
-        for (int i = 0; i < 7; ++i)
-            if (gm_overlap(outs[o], outb[o], ins[i], inb[i])) return fail(nullptr, ECB_ERR_ARG, "an output overlaps an input");
-        for (int p = 0; p < o; ++p)
-            if (gm_overlap(outs[o], outb[o], outs[p], outb[p])) return fail(nullptr, ECB_ERR_ARG, "the outputs overlap");
-    }
+    const u64 pa = (E + 1) * 4, za = nnz_a * 4, pn = (S + 1) * 4, zn = nnz_n * 4;
+    if (const SpanClash clash = span_clash({{d_indptr_a, pa}, {d_indices_a, za}, {d_data_a, za}, {d_indptr_n, pn}, {d_indices_n, zn}, {d_data_n, zn},
+                                            {d_sample_keep, d_sample_keep ? S : 0}, {d_out_indptr_a, pa}, {d_out_indices_a, za}, {d_out_data_a, za},
+                                            {d_out_indptr_n, pn}, {d_out_indices_n, zn}, {d_out_data_n, zn}, {d_out_sample_keep, S}}, 7))
+        return fail(nullptr, ECB_ERR_ARG, "%s", clash == SPANS_OUT_IN ? "an output overlaps an input" : "the outputs overlap");
     Call c(device, "select: "); if (c.rc) return c.rc;
     hipStream_t st = c.st;
     const bool classed = row_class != SEL_ALL, threshold = min_count >= 0;
@@ -6093,7 +6155,6 @@ namespace {
 using u8 = unsigned char;
 constexpr u32 SL_TILE = TPB * 16;                         // bytes per workgroup of k_sl_count / k_sl_place
 constexpr u32 SL_NONE = 256u;                             // "no byte" (before the start, after the end): not a digit, not a separator
-constexpr u64 SL_NO_ERR = ~0ull;
 enum : u32 { SL_R_BYTE = 1, SL_R_EMPTY, SL_R_BIG, SL_R_FEW, SL_R_K, SL_R_TARGET, SL_R_REPEAT, SL_R_COUNT };
 const char* sl_reason(u32 r) {
     switch (r) {
@@ -6111,7 +6172,6 @@ const char* sl_reason(u32 r) {
 __device__ __forceinline__ bool sl_digit(u32 c) { return c - 48u < 10u; }
 // value * 10 + digit, held at 2^31 once it gets there (every value from 2^31 on is refused alike)
 __device__ __forceinline__ u32 sl_acc(u32 acc, u32 c) { const u64 x = (u64)acc * 10u + (c - 48u); return x < (1ull << 31) ? (u32)x : 1u << 31; }
-__device__ __forceinline__ void sl_err(u64* err, u64 line, u32 reason) { atomicMin(reinterpret_cast<unsigned long long*>(err), (unsigned long long)(line << 8 | reason)); }
 // the 16 bytes at base (zero past the end), and the bytes just before and after them (SL_NONE outside the text)
 __device__ __forceinline__ void sl_load(const u8* text, u64 L, u64 base, u32 w[4], u32& prev, u32& next) {
     if (base + 16 <= L && (reinterpret_cast<uintptr_t>(text + base) & 15u) == 0u) {
@@ -6189,15 +6249,15 @@ __global__ __launch_bounds__(TPB) void k_sl_place(const u8* text, u64 L, const u
                     fval[f] = acc; fline[f] = l; ++f; open = false;
                 }
             } else if (c == 10u) {
-                if (!sl_digit(pc) && pc != 13u) sl_err(err, l, SL_R_EMPTY);
+                if (!sl_digit(pc) && pc != 13u) offender(err, l, SL_R_EMPTY);
                 fend[l] = f; ++l;
             } else if (c == 9u) {
-                if (!sl_digit(pc) || !sl_digit(nc)) sl_err(err, l, SL_R_EMPTY);
+                if (!sl_digit(pc) || !sl_digit(nc)) offender(err, l, SL_R_EMPTY);
             } else if (c == 13u) {
-                if (nc != 10u) sl_err(err, l, SL_R_BYTE);
-                else if (!sl_digit(pc)) sl_err(err, l, SL_R_EMPTY);
+                if (nc != 10u) offender(err, l, SL_R_BYTE);
+                else if (!sl_digit(pc)) offender(err, l, SL_R_EMPTY);
             } else {
-                sl_err(err, l, SL_R_BYTE);
+                offender(err, l, SL_R_BYTE);
             }
             if (p + 1 == L && c != 10u) fend[l] = fs_total;    // (the last line has no line end)
             pc = c;
@@ -6221,15 +6281,15 @@ __global__ __launch_bounds__(TPB) void k_sl_fields(const u32* fval, const u32* f
     if (f >= n_fields) return;
     const u32 v = fval[f], l = fline[f];
     const u32 f0 = l ? fend[l - 1] : 0u, nf = fend[l] - f0, i = (u32)f - f0;
-    if (v >= (1u << 31)) sl_err(err, l, SL_R_BIG);
-    if (i == 0 && nf < 2) sl_err(err, l, SL_R_FEW);
-    else if (i == 0 && v != nf - 2) sl_err(err, l, SL_R_K);
+    if (v >= (1u << 31)) offender(err, l, SL_R_BIG);
+    if (i == 0 && nf < 2) offender(err, l, SL_R_FEW);
+    else if (i == 0 && v != nf - 2) offender(err, l, SL_R_K);
     if (nf >= 2 && i == nf - 1) cnt[l] = v;
     const bool target = nf >= 2 && i >= 1 && i + 1 < nf;
     u64 key = ~0ull;
     u32 val = 0;
     if (target) {
-        if (v >= n_targets) sl_err(err, l, SL_R_TARGET);
+        if (v >= n_targets) offender(err, l, SL_R_TARGET);
         else { const u32 h = thap[v]; key = (u64)l << 32 | (tcol[v] << 5 | h); val = 1u << h; }
     }
     if (dense) {
@@ -6253,7 +6313,7 @@ __global__ __launch_bounds__(TPB) void k_sl_heads(const u64* keys, u64 n, u32* f
     u32 h = 0;
     if (k != ~0ull) {
         const u64 q = i ? keys[i - 1] : ~0ull;
-        if (q == k) sl_err(err, k >> 32, SL_R_REPEAT);
+        if (q == k) offender(err, k >> 32, SL_R_REPEAT);
         h = i == 0 || (q >> 5) != (k >> 5);
     }
     flag[i] = h;
@@ -6300,14 +6360,12 @@ extern "C" int ecb_salmon_ecs_device(int device, const void* d_text, uint64_t n_
     if (nb >= (1ull << 31)) return fail(nullptr, ECB_ERR_LIMIT, "salmon: text too long");
     u32 *blk_nl = c.get<u32>(nb), *blk_fs = c.get<u32>(nb), *nl_ex = c.get<u32>(nb), *fs_ex = c.get<u32>(nb);
     u32 *sc1 = c.get<u32>(scan_words(nb)), *sc2 = c.get<u32>(scan_words(nb));
-    u64* words = c.get<u64>(8);                        // [0] lowest (line << 8 | reason), [1] [2] line ends, field starts, [3] bad target map, [4] [5] scan totals
-    RCCHK(c.missing());
+    u64* words;                                        // [0] lowest (line << 8 | reason), [1] [2] line ends, field starts, [3] bad target map, [4] [5] scan totals
+    RCCHK(c.status_words(words, 8, 1, true));
     u64* err = words;
     u32* bad = reinterpret_cast<u32*>(words + 3);
     u64 back[8] = {0};
     u8 last = 10;
-    CALLCHK(c, hipMemsetAsync(words, 0, 64, st));
-    CALLCHK(c, hipMemsetAsync(err, 0xFF, 8, st));
     // 1. the target map; line ends and field starts per tile, placed
     if (n_targets) k_sl_targets<<<nblk(n_targets, TPB), TPB, 0, st>>>(tcol, thap, n_targets, n_loci, n_haps, bad);
     if (L) {
@@ -6321,7 +6379,7 @@ extern "C" int ecb_salmon_ecs_device(int device, const void* d_text, uint64_t n_
     const u64 n_lines = back[1] + (L && last != 10), NF = back[2];
     if (NF >= (1ull << 30) || n_lines >= (1ull << 31) - 1) return fail(nullptr, ECB_ERR_LIMIT, "salmon: %llu fields in %llu lines: beyond the limits (2^30, 2^31-1)",
                                                                        (unsigned long long)NF, (unsigned long long)n_lines);
-    const u64 count_err = n_lines != n_ecs ? (std::min<u64>(n_lines, n_ecs) << 8 | SL_R_COUNT) : SL_NO_ERR;
+    const u64 count_err = n_lines != n_ecs ? (std::min<u64>(n_lines, n_ecs) << 8 | SL_R_COUNT) : NO_OFFENDER;
     // 2. bytes checked, fields parsed; 3. fields classified, targets to keys (dense slots)
     u32 *fval = c.get<u32>(NF), *fline = c.get<u32>(NF), *fend = c.get<u32>(n_lines), *cnt = c.get<u32>(n_lines);
     u64 *keys0 = c.get<u64>(NF), *keys1 = c.get<u64>(NF);
@@ -6333,7 +6391,7 @@ extern "C" int ecb_salmon_ecs_device(int device, const void* d_text, uint64_t n_
     if (NF) k_sl_fields<<<nblk(NF, TPB), TPB, 0, st>>>(fval, fline, fend, (u32)NF, n_targets, tcol, thap, true, NP, keys0, vals0, cnt, err);
     RCCHK(c.read_back(back, words, 8));
     SortBufs s{{keys0, keys1}, {vals0, vals1}};
-    if (back[0] != SL_NO_ERR) {
+    if (back[0] != NO_OFFENDER) {
         // a malformed line: every field in a slot of its own, sorted on all bits, so that repeats in the lines before it are found too
         k_sl_fields<<<nblk(NF, TPB), TPB, 0, st>>>(fval, fline, fend, (u32)NF, n_targets, tcol, thap, false, NF, keys0, vals0, cnt, err);
         CALLCHK(c, radix_sort_pairs64(st, s, NF, ss));
@@ -6348,7 +6406,7 @@ extern "C" int ecb_salmon_ecs_device(int device, const void* d_text, uint64_t n_
     if (NP) k_sl_heads<<<nblk(NP, TPB), TPB, 0, st>>>(keys, NP, flag, err);
     CALLCHK(c, scan_launch(st, flag, NP, pos, sc3, words + 4, 1, pos + NP));
     RCCHK(c.read_back(back, words, 8));
-    if (std::min(back[0], count_err) != SL_NO_ERR) return refuse(std::min(back[0], count_err));
+    if (std::min(back[0], count_err) != NO_OFFENDER) return refuse(std::min(back[0], count_err));
     const u64 nnz = NP ? back[4] : 0;
     if (nnz > capacity) return fail(nullptr, ECB_ERR_LIMIT, "salmon: %llu non-zeros, room for %llu", (unsigned long long)nnz, (unsigned long long)capacity);
     if (nnz >= (1ull << 31)) return fail(nullptr, ECB_ERR_LIMIT, "salmon: non-zeros beyond int32");

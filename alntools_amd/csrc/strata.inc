@@ -1,5 +1,5 @@
 // ---- --best-strata: of every read's passing records, the best-scoring ones kept (ecb_best_strata / ecb_best_strata_device; included by
-// ecb.hip after bus_correct.inc, whose lowest-offender word it shares) ----------------------------------------------------------------
+// ecb.hip; of its siblings it needs none: Call, the lowest-offender word, tuple_step, Arena and the span check are ecb.hip's) -------------
 // The rule is include/ecb_strata.h's.  A read's verdict is ONE 64-bit word, key = (biased score << 32 | record index), the minimum over
 // the read's passing records (mode "highest" flips the biased score): its high word is the best score, its low word the first kept
 // record; next to it travels the index of the read's first passing record, a minimum too.  Minima do not depend on arrival order.
@@ -27,17 +27,8 @@ constexpr u32 STRATA_SUM_WAVES = 16;                          // waves whose cou
 constexpr u32 STRATA_NONE = 0xFFFFFFFFu;                      // no slot: the wave's first (last) read does not cross its span
 constexpr u64 STRATA_INF = ~0ull;                             // the word of a read without a passing record (no real key: n < 2^32)
 constexpr u32 STRATA_DROP_BITS = 0x4u | ECB_FLAG_STRATA_DROPPED;
-enum : u32 { STRATA_R_FALLS = 1, STRATA_R_JUMPS, STRATA_R_FILTERED };
 static_assert(STRATA_LANE_RECS == 4 && TPB % 64 == 0, "a lane's records are one 16-byte vector, a workgroup is whole waves");
 
-const char* strata_reason(u32 r) {
-    switch (r) {
-    case STRATA_R_FALLS: return "read_id falls";
-    case STRATA_R_JUMPS: return "read_id steps by more than 1";
-    case STRATA_R_FILTERED: return "read_id steps on a record that does not pass the filter";
-    default: return "unknown";
-    }
-}
 // records [i, i + 4) of a stream (i a multiple of 4): one vector where the stream is 16-byte aligned and the four exist, otherwise one
 // by one; a record at or beyond n reads as record n - 1
 __device__ __forceinline__ void strata_load(const u32* p, bool vec, u64 i, u64 n, u32 (&v)[STRATA_LANE_RECS]) {
@@ -143,11 +134,8 @@ __global__ __launch_bounds__(TPB) void k_strata_reduce(const u32* rid, const u32
     const u32 left = prev;
 #pragma unroll
     for (u32 q = 0; q < STRATA_LANE_RECS; ++q) {
-        if (i + q < n) {
-            const u32 d = a.id[q] - prev;
-            if (d == 1u) { if (!a.pass[q]) bus_err(err, i + q, STRATA_R_FILTERED); }
-            else if (d != 0u) bus_err(err, i + q, d < 0x80000000u ? STRATA_R_JUMPS : STRATA_R_FALLS);
-        }
+        const u32 why = i + q < n ? tuple_step(prev, a.id[q], a.pass[q]) : 0u;
+        if (why) offender(err, i + q, why);
         prev = a.id[q];
     }
     u64 K[STRATA_LANE_RECS];
@@ -233,16 +221,12 @@ int strata_check_args(const void* read_id, const void* hapflag, const void* scor
     if (!read_id || !hapflag || !score || !out_read_id || !out_hapflag || !out_counts || !n) return fail(nullptr, ECB_ERR_ARG, "strata: bad argument");
     if (mode != ECB_STRATA_LOWEST && mode != ECB_STRATA_HIGHEST) return fail(nullptr, ECB_ERR_ARG, "strata: mode is 0 (lowest) or 1 (highest)");
     if (n >= (1ull << 32)) return fail(nullptr, ECB_ERR_LIMIT, "strata: 2^32 records or more");
-    const uintptr_t ptrs[5] = {(uintptr_t)read_id, (uintptr_t)hapflag, (uintptr_t)score, (uintptr_t)out_read_id, (uintptr_t)out_hapflag};
-    for (const uintptr_t p : ptrs) if (p & 3u) return fail(nullptr, ECB_ERR_ARG, "strata: a pointer that is not 4-byte aligned");
-    // an output may be exactly its own input; any other two of the five that an output is one of may not share a byte
     const u64 bytes = n * 4;
-    for (int o = 3; o < 5; ++o)
-        for (int j = 0; j < o; ++j) {
-            if (j == o - 3 && ptrs[j] == ptrs[o]) continue;
-            if (ptrs[j] < ptrs[o] + bytes && ptrs[o] < ptrs[j] + bytes)
-                return fail(nullptr, ECB_ERR_ARG, "strata: an output overlaps an input or the other output (it may only be exactly its own input)");
-        }
+    const std::vector<Span> spans = {{read_id, bytes}, {hapflag, bytes}, {score, bytes}, {out_read_id, bytes}, {out_hapflag, bytes}};
+    for (const Span& s : spans) if ((uintptr_t)s.p & 3u) return fail(nullptr, ECB_ERR_ARG, "strata: a pointer that is not 4-byte aligned");
+    // an output may be exactly its own input; any other two of the five that an output is one of may not share a byte
+    if (span_clash(spans, 2, {0, 1}))
+        return fail(nullptr, ECB_ERR_ARG, "strata: an output overlaps an input or the other output (it may only be exactly its own input)");
     return ECB_OK;
 }
 }  // namespace
@@ -253,10 +237,9 @@ extern "C" int ecb_best_strata_device(int device, const void* d_read_id, const v
     Call c(device, "strata: "); if (c.rc) return c.rc;
     hipStream_t st = c.st;
     const u64 n_waves = (n + STRATA_WAVE_RECS - 1) / STRATA_WAVE_RECS;
-    u64* words = c.get<u64>(CV_WORDS, 8);                    // [0] lowest (record << 8 | reason)  [1 .. 4] the counts
-    BusArena ar;
-    ar.cap = BusArena::pad(n_waves, 8) + BusArena::pad(n_waves, 4) + BusArena::pad(2 * n_waves, 4) + BusArena::pad(4 * n_waves, 4);
-    ar.p = c.get<char>(CV_X0, ar.cap);
+    u64* words;                                              // [0] lowest (record << 8 | reason)  [1 .. 4] the counts
+    RCCHK(c.status_words(words, 8, 1));
+    Arena ar(c, CV_X0, Arena::pad(n_waves, 8) + Arena::pad(n_waves, 4) + Arena::pad(2 * n_waves, 4) + Arena::pad(4 * n_waves, 4));
     RCCHK(c.missing());
     u64* best = ar.take<u64>(n_waves);
     u32 *firstp = ar.take<u32>(n_waves), *info = ar.take<u32>(2 * n_waves), *wcount = ar.take<u32>(4 * n_waves);
@@ -264,14 +247,11 @@ extern "C" int ecb_best_strata_device(int device, const void* d_read_id, const v
     const u32 flip = mode == ECB_STRATA_HIGHEST ? 0xFFFFFFFFu : 0u;
     const u32 *rid = (const u32*)d_read_id, *hf = (const u32*)d_hapflag, *sc = (const u32*)d_score;
     u64 back[8];
-    CALLCHK(c, hipMemsetAsync(words, 0, 8 * 8, st));
-    CALLCHK(c, hipMemsetAsync(words, 0xFF, 8, st));
-    CALLCHK(c, hipMemsetAsync(best, 0xFF, BusArena::pad(n_waves, 8) + BusArena::pad(n_waves, 4), st));      // (best and firstp lie behind each other)
+    CALLCHK(c, hipMemsetAsync(best, 0xFF, Arena::pad(n_waves, 8) + Arena::pad(n_waves, 4), st));      // (best and firstp lie behind each other)
     k_strata_reduce<<<nblk(n, STRATA_WG_RECS), TPB, 0, st>>>(rid, hf, sc, n, flip, words, best, firstp, info);
     CALLCHK(c, hipGetLastError());
     RCCHK(c.read_back(back, words, 1));
-    if (back[0] != BUS_NO_ERR)
-        return fail(nullptr, ECB_ERR_CONTRACT, "strata: record %llu: %s", (unsigned long long)(back[0] >> 8), strata_reason((u32)(back[0] & 255u)));
+    RCCHK(refuse_offender(back[0], "strata: record", tuple_reason));
     k_strata_apply<<<nblk(n, STRATA_WG_RECS), TPB, 0, st>>>(rid, hf, sc, n, flip, best, firstp, info, (u32*)d_out_read_id, (u32*)d_out_hapflag, wcount);
     k_strata_sum<<<nblk(n_waves, STRATA_SUM_WAVES * TPB), TPB, 0, st>>>(reinterpret_cast<const uint4*>(wcount), n_waves, words + 1);
     CALLCHK(c, hipGetLastError());

@@ -1,9 +1,9 @@
-// ---- --collapse-umis: the reads of one molecule made one read (ecb_collapse_umis / ecb_collapse_umis_device; included by ecb.hip after
-// strata.inc; it shares bus.inc's lowest-offender word and arena) ----------------------------------------------------------------------
+// ---- --collapse-umis: the reads of one molecule made one read (ecb_collapse_umis / ecb_collapse_umis_device; included by ecb.hip; of
+// its siblings it needs none: Call, the lowest-offender word, tuple_step, Arena and the span check are ecb.hip's) -----------------------
 // The rule is include/ecb_umi.h's -- bus2ec's, stated on tuple streams.  Every step is a map over an array (one element per thread:
 // UMI_LANE_RECS = 1, a wave UMI_WAVE_RECS = 64, a workgroup UMI_WG_RECS = TPB, whatever n is), one of the library's scans (scan_launch)
 // or its stable LSD sort (radix_sort_pairs64); every place written is computed from scans, nothing is placed by an atomic, so every output
-// is a function of the input alone.  The only atomic is the atomicMin of the lowest offender (bus_err), which only a refusal reads.
+// is a function of the input alone.  The only atomic is the atomicMin of the lowest offender (offender, ecb.hip), which only a refusal reads.
 // A run of any length -- a molecule of every read -- is measured by two scan values, never walked: there is no "long run" path.
 //   1. k_umi_check: 12 bytes per record in.  The contract against the record before, locus and haplotype of a passing record, the
 //      filter's verdict per record (pass), whether the first id has a passing record.  || read back: refusals, the number of reads.
@@ -29,7 +29,8 @@ constexpr u32 UMI_LOC_BITS = 26;                              // at the most 30 
 constexpr u32 UMI_MM_BITS = 30;
 constexpr u32 UMI_NONE = 0xFFFFFFFFu;                         // a read's mm: its molecule has no other read
 constexpr u64 UMI_KEY_NONE = ECB_UMI_NONE;
-enum : u32 { UMI_R_FALLS = 1, UMI_R_JUMPS, UMI_R_FILTERED, UMI_R_LOCUS, UMI_R_HAP };
+enum : u32 { UMI_R_LOCUS = TUPLE_R_FILTERED + 1, UMI_R_HAP };      // (the tuple contract's reasons come first: tuple_reason)
+static_assert(UMI_R_LOCUS == 4 && UMI_R_HAP == 5, "the reason codes of a refusal do not move");
 static_assert(UMI_WG_RECS == (u32)TPB, "a launch of nblk(n, UMI_WG_RECS) workgroups of TPB threads is one element per thread");
 static_assert(MAX_LOCI <= 1u << UMI_LOC_BITS && UMI_MM_BITS + UMI_LOC_BITS + UMI_HAP_BITS <= 64, "a molecule's rank, a locus and a haplotype below 32 fit the key");
 // where the three parts of the key lie: fewer bits are fewer passes of the sort (config 4's 80 000 loci x 8 haplotypes: 20 bits below the rank, not 31)
@@ -42,12 +43,9 @@ struct UmiKey {
 
 const char* umi_reason(u32 r) {
     switch (r) {
-    case UMI_R_FALLS: return "read_id falls";
-    case UMI_R_JUMPS: return "read_id steps by more than 1";
-    case UMI_R_FILTERED: return "read_id steps on a record that does not pass the filter";
     case UMI_R_LOCUS: return "locus at or beyond n_loci";
     case UMI_R_HAP: return "haplotype at or beyond n_haps";
-    default: return "unknown";
+    default: return tuple_reason(r);
     }
 }
 // record i against the record before and against the targets; pass[i]; info[0] = 1 where a passing record carries the first id (that id is
@@ -55,13 +53,12 @@ const char* umi_reason(u32 r) {
 __global__ __launch_bounds__(TPB) void k_umi_check(const u32* rid, const u32* loc, const u32* hf, u64 n, u32 n_loci, u32 n_haps, u64* err, u64* info, u32* pass) {
     const u64 i = blockIdx.x * (u64)TPB + threadIdx.x;
     if (i >= n) return;
-    const u32 id = rid[i], f = hf[i], d = id - (i ? rid[i - 1] : id);
+    const u32 id = rid[i], f = hf[i];
     const bool ok = rec_valid(f);
-    if (d == 1u) { if (!ok) bus_err(err, i, UMI_R_FILTERED); }
-    else if (d != 0u) bus_err(err, i, d < 0x80000000u ? UMI_R_JUMPS : UMI_R_FALLS);
+    if (const u32 why = tuple_step(i ? rid[i - 1] : id, id, ok)) offender(err, i, why);
     if (ok) {
-        if (loc[i] >= n_loci) bus_err(err, i, UMI_R_LOCUS);
-        else if ((f >> ECB_HAP_SHIFT) >= n_haps) bus_err(err, i, UMI_R_HAP);
+        if (loc[i] >= n_loci) offender(err, i, UMI_R_LOCUS);
+        else if ((f >> ECB_HAP_SHIFT) >= n_haps) offender(err, i, UMI_R_HAP);
         if (id == rid[0]) info[0] = 1ull;                     // (every writer stores the same word)
     }
     pass[i] = ok;
@@ -187,16 +184,12 @@ int umi_check_args(const void* read_id, const void* locus, const void* hapflag, 
     if (!n_haps || n_haps > 31) return fail(nullptr, ECB_ERR_ARG, "umi: n_haps out of range (1 .. 31)");
     if (!n_loci || n_loci >= MAX_LOCI) return fail(nullptr, ECB_ERR_ARG, "umi: n_loci out of range (1 .. 2^26-3)");
     if (n >= (1ull << 30)) return fail(nullptr, ECB_ERR_LIMIT, "umi: 2^30 records or more");                   // (radix_sort_pairs64)
-    const uintptr_t ptrs[8] = {(uintptr_t)read_id, (uintptr_t)locus, (uintptr_t)hapflag, (uintptr_t)mol_key, (uintptr_t)out_read_id, (uintptr_t)out_locus,
-                               (uintptr_t)out_hapflag, (uintptr_t)out_first_read};
     // (a stream that holds other than n_reads reads is refused later; until then no byte of mol_key or out_first_read beyond n entries counts)
     const u64 nr = std::min<u64>(n_reads, n);
-    const u64 bytes[8] = {n * 4, n * 4, n * 4, nr * 8, n * 4, n * 4, n * 4, nr * 4};
-    for (int j = 0; j < 8; ++j) if (ptrs[j] & (j == 3 ? 7u : 3u)) return fail(nullptr, ECB_ERR_ARG, "umi: a pointer that is not aligned to its element");
-    for (int o = 4; o < 8; ++o)
-        for (int j = 0; j < o; ++j)
-            if (bytes[o] && bytes[j] && ptrs[j] < ptrs[o] + bytes[o] && ptrs[o] < ptrs[j] + bytes[j])
-                return fail(nullptr, ECB_ERR_ARG, "umi: an output overlaps an input or another output");
+    const std::vector<Span> spans = {{read_id, n * 4}, {locus, n * 4}, {hapflag, n * 4}, {mol_key, nr * 8}, {out_read_id, n * 4}, {out_locus, n * 4},
+                                     {out_hapflag, n * 4}, {out_first_read, nr * 4}};
+    for (size_t j = 0; j < spans.size(); ++j) if ((uintptr_t)spans[j].p & (j == 3 ? 7u : 3u)) return fail(nullptr, ECB_ERR_ARG, "umi: a pointer that is not aligned to its element");
+    if (span_clash(spans, 4)) return fail(nullptr, ECB_ERR_ARG, "umi: an output overlaps an input or another output");
     return ECB_OK;
 }
 }  // namespace
@@ -211,15 +204,11 @@ extern "C" int ecb_collapse_umis_device(int device, const void* d_read_id, const
     u32 *orid = (u32*)d_out_read_id, *oloc = (u32*)d_out_locus, *ohf = (u32*)d_out_hapflag;
     // [0] lowest (record << 8 | reason)  [1] the first id has a passing record  [2] first id | last id << 32  [3] the sort's word
     // [4] the record a read starts at  [5] ECB_UMI_NONE reads  [6 ..) scan totals
-    u64* words = c.get<u64>(CV_WORDS, 16);
+    u64* words;
+    RCCHK(c.status_words(words, 16, 1));
     // the sorts' buffers are the device's pool's; what outlives a sort is cut from one more pool buffer, sized from n alone (a stream holds
     // at most n reads, at most n / 2 molecules of several): eight arrays per record, twelve per read, three per k > 1 molecule, one scan's scratch
-    BusArena ar;
-    {
-        auto pad = BusArena::pad;
-        ar.cap = 20 * pad(n + 1, 4) + 3 * pad(n / 2 + 2, 4) + pad(scan_words(n + 1), 4);
-        ar.p = c.get<char>(CV_X0, ar.cap);
-    }
+    Arena ar(c, CV_X0, 20 * Arena::pad(n + 1, 4) + 3 * Arena::pad(n / 2 + 2, 4) + Arena::pad(scan_words(n + 1), 4));
     u64 *k0 = c.get<u64>(CV_KEYS0, n), *k1 = c.get<u64>(CV_KEYS1, n);
     u32 *v0 = c.get<u32>(CV_VALS0, n), *v1 = c.get<u32>(CV_VALS1, n);
     const SortScratch ss{c.get<u32>(CV_HIST, rs_words(n)), c.get<u32>(CV_OFFS, RS_AUX_WORDS), words + 3};
@@ -227,15 +216,12 @@ extern "C" int ecb_collapse_umis_device(int device, const void* d_read_id, const
     u32 *pass = ar.take<u32>(n), *ppos = ar.take<u32>(n + 1), *sums = ar.take<u32>(scan_words(n + 1));
     RCCHK(ar.missing(c));
     u64 back[16];
-    CALLCHK(c, hipMemsetAsync(words, 0, 16 * 8, st));
-    CALLCHK(c, hipMemsetAsync(words, 0xFF, 8, st));
     const unsigned grid_n = nblk(n, UMI_WG_RECS);
     // 1. the contract, the reads
     k_umi_check<<<grid_n, TPB, 0, st>>>(rid, loc, hf, n, n_loci, n_haps, words, words + 1, pass);
     CALLCHK(c, hipGetLastError());
     RCCHK(c.read_back(back, words, 3));
-    if (back[0] != BUS_NO_ERR)
-        return fail(nullptr, ECB_ERR_CONTRACT, "umi: record %llu: %s", (unsigned long long)(back[0] >> 8), umi_reason((u32)(back[0] & 255u)));
+    RCCHK(refuse_offender(back[0], "umi: record", umi_reason));
     const u32 id0 = (u32)back[2], id_last = (u32)(back[2] >> 32), lead = back[1] ? 0u : 1u;      // (lead: the first id is no read's)
     const u64 in_stream = (u64)(id_last - id0) + 1 - lead;
     if (in_stream != n_reads) {

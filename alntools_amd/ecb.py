@@ -66,10 +66,40 @@ class EcbError(RuntimeError):
         self.code = code
 
 
+class OffenderError(EcbError):
+    """A refusal that names the lowest offender: ``what`` it is (``"record"``, ``"line"`` ...), ``index`` its 0-based number (``record``:
+    the same).  The entry points' own errors derive from it."""
+
+    def __init__(self, code, msg, what, index):
+        EcbError.__init__(self, code, msg)
+        self.what, self.index = what, index
+
+    record = property(lambda self: self.index)
+
+
+class TupleContractError(OffenderError):
+    """A tuple stream refused: ``record`` is the lowest offending record (0-based)."""
+
+    def __init__(self, code, msg, record):
+        OffenderError.__init__(self, code, msg, "record", record)
+
+
 def _check(lib, rc, h=None):
     """Raise :class:`EcbError` for a non-zero return code of libecb, with the message of handle ``h`` (None: of the last call without one)."""
     if rc != 0:
         raise EcbError(rc, (lib.ecb_last_error(h) or b"").decode())
+
+
+def _check_offender(lib, rc, pattern, error):
+    """:func:`_check` for a call without a handle whose ``ECB_ERR_CONTRACT`` names a lowest offender: where the message matches the
+    compiled ``pattern``, ``error(rc, msg, *groups)`` is raised, the groups of digits as ints (``error``: an :class:`OffenderError`
+    class, or a function that picks one); everything else is an :class:`EcbError`."""
+    if rc != 0:
+        msg = (lib.ecb_last_error(None) or b"").decode()
+        m = pattern.match(msg) if rc == ECB_ERR_CONTRACT else None
+        if m is None:
+            raise EcbError(rc, msg)
+        raise error(rc, msg, *(int(g) if g.isdigit() else g for g in m.groups()))
 
 
 class Config(C.Structure):
@@ -174,6 +204,29 @@ SIGNATURES = (
 )
 
 _lib = None
+_tables = {}        # id of a signature table -> the library object its rows were last bound on
+
+
+def bind(signatures):
+    """:func:`load`'s library with the rows of ``signatures`` (a table like :data:`SIGNATURES`) bound on it, once per library object.
+    A symbol the library lacks fails here, unless the row is ``optional`` and ``ECB_LIB`` names the build."""
+    lib = load()
+    if _tables.get(id(signatures)) is not lib:
+        _bind(lib, signatures)
+    return lib
+
+
+def _bind(lib, signatures):
+    ab = "ECB_LIB" in os.environ        # (an A/B build named by hand, tools/: may be an older ABI; what it lacks is simply not bound)
+    for name, argtypes, restype, twin, optional in signatures:
+        for n in ((name + "_device", name) if twin else (name,)):
+            if optional and ab and not hasattr(lib, n):
+                continue
+            f = getattr(lib, n)             # (a normal build that lacks one fails here)
+            f.restype = restype
+            if argtypes is not None:
+                f.argtypes = argtypes
+    _tables[id(signatures)] = lib
 
 
 def load():
@@ -196,18 +249,10 @@ def load():
                           "(the HIP path has no fallback)" % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     lib.ecb_abi_version.restype = C.c_int
-    ab = "ECB_LIB" in os.environ        # (an A/B build named by hand, tools/: may be an older ABI; what it lacks is simply not bound)
-    if lib.ecb_abi_version() != ABI_VERSION and not ab:
+    if lib.ecb_abi_version() != ABI_VERSION and "ECB_LIB" not in os.environ:
         raise ImportError("%s has ABI %d, this binding is for ABI %d: rebuild it (python -m alntools_amd.build)"
                           % (LIB_PATH, lib.ecb_abi_version(), ABI_VERSION))
-    for name, argtypes, restype, twin, optional in SIGNATURES:
-        for n in ((name + "_device", name) if twin else (name,)):
-            if optional and ab and not hasattr(lib, n):
-                continue
-            f = getattr(lib, n)             # (a normal build that lacks one fails here)
-            f.restype = restype
-            if argtypes is not None:
-                f.argtypes = argtypes
+    _bind(lib, SIGNATURES)
     _lib = lib
     return lib
 
@@ -242,7 +287,7 @@ class _Numpy(object):
     """What a one-call wrapper asks of the arrays it was handed -- numpy arrays here: the host entry points, on the device the caller
     numbers.  :func:`_kind` picks this or :class:`_Torch` once per call; the wrapper then has one body for both."""
     tensors = False
-    i32, i64, u32, f64, u8 = np.int32, np.int64, np.uint32, np.float64, np.uint8
+    i32, i64, u32, u64, f64, u8 = np.int32, np.int64, np.uint32, np.uint64, np.float64, np.uint8
     ptr = staticmethod(_ptr)
 
     def __init__(self, device):
@@ -254,6 +299,10 @@ class _Numpy(object):
     def arr(self, a, dt):
         """``a`` as a contiguous array of type ``dt``, of this kind and on this device (None stays None)."""
         return None if a is None else np.ascontiguousarray(a, dtype=dt)
+
+    def words(self, a, bits=32):
+        """Unsigned words of ``bits`` bits as this kind carries them: a contiguous uint32 / uint64 array (None stays None)."""
+        return self.arr(a, self.u32 if bits == 32 else self.u64)
 
     def flags(self, a):
         """uint8 0 / 1, flat, of anything truthy (None stays None)."""
@@ -278,7 +327,7 @@ class _Torch(_Numpy):
         import torch
         self.torch, self.dev, self.device = torch, dev, dev.index or 0
         self.i32, self.i64, self.f64, self.u8 = torch.int32, torch.int64, torch.float64, torch.uint8
-        self.u32 = torch.int32                  # (torch computes with no uint32: int32 holds the same bytes)
+        self.u32, self.u64 = torch.int32, torch.int64      # (torch computes with no unsigned words: the signed ones hold the same bytes)
 
     def entry(self, lib, name):
         return getattr(lib, name + "_device")
@@ -287,6 +336,12 @@ class _Torch(_Numpy):
         if a is None:
             return None
         return (a if isinstance(a, self.torch.Tensor) else self.torch.as_tensor(a)).to(self.dev, dt).contiguous()
+
+    def words(self, a, bits=32):
+        """... an int32 / int64 tensor holding the same bytes; what is no tensor yet gets there by a view of the unsigned numpy array."""
+        if a is not None and not hasattr(a, "data_ptr"):
+            a = np.ascontiguousarray(a, dtype=_Numpy.u32 if bits == 32 else _Numpy.u64).view(_Numpy.i32 if bits == 32 else _Numpy.i64)
+        return self.arr(a, self.u32 if bits == 32 else self.u64)
 
     def flags(self, a):
         return None if a is None else self.torch.as_tensor(a).to(device=self.dev).ne(0).to(self.torch.uint8).contiguous().reshape(-1)
@@ -698,12 +753,17 @@ SALMON_REASONS = {1: "a byte other than a digit, tab or line end", 2: "an empty 
                   7: "a target id repeated within the line", 8: "the number of EC lines differs from the header's"}
 
 
-class SalmonFormatError(EcbError):
+class SalmonFormatError(OffenderError):
     """``ecb_salmon_ecs`` refused the EC section: ``line`` is the lowest offending EC line (0-based), ``reason`` its code."""
 
     def __init__(self, code, msg, line, reason):
-        EcbError.__init__(self, code, msg)
-        self.line, self.reason = line, reason
+        OffenderError.__init__(self, code, msg, "EC line", line)
+        self.reason = reason
+
+    line = property(lambda self: self.index)
+
+
+_SALMON_REFUSAL = re.compile(r"EC line (\d+): .* \(reason (\d+)\)$")
 
 
 def salmon_ecs(text, n_ecs, target_col, target_hap, n_loci, n_haps, device=0):
@@ -725,13 +785,8 @@ def salmon_ecs(text, n_ecs, target_col, target_hap, n_loci, n_haps, device=0):
         raise ValueError("target_col and target_hap differ in length")
     out = [k.empty(n, k.i32) for n in (n_ecs + 1, max(cap, 1), max(cap, 1), max(n_ecs, 1), max(n_ecs, 1))]
     sizes = (C.c_uint64 * 2)()
-    rc = k.entry(lib, "ecb_salmon_ecs")(k.device, p(t), len(t), n_ecs, len(tc), p(tc), p(th), n_loci, n_haps, cap, *[p(o) for o in out], sizes)
-    if rc != 0:
-        msg = (lib.ecb_last_error(None) or b"").decode()
-        m = re.match(r"EC line (\d+): .* \(reason (\d+)\)$", msg)
-        if rc == ECB_ERR_CONTRACT and m:
-            raise SalmonFormatError(rc, msg, int(m.group(1)), int(m.group(2)))
-        raise EcbError(rc, msg)
+    _check_offender(lib, k.entry(lib, "ecb_salmon_ecs")(k.device, p(t), len(t), n_ecs, len(tc), p(tc), p(th), n_loci, n_haps, cap, *[p(o) for o in out], sizes),
+                    _SALMON_REFUSAL, SalmonFormatError)
     nnz, nnz_n = int(sizes[0]), int(sizes[1])
     return out[0], out[1][:nnz], out[2][:nnz], out[3][:nnz_n], out[4][:nnz_n]
 

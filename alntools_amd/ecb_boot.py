@@ -17,20 +17,9 @@ BOOT_SIGNATURES = (
     _sig("ecb_quantify_bootstrap", _A_N + [_i64, _vp, _u32, _dbl, _u64, _u32, _vp, _u32, _u64, _u32] + [_vp] * 9, twin=True),
 )
 
-_bound = None
-
-
 def load():
     """:func:`alntools_amd.ecb.load`'s library with this module's entry points bound (a library that lacks one fails here)."""
-    global _bound
-    lib = ecb.load()
-    if _bound is not lib:
-        for name, argtypes, restype, twin, _optional in BOOT_SIGNATURES:
-            for n in ((name + "_device", name) if twin else (name,)):
-                f = getattr(lib, n)
-                f.restype, f.argtypes = restype, argtypes
-        _bound = lib
-    return lib
+    return ecb.bind(BOOT_SIGNATURES)
 
 
 def resample(n_ecs, indptr_n, indices_n, data_n, sample=None, seed=0, b0=0, n_reps=1, device=0):

@@ -24,28 +24,16 @@ NO_UMI = 1                 # include/ecb_bus.h: ECB_BUS_NO_UMI
 MAX_UMILEN = 16            # include/ecb_bus.h: ECB_BUS_MAX_UMILEN
 RECORD_BYTES = 32
 
-_bound = None
+_REFUSAL = re.compile(r"bus: (?:matrix\.ec )?(record|line) (\d+): ")
 
 
-class BusFormatError(ecb.EcbError):
+class BusFormatError(ecb.OffenderError):
     """``ecb_bus_molecules`` refused its input: ``what`` is ``"record"`` or ``"line"``, ``index`` the lowest offender (0-based)."""
-
-    def __init__(self, code, msg, what, index):
-        ecb.EcbError.__init__(self, code, msg)
-        self.what, self.index = what, index
 
 
 def load():
     """:func:`alntools_amd.ecb.load`'s library with this module's entry points bound (a library that lacks one fails here)."""
-    global _bound
-    lib = ecb.load()
-    if _bound is not lib:
-        for name, argtypes, restype, twin, _optional in BUS_SIGNATURES:
-            for n in ((name + "_device", name) if twin else (name,)):
-                f = getattr(lib, n)
-                f.restype, f.argtypes = restype, argtypes
-        _bound = lib
-    return lib
+    return ecb.bind(BUS_SIGNATURES)
 
 
 def a_capacity(records, ec_ptr):
@@ -75,14 +63,11 @@ def molecules(records, bclen, umilen, ec_ptr, ec_targets, target_col, target_hap
     if len(rec) % RECORD_BYTES:
         raise ValueError("the records are %d bytes: not a multiple of %d" % (len(rec), RECORD_BYTES))
     n = len(rec) // RECORD_BYTES
-    u64 = k.i64 if k.tensors else np.uint64
     if k.tensors:                                    # what differs: a tensor is made of the ids as int64 (torch takes no uint32 array everywhere)
         ec_ptr, ec_targets, target_col, target_hap = (a if hasattr(a, "data_ptr") else np.asarray(a, dtype=np.int64)
                                                       for a in (ec_ptr, ec_targets, target_col, target_hap))
-        if keep is not None and not hasattr(keep, "data_ptr"):
-            keep = np.asarray(keep, dtype=np.uint64).view(np.int64)
     ptr, ids, tc, th = (k.arr(a, k.u32) for a in (ec_ptr, ec_targets, target_col, target_hap))
-    kp = k.arr(keep, u64)
+    kp = k.words(keep, 64)
     if len(tc) != len(th):
         raise ValueError("target_col and target_hap differ in length")
     if capacities is None:
@@ -90,18 +75,13 @@ def molecules(records, bclen, umilen, ec_ptr, ec_targets, target_col, target_hap
         host_rec = rec.cpu().numpy() if k.tensors else rec
         capacities = (n if kp is None else min(n, len(kp)), n, min(a_capacity(host_rec, host_ptr.view(np.uint32)), (1 << 31) - 1), n)
     cc, cr, ca, cn = (int(x) for x in capacities)
-    out = [k.empty(max(cc, 1), u64), k.empty(cr + 1, k.i32), k.empty(max(ca, 1), k.i32), k.empty(max(ca, 1), k.i32), k.empty(cc + 1, k.i32),
+    out = [k.empty(max(cc, 1), k.u64), k.empty(cr + 1, k.i32), k.empty(max(ca, 1), k.i32), k.empty(max(ca, 1), k.i32), k.empty(cc + 1, k.i32),
            k.empty(max(cn, 1), k.i32), k.empty(max(cn, 1), k.i32), k.empty(max(cr, 1), k.i32)]
     sizes = (C.c_uint64 * 8)()
     rc = k.entry(lib, "ecb_bus_molecules")(k.device, p(rec), n, int(bclen), int(umilen), NO_UMI if no_umi else 0, len(ptr) - 1, len(ids), p(ptr), p(ids),
                                            len(tc), p(tc), p(th), int(n_loci), int(n_haps), p(kp), 0 if kp is None else len(kp), cc, cr, ca, cn,
                                            *([p(o) for o in out] + [sizes]))
-    if rc != 0:
-        msg = (lib.ecb_last_error(None) or b"").decode()
-        m = re.match(r"bus: (?:matrix\.ec )?(record|line) (\d+): ", msg)
-        if rc == ecb.ECB_ERR_CONTRACT and m:
-            raise BusFormatError(rc, msg, m.group(1), int(m.group(2)))
-        raise ecb.EcbError(rc, msg)
+    ecb._check_offender(lib, rc, _REFUSAL, BusFormatError)
     cells, rows, nnz_a, nnz_n = (int(x) for x in sizes[:4])
     return (out[0][:cells], (out[1][:rows + 1], out[2][:nnz_a], out[3][:nnz_a]), (out[4][:cells + 1], out[5][:nnz_n], out[6][:nnz_n]), out[7][:rows],
             tuple(int(x) for x in sizes))

@@ -8,8 +8,6 @@ from __future__ import annotations
 import ctypes as C
 import re
 
-import numpy as np
-
 from . import ecb
 from .ecb import _P, _int, _kind, _sig, _u32, _u64, _vp
 from .ecb_bus import RECORD_BYTES, BusFormatError
@@ -23,24 +21,20 @@ BUS_CORRECT_SIGNATURES = (
 
 EXACT, CORRECTED, NO_CANDIDATE, AMBIGUOUS = 0, 1, 2, 3      # include/ecb_bus_correct.h: ECB_BUS_EXACT ..., and the order of the sizes
 
-_bound = None
+_REFUSAL = re.compile(r"bus: (record|whitelist entry) (\d+): ")
 
 
 class WhitelistFormatError(BusFormatError):
     """``ecb_bus_correct`` refused its whitelist: ``what`` is ``"whitelist entry"``, ``index`` the lowest offending entry (0-based)."""
 
 
+def _refusal(code, msg, what, index):
+    return (BusFormatError if what == "record" else WhitelistFormatError)(code, msg, what, index)
+
+
 def load():
     """:func:`alntools_amd.ecb.load`'s library with this module's entry points bound (a library that lacks one fails here)."""
-    global _bound
-    lib = ecb.load()
-    if _bound is not lib:
-        for name, argtypes, restype, twin, _optional in BUS_CORRECT_SIGNATURES:
-            for n in ((name + "_device", name) if twin else (name,)):
-                f = getattr(lib, n)
-                f.restype, f.argtypes = restype, argtypes
-        _bound = lib
-    return lib
+    return ecb.bind(BUS_CORRECT_SIGNATURES)
 
 
 def correct(records, bclen, whitelist, want_status=False, capacity=None, device=0):
@@ -58,20 +52,13 @@ def correct(records, bclen, whitelist, want_status=False, capacity=None, device=
     if len(rec) % RECORD_BYTES:
         raise ValueError("the records are %d bytes: not a multiple of %d" % (len(rec), RECORD_BYTES))
     n = len(rec) // RECORD_BYTES
-    if k.tensors and not hasattr(whitelist, "data_ptr"):         # (torch takes no uint64 array everywhere: int64 holds the same bytes)
-        whitelist = np.asarray(whitelist, dtype=np.uint64).view(np.int64)
-    wl = k.arr(whitelist, k.i64 if k.tensors else np.uint64)
+    wl = k.words(whitelist, 64)
     cap = n if capacity is None else int(capacity)
     out = k.empty(max(cap, 1) * RECORD_BYTES, k.u8)
     status = k.empty(max(n, 1), k.u8) if want_status else None
     sizes = (C.c_uint64 * 4)()
     rc = k.entry(lib, "ecb_bus_correct")(k.device, p(rec), n, int(bclen), p(wl), len(wl), cap, p(out), p(status), sizes)
-    if rc != 0:
-        msg = (lib.ecb_last_error(None) or b"").decode()
-        m = re.match(r"bus: (record|whitelist entry) (\d+): ", msg)
-        if rc == ecb.ECB_ERR_CONTRACT and m:
-            raise (BusFormatError if m.group(1) == "record" else WhitelistFormatError)(rc, msg, m.group(1), int(m.group(2)))
-        raise ecb.EcbError(rc, msg)
+    ecb._check_offender(lib, rc, _REFUSAL, _refusal)
     sizes = tuple(int(x) for x in sizes)
     n_out = sizes[0] + sizes[1]
     return out[:n_out * RECORD_BYTES].reshape(n_out, RECORD_BYTES), (None if status is None else status[:n]), sizes

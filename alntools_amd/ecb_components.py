@@ -16,20 +16,9 @@ COMPONENTS_SIGNATURES = (
     _sig("ecb_components", _A_N + [_i64, _i64] + [_vp] * 5 + [_P(_u64)], twin=True),
 )
 
-_bound = None
-
-
 def load():
     """:func:`alntools_amd.ecb.load`'s library with this module's entry points bound (a library that lacks one fails here)."""
-    global _bound
-    lib = ecb.load()
-    if _bound is not lib:
-        for name, argtypes, restype, twin, _optional in COMPONENTS_SIGNATURES:
-            for n in ((name + "_device", name) if twin else (name,)):
-                f = getattr(lib, n)
-                f.restype, f.argtypes = restype, argtypes
-        _bound = lib
-    return lib
+    return ecb.bind(COMPONENTS_SIGNATURES)
 
 
 def components(indptr, indices, data, n_loci, n_haps, indptr_n, indices_n, data_n, sample=None, min_count=1, device=0):

@@ -28,15 +28,11 @@ LOWEST, HIGHEST = 0, 1             # ECB_STRATA_LOWEST, ECB_STRATA_HIGHEST
 TAGS = {"NM": ("NM", None, True), "XM": ("XM", None, True), "nM": ("nM", None, True), "AS": ("AS", None, False),
         "AS+YS": ("AS", "YS", False)}
 
-_bound = None
+_REFUSAL = re.compile(r"strata: record (\d+): ")
 
 
-class StrataContractError(ecb.EcbError):
+class StrataContractError(ecb.TupleContractError):
     """``ecb_best_strata`` refused its stream: ``record`` is the lowest offending record (0-based)."""
-
-    def __init__(self, code, msg, record):
-        ecb.EcbError.__init__(self, code, msg)
-        self.record = record
 
 
 def parse_tag(tag):
@@ -59,15 +55,7 @@ def cut_whole_reads(read_id, final=False):
 
 def load():
     """:func:`alntools_amd.ecb.load`'s library with this module's entry points bound (a library that lacks one fails here)."""
-    global _bound
-    lib = ecb.load()
-    if _bound is not lib:
-        for name, argtypes, restype, twin, _optional in STRATA_SIGNATURES:
-            for n in ((name + "_device", name) if twin else (name,)):
-                f = getattr(lib, n)
-                f.restype, f.argtypes = restype, argtypes
-        _bound = lib
-    return lib
+    return ecb.bind(STRATA_SIGNATURES)
 
 
 def best_strata(read_id, hapflag, score, lowest=True, device=0, inplace=False):
@@ -81,12 +69,7 @@ def best_strata(read_id, hapflag, score, lowest=True, device=0, inplace=False):
     lib = load()
     k = _kind(read_id, device)
     p = k.ptr
-
-    def words(a, dt):
-        if k.tensors and not hasattr(a, "data_ptr"):             # (torch computes with no uint32: int32 holds the same bytes)
-            a = np.ascontiguousarray(a, dtype=dt).view(np.int32)
-        return k.arr(a, k.i32 if k.tensors else dt)
-    rid, hf, sc = words(read_id, np.uint32), words(hapflag, np.uint32), words(score, np.int32)
+    rid, hf, sc = k.words(read_id), k.words(hapflag), k.arr(score, k.i32)
     n = len(rid)
     if len(hf) != n or len(sc) != n:
         raise ValueError("read_id, hapflag and score hold %d, %d and %d records" % (n, len(hf), len(sc)))
@@ -98,10 +81,5 @@ def best_strata(read_id, hapflag, score, lowest=True, device=0, inplace=False):
         out_rid, out_hf = k.empty(max(n, 1), k.u32), k.empty(max(n, 1), k.u32)
     counts = (C.c_uint64 * 4)()
     rc = k.entry(lib, "ecb_best_strata")(k.device, p(rid), p(hf), p(sc), n, LOWEST if lowest else HIGHEST, p(out_rid), p(out_hf), counts)
-    if rc != 0:
-        msg = (lib.ecb_last_error(None) or b"").decode()
-        m = re.match(r"strata: record (\d+): ", msg)
-        if rc == ecb.ECB_ERR_CONTRACT and m:
-            raise StrataContractError(rc, msg, int(m.group(1)))
-        raise ecb.EcbError(rc, msg)
+    ecb._check_offender(lib, rc, _REFUSAL, StrataContractError)
     return out_rid, out_hf, tuple(int(x) for x in counts)            # (n = 0 is refused: the outputs hold n records)

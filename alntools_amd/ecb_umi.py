@@ -28,15 +28,11 @@ MAX_RECORDS = (1 << 30) - 1        # include/ecb_umi.h: n < 2^30
 COUNT_NAMES = ("reads in", "molecules", "molecules of several reads", "molecules discarded", "records out", "reads without a UMI")
 
 _CODE = {"A": 0, "C": 1, "G": 2, "T": 3}
-_bound = None
+_REFUSAL = re.compile(r"umi: record (\d+): ")
 
 
-class UmiContractError(ecb.EcbError):
+class UmiContractError(ecb.TupleContractError):
     """``ecb_collapse_umis`` refused its stream: ``record`` is the lowest offending record (0-based)."""
-
-    def __init__(self, code, msg, record):
-        ecb.EcbError.__init__(self, code, msg)
-        self.record = record
 
 
 def pack_umi(text):
@@ -74,15 +70,7 @@ def mol_keys(cell_ids, umis):
 
 def load():
     """:func:`alntools_amd.ecb.load`'s library with this module's entry points bound (a library that lacks one fails here)."""
-    global _bound
-    lib = ecb.load()
-    if _bound is not lib:
-        for name, argtypes, restype, twin, _optional in UMI_SIGNATURES:
-            for n in ((name + "_device", name) if twin else (name,)):
-                f = getattr(lib, n)
-                f.restype, f.argtypes = restype, argtypes
-        _bound = lib
-    return lib
+    return ecb.bind(UMI_SIGNATURES)
 
 
 def collapse_umis(read_id, locus, hapflag, mol_key, n_loci, n_haps, device=0):
@@ -96,28 +84,18 @@ def collapse_umis(read_id, locus, hapflag, mol_key, n_loci, n_haps, device=0):
     lib = load()
     k = _kind(read_id, device)
     p = k.ptr
-
-    def words(a, dt, tdt):
-        if k.tensors and not hasattr(a, "data_ptr"):             # (torch computes with no unsigned words: the signed ones hold the same bytes)
-            a = np.ascontiguousarray(a, dtype=dt).view(np.int32 if dt == np.uint32 else np.int64)
-        return k.arr(a, tdt if k.tensors else dt)
-    rid, loc, hf = (words(a, np.uint32, k.i32) for a in (read_id, locus, hapflag))
-    key = words(mol_key, np.uint64, k.i64)
+    rid, loc, hf = (k.words(a) for a in (read_id, locus, hapflag))
+    key = k.words(mol_key, 64)
     n, n_reads = len(rid), len(key)
     if len(loc) != n or len(hf) != n:
         raise ValueError("read_id, locus and hapflag hold %d, %d and %d records" % (n, len(loc), len(hf)))
     if not n_reads:
-        key = k.empty(1, k.i64 if k.tensors else np.uint64)      # (a stream of no read: still a pointer)
+        key = k.empty(1, k.u64)                                  # (a stream of no read: still a pointer)
     out = [k.empty(max(n, 1), k.u32) for _ in range(3)]
     first = k.empty(max(n_reads, 1), k.u32)
     counts = (C.c_uint64 * 6)()
     rc = k.entry(lib, "ecb_collapse_umis")(k.device, p(rid), p(loc), p(hf), p(key), n, n_reads, n_loci, n_haps, p(out[0]), p(out[1]), p(out[2]),
                                            p(first), counts)
-    if rc != 0:
-        msg = (lib.ecb_last_error(None) or b"").decode()
-        m = re.match(r"umi: record (\d+): ", msg)
-        if rc == ecb.ECB_ERR_CONTRACT and m:
-            raise UmiContractError(rc, msg, int(m.group(1)))
-        raise ecb.EcbError(rc, msg)
+    ecb._check_offender(lib, rc, _REFUSAL, UmiContractError)
     c = tuple(int(x) for x in counts)
     return out[0][:c[4]], out[1][:c[4]], out[2][:c[4]], first[:c[1] - c[3]], c

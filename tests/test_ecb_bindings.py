@@ -198,3 +198,86 @@ def test_every_wrapper_reaches_its_own_symbol_with_the_tables_number_of_argument
     for wrapper, symbols in REACHES.items():
         assert REACHES[wrapper][0] + suffix in reached[wrapper], wrapper
         assert reached[wrapper] <= {s + suffix for s in symbols}
+
+
+MODULES = {"ecb_boot": "BOOT", "ecb_components": "COMPONENTS", "ecb_bus": "BUS", "ecb_bus_correct": "BUS_CORRECT", "ecb_strata": "STRATA", "ecb_umi": "UMI"}
+
+
+class Counting(object):
+    """A library of every symbol: what was bound on it, and how often."""
+
+    def __init__(self):
+        self.funcs, self.sets = {}, 0
+
+    def __getattr__(self, name):
+        if not name.startswith("ecb_"):
+            raise AttributeError(name)
+        lib = self
+
+        class Func(object):
+            def __setattr__(self, key, value):
+                lib.sets += 1
+                object.__setattr__(self, key, value)
+        return self.funcs.setdefault(name, Func())
+
+
+@pytest.mark.parametrize("module", sorted(MODULES))
+def test_a_modules_entry_points_are_bound_by_its_first_bind_and_not_again(monkeypatch, module):
+    mod = __import__("alntools_amd." + module, fromlist=[module])
+    table, symbols = getattr(mod, MODULES[module] + "_SIGNATURES"), getattr(mod, MODULES[module] + "_SYMBOLS")
+    lib = Counting()
+    monkeypatch.setattr(ecb, "_lib", lib)
+    assert mod.load() is lib and ecb.bind(table) is lib
+    rows = {n: row for row in table for n in ((row[0], row[0] + "_device") if row[3] else (row[0],))}
+    assert sorted(rows) == sorted(symbols) == sorted(lib.funcs)
+    for n, (_, argtypes, restype, _, _) in rows.items():
+        assert lib.funcs[n].argtypes == argtypes and lib.funcs[n].restype == restype
+    assert lib.sets == 2 * len(symbols)                    # (restype and argtypes of each, once: the second call bound nothing)
+    other = Counting()                                     # another library object: bound again, on that one
+    monkeypatch.setattr(ecb, "_lib", other)
+    assert mod.load() is other and sorted(other.funcs) == sorted(symbols) and other.sets == 2 * len(symbols) and lib.sets == 2 * len(symbols)
+
+
+def test_the_refusals_that_name_an_offender_keep_their_names_attributes_and_bases():
+    from alntools_amd import ecb_bus, ecb_bus_correct, ecb_strata, ecb_umi
+    for cls in (ecb_strata.StrataContractError, ecb_umi.UmiContractError):
+        e = cls(-5, "x: record 3: y", 3)
+        assert (e.record, e.index, e.what, e.code) == (3, 3, "record", -5) and isinstance(e, ecb.OffenderError) and isinstance(e, ecb.EcbError)
+    assert not issubclass(ecb_strata.StrataContractError, ecb_umi.UmiContractError) and not issubclass(ecb_umi.UmiContractError, ecb_strata.StrataContractError)
+    e = ecb_bus.BusFormatError(-5, "bus: matrix.ec line 7: y", "line", 7)
+    assert (e.what, e.index, e.record, e.code) == ("line", 7, 7, -5) and isinstance(e, ecb.EcbError)
+    w = ecb_bus_correct.WhitelistFormatError(-5, "bus: whitelist entry 2: y", "whitelist entry", 2)
+    assert (w.what, w.index) == ("whitelist entry", 2) and isinstance(w, ecb_bus.BusFormatError) and ecb_bus_correct.BusFormatError is ecb_bus.BusFormatError
+    s = ecb.SalmonFormatError(-5, "EC line 4: an empty field (reason 2)", 4, 2)
+    assert (s.line, s.reason, s.index, s.code) == (4, 2, 4, -5) and isinstance(s, ecb.EcbError)
+    assert "libecb error -5: EC line 4" in str(s)
+
+
+@pytest.mark.parametrize("rc, text, raised, attrs", [
+    (-5, b"strata: record 12: read_id falls", "ecb_strata.StrataContractError", {"record": 12}),
+    (-5, b"umi: record 0: locus at or beyond n_loci", "ecb_umi.UmiContractError", {"record": 0}),
+    (-5, b"bus: matrix.ec line 3: x", "ecb_bus.BusFormatError", {"what": "line", "index": 3}),
+    (-5, b"bus: record 9: x", "ecb_bus.BusFormatError", {"what": "record", "index": 9}),
+    (-5, b"bus: whitelist entry 5: x", "ecb_bus_correct.WhitelistFormatError", {"what": "whitelist entry", "index": 5}),
+    (-5, b"EC line 8: an empty field (reason 2)", "ecb.SalmonFormatError", {"line": 8, "reason": 2}),
+    (-5, b"bus: the barcodes to keep are not strictly ascending", "ecb.EcbError", {"code": -5}),
+    (-1, b"strata: record 12: read_id falls", "ecb.EcbError", {"code": -1}),
+])
+def test_a_refusal_raises_the_class_its_text_names(rc, text, raised, attrs):
+    import alntools_amd
+    from alntools_amd import ecb_bus, ecb_bus_correct, ecb_strata, ecb_umi  # noqa: F401
+    pattern, error = {b"st": (ecb_strata._REFUSAL, ecb_strata.StrataContractError), b"um": (ecb_umi._REFUSAL, ecb_umi.UmiContractError),
+                      b"EC": (ecb._SALMON_REFUSAL, ecb.SalmonFormatError),
+                      b"bu": (ecb_bus_correct._REFUSAL, ecb_bus_correct._refusal) if b"whitelist" in text or b"record 9" in text
+                      else (ecb_bus._REFUSAL, ecb_bus.BusFormatError)}[text[:2]]
+
+    class Lib(object):
+        @staticmethod
+        def ecb_last_error(h):
+            return text
+    module, name = raised.split(".")
+    cls = getattr(getattr(alntools_amd, module), name)
+    with pytest.raises(cls) as info:
+        ecb._check_offender(Lib, rc, pattern, error)
+    assert type(info.value) is cls and all(getattr(info.value, a) == v for a, v in attrs.items()) and text.decode() in str(info.value)
+    ecb._check_offender(Lib, 0, pattern, error)            # (no refusal: nothing raised)

@@ -44,8 +44,20 @@ def test_the_spans_are_what_the_launches_use_and_there_is_one_path():
 
 def test_no_index_comes_from_a_read_id_and_nothing_is_placed_by_an_atomic():
     src = re.sub(r"//.*", "", _source("strata.inc"))
-    assert set(re.findall(r"atomic\w+\(", src)) == {"atomicMin(", "atomicAdd("}
+    atomics = re.findall(r"atomic\w+\(", src)
+    assert atomics.count("atomicMin(") == 4 and len(atomics) == 5   # the crossing reads' words and first passing records to their slots, and ...
     assert src.count("atomicAdd(") == 1 and "k_strata_sum" in src   # the four counts: integers, added up per 16 x 256 waves, never per wave of records
     # the only places a slot is named: by the wave's own number, or by a record's position (strata_read_start) over the span
     assert re.findall(r"\b[ht]s = \(u32\)([^;]+);", src) == ["(strata_read_start(rid, rid[0], base, a.rel[0]) / STRATA_WAVE_RECS)", "w"]
-    assert src.count("bus_err(err, i + q, ") == 2                    # the lowest offender: three reasons, two call sites
+    # the lowest offender: the three reasons are the shared step rule's, one call of it, its verdict to the shared word
+    assert src.count("tuple_step(prev, a.id[q], a.pass[q])") == src.count("tuple_step(") == 1
+    assert src.count("if (why) offender(err, i + q, why);") == src.count("offender(") - src.count("refuse_offender(") == 1
+
+
+def test_the_lowest_offender_and_the_step_rule_are_defined_once_in_the_tree():
+    tree = "".join(_source(f) for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".inc", ".h")))
+    assert len(re.findall(r"\bvoid offender\(", tree)) == 1 and len(re.findall(r"\bu32 tuple_step\(", tree)) == 1
+    assert len(re.findall(r"atomicMin\([^;]*<< 8 \| reason", tree)) == 1
+    assert len(re.findall(r"\bconst char\* tuple_reason\(", tree)) == 1 and len(re.findall(r"TUPLE_R_FALLS = 1, TUPLE_R_JUMPS, TUPLE_R_FILTERED", tree)) == 1
+    for text in ("read_id falls", "read_id steps by more than 1", "read_id steps on a record that does not pass the filter"):
+        assert tree.count('"%s"' % text) == 1, text

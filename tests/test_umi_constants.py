@@ -57,8 +57,10 @@ def test_one_path_whatever_the_size_and_nothing_placed_by_an_atomic():
     assert [g for g, tpb in launches if tpb == "64"] == ["1"]
     assert all(g.startswith("grid_") or g == "nblk(n_runs, UMI_WG_RECS)" for g, tpb in launches if tpb == "TPB")
     assert set(re.findall(r"= nblk\((\w+), UMI_WG_RECS\);", src)) == {"n", "R", "m", "n_runs"}
-    # the only atomic is the lowest offender's minimum (bus_err), read by refusals alone; no float atomics; one sort implementation
-    assert re.findall(r"atomic\w+\(", src) == [] and src.count("bus_err(err, i, ") == 4
+    # the only atomic is the lowest offender's minimum (ecb.hip's offender), read by refusals alone; no float atomics; one sort implementation
+    assert re.findall(r"atomic\w+\(", src) == [] and src.count("offender(err, i, ") == src.count("offender(") - src.count("refuse_offender(") == 3
+    assert src.count("tuple_step(i ? rid[i - 1] : id, id, ok)") == src.count("tuple_step(") == 1       # the step rule's three reasons; locus; haplotype
+    assert "UMI_R_LOCUS == 4 && UMI_R_HAP == 5" in src and "default: return tuple_reason(r);" in src
     assert src.count("radix_sort_pairs64(") == 2 and "k_rs_" not in src and "hipMalloc" not in src
     # the second sort is behind the test for a molecule of several reads
     assert src.index("if (n_multi) {") < src.index("radix_sort_pairs64(st, s2")
