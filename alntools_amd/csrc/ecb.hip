@@ -282,6 +282,16 @@ __device__ __forceinline__ void ranked_pairs_wave(const Slot& s, const uint2* ar
         __builtin_amdgcn_wave_barrier();
     }
 }
+// -DECB_TIMING: what the waves of a launch did to each other OUTSIDE k_stream's flush (which counts its own, k_stream.inc) -- in k_slow and
+// k_merge, the callers of table_lookup: claims lost to another hash [0] and to a founder with the same hash [1], lookups settled on a slot
+// that carries their hash (table_settle in k_merge; same_key in k_slow, which compares every such slot) [2], and those of them that ended on
+// the other key of the hash [3].  One device-wide word each, read and zeroed by ecb_timing_race (tools/racing_founders.py).
+#ifdef ECB_TIMING
+__device__ u64 g_race[4];
+#define RACE(i) atomicAdd(&g_race[i], 1ull)
+#else
+#define RACE(i) do { } while (0)
+#endif
 template <class Cmp>
 __device__ __forceinline__ int table_lookup(Slot* table, u64 cap_mask, u64 lo, u64& j, u32& probes, const Cmp& cmp, u32 abl = 0u, u32* first_inv_seen = nullptr) {
     for (; probes < MAX_PROBE; ++probes, j = (j + 1) & cap_mask) {
@@ -294,7 +304,8 @@ __device__ __forceinline__ int table_lookup(Slot* table, u64 cap_mask, u64 lo, u
         if (clo == 0ull) {
             clo = atomicCAS(&s->lo, 0ull, lo);
             if (clo == 0ull) return ST_CREATED;
-            if (clo == lo) return ST_PENDING;                     // claimed with our hash a moment ago: its key decides
+            if (clo == lo) { RACE(1); return ST_PENDING; }        // claimed with our hash a moment ago: its key decides
+            RACE(0);
             continue;
         }
         if (clo != lo) continue;
@@ -417,6 +428,7 @@ struct TileRegs { u32 rr[RPL], ll[RPL], hh[RPL]; };
 // -DECB_TIMING: profiling build.  Every wave adds up the shader clocks it spends in each phase of a tile (stalls are
 // charged to the phase whose s_waitcnt sits them out); k_stream adds them into StreamArgs::timing[8].
 #ifdef ECB_TIMING
+#define ECB_TIMING_WORDS 20          // 0 - 6 clocks per phase | 7 probe-on tiles | 8 - 14 table trips per lookup | 15 - 18 lost claims and settles | 19 spare
 #define TICK(i) do { const u64 t_ = __builtin_readcyclecounter(); tacc[i] += t_ - tlast; tlast = t_; } while (0)
 #else
 #define TICK(i) do { } while (0)
@@ -1006,6 +1018,8 @@ __device__ __forceinline__ void slow_body(const SlowArgs& A, u32* key, u32* msk,
                 const int r = same_key();
                 __syncthreads();
                 if (tid == 0) {
+                    RACE(2);
+                    if (r == CMP_DIFFERENT) RACE(3);
                     if (r == CMP_EQUAL) { s_st = ST_HIT; A.read_slot[r0] = (u32)s_j; atomicMax(&A.table[s_j].first_inv, ~r0); }
                     else if (r == CMP_INCOMPLETE) { s_st = ST_NONE; atomicOr(&A.ctr->err, ERR_INTERNAL); }
                     else { s_j = (s_j + 1) & A.cap_mask; s_probes += 1; if (s_probes >= MAX_PROBE) { s_st = ST_FULL; A.requeue[atomicAdd(A.n_requeue, 1ull)] = h; } }
@@ -1340,6 +1354,8 @@ __global__ __launch_bounds__(TPB) void k_merge(const MergeDesc* D, Slot* table, 
             if (round >= 64u) { if (st == ST_PENDING) { atomicOr(&ctr->err, ERR_INTERNAL); st = ST_NONE; } break; }
             if (st == ST_PENDING) {
                 const int r = table_settle(table + j, cmp);
+                RACE(2);
+                if (r == ST_OTHER) RACE(3);
                 if (r == ST_HIT) st = ST_HIT;
                 else if (r == ST_STUCK) { atomicOr(&ctr->err, ERR_INTERNAL); st = ST_NONE; }
                 else { j = (j + 1) & cap_mask; ++probes; st = table_lookup(table, cap_mask, s.lo, j, probes, cmp); }
@@ -2948,8 +2964,8 @@ int build_batch(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* d_
     RCCHK(plan_stream(h, n, &P, v));
     u64* timing = nullptr;
 #ifdef ECB_TIMING
-    HIPCHK(h, hipMalloc(&timing, 16 * sizeof(u64)));
-    HIPCHK(h, hipMemset(timing, 0, 16 * sizeof(u64)));
+    HIPCHK(h, hipMalloc(&timing, ECB_TIMING_WORDS * sizeof(u64)));
+    HIPCHK(h, hipMemset(timing, 0, ECB_TIMING_WORDS * sizeof(u64)));
 #endif
     h->ctr_synced = false;
     *launched = true;
@@ -2974,7 +2990,7 @@ int build_batch(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* d_
     }
 #ifdef ECB_TIMING
     {
-        u64 t[16];
+        u64 t[ECB_TIMING_WORDS];
         hipMemcpy(t, timing, sizeof(t), hipMemcpyDeviceToHost); hipFree(timing);
         static const char* nm[8] = {"(a) filter+heads", "tile decisions", "prefetch issue+clear+geometry", "(b) LDS tables", "hash entries", "(c) lookup", "publish/settle/slot stores", "-"};
         u64 tot = 0; for (int i = 0; i < 7; ++i) tot += t[i];
@@ -2985,6 +3001,10 @@ int build_batch(ecb_handle* h, const u32* d_rid, const u32* d_loc, const u32* d_
         fprintf(stderr, "  table trips per lookup %.3f (claim-only %.3f) over %llu lookups: 1: %.1f%%  2: %.1f%%  3: %.1f%%  4+: %.1f%%", (double)t[12] / std::max<u64>(t[14], 1),
                 (double)t[13] / std::max<u64>(t[14], 1), (unsigned long long)t[14], 100.0 * t[8] / std::max<u64>(t[14], 1), 100.0 * t[9] / std::max<u64>(t[14], 1),
                 100.0 * t[10] / std::max<u64>(t[14], 1), 100.0 * t[11] / std::max<u64>(t[14], 1));
+        // races between waves (k_stream's flush only): claims that found the slot taken since the line was read, by another hash or by a founder with
+        // the same; lanes that went through table_settle, and those it sent on to the next slot (the other key of a colliding pair)
+        fprintf(stderr, "  [race] claims lost to another hash %llu, to the same hash %llu; lanes in table_settle %llu, of them ST_OTHER %llu",
+                (unsigned long long)t[15], (unsigned long long)t[16], (unsigned long long)t[17], (unsigned long long)t[18]);
         fprintf(stderr, "\n");
     }
 #endif
@@ -4278,6 +4298,17 @@ int ecb_profile_read(ecb_handle* h, double* ms, uint64_t* launches, uint64_t* re
 // the stream kernel the last batch launched, as rocprofv3 names it (k_stream.inc is compiled more than once: which compilation a
 // batch takes is decided per batch, in pick_variant)
 const char* ecb_profile_kernel(const ecb_handle* h) { return h && h->last_variant != SV_N ? STREAM_VARIANTS[h->last_variant].name : ""; }
+#ifdef ECB_TIMING
+// profiling build only: the device-wide race counters of k_slow and k_merge (g_race) since the last call, which it zeroes -> 0, or a HIP error
+int ecb_timing_race(int device, unsigned long long out[4]) {
+    static const u64 zero[4] = {0, 0, 0, 0};
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_race), sizeof(zero));
+    if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(g_race), zero, sizeof(zero));
+    return (int)e;
+}
+#endif
 
 }  // extern "C"
 

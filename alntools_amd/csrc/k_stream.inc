@@ -304,7 +304,7 @@ __global__ __launch_bounds__(TPB, RANGES ? (WAVES_PER_SIMD < 4 ? WAVES_PER_SIMD 
     if (lane == 0) L.ws[7] = 0u;
     if (!VERIFY && lane == 0) { const u64* wa = C->wave_arena; const u64 ca = wa[2 * pw]; L.ws[2] = (u32)ca; L.ws[3] = (u32)(ca >> 32); L.ws[4] = (u32)wa[2 * pw + 1]; }
 #ifdef ECB_TIMING
-    u64 tacc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast = __builtin_readcyclecounter();
+    u64 tacc[ECB_TIMING_WORDS] = {}, tlast = __builtin_readcyclecounter();
 #endif
     // this wave's per-pass LDS state: table, hash sums, pair counts -- cleared here and behind every flush
     auto clear_pass = [&](u32 ln) {
@@ -780,6 +780,10 @@ __global__ __launch_bounds__(TPB, RANGES ? (WAVES_PER_SIMD < 4 ? WAVES_PER_SIMD 
                             else if (got == lo) st = ST_PENDING;             // claimed with our hash a moment ago: its key decides
                             else adv = true;
                         }
+#ifdef ECB_TIMING
+                        // (profiling: what the claims of this trip lost to -- a slot taken since its line was read, by another hash or by a founder with mine)
+                        tacc[15] += (u64)__popcll(__ballot(claim && got != 0ull && got != lo)); tacc[16] += (u64)__popcll(__ballot(claim && got == lo));
+#endif
                         if (adv) { j = (j + 1) & A.cap_mask; ++probes; st = probes < MAX_PROBE ? ST_LOOK : ST_FULL; }
                         if (first) {
                             TICK(5);
@@ -848,13 +852,21 @@ __global__ __launch_bounds__(TPB, RANGES ? (WAVES_PER_SIMD < 4 ? WAVES_PER_SIMD 
                     if (round >= 64u) { if (st == ST_PENDING) { bad |= ERR_INTERNAL; st = ST_NONE; } break; }
 #ifdef ECB_TIMING
                     f_rounds += 1u;                                      // (a settle polls the slot: a trip at the least)
+                    tacc[17] += (u64)__popcll(__ballot(st == ST_PENDING));   // (profiling: lanes that go through table_settle ...)
+                    bool s_other = false;
 #endif
                     if (st == ST_PENDING) {
                         const int r = table_settle(A.table + j, cmp);
+#ifdef ECB_TIMING
+                        s_other = r == ST_OTHER;
+#endif
                         if (r == ST_HIT) st = ST_HIT;
                         else if (r == ST_STUCK) { bad |= ERR_INTERNAL; st = ST_NONE; atomicExch(&A.ctr->full, 1u); }   // (every wave stops at its next tile)
                         else { j = (j + 1) & A.cap_mask; ++probes; st = probes < MAX_PROBE ? ST_LOOK : ST_FULL; }
                     }
+#ifdef ECB_TIMING
+                    tacc[18] += (u64)__popcll(__ballot(s_other));            // (... and those it sent on to the next slot: the slot holds the other key of their hash)
+#endif
                 }
 #ifdef ECB_TIMING
                 // trips to the EC table this lookup of up to 64 reads made: a histogram (1, 2, 3, 4 or more), their sum, the claim-only ones, lookups
@@ -921,7 +933,7 @@ __global__ __launch_bounds__(TPB, RANGES ? (WAVES_PER_SIMD < 4 ? WAVES_PER_SIMD 
     // per-wave totals go to their own words: thousands of waves adding to three shared counters serialise (~50 ns each)
     const u32 wn = VERIFY ? wave_sum(my_new) : my_new;
 #ifdef ECB_TIMING
-    if (lane == 0 && C->timing) for (int i = 0; i < 16; ++i) atomicAdd(C->timing + i, tacc[i]);
+    if (lane == 0 && C->timing) for (int i = 0; i < ECB_TIMING_WORDS; ++i) atomicAdd(C->timing + i, tacc[i]);
 #endif
     if (lane == 0) { u32* wc = C->wave_counts; wc[3 * pw] = wa; wc[3 * pw + 1] = wv; wc[3 * pw + 2] = wn; }
     if (!VERIFY && lane == 0) { u64* wav = C->wave_arena; wav[2 * pw] = ((u64)L.ws[3] << 32) | L.ws[2]; wav[2 * pw + 1] = L.ws[4]; }

@@ -17,7 +17,8 @@ The stored order of a key's pairs is the founder's entry-queue order, which a te
 pairs take is covered by SPREAD, not by construction -- their loci are the lowest, middle or highest of the key, the founding read
 lists its loci ascending or descending, either key founds, and several instances of every family are used.  Displaced pairs (a stored
 locus whose first LDS place holds another (read, locus)) ARE placed by construction, in ``test_displaced_pairs_of_colliding_keys``.
-Nothing here can force CMP_INCOMPLETE or ST_STUCK: those are races between a publisher and a reader."""
+Nothing here can force CMP_INCOMPLETE or ST_STUCK: those are races between a publisher and a reader, which
+``test_gpu_racing_founders.py`` makes the common case with streams laid out on the slices of one launch."""
 import numpy as np
 import pytest
 
