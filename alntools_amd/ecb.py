@@ -265,6 +265,31 @@ def _dev_ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _side_stream(device, torch=None):
+    """torch's current stream on CUDA device ``device`` where that is not the default stream, else None -- also where PyTorch is not
+    imported or has not opened a GPU (no tensor can then be in flight).  libecb wants finished inputs and works on streams of its own
+    (include/ecb.h); those order themselves behind torch's default stream, the legacy null stream, and behind no other: INTEGRATION.md,
+    "Streams".  On the default stream this is two look-ups and nothing on the device."""
+    torch = torch or sys.modules.get("torch")
+    if torch is None or not torch.cuda.is_initialized():
+        return None
+    s = torch.cuda.current_stream(device)
+    return None if s == torch.cuda.default_stream(device) else s
+
+
+def _wait_side_stream(device, torch=None):
+    """The host waits for what :func:`_side_stream` names, if it names a stream -> whether it did."""
+    s = _side_stream(device, torch)
+    if s is not None:
+        s.synchronize()
+    return s is not None
+
+
+def _wait_device(device, torch=None):
+    """The host waits for everything on CUDA device ``device``, libecb's own streams among it."""
+    (torch or sys.modules["torch"]).cuda.synchronize(device)
+
+
 def tile_tuples(read_id, locus, hapflag, out=None):
     """Three device arrays of ``n`` records -> one int32 tensor of whole tiles for :meth:`EcBuilder.push_device_tiled` (tile t = words
     ``[1536 t, 1536 t + 1536)`` = 512 read ids | 512 loci | 512 haplotype/flag words; the last tile's padding is zero)."""
@@ -317,6 +342,10 @@ class _Numpy(object):
     def zeros(self, shape, dt):
         return np.zeros(shape, dtype=dt)
 
+    def ready(self):
+        """What every wrapper passes once, after its arrays are prepared and before its first call of the library: host arrays are
+        always ready."""
+
 
 class _Torch(_Numpy):
     """The same for tensors: the ``_device`` entry points, on the tensors' own device."""
@@ -353,7 +382,16 @@ class _Torch(_Numpy):
         return self.torch.empty(shape, dtype=dt, device=self.dev)
 
     def zeros(self, shape, dt):
-        return self.torch.zeros(shape, dtype=dt, device=self.dev)
+        """... and in place when it returns: off the default stream the host waits for the fill (the library would write first)."""
+        z = self.torch.zeros(shape, dtype=dt, device=self.dev)
+        _wait_side_stream(self.dev, self.torch)
+        return z
+
+    def ready(self):
+        """... tensors may be in flight on torch's current stream -- the caller's kernels, the conversions of :meth:`arr` -- and the
+        library waits for nothing of the caller's: off the default stream the host waits for that stream here.  (The other way round needs
+        nothing: every entry point without a handle has waited for its own work when it returns.)"""
+        _wait_side_stream(self.dev, self.torch)
 
 
 _torch_kinds = {}
@@ -398,6 +436,7 @@ def csr_to_hapcsc(indptr, indices, data, n_loci, n_haps, nnz=None, device=0):
     k = _kind(indptr, device)
     p, fn = k.ptr, k.entry(lib, "ecb_csr_to_hapcsc")
     ip, ix, da = (k.arr(a, k.i32) for a in (indptr, indices, data))
+    k.ready()
     head = (k.device, len(ip) - 1, n_loci, n_haps, p(ip), p(ix), p(da))
     room = (lambda n: ()) if k.tensors else (lambda n: (n,))      # what differs: only the host entry point is told csc_indices' room
     tot = C.c_uint64()
@@ -427,6 +466,7 @@ def csr_to_hapcsc_values(indptr, indices, data, values, n_loci, n_haps, device=0
     p, fn = k.ptr, k.entry(lib, "ecb_csr_to_hapcsc_values")
     ip, ix, da = (k.arr(a, k.i32) for a in (indptr, indices, data))
     va = k.arr(values, k.f64)
+    k.ready()
     head = (k.device, len(ip) - 1, n_loci, n_haps, p(ip), p(ix), p(da))
     room = (lambda n: ()) if k.tensors else (lambda n: (n,))      # what differs: only the host entry point is told the outputs' room
     tot = C.c_uint64()
@@ -450,6 +490,7 @@ def hapcsc_to_csr(csc_indptr, csc_indices, n_ecs, device=0):
     k = _kind(csc_indptr, device)
     p = k.ptr
     cptr, cidx = k.arr(csc_indptr, k.i32), k.arr(csc_indices, k.i32)
+    k.ready()
     H, T1 = cptr.shape
     total = len(cidx)
     room = total if k.tensors else max(total, 1)     # what differs: tensors have always been sized exactly (an empty one's pointer is null)
@@ -472,6 +513,7 @@ def apply_mask(indptr, indices, data, mask, n_haps, device=0):
     p = k.ptr
     ip, ix, da = (k.arr(a, k.i32) for a in (indptr, indices, data))
     mk = k.arr(mask, k.u32)
+    k.ready()
     E, T, nnz = len(ip) - 1, len(mk), len(ix)
     if len(da) != nnz:
         raise ValueError("indices and data differ in length")
@@ -493,6 +535,7 @@ def count_alignments(indptr, indices, data, n_loci, n_haps, indptr_n, indices_n,
     p = k.ptr
     s = -1 if sample is None else int(sample)
     (ip, ix, da, pn, xn, dn), (E, nnz, S, nnz_n) = _matrices(k, (indptr, indices, data, indptr_n, indices_n, data_n))
+    k.ready()
     aln, uniq, lu = k.empty((n_haps, n_loci), k.i64), k.empty((n_haps, n_loci), k.i64), k.empty(n_loci, k.i64)
     _check(lib, k.entry(lib, "ecb_count_alignments")(k.device, E, n_loci, n_haps, nnz, p(ip), p(ix), p(da), S, nnz_n, p(pn), p(xn), p(dn), s,
                                                      p(aln), p(uniq), p(lu)))
@@ -521,6 +564,7 @@ def _quantify(mats, n_loci, n_haps, sample, scale, theta_in, max_iters, tol, dev
     sc, th, gn = k.arr(scale, k.f64), k.arr(theta_in, k.f64), k.arr(grouping and grouping[0], k.i32)
     _check_gene(gn, n_loci)                          # (the genes before the tables here, after them per cell: the order each has always had)
     _check_tables((sc, th), n_loci, n_haps, "scale and theta_in")
+    k.ready()
     s = -1 if sample is None else int(sample)
     it, dl, ex, cv = C.c_uint32(), C.c_double(), C.c_int64(), C.c_uint32()
     theta = k.empty((n_haps, n_loci), k.f64)
@@ -558,6 +602,7 @@ def posterior(indptr, indices, data, n_loci, n_haps, theta, scale=None, gene=Non
     ip, ix, da = (k.arr(a, k.i32) for a in (indptr, indices, data))
     sc, th, gn = k.arr(scale, k.f64), k.arr(theta, k.f64), k.arr(gene, k.i32)
     E, nnz = len(ip) - 1, len(ix)
+    k.ready()
     # what differs: how the set bits are counted -- host masks here, device masks by the conversion's count-only call (one pass over the
     # masks it is told of), and only over a CSR it can walk
     n_bits = 0
@@ -594,9 +639,16 @@ def cell_support(indptr, indices, data, n_loci, n_haps, indptr_n, indices_n, dat
     two, ``slot_locus`` is then None."""
     lib = load()
     k = _kind(indptr, device)
+    mats, sizes = _matrices(k, (indptr, indices, data, indptr_n, indices_n, data_n))
+    keep = _cell_keep(k, cell_keep, sizes[2])
+    k.ready()
+    return _cell_support(lib, k, mats, sizes, keep, n_loci, n_haps, count_only)
+
+
+def _cell_support(lib, k, mats, sizes, keep, n_loci, n_haps, count_only):
+    """:func:`cell_support` on arrays of kind ``k`` that are prepared and ready (:func:`_quantify_cells` sizes its support here)."""
     p, fn = k.ptr, k.entry(lib, "ecb_cell_support")
-    (ip, ix, da, pn, xn, dn), (E, nnz, S, nnz_n) = _matrices(k, (indptr, indices, data, indptr_n, indices_n, data_n))
-    keep = _cell_keep(k, cell_keep, S)
+    (ip, ix, da, pn, xn, dn), (E, nnz, S, nnz_n) = mats, sizes
     ns = C.c_uint64()
     head = (k.device, E, n_loci, n_haps, nnz, p(ip), p(ix), p(da), S, nnz_n, p(pn), p(xn), p(dn), p(keep))
     cell_ptr = k.empty(S + 1, k.i64)
@@ -632,8 +684,9 @@ def _quantify_cells(mats, n_loci, n_haps, cell_keep, scale, theta_in, max_iters,
     sc, th, gn = k.arr(scale, k.f64), k.arr(theta_in, k.f64), k.arr(grouping and grouping[0], k.i32)
     _check_tables((sc, th), n_loci, n_haps, "scale and theta_in")
     _check_gene(gn, n_loci)
+    k.ready()
     if n_slots is None:
-        n_slots = int(cell_support(ip, ix, da, n_loci, n_haps, pn, xn, dn, keep, device, count_only=True)[0][-1])
+        n_slots = int(_cell_support(lib, k, (ip, ix, da, pn, xn, dn), (E, nnz, S, nnz_n), keep, n_loci, n_haps, True)[0][-1])
     fn = k.entry(lib, "ecb_quantify_cells" + ("_model" if grouping else ""))
     model_args = (int(grouping[1]), p(gn), int(grouping[2])) if grouping else ()
     cell_ptr, slot_locus, theta = k.empty(S + 1, k.i64), k.empty(n_slots, k.i32), k.empty((n_slots, n_haps), k.f64)
@@ -682,6 +735,7 @@ def combine(parts, n_loci, n_haps, n_samples, device=0):
         for n, x in zip(("indptr_a", "indices_a", "data_a", "indptr_n", "indices_n", "data_n", "target_map", "sample_map"), a):
             setattr(c, n, None if x is None else k.ptr(x).value)
         R, NP, NZ = R + E, NP + len(a[1]), NZ + len(a[4])
+    k.ready()
     out = [k.empty(max(n, 1), k.i32) for n in (R + 1, NP, NP, n_samples + 1, NZ, NZ)]
     sizes = (C.c_uint64 * 3)()
     _check(lib, k.entry(lib, "ecb_combine")(k.device, len(parts), cp, n_loci, n_haps, n_samples, *[k.ptr(o) for o in out], sizes))
@@ -711,6 +765,7 @@ def bundle(indptrA, indicesA, dataA, indptrN, indicesN, dataN, n_loci, n_haps, n
         per = (mp[1:] - mp[:-1]).clamp(min=0) if k.tensors else np.maximum(np.diff(mp.astype(np.int64)), 0)
         cols = ixa.long().clamp(0, n_loci - 1) if k.tensors else np.clip(ixa, 0, n_loci - 1)
         cap = min(int(per[cols].sum()), E * n_groups, (1 << 31) - 1)
+    k.ready()
     out = [k.empty(max(n, 1), k.i32) for n in (E + 1, cap, cap, S + 1, nnz_n, nnz_n)]
     sizes = (C.c_uint64 * 3)()
     _check(lib, k.entry(lib, "ecb_bundle")(k.device, E, n_loci, n_haps, S, n_groups, nnz, p(ipa), p(ixa), p(daa), nnz_n, p(ipn), p(ixn), p(dan),
@@ -738,6 +793,7 @@ def select(indptrA, indicesA, dataA, indptrN, indicesN, dataN, n_loci, n_haps, r
     sk = k.flags(sample_keep)
     if sk is not None and len(sk) != S:
         raise ValueError("sample_keep has %d entries for %d samples" % (len(sk), S))
+    k.ready()
     out = [k.empty(max(n, 1), k.i32) for n in (E + 1, nnz, nnz, S + 1, nnz_n, nnz_n)]
     kept = k.empty(max(S, 1), k.u8)
     sizes = (C.c_uint64 * 4)()
@@ -783,6 +839,7 @@ def salmon_ecs(text, n_ecs, target_col, target_hap, n_loci, n_haps, device=0):
     tc, th = k.arr(target_col, k.u32), k.arr(target_hap, k.u32)
     if not k.tensors and len(tc) != len(th):         # what differs: only the host arrays have ever been compared
         raise ValueError("target_col and target_hap differ in length")
+    k.ready()
     out = [k.empty(n, k.i32) for n in (n_ecs + 1, max(cap, 1), max(cap, 1), max(n_ecs, 1), max(n_ecs, 1))]
     sizes = (C.c_uint64 * 2)()
     _check_offender(lib, k.entry(lib, "ecb_salmon_ecs")(k.device, p(t), len(t), n_ecs, len(tc), p(tc), p(th), n_loci, n_haps, cap, *[p(o) for o in out], sizes),
@@ -804,11 +861,26 @@ class EcBuilder(object):
                      arena_capacity, max_batch_records)
         _check(self._lib, self._lib.ecb_create(C.byref(cfg), C.byref(self._h)))
         self.n_loci, self.n_haplotypes, self.track_ranges = n_loci, n_haplotypes, track_ranges
+        self.device = device
         self.sizes = None
 
     # -- plumbing ------------------------------------------------------------
     def _chk(self, rc):
         _check(self._lib, rc, self._h)
+
+    def _device_call(self, *calls):
+        """Every ``*_device`` method's way into the library: ``calls`` = ``(function, argument after the handle, ...)``, made in order.
+        The tensors behind the pointers may be in flight on torch's current stream, and the handle works on a stream of its own that
+        waits for nothing of the caller's and that some entry points do not wait for either (include/ecb.h: "no wait").  On the default
+        stream both orderings are given (:func:`_side_stream`); off it the host waits for the caller's stream before the first call and
+        for the device after the last, so that what the caller queues next finds the library's reads and writes done."""
+        side = _wait_side_stream(self.device)
+        try:
+            for c in calls:
+                self._chk(c[0](self._h, *c[1:]))
+        finally:
+            if side:
+                _wait_device(self.device)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -845,19 +917,18 @@ class EcBuilder(object):
         for t in (read_id, locus, hapflag) + ((pos,) if pos is not None else ()):
             if not t.is_cuda or not t.is_contiguous() or t.element_size() != 4 or t.numel() != n:
                 raise ValueError("device tuple streams must be contiguous 4-byte CUDA tensors of equal length")
-        self._chk(self._lib.ecb_push_device(self._h, _dev_ptr(read_id), _dev_ptr(locus), _dev_ptr(hapflag),
-                                            _dev_ptr(pos), n))
+        self._device_call((self._lib.ecb_push_device, _dev_ptr(read_id), _dev_ptr(locus), _dev_ptr(hapflag), _dev_ptr(pos), n))
 
     def push_device_tiled(self, tiles, n):
         """``n`` records in ONE int32 CUDA tensor of whole tiles (``ecb_push_device_tiled``: 512 read ids | 512 loci | 512 haplotype/flag
         words per tile, ``ceil(n / 512) * 1536`` words); whole reads per call.  :func:`tile_tuples` lays three arrays out this way."""
         if not tiles.is_cuda or not tiles.is_contiguous() or tiles.element_size() != 4 or tiles.numel() < (n + 511) // 512 * 1536:
             raise ValueError("tiles: a contiguous 4-byte CUDA tensor of ceil(n / 512) * 1536 words")
-        self._chk(self._lib.ecb_push_device_tiled(self._h, _dev_ptr(tiles), n))
+        self._device_call((self._lib.ecb_push_device_tiled, _dev_ptr(tiles), n))
 
     def verify_device_tiled(self, tiles, n):
         bad, skipped = C.c_uint64(), C.c_uint64()
-        self._chk(self._lib.ecb_verify_device_tiled(self._h, _dev_ptr(tiles), n, C.byref(bad), C.byref(skipped)))
+        self._device_call((self._lib.ecb_verify_device_tiled, _dev_ptr(tiles), n, C.byref(bad), C.byref(skipped)))
         return bad.value, skipped.value
 
     def hint_reads(self, max_reads):
@@ -869,8 +940,8 @@ class EcBuilder(object):
         """Independent exactness pass over the device-resident stream that was pushed: -> (reads whose target set differs
         from their EC's stored key, reads that took the long-read compare)."""
         bad, skipped = C.c_uint64(), C.c_uint64()
-        self._chk(self._lib.ecb_verify_device(self._h, _dev_ptr(read_id), _dev_ptr(locus), _dev_ptr(hapflag),
-                                              read_id.numel(), C.byref(bad), C.byref(skipped)))
+        self._device_call((self._lib.ecb_verify_device, _dev_ptr(read_id), _dev_ptr(locus), _dev_ptr(hapflag), read_id.numel(), C.byref(bad),
+                           C.byref(skipped)))
         return bad.value, skipped.value
 
     def push_cells(self, meta, first_read):
@@ -880,7 +951,7 @@ class EcBuilder(object):
 
     def push_cells_device(self, meta, first_read):
         """The same from an int32 CUDA tensor (kept alive by the caller until ``finalize``)."""
-        self._chk(self._lib.ecb_push_cells_device(self._h, _dev_ptr(meta), first_read, meta.numel()))
+        self._device_call((self._lib.ecb_push_cells_device, _dev_ptr(meta), first_read, meta.numel()))
 
     def ms_filter_sizes(self, n_cells, minimum_count):
         """``ecb_ms_filter`` alone: the result stays on the device (``ms_filter`` also copies it to the host) -> its sizes."""
@@ -958,15 +1029,15 @@ class EcBuilder(object):
         return a.value, b.value, c.value
 
     def table_export_device(self, entries, pairs, read_base):
-        self._chk(self._lib.ecb_table_export_device(self._h, _dev_ptr(entries), _dev_ptr(pairs), read_base))
+        self._device_call((self._lib.ecb_table_export_device, _dev_ptr(entries), _dev_ptr(pairs), read_base))
 
     def table_merge_device(self, entries, n_entries, pairs, n_pairs):
-        self._chk(self._lib.ecb_table_merge_device(self._h, _dev_ptr(entries), n_entries, _dev_ptr(pairs), n_pairs))
+        self._device_call((self._lib.ecb_table_merge_device, _dev_ptr(entries), n_entries, _dev_ptr(pairs), n_pairs))
 
     def table_export_parts_device(self, entries, pairs, read_base, n_parts):
         """Export grouped into ``n_parts`` key ranges -> (entry_offsets, pair_offsets), lists of n_parts + 1."""
         eo, po = (C.c_uint64 * (n_parts + 1))(), (C.c_uint64 * (n_parts + 1))()
-        self._chk(self._lib.ecb_table_export_parts_device(self._h, _dev_ptr(entries), _dev_ptr(pairs), read_base, n_parts, eo, po))
+        self._device_call((self._lib.ecb_table_export_parts_device, _dev_ptr(entries), _dev_ptr(pairs), read_base, n_parts, eo, po))
         return list(eo), list(po)
 
     def _batch(self, fn, tables):
@@ -974,7 +1045,7 @@ class EcBuilder(object):
         n = len(tables)
         pe, ne = (C.c_void_p * n)(*[t[0].data_ptr() for t in tables]), (C.c_uint64 * n)(*[t[1] for t in tables])
         pp, npr = (C.c_void_p * n)(*[t[2].data_ptr() for t in tables]), (C.c_uint64 * n)(*[t[3] for t in tables])
-        self._chk(fn(self._h, n, pe, ne, pp, npr))
+        self._device_call((fn, n, pe, ne, pp, npr))
 
     def table_merge_batch_device(self, tables):
         self._batch(self._lib.ecb_table_merge_batch_device, tables)
@@ -984,17 +1055,17 @@ class EcBuilder(object):
 
     def table_rebase_device(self, entries, n_entries, read_base):
         """Exported entries (device tensor), in place: first reads moved on by ``read_base``; ordered ahead of a merge on this handle."""
-        self._chk(self._lib.ecb_table_rebase_device(self._h, _dev_ptr(entries), n_entries, read_base))
+        self._device_call((self._lib.ecb_table_rebase_device, _dev_ptr(entries), n_entries, read_base))
 
     def table_adopt_device(self, entries, n_entries, pairs, n_pairs):
-        self._chk(self._lib.ecb_table_adopt_device(self._h, _dev_ptr(entries), n_entries, _dev_ptr(pairs), n_pairs))
+        self._device_call((self._lib.ecb_table_adopt_device, _dev_ptr(entries), n_entries, _dev_ptr(pairs), n_pairs))
 
     # -- finalize per key range ----------------------------------------------
     def export_piece_device(self, indptr, indices, data, counts, firsts):
         """After finalize, on the handle that merged one key range: CSR A, the EC counts and every EC's first read (global
         index) into int32 device tensors of E + 1 / nnz / nnz / E / E elements."""
-        self._chk(self._lib.ecb_export_device(self._h, _dev_ptr(indptr), _dev_ptr(indices), _dev_ptr(data), None, None, _dev_ptr(counts)))
-        self._chk(self._lib.ecb_export_firsts_device(self._h, _dev_ptr(firsts)))
+        self._device_call((self._lib.ecb_export_device, _dev_ptr(indptr), _dev_ptr(indices), _dev_ptr(data), None, None, _dev_ptr(counts)),
+                          (self._lib.ecb_export_firsts_device, _dev_ptr(firsts)))
 
     def assemble_ranges_device(self, pieces, n_reads, all_alignments, valid_alignments):
         """``pieces``: [(indptr, indices, data, counts, firsts, n_ecs, nnz), ...] of int32 device tensors, one per key range,
@@ -1003,26 +1074,25 @@ class EcBuilder(object):
         ptrs = [(C.c_void_p * k)(*[p[i].data_ptr() for p in pieces]) for i in range(5)]
         ne, nz = (C.c_uint64 * k)(*[p[5] for p in pieces]), (C.c_uint64 * k)(*[p[6] for p in pieces])
         s = Sizes()
-        self._chk(self._lib.ecb_assemble_ranges_device(self._h, k, *ptrs, ne, nz, n_reads, all_alignments, valid_alignments, C.byref(s)))
+        self._device_call((self._lib.ecb_assemble_ranges_device, k) + tuple(ptrs) + (ne, nz, n_reads, all_alignments, valid_alignments, C.byref(s)))
         self.sizes = {k_: int(getattr(s, k_)) for k_, _ in Sizes._fields_}
         return self.sizes
 
     # -- multisample across GPUs ----------------------------------------------
     def export_ec_keys_device(self, keys):
         """After finalize: the 8-byte set hash of every EC in rank order into ``keys`` (int64 tensor of n_ecs)."""
-        self._chk(self._lib.ecb_export_ec_keys_device(self._h, _dev_ptr(keys)))
+        self._device_call((self._lib.ecb_export_ec_keys_device, _dev_ptr(keys)))
 
     def export_device(self, indptr, indices, data):
         """After finalize: CSR A into int32 device tensors of E + 1 / nnz / nnz elements."""
-        self._chk(self._lib.ecb_export_device(self._h, _dev_ptr(indptr), _dev_ptr(indices), _dev_ptr(data), None, None, None))
+        self._device_call((self._lib.ecb_export_device, _dev_ptr(indptr), _dev_ptr(indices), _dev_ptr(data), None, None, None))
 
     def ms_local_triples_device(self, keys, indptr, indices, data, n_ecs, read_base, out_key, out_count, out_first):
         """A shard's (EC, cell, file) triples with global EC ids (its ECs found in the merged result by hash ``keys`` and
         then by key against the merged CSR rows) -> number of triples written."""
         n = C.c_uint64()
-        self._chk(self._lib.ecb_ms_local_triples_device(self._h, _dev_ptr(keys), _dev_ptr(indptr), _dev_ptr(indices), _dev_ptr(data),
-                                                        n_ecs, read_base, _dev_ptr(out_key), _dev_ptr(out_count), _dev_ptr(out_first),
-                                                        C.byref(n)))
+        self._device_call((self._lib.ecb_ms_local_triples_device, _dev_ptr(keys), _dev_ptr(indptr), _dev_ptr(indices), _dev_ptr(data), n_ecs,
+                           read_base, _dev_ptr(out_key), _dev_ptr(out_count), _dev_ptr(out_first), C.byref(n)))
         return n.value
 
     def ms_adopt_triples_device(self, tables):
@@ -1031,7 +1101,7 @@ class EcBuilder(object):
         pk, pc = (C.c_void_p * k)(*[t[0].data_ptr() for t in tables]), (C.c_void_p * k)(*[t[1].data_ptr() for t in tables])
         pf, nn = (C.c_void_p * k)(*[t[2].data_ptr() for t in tables]), (C.c_uint64 * k)(*[t[3] for t in tables])
         out = C.c_uint64()
-        self._chk(self._lib.ecb_ms_adopt_triples_device(self._h, k, pk, pc, pf, nn, C.byref(out)))
+        self._device_call((self._lib.ecb_ms_adopt_triples_device, k, pk, pc, pf, nn, C.byref(out)))
         if self.sizes is not None:
             self.sizes["nnz_n"] = out.value
         return out.value

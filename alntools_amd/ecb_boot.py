@@ -33,6 +33,7 @@ def resample(n_ecs, indptr_n, indices_n, data_n, sample=None, seed=0, b0=0, n_re
     pn, xn, dn = (k.arr(a, k.i32) for a in (indptr_n, indices_n, data_n))
     if len(xn) != len(dn):
         raise ValueError("indices and data differ in length")
+    k.ready()
     s = -1 if sample is None else int(sample)
     head = (k.device, int(n_ecs), len(pn) - 1, len(xn), p(pn), p(xn), p(dn), s, int(seed), int(b0), int(n_reps))
     nnz = C.c_uint64()
@@ -59,6 +60,7 @@ def quantify_bootstrap(indptr, indices, data, n_loci, n_haps, indptr_n, indices_
     sc, gn = k.arr(scale, k.f64), k.arr(gene, k.i32)
     _check_tables((sc,), n_loci, n_haps, "scale")
     _check_gene(gn, n_loci)
+    k.ready()
     B = int(n_reps)
     s = -1 if sample is None else int(sample)
     mean, sd = k.empty((n_haps, n_loci), k.f64), k.empty((n_haps, n_loci), k.f64)

@@ -70,6 +70,7 @@ def molecules(records, bclen, umilen, ec_ptr, ec_targets, target_col, target_hap
     kp = k.words(keep, 64)
     if len(tc) != len(th):
         raise ValueError("target_col and target_hap differ in length")
+    k.ready()
     if capacities is None:
         host_ptr = ptr.cpu().numpy() if k.tensors else ptr
         host_rec = rec.cpu().numpy() if k.tensors else rec

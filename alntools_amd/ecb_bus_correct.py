@@ -53,6 +53,7 @@ def correct(records, bclen, whitelist, want_status=False, capacity=None, device=
         raise ValueError("the records are %d bytes: not a multiple of %d" % (len(rec), RECORD_BYTES))
     n = len(rec) // RECORD_BYTES
     wl = k.words(whitelist, 64)
+    k.ready()
     cap = n if capacity is None else int(capacity)
     out = k.empty(max(cap, 1) * RECORD_BYTES, k.u8)
     status = k.empty(max(n, 1), k.u8) if want_status else None

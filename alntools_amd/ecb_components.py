@@ -33,6 +33,7 @@ def components(indptr, indices, data, n_loci, n_haps, indptr_n, indices_n, data_
     p = k.ptr
     s = -1 if sample is None else int(sample)
     (ip, ix, da, pn, xn, dn), (E, nnz, S, nnz_n) = _matrices(k, (indptr, indices, data, indptr_n, indices_n, data_n))
+    k.ready()
     T = int(n_loci)
     of_locus, of_ec = k.empty(T, k.i32), k.empty(E, k.i32)
     loci, ecs, reads = k.empty(T, k.i32), k.empty(T, k.i32), k.empty(T, k.i64)

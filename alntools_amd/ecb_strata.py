@@ -73,6 +73,7 @@ def best_strata(read_id, hapflag, score, lowest=True, device=0, inplace=False):
     n = len(rid)
     if len(hf) != n or len(sc) != n:
         raise ValueError("read_id, hapflag and score hold %d, %d and %d records" % (n, len(hf), len(sc)))
+    k.ready()
     if inplace:
         if rid is not read_id or hf is not hapflag:
             raise ValueError("inplace needs contiguous %s arrays" % ("int32" if k.tensors else "uint32"))

@@ -91,6 +91,7 @@ def collapse_umis(read_id, locus, hapflag, mol_key, n_loci, n_haps, device=0):
         raise ValueError("read_id, locus and hapflag hold %d, %d and %d records" % (n, len(loc), len(hf)))
     if not n_reads:
         key = k.empty(1, k.u64)                                  # (a stream of no read: still a pointer)
+    k.ready()
     out = [k.empty(max(n, 1), k.u32) for _ in range(3)]
     first = k.empty(max(n_reads, 1), k.u32)
     counts = (C.c_uint64 * 6)()

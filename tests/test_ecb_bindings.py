@@ -281,3 +281,206 @@ def test_a_refusal_raises_the_class_its_text_names(rc, text, raised, attrs):
         ecb._check_offender(Lib, rc, pattern, error)
     assert type(info.value) is cls and all(getattr(info.value, a) == v for a, v in attrs.items()) and text.decode() in str(info.value)
     ecb._check_offender(Lib, 0, pattern, error)            # (no refusal: nothing raised)
+
+
+# ---- the stream hook: every tensor path waits for a current stream that is not the default one, once, between its conversions and the library ----
+class TorchStandIn(object):
+    """A ``torch`` module as far as the hook looks at it: ``cuda.is_initialized / current_stream / default_stream / synchronize``, each call
+    recorded; the current stream is ``side`` (a stream of its own) or the default one."""
+
+    class Stream(object):
+        def __init__(self, log, name):
+            self.log, self.name = log, name
+
+        def synchronize(self):
+            self.log.append("synchronize " + self.name)
+
+    def __init__(self, side, initialized=True):
+        self.log = []
+        self.cuda = self
+        self._default, self._side, self._current, self._initialized = self.Stream(self.log, "default"), self.Stream(self.log, "side"), side, initialized
+
+    def is_initialized(self):
+        return self._initialized
+
+    def current_stream(self, device):
+        self.log.append("current_stream %s" % device)
+        return self._side if self._current else self._default
+
+    def default_stream(self, device):
+        self.log.append("default_stream %s" % device)
+        return self._default
+
+    def synchronize(self, device):
+        self.log.append("synchronize device %s" % device)
+
+
+def test_the_hook_waits_for_a_side_stream_and_adds_nothing_on_the_default_one():
+    side, default, cold = TorchStandIn(True), TorchStandIn(False), TorchStandIn(True, initialized=False)
+    assert ecb._wait_side_stream(3, side) is True and side.log == ["current_stream 3", "default_stream 3", "synchronize side"]
+    assert ecb._wait_side_stream(3, default) is False and default.log == ["current_stream 3", "default_stream 3"]      # two look-ups, no wait
+    assert ecb._wait_side_stream(3, cold) is False and cold.log == []                                                  # (no GPU opened: no tensor in flight)
+    ecb._wait_device(2, side)
+    assert side.log[-1] == "synchronize device 2"
+    ecb._Numpy(0).ready()                                                    # (host arrays: nothing to wait for)
+
+
+class HookLib(object):
+    """A library of every symbol: each call is an event, returns 0 and writes nothing."""
+
+    def __init__(self, events):
+        self.events = events
+
+    def __getattr__(self, name):
+        if not name.startswith("ecb_"):
+            raise AttributeError(name)
+        if name == "ecb_last_error":
+            return lambda h: b""
+        return lambda *a: (self.events.append("C " + name), 0)[1]
+
+
+def _recording_kind(events):
+    import torch
+
+    class Recording(ecb._Torch):
+        def empty(self, shape, dt):                                          # (what the stand-in library leaves unwritten reads as 0)
+            return torch.zeros(shape, dtype=dt)
+
+        def ready(self):
+            events.append("ready")
+            ecb._Torch.ready(self)
+    for name in ("arr", "words", "flags", "bytes", "zeros"):
+        def method(self, *a, _name=name, **k):
+            events.append("prepare " + _name)
+            return getattr(ecb._Torch, _name)(self, *a, **k)
+        setattr(Recording, name, method)
+    return Recording(torch.device("cpu"))
+
+
+#: every wrapper that takes tensors -> a call of it on CPU tensors (the stand-in library takes any pointer)
+def _hooked_calls():
+    import numpy as np
+    import torch
+    from alntools_amd import ecb_boot, ecb_bus, ecb_bus_correct, ecb_components, ecb_strata, ecb_umi
+    i32 = lambda *v: torch.tensor(v, dtype=torch.int32)                      # noqa: E731
+    wide = lambda *v: torch.tensor(v, dtype=torch.int64)                     # noqa: E731
+    ip, ix, da, pn, xn, dn = wide(0, 1, 2), wide(0, 1), wide(1, 2), wide(0, 2), wide(0, 1), wide(3, 4)     # (int64: every one is converted)
+    T, H = 2, 2
+    mats = (ip, ix, da, T, H, pn, xn, dn)
+    tab, gene = torch.ones(H, T, dtype=torch.float64), wide(0, 0)
+    part = dict(indptrA=ip, indicesA=ix, dataA=da, indptrN=pn, indicesN=xn, dataN=dn, n_loci=T, target_map=None, sample_map=wide(0))
+    rec = torch.zeros(2 * 32, dtype=torch.uint8)
+    return {
+        "ecb.csr_to_hapcsc": lambda: ecb.csr_to_hapcsc(ip, ix, da, T, H),
+        "ecb.csr_to_hapcsc_values": lambda: ecb.csr_to_hapcsc_values(ip, ix, da, torch.zeros(0, dtype=torch.float64), T, H),
+        "ecb.hapcsc_to_csr": lambda: ecb.hapcsc_to_csr(wide(0, 1, 1, 0, 0, 1).view(2, 3), wide(0, 1), 2),
+        "ecb.apply_mask": lambda: ecb.apply_mask(ip, ix, da, wide(3, 3), H),
+        "ecb.count_alignments": lambda: ecb.count_alignments(*mats),
+        "ecb.quantify": lambda: ecb.quantify(*mats, scale=tab, theta_in=tab),
+        "ecb.quantify_model": lambda: ecb.quantify_model(*mats, gene, 1, 2, scale=tab),
+        "ecb.posterior": lambda: ecb.posterior(ip, ix, da, T, H, tab, scale=tab, gene=gene, n_genes=1, model=1),
+        "ecb.cell_support": lambda: ecb.cell_support(*mats, cell_keep=[1]),
+        "ecb.quantify_cells": lambda: ecb.quantify_cells(*mats, cell_keep=[1], scale=tab, theta_in=tab),
+        "ecb.quantify_cells_model": lambda: ecb.quantify_cells_model(*mats, gene, 1, 3, theta_in=tab),
+        "ecb.combine": lambda: ecb.combine([part, part], T, H, 1),
+        "ecb.bundle": lambda: ecb.bundle(ip, ix, da, pn, xn, dn, T, H, 1, wide(0, 1, 2), wide(0, 0)),
+        "ecb.select": lambda: ecb.select(ip, ix, da, pn, xn, dn, T, H, row_class="unique", sample_keep=[1], min_count=1),
+        "ecb.salmon_ecs": lambda: ecb.salmon_ecs(torch.tensor(list(b"1\t0\t5\n"), dtype=torch.uint8), 1, [0], [0], 1, 1),
+        "ecb_boot.resample": lambda: ecb_boot.resample(2, pn, xn, dn),
+        "ecb_boot.quantify_bootstrap": lambda: ecb_boot.quantify_bootstrap(*mats, 2, scale=tab, gene=gene, n_genes=1, model=1),
+        "ecb_components.components": lambda: ecb_components.components(*mats),
+        "ecb_bus.molecules": lambda: ecb_bus.molecules(rec, 12, 8, wide(0, 1), wide(0), wide(0), wide(0), 1, 1, keep=np.array([1, 2], dtype=np.uint64)),
+        "ecb_bus_correct.correct": lambda: ecb_bus_correct.correct(rec, 16, np.array([1, 2], dtype=np.uint64), want_status=True),
+        "ecb_strata.best_strata": lambda: ecb_strata.best_strata(wide(0, 0, 1), wide(0, 0, 0), wide(1, 2, 3)),
+        "ecb_strata.best_strata inplace": lambda: ecb_strata.best_strata(i32(0, 0, 1), i32(0, 0, 0), wide(1, 2, 3), inplace=True),
+        "ecb_umi.collapse_umis": lambda: ecb_umi.collapse_umis(wide(0, 0, 1), wide(0, 1, 0), wide(0, 0, 0), wide(5, 6), T, H),
+    }
+
+
+#: the public functions of the binding modules that take no tensor to the library: host helpers, loaders, and the names the host callers know
+NOT_WRAPPERS = {"ecb.bind", "ecb.load", "ecb.tile_tuples", "ecb.csr_to_hapcsc_host", "ecb.csr_to_hapcsc_values_host", "ecb.hapcsc_to_csr_host",
+                "ecb_boot.load", "ecb_components.load", "ecb_bus.load", "ecb_bus.a_capacity", "ecb_bus_correct.load", "ecb_strata.load",
+                "ecb_strata.parse_tag", "ecb_strata.cut_whole_reads", "ecb_umi.load", "ecb_umi.pack_umi", "ecb_umi.mol_keys"}
+
+
+def _public_functions():
+    import inspect
+    out = set()
+    for name in ["ecb"] + sorted(MODULES):
+        mod = __import__("alntools_amd." + name, fromlist=[name])
+        out |= {"%s.%s" % (name, n) for n, f in vars(mod).items() if inspect.isfunction(f) and f.__module__ == mod.__name__ and not n.startswith("_")}
+    return out
+
+
+def test_every_tensor_wrapper_passes_the_hook_once_after_its_conversions_and_before_the_library(monkeypatch):
+    """A wrapper added to one of the binding modules is either listed as taking no tensor or called here -- and then it passes
+    ``ready()`` exactly once, after the last conversion it queues (``arr``, ``words``, ``flags``, ``bytes``) and before the first symbol
+    of the library; a ``zeros()`` behind the hook waits for its own fill (``_Torch.zeros``)."""
+    import torch
+    events = []
+    monkeypatch.setattr(ecb, "_lib", HookLib(events))
+    monkeypatch.setattr(ecb, "_tables", {})
+    monkeypatch.setitem(ecb._torch_kinds, torch.device("cpu"), _recording_kind(events))
+    calls = _hooked_calls()
+    assert {c.split()[0] for c in calls} == _public_functions() - NOT_WRAPPERS
+    for label, thunk in calls.items():
+        del events[:]
+        thunk()
+        assert events.count("ready") == 1, (label, events)
+        at = events.index("ready")
+        assert any(e.startswith("prepare ") for e in events[:at]) or "inplace" in label, (label, events)
+        assert not any(e.startswith("C ") for e in events[:at]), (label, events)
+        assert any(e.startswith("C ") for e in events[at:]), (label, events)
+        assert all(e == "prepare zeros" for e in events[at:] if e.startswith("prepare ")), (label, events)
+    # the fill that a wrapper queues behind the hook is waited for where it is queued
+    waits = []
+    monkeypatch.setattr(ecb, "_wait_side_stream", lambda device, torch=None: waits.append(device))
+    ecb._Torch(torch.device("cpu")).zeros(3, torch.float64)
+    assert waits == [torch.device("cpu")]
+
+
+class FakeTensor(object):
+    """What a ``*_device`` method of the handle looks at: a contiguous 4-byte CUDA tensor of ``n`` elements somewhere."""
+    is_cuda = True
+
+    def __init__(self, n=1536):
+        self.n = n
+
+    def is_contiguous(self):
+        return True
+
+    def element_size(self):
+        return 4
+
+    def numel(self):
+        return self.n
+
+    def data_ptr(self):
+        return 0x1000
+
+
+def test_every_device_method_of_the_handle_passes_the_hook_once_before_the_library(monkeypatch):
+    """Every method of ``EcBuilder`` with ``_device`` in its name goes through ``_device_call``: the wait for a side stream once, before
+    its first symbol, and -- where there was one to wait for -- the wait for the device once, after its last."""
+    events = []
+    monkeypatch.setattr(ecb, "_lib", HookLib(events))
+    t = FakeTensor()
+    table, triple, piece = [(t, 1, t, 1)], [(t, t, t, 1)], [(t, t, t, t, t, 1, 1)]
+    args = {"push_device": (t, t, t), "push_device_tiled": (t, 512), "verify_device": (t, t, t), "verify_device_tiled": (t, 512),
+            "push_cells_device": (t, 0), "table_export_device": (t, t, 0), "table_merge_device": (t, 1, t, 1), "table_adopt_device": (t, 1, t, 1),
+            "table_export_parts_device": (t, t, 0, 2), "table_merge_batch_device": (table,), "table_adopt_batch_device": (table,),
+            "table_rebase_device": (t, 1, 0), "export_piece_device": (t, t, t, t, t), "assemble_ranges_device": (piece, 1, 1, 1),
+            "export_ec_keys_device": (t,), "export_device": (t, t, t), "ms_local_triples_device": (t, t, t, t, 1, 0, t, t, t),
+            "ms_adopt_triples_device": (triple,)}
+    assert sorted(args) == sorted(n for n in dir(ecb.EcBuilder) if "_device" in n and not n.startswith("_"))
+    b = ecb.EcBuilder(10, 2)
+    for side in (False, True):
+        monkeypatch.setattr(ecb, "_wait_side_stream", lambda device, torch=None: (events.append("ready %s" % device), side)[1])
+        monkeypatch.setattr(ecb, "_wait_device", lambda device, torch=None: events.append("device %s" % device))
+        for name, a in args.items():
+            del events[:]
+            getattr(b, name)(*a)
+            assert events[0] == "ready 0" and events.count("ready 0") == 1, (name, events)
+            assert events[1].startswith("C ecb_"), (name, events)
+            assert events.count("device 0") == side and (not side or events[-1] == "device 0"), (name, events)
+            assert len(events) == 1 + (2 if name == "export_piece_device" else 1) + side, (name, events)
