@@ -310,6 +310,84 @@ def ecselect(ec_filename, out_filename, row_class=None, samples=None, samples_fi
         LOG.info("Saving completed")
 
 
+def downsample_rule(reads=None, fraction=None, equalize=False):
+    """What ``ecdownsample`` refuses before it opens a file: anything but exactly one of ``-n/--reads N`` (N >= 1), ``-f/--fraction P``
+    (0 < P <= 1) and ``--equalize``.  -> ``"reads"``, ``"fraction"`` or ``"equalize"``."""
+    given = [name for name, on in (("-n/--reads", reads is not None), ("-f/--fraction", fraction is not None), ("--equalize", bool(equalize))) if on]
+    if len(given) != 1:
+        raise ValueError("exactly one of -n/--reads, -f/--fraction and --equalize must be given ({})".format(" and ".join(given) if given else "none is"))
+    if reads is not None and int(reads) < 1:
+        raise ValueError("-n/--reads {}: the number of reads is at least 1".format(reads))
+    if fraction is not None and not 0.0 < float(fraction) <= 1.0:
+        raise ValueError("-f/--fraction {}: the fraction is above 0 and at most 1".format(fraction))
+    return "reads" if reads is not None else "fraction" if fraction is not None else "equalize"
+
+
+def downsample_targets(totals, stay, reads=None, fraction=None, equalize=False):
+    """``ecdownsample``'s target per column of the input: for a sample that stays ``reads``, ``floor(fraction * M_s)`` taken in float64, or
+    the smallest ``M_s`` among the samples that stay; -1 for every other column."""
+    rule = downsample_rule(reads, fraction, equalize)
+    totals, stay = np.asarray(totals, dtype=np.int64), np.asarray(stay, dtype=bool)
+    target = np.full(len(totals), -1, dtype=np.int64)
+    if not stay.any():
+        return target
+    if rule == "reads":
+        target[stay] = int(reads)
+    elif rule == "fraction":
+        target[stay] = np.floor(np.float64(fraction) * totals[stay].astype(np.float64)).astype(np.int64)
+    else:
+        target[stay] = totals[stay].min()
+    return target
+
+
+def ecdownsample(ec_filename, out_filename, reads=None, fraction=None, equalize=False, seed=0, samples=None, samples_file=None, mincount=None,
+                 stats_file=None, device=0):
+    """``alntools ecdownsample``: the samples of a ``.bin`` thinned to a read depth -- ``reads`` of every sample's reads, or the
+    ``fraction`` of them, or (``equalize``) as many as the shallowest sample has, drawn WITHOUT replacement on the GPU
+    (``ecb_downsample``: the rule is ``include/ecb_downsample.h``'s).  The steps, in this order: the totals ``M_s``; the samples that stay
+    are the named ones (``named_samples``; none named: all) with ``M_s >= max(mincount, 1)``; the target per column of the INPUT
+    (:func:`downsample_targets`); the draw on the input's N, so that a sample's result depends on its own column number and on no other
+    sample; ``ecb.select`` with every read class, the samples that stay and a threshold of 1 -- the zero entries go, then the rows
+    without a read, then the samples thinned to nothing.  Targets, lengths and haplotypes are copied.  ``stats_file``: a tab-separated
+    table ``sample, reads_in, reads_out, ecs_in, ecs_out`` under a header line, one line per sample that stays.  A result without a sample
+    or without a read is refused.  Any failure is logged as ``Error: ...``, no file is written and the exception is raised again (the
+    command line exits with status 1)."""
+    opened = []
+    with command(KEY, created=out_filename, written=opened):
+        downsample_rule(reads, fraction, equalize)
+        LOG.info("Loading {}...".format(ec_filename))
+        m = ecload(ec_filename)
+        named = named_samples(m, samples, samples_file)
+        ptr, data = np.asarray(m.indptrN, dtype=np.int64), np.asarray(m.dataN, dtype=np.int64)
+        cum = np.concatenate([[0], np.cumsum(data)])
+        totals = cum[ptr[1:]] - cum[ptr[:-1]]
+        stay = (totals >= max(int(mincount or 0), 1)) & (np.ones(m.num_samples, dtype=bool) if named is None else named)
+        target = downsample_targets(totals, stay, reads, fraction, equalize)
+        LOG.info("Downsampling {:,} of {:,} samples...".format(int(stay.sum()), m.num_samples))
+        from . import ecb, ecb_downsample
+        thin, reads_in, reads_out = ecb_downsample.downsample(m.indptrN, m.indicesN, m.dataN, m.num_reads, target, seed=seed, device=device)
+        A_N, kept = ecb.select(m.indptrA, m.indicesA, m.dataA, m.indptrN, m.indicesN, thin, m.num_loci, m.num_haplotypes,
+                               row_class=None, sample_keep=stay, min_count=1, device=device)
+        out = ECMatrices(m.hname, m.lname, m.lengths, [s for s, k in zip(m.sname, kept) if k], *A_N)
+        if out.num_samples == 0:
+            raise ValueError("no sample left")
+        if out.num_reads == 0:
+            raise ValueError("no read left")
+        if stats_file:
+            nz = lambda d: np.diff(np.concatenate([[0], np.cumsum(np.asarray(d) > 0)])[ptr])      # noqa: E731
+            ecs_in, ecs_out = nz(m.dataN), nz(thin)
+            opened.append(stats_file)
+            with open(stats_file, "w") as fh:
+                fh.write("sample\treads_in\treads_out\tecs_in\tecs_out\n")
+                for s in np.flatnonzero(stay):
+                    fh.write("{}\t{}\t{}\t{}\t{}\n".format(m.sname[s], int(reads_in[s]), int(reads_out[s]), int(ecs_in[s]), int(ecs_out[s])))
+        log_saving("Saving to {}...".format(out_filename), out, "Number of samples: {:,} (from {:,})".format(out.num_samples, m.num_samples),
+                   "Number of ECs: {:,} (from {:,} rows)".format(out.num_reads, m.num_reads),
+                   "Number of reads: {:,} (from {:,})".format(int(np.asarray(reads_out)[stay].sum()), int(totals.sum())), samples=None)
+        write_bin(out_filename, out)
+        LOG.info("Saving completed")
+
+
 def genotype_mask(m, gt_filename, gname, groups):
     """Genotype file -> ``mask u32[T]`` (bit h = haplotype h allowed at that locus) -- ``AlignmentPropertyMatrix.apply_genotypes``
     (``AlignmentPropertyMatrix.py:483-505``): the leading lines that start with ``#`` are skipped; every later line gives ``gene,

@@ -19,7 +19,7 @@ def inputs():
     import re
     csrc = os.path.dirname(SRC)
     local = set(re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(SRC).read(), re.M))
-    return [SRC] + [p for p in (os.path.normpath(os.path.join(csrc, n)) for n in sorted(local)) if os.path.dirname(p) == csrc] + [os.path.join(HERE, "..", "include", h) for h in ("ecb.h", "ecb_count.h", "ecb_bundle.h", "ecb_select.h", "ecb_quant.h", "ecb_quant_model.h", "ecb_quant_cells.h", "ecb_quant_cells_model.h", "ecb_quant_post.h", "ecb_quant_boot.h", "ecb_components.h", "ecb_bus.h", "ecb_bus_correct.h", "ecb_strata.h", "ecb_umi.h")]
+    return [SRC] + [p for p in (os.path.normpath(os.path.join(csrc, n)) for n in sorted(local)) if os.path.dirname(p) == csrc] + [os.path.join(HERE, "..", "include", h) for h in ("ecb.h", "ecb_count.h", "ecb_bundle.h", "ecb_select.h", "ecb_quant.h", "ecb_quant_model.h", "ecb_quant_cells.h", "ecb_quant_cells_model.h", "ecb_quant_post.h", "ecb_quant_boot.h", "ecb_components.h", "ecb_bus.h", "ecb_bus_correct.h", "ecb_strata.h", "ecb_umi.h", "ecb_downsample.h")]
 
 
 def needs_build():

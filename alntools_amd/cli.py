@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
 """Command line with the reference's hot-path sub-commands and options (``alntools/cli.py:43-113``):
-``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``, ``apply-genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``bus2ec`` (``-w``: the barcodes corrected against a whitelist first), ``buscorrect``, ``count-alignments``, ``ecquant`` (``-w``: the posterior of every alignment too), ``ecboot``, ``ecclusters``, ``ecquant-cells``, ``ecdump``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
+``bam2ec``, ``bam2emase``, ``ec2emase``, ``emase2ec``, ``apply-genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``ecdownsample``, ``salmon2ec``, ``bus2ec`` (``-w``: the barcodes corrected against a whitelist first), ``buscorrect``, ``count-alignments``, ``ecquant`` (``-w``: the posterior of every alignment too), ``ecboot``, ``ecclusters``, ``ecquant-cells``, ``ecdump``.  ``python -m alntools_amd.cli bam2ec in.bam out.bin``."""
 from __future__ import annotations
 
 import glob
@@ -218,6 +218,31 @@ def ecselect(ec_file, out_file, classes, samples, samples_file, mincount, verbos
         methods.ecselect(ec_file, out_file, classes[0] if classes else None, list(samples) or None, samples_file, mincount)
     except Exception:
         sys.exit(1)                                                  # (logged as "Error: ..." by bin_utils.ecselect)
+
+
+@cli.command('ecdownsample', options_metavar='<options>', short_help='thin the samples of an EC file to a read depth')
+@click.argument('ec_file', metavar='ec_file', type=click.Path(exists=True, resolve_path=True, dir_okay=False))
+@click.argument('out_file', metavar='out_file', type=click.Path(resolve_path=True, dir_okay=False, writable=True))
+@click.option('-n', '--reads', 'reads', metavar='N', default=None, type=int, help='keep N reads of every sample (a sample of fewer keeps all)')
+@click.option('-f', '--fraction', 'fraction', metavar='P', default=None, type=float, help="keep floor(P x reads) of every sample's reads (0 < P <= 1)")
+@click.option('--equalize', is_flag=True, help='keep as many reads of every sample as the shallowest one has')
+@click.option('--seed', metavar='S', default=0, type=int, help='seed of the draw (default: 0)')
+@click.option('-s', '--sample', 'samples', metavar='NAME', multiple=True, help="sample to keep, can specify multiple (default: all)")
+@click.option('--samples', 'samples_file', metavar='FILE', type=click.Path(exists=True, resolve_path=True, dir_okay=False),
+              help="file with the names of the samples to keep, one per line")
+@click.option('-m', '--mincount', default=None, type=int, help='drop the samples that count fewer reads than this before the draw')
+@click.option('--stats', 'stats_file', metavar='FILE', type=click.Path(resolve_path=True, dir_okay=False, writable=True),
+              help="write sample, reads_in, reads_out, ecs_in, ecs_out per sample that stays")
+@click.option('-v', '--verbose', count=True, help='enables verbose mode')
+def ecdownsample(ec_file, out_file, reads, fraction, equalize, seed, samples, samples_file, mincount, stats_file, verbose):
+    """
+    Thin the samples of a binary EC file (ec_file) to a read depth, drawn without replacement, and write the result (out_file)
+    """
+    utils.configure_logging(verbose)
+    try:
+        methods.ecdownsample(ec_file, out_file, reads, fraction, equalize, seed, list(samples) or None, samples_file, mincount, stats_file)
+    except Exception:
+        sys.exit(1)                                                  # (logged as "Error: ..." by bin_utils.ecdownsample)
 
 
 @cli.command('salmon2ec', options_metavar='<options>', short_help='convert a salmon eq_classes file to EC')

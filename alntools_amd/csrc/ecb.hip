@@ -6482,6 +6482,9 @@ extern "C" int ecb_salmon_ecs(int device, const char* text, uint64_t n_bytes, ui
 #include "strata.inc"
 // ... and the reads of one molecule made one read (ecb_collapse_umis / ecb_collapse_umis_device)
 #include "umi.inc"
+// ... and, for a .bin's N, n of a sample's reads kept, drawn without replacement (ecb_downsample / ecb_downsample_device)
+#include "ds_key.h"
+#include "downsample.inc"
 
 // ---- ecb_merge: the multi-GPU merge for ONE process that drives several GPUs ----------------------------------------------
 // shards[r] holds the reads of contiguous read shard r on its own device; `root` is an empty handle (any device).  The same protocol as

@@ -1,5 +1,5 @@
 # -*- coding: utf-8 -*-
-"""Same driver functions as the reference's ``alntools/methods.py:32-53, 205-210``, ``apply_genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``salmon2ec``, ``bus2ec``, ``buscorrect``, ``count_alignments``, ``ecquant``, ``ecboot``, ``ecclusters``, ``ecquant_cells`` and ``ecdump`` for the hot path."""
+"""Same driver functions as the reference's ``alntools/methods.py:32-53, 205-210``, ``apply_genotypes``, ``ecmerge``, ``ecbundle``, ``ecselect``, ``ecdownsample``, ``salmon2ec``, ``bus2ec``, ``buscorrect``, ``count_alignments``, ``ecquant``, ``ecboot``, ``ecclusters``, ``ecquant_cells`` and ``ecdump`` for the hot path."""
 from __future__ import annotations
 
 from . import bam_utils, bin_utils
@@ -57,6 +57,11 @@ def ecmerge(input_files, out_file):
 
 def ecbundle(ec_file, grp_file, out_file):
     bin_utils.ecbundle(ec_file, grp_file, out_file)
+
+
+def ecdownsample(ec_file, out_file, reads=None, fraction=None, equalize=False, seed=0, samples=None, samples_file=None, mincount=None, stats_file=None):
+    bin_utils.ecdownsample(ec_file, out_file, reads=reads, fraction=fraction, equalize=equalize, seed=seed, samples=samples,
+                           samples_file=samples_file, mincount=mincount, stats_file=stats_file)
 
 
 def ecselect(ec_file, out_file, row_class=None, samples=None, samples_file=None, mincount=None):

@@ -417,5 +417,7 @@ const char* ecb_profile_kernel(const ecb_handle* h);
 #        include "ecb_strata.h"
 /* ... and the ones that make the reads of one molecule one read, likewise before ecb_push* (--collapse-umis). */
 #         include "ecb_umi.h"
+/* ... and the ones that thin the samples of a .bin to a read depth, drawn without replacement (ecdownsample). */
+#          include "ecb_downsample.h"
 
 #endif /* ECB_H */
